@@ -3,11 +3,14 @@
     python bench.py [--gpus N --steps K --warmup W --batch 512 --precision bf16]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
     python bench.py --gpus N          (no launcher: bench.py starts the N ranks itself, one fresh process per GPU)
+    python bench.py --full            (+ roofline, side figures, golden parity, CPU baseline: runs of their own after the headline)
+    python bench.py --dump-outputs DIR  (+ what the last timed step computed, as DIR/<name>.npy)
 
 A step = zero_grad -> model('train', x, c, pr_mat, tfr=1, beta, weights) -> backward -> RCCL
 all-reduce (N>1) -> fused global-norm clip + Adam -> MinExponentialLR.step, on synthetic batches
 resident in HBM (BASELINE.json configs[1]: batch 512 per GPU, bf16 MFMA GRU/Linear products,
-z_dim 256+256, teacher-forced decoder).  Prints ONE JSON line (rank 0).
+z_dim 256+256, teacher-forced decoder).  Prints ONE JSON line (rank 0).  A plain run sets up, warms up,
+times the K steps and prints; the roofline, the side figures, golden parity and the CPU baseline need --full.
 """
 import argparse
 import json
@@ -328,7 +331,7 @@ PMC_FILE = 'profiles/r06_pmc_pick.json'
 
 def _roofline(lib, B, model, args, ms_per_step=None):
     """roofline of the step's dominant kernel FAMILY, measured live: HIP events on each launch's own stream (ptv_prof_*,
-    include/ptvae_hip_debug.h) over the timed region.  Candidates: the weight-gradient family (ptv_wgrad / ptv_wgrad_batch: product +
+    include/ptvae_hip_debug.h) over K steps of their own after the timed ones (--full).  Candidates: the weight-gradient family (ptv_wgrad / ptv_wgrad_batch: product +
     reduction launches; MFMA roofline), the notes GRU of the teacher-forced decoder as one row-partitioned launch per direction of time
     (csrc/notes_roles.hip; HBM roofline), the BPTT of the persistent small-M recurrences (MFMA).  The top-level record is the candidate
     with the most summed launch time per step (round-5 review: it used to be the notes forward whatever its share); the rest follow in
@@ -403,7 +406,7 @@ def _roofline(lib, B, model, args, ms_per_step=None):
                     'executed_mfma_tflop_per_step_pmc': k.get('executed_tflop_per_step'), 'mfma_busy_frac_pmc': k.get('mfma_busy_frac'),
                     'operand_bytes_note': 'products with M or N <= 135 are HBM-bound (3-4.4 TB/s standalone, profiles/r05_bench_wgrad.txt); the '
                                           'family figure is FLOP-weighted and dominated by the deep products',
-                    'note': 'event-timed per call (a batch = one product launch + one reduction launch) on its own stream inside the timed region, '
+                    'note': 'event-timed per call (a batch = one product launch + one reduction launch) on its own stream inside the event-timed steps, '
                             'in situ: the calls overlap each other and the latency chains, so the summed time exceeds their share of the step'})
     # ---- notes GRU (HBM roofline)
     kernels = [(3, 'notes_fwd_kernel', fwd_bytes, fwd_min)]
@@ -459,6 +462,38 @@ def _roofline(lib, B, model, args, ms_per_step=None):
     return roof
 
 
+# --dump-outputs: at most this many elements per array (16 MB of float32); a larger output is written as the elements at a fixed,
+# seeded set of positions, the same in every run of the same arguments, so that two builds can be compared output for output
+DUMP_MAX_ELEMS = 1 << 22
+
+
+def _dump_array(t, seed):
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.double().cpu().numpy() if flat.dtype == torch.float64 else flat.float().cpu().numpy()
+
+
+def dump_outputs(d, args, model, out):
+    """what a caller of the timed step holds after its last step -- train: the 11 losses, the updated parameters and their gradients
+    (all parameters flattened in named_parameters() order, 27.3 M at full geometry: a seeded sample); decode: the pitch and duration
+    logits and the decoded note grid"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    if args.mode == 'decode':
+        arrays = {'pitch_logits': out[1], 'dur_logits': out[2], 'notes': model.decoder.last_xhat}
+    else:
+        ps = [p for _, p in model.named_parameters()]
+        arrays = {'losses': torch.stack([l.detach().reshape(()) for l in out]),
+                  'params': torch.cat([p.detach().reshape(-1) for p in ps]),
+                  'grads': torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in ps])}
+    for name, t in arrays.items():                          # (params and grads: the same positions)
+        np.save(os.path.join(d, name + '.npy'), _dump_array(t, seed=0))
+    return sorted(arrays)
+
+
 def _launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh children of this script, one per GPU (RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in their environment, as `torch.distributed.run` would), BEFORE this process makes any GPU call -- it
@@ -498,9 +533,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=512, help='per-GPU batch (weak scaling)')
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true', help='skip the golden-vector parity block of the benched dtype')
-    ap.add_argument('--no-extras', action='store_true', help='skip the side figures (tfr=0 train, trainer surface, fp32, decode)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: the event-timed roofline steps, the side figures, golden parity and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a seeded sample of a large output)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-parity', action='store_true', help='--full: skip the golden-vector parity block of the benched dtype')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip the side figures (tfr=0 train, trainer surface, fp32, decode)')
     ap.add_argument('--graph', action='store_true', help='decode mode: replay the step loop from a captured hipGraph')
     ap.add_argument('--tfr', type=float, default=1.0, help='teacher-forcing ratio (1 = configs[1]; 0 = free-running training)')
     ap.add_argument('--mode', default='train', choices=['train', 'decode'],
@@ -575,8 +614,8 @@ def main():
             zc = torch.randn(B, 256, device=dev, generator=gen)
             zr = torch.randn(B, 256, device=dev, generator=gen)
             with torch.no_grad():
-                model.decoder(torch.cat([zc, zr], -1), True, None, None, 0., 0.)
-            return (model.decoder.last_xhat.sum().float(),)
+                pitch, dur = model.decoder(torch.cat([zc, zr], -1), True, None, None, 0., 0.)
+            return (model.decoder.last_xhat.sum().float(), pitch, dur)
         out = model('train', x, c, pr, tfr1=args.tfr, tfr2=args.tfr, tfr3=args.tfr, beta=0.1, weights=[1, 0.5])
         out[0].backward()
         if sync is not None:
@@ -601,11 +640,6 @@ def main():
     freeze_gc()                                            # a full collection (~100 ms: it walks the whole module tree) must not fall into
                                                            # the timed steps; what is alive now moves to the permanent generation
     barrier()
-    lib.ptv_prof_reset()
-    lib.ptv_prof_config(32 * B, model.decoder.dec_notes_hid_size)
-    # tags 3, 4: the row-partitioned notes GRU, forward and BPTT; 5: the weight-gradient family (~20 calls per step since the products are
-    # batched); 6: BPTT of the persistent recurrences -- all event-timed on their own streams INSIDE the timed region
-    lib.ptv_prof_enable(4 | 8 | 16 | 32)
     opt.throttle_wait_s = 0.0
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -614,8 +648,23 @@ def main():
     t_wait = getattr(opt, 'throttle_wait_s', 0.0)          # ... of which the optimiser spent this waiting for the GPU (two steps in flight at most)
     barrier()
     dt = time.perf_counter() - t0
-    lib.ptv_prof_enable(0)
     rep = sync.exchange_report() if world > 1 else None        # (the exchange figures of the TIMED steps: taken before the extra ones below)
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, args, model, out)
+        print('[bench] wrote %s to %s' % (', '.join(n + '.npy' for n in dumped), args.dump_outputs), file=sys.stderr, flush=True)
+    loss = float(out[0].item())
+    with_roofline = args.full and args.mode == 'train' and args.tfr >= 1.0
+    if with_roofline:
+        # --full: K more steps of the same workload with launch timing on, for the roofline record (every rank: the steps hold the
+        # gradient exchange).  Tags 3, 4: the row-partitioned notes GRU, forward and BPTT; 5: the weight-gradient family (~20 calls per
+        # step since the products are batched); 6: BPTT of the persistent recurrences -- all event-timed on their own streams
+        lib.ptv_prof_reset()
+        lib.ptv_prof_config(32 * B, model.decoder.dec_notes_hid_size)
+        lib.ptv_prof_enable(4 | 8 | 16 | 32)
+        for i in range(args.steps):
+            step(args.warmup + args.steps + i)
+        barrier()
+        lib.ptv_prof_enable(0)
     dp = None
     if world > 1:
         import torch.distributed as dist
@@ -635,13 +684,11 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    loss = float(out[0].item())
 
     if rank == 0:
-        import ctypes
         ms_per_step = dt / args.steps * 1e3
         value = world * B * args.steps / dt
-        roof = _roofline(lib, B, model, args, ms_per_step) if args.mode == 'train' and args.tfr >= 1.0 else None
+        roof = _roofline(lib, B, model, args, ms_per_step) if with_roofline else None
         if args.mode == 'decode':
             workload = 'configs[3]: free-running PtvaeDecoder sampling (inference_decode), batch=%d, 32x15x(1+5) step loop' % B
         elif args.tfr >= 1.0:
@@ -674,7 +721,7 @@ def main():
             res['data_parallel'] = dp
         from polyphonic_chord_texture_disentanglement_amd.functional import persist_check
         persist_check()                                        # a persistent launch that gave up would have invalidated the run
-        if world == 1 and args.mode == 'train' and not args.no_extras:
+        if args.full and world == 1 and args.mode == 'train' and not args.no_extras:
             unfreeze_gc()                                      # (the headline model may be collected again: the side figures build their own)
             del model, opt
             gc.collect()
@@ -683,7 +730,7 @@ def main():
                 res['extra'] = extras(dev, B, rank)
             except Exception as e:                             # side figures must never cost the headline line
                 res['extra'] = {'error': repr(e)}
-        if world == 1 and args.mode == 'train' and not args.no_parity:
+        if args.full and world == 1 and args.mode == 'train' and not args.no_parity:
             try:
                 res['parity'] = {'benched': golden_parity(args.precision, dev, via_loss=True), 'run_then_loss_function': golden_parity(args.precision, dev), 'fp32_path': golden_parity('fp32', dev) if args.precision != 'fp32' else None,
                                  'bar': 'north_star: losses within 1e-4 of the CPU reference -- held by the fp32 path (fp32_path / by_batch.*.fp32); the benched bf16 dtype '
@@ -694,7 +741,7 @@ def main():
                     for b_ in (4, 512)}
             except Exception as e:
                 res['parity'] = {'error': repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline()
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -1,10 +1,13 @@
 #!/bin/bash
 # round-6 evidence: bench (full line), kernel tables (headline, free-running, fp32), PMC passes
-python bench.py > gpurun_out/r06_bench.json 2> gpurun_out/r06_bench.err
-tail -c 300 gpurun_out/r06_bench.err
-python - <<'PY'
-import json
-r=json.load(open('gpurun_out/r06_bench.json'))
+# usage (GPU box): bash scripts/gpu_evidence.sh <dir>     -> <dir>/r06_bench.json (the --full line) and its stderr
+out=${1:?usage: bash scripts/gpu_evidence.sh <output dir>}
+mkdir -p "$out"
+python bench.py --full > "$out/r06_bench.json" 2> "$out/r06_bench.err"
+tail -c 300 "$out/r06_bench.err"
+python - "$out/r06_bench.json" <<'PY'
+import json, sys
+r=json.load(open(sys.argv[1]))
 print('VALUE', r['value'], r['ms_per_step'], 'host', r['host_enqueue_ms_per_step'])
 ro=r['roofline']; print('ROOF', ro['kernel'][:50], ro['achieved'], ro['frac'], ro['ms_per_step'], ro.get('launches_per_step'))
 for a in ro['also']: print('  also', a['kernel'][:50], a.get('achieved'), a.get('frac'), a.get('ms_per_step'))
