@@ -1753,7 +1753,7 @@ CHD_COMPOSITE = True
 _DTF = {}
 
 
-def _decoder_tf_composite(ctx, z, emb, xs, force_dur, prec, P, W, params, B, R, E, He, Ht, Hn, Hd, NP):
+def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, B, R, E, He, Ht, Hn, Hd, NP):
     """-> the node's outputs when ptv_decoder_tf_fwd ran (ctx then holds exactly what the launch-by-launch path leaves on it), else None"""
     if 't' not in _DTF:
         from ._lib import header_enum
@@ -1809,20 +1809,20 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, prec, P, W, params, B, R, 
             'NS': NS, 'NS16': NS16, 'Z_IN': z_in, 'TOKS': TOKS, 'GI_T': gi_t, 'ZG': zg, 'GATES_T': gates_t, 'HN': HN, 'HN16': HN16, 'GC': GC,
             'GATES_N': gates_n, 'PITCH': pitch, 'HD': HD, 'HD16': HD16, 'TAB0': tab0, 'TAB': tab, 'GATES_D': gates_d, 'DUR': dur, 'IDX': idx,
             'XCH': xch, 'SYNC': sync}
-    live = live_top_for(dev)
-    srt = _LIVE.get('sort') if live is not None else None
+    srt = live.sort if live is not None else None
     if srt is not None and not (force_dur is None and decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P)):
         srt = None                                            # (the backward composite is the only un-sorter: no sorted forward without it)
     if srt is not None:
         tens.update(PERM=srt['perm'], ROW_LEN=srt['len'], NS16S=_empty(R, Ht, dev=dev, dtype=BF16), TOK_S=_empty(15, R, E, dev=dev), SEG_N=srt.get('seg_n'))
-    if live is not None and POISON_DEAD_STEPS:
+    top = live.top if live is not None else None
+    if top is not None and POISON_DEAD_STEPS:
         _poison(HN16, gates_n, pitch, HD, HD16, gates_d, dur, idx)
         if srt is not None and srt.get('seg_n') is not None:
             _poison(tens['TOK_S'])                            # (gathered for the live blocks only: nobody may read the rest)
     slots = [None] * T_['PTV_DTF_COUNT']
     for k, v in tens.items():
         slots[T_['PTV_DTF_' + k]] = v.data_ptr() if v is not None else None
-    slots[T_['PTV_DTF_LIVE_TOP']] = live.data_ptr() if live is not None else None
+    slots[T_['PTV_DTF_LIVE_TOP']] = top.data_ptr() if top is not None else None
     # (the two event slots carry hipEvent_t handles, not tensors: events are created lazily -- record / wait once here to have a handle)
     if prev is not None:
         slots[T_['PTV_DTF_WAIT_EVENT']] = prev.cuda_event
@@ -1840,9 +1840,10 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, prec, P, W, params, B, R, 
     ctx.emb_link = _EMB_LINK.get(emb.data_ptr()) if (ctx.needs_input_grad[2] and ctx.needs_input_grad[1] and emb.is_contiguous()) else None
     ctx.st = dict(B=B, R=R, E=E, He=He, Ht=Ht, Hn=Hn, Hd=Hd, NP=NP, prec=prec, NS=NS, z_in=z_in, NS16=NS16, HN16=HN16, HD16=HD16,
                   TOKS=TOKS, gates_t=gates_t, HN=HN, gates_n=gates_n, gates_n_rowk=True, pitch=pitch, HD=HD, gates_d=gates_d, idx=idx,
-                  dur_tabs=(tab0, tab), dur16_only=True, live_top=live)
+                  dur_tabs=(tab0, tab), dur16_only=True, live_top=top)
+    if live is not None:
+        live.record_order(srt is not None)                    # (the loss node takes its targets in the same row order)
     if srt is not None:
-        srt['used'] = True                # (the loss node now takes the targets in the same row order: _cached_targets)
         ctx.st['sorted'] = dict(perm=srt['perm'], len=srt['len'], NS16S=tens['NS16S'], TOK_S=tens['TOK_S'], seg_n=srt.get('seg_n'))
         _DTF['sorted_calls'] = _DTF.get('sorted_calls', 0) + 1
     _DTF['calls'] = _DTF.get('calls', 0) + 1
@@ -1854,11 +1855,11 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, prec, P, W, params, B, R, 
 
 class DecoderTFFn(torch.autograd.Function):
     """(z [B,Zs], emb step-major [16,32,B,E], xs [32B, 2He] ground-truth note summaries (BiGruFinalFn over
-    emb, ptvae.py:446-453), force_dur_idx or None, *params)
+    emb, ptvae.py:446-453), force_dur_idx or None, live (loss()'s LiveRows plan) or None, prec, *params)
     -> pitch logits step-major [15,32,B,130], dur logits [15*32*B, 5, 2], dur argmax indices"""
 
     @staticmethod
-    def forward(ctx, z, emb, xs, force_dur, prec, *params):
+    def forward(ctx, z, emb, xs, force_dur, live, prec, *params):
         P = dict(zip(DEC_PARAM_NAMES, params))
         W = {n: _W(p, prec) for n, p in P.items()}            # bf16 shadows of the weights as MFMA operands
         dev = z.device
@@ -1874,7 +1875,7 @@ class DecoderTFFn(torch.autograd.Function):
         S = ctx                                                  # stash everything on ctx
 
         if DEC_COMPOSITE:
-            outs = _decoder_tf_composite(ctx, z, emb, xs, force_dur, prec, P, W, params, B, R, E, He, Ht, Hn, Hd, NP)
+            outs = _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, B, R, E, He, Ht, Hn, Hd, NP)
             if outs is not None:
                 return outs
 
@@ -1921,13 +1922,13 @@ class DecoderTFFn(torch.autograd.Function):
             # recomputed gates, and their backward halves): the generic heads / per-step duration GRU and their weight-gradient sums
             # read every row, so rows this launch leaves unwritten would meet zero gradients as NaN bit patterns (round-5 advice)
             chain_live = heads_ok(prec, Hn, NP, Hd, HN16, _act_dtype(prec, Hd) == BF16 or None) and prec == 1 and Hd == 64 and FUSED_DUR
-            live = live_top_for(dev) if chain_live else None
-            if live is not None and POISON_DEAD_STEPS:
+            top = live.top if (live is not None and chain_live) else None
+            if top is not None and POISON_DEAD_STEPS:
                 _poison(HN16, gates_n)
             call('ptv_notes_gru_persist_fwd_top', ptr(pk['wg_h']), ptr(pk['wg_t']), ptr(P['dec_notes_gru.bias_hh_l0']), ptr(GC), ptr(emb3),
-                 ptr(HN), ptr(HN16), ptr(gates_n), R, 15, ptr(live), stream_ptr())
+                 ptr(HN), ptr(HN16), ptr(gates_n), R, 15, ptr(top), stream_ptr())
         else:
-            live = None
+            top = None
             GT = gemm(emb3[:15].view(15 * R, E), w_ih_n[:, Ht:], prec=prec, out_dtype=adt)                    # [15R, 3Hn]
             gru_fwd(prec, GT, R * 3 * Hn, 3 * Hn, W['dec_notes_gru.weight_hh_l0'], P['dec_notes_gru.bias_hh_l0'], HN,
                     gates_n, gi2=GC, gi2_step=0, gi2_ld=3 * Hn, hall16=HN16)
@@ -1946,10 +1947,10 @@ class DecoderTFFn(torch.autograd.Function):
         if fused_heads:
             # ONE pass over the note summaries for both Linears; the logits feed the second product from LDS (csrc/heads.hip)
             hp = heads_packs(P['pitch_out_linear.weight'], P['dur_hid_linear.weight'])
-            if live is not None and POISON_DEAD_STEPS:
+            if top is not None and POISON_DEAD_STEPS:
                 _poison(pitch, HD, HD16)
             call('ptv_heads_fwd_top', ptr(NSUM_op), ptr(hp['wp']), ptr(hp['wdh']), ptr(hp['wdp']), ptr(P['pitch_out_linear.bias']),
-                 ptr(P['dur_hid_linear.bias']), ptr(pitch), pitch.stride(0), ptr(HD[0]), ptr(HD16[0]), M, ptr(live), R, stream_ptr())
+                 ptr(P['dur_hid_linear.bias']), ptr(pitch), pitch.stride(0), ptr(HD[0]), ptr(HD16[0]), M, ptr(top), R, stream_ptr())
         else:
             gemm(NSUM_op, W['pitch_out_linear.weight'], pitch, bias=P['pitch_out_linear.bias'], prec=prec)          # [M,130]
             w_dh = W['dur_hid_linear.weight']
@@ -1968,7 +1969,7 @@ class DecoderTFFn(torch.autograd.Function):
         dur2 = dur.view(M, 10)
         if fused_dur:
             # one kernel for the 5 steps + output layer + argmax feedback (dur.hip)
-            live_d = live                                   # (None unless the fused heads took the limit too: chain_live above)
+            live_d = top                                    # (None unless the fused heads took the limit too: chain_live above)
             if live_d is not None and POISON_DEAD_STEPS:
                 _poison(gates_d, dur, idx)
             call('ptv_dur_gru_fwd_top', Hd, M, ptr(HD[0]), Hd, ptr(P['dec_dur_gru.weight_hh_l0']), ptr(P['dec_dur_gru.bias_hh_l0']),
@@ -1993,8 +1994,10 @@ class DecoderTFFn(torch.autograd.Function):
         S.st = dict(B=B, R=R, E=E, He=He, Ht=Ht, Hn=Hn, Hd=Hd, NP=NP, prec=prec, NS=NS, z_in=z_in, NS16=NS16, HN16=HN16,
                     HD16=HD16,
                     TOKS=TOKS, gates_t=gates_t, HN=HN, gates_n=gates_n, gates_n_rowk=gates_n_rowk, pitch=pitch, HD=HD, gates_d=gates_d, idx=idx,
-                    dur_tabs=(tab0, tab), live_top=live,
+                    dur_tabs=(tab0, tab), live_top=top,
                     dur16_only=bool(prec == 1 and Hd == 64 and FUSED_DUR and HD16 is not None))   # HD[1:] never written
+        if live is not None:
+            live.record_order(False)
         S.mark_non_differentiable(idx)
         return pitch.view(15, 32, B, NP), dur, idx
 
@@ -2027,7 +2030,7 @@ class DecoderTFFn(torch.autograd.Function):
         if ctx.emb_link is not None and ctx.needs_input_grad[2] and demb.dtype == F32 and demb.is_contiguous():
             ctx.emb_link['demb'] = demb                   # the summary node accumulates into it and returns it (BiGruFinalFn.backward)
             demb_out = None
-        return (dz, demb_out, dTOKS[1:].view(R, 2 * He), None, None) + tuple(G[n] for n in DEC_PARAM_NAMES)
+        return (dz, demb_out, dTOKS[1:].view(R, 2 * He), None, None, None) + tuple(G[n] for n in DEC_PARAM_NAMES)
 
 
 # decoder_bwd_core's fused bf16 path through ptv_decoder_tf_bwd (one C call: ~50 launches, four forks, the persistent turn);
@@ -2642,15 +2645,14 @@ def _mem_order(ts, perms):
 WDUR = (1.0, 0.6, 0.4, 0.3, 0.3)          # ptvae.py:519-520
 
 
-def _pianotree_ce_fwd(pitch, dur, x, sums, st, weighted=False):
-    (pitch_m, dur_m), sm = _mem_order([pitch, dur], [_PERM[4], _PERM[5]])
-    dev = pitch.device
+def _pianotree_ce_fwd(pitch_m, dur_m, sm, x, sums, st, weighted=False, targets=None):
+    """targets: (pitch_t, dur_t, counts) in the logits' row order, or None = computed here  -> (pitch_t, dur_t, counts, gcnt)"""
+    dev = pitch_m.device
     B = x.shape[0]
     rows = B * 480
-    NP = pitch.shape[-1]
-    cached = _cached_targets(x, sm)                          # (DisentangleVAE.loss() computed them before the decoder ran)
-    if cached is not None:
-        pitch_t, dur_t, counts = cached
+    NP = pitch_m.shape[-1]
+    if targets is not None:
+        pitch_t, dur_t, counts = targets
     else:
         pitch_t = torch.empty(rows, device=dev, dtype=torch.int32)
         dur_t = torch.empty(rows * 5, device=dev, dtype=torch.int32)
@@ -2662,9 +2664,9 @@ def _pianotree_ce_fwd(pitch, dur, x, sums, st, weighted=False):
         gcnt = _izeros(5, dev)
         call('ptv_ce_group_fwd', ptr(dur_m), 2, ptr(dur_t), rows * 5, 2, 2, 5, ptr(gsum), ptr(gcnt), st)
         call('ptv_wdur_finalize', ptr(gsum), ptr(gcnt), *WDUR, ptr(sums[1:]), ptr(counts[1:]), st)
-        return pitch_m, dur_m, sm, pitch_t, dur_t, counts, gcnt
+        return pitch_t, dur_t, counts, gcnt
     call('ptv_ce_fwd', ptr(dur_m), 2, ptr(dur_t), rows * 5, 2, 2, ptr(sums[1:]), st)
-    return pitch_m, dur_m, sm, pitch_t, dur_t, counts, None
+    return pitch_t, dur_t, counts, None
 
 
 def _pianotree_ce_bwd(pitch_m, dur_m, sm, pitch_t, dur_t, gs, st, gcnt=None):
@@ -2691,28 +2693,48 @@ _LOSS_TOP = {}
 # The loss ignores the padded note slots (CrossEntropyLoss(ignore_index), ptvae.py:498-511): the decoder outputs of the note steps after
 # the last one that holds ANY target of the batch are dead values when the caller only wants the loss.  DisentangleVAE.loss() -- run +
 # loss_function in one call, nothing of run()'s outputs returned -- computes the targets before the decoder (they depend on x only) and
-# arms `live_top`; the teacher-forced decoder node then runs its notes GRU, heads and duration GRU for the live steps only (device-side
-# limit: no host sync) and the loss node reuses the targets.  run() itself always computes every step (its outputs ARE the result).
+# hands that LiveRows plan to both nodes; the teacher-forced decoder node then runs its notes GRU, heads and duration GRU for the live
+# steps only (device-side limit: no host sync) and the loss node takes the targets in the row order the decoder recorded.  run() itself
+# always computes every step (its outputs ARE the result).
 # The backward's zero-skip limit is the same number, so nothing reads the unwritten rows (tests poison them with NaN: POISON_DEAD_STEPS).
 DEAD_STEPS = os.environ.get('PTV_DEAD_STEPS', '1') != '0'
 POISON_DEAD_STEPS = False
+# diagnostic records of the last plan (bench.py's roofline figures); nothing in the package reads them
 _LIVE = {}
 
 
-def pianotree_targets(x, step_major):
-    """-> (pitch_t [480 B] int32, dur_t [2400 B] int32, counts int32 [3]: valid pitch / duration targets, last note step with any)"""
-    B = x.shape[0]
-    dev = x.device
-    pitch_t = torch.empty(B * 480, device=dev, dtype=torch.int32)
-    dur_t = torch.empty(B * 2400, device=dev, dtype=torch.int32)
-    counts = _izeros(3, dev)
-    call('ptv_pianotree_targets', ptr(x), B, int(step_major), ptr(pitch_t), ptr(dur_t), ptr(counts), stream_ptr())
-    return pitch_t, dur_t, counts
+class LiveRows:
+    """loss()'s plan for one forward: the targets of x (step-major), the last live note step `top` = counts[2:3] and, for length-sorted
+    rows, `sort` = dict(perm, len, pt, dt, seg_n).  The decoder node records the row order of its logits; the loss takes matching targets."""
+
+    def __init__(self, x, pitch_t, dur_t, counts, sort=None):
+        self.x, self.version = x, x._version
+        self.pitch_t, self.dur_t, self.counts = pitch_t, dur_t, counts
+        self.top = counts[2:3]
+        self.sort = sort
+        self.sorted = None
+
+    def record_order(self, sorted):
+        if self.sorted is not None or (sorted and self.sort is None):
+            raise RuntimeError('LiveRows: row order recorded twice, or sorted without a sort (one plan serves one forward)')
+        self.sorted = bool(sorted)
+
+    def targets(self, x, step_major):
+        """-> (pitch_t, dur_t, counts) in the row order of the decoder's logits; raises unless they are the logits of this plan's x"""
+        if self.sorted is None:
+            raise RuntimeError('LiveRows: no decoder recorded its row order')
+        if x.data_ptr() != self.x.data_ptr() or x.shape != self.x.shape or x._version != self.version:
+            raise RuntimeError('LiveRows: the loss is given another x than the plan was built for')
+        if not step_major:
+            raise RuntimeError('LiveRows: the logits are not step-major')
+        if self.sorted:
+            return self.sort['pt'], self.sort['dt'], self.counts
+        return self.pitch_t, self.dur_t, self.counts
 
 
-def arm_live_top(x):
-    """called by DisentangleVAE.loss() before run(): targets of x now (step-major: the teacher-forced decoder's layout), kept for the loss
-    node; the decoder node of THIS forward may stop at counts[2].  -> token for disarm_live_top"""
+def live_rows(x):
+    """called by DisentangleVAE.loss() before run(): -> the LiveRows plan of x (targets computed now, on the current stream), or None
+    where the decoder takes no dead-step limit"""
     # (B a multiple of 4: the heads kernel's 128-row blocks must not straddle the limit -- a note step holds 32 B rows)
     if not (DEAD_STEPS and ZERO_SKIP and x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.shape[0] % 4 == 0):
         return None
@@ -2724,12 +2746,11 @@ def arm_live_top(x):
     dur_t = torch.empty(B * 2400, device=x.device, dtype=torch.int32)
     counts = _izeros(3, x.device)
     call('ptv_pianotree_targets_rows', ptr(x), B, 1, ptr(pitch_t), ptr(dur_t), ptr(counts), ptr(row_live), stream_ptr())
-    pt, dt = pitch_t, dur_t
-    _LIVE.pop('sort', None)
+    srt = None
     if sort:
         # per-row dead work (round 6): the decoder's rows (t, b) in the order of DESCENDING number of live note steps.  Here: the
         # permutation, the lengths and the loss targets in that order; the decoder node takes them up if its composite runs
-        # (_decoder_tf_composite) and then marks them used -- the loss node picks the targets that match the logits it is given
+        # (_decoder_tf_composite) and records which order its logits are in
         perm = torch.empty(R, device=x.device, dtype=torch.int32)
         call('ptv_rows_by_length', ptr(row_live), ptr(perm), R, 15, stream_ptr())
         len_s = torch.empty(R, device=x.device, dtype=torch.int32)
@@ -2744,34 +2765,9 @@ def arm_live_top(x):
             call('ptv_rows_seg_counts', ptr(len_s), R, 15, ptr(seg_n), stream_ptr())
             global _LAST_SEG_N
             _LAST_SEG_N = seg_n                                  # (bench.py's roofline record: the live fraction of the segmented products)
-        _LIVE['sort'] = dict(perm=perm, len=len_s, pt=pt_s, dt=dt_s, used=False, x=x.data_ptr(), seg_n=seg_n)
-    _LIVE['x'] = (weakref.ref(x), x.data_ptr(), x._version, True, pt, dt, counts)
-    _LIVE['top'] = counts[2:3]
+        srt = dict(perm=perm, len=len_s, pt=pt_s, dt=dt_s, seg_n=seg_n)
     _LIVE['last_counts'] = counts                               # (bench.py's roofline record: how many note steps the launches ran)
-    return counts
-
-
-def disarm_live_top():
-    _LIVE.pop('top', None)
-
-
-def live_top_for(dev):
-    t = _LIVE.get('top')
-    return t if (t is not None and t.device == dev) else None
-
-
-def _cached_targets(x, sm):
-    ent = _LIVE.get('x')
-    if ent is None:
-        return None
-    ref, p, ver, sm0, pt, dt, counts = ent
-    if ref() is x and x.data_ptr() == p and x._version == ver and bool(sm) == sm0:
-        _LIVE.pop('x', None)
-        srt = _LIVE.pop('sort', None)
-        if srt is not None and srt['used'] and srt['x'] == p:      # the decoder node ran on length-sorted rows: its logits are in that order
-            return srt['pt'], srt['dt'], counts
-        return pt, dt, counts
-    return None
+    return LiveRows(x, pitch_t, dur_t, counts, srt)
 
 
 def _poison(*tensors):
@@ -2820,26 +2816,25 @@ def _vl_ok(*ts):
     return all(t.is_cuda and t.dtype == F32 and t.is_contiguous() for t in ts)
 
 
-def _vae_loss_fwd_composite(pitch, dur, x, c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, sm_c, root_t, chroma_t, bass_t, sums, out, scal, st):
-    """-> (pitch_m, dur_m, sm_p, pitch_t, dur_t, counts) when ptv_vae_loss_fwd ran, else None"""
+def _vae_loss_fwd_composite(pitch_m, dur_m, sm_p, x, c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, sm_c, root_t, chroma_t, bass_t,
+                            targets, sums, out, scal, st):
+    """-> (pitch_t, dur_t, counts) when ptv_vae_loss_fwd ran (targets None: it computed them), else None"""
     T_, D_ = _vl_tables()
-    (pitch_m, dur_m), sm_p = _mem_order([pitch, dur], [_PERM[4], _PERM[5]])
     B = x.shape[0]
-    NP = pitch.shape[-1]
+    NP = pitch_m.shape[-1]
     if (x.dtype != torch.int64 or not _vl_ok(c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m) or pitch_m.dtype != F32 or dur_m.dtype != F32
             or not dur_m.is_contiguous() or not _row_dense(pitch_m) or pitch_m.numel() != B * 480 * NP or dur_m.numel() != B * 4800):
         return None
-    dev = pitch.device
-    cached = _cached_targets(x, sm_p)
-    if cached is not None:
-        pitch_t, dur_t, counts = cached
+    dev = pitch_m.device
+    if targets is not None:
+        pitch_t, dur_t, counts = targets
     else:
         pitch_t = torch.empty(B * 480, device=dev, dtype=torch.int32)
         dur_t = torch.empty(B * 2400, device=dev, dtype=torch.int32)
         counts = _izeros(3, dev)
     dims = [0] * D_['PTV_VL_D_COUNT']
     for k, v in (('B', B), ('Z', mu_c.shape[1]), ('NP', NP), ('LDP', pitch_m.stride(-2)), ('SM_P', int(sm_p)), ('SM_C', int(sm_c)),
-                 ('HAVE_TARGETS', int(cached is not None))):
+                 ('HAVE_TARGETS', int(targets is not None))):
         dims[D_['PTV_VL_D_' + k]] = v
     slots = [None] * T_['PTV_VL_COUNT']
     for k, v in (('X', x), ('C', c), ('PITCH', pitch_m), ('DUR', dur_m), ('MU_C', mu_c), ('SD_C', sd_c), ('MU_R', mu_r), ('SD_R', sd_r),
@@ -2849,7 +2844,7 @@ def _vae_loss_fwd_composite(pitch, dur, x, c, mu_c, sd_c, mu_r, sd_r, root_m, ch
     rc = lib().ptv_vae_loss_fwd((ctypes.c_void_p * len(slots))(*slots), _larr(dims), (ctypes.c_double * 6)(*scal), st)
     check(rc, 'ptv_vae_loss_fwd')
     _VL['calls'] = _VL.get('calls', 0) + 1
-    return pitch_m, dur_m, sm_p, pitch_t, dur_t, counts
+    return pitch_t, dur_t, counts
 
 
 def _vae_loss_bwd_composite(gout, gs, pitch_m, dur_m, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, pitch_t, dur_t, counts, root_t, chroma_t,
@@ -2876,10 +2871,11 @@ def _vae_loss_bwd_composite(gout, gs, pitch_m, dur_m, mu_c, sd_c, mu_r, sd_r, ro
 
 class VaeLossFn(torch.autograd.Function):
     """(pitch [B,32,15,130], dur [B,32,15,5,2], mu_c, sd_c, mu_r, sd_r, root [B,8,12], chroma [B,8,12,2],
-    bass [B,8,12], x, c, beta, w0, w1) -> the 11 scalars of model.py:67-68 as one [11] tensor."""
+    bass [B,8,12], x, c, beta, w0, w1, weighted_dur, live (loss()'s LiveRows plan: the targets of x in the logits' row order) or None)
+    -> the 11 scalars of model.py:67-68 as one [11] tensor."""
 
     @staticmethod
-    def forward(ctx, pitch, dur, mu_c, sd_c, mu_r, sd_r, root, chroma, bass, x, c, beta, w0, w1, weighted_dur=False):
+    def forward(ctx, pitch, dur, mu_c, sd_c, mu_r, sd_r, root, chroma, bass, x, c, beta, w0, w1, weighted_dur=False, live=None):
         dev = pitch.device
         B = x.shape[0]
         st = stream_ptr()
@@ -2887,6 +2883,8 @@ class VaeLossFn(torch.autograd.Function):
         c = c.contiguous()
         mu_c, sd_c, mu_r, sd_r = (t.contiguous() for t in (mu_c, sd_c, mu_r, sd_r))
         sums = _zeros(8, dev=dev)
+        (pitch_m, dur_m), sm_p = _mem_order([pitch, dur], [_PERM[4], _PERM[5]])
+        targets = live.targets(x, sm_p) if live is not None else None
         (root_m, chroma_m, bass_m), sm_c = _mem_order([root, chroma, bass], [_chord_perm(root), _chord_perm(chroma),
                                                                               _chord_perm(bass)])
         root_t = torch.empty(B * 8, device=dev, dtype=torch.int32)
@@ -2907,13 +2905,13 @@ class VaeLossFn(torch.autograd.Function):
         ctx.scal = (float(beta), float(w0), float(w1), float(B * Z), float(B * 8), float(B * 96))
         comp = None
         if LOSS_COMPOSITE and not weighted_dur:
-            comp = _vae_loss_fwd_composite(pitch, dur, x, c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, sm_c, root_t, chroma_t, bass_t,
-                                           sums, out, ctx.scal, st)
+            comp = _vae_loss_fwd_composite(pitch_m, dur_m, sm_p, x, c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, sm_c, root_t, chroma_t,
+                                           bass_t, targets, sums, out, ctx.scal, st)
         if comp is not None:
-            pitch_m, dur_m, sm_p, pitch_t, dur_t, counts = comp
+            pitch_t, dur_t, counts = comp
             ctx.gcnt = None
         else:
-            pitch_m, dur_m, sm_p, pitch_t, dur_t, counts, gcnt = _pianotree_ce_fwd(pitch, dur, x, sums, st, weighted_dur)
+            pitch_t, dur_t, counts, gcnt = _pianotree_ce_fwd(pitch_m, dur_m, sm_p, x, sums, st, weighted_dur, targets)
             ctx.gcnt = gcnt
             small()                               # (on a sibling stream beside the PianoTree cross-entropy: 8.298 against 8.302 ms -- in line)
             call('ptv_loss_finalize', ptr(sums), ptr(counts), *ctx.scal, ptr(out), st)
@@ -2965,7 +2963,7 @@ class VaeLossFn(torch.autograd.Function):
         _LOSS_TOP.clear()
         if LOSS_TOP_HINT and sm_p:
             _LOSS_TOP['hint'] = (dpitch, ddur, dpitch._version, ddur._version, counts[2:3])
-        return (dpitch, ddur, dmu_c, dsd_c, dmu_r, dsd_r, droot, dchroma, dbass) + (None,) * 6
+        return (dpitch, ddur, dmu_c, dsd_c, dmu_r, dsd_r, droot, dchroma, dbass) + (None,) * 7
 
 
 class SplitScalarsFn(torch.autograd.Function):
@@ -2999,7 +2997,8 @@ class ReconLossFn(torch.autograd.Function):
         st = stream_ptr()
         x = x.contiguous()
         sums = _zeros(8, dev=dev)
-        pitch_m, dur_m, sm, pitch_t, dur_t, counts, gcnt = _pianotree_ce_fwd(pitch, dur, x, sums, st, weighted_dur)
+        (pitch_m, dur_m), sm = _mem_order([pitch, dur], [_PERM[4], _PERM[5]])
+        pitch_t, dur_t, counts, gcnt = _pianotree_ce_fwd(pitch_m, dur_m, sm, x, sums, st, weighted_dur)
         ctx.gcnt = gcnt
         out = _empty(11, dev=dev)
         ctx.scal = (0.0, float(w0), float(w1), 1.0, 1.0, 1.0)

@@ -91,7 +91,7 @@ class DisentangleVAE(PytorchModel):
         return torch.log(c + 1)
 
     # ---- model.py:42-55
-    def run(self, x, c, pr_mat, tfr1, tfr2, tfr3, confuse=True):
+    def run(self, x, c, pr_mat, tfr1, tfr2, tfr3, confuse=True, *, live=None):
         F_.mark('run:start')
         refresh_weight_shadows()                         # bf16 operand copies of the flat parameter buffer (if any)
         F_.mark('run:shadows')
@@ -125,16 +125,16 @@ class DisentangleVAE(PytorchModel):
         s_cd = F_.Side(CHD_DEC_SLOT)
         recon_root, recon_chroma, recon_bass = s_cd(
             lambda: self.chd_decoder(z_chd, False, tfr3, c, coins=chd_coins), z_chd, c)
-        pitch_outs, dur_outs = self.decoder(dec_z, False, embedded_x, lengths, tfr1, tfr2, coins=dec_coins)
+        pitch_outs, dur_outs = self.decoder(dec_z, False, embedded_x, lengths, tfr1, tfr2, coins=dec_coins, live=live)
         s_cd.join()
         return pitch_outs, dur_outs, dist_chd, dist_rhy, recon_root, recon_chroma, recon_bass
 
     # ---- model.py:57-68: one fused loss node (CE with ignore_index x2, KL x2, chord CE x3)
     def loss_function(self, x, c, recon_pitch, recon_dur, dist_chd, dist_rhy, recon_root, recon_chroma,
-                      recon_bass, beta, weights, weighted_dur=False):
+                      recon_bass, beta, weights, weighted_dur=False, *, live=None):
         out = F_.VaeLossFn.apply(recon_pitch, recon_dur, dist_chd.mean, dist_chd.scale, dist_rhy.mean,
                                  dist_rhy.scale, recon_root, recon_chroma, recon_bass, x.long(), c.float(),
-                                 float(beta), float(weights[0]), float(weights[1]), bool(weighted_dur))
+                                 float(beta), float(weights[0]), float(weights[1]), bool(weighted_dur), live)
         return F_.SplitScalarsFn.apply(out)
 
     # ---- model.py:70-90 (stand-alone forms; loss_function computes them fused)
@@ -167,14 +167,11 @@ class DisentangleVAE(PytorchModel):
                 raise TypeError("loss() got an unexpected keyword argument '%s'" % k)
             p[k] = v
         # run()'s outputs go nowhere but into the loss, which ignores the padded note slots: the teacher-forced decoder may leave the note
-        # steps after the batch's last target uncomputed (functional.arm_live_top; run() on its own always computes all of them)
-        armed = F_.arm_live_top(x) if (torch.is_grad_enabled() and p['tfr1'] >= 1. and p['tfr2'] >= 1.) else None
-        try:
-            outputs = self.run(x, c, pr_mat, p['tfr1'], p['tfr2'], p['tfr3'])
-        finally:
-            if armed is not None:
-                F_.disarm_live_top()
-        return self.loss_function(x, c, *outputs, p['beta'], p['weights'])
+        # steps after the batch's last target uncomputed.  Both nodes get the plan (functional.live_rows): the decoder records the row order
+        # of its logits, the loss takes the targets in that order (run() on its own gets no plan and always computes every step)
+        live = F_.live_rows(x) if (torch.is_grad_enabled() and p['tfr1'] >= 1. and p['tfr2'] >= 1.) else None
+        outputs = self.run(x, c, pr_mat, p['tfr1'], p['tfr2'], p['tfr3'], live=live)
+        return self.loss_function(x, c, *outputs, p['beta'], p['weights'], live=live)
 
     # ---- model.py:117-122
     def inference_encode(self, pr_mat, c):

@@ -323,7 +323,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
                 time.append(random.random() < tfr1)
         return notes, time
 
-    def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None):
+    def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None):
         _require_cuda(z, 'PtvaeDecoder')
         B = z.size(0)
         if inference:
@@ -364,15 +364,17 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             else:
                 pitch, dur, xhat, idx = FF_.DecoderStepFn.apply(z, emb, xs, coins, False, self.force_trace, self._prec,
                                                                 *self._params_free())
+            if live is not None:
+                live.record_order(False)                                       # (every step computed, rows in (t, b) order)
             self.last_dur_idx, self.last_xhat = idx, xhat
             return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
-        pitch, dur, idx = F_.DecoderTFFn.apply(z, emb, xs, self.force_dur_idx, self._prec, *self._params())
+        pitch, dur, idx = F_.DecoderTFFn.apply(z, emb, xs, self.force_dur_idx, live, self._prec, *self._params())
         self.last_dur_idx = idx
         # reference shapes [B,32,15,130] / [B,32,15,5,2] as permuted views of the step-major buffers
         return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
 
-    def forward(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None):
-        return self.decoder(z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=coins)
+    def forward(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None):
+        return self.decoder(z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=coins, live=live)
 
     # ---- the reference's helper METHODS (ptvae.py:292-428), callable by reference-side code.  Forward-only entry points onto the
     # kernels the fused path runs (`decoder()` never calls them: it runs DecoderTFFn / DecoderStepFn); results carry no autograd graph.

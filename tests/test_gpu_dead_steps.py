@@ -1,4 +1,4 @@
-"""DisentangleVAE.loss() lets the teacher-forced decoder stop at the last note step that holds a target (functional.arm_live_top): the loss
+"""DisentangleVAE.loss() lets the teacher-forced decoder stop at the last note step that holds a target (functional.live_rows): the loss
 ignores the padded note slots (ptvae.py:498-511), so the later steps' outputs are dead values there.  Checked three ways: (i) with the
 unwritten rows of every forward tensor POISONED with NaN, losses and every gradient are bit-identical to the dense path -- nothing reads
 them; (ii) the reference golden through loss(); (iii) run() on its own still computes every step."""
@@ -115,13 +115,17 @@ def test_a_chain_that_is_not_limit_aware_end_to_end_stays_dense(switch, monkeypa
         assert torch.equal(g0[k], g1[k]), k
 
 
-def test_live_steps_equal_the_last_target_and_run_stays_dense(monkeypatch):
+def test_loss_plan_hands_the_decoder_the_last_target_step_and_run_stays_dense(monkeypatch):
     B = 16
     x, c, pr = (torch.from_numpy(a).to(DEV) for a in synth_batch(B, 7))
     m = _model()
     seen = {}
-    orig = F_.live_top_for
-    monkeypatch.setattr(F_, 'live_top_for', lambda dev: seen.setdefault('t', orig(dev)))
+    orig = F_.DecoderTFFn.forward
+
+    def forward(ctx, z, emb, xs, force_dur, live, *rest):           # the limit the teacher-forced decoder node is handed
+        seen['t'] = live.top if live is not None else None
+        return orig(ctx, z, emb, xs, force_dur, live, *rest)
+    monkeypatch.setattr(F_.DecoderTFFn, 'forward', staticmethod(forward))
     m.use_philox(3, 0)
     outs = m.run(x, c, pr, 1., 1., 1.)
     assert seen['t'] is None                                      # run(): its outputs are the result -- every step computed
@@ -131,12 +135,31 @@ def test_live_steps_equal_the_last_target_and_run_stays_dense(monkeypatch):
     top = int(((x[..., 1:, 0] != 130) | (x[..., 1:, 1:] != 2).any(-1)).any(0).any(0).nonzero().max())
     assert seen['t'] is not None and int(seen['t'].item()) == top
     seen.clear()
-    with torch.no_grad():                                         # nothing armed without a backward pass to come
+    with torch.no_grad():                                         # no plan without a backward pass to come
         m.loss(x, c, pr, 1., 1., 1., 0.1, [1, 0.5])
     assert seen.get('t') is None
     seen.clear()
     m.loss(x, c, pr, 0., 0., 0., 0.1, [1, 0.5])                   # the free-running node takes no limit
     assert seen.get('t') is None
+
+
+def test_a_plan_for_another_x_fails_the_loss_instead_of_pairing_wrong_targets():
+    """the loss takes its targets from loss()'s plan only for the very x the plan was built for: handed another tensor, or the same one
+    modified in place, loss_function raises (natural-order targets beside length-sorted logits would be a silently wrong loss)"""
+    B = 16
+    x, c, pr = (torch.from_numpy(a).to(DEV) for a in synth_batch(B, 7))
+    m = _model()
+    m.use_philox(3, 0)
+    plan = F_.live_rows(x)
+    assert plan is not None
+    outs = m.run(x, c, pr, 1., 1., 1., live=plan)
+    assert plan.sorted is not None                                # the decoder node recorded the row order of its logits
+    with pytest.raises(RuntimeError, match='another x'):
+        m.loss_function(x.clone(), c, *outs, 0.1, [1, 0.5], live=plan)
+    x.add_(0)                                                     # same storage, version bumped
+    with pytest.raises(RuntimeError, match='another x'):
+        m.loss_function(x, c, *outs, 0.1, [1, 0.5], live=plan)
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize('B', [6, 3])

@@ -219,6 +219,42 @@ def test_loss_node_zero_skip_hint_matches_only_the_very_tensors():
     F_._LOSS_TOP.clear()
 
 
+def test_live_rows_plan_hands_out_the_targets_of_the_recorded_row_order_for_its_own_x_only():
+    """functional.LiveRows: loss()'s plan gives the loss node the targets in the row order the decoder node recorded -- and only for the
+    very x it was built for, unmodified, with step-major logits; anything else raises instead of pairing targets with the wrong rows"""
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_
+    x = torch.zeros(4, 32, 16, 6, dtype=torch.long)
+    pt, dt, counts = torch.arange(8, dtype=torch.int32), torch.arange(40, dtype=torch.int32), torch.tensor([5, 7, 3], dtype=torch.int32)
+    pt_s, dt_s = pt.flip(0), dt.flip(0)
+
+    def plan(sort=True):
+        return F_.LiveRows(x, pt, dt, counts, dict(perm=None, len=None, pt=pt_s, dt=dt_s, seg_n=None) if sort else None)
+    p = plan()
+    assert p.top.tolist() == [3]
+    with pytest.raises(RuntimeError):
+        p.targets(x, True)                                                   # no decoder recorded its row order yet
+    p.record_order(True)
+    got = p.targets(x.view(4, 32, 16, 6), True)                              # another wrapper of the same tensor: accepted
+    assert got[0] is pt_s and got[1] is dt_s and got[2] is counts
+    with pytest.raises(RuntimeError):
+        p.record_order(False)                                                # one plan, one forward
+    p = plan()
+    p.record_order(False)
+    got = p.targets(x, True)
+    assert got[0] is pt and got[1] is dt and got[2] is counts
+    with pytest.raises(RuntimeError):
+        p.targets(x.clone(), True)                                           # another tensor
+    with pytest.raises(RuntimeError):
+        p.targets(x[:2], True)                                               # same storage, other shape
+    with pytest.raises(RuntimeError):
+        p.targets(x, False)                                                  # batch-major logits
+    x.add_(0)
+    with pytest.raises(RuntimeError):
+        p.targets(x, True)                                                   # modified in place: version bumped
+    with pytest.raises(RuntimeError):
+        plan(sort=False).record_order(True)                                  # sorted logits need a row order
+
+
 def test_grad_arena_views_are_fresh_objects_over_the_bucket():
     """optim.GradArena.view: a new tensor object per call (autograd adopts a gradient only when nothing else references it) that aliases
     the parameter's 16-byte aligned range of the flat bucket with the parameter's shape"""
