@@ -73,6 +73,54 @@ def header_enum(name, path=None):
     return out
 
 
+class SlotTable(dict):
+    """The two tables of one composite entry point: SlotTable('DTF') is enum PtvDtfTensor / enum PtvDtfDim of include/ptvae_hip.h, their
+    slots named without the PTV_DTF_ / PTV_DTF_D_ prefix.  The header is read on first use, not at import.  The dict itself holds only
+    the call counters of the sites that use the table (count(); tests read them: "the composite really ran")."""
+
+    def __init__(self, tag):
+        super().__init__()
+        self.tag = tag
+        self._slots = None
+
+    def count(self, key='calls'):
+        self[key] = self.get(key, 0) + 1
+
+    def _index(self):
+        pre, names = 'PTV_%s_' % self.tag, ('Ptv%sTensor' % self.tag.capitalize(), 'Ptv%sDim' % self.tag.capitalize())
+        t, d = (header_enum(n) for n in names)
+        self._ptr_t, self._dim_t = ctypes.c_void_p * t.pop(pre + 'COUNT'), ctypes.c_long * d.pop(pre + 'D_COUNT')
+        self._dims = {k[len(pre) + 2:]: i for k, i in d.items()}
+        self._slots = {k[len(pre):]: i for k, i in t.items()}
+
+    def pointers(self, *tensors, handles=None):
+        """{slot: tensor or None}, ... and {slot: raw handle} (an event, a stream) -> the void* table; a slot nobody names stays NULL"""
+        if self._slots is None:
+            self._index()
+        idx, arr = self._slots, self._ptr_t()
+        try:
+            for m in tensors:
+                for k, v in m.items():
+                    arr[idx[k]] = ptr(v)
+            for k, v in (handles or {}).items():
+                arr[idx[k]] = v
+        except KeyError as e:
+            raise KeyError('PTV_%s_%s is not an enumerator of enum Ptv%sTensor' % (self.tag, e.args[0], self.tag.capitalize())) from None
+        return arr
+
+    def dims(self, values):
+        """{slot: int} -> the long table; a slot nobody names stays 0"""
+        if self._slots is None:
+            self._index()
+        idx, arr = self._dims, self._dim_t()
+        try:
+            for k, v in values.items():
+                arr[idx[k]] = int(v)
+        except KeyError as e:
+            raise KeyError('PTV_%s_D_%s is not an enumerator of enum Ptv%sDim' % (self.tag, e.args[0], self.tag.capitalize())) from None
+        return arr
+
+
 _SIGNATURES = _parse_header(HEADER_PATH)
 _SIGNATURES.update(_parse_header(DEBUG_HEADER_PATH))
 

@@ -16,7 +16,7 @@ import weakref
 import torch
 
 from . import _lib as _libmod
-from ._lib import call, check, lib, prec_code, ptr, stream_ptr
+from ._lib import SlotTable, call, check, lib, prec_code, ptr, stream_ptr
 
 
 # torch.cuda.current_stream() costs ~10 us of python (device-index resolution, lazy-init checks) and the step asks ~60 times
@@ -407,6 +407,25 @@ class _PersistTurn:
     def __exit__(self, *exc):
         _PERSIST_LAST[self.cur.device.index] = record_event(self.cur)
         return False
+
+
+class _CompositeTurn:
+    """the same turn for a composite entry point, which waits and records INSIDE the call: `handles` go into its pointer table, and
+    taken() -- only after the call returned 0 -- makes `done` the event the next persistent launch waits for"""
+
+    def __init__(self, cur):
+        self.dev = cur.device.index
+        self.prev = _PERSIST_LAST.get(self.dev)
+        self.done = torch.cuda.Event()
+        # (the slots carry hipEvent_t handles: events are created lazily, so record once here to have one -- the library records it
+        # again after the persistent launch)
+        self.done.record(cur)
+        self.handles = {'RECORD_EVENT': self.done.cuda_event}
+        if self.prev is not None:
+            self.handles['WAIT_EVENT'] = self.prev.cuda_event
+
+    def taken(self):
+        _PERSIST_LAST[self.dev] = self.done
 
 
 def _persist_sync(NC, dev):
@@ -994,35 +1013,30 @@ class EmbedFn(torch.autograd.Function):
 # =============================================================================================
 # bidirectional GRU, final states only  (RnnEncoder / TextureEncoder / dec_notes_emb_gru)
 # =============================================================================================
-_BGF = {}
-_BRF, _BRB = {}, {}
+_BGF, _BGB, _BRF, _BRB = SlotTable('BGF'), SlotTable('BGB'), SlotTable('BRF'), SlotTable('BRB')
+_BIGRU_G = tuple('G_%s%d' % (nm, d_) for d_ in range(2) for nm in ('W_IH', 'W_HH', 'B_IH', 'B_HH'))     # the slots of _gbuf(w[0..7])
+_FORK_EVENTS = {}           # (call site, device index, raw stream) -> the events that site's composite forks / joins with
 
 
-def _fork_events(cache, n=2):
-    """per (device, stream): the fork / join events a composite call needs, created once"""
+def _fork_events(site, n=2):
+    """per (call site, device, stream): the fork / join events a composite call needs, created once (a wait takes the record that
+    precedes it)"""
     cur = cur_stream()
-    key = ('ev', cur.device.index, stream_ptr())
-    evs = cache.get(key)
+    key = (site, cur.device.index, stream_ptr())
+    evs = _FORK_EVENTS.get(key)
     if evs is None:
         evs = [torch.cuda.Event() for _ in range(n)]
         for e in evs:
             e.record(cur)
-        cache[key] = evs
+        _FORK_EVENTS[key] = evs
     return evs
 
 
 def _bigru_rows_fwd_composite(x3, lengths, perm, w, out, side, T, M, I, H, dev, seg=None):
     """-> _bigru_forward's result when ptv_bigru_rows_fwd ran its row-kernel branch, else None"""
-    if 't' not in _BRF:
-        from ._lib import header_enum
-        _BRF['t'], _BRF['d'] = header_enum('PtvBrfTensor'), header_enum('PtvBrfDim')
-    T_, D_ = _BRF['t'], _BRF['d']
     if (not OVERLAP or side.s == side.main or torch.cuda.is_current_stream_capturing() or not x3.is_contiguous() or x3.dtype != F32
             or H != 128 or I != 128):
         return None
-    dims = [0] * D_['PTV_BRF_D_COUNT']
-    for k, v in (('M', M), ('T', T), ('H', H), ('I', I)):
-        dims[D_['PTV_BRF_D_' + k]] = v
     tens = {'X': x3, 'LENGTHS': lengths, 'PERM': perm, 'OUT': out}
     saved = []
     for d_ in range(2):
@@ -1033,26 +1047,18 @@ def _bigru_rows_fwd_composite(x3, lengths, perm, w, out, side, T, M, I, H, dev, 
         saved.append((hall, gates, h16, (lengths if ZERO_SKIP else None), perm, seg))
         tens.update({'PK_WG_H%d' % d_: pk['wg_h'], 'PK_WG_T%d' % d_: pk['wg_t'], 'B_HH%d' % d_: b_hh, 'B_IH%d' % d_: b_ih,
                      'HALL%d' % d_: hall, 'H16_%d' % d_: h16, 'GATES%d' % d_: gates})
-    slots = [None] * T_['PTV_BRF_COUNT']
-    for k, v in tens.items():
-        slots[T_['PTV_BRF_' + k]] = ptr(v)
-    evs = _fork_events(_BRF)
-    slots[T_['PTV_BRF_FORK_EVENT']], slots[T_['PTV_BRF_JOIN_EVENT']] = evs[0].cuda_event, evs[1].cuda_event
-    slots[T_['PTV_BRF_SIDE_STREAM']] = side.s.cuda_stream
-    rc = lib().ptv_bigru_rows_fwd((ctypes.c_void_p * len(slots))(*slots), _larr(dims), stream_ptr())
+    evs = _fork_events('BRF')
+    slots = _BRF.pointers(tens, handles={'FORK_EVENT': evs[0].cuda_event, 'JOIN_EVENT': evs[1].cuda_event, 'SIDE_STREAM': side.s.cuda_stream})
+    rc = lib().ptv_bigru_rows_fwd(slots, _BRF.dims({'M': M, 'T': T, 'H': H, 'I': I}), stream_ptr())
     if rc == -3:
         return None
     check(rc, 'ptv_bigru_rows_fwd')
-    _BRF['calls'] = _BRF.get('calls', 0) + 1
+    _BRF.count()
     return out, saved
 
 
 def _bigru_rows_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, side, T, M, I, H):
     """-> _bigru_backward's result when ptv_bigru_rows_bwd ran its row-kernel branch, else None"""
-    if 't' not in _BRB:
-        from ._lib import header_enum
-        _BRB['t'], _BRB['d'] = header_enum('PtvBrbTensor'), header_enum('PtvBrbDim')
-    T_, D_ = _BRB['t'], _BRB['d']
     dev = x3.device
     if (prec != 1 or not OVERLAP or side.s == side.main or torch.cuda.is_current_stream_capturing() or H != 128 or I != 128 or T * M < 512
             or xf.dtype != F32 or xf.stride(1) != 1 or xf.stride(0) != I or dout.dtype != F32 or dout.stride(1) != 1):
@@ -1064,9 +1070,6 @@ def _bigru_rows_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, sid
         return None
     lengths = saved[0][3] if len(saved[0]) > 3 else None
     perm = saved[0][4] if len(saved[0]) > 4 else None
-    dims = [0] * D_['PTV_BRB_D_COUNT']
-    for k, v in (('M', M), ('T', T), ('H', H), ('I', I), ('DX_ACC', int(dx_acc is not None)), ('DOUT_LD', dout.stride(0))):
-        dims[D_['PTV_BRB_D_' + k]] = v
     G = [_gbuf(p_) for p_ in w]
     dx = None
     if need_dx:
@@ -1080,38 +1083,27 @@ def _bigru_rows_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, sid
                      'DGI%d' % d_: _empty(T, M, 3 * H, dev=dev, dtype=BF16), 'DGH%d' % d_: _empty(T, M, 3 * H, dev=dev, dtype=BF16),
                      'SCRATCH%d' % d_: _empty(n_scr, dev=dev, dtype=BF16),
                      'TOP%d' % d_: _ineg1(dev) if (lengths is not None and M % 32 == 0) else None})
-    slots = [None] * T_['PTV_BRB_COUNT']
-    for k, v in tens.items():
-        slots[T_['PTV_BRB_' + k]] = ptr(v)
-    for d_ in range(2):
-        for j, nm in enumerate(('W_IH', 'W_HH', 'B_IH', 'B_HH')):
-            slots[T_['PTV_BRB_G_%s%d' % (nm, d_)]] = ptr(G[4 * d_ + j])
-    evs = _fork_events(_BRB)
-    slots[T_['PTV_BRB_FORK_EVENT']], slots[T_['PTV_BRB_JOIN_EVENT']] = evs[0].cuda_event, evs[1].cuda_event
-    slots[T_['PTV_BRB_SIDE_STREAM']] = side.s.cuda_stream
-    arr_, darr_, sp_ = (ctypes.c_void_p * len(slots))(*slots), _larr(dims), stream_ptr()
+    evs = _fork_events('BRB')
+    arr_ = _BRB.pointers(tens, dict(zip(_BIGRU_G, G)),
+                         handles={'FORK_EVENT': evs[0].cuda_event, 'JOIN_EVENT': evs[1].cuda_event, 'SIDE_STREAM': side.s.cuda_stream})
+    darr_ = _BRB.dims({'M': M, 'T': T, 'H': H, 'I': I, 'DX_ACC': dx_acc is not None, 'DOUT_LD': dout.stride(0)})
+    sp_ = stream_ptr()
     rc = _defer_or_run('rows_bwd', (arr_, darr_, (tens, G, saved, dout, xf)), lambda: lib().ptv_bigru_rows_bwd(arr_, darr_, sp_))
     _SIDE_DEPTH[1] = 1
     if rc == -3:                          # (H = I = 128 was checked above: ptv_bigru_rows_bwd's only refusal)
         raise RuntimeError('ptv_bigru_rows_bwd refused a configuration its Python-side checks accepted')
     check(rc, 'ptv_bigru_rows_bwd')
-    _BRB['calls'] = _BRB.get('calls', 0) + 1
+    _BRB.count()
     return G[0:4] + G[4:8], (dx.view(T, M, I) if need_dx else None)
 
 
 def _bigru_fwd_composite(prec, xf, lengths, w, w16, out, T, M, I, H, dev):
     """-> _bigru_forward's result when ptv_bigru_final_fwd ran its persistent branch, else None"""
-    if 't' not in _BGF:
-        from ._lib import header_enum
-        _BGF['t'], _BGF['d'] = header_enum('PtvBgfTensor'), header_enum('PtvBgfDim')
-    T_, D_ = _BGF['t'], _BGF['d']
     wih16 = [_W(w[0], prec), _W(w[4], prec)]
     if (torch.cuda.is_current_stream_capturing() or xf.dtype not in (F32, BF16) or xf.stride(1) != 1 or xf.stride(0) != I
             or wih16[0].dtype != wih16[1].dtype or not wih16[0].is_contiguous() or not wih16[1].is_contiguous()):
         return None
-    dims = [0] * D_['PTV_BGF_D_COUNT']
-    for k, v in (('M', M), ('T', T), ('H', H), ('I', I), ('X_BF16', _bf(xf)), ('WIH_F32', int(wih16[0].dtype == F32))):
-        dims[D_['PTV_BGF_D_' + k]] = v
+    dims = {'M': M, 'T': T, 'H': H, 'I': I, 'X_BF16': _bf(xf), 'WIH_F32': wih16[0].dtype == F32}
     saved = []
     tens = {'X': xf, 'LENGTHS': lengths, 'OUT': out, 'SYNC': _persist_sync(2, dev)}
     for d_ in range(2):
@@ -1121,23 +1113,15 @@ def _bigru_fwd_composite(prec, xf, lengths, w, w16, out, T, M, I, H, dev):
         tens.update({'W16_IH%d' % d_: wih16[d_], 'B_IH%d' % d_: w[4 * d_ + 2], 'W16_HH%d' % d_: w16[d_], 'B_HH%d' % d_: w[4 * d_ + 3],
                      'GI%d' % d_: _empty(T * M, 3 * H, dev=dev, dtype=BF16), 'HALL%d' % d_: hall, 'H16_%d' % d_: h16, 'GATES%d' % d_: gates,
                      'XCH%d' % d_: torch.empty((T + 1) * M * H, device=dev, dtype=BF16)})
-    slots = [None] * T_['PTV_BGF_COUNT']
-    for k, v in tens.items():
-        slots[T_['PTV_BGF_' + k]] = ptr(v)
-    cur = cur_stream()
-    prev = _PERSIST_LAST.get(cur.device.index)
-    done = torch.cuda.Event()
-    if prev is not None:
-        slots[T_['PTV_BGF_WAIT_EVENT']] = prev.cuda_event
-    done.record(cur)
-    slots[T_['PTV_BGF_RECORD_EVENT']] = done.cuda_event
+    turn = _CompositeTurn(cur_stream())
+    slots = _BGF.pointers(tens, handles=turn.handles)
     _chain_prio()
-    rc = lib().ptv_bigru_final_fwd((ctypes.c_void_p * len(slots))(*slots), _larr(dims), stream_ptr())
+    rc = lib().ptv_bigru_final_fwd(slots, _BGF.dims(dims), stream_ptr())
     if rc == -3:
         return None
     check(rc, 'ptv_bigru_final_fwd')
-    _PERSIST_LAST[cur.device.index] = done
-    _BGF['calls'] = _BGF.get('calls', 0) + 1
+    turn.taken()
+    _BGF.count()
     return out, saved
 
 
@@ -1233,15 +1217,10 @@ def _bigru_forward(prec, x3, lengths, w):
 
 
 BIGRU_BWD_COMPOSITE = os.environ.get('PTV_BWD_COMPOSITES', '1') != '0'    # the encoders' bi-GRU backward through ptv_bigru_final_bwd (one C call)
-_BGB = {}
 
 
 def _bigru_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, wts, side, T, M, I, H):
     """-> _bigru_backward's result when ptv_bigru_final_bwd ran its persistent branch, else None"""
-    if 't' not in _BGB:
-        from ._lib import header_enum
-        _BGB['t'], _BGB['d'] = header_enum('PtvBgbTensor'), header_enum('PtvBgbDim')
-    T_, D_ = _BGB['t'], _BGB['d']
     dev = x3.device
     if (T * M < 512 or not OVERLAP or side.s == side.main or torch.cuda.is_current_stream_capturing() or xf.stride(1) != 1
             or xf.stride(0) != I or xf.dtype not in (F32, BF16) or dout.dtype != F32 or dout.stride(1) != 1 or dout.stride(0) != 2 * H
@@ -1251,9 +1230,7 @@ def _bigru_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, wts, sid
     if need_dx and (wt_ih[0] is None or wt_ih[1] is None):
         return None
     S = persist_splitk(2, M, H)
-    dims = [0] * D_['PTV_BGB_D_COUNT']
-    for k, v in (('M', M), ('T', T), ('H', H), ('I', I), ('X_BF16', _bf(xf)), ('DX_ACC', int(dx_acc is not None)), ('SPLITK', S)):
-        dims[D_['PTV_BGB_D_' + k]] = v
+    dims = {'M': M, 'T': T, 'H': H, 'I': I, 'X_BF16': _bf(xf), 'DX_ACC': dx_acc is not None, 'SPLITK': S}
     G = [_gbuf(p_) for p_ in w]                           # (w_ih, w_hh, b_ih, b_hh) x 2 directions
     dx = None
     if need_dx:
@@ -1266,34 +1243,17 @@ def _bigru_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, wts, sid
                      'DGI%d' % d_: _empty(T, M, 3 * H, dev=dev, dtype=BF16), 'DGH%d' % d_: _empty(T, M, 3 * H, dev=dev, dtype=BF16),
                      'XCH%d' % d_: torch.empty(T * M * 3 * H, device=dev, dtype=BF16),
                      'PART%d' % d_: torch.empty(n_part, device=dev) if S else None})
-    slots = [None] * T_['PTV_BGB_COUNT']
-    for k, v in tens.items():
-        slots[T_['PTV_BGB_' + k]] = ptr(v)
-    for d_ in range(2):
-        for j, nm in enumerate(('W_IH', 'W_HH', 'B_IH', 'B_HH')):
-            slots[T_['PTV_BGB_G_%s%d' % (nm, d_)]] = ptr(G[4 * d_ + j])
-    cur = cur_stream()
-    evs = _BGB.get(('ev', cur.device.index, stream_ptr()))
-    if evs is None:                                   # fork / join events of this stream, created once
-        evs = [torch.cuda.Event(), torch.cuda.Event()]
-        for e in evs:
-            e.record(cur)
-        _BGB[('ev', cur.device.index, stream_ptr())] = evs
-    slots[T_['PTV_BGB_FORK_EVENT']], slots[T_['PTV_BGB_JOIN_EVENT']] = evs[0].cuda_event, evs[1].cuda_event
-    slots[T_['PTV_BGB_SIDE_STREAM']] = side.s.cuda_stream
-    prev = _PERSIST_LAST.get(cur.device.index)
-    done = torch.cuda.Event()
-    if prev is not None:
-        slots[T_['PTV_BGB_WAIT_EVENT']] = prev.cuda_event
-    done.record(cur)
-    slots[T_['PTV_BGB_RECORD_EVENT']] = done.cuda_event
-    rc = lib().ptv_bigru_final_bwd((ctypes.c_void_p * len(slots))(*slots), _larr(dims), stream_ptr())
+    evs = _fork_events('BGB')
+    turn = _CompositeTurn(cur_stream())
+    slots = _BGB.pointers(tens, dict(zip(_BIGRU_G, G)), handles={'FORK_EVENT': evs[0].cuda_event, 'JOIN_EVENT': evs[1].cuda_event,
+                                                                 'SIDE_STREAM': side.s.cuda_stream, **turn.handles})
+    rc = lib().ptv_bigru_final_bwd(slots, _BGB.dims(dims), stream_ptr())
     _SIDE_DEPTH[1] = 1
     if rc == -3:                          # (persist_supported() was asked before the arena views were taken)
         raise RuntimeError('ptv_bigru_final_bwd refused a configuration its Python-side checks accepted')
     check(rc, 'ptv_bigru_final_bwd')
-    _PERSIST_LAST[cur.device.index] = done
-    _BGB['calls'] = _BGB.get('calls', 0) + 1
+    turn.taken()
+    _BGB.count()
     # (the side stream was joined inside the call: what it read may be released in this stream's order)
     return G[0:4] + G[4:8], (dx.view(T, M, I) if need_dx else None)
 
@@ -1750,15 +1710,11 @@ DEC_COMPOSITE = True
 # chain: MEASURED SLOWER (9.0 vs 8.38 ms per step) -- the persistent time BPTT then starts earlier and runs beside more of the bulk
 # products, and a persistent grid with company loses more than the chain gained.  Off.
 CHD_COMPOSITE = True
-_DTF = {}
+_DTF, _CDF = SlotTable('DTF'), SlotTable('CDF')
 
 
 def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, B, R, E, He, Ht, Hn, Hd, NP):
     """-> the node's outputs when ptv_decoder_tf_fwd ran (ctx then holds exactly what the launch-by-launch path leaves on it), else None"""
-    if 't' not in _DTF:
-        from ._lib import header_enum
-        _DTF['t'], _DTF['d'] = header_enum('PtvDtfTensor'), header_enum('PtvDtfDim')
-    T_, D_ = _DTF['t'], _DTF['d']
     dev = z.device
     emb3 = emb.view(16, R, E)
     w16 = [W[n] for n in ('z2dec_hid_linear.weight', 'z2dec_in_linear.weight', 'dec_time_gru.weight_ih_l0', 'dec_time_gru.weight_hh_l0',
@@ -1770,10 +1726,7 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, 
             or z.dtype != F32 or not persist_supported(1, B, Ht, 32)):
         return None
     Zs, Zi = z.shape[1], W['z2dec_in_linear.weight'].shape[0]
-    dims = [0] * D_['PTV_DTF_D_COUNT']
-    for k, v in (('B', B), ('E', E), ('HE', He), ('HT', Ht), ('HN', Hn), ('HD', Hd), ('NP', NP), ('ZS', Zs), ('ZI', Zi), ('LDP', _pad8(NP))):
-        dims[D_['PTV_DTF_D_' + k]] = v
-    darr = _larr(dims)
+    darr = _DTF.dims({'B': B, 'E': E, 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'NP': NP, 'ZS': Zs, 'ZI': Zi, 'LDP': _pad8(NP)})
     if not lib().ptv_decoder_tf_supported(darr):
         return None
     M = 15 * R
@@ -1794,9 +1747,6 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, 
     sync = _persist_sync(1, dev)
     pk = notes_packs(P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0'], Ht)
     hp = heads_packs(P['pitch_out_linear.weight'], P['dur_hid_linear.weight'])
-    cur = cur_stream()
-    prev = _PERSIST_LAST.get(cur.device.index)
-    done = torch.cuda.Event()
     tens = {'Z': z, 'EMB': emb3, 'XS': xs, 'FORCE_DUR': force_dur,
             'B_ZHID': P['z2dec_hid_linear.bias'], 'B_ZIN': P['z2dec_in_linear.bias'], 'INIT_INPUT': P['dec_init_input'],
             'B_IH_T': P['dec_time_gru.bias_ih_l0'], 'B_HH_T': P['dec_time_gru.bias_hh_l0'], 'B_T2N': P['dec_time_to_notes_hid.bias'],
@@ -1808,33 +1758,26 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, 
             'PK_NOTES_H': pk['wg_h'], 'PK_NOTES_T': pk['wg_t'], 'PK_WP': hp['wp'], 'PK_WDH': hp['wdh'], 'PK_WDP': hp['wdp'],
             'NS': NS, 'NS16': NS16, 'Z_IN': z_in, 'TOKS': TOKS, 'GI_T': gi_t, 'ZG': zg, 'GATES_T': gates_t, 'HN': HN, 'HN16': HN16, 'GC': GC,
             'GATES_N': gates_n, 'PITCH': pitch, 'HD': HD, 'HD16': HD16, 'TAB0': tab0, 'TAB': tab, 'GATES_D': gates_d, 'DUR': dur, 'IDX': idx,
-            'XCH': xch, 'SYNC': sync}
+            'XCH': xch, 'SYNC': sync, 'LIVE_TOP': live.top if live is not None else None}
     srt = live.sort if live is not None else None
     if srt is not None and not (force_dur is None and decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P)):
         srt = None                                            # (the backward composite is the only un-sorter: no sorted forward without it)
     if srt is not None:
         tens.update(PERM=srt['perm'], ROW_LEN=srt['len'], NS16S=_empty(R, Ht, dev=dev, dtype=BF16), TOK_S=_empty(15, R, E, dev=dev), SEG_N=srt.get('seg_n'))
-    top = live.top if live is not None else None
+    top = tens['LIVE_TOP']
     if top is not None and POISON_DEAD_STEPS:
         _poison(HN16, gates_n, pitch, HD, HD16, gates_d, dur, idx)
         if srt is not None and srt.get('seg_n') is not None:
             _poison(tens['TOK_S'])                            # (gathered for the live blocks only: nobody may read the rest)
-    slots = [None] * T_['PTV_DTF_COUNT']
-    for k, v in tens.items():
-        slots[T_['PTV_DTF_' + k]] = v.data_ptr() if v is not None else None
-    slots[T_['PTV_DTF_LIVE_TOP']] = top.data_ptr() if top is not None else None
-    # (the two event slots carry hipEvent_t handles, not tensors: events are created lazily -- record / wait once here to have a handle)
-    if prev is not None:
-        slots[T_['PTV_DTF_WAIT_EVENT']] = prev.cuda_event
-    done.record(cur)                      # creates the handle; the library records it again after the persistent launch
-    slots[T_['PTV_DTF_RECORD_EVENT']] = done.cuda_event
+    turn = _CompositeTurn(cur_stream())
+    slots = _DTF.pointers(tens, handles=turn.handles)
     _chain_prio()
     mark('dec_fwd:start')
-    rc = lib().ptv_decoder_tf_fwd((ctypes.c_void_p * len(slots))(*slots), darr, stream_ptr())
+    rc = lib().ptv_decoder_tf_fwd(slots, darr, stream_ptr())
     if rc == -3:
         return None
     check(rc, 'ptv_decoder_tf_fwd')
-    _PERSIST_LAST[cur.device.index] = done
+    turn.taken()
     mark('dec_fwd:heads')
     ctx.save_for_backward(z, emb, *params)
     ctx.emb_link = _EMB_LINK.get(emb.data_ptr()) if (ctx.needs_input_grad[2] and ctx.needs_input_grad[1] and emb.is_contiguous()) else None
@@ -1845,8 +1788,8 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, 
         live.record_order(srt is not None)                    # (the loss node takes its targets in the same row order)
     if srt is not None:
         ctx.st['sorted'] = dict(perm=srt['perm'], len=srt['len'], NS16S=tens['NS16S'], TOK_S=tens['TOK_S'], seg_n=srt.get('seg_n'))
-        _DTF['sorted_calls'] = _DTF.get('sorted_calls', 0) + 1
-    _DTF['calls'] = _DTF.get('calls', 0) + 1
+        _DTF.count('sorted_calls')
+    _DTF.count()
     ctx.mark_non_differentiable(idx)
     # (returned, never stored on ctx: outputs referenced from their own grad_fn are a cycle that only the garbage collector frees -- at an
     # arbitrary later moment, e.g. inside a graph capture, where releasing blocks that other streams used records events and kills the capture)
@@ -2036,8 +1979,9 @@ class DecoderTFFn(torch.autograd.Function):
 # decoder_bwd_core's fused bf16 path through ptv_decoder_tf_bwd (one C call: ~50 launches, four forks, the persistent turn);
 # PTV_BWD_COMPOSITES=0: both backward composites off -- the same launches sequenced from Python (bit-identical)
 DEC_BWD_COMPOSITE = os.environ.get('PTV_BWD_COMPOSITES', '1') != '0'
-_DTB = {}
-_DTB_G = (('W_ZHID', 'z2dec_hid_linear.weight'), ('B_ZHID', 'z2dec_hid_linear.bias'), ('W_ZIN', 'z2dec_in_linear.weight'),
+_DTB = SlotTable('DTB')
+_DTB_G = tuple(('G_' + k, n) for k, n in (
+          ('W_ZHID', 'z2dec_hid_linear.weight'), ('B_ZHID', 'z2dec_hid_linear.bias'), ('W_ZIN', 'z2dec_in_linear.weight'),
           ('B_ZIN', 'z2dec_in_linear.bias'), ('INIT_INPUT', 'dec_init_input'), ('W_IH_T', 'dec_time_gru.weight_ih_l0'),
           ('W_HH_T', 'dec_time_gru.weight_hh_l0'), ('B_IH_T', 'dec_time_gru.bias_ih_l0'), ('B_HH_T', 'dec_time_gru.bias_hh_l0'),
           ('W_T2N', 'dec_time_to_notes_hid.weight'), ('B_T2N', 'dec_time_to_notes_hid.bias'), ('W_IH_N', 'dec_notes_gru.weight_ih_l0'),
@@ -2045,7 +1989,7 @@ _DTB_G = (('W_ZHID', 'z2dec_hid_linear.weight'), ('B_ZHID', 'z2dec_hid_linear.bi
           ('W_P', 'pitch_out_linear.weight'), ('B_P', 'pitch_out_linear.bias'), ('W_DH', 'dur_hid_linear.weight'),
           ('B_DH', 'dur_hid_linear.bias'), ('W_OUT_D', 'dur_out_linear.weight'), ('B_OUT_D', 'dur_out_linear.bias'),
           ('W_IH_D', 'dec_dur_gru.weight_ih_l0'), ('W_HH_D', 'dec_dur_gru.weight_hh_l0'), ('B_IH_D', 'dec_dur_gru.bias_ih_l0'),
-          ('B_HH_D', 'dec_dur_gru.bias_hh_l0'), ('SOS', 'dur_sos_token'))
+          ('B_HH_D', 'dec_dur_gru.bias_hh_l0'), ('SOS', 'dur_sos_token')))       # (gradient slot, parameter)
 
 
 def decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P=None):
@@ -2061,10 +2005,6 @@ def decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P=None):
 
 def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
     """-> decoder_bwd_core's result tuple when ptv_decoder_tf_bwd ran the whole sequence, else None (the caller sequences it: same bits)"""
-    if 't' not in _DTB:
-        from ._lib import header_enum
-        _DTB['t'], _DTB['d'] = header_enum('PtvDtbTensor'), header_enum('PtvDtbDim')
-    T_, D_ = _DTB['t'], _DTB['d']
     B, R, E, He, Ht, Hn, Hd, NP, prec = (st[k] for k in ('B', 'R', 'E', 'He', 'Ht', 'Hn', 'Hd', 'NP', 'prec'))
     dev = z.device
     M = 15 * R
@@ -2089,10 +2029,7 @@ def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
     S = persist_splitk(1, B, Ht)
     nblk = min(256, (M + 63) // 64)
     psz = lib().ptv_dur_gru_bwd_part_size()
-    dims = [0] * D_['PTV_DTB_D_COUNT']
-    for k, v in (('B', B), ('E', E), ('HE', He), ('HT', Ht), ('HN', Hn), ('HD', Hd), ('NP', NP), ('ZS', Zs), ('ZI', Zi), ('LDP', _pad8(NP)),
-                 ('NBLK', nblk), ('SPLITK', S)):
-        dims[D_['PTV_DTB_D_' + k]] = v
+    dims = {'B': B, 'E': E, 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'NP': NP, 'ZS': Zs, 'ZI': Zi, 'LDP': _pad8(NP), 'NBLK': nblk, 'SPLITK': S}
     hp = heads_packs(P['pitch_out_linear.weight'], P['dur_hid_linear.weight'])
     pk = notes_packs(P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0'], Ht)
     for _, n in _DTB_G:
@@ -2122,38 +2059,23 @@ def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
                     DTOK_S=_empty(15, R, E, dev=dev), SEG_N=srt.get('seg_n'))
     if POISON_DEAD_STEPS and top_h is not None and st.get('live_top') is not None:        # (tests: whatever reads a dead row of these gets NaN -- heads_bwd / the BPTT leave them unwritten)
         _poison(tens['DNSUM'], tens['DGI_N'], tens['DGH_N'], tens['DY16'])
-    slots = [None] * T_['PTV_DTB_COUNT']
-    for k, v in tens.items():
-        slots[T_['PTV_DTB_' + k]] = ptr(v)
-    for k, n in _DTB_G:
-        slots[T_['PTV_DTB_G_' + k]] = ptr(G[n])
-    cur = cur_stream()
-    evs = _DTB.get(('ev', cur.device.index))
-    if evs is None:                                   # the four fork events, created once (a wait takes the record that precedes it)
-        evs = [torch.cuda.Event() for _ in range(4)]
-        for e in evs:
-            e.record(cur)
-        _DTB[('ev', cur.device.index)] = evs
-    for i, e in enumerate(evs):
-        slots[T_['PTV_DTB_FORK_EVENT%d' % i]] = e.cuda_event
-    slots[T_['PTV_DTB_SIDE_STREAM']] = side.s.cuda_stream
-    prev = _PERSIST_LAST.get(cur.device.index)
-    done = torch.cuda.Event()
-    if prev is not None:
-        slots[T_['PTV_DTB_WAIT_EVENT']] = prev.cuda_event
-    done.record(cur)                      # creates the handle; the library records it again after the persistent launch
-    slots[T_['PTV_DTB_RECORD_EVENT']] = done.cuda_event
+    evs = _fork_events('DTB', 4)
+    turn = _CompositeTurn(cur_stream())
+    arr_ = _DTB.pointers(tens, {k: G[n] for k, n in _DTB_G},
+                         handles={'FORK_EVENT0': evs[0].cuda_event, 'FORK_EVENT1': evs[1].cuda_event, 'FORK_EVENT2': evs[2].cuda_event,
+                                  'FORK_EVENT3': evs[3].cuda_event, 'SIDE_STREAM': side.s.cuda_stream, **turn.handles})
     mark('dec_bwd:composite')
-    arr_, darr_, sp_ = (ctypes.c_void_p * len(slots))(*slots), _larr(dims), stream_ptr()
+    darr_, sp_ = _DTB.dims(dims), stream_ptr()
     # (payload: the tables AND everything they point to that nothing else keeps alive until a collected call runs -- the tensors, and the
-    # previous persistent launch's event, which _PERSIST_LAST drops below: a destroyed hipEvent_t in the table was a segfault)
-    rc = _defer_or_run('tf_bwd', (arr_, darr_, tens, prev, done, evs), lambda: lib().ptv_decoder_tf_bwd(arr_, darr_, sp_))
+    # previous persistent launch's event, which turn.taken() drops from _PERSIST_LAST below: a destroyed hipEvent_t in the table was a
+    # segfault)
+    rc = _defer_or_run('tf_bwd', (arr_, darr_, tens, turn.prev, turn.done, evs), lambda: lib().ptv_decoder_tf_bwd(arr_, darr_, sp_))
     _SIDE_DEPTH[1] = 1                    # (the library's priority state as the call leaves it)
     if rc == -3:                          # (the checks above mirror ptv_decoder_tf_bwd's: a late refusal would leave taken arena views behind)
         raise RuntimeError('ptv_decoder_tf_bwd refused a configuration its Python-side checks accepted')
     check(rc, 'ptv_decoder_tf_bwd')
-    _PERSIST_LAST[cur.device.index] = done
-    _DTB['calls'] = _DTB.get('calls', 0) + 1
+    turn.taken()
+    _DTB.count()
     st['ev_dtoks'] = None
     # the sibling stream's products are queued, not run: everything they read or write stays referenced until the join (the caller defers
     # it to the end of the backward pass) -- EXCEPT the gradient buffers (a second reference makes AccumulateGrad clone them)
@@ -2429,15 +2351,11 @@ CHD_PARAM_NAMES = ['init_input', 'z2dec_hid.weight', 'z2dec_hid.bias', 'z2dec_in
 
 
 CHD_BWD_COMPOSITE = os.environ.get('PTV_BWD_COMPOSITES', '1') != '0'     # ChordDecoderTFFn.backward through ptv_chord_decoder_bwd (one C call: 26 launches + the persistent launch's turn)
-_CDB = {}
+_CDB = SlotTable('CDB')
 
 
 def _chord_decoder_bwd_composite(P, st, z, droot, dchroma, dbass):
     """-> (dz, {name: gradient}) when ptv_chord_decoder_bwd ran, else None (the caller sequences the launches itself: same bits)"""
-    if 't' not in _CDB:
-        from ._lib import header_enum
-        _CDB['t'], _CDB['d'] = header_enum('PtvCdbTensor'), header_enum('PtvCdbDim')
-    T_, D_ = _CDB['t'], _CDB['d']
     prec, T, B, H, I = st['prec'], st['T'], st['B'], st['H'], st['I']
     dev = z.device
     hall, gates, toks, z_in = st['hall'], st['gates'], st['toks'], st['z_in']
@@ -2457,11 +2375,8 @@ def _chord_decoder_bwd_composite(P, st, z, droot, dchroma, dbass):
     persist = bool(adt == BF16 and wt is not None and T >= 2 and persist_supported(1, B, H, T))
     S = persist_splitk(1, B, H) if persist else 0
     Z, Zi = z.shape[1], z_in.shape[1]
-    dims = [0] * D_['PTV_CDB_D_COUNT']
-    for k, v in (('B', B), ('T', T), ('H', H), ('I', I), ('Z', Z), ('ZI', Zi), ('PREC', prec), ('ACT_BF16', int(adt == BF16)),
-                 ('NROOT', P['root_out.weight'].shape[0]), ('NCHROMA', P['chroma_out.weight'].shape[0]), ('NBASS', P['bass_out.weight'].shape[0]),
-                 ('PERSIST', int(persist)), ('SPLITK', S)):
-        dims[D_['PTV_CDB_D_' + k]] = v
+    dims = {'B': B, 'T': T, 'H': H, 'I': I, 'Z': Z, 'ZI': Zi, 'PREC': prec, 'ACT_BF16': adt == BF16, 'NROOT': P['root_out.weight'].shape[0],
+            'NCHROMA': P['chroma_out.weight'].shape[0], 'NBASS': P['bass_out.weight'].shape[0], 'PERSIST': persist, 'SPLITK': S}
     G = {n: _gbuf(P[n]) for n in CHD_PARAM_NAMES}
     dz = _empty(B, Z, dev=dev)
     tens = {'Z': z, 'W_ZHID': P['z2dec_hid.weight'], 'W_ZIN': P['z2dec_in.weight'], 'W_IH': P['gru.weight_ih_l0'], 'W_HH': w_hh,
@@ -2477,26 +2392,16 @@ def _chord_decoder_bwd_composite(P, st, z, droot, dchroma, dbass):
             'XCH': torch.empty(T * B * 3 * H, device=dev, dtype=BF16) if persist else None,
             'PART': torch.empty(lib().ptv_gru_persist_part_elems(1, B, H, S), device=dev) if S else None,
             'SYNC': _persist_sync(1, dev) if persist else None}
-    slots = [None] * T_['PTV_CDB_COUNT']
-    for k, v in tens.items():
-        slots[T_['PTV_CDB_' + k]] = ptr(v)
-    cur = cur_stream()
-    done = None
-    if persist:
-        prev = _PERSIST_LAST.get(cur.device.index)
-        done = torch.cuda.Event()
-        if prev is not None:
-            slots[T_['PTV_CDB_WAIT_EVENT']] = prev.cuda_event
-        done.record(cur)                  # creates the handle; the library records it again after the persistent launch
-        slots[T_['PTV_CDB_RECORD_EVENT']] = done.cuda_event
+    turn = _CompositeTurn(cur_stream()) if persist else None
+    slots = _CDB.pointers(tens, handles=turn.handles if turn else None)
     _chain_prio()
-    rc = lib().ptv_chord_decoder_bwd((ctypes.c_void_p * len(slots))(*slots), _larr(dims), stream_ptr())
+    rc = lib().ptv_chord_decoder_bwd(slots, _CDB.dims(dims), stream_ptr())
     if rc == -3:                          # (persist_supported() was asked before the arena views were taken)
         raise RuntimeError('ptv_chord_decoder_bwd refused a configuration its Python-side checks accepted')
     check(rc, 'ptv_chord_decoder_bwd')
-    if done is not None:
-        _PERSIST_LAST[cur.device.index] = done
-    _CDB['calls'] = _CDB.get('calls', 0) + 1
+    if turn:
+        turn.taken()
+    _CDB.count()
     # (the scratch tensors die here while the launches are only queued: the caching allocator reuses a block in stream order; the gradient
     # views must NOT be kept anywhere -- a second reference makes AccumulateGrad clone instead of adopt them)
     return dz, G
@@ -2516,10 +2421,6 @@ class ChordDecoderTFFn(torch.autograd.Function):
         I = c_sm.shape[2]
         if CHD_COMPOSITE and c_sm.is_contiguous() and c_sm.dtype == F32 and z.dtype == F32 and not capturing_part():
             # the whole forward behind ONE C call (ptv_chord_decoder_fwd, csrc/composite.hip)
-            if 'ct' not in _DTF:
-                from ._lib import header_enum
-                _DTF['ct'], _DTF['cd'] = header_enum('PtvCdfTensor'), header_enum('PtvCdfDim')
-            CT, CD = _DTF['ct'], _DTF['cd']
             Zi = P['z2dec_in.weight'].shape[0]
             adt = _act_dtype(prec, H)
             hall, z_in, toks = _empty(T + 1, B, H, dev=dev), _empty(B, Zi, dev=dev), _empty(T, B, I, dev=dev)
@@ -2533,16 +2434,12 @@ class ChordDecoderTFFn(torch.autograd.Function):
                     'W_CHROMA': P['chroma_out.weight'], 'B_CHROMA': P['chroma_out.bias'], 'W_BASS': P['bass_out.weight'],
                     'B_BASS': P['bass_out.bias'], 'HALL': hall, 'Z_IN': z_in, 'TOKS': toks, 'GI': gi, 'ZG': zg, 'GATES': gates, 'ROOT': root,
                     'CHROMA': chroma, 'BASS': bass}
-            slots = [None] * CT['PTV_CDF_COUNT']
-            for k, v in tens.items():
-                slots[CT['PTV_CDF_' + k]] = ptr(v)
-            dims = [0] * CD['PTV_CDF_D_COUNT']
-            for k, v in (('B', B), ('T', T), ('H', H), ('I', I), ('Z', z.shape[1]), ('ZI', Zi), ('PREC', prec), ('GATES_BF16', int(adt == BF16)),
-                         ('NROOT', nr), ('NCHROMA', nc), ('NBASS', nb)):
-                dims[CD['PTV_CDF_D_' + k]] = v
+            dims = {'B': B, 'T': T, 'H': H, 'I': I, 'Z': z.shape[1], 'ZI': Zi, 'PREC': prec, 'GATES_BF16': adt == BF16, 'NROOT': nr,
+                    'NCHROMA': nc, 'NBASS': nb}
+            slots = _CDF.pointers(tens)
             _chain_prio()
-            check(lib().ptv_chord_decoder_fwd((ctypes.c_void_p * len(slots))(*slots), _larr(dims), stream_ptr()), 'ptv_chord_decoder_fwd')
-            _DTF['chd_calls'] = _DTF.get('chd_calls', 0) + 1
+            check(lib().ptv_chord_decoder_fwd(slots, _CDF.dims(dims), stream_ptr()), 'ptv_chord_decoder_fwd')
+            _DTF.count('chd_calls')              # (counted beside the note decoder's forward)
             ctx.save_for_backward(z, *params)
             ctx.st = dict(hall=hall, gates=gates, toks=toks, z_in=z_in, prec=prec, T=T, B=B, H=H, I=I)
             return root.view(T, B, -1), chroma.view(T, B, -1), bass.view(T, B, -1)
@@ -2802,14 +2699,7 @@ LOSS_TOP_HINT = True
 
 
 LOSS_COMPOSITE = os.environ.get('PTV_BWD_COMPOSITES', '1') != '0'     # VaeLossFn through ptv_vae_loss_fwd / ptv_vae_loss_bwd (one C call each)
-_VL = {}
-
-
-def _vl_tables():
-    if 't' not in _VL:
-        from ._lib import header_enum
-        _VL['t'], _VL['d'] = header_enum('PtvVlTensor'), header_enum('PtvVlDim')
-    return _VL['t'], _VL['d']
+_VL = SlotTable('VL')
 
 
 def _vl_ok(*ts):
@@ -2819,7 +2709,6 @@ def _vl_ok(*ts):
 def _vae_loss_fwd_composite(pitch_m, dur_m, sm_p, x, c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, sm_c, root_t, chroma_t, bass_t,
                             targets, sums, out, scal, st):
     """-> (pitch_t, dur_t, counts) when ptv_vae_loss_fwd ran (targets None: it computed them), else None"""
-    T_, D_ = _vl_tables()
     B = x.shape[0]
     NP = pitch_m.shape[-1]
     if (x.dtype != torch.int64 or not _vl_ok(c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m) or pitch_m.dtype != F32 or dur_m.dtype != F32
@@ -2832,40 +2721,31 @@ def _vae_loss_fwd_composite(pitch_m, dur_m, sm_p, x, c, mu_c, sd_c, mu_r, sd_r, 
         pitch_t = torch.empty(B * 480, device=dev, dtype=torch.int32)
         dur_t = torch.empty(B * 2400, device=dev, dtype=torch.int32)
         counts = _izeros(3, dev)
-    dims = [0] * D_['PTV_VL_D_COUNT']
-    for k, v in (('B', B), ('Z', mu_c.shape[1]), ('NP', NP), ('LDP', pitch_m.stride(-2)), ('SM_P', int(sm_p)), ('SM_C', int(sm_c)),
-                 ('HAVE_TARGETS', int(targets is not None))):
-        dims[D_['PTV_VL_D_' + k]] = v
-    slots = [None] * T_['PTV_VL_COUNT']
-    for k, v in (('X', x), ('C', c), ('PITCH', pitch_m), ('DUR', dur_m), ('MU_C', mu_c), ('SD_C', sd_c), ('MU_R', mu_r), ('SD_R', sd_r),
-                 ('ROOT', root_m), ('CHROMA', chroma_m), ('BASS', bass_m), ('PITCH_T', pitch_t), ('DUR_T', dur_t), ('COUNTS', counts),
-                 ('ROOT_T', root_t), ('CHROMA_T', chroma_t), ('BASS_T', bass_t), ('SUMS', sums), ('OUT', out)):
-        slots[T_['PTV_VL_' + k]] = ptr(v)
-    rc = lib().ptv_vae_loss_fwd((ctypes.c_void_p * len(slots))(*slots), _larr(dims), (ctypes.c_double * 6)(*scal), st)
+    dims = _VL.dims({'B': B, 'Z': mu_c.shape[1], 'NP': NP, 'LDP': pitch_m.stride(-2), 'SM_P': sm_p, 'SM_C': sm_c,
+                     'HAVE_TARGETS': targets is not None})
+    slots = _VL.pointers({'X': x, 'C': c, 'PITCH': pitch_m, 'DUR': dur_m, 'MU_C': mu_c, 'SD_C': sd_c, 'MU_R': mu_r, 'SD_R': sd_r,
+                          'ROOT': root_m, 'CHROMA': chroma_m, 'BASS': bass_m, 'PITCH_T': pitch_t, 'DUR_T': dur_t, 'COUNTS': counts,
+                          'ROOT_T': root_t, 'CHROMA_T': chroma_t, 'BASS_T': bass_t, 'SUMS': sums, 'OUT': out})
+    rc = lib().ptv_vae_loss_fwd(slots, dims, (ctypes.c_double * 6)(*scal), st)
     check(rc, 'ptv_vae_loss_fwd')
-    _VL['calls'] = _VL.get('calls', 0) + 1
+    _VL.count()
     return pitch_t, dur_t, counts
 
 
 def _vae_loss_bwd_composite(gout, gs, pitch_m, dur_m, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, pitch_t, dur_t, counts, root_t, chroma_t,
                             bass_t, dpitch, ddur, dmu_c, dsd_c, dmu_r, dsd_r, droot, dchroma, dbass, scal, st):
-    T_, D_ = _vl_tables()
     B = root_t.numel() // 8
     NP = pitch_m.shape[-1]
     if gout.dtype != F32 or not _row_dense(pitch_m) or not dur_m.is_contiguous():
         return False
-    dims = [0] * D_['PTV_VL_D_COUNT']
-    for k, v in (('B', B), ('Z', mu_c.shape[1]), ('NP', NP), ('LDP', pitch_m.stride(-2))):
-        dims[D_['PTV_VL_D_' + k]] = v
-    slots = [None] * T_['PTV_VL_COUNT']
-    for k, v in (('PITCH', pitch_m), ('DUR', dur_m), ('MU_C', mu_c), ('SD_C', sd_c), ('MU_R', mu_r), ('SD_R', sd_r), ('ROOT', root_m),
-                 ('CHROMA', chroma_m), ('BASS', bass_m), ('PITCH_T', pitch_t), ('DUR_T', dur_t), ('COUNTS', counts), ('ROOT_T', root_t),
-                 ('CHROMA_T', chroma_t), ('BASS_T', bass_t), ('GOUT', gout), ('GS', gs), ('DPITCH', dpitch), ('DDUR', ddur), ('DMU_C', dmu_c),
-                 ('DSD_C', dsd_c), ('DMU_R', dmu_r), ('DSD_R', dsd_r), ('DROOT', droot), ('DCHROMA', dchroma), ('DBASS', dbass)):
-        slots[T_['PTV_VL_' + k]] = ptr(v)
-    rc = lib().ptv_vae_loss_bwd((ctypes.c_void_p * len(slots))(*slots), _larr(dims), (ctypes.c_double * 6)(*scal), st)
+    dims = _VL.dims({'B': B, 'Z': mu_c.shape[1], 'NP': NP, 'LDP': pitch_m.stride(-2)})
+    slots = _VL.pointers({'PITCH': pitch_m, 'DUR': dur_m, 'MU_C': mu_c, 'SD_C': sd_c, 'MU_R': mu_r, 'SD_R': sd_r, 'ROOT': root_m,
+                          'CHROMA': chroma_m, 'BASS': bass_m, 'PITCH_T': pitch_t, 'DUR_T': dur_t, 'COUNTS': counts, 'ROOT_T': root_t,
+                          'CHROMA_T': chroma_t, 'BASS_T': bass_t, 'GOUT': gout, 'GS': gs, 'DPITCH': dpitch, 'DDUR': ddur, 'DMU_C': dmu_c,
+                          'DSD_C': dsd_c, 'DMU_R': dmu_r, 'DSD_R': dsd_r, 'DROOT': droot, 'DCHROMA': dchroma, 'DBASS': dbass})
+    rc = lib().ptv_vae_loss_bwd(slots, dims, (ctypes.c_double * 6)(*scal), st)
     check(rc, 'ptv_vae_loss_bwd')
-    _VL['bwd_calls'] = _VL.get('bwd_calls', 0) + 1
+    _VL.count('bwd_calls')
     return True
 
 

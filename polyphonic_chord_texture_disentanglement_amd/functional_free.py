@@ -19,7 +19,7 @@ import weakref
 import torch
 
 from . import functional as F_
-from ._lib import call, lib, ptr, stream_ptr
+from ._lib import SlotTable, call, lib, ptr, stream_ptr
 from .functional import (DEC_PARAM_NAMES, Side, _bgrad, _bigru_backward, _empty, _eye2, _gbuf, _onehot2x5, _zeros,
                          colsum, copy2d, gemm, gru_bwd, sum_steps)
 
@@ -69,7 +69,9 @@ FREE_PERSIST = True
 # the persistent path of DecoderStepFn.forward behind ONE C call (ptv_decoder_free_fwd, csrc/composite.hip: ~170 launches -- prologue, the
 # 32-step loop, the batched recompute); PTV_FREE_COMPOSITE=0: the same launches sequenced from here (bit-identical)
 FREE_COMPOSITE = os.environ.get('PTV_FREE_COMPOSITE', '1') != '0'
-_DFF = {}
+_DFF, _DFB = SlotTable('DFF'), SlotTable('DFB')
+_DFF_KEEP = []              # what the last ptv_decoder_free_fwd call points to: its launches are queued, not run, when the call returns
+_DFB_FLUSHED = []           # (diagnostic) why the last DecoderStepFn.backward did not go through ptv_decoder_free_bwd as one call
 # training forward of the step loop: the panels store only decisions, logits and fed tokens; states and gates the backward needs are
 # recomputed afterwards for all 480*B rows at once by the teacher-forced kernels (same tokens, same decisions forced)
 FREE_REPLAY = True
@@ -169,10 +171,6 @@ def gru_step(prec, hprev, gi, gi_ld, w_hh, b_hh, hout, *, gi2=None, gates=None, 
 def _decoder_free_fwd_composite(P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of, ior, dims, tens, coins, w_hh_t, w_ih_t16, prec, dev, M, R):
     """DecoderStepFn.forward's persistent path through ptv_decoder_free_fwd (one C call); True when it ran"""
     import ctypes
-    if 't' not in _DFF:
-        from ._lib import header_enum
-        _DFF['t'], _DFF['d'] = header_enum('PtvDffTensor'), header_enum('PtvDffDim')
-    T_, D_ = _DFF['t'], _DFF['d']
     B, He, Ht, Hn, Hd, E = (dims[k] for k in ('B', 'He', 'Ht', 'Hn', 'Hd', 'E'))
     replay, need_resum = bool(dims['replay']), ior is not None
     w_ih_n, w_hh_n = P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0']
@@ -195,16 +193,10 @@ def _decoder_free_fwd_composite(P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of,
                 w_ih_e, w_hh_e, b_ih_e, b_hh_e = wE[4 * d_: 4 * d_ + 4]
                 pke = F_.notes_packs(w_ih_e, w_hh_e, 0)
                 t.update({'PK_E_H%d' % d_: pke['wg_h'], 'PK_E_T%d' % d_: pke['wg_t'], 'B_HH_E%d' % d_: b_hh_e, 'B_IH_E%d' % d_: b_ih_e})
-    slots = [None] * T_['PTV_DFF_COUNT']
-    for k, v in t.items():
-        if v is not None:
-            slots[T_['PTV_DFF_' + k]] = v.data_ptr()
-    dvals = [0] * D_['PTV_DFF_D_COUNT']
-    for k, v in (('B', B), ('ZS', dims['Zs']), ('ZI', dims['Zi']), ('HE', He), ('HT', Ht), ('HN', Hn), ('HD', Hd), ('E', E), ('NP', dims['NP']),
-                 ('LDP', dims['ldp']), ('TRAIN', dims['train']), ('REPLAY', dims['replay']), ('INFERENCE', dims['inference']),
-                 ('LOOP_FLAGS', dims['loop_flags']), ('CLUSTER', dims['cluster']), ('RESUM_TRAIN', dims['resum_train']), ('TOK0_LDS', tok0_lds),
-                 ('W_IH_T_BF16', int(w_ih_t16.dtype == torch.bfloat16)), ('W_HH_T_BF16', int(w_hh_t.dtype == torch.bfloat16))):
-        dvals[D_['PTV_DFF_D_' + k]] = int(v)
+    dvals = _DFF.dims({'B': B, 'ZS': dims['Zs'], 'ZI': dims['Zi'], 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'E': E, 'NP': dims['NP'],
+                       'LDP': dims['ldp'], 'TRAIN': dims['train'], 'REPLAY': dims['replay'], 'INFERENCE': dims['inference'],
+                       'LOOP_FLAGS': dims['loop_flags'], 'CLUSTER': dims['cluster'], 'RESUM_TRAIN': dims['resum_train'], 'TOK0_LDS': tok0_lds,
+                       'W_IH_T_BF16': w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': w_hh_t.dtype == torch.bfloat16})
     coin_notes, coin_time = coins
     masks = (ctypes.c_uint * 32)()
     tc = (ctypes.c_ubyte * 31)()
@@ -216,50 +208,34 @@ def _decoder_free_fwd_composite(P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of,
             masks[ts] = m_
         for ts in range(31):
             tc[ts] = int(bool(coin_time[ts]))
-    cur = F_.cur_stream()
-    done_ev = None
-    if dims['cluster']:                                     # the cluster-mode note loops take the persistent-launch turn (functional._PersistTurn)
-        prev = F_._PERSIST_LAST.get(cur.device.index)
-        done_ev = torch.cuda.Event()
-        if prev is not None:
-            slots[T_['PTV_DFF_WAIT_EVENT']] = prev.cuda_event
-        done_ev.record(cur)                                 # creates the handle; the library records it again after the last note loop
-        slots[T_['PTV_DFF_RECORD_EVENT']] = done_ev.cuda_event
+    # the cluster-mode note loops take the persistent-launch turn (functional._PersistTurn): the library records again after the last one
+    turn = F_._CompositeTurn(F_.cur_stream()) if dims['cluster'] else None
+    slots = _DFF.pointers(t, handles=turn.handles if turn else None)
     F_._chain_prio()
-    rc = lib().ptv_decoder_free_fwd((ctypes.c_void_p * len(slots))(*slots), F_._larr(dvals), wl, io_of(t['H0GC']), wr, ior, masks, tc, stream_ptr())
+    rc = lib().ptv_decoder_free_fwd(slots, dvals, wl, io_of(t['H0GC']), wr, ior, masks, tc, stream_ptr())
     if rc == -3:
         return False
     F_.check(rc, 'ptv_decoder_free_fwd')
-    if done_ev is not None:
-        F_._PERSIST_LAST[cur.device.index] = done_ev
-    _DFF['calls'] = _DFF.get('calls', 0) + 1
-    _DFF['keep'] = (t, masks, tc)                           # (the scratch tensors stay referenced until the next call: their launches are queued, not run)
+    if turn:
+        turn.taken()
+    _DFF.count()
+    _DFF_KEEP[:] = (t, masks, tc)                           # (the scratch tensors stay referenced until the next call)
     return True
 
 
 def _decoder_free_bwd_call(items, dTOK, dTOKS, demb, dPRED, dxs, dxsp, mask_tok, mask_time, dx_pred, xhat, mh, gw, gb, B, E, He):
     """the collected stages of DecoderStepFn.backward through ptv_decoder_free_bwd (one C call); True when it ran"""
-    import ctypes
-    if 'bt' not in _DFF:
-        from ._lib import header_enum
-        _DFF['bt'], _DFF['bd'] = header_enum('PtvDfbTensor'), header_enum('PtvDfbDim')
-    T_, D_ = _DFF['bt'], _DFF['bd']
     tf = [p for k, p, _ in items if k == 'tf_bwd'][0]
     rows = [p for k, p, _ in items if k == 'rows_bwd']
-    slots = [None] * T_['PTV_DFB_COUNT']
-    for k, v in (('DTOK', dTOK), ('DTOKS', dTOKS), ('DEMB', demb), ('DPRED', dPRED), ('DXS', dxs), ('DXSP', dxsp), ('MASK_TOK', mask_tok),
-                 ('MASK_TIME', mask_time), ('DX_PRED', dx_pred), ('XHAT', xhat), ('MH', mh), ('G_W_EMB', gw), ('G_B_EMB', gb)):
-        if v is not None:
-            slots[T_['PTV_DFB_' + k]] = v.data_ptr()
-    dvals = [0] * D_['PTV_DFB_D_COUNT']
-    dvals[D_['PTV_DFB_D_B']], dvals[D_['PTV_DFB_D_E']], dvals[D_['PTV_DFB_D_HE']] = B, E, He
     if dx_pred is not None and not dx_pred.is_contiguous():
         return False
+    slots = _DFB.pointers({'DTOK': dTOK, 'DTOKS': dTOKS, 'DEMB': demb, 'DPRED': dPRED, 'DXS': dxs, 'DXSP': dxsp, 'MASK_TOK': mask_tok,
+                           'MASK_TIME': mask_time, 'DX_PRED': dx_pred, 'XHAT': xhat, 'MH': mh, 'G_W_EMB': gw, 'G_B_EMB': gb})
     F_._chain_prio()
-    rc = lib().ptv_decoder_free_bwd(tf[0], tf[1], rows[0][0] if rows else None, rows[0][1] if rows else None,
-                                    (ctypes.c_void_p * len(slots))(*slots), F_._larr(dvals), stream_ptr())
+    rc = lib().ptv_decoder_free_bwd(tf[0], tf[1], rows[0][0] if rows else None, rows[0][1] if rows else None, slots,
+                                    _DFB.dims({'B': B, 'E': E, 'HE': He}), stream_ptr())
     F_.check(rc, 'ptv_decoder_free_bwd')
-    _DFF['bcalls'] = _DFF.get('bcalls', 0) + 1
+    _DFF.count('bcalls')                # (counted beside the forward's)
     return True
 
 
@@ -583,7 +559,7 @@ class DecoderStepFn(torch.autograd.Function):
             F_._defer_or_run('tail', None, tail)
             items = F_._DEFER
             if items is None and collect:
-                _DFF['bflush'] = 'a stage flushed'
+                _DFB_FLUSHED[:] = ['a stage flushed']
             if items is not None:
                 F_._DEFER = None
                 kinds = [k for k, _, _ in items]
@@ -592,7 +568,7 @@ class DecoderStepFn(torch.autograd.Function):
                                                             G['note_embedding.weight'], G['note_embedding.bias'], B, E, He):
                     pass
                 else:                                       # (not the whole pattern: the collected stages run as they are, in order)
-                    _DFF['bflush'] = kinds
+                    _DFB_FLUSHED[:] = kinds
                     F_._DEFER = items
                     F_._defer_flush()
         finally:

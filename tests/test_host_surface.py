@@ -270,3 +270,31 @@ def test_grad_arena_views_are_fresh_objects_over_the_bucket():
     assert a.take(ps[0]) is not None and a.take(ps[0]) is None               # handed out once per zero()
     a.zero()
     assert float(a.flat.abs().sum()) == 0 and a.take(ps[0]) is not None
+
+
+@pytest.mark.parametrize('tag', ['BRF', 'BRB', 'BGF', 'BGB', 'DTF', 'DTB', 'CDF', 'CDB', 'VL', 'DFF', 'DFB'])
+def test_slot_table_fills_the_tables_of_every_composite_enum_pair(tag):
+    """_lib.SlotTable(tag): both enums of include/ptvae_hip.h parsed, the arrays as long as their *_COUNT enumerators say, a value given under
+    a slot's short name at the index header_enum reports, every other slot NULL / 0, a name that is no enumerator a KeyError"""
+    import ctypes
+    from polyphonic_chord_texture_disentanglement_amd._lib import SlotTable, header_enum
+    name = 'Ptv%s' % tag.capitalize()
+    T, D = header_enum(name + 'Tensor'), header_enum(name + 'Dim')
+    n_t, n_d = T.pop('PTV_%s_COUNT' % tag), D.pop('PTV_%s_D_COUNT' % tag)
+    assert n_t == len(T) and n_d == len(D)
+    tab = SlotTable(tag)
+    tab.count(), tab.count(), tab.count('other')
+    assert tab == {'calls': 2, 'other': 1}                                   # (the dict holds the call counters, nothing else)
+    for full, i in T.items():
+        short = full[len('PTV_%s_' % tag):]
+        arr = tab.pointers({short: None}, handles={short: 0x1000 + i})       # (the handle is written after the tensors' None)
+        assert isinstance(arr, ctypes.c_void_p * n_t) and len(arr) == n_t
+        assert [arr[j] for j in range(n_t)] == [0x1000 + i if j == i else None for j in range(n_t)]
+    for full, i in D.items():
+        arr = tab.dims({full[len('PTV_%s_D_' % tag):]: 7 + i})
+        assert isinstance(arr, ctypes.c_long * n_d) and list(arr) == [7 + i if j == i else 0 for j in range(n_d)]
+    assert all(v is None for v in tab.pointers({}, {k[len('PTV_%s_' % tag):]: None for k in T})) and not any(tab.dims({}))
+    for bad in (lambda: tab.pointers({'NO_SUCH_SLOT': None}), lambda: tab.pointers(handles={'NO_SUCH_SLOT': 1}),
+                lambda: tab.pointers(handles={'COUNT': 1}), lambda: tab.dims({'NO_SUCH_SLOT': 1}), lambda: tab.dims({'COUNT': 1})):
+        with pytest.raises(KeyError, match=name):
+            bad()
