@@ -720,6 +720,32 @@ int ptv_batch_transform(const unsigned char* pr, const float* chord14, const int
 int ptv_slerp_path(const float* z1, const float* z2, float* out, int B, int D, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Output path on device: the inverse of the data contract above, from what the decoders emit to what the model consumes.
+ * ptv_grid_to_pr (PtvaeDecoder.grid_to_pr_and_notes, ptvae.py:558-575, for a whole batch; one workgroup per sample, csrc/output.hip):
+ *   grid [B,32,R,6] int64 contiguous, 16-byte aligned, R = 15 or 16; with R = 16 row 0 of every step is <sos> and is skipped (the
+ *   reference's grid[:, 1:]).  A step's rows are read in order up to the first row whose pitch is pitch_eos, at most max_notes
+ *   (1..R; the reference reads 10) and at most the 15 rows a step holds after <sos>.  pitch = row[0] + min_pitch,
+ *   dur = 1 + the MSB-first binary value of row[1..5].  Every output but err may be NULL (notes and count go together):
+ *   -> pr_mat  [B,32,128] f32    0, then pr[t, pitch] = min(dur, 32 - t); of two rows of a step with one pitch the later wins
+ *      notes   [B,32*max_notes,3] int32 (pitch, t, dur) with dur unclipped, time step major, row minor (both rows of a duplicate
+ *              pitch); count [B] int32 entries are valid, the rest is not written
+ *      x_clean [B,32,16,6] int64  the layout ptv_batch_transform writes: <sos>, the step's first 14 accepted notes in decoded order
+ *              as (pitch, 5 duration bits), <eos>, <pad> rows
+ *      err     [B] int32, written for every sample: bit 0 = a row before <eos> has a pitch outside 0..127 (the reference raises
+ *              IndexError), bit 1 = a duration bit is not 0 or 1 (ValueError); such a row is skipped (no cell, no note, no x_clean
+ *              row) and the sample goes on.  Bit 2 = the FIRST skipped row (time step major) had a bad duration bit, i.e. the
+ *              reference's exception for this sample is ValueError (it parses the duration before it indexes the pitch);
+ *              bit 3 = a step held 15 accepted notes, x_clean kept 14 (only with max_notes >= 15).
+ * ptv_chord_tokens (the token RnnDecoder.forward feeds back, ptvae.py:72-78, per row): logits in the chord decoder's step-major
+ *   layout root [T,B,12], chroma [T,B,24] (12 pairs), bass [T,B,12] -> c [B,T,36] f32 = root one-hot | 12 chroma bits | bass one-hot
+ *   (the layout chd_encoder and loss() take) and chord14 [B,T,14] f32 = root index | 12 chroma bits | bass index (the bank layout
+ *   ptv_batch_transform reads); either may be NULL.  Argmax ties resolve to the lowest index.
+ */
+int ptv_grid_to_pr(const long* grid, int B, int R, int max_notes, int min_pitch, int pitch_eos, float* pr_mat, int* notes, int* count,
+                   long* x_clean, int* err, void* stream);
+int ptv_chord_tokens(const float* root, const float* chroma, const float* bass, float* c, float* chord14, int T, int B, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Free-running / scheduled-sampling decoder as row-partitioned persistent kernels (csrc/freerun.hip): PtvaeDecoder.decode_notes
  * + decode_note (ptvae.py:336-428) for ONE time step t and ALL 15 note steps in one launch, a workgroup per panel of 16 samples
  * (state in LDS / registers, weights streamed from L2 in MFMA-fragment-major packing), and the re-summarisation of the

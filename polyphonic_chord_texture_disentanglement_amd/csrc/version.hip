@@ -13,7 +13,7 @@ extern "C" const char* ptv_arch(void) { return "gfx950"; }
 // 6 (round 6): the ptv_*_top entry points / PTV_DTF_LIVE_TOP (round 5, unversioned then), the bwd / loss / bigru composites, row limits in
 // ptv_wgrad's guarded tail and ptv_dur_out_wgrad, PTV_BGF_D_W_IH_F32; debug / profiling entry points moved to ptvae_hip_debug.h;
 // ptv_header_hash added (the loader compares it with the headers it binds from)
-extern "C" int ptv_abi_version(void) { return 6; }
+extern "C" int ptv_abi_version(void) { return 7; }
 #ifndef PTV_HEADER_HASH
 #define PTV_HEADER_HASH "unknown"
 #endif

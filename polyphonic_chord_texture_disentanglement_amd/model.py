@@ -193,6 +193,28 @@ class DisentangleVAE(PytorchModel):
             est_x = self.decoder.last_xhat[:, :, 1:, :].cpu().numpy()
         return est_x
 
+    # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
+    # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
+    def decode_to_inputs(self, z_chd, z_rhy, max_notes=10):
+        """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
+        [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
+        pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch."""
+        from .ptvae import _require_cuda
+        _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
+        _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')
+        self.eval()
+        refresh_weight_shadows()
+        with torch.no_grad():
+            self.decoder(torch.cat([z_chd, z_rhy], dim=-1), True, None, None, 0., 0.)
+            pr_mat, notes, count, x, err = self.decoder.grid_to_pr_and_notes_batch(self.decoder.last_xhat, max_notes)
+            c, _ = self.chd_decoder.decode_tokens(z_chd)
+        return pr_mat, x, c, notes, count, err
+
+    def reencode(self, z_chd, z_rhy):
+        """(dist_chd, dist_rhy) of the music decoded from (z_chd, z_rhy): decode_to_inputs, then inference_encode"""
+        pr_mat, _, c, _, _, _ = self.decode_to_inputs(z_chd, z_rhy)
+        return self.inference_encode(pr_mat, c)
+
     # ---- model.py:133-142
     def inference(self, pr_mat, c, sample):
         self.eval()

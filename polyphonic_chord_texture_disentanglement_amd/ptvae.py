@@ -207,6 +207,30 @@ class RnnDecoder(nn.Module, _PrecMixin):
         # reference shapes [B,8,12] / [B,8,12,2] / [B,8,12] as views of the step-major buffers
         return root.transpose(0, 1), chroma.view(T, bs, 12, 2).transpose(0, 1), bass.transpose(0, 1)
 
+    def decode_tokens(self, z_chd):
+        """Inference chord decode of z_chd [B, z_dim] -> (c [B,8,36], chord14 [B,8,14]) on the device: per step and sample the token
+        the reference feeds back (root one-hot | 12 chroma bits | bass one-hot, ptvae.py:72-78) and the same chord in the bank
+        layout batch_transform reads (root index | chroma bits | bass index).  No autograd graph."""
+        _require_cuda(z_chd, 'RnnDecoder.decode_tokens')
+        T = int(self.num_step / 4)
+        with torch.no_grad():
+            root, chroma, bass = self.forward(z_chd.detach(), True, 0.)
+            # forward() hands out reference-shaped views of its step-major buffers: undo them
+            return chord_tokens(root.transpose(0, 1), chroma.transpose(0, 1).reshape(T, z_chd.size(0), 24), bass.transpose(0, 1))
+
+
+def chord_tokens(root, chroma, bass):
+    """Chord-decoder logits in step-major layout (root [T,B,12], chroma [T,B,24] as 12 pairs, bass [T,B,12]) -> (c [B,T,36],
+    chord14 [B,T,14]) f32 (ptv_chord_tokens); argmax ties go to the lowest index.  No synchronisation."""
+    _require_cuda(root, 'chord_tokens')
+    root, chroma, bass = (a.detach().float().contiguous() for a in (root, chroma, bass))
+    T, B = root.shape[0], root.shape[1]
+    assert root.shape == (T, B, 12) and chroma.shape == (T, B, 24) and bass.shape == (T, B, 12), 'step-major [T,B,12|24|12] logits'
+    c = torch.empty(B, T, 36, device=root.device, dtype=torch.float32)
+    chord14 = torch.empty(B, T, 14, device=root.device, dtype=torch.float32)
+    F_.call('ptv_chord_tokens', F_.ptr(root), F_.ptr(chroma), F_.ptr(bass), F_.ptr(c), F_.ptr(chord14), T, B, F_.stream_ptr())
+    return c, chord14
+
 
 class PtvaeDecoder(nn.Module, _PrecMixin):
     """PianoTree decoder (ptvae.py:218-575): time GRU (32) -> notes GRU (15) -> pitch head +
@@ -490,6 +514,50 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
                 pr[t, pitch] = min(dur, 32 - t)
                 notes.append((pitch, start + t * alpha, start + (t + dur) * alpha))
         return pr, notes
+
+    # ---- the same transform for a whole batch on the device (ptv_grid_to_pr): nothing comes back to the host
+    def grid_to_pr_and_notes_batch(self, grid, max_notes=10, check=False):
+        """grid int64 [B,32,R,6], R = 15 or 16 (a 16-row step starts with <sos>, which is skipped) -> (pr_mat f32 [B,32,128],
+        notes int32 [B,32*max_notes,3] = (pitch, t, dur), count int32 [B], x_clean int64 [B,32,16,6], err int32 [B]), all on the
+        device.  pr_mat is the duration-at-onset layout the texture encoder takes, x_clean the canonical input grid of what was read
+        (emb_x / loss()); notes_to_tuples() turns notes / count into this class's (pitch, start, end) tuples.  A row the reference
+        would raise on is skipped and flagged in err (bit 0 pitch outside 0..127, bit 1 a duration bit that is not 0 or 1).
+        check=False neither synchronises nor reads back (graph-capturable); check=True synchronises and raises the reference's
+        IndexError / ValueError for the first flagged sample."""
+        _require_cuda(grid, 'PtvaeDecoder.grid_to_pr_and_notes_batch')
+        if grid.dim() != 4 or grid.shape[1] != 32 or grid.shape[2] not in (15, 16) or grid.shape[3] != 6:
+            raise ValueError('grid: [B,32,15|16,6] expected, got %s' % (tuple(grid.shape),))
+        B, R = grid.shape[0], grid.shape[2]
+        if not 1 <= int(max_notes) <= R:
+            raise ValueError('max_notes must be in 1..%d' % R)
+        g = grid.detach().long().contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        dev = g.device
+        pr_mat = torch.empty(B, 32, 128, device=dev, dtype=torch.float32)
+        notes = torch.empty(B, 32 * int(max_notes), 3, device=dev, dtype=torch.int32)
+        count = torch.empty(B, device=dev, dtype=torch.int32)
+        x_clean = torch.empty(B, 32, 16, 6, device=dev, dtype=torch.int64)
+        err = torch.empty(B, device=dev, dtype=torch.int32)
+        F_.call('ptv_grid_to_pr', F_.ptr(g), B, R, int(max_notes), int(self.min_pitch), int(self.pitch_eos), F_.ptr(pr_mat), F_.ptr(notes),
+                F_.ptr(count), F_.ptr(x_clean), F_.ptr(err), F_.stream_ptr())
+        if check:
+            e = err.cpu().numpy()
+            bad = (e & 3).nonzero()[0]                  # (bit 3 alone only says x_clean kept 14 of a step's 15 notes)
+            if len(bad):
+                b = int(bad[0])
+                if e[b] & 4:
+                    raise ValueError('sample %d: a duration bit before <eos> is not 0 or 1 (ptvae.py:570 raises here)' % b)
+                raise IndexError('sample %d: a pitch before <eos> is outside 0..127 (ptvae.py:571 raises here)' % b)
+        return pr_mat, notes, count, x_clean, err
+
+    @staticmethod
+    def notes_to_tuples(notes, count, bpm=60., start=0.):
+        """notes [B,N,3] / count [B] of grid_to_pr_and_notes_batch -> per sample the list of (pitch, start + t * alpha,
+        start + (t + dur) * alpha), alpha = 0.25 * 60 / bpm: the tuples grid_to_pr_and_notes returns.  Host helper (copies back)."""
+        notes, count = notes.cpu().tolist(), count.cpu().tolist()
+        alpha = 0.25 * 60 / bpm
+        return [[(p, start + t * alpha, start + (t + d) * alpha) for p, t, d in rows[:n]] for rows, n in zip(notes, count)]
 
 
 class PtvaeEncoder(nn.Module, _PrecMixin):
