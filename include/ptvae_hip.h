@@ -746,6 +746,37 @@ int ptv_grid_to_pr(const long* grid, int B, int R, int max_notes, int min_pitch,
 int ptv_chord_tokens(const float* root, const float* chroma, const float* bass, float* c, float* chord14, int T, int B, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Note-matrix song bank on device (csrc/dataset.hip): what ArrangementDataset.__getitem__ does BEFORE the data contract above, from
+ * the per-bar note matrices (dataset.py:67-93 over converter.py:35-76), and detrend_pianotree (dataset.py:123-213) after it.
+ * Bank: the bars of all songs in order.  acc_rec / mel_rec hold one 32-bit record per note, bar after bar, acc_off / mel_off [n_bar+1]
+ * int32 the first record of every bar (a bar whose track is None has none).  A record is
+ *     bits 0..7   pitch, 255 = anything above 254
+ *     bits 8..13  onset step when the bar is the FIRST bar of a window, int(sb*sde+sq) of converter.py:41; 63 = anything above 62
+ *     bits 14..19 end step in that place, int(eb*ede+eq), already clipped to 32
+ *     bits 20..25 / 26..31  the same two steps when the bar is the SECOND bar (the note translated by ts beats, dataset.py:58)
+ * all evaluated by the host builder in the reference's own arithmetic; negative values never enter a bank.
+ * chord_bars [n_bar,4,14] f32: the bars' raw chords [root, 12 chroma bits, bass].
+ * ptv_window_rolls, one workgroup per sample: the window of sample b is bars first_bar[b], first_bar[b]+1, shift[b] (NULL = 0) its
+ *   transposition.  Notes are applied first bar first, in record order.  Every output but err may be NULL; pr, prs, mel 16-byte aligned:
+ *   -> pr      [B,32,128] u8     ext_nmat_to_pr UNSHIFTED (what ptv_batch_transform reads): per note pr[s,p] = 2, then
+ *                                pr[s+1:min(e,32), p] = 1, later notes overwriting earlier ones
+ *      prs     [B,32,128,3] u8   onset / sustain / silence one-hots of that roll rolled by shift along the pitch axis (wraps)
+ *      mel     [B,1,32,130] f32  ext_nmat_to_mel_pr: column 129 is 1 except over [s,e), column 128 is 1 over [s+1,e), mel[s,p] = 1;
+ *                                then the 128 pitch columns rolled by shift
+ *      chord14 [B,8,14] f32      the two bars' chord rows
+ *      err     [B] int32, written for every sample: bit 0 = a note of the window has an onset step >= 32 or a pitch > 127 (the
+ *                                reference raises IndexError; the note is skipped, the sample goes on); bit 1 = first_bar[b] is not in
+ *                                0 .. n_bar-2 (the sample is an empty window with zero chords)
+ * ptv_detrend_pianotree, one workgroup per sample, one thread per row: x [B,32,16,6] int64 and c [B,8,36] f32 (what
+ *   ptv_batch_transform writes), x and dt_x 16-byte aligned -> dt_x [B,32,16,39] u8 = one-hots is_note 4 | is_bass 3 | octave 12 | degree 8 |
+ *   n_state 7, then the row's five duration columns as they are.  A pitch outside 0..143 sets none of the 34 class cells.
+ */
+int ptv_window_rolls(const unsigned* acc_rec, const int* acc_off, const unsigned* mel_rec, const int* mel_off, const float* chord_bars,
+                     int n_bar, const int* first_bar, const int* shift, int B, unsigned char* pr, unsigned char* prs, float* mel,
+                     float* chord14, int* err, void* stream);
+int ptv_detrend_pianotree(const long* x, const float* c, unsigned char* dt_x, int B, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Free-running / scheduled-sampling decoder as row-partitioned persistent kernels (csrc/freerun.hip): PtvaeDecoder.decode_notes
  * + decode_note (ptvae.py:336-428) for ONE time step t and ALL 15 note steps in one launch, a workgroup per panel of 16 samples
  * (state in LDS / registers, weights streamed from L2 in MFMA-fragment-major packing), and the re-summarisation of the

@@ -9,6 +9,7 @@ import torch
 
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import DataLoaders, TrainingInterface
+from .ptvae import _require_cuda
 from .synthetic import synth_batch
 
 SEED = 3345            # dataset.py:13
@@ -53,9 +54,33 @@ class DeviceBatcher:
     touching the host: one epoch enumerates every (item, shift) pair of ArrangementDataset (dataset.py:63-69: ids
     0 .. N*(shift_high-shift_low+1)-1, item = id // n_shift, shift = id % n_shift + shift_low) in a device-side
     permutation (the DataLoader's shuffle=True of dataset.py:279) and runs ptv_batch_transform per batch.  Yields the
-    reference's 6-tuple batch layout (mel_segments, prs, pr_mats, p_grids, chord, dt_x) with the unused slots empty."""
+    reference's 6-tuple batch layout (mel_segments, prs, pr_mats, p_grids, chord, dt_x) with the unused slots empty.
 
-    def __init__(self, pr, chord14, batch_size, shift_low=-6, shift_high=5, shuffle=True, seed=3345, drop_last=False, device=None):
+    `pr` may instead be a `dataset.ArrangementDataset` (chord14 = None): the windows then come from its note bank, and `slots` names
+    which of the otherwise empty slots ('mel', 'prs', 'dt_x') to fill.  The shifts and the device are the dataset's: shift_low /
+    shift_high / device other than their defaults or the dataset's own values raise ValueError."""
+
+    def __init__(self, pr, chord14, batch_size, shift_low=-6, shift_high=5, shuffle=True, seed=3345, drop_last=False, device=None,
+                 slots=()):
+        from .dataset import ArrangementDataset
+        self.dataset, self.slots = None, tuple(slots)
+        if isinstance(pr, ArrangementDataset):
+            assert chord14 is None, 'an ArrangementDataset carries its own chords'
+            if (shift_low, shift_high) not in ((-6, 5), (pr.shift_low, pr.shift_high)):
+                raise ValueError('shifts %d..%d asked, the dataset has %d..%d: build the dataset (or a subset()) with the shifts wanted'
+                                 % (shift_low, shift_high, pr.shift_low, pr.shift_high))
+            if device is not None and pr.device is not None and torch.device(device) != pr.device:
+                raise ValueError('device %s asked, the dataset lives on %s' % (device, pr.device))
+            if pr.device is None:
+                _require_cuda(torch.empty(0), 'DeviceBatcher')
+            self.dataset, self.pr = pr, None
+            self.batch_size, self.shift_low, self.n_shift = batch_size, pr.shift_low, pr.n_shift
+            self.shuffle, self.drop_last = shuffle, drop_last
+            self.gen = torch.Generator(device=pr.device).manual_seed(seed)
+            self.n = len(pr)
+            return
+        if self.slots:
+            raise ValueError('slots %s need the notes: pass an ArrangementDataset, a (pr, chord14) bank has none' % (self.slots,))
         dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         self.pr = torch.as_tensor(pr).to(dev, torch.uint8).contiguous()
         self.chord = torch.as_tensor(chord14).to(dev, torch.float32).contiguous()
@@ -68,11 +93,14 @@ class DeviceBatcher:
         return self.n // self.batch_size if self.drop_last else (self.n + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
-        dev = self.pr.device
+        dev = self.pr.device if self.dataset is None else self.dataset.device
         ids = torch.randperm(self.n, device=dev, generator=self.gen) if self.shuffle else torch.arange(self.n, device=dev)
         empty = torch.empty(0, device=dev)
         for i in range(len(self)):
             b = ids[i * self.batch_size:(i + 1) * self.batch_size]
+            if self.dataset is not None:
+                yield self.dataset.batch(b, self.slots)
+                continue
             index = torch.div(b, self.n_shift, rounding_mode='floor').int()
             shift = (b % self.n_shift + self.shift_low).int()
             pr_mat, x, c = batch_transform(self.pr, self.chord, shift, index)
@@ -85,7 +113,17 @@ class MusicDataLoaders(DataLoaders):
     def get_loaders(seed, bs_train, bs_val, portion=8, shift_low=-6, shift_high=5, num_bar=2, contain_chord=True,
                     random_train=True, random_val=False, n_train_batch=8, n_val_batch=2, device_bank=None):
         """device_bank = (pr uint8 [N,32,128], chord14 [N,8,14]) serves the reference's augmented epochs from HBM
-        (DeviceBatcher); otherwise the synthetic three-tensor generator."""
+        (DeviceBatcher); an ArrangementDataset (its last 1/(portion+1) windows validate, unshifted) or a (train, validation) pair
+        of them serves them from the note bank; otherwise the synthetic three-tensor generator."""
+        from .dataset import ArrangementDataset
+        if isinstance(device_bank, ArrangementDataset):
+            inds = device_bank.valid_inds
+            n_val = max(1, len(inds) // (portion + 1))
+            device_bank = (device_bank.subset(inds[:-n_val], shift_low, shift_high), device_bank.subset(inds[-n_val:], 0, 0))
+        if device_bank is not None and isinstance(device_bank[0], ArrangementDataset):
+            train = DeviceBatcher(device_bank[0], None, bs_train, shuffle=random_train, seed=seed)
+            val = DeviceBatcher(device_bank[1], None, bs_val, shuffle=random_val, seed=seed + 1)
+            return MusicDataLoaders(train, val, bs_train, bs_val)
         if device_bank is not None:
             pr, chord = device_bank
             n_val = max(1, pr.shape[0] // (portion + 1))                 # dataset.py:241-245,273-276: 1/(portion+1) validates, unshifted
