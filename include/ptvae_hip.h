@@ -195,8 +195,11 @@ int ptv_transpose01(float* dst, const float* src, int D0, int D1, int W, void* s
 /* out[i] = (accumulate ? out[i] : 0) + sum_t in[t*stride + i] */
 int ptv_sum_steps(float* out, const void* in, long n, int T, long stride, int accumulate, int in_bf16, void* stream);
 /* the same over the planes 0 .. *t_top only (device int; the later planes are known to be zero, see ptv_notes_gru_persist_bwd) */
-/* *top = max(*top, index of the last `unit`-row block of x [rows, cols] (fp32, row stride ld) that holds a non-zero): which trailing
- * note steps of a gradient received nothing (the loss ignores padded slots) -- the limit handed to ptv_gemm_mtop / ptv_wgrad */
+/* *top = max(*top, index of the `unit`-row block that holds the LAST ROW of the last 64-row chunk of x [rows, cols] (fp32, row stride ld)
+ * with a non-zero in it): which trailing note steps of a gradient received nothing (the loss ignores padded slots) -- the limit handed to
+ * ptv_gemm_mtop / ptv_wgrad.  The scan goes by 64-row chunks, so this is the block of the last non-zero row when unit is a multiple of
+ * 64 and an upper bound of it otherwise; -0.0 counts as zero, NaN as non-zero.  Rows whose padding columns cols .. ld - 1 are not zero
+ * may raise it further (whole chunks are read as one span when they are 16-byte aligned). */
 /* process-wide switch (default 1): the backward kernels pass over work whose result is exactly zero -- note steps / tiles at which no
  * gradient arrives (tested on the arriving gradient), panel steps beyond the longest packed sequence.  0 = run everything dense. */
 int ptv_zero_skip(int enable);
@@ -1032,9 +1035,9 @@ int ptv_gradnorm_clip_adam_step(float* p, const float* g, float* m, float* v, lo
  * reference's CPU path is run-to-run deterministic.  With the switch on, nothing on the train step ends in an fp32
  * atomicAdd whose order depends on arrival: the K slabs of ptv_wgrad and the K splits of ptv_gemm store partial tiles into a
  * per-stream workspace and one more launch adds them in slab order; the grid reductions (ptv_grad_sumsq, ptv_kl_fwd,
- * ptv_reparam_kl_fwd, ptv_ce_fwd, ptv_colsum, ptv_dur_out_wgrad, ptv_txt_conv_relu_pool_bwd) park one partial per block and the last
- * block to arrive adds them in block order.  Two runs of the same step then produce the same bits.  (Still atomic: the grouped
- * cross-entropy of the weighted duration loss, ptv_ce_group_fwd.)  ptv_wgrad_mode switches the two product paths only. */
+ * ptv_reparam_kl_fwd, ptv_ce_fwd, ptv_ce_group_fwd, ptv_colsum, ptv_dur_out_wgrad, ptv_txt_conv_relu_pool_bwd) park one partial per
+ * block and the last block to arrive adds them in block order.  Two runs of the same step then produce the same bits.
+ * ptv_wgrad_mode switches the two product paths only. */
 int ptv_ordered_reductions(int on);
 int ptv_wgrad_mode(int ordered);
 /* bf16 x bf16 weight-gradient products through the LDS-DMA kernel (global_load_lds staging, three stage buffers; default 0 = register-staged:

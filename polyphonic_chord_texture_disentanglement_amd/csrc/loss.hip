@@ -232,7 +232,7 @@ __global__ void ce_small_kernel(const float* __restrict__ logits, long ld, const
 template <bool BWD>
 __global__ void ce_group_kernel(const float* __restrict__ logits, long ld, const int* __restrict__ tgt, long rows, int C, int ignore, int G,
                                 float* __restrict__ nll_sum, int* __restrict__ cnt, const float* __restrict__ gscale,
-                                float* __restrict__ dlogits, long ldd) {
+                                float* __restrict__ dlogits, long ldd, OrdScratch sc) {
   float local[8]; int lc[8];
 #pragma unroll
   for (int g = 0; g < 8; g++) { local[g] = 0.f; lc[g] = 0; }
@@ -263,14 +263,30 @@ __global__ void ce_group_kernel(const float* __restrict__ logits, long ld, const
     }
   }
   if (!BWD) {
+    // one partial per block and group, added by the last block in a fixed tree (ordered_commit): 8192 fp32 atomicAdds of wave
+    // partials onto one word drifted by 3 ulp of a 7e5 sum, and by another amount every run.  The counts are integers: atomics.
+    __shared__ float red[8][4];
+    __shared__ int redc[8][4];
+    __shared__ float part[1];
 #pragma unroll
     for (int g = 0; g < 8; g++) {
       if (g < G) {
         const float t = wave_sum(local[g]);
         int c = lc[g];
         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if ((threadIdx.x & 63) == 0 && c != 0) { atomicAdd(nll_sum + g, t); atomicAdd(cnt + g, c); }
+        if ((threadIdx.x & 63) == 0) { red[g][threadIdx.x >> 6] = t; redc[g][threadIdx.x >> 6] = c; }
       }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < G) {
+      const int c = redc[threadIdx.x][0] + redc[threadIdx.x][1] + redc[threadIdx.x][2] + redc[threadIdx.x][3];
+      if (c != 0) atomicAdd(cnt + threadIdx.x, c);
+    }
+    for (int g = 0; g < G; g++) {
+      if (threadIdx.x == 0) part[0] = red[g][0] + red[g][1] + red[g][2] + red[g][3];
+      __syncthreads();
+      ordered_commit(nll_sum + g, part, 1, sc, g, blockIdx.x, gridDim.x);
+      __syncthreads();
     }
   }
 }
@@ -429,7 +445,7 @@ extern "C" int ptv_ce_group_fwd(const float* logits, long ld, const int* targets
                                 float* nll_sum, int* count, void* stream) {
   if (!logits || !targets || !nll_sum || !count || rows <= 0 || C <= 0 || C > 16 || G <= 0 || G > 8) return PTV_ERR_ARG;
   hipLaunchKernelGGL((ce_group_kernel<false>), dim3(grid_rows(rows, 256, 2048)), dim3(256), 0, (hipStream_t)stream, logits, ld, targets, rows, C,
-                     ignore_index, G, nll_sum, count, nullptr, nullptr, 0L);
+                     ignore_index, G, nll_sum, count, nullptr, nullptr, 0L, ord_scratch((hipStream_t)stream, 2048L * G, G));
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }
@@ -438,7 +454,7 @@ extern "C" int ptv_ce_group_bwd(const float* logits, long ld, const int* targets
                                 const float* gscale, float* dlogits, long ldd, void* stream) {
   if (!logits || !targets || !gscale || !dlogits || rows <= 0 || C <= 0 || C > 16 || G <= 0 || G > 8) return PTV_ERR_ARG;
   hipLaunchKernelGGL((ce_group_kernel<true>), dim3(grid_rows(rows, 256, 2048)), dim3(256), 0, (hipStream_t)stream, logits, ld, targets, rows, C,
-                     ignore_index, G, nullptr, nullptr, gscale, dlogits, ldd);
+                     ignore_index, G, nullptr, nullptr, gscale, dlogits, ldd, OrdScratch{nullptr, nullptr});
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

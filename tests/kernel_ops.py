@@ -27,3 +27,15 @@ def gru_seq_fwd(gi, w_hh, b_hh, hall, gates=None, *, gi2=None, lengths=None, rev
 def gru_seq_bwd(hall, gates, w_hh, *, dh_ext=None, dh_last=None, reverse=False, prec='fp32', need_dh0=True):
     return F_.gru_bwd(prec_code(prec), hall, gates, w_hh, dh_ext=dh_ext, dh_last=dh_last, reverse=reverse,
                       need_dh0=need_dh0)
+
+
+# ---- leaf kernels (tests/test_gpu_leaf_kernels.py): the C ABI called as it is declared, tensors for the pointers, on the current stream
+def leaf_rc(name, *args):
+    """status code of `name(*args, stream)`: tensors become device pointers, None a NULL pointer"""
+    from polyphonic_chord_texture_disentanglement_amd._lib import lib, ptr, stream_ptr
+    return getattr(lib(), name)(*[ptr(a) if isinstance(a, torch.Tensor) else a for a in args], stream_ptr())
+
+
+def leaf(name, *args):
+    from polyphonic_chord_texture_disentanglement_amd._lib import check
+    check(leaf_rc(name, *args), name)
