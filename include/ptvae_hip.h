@@ -236,6 +236,21 @@ int ptv_embed_fwd_geom(const long* x, const float* W, const float* bias, float* 
                        int S, int N, int P, int D, int pad, void* stream);
 int ptv_grid_lengths_geom(const long* x, int* lengths, int B, int S, int N, int D, int pad, void* stream);
 int ptv_multihot_geom(const long* x, void* out, long ld, int B, int S, int N, int P, int D, int bf16, void* stream);
+/* Note embedding of a BYTE multi-hot grid: the input of the texture encoder train.py:32 builds, the detrended PianoTree grid dt_x of
+ * ptv_detrend_pianotree (K = 39: 34 class columns of 0/1, 5 duration columns of 0/1/2; a row holds at most 10 non-zero bytes).
+ *   mh [B,S,N,K] uint8 (any values), W [E,K], bias [E] -> emb step-major [N][S][B][E] fp32 (the layout of ptv_embed_fwd_geom):
+ *   emb[n][s][b][:] = bias + sum_k mh[b,s,n,k] * W[:,k]; zero bytes are skipped, the other terms added in ascending k -- a pure function
+ *   of the inputs (bit-reproducible); an all-zero row gives bias.
+ *   lengths [S][B] int32 (or NULL) = number of rows n with mh[b,s,n,pad_col] == 0; for dt_x pad_col = 3, the is_note class of the <pad>
+ *   pitch, which makes it get_len_index_tensor (ptvae.py:167-172) of the grid the dt_x came from.  pad_col < 0: no lengths wanted.
+ * One launch: W is staged transposed in LDS, a tile is one step and 8 samples, a row's E floats leave as 16-byte stores.
+ * PTV_ERR_ARG before any launch for: a NULL mh / W / bias / emb, B, S, N or K <= 0, K > 64, E > 256 or not a multiple of 4, K*E*4 > 150 KB,
+ * N*K > 16384, pad_col >= K, lengths without a pad_col >= 0, emb not 16-byte aligned (mh may sit anywhere). */
+int ptv_embed_multihot_fwd(const unsigned char* mh, const float* W, const float* bias, float* emb, int* lengths,
+                           int B, int E, int S, int N, int K, int pad_col, void* stream);
+/* the same bytes widened (0 / 1 / 2 are exact in both types): out [N*S*B][ld] fp32 (bf16 != 0: bf16) in the step-major row order of emb,
+ * ld >= K, columns K .. ld-1 zeroed -- what ptv_multihot_geom is to the index grid: the operand of grad_W = demb^T . rows(mh) */
+int ptv_multihot_bytes_rows(const unsigned char* mh, void* out, long ld, int B, int S, int N, int K, int bf16, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * TextureEncoder front end (ptvae.py:95-99,112-114): Conv2d(1,C,(4,12),stride(4,1)) + ReLU +

@@ -170,8 +170,8 @@ class TrainingInterface:
         mode = os.environ.get('PTV_GRAPH_STEP', self.graph_step)
         mode = {'1': True, 'on': True, '0': False, 'off': False}.get(str(mode).lower(), mode)
         opt = self.opt_scheduler.optimizer
-        if mode is False or not hasattr(opt, 'clip_and_step') or not inputs[0].is_cuda:
-            return None
+        if mode is False or not hasattr(opt, 'clip_and_step') or len(inputs) != 3 or not inputs[0].is_cuda:
+            return None                                        # (the replayed step takes (x, c, pr_mat): the detrended variant's four inputs run eagerly)
         tfr = (params.get('tfr1', 0.), params.get('tfr2', 0.), params.get('tfr3', 0.))
         if any(float(t) != 1.0 for t in tfr) or 'weights' not in params:
             return None

@@ -292,6 +292,102 @@ __global__ void multihot_kernel(const long* __restrict__ x, T* __restrict__ out,
 }
 
 // ---------------------------------------------------------------------------------------------
+// note embedding of a BYTE multi-hot grid (the detrended PianoTree grid dt_x of csrc/dataset.hip: 34 class columns of 0/1, 5 duration
+// columns of 0/1/2; at most 10 of a row's 39 bytes are set):
+//   mh [B,S,N,K] uint8 -> emb step-major [N][S][B][E] = bias + sum_k mh[b,s,n,k] * W[:,k], lengths [S][B] = rows with mh[.., pad_col] == 0
+// A tile is one step s and BC consecutive samples: their N*K-byte slabs are contiguous in mh (16-byte loads when N*K is a multiple of 16,
+// as 16*39 is), and every note row n of the tile is BC*E contiguous floats of emb.  The slabs are staged in LDS as they stand; a row's bytes
+// are read back as dwords (a zero dword = four skipped terms), the set bytes' weight rows as 16-byte LDS reads in ascending k: the sum is a
+// pure function of the inputs.  E/4 lanes share a row, each writes one float4.
+// ---------------------------------------------------------------------------------------------
+__global__ void embed_multihot_fwd_kernel(const unsigned char* __restrict__ mh, const float* __restrict__ W, const float* __restrict__ bias,
+                                          float* __restrict__ emb, int* __restrict__ lengths, int B, int E, int S, int N, int K, int pad_col,
+                                          int BC, int vec) {
+  __builtin_amdgcn_s_setprio(3);                                         // always part of a latency chain
+  extern __shared__ __attribute__((aligned(16))) float wt[];     // [K][E] transposed weight, then the tile's bytes [BC][N][K] (+ 16 spare)
+  unsigned* raw = reinterpret_cast<unsigned*>(wt + K * E);
+  unsigned char* raw8 = reinterpret_cast<unsigned char*>(raw);
+  for (int i = threadIdx.x; i < K * E; i += blockDim.x) { int e = i / K, k = i % K; wt[k * E + e] = W[i]; }     // (coalesced reads; the transposing side is the LDS)
+  const int slab = N * K;                                        // bytes of one (sample, step)
+  const int bchunks = (B + BC - 1) / BC;
+  const int tpn = E / 4, per = blockDim.x / tpn;                 // lanes per note row, rows in flight per block
+  const int e = (threadIdx.x % tpn) * 4, sub = threadIdx.x / tpn;
+  const float4 bv = *reinterpret_cast<const float4*>(bias + e);
+  for (int tile = blockIdx.x; tile < S * bchunks; tile += gridDim.x) {
+    const int s = tile / bchunks, b0 = (tile % bchunks) * BC;
+    const int bc = min(BC, B - b0);
+    __syncthreads();                                             // (the weight is staged; the previous tile's readers are done)
+    if (vec) {
+      const int q = slab / 16;
+      for (int i = threadIdx.x; i < bc * q; i += blockDim.x) {
+        const int bi = i / q, j = i % q;
+        reinterpret_cast<uint4*>(raw)[i] = reinterpret_cast<const uint4*>(mh + ((long)(b0 + bi) * S + s) * slab)[j];
+      }
+    } else {
+      for (int i = threadIdx.x; i < bc * slab; i += blockDim.x) {
+        const int bi = i / slab, j = i % slab;
+        raw8[i] = mh[((long)(b0 + bi) * S + s) * slab + j];
+      }
+    }
+    for (int i = threadIdx.x; i < 16; i += blockDim.x) raw8[bc * slab + i] = 0;      // (a row's last dword may reach past the tile)
+    __syncthreads();
+    if (lengths && threadIdx.x < bc) {
+      int live = 0;
+      for (int n = 0; n < N; n++) live += raw8[(threadIdx.x * N + n) * K + pad_col] == 0;
+      lengths[(long)s * B + b0 + threadIdx.x] = live;
+    }
+    if (sub >= per) continue;
+    for (int r = sub; r < N * bc; r += per) {                    // r = n * bc + bi: the tile's output rows, bi fastest
+      const int n = r / bc, bi = r % bc;
+      const int off = (bi * N + n) * K;                          // the row's first byte in the staged tile
+      const int d0 = off >> 2, sh = off & 3;
+      const int nd = (sh + K + 3) >> 2;
+      float4 v = bv;
+      for (int j = 0; j < nd; j++) {
+        const unsigned w = raw[d0 + j];
+        if (w == 0u) continue;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const unsigned byte = (w >> (8 * q)) & 255u;
+          const int k = j * 4 + q - sh;
+          if (byte != 0u && k >= 0 && k < K) {
+            const float f = (float)byte;
+            const float4 c = *reinterpret_cast<const float4*>(wt + k * E + e);
+            v.x += c.x * f; v.y += c.y * f; v.z += c.z * f; v.w += c.w * f;
+          }
+        }
+      }
+      *reinterpret_cast<float4*>(emb + (((long)n * S + s) * B + b0 + bi) * E + e) = v;
+    }
+  }
+}
+
+// the same bytes widened: out [N*S*B][ld] in the embedding's step-major row order, columns K .. ld-1 zero (operand of the weight gradient)
+template <typename T>
+__global__ void multihot_bytes_rows_kernel(const unsigned char* __restrict__ mh, T* __restrict__ out, long ld, int B, int S, int N, int K, int vec) {
+  const long rows = (long)B * S * N;
+  if (vec) {
+    const long q = ld / 4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < rows * q; i += (long)gridDim.x * blockDim.x) {
+      const long r = i / q; const int c = (int)(i % q) * 4;
+      const int b = (int)(r % B); const long u = r / B; const int s = (int)(u % S), n = (int)(u / S);
+      const unsigned char* src = mh + (((long)b * S + s) * N + n) * K;
+      alignas(16) T o[4];
+#pragma unroll
+      for (int d = 0; d < 4; d++) o[d] = (T)(c + d < K ? (float)src[c + d] : 0.f);
+      if constexpr (sizeof(T) == 4) *reinterpret_cast<float4*>(out + r * ld + c) = *reinterpret_cast<const float4*>(o);
+      else *reinterpret_cast<uint2*>(out + r * ld + c) = *reinterpret_cast<const uint2*>(o);
+    }
+    return;
+  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < rows * ld; i += (long)gridDim.x * blockDim.x) {
+    const long r = i / ld; const int c = (int)(i % ld);
+    const int b = (int)(r % B); const long u = r / B; const int s = (int)(u % S), n = (int)(u / S);
+    out[i] = (T)(c < K ? (float)mh[(((long)b * S + s) * N + n) * K + c] : 0.f);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // reparameterisation + KL (train_utils.py:33-34,45-49):  z = mu + std*eps ; kl = mean(-log std + (std^2+mu^2)/2 - 1/2)
 // ---------------------------------------------------------------------------------------------
 __global__ void reparam_kl_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ sd, const float* __restrict__ eps,
@@ -478,6 +574,41 @@ extern "C" int ptv_multihot(const long* x, float* out, long ld, int B, void* str
 extern "C" int ptv_multihot_bf16(const long* x, void* out, long ld, int B, void* stream) {
   if (ld < 136) return PTV_ERR_ARG;
   return ptv_multihot_geom(x, out, ld, B, 32, 16, 130, 5, 1, stream);
+}
+
+extern "C" int ptv_embed_multihot_fwd(const unsigned char* mh, const float* W, const float* bias, float* emb, int* lengths,
+                                      int B, int E, int S, int N, int K, int pad_col, void* stream) {
+  if (!mh || !W || !bias || !emb || B <= 0 || S <= 0 || N <= 0 || K <= 0 || K > 64 || E <= 0 || E > 256 || (E & 3)) return PTV_ERR_ARG;
+  if ((size_t)K * E * sizeof(float) > 150 * 1024 || (long)N * K > 16384) return PTV_ERR_ARG;
+  if (pad_col >= K || (lengths && pad_col < 0)) return PTV_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(emb) & 15) return PTV_ERR_ARG;                       // (16-byte stores; mh may sit anywhere)
+  const size_t wbytes = (size_t)K * E * sizeof(float), cap = 160 * 1024;
+  int BC = 8;                                                                          // samples per tile: 8 x 624 bytes staged for dt_x
+  while (BC > 1 && ((size_t)BC * N * K > 16384 || wbytes + (size_t)BC * N * K + 16 > cap)) BC >>= 1;
+  const size_t lds = wbytes + (size_t)BC * N * K + 16;
+  if (lds > cap) return PTV_ERR_ARG;
+  if (lds > 64 * 1024) {
+    static bool attr = false;
+    if (!attr) { if (hipFuncSetAttribute((const void*)embed_multihot_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess) return PTV_ERR_LAUNCH; attr = true; }
+  }
+  const int vec = ((N * K) % 16 == 0) && (reinterpret_cast<uintptr_t>(mh) & 15) == 0;
+  const long tiles = (long)S * ((B + BC - 1) / BC);
+  const int grid = (int)(tiles < 1024 ? tiles : 1024);
+  hipLaunchKernelGGL(embed_multihot_fwd_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, mh, W, bias, emb, lengths, B, E, S, N, K,
+                     pad_col, BC, vec);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+extern "C" int ptv_multihot_bytes_rows(const unsigned char* mh, void* out, long ld, int B, int S, int N, int K, int bf16, void* stream) {
+  if (!mh || !out || B <= 0 || S <= 0 || N <= 0 || K <= 0 || ld < K) return PTV_ERR_ARG;
+  const int vec = (ld % 4 == 0) && (reinterpret_cast<uintptr_t>(out) & (bf16 ? 7 : 15)) == 0;
+  const long work = (long)B * S * N * (vec ? ld / 4 : ld);
+  const int grid = grid_for(work, 256, 8192);
+  if (bf16) hipLaunchKernelGGL((multihot_bytes_rows_kernel<__bf16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, mh, (__bf16*)out, ld, B, S, N, K, vec);
+  else hipLaunchKernelGGL((multihot_bytes_rows_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, mh, (float*)out, ld, B, S, N, K, vec);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
 }
 
 extern "C" int ptv_reparam_kl_fwd(const float* mu, const float* sd, const float* eps, float* z, long ldz, float* kl_sum, int B, int Z, void* stream) {

@@ -4,7 +4,8 @@ The POP909 files the reference's `dataset.py` needs are not available, so `get_l
 synthetic generator of `synthetic.py` in the reference's batch layout
 `(mel_segments, prs, pr_mats, p_grids, chord, dt_x)` (`dataset.py:117-118`); `_batch_to_inputs` applies
 the reference's casts (`dataset_loaders.py:28-34`) and returns the THREE tensors the model consumes
-(the reference returns four and cannot run)."""
+(the reference returns four and cannot run) -- or four, with `dt_x`, when the model's
+texture encoder is the `PtvaeEncoder` of the reference's `train.py:32` (`DisentangleVAE.init_model_detrended`)."""
 import torch
 
 from ._lib import call, ptr, stream_ptr
@@ -111,24 +112,26 @@ class MusicDataLoaders(DataLoaders):
 
     @staticmethod
     def get_loaders(seed, bs_train, bs_val, portion=8, shift_low=-6, shift_high=5, num_bar=2, contain_chord=True,
-                    random_train=True, random_val=False, n_train_batch=8, n_val_batch=2, device_bank=None):
+                    random_train=True, random_val=False, n_train_batch=8, n_val_batch=2, device_bank=None, slots=()):
         """device_bank = (pr uint8 [N,32,128], chord14 [N,8,14]) serves the reference's augmented epochs from HBM
         (DeviceBatcher); an ArrangementDataset (its last 1/(portion+1) windows validate, unshifted) or a (train, validation) pair
-        of them serves them from the note bank; otherwise the synthetic three-tensor generator."""
+        of them serves them from the note bank; otherwise the synthetic three-tensor generator.  slots: which of the otherwise empty
+        batch slots a DeviceBatcher fills (('dt_x',) for the detrended variant; a (pr, chord14) bank has no notes and refuses any;
+        the synthetic generator leaves placeholders, and TrainingVAE then computes dt_x on the device)."""
         from .dataset import ArrangementDataset
         if isinstance(device_bank, ArrangementDataset):
             inds = device_bank.valid_inds
             n_val = max(1, len(inds) // (portion + 1))
             device_bank = (device_bank.subset(inds[:-n_val], shift_low, shift_high), device_bank.subset(inds[-n_val:], 0, 0))
         if device_bank is not None and isinstance(device_bank[0], ArrangementDataset):
-            train = DeviceBatcher(device_bank[0], None, bs_train, shuffle=random_train, seed=seed)
-            val = DeviceBatcher(device_bank[1], None, bs_val, shuffle=random_val, seed=seed + 1)
+            train = DeviceBatcher(device_bank[0], None, bs_train, shuffle=random_train, seed=seed, slots=slots)
+            val = DeviceBatcher(device_bank[1], None, bs_val, shuffle=random_val, seed=seed + 1, slots=slots)
             return MusicDataLoaders(train, val, bs_train, bs_val)
         if device_bank is not None:
             pr, chord = device_bank
             n_val = max(1, pr.shape[0] // (portion + 1))                 # dataset.py:241-245,273-276: 1/(portion+1) validates, unshifted
-            train = DeviceBatcher(pr[:-n_val], chord[:-n_val], bs_train, shift_low, shift_high, random_train, seed)
-            val = DeviceBatcher(pr[-n_val:], chord[-n_val:], bs_val, 0, 0, random_val, seed + 1)
+            train = DeviceBatcher(pr[:-n_val], chord[:-n_val], bs_train, shift_low, shift_high, random_train, seed, slots=slots)
+            val = DeviceBatcher(pr[-n_val:], chord[-n_val:], bs_val, 0, 0, random_val, seed + 1, slots=slots)
             return MusicDataLoaders(train, val, bs_train, bs_val)
         train = _SyntheticLoader(n_train_batch, bs_train, seed)
         val = _SyntheticLoader(n_val_batch, bs_val, seed + 10 ** 6)
@@ -141,9 +144,26 @@ class MusicDataLoaders(DataLoaders):
 
 class TrainingVAE(TrainingInterface):
 
+    def __init__(self, device, model, parallel, *args, **kwargs):
+        # The detrended variant has not been run under data parallelism: GradSync sends slices of the gradient bucket early, from hook
+        # sites that were placed and measured for the conv texture encoder's backward order.  Refused rather than exchanged unverified.
+        if parallel and getattr(model, 'detrended', False):
+            raise NotImplementedError('TrainingVAE: the detrended texture encoder (PtvaeEncoder as rhy_encoder) does not train under data '
+                                      'parallelism yet -- GradSync\'s early gradient exchange is unverified for it; run it on one GPU '
+                                      '(parallel=False) or use the conv TextureEncoder')
+        super().__init__(device, model, parallel, *args, **kwargs)
+
     def _batch_to_inputs(self, batch):
-        _, _, pr_mat, x, c, _ = batch
+        _, _, pr_mat, x, c, dt_x = batch
         pr_mat = pr_mat.to(self.device).float()
         x = x.to(self.device).long()
         c = c.to(self.device).float()
-        return x, c, pr_mat
+        if not getattr(self.model, 'detrended', False):
+            return x, c, pr_mat
+        # the sixth slot holds dt_x when the loader fills it (DeviceBatcher slots=('dt_x',)); empty or a placeholder: computed on the device
+        if torch.is_tensor(dt_x) and dt_x.dim() == 4 and tuple(dt_x.shape) == (x.shape[0], 32, 16, 39):
+            dt_x = dt_x.to(self.device).to(torch.uint8)
+        else:
+            from .dataset import detrend_pianotree
+            dt_x = detrend_pianotree(x, c)
+        return x, c, pr_mat, dt_x

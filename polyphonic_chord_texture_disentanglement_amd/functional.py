@@ -1011,6 +1011,59 @@ class EmbedFn(torch.autograd.Function):
 
 
 # =============================================================================================
+# PtvaeEncoder.encode_multihot: note embedding of a byte multi-hot grid (the detrended grid dt_x, train.py:32's encoder input)
+# =============================================================================================
+class EmbedMultihotFn(torch.autograd.Function):
+    """mh uint8 [B,S,N,K] -> (emb step-major [N,S,B,E], lengths int32 [S*B] = rows with mh[..., pad_col] == 0; pad_col < 0: no lengths,
+    an empty tensor comes back).  One launch (ptv_embed_multihot_fwd): no float copy of mh, no transpose.  The weight gradient is
+    demb^T . rows(mh) with the bytes widened by ptv_multihot_bytes_rows into rows of stride K rounded up to 8; no gradient to mh."""
+
+    @staticmethod
+    def forward(ctx, mh, w, b, prec=0, pad_col=-1):
+        assert mh.dim() == 4 and mh.dtype == torch.uint8 and w.shape[1] == mh.shape[3], (tuple(mh.shape), mh.dtype, tuple(w.shape))
+        B, S, N, K = mh.shape
+        E = w.shape[0]
+        ctx.prec = prec
+        mh = mh.contiguous()
+        emb = _empty(N, S, B, E, dev=w.device)
+        lengths = torch.empty(S * B if pad_col >= 0 else 0, device=w.device, dtype=torch.int32)
+        call('ptv_embed_multihot_fwd', ptr(mh), ptr(w), ptr(b), ptr(emb), ptr(lengths) if pad_col >= 0 else None, B, E, S, N, K, int(pad_col),
+             stream_ptr())
+        ctx.save_for_backward(mh, w, b)
+        ctx.mark_non_differentiable(lengths)
+        # as EmbedFn: in bf16 precision the operand of the weight gradient depends on the input only and is built NOW on a sibling stream
+        ctx.op = ctx.op_ev = None
+        if (EMBED_MH_FWD and prec == 1 and E % 8 == 0 and OVERLAP and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+                and not capturing_part()):
+            def build():
+                op = _empty(B * S * N, _pad8(K), dev=w.device, dtype=BF16)
+                call('ptv_multihot_bytes_rows', ptr(mh), ptr(op), _pad8(K), B, S, N, K, 1, stream_ptr())
+                return op, record_event()
+            ctx.op, ctx.op_ev = Side(EMBED_MH_SLOT)(build, mh)           # (op_ev: the event the backward waits for -- not the whole stream)
+        return emb, lengths
+
+    @staticmethod
+    def backward(ctx, demb, _dl):
+        mh, w, b = ctx.saved_tensors
+        B, S, N, K = mh.shape
+        E = w.shape[0]
+        demb2 = demb.contiguous().view(B * S * N, E)
+        op, ev, ctx.op, ctx.op_ev = ctx.op, ctx.op_ev, None, None
+        if op is not None:
+            wait_event(cur_stream(), ev)
+        else:
+            bf = ctx.prec == 1 and E % 8 == 0
+            op = _empty(B * S * N, _pad8(K), dev=w.device, dtype=BF16 if bf else F32)
+            call('ptv_multihot_bytes_rows', ptr(mh), ptr(op), _pad8(K), B, S, N, K, int(bf), stream_ptr())
+        if op.dtype == BF16:
+            dw, db = wgrad_bias(demb2, op[:, :K], _gbuf(w), _gbuf(b), ctx.prec)       # bias gradient inside the same pass over demb
+        else:
+            dw = gemm(demb2, op[:, :K], _gbuf(w), ta=True, tb=True, acc=True, prec=ctx.prec)
+            db = _bgrad(b, demb2)
+        return None, dw, db, None, None
+
+
+# =============================================================================================
 # bidirectional GRU, final states only  (RnnEncoder / TextureEncoder / dec_notes_emb_gru)
 # =============================================================================================
 _BGF, _BGB, _BRF, _BRB = SlotTable('BGF'), SlotTable('BGB'), SlotTable('BRF'), SlotTable('BRB')

@@ -12,7 +12,7 @@ import torch
 from . import functional as F_
 from .amc_dl.torch_plus import PytorchModel
 from .optim import refresh_weight_shadows
-from .ptvae import HipNormal, PtvaeDecoder, RnnDecoder, RnnEncoder, TextureEncoder
+from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder
 
 LOSS_NAMES = ['loss', 'recon_loss', 'pl', 'dl', 'kl_loss', 'kl_chd', 'kl_rhy', 'chord_loss', 'root_loss',
               'chroma_loss', 'bass_loss']                       # train.py:54-55
@@ -30,6 +30,8 @@ CHD_DEC_SLOT = 4        # the chord decoder beside the PianoTree decoder
 # The two encoders ARE the latency chain of the head of the step (the decoder waits for z; the embedding / note summaries beside them are
 # needed later): their products keep the raised wave priority although they run inside sibling-stream calls, the note-summary GRUs drop it
 ENC_CHAIN = True
+DT_PAD_COL = 3          # column of dt_x that is set for a <pad> row (is_note class 3, dataset.py:194-195): its zeros count the live rows
+DT_SHAPE = (32, 16, 39)
 
 
 class DisentangleVAE(PytorchModel):
@@ -44,6 +46,27 @@ class DisentangleVAE(PytorchModel):
         self.eps_source = None      # optional callable (name, shape, device) -> eps tensor (tests)
         self._philox = None         # (seed, global index of this process's first sample): see use_philox()
         self._draws = 0
+
+    # ---- the texture encoder decides what the texture input is.  A TextureEncoder (init_model) reads the piano-roll pr_mat; a PtvaeEncoder
+    # (init_model_detrended: the wiring of the reference's train.py:31-39) reads the detrended PianoTree grid dt_x, uint8 [B,32,16,39]
+    @property
+    def detrended(self):
+        return isinstance(self.rhy_encoder, PtvaeEncoder)
+
+    @staticmethod
+    def _check_dt_x(dt_x, batch=None):
+        if not torch.is_tensor(dt_x) or dt_x.dtype != torch.uint8 or dt_x.dim() != 4 or tuple(dt_x.shape[1:]) != DT_SHAPE \
+                or (batch is not None and dt_x.shape[0] != batch):
+            got = '%s %s' % (dt_x.dtype, tuple(dt_x.shape)) if torch.is_tensor(dt_x) else type(dt_x).__name__
+            raise ValueError('this model\'s texture encoder is a PtvaeEncoder: its input is the detrended grid dt_x, uint8 [%s,32,16,39] '
+                             '(dataset.detrend_pianotree(x, c)), not the piano-roll; got %s' % ('B' if batch is None else batch, got))
+        return dt_x
+
+    def _encode_texture(self, t):
+        """the texture encoder on what the reference's signatures call `pr_mat`: pr_mat itself, or dt_x for the detrended variant"""
+        if not self.detrended:
+            return self.rhy_encoder(t)
+        return self.rhy_encoder.encode_multihot(self._check_dt_x(t), pad_col=DT_PAD_COL)[0]
 
     # ---- precision switch: 'fp32' (exact, parity) | 'bf16' (bf16 MFMA operands, fp32 accumulate)
     def set_precision(self, precision):
@@ -91,7 +114,9 @@ class DisentangleVAE(PytorchModel):
         return torch.log(c + 1)
 
     # ---- model.py:42-55
-    def run(self, x, c, pr_mat, tfr1, tfr2, tfr3, confuse=True, *, live=None):
+    def run(self, x, c, pr_mat, tfr1, tfr2, tfr3, confuse=True, *, live=None, dt_x=None):
+        """dt_x: the detrended variant's texture input (uint8 [B,32,16,39]; None = computed here by dataset.detrend_pianotree(x, c));
+        ignored when the texture encoder is a TextureEncoder"""
         F_.mark('run:start')
         refresh_weight_shadows()                         # bf16 operand copies of the flat parameter buffer (if any)
         F_.mark('run:shadows')
@@ -100,12 +125,21 @@ class DisentangleVAE(PytorchModel):
         # what its parent has queued so far, and the embedding (queued on the parent next) is not their input
         from .ptvae import _require_cuda
         _require_cuda(x, 'DisentangleVAE.run')               # (fails loudly off-GPU before any stream is touched)
+        if self.detrended:
+            if dt_x is None:
+                from .dataset import detrend_pianotree
+                dt_x = detrend_pianotree(x.long(), c)        # (on the caller's stream: the sibling stream below waits for it)
+            else:
+                self._check_dt_x(dt_x, x.size(0))
         s_chd, s_rhy = F_.Side(CHD_ENC_SLOT, chain=ENC_CHAIN), F_.Side(RHY_ENC_SLOT, chain=ENC_CHAIN)
         self.decoder.summaries_needed = tfr1 > 0             # with tfr1 = 0 no time step is fed a ground-truth note summary
         # (creating the embedding / note-summary nodes FIRST, so that autograd runs the encoders' BPTTs before the note-summary BPTT, measured
         # inside box noise, 8.11-9.0 ms per step: the plain order stays)
         dist_chd = s_chd(lambda: self.chd_encoder(c), c)
-        dist_rhy = s_rhy(lambda: self.rhy_encoder(pr_mat), pr_mat)
+        if self.detrended:
+            dist_rhy = s_rhy(lambda: self._encode_texture(dt_x), dt_x)
+        else:
+            dist_rhy = s_rhy(lambda: self.rhy_encoder(pr_mat), pr_mat)
         try:
             embedded_x, lengths = self.decoder.emb_x(x)
         finally:
@@ -148,12 +182,14 @@ class DisentangleVAE(PytorchModel):
         return kl_chd + kl_rhy, kl_chd, kl_rhy
 
     # ---- model.py:92-96.  Same positional/keyword signature (x, c, pr_mat, tfr1=0., tfr2=0., tfr3=0.,
-    # beta=0.1, weights=(1, 0.5)); additionally a 4th positional TENSOR (the reference's unused `dt_x`,
-    # which makes its own trainer call fail -- SURVEY.md §0.2) is accepted and ignored.
+    # beta=0.1, weights=(1, 0.5)); additionally a 4th positional TENSOR, the `dt_x` the reference's trainer passes (its own loss() has no
+    # slot for it -- SURVEY.md §0.2), is accepted: the detrended variant's texture input; ignored with a TextureEncoder.
     def loss(self, x, c, pr_mat, *args, **kwargs):
         args = list(args)
+        dt_x = None
         while args and torch.is_tensor(args[0]):
-            args.pop(0)
+            t = args.pop(0)
+            dt_x = t if dt_x is None else dt_x
         names = ('tfr1', 'tfr2', 'tfr3', 'beta', 'weights')
         if len(args) > len(names):
             raise TypeError('loss() takes at most %d scalar arguments after pr_mat' % len(names))
@@ -170,16 +206,24 @@ class DisentangleVAE(PytorchModel):
         # steps after the batch's last target uncomputed.  Both nodes get the plan (functional.live_rows): the decoder records the row order
         # of its logits, the loss takes the targets in that order (run() on its own gets no plan and always computes every step)
         live = F_.live_rows(x) if (torch.is_grad_enabled() and p['tfr1'] >= 1. and p['tfr2'] >= 1.) else None
-        outputs = self.run(x, c, pr_mat, p['tfr1'], p['tfr2'], p['tfr3'], live=live)
+        if self.detrended:
+            outputs = self.run(x, c, pr_mat, p['tfr1'], p['tfr2'], p['tfr3'], live=live, dt_x=dt_x)
+        else:
+            outputs = self.run(x, c, pr_mat, p['tfr1'], p['tfr2'], p['tfr3'], live=live)
         return self.loss_function(x, c, *outputs, p['beta'], p['weights'], live=live)
 
-    # ---- model.py:117-122
+    # ---- model.py:117-122.  In the whole inference family (inference_encode, inference, swap, posterior_sample, prior_sample, interp) the
+    # argument the reference names `pr_mat` (`x` in prior_sample) is the texture encoder's input: the piano-roll f32 [B,32,128] for a
+    # TextureEncoder, the detrended grid dt_x uint8 [B,32,16,39] for the detrended variant (anything else: ValueError)
     def inference_encode(self, pr_mat, c):
+        """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
+        if self.detrended:
+            self._check_dt_x(pr_mat)                     # (a piano-roll here is a ValueError, not a shape crash inside a kernel)
         self.eval()
         refresh_weight_shadows()                         # no-op unless the parameters changed since the last cast
         with torch.no_grad():
             dist_chd = self.chd_encoder(c)
-            dist_rhy = self.rhy_encoder(pr_mat)
+            dist_rhy = self._encode_texture(pr_mat)
         return dist_chd, dist_rhy
 
     # ---- model.py:124-131: free-running decode; est_x = the argmax grid the step loop produced on device
@@ -217,23 +261,28 @@ class DisentangleVAE(PytorchModel):
 
     # ---- model.py:133-142
     def inference(self, pr_mat, c, sample):
+        """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
+        if self.detrended:
+            self._check_dt_x(pr_mat)                     # (a piano-roll here is a ValueError, not a shape crash inside a kernel)
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
             dist_chd = self.chd_encoder(c)
-            dist_rhy = self.rhy_encoder(pr_mat)
+            dist_rhy = self._encode_texture(pr_mat)
             z_chd = self._rsample('chd', dist_chd) if sample else dist_chd.mean
             z_rhy = self._rsample('rhy', dist_rhy) if sample else dist_rhy.mean
         return self.inference_decode(z_chd, z_rhy)
 
     # ---- model.py:144-148
     def swap(self, pr_mat1, pr_mat2, c1, c2, fix_rhy, fix_chd):
+        """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant"""
         pr_mat = pr_mat1 if fix_rhy else pr_mat2
         c = c1 if fix_chd else c2
         return self.inference(pr_mat, c, sample=False)
 
     # ---- model.py:150-172
     def posterior_sample(self, pr_mat, c, scale=None, sample_chd=True, sample_txt=True):
+        """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
         if scale is None and sample_chd and sample_txt:
             return self.inference(pr_mat, c, sample=True)
         dist_chd, dist_rhy = self.inference_encode(pr_mat, c)
@@ -253,6 +302,7 @@ class DisentangleVAE(PytorchModel):
 
     # ---- model.py:174-184
     def prior_sample(self, x, c, sample_chd=False, sample_rhy=False, scale=1.):
+        """x: the texture encoder's input (the reference's name for this slot here) -- the piano-roll, or dt_x for the detrended variant"""
         dist_chd, dist_rhy = self.inference_encode(x, c)
         mean = torch.zeros_like(dist_rhy.mean)
         loc = torch.ones_like(dist_rhy.mean) * scale
@@ -270,6 +320,7 @@ class DisentangleVAE(PytorchModel):
 
     # ---- model.py:190-209: decode int_count points on the path between two items' latent codes
     def interp(self, pr_mat1, c1, pr_mat2, c2, interp_chd=False, interp_rhy=False, int_count=10):
+        """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant"""
         dist_chd1, dist_rhy1 = self.inference_encode(pr_mat1, c1)
         dist_chd2, dist_rhy2 = self.inference_encode(pr_mat2, c2)
         z_chd1, z_rhy1, z_chd2, z_rhy2 = dist_chd1.mean, dist_rhy1.mean, dist_chd2.mean, dist_rhy2.mean
@@ -308,6 +359,18 @@ class DisentangleVAE(PytorchModel):
         rhy_encoder = TextureEncoder(256, 1024, txt_size, num_channel)
         chd_decoder = RnnDecoder(z_dim=chd_size)
         pt_decoder = PtvaeDecoder(note_embedding=None, dec_dur_hid_size=64, z_size=chd_size + txt_size)
+        return DisentangleVAE(name, device, chd_encoder, rhy_encoder, pt_decoder, chd_decoder)
+
+    # ---- train.py:31-39: the reference's own entry script wires a PtvaeEncoder over the 39-wide detrended grid as the texture encoder
+    @staticmethod
+    def init_model_detrended(device=None):
+        name = 'disvae-nozoth'
+        if device is None:
+            device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+        chd_encoder = RnnEncoder(36, 1024, 256)
+        rhy_encoder = PtvaeEncoder(device=device, z_size=256, max_pitch=39 - 8, min_pitch=0)
+        chd_decoder = RnnDecoder(z_dim=256)
+        pt_decoder = PtvaeDecoder(note_embedding=None, dec_dur_hid_size=64, z_size=512)
         return DisentangleVAE(name, device, chd_encoder, rhy_encoder, pt_decoder, chd_decoder)
 
 

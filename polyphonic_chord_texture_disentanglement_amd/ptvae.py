@@ -619,6 +619,36 @@ class PtvaeEncoder(nn.Module, _PrecMixin):
                                          self._prec)
         return HipNormal(mu, sd), emb_b
 
+    def encode_multihot(self, mh, lengths=None, pad_col=None):
+        """encoder() for a BYTE multi-hot grid: mh uint8 [B,S,N,note_size] on the device (the detrended grid dt_x of
+        dataset.detrend_pianotree is one: train.py:32 builds this class for it) -> (Normal, embedded [B,S,N,E] as the permuted view of
+        the step-major buffer); differentiable in the parameters.  lengths: the reference's [B,S] (get_len_index_tensor of the grid the
+        multi-hot came from), or derived from pad_col: the rows whose byte in that column is 0 (dt_x: pad_col = 3, the is_note class of
+        the <pad> pitch).  One embedding launch (EmbedMultihotFn): no float copy of mh, no [B*S*N, note_size] product, no transpose."""
+        _require_cuda(mh, 'PtvaeEncoder.encode_multihot')
+        self._check_grid()
+        S, N, K = self.num_step, self.max_simu_note, self.note_size
+        if mh.dtype != torch.uint8 or mh.dim() != 4 or tuple(mh.shape[1:]) != (S, N, K):
+            raise ValueError('encode_multihot: uint8 [B,%d,%d,%d] expected, got %s %s' % (S, N, K, mh.dtype, tuple(mh.shape)))
+        if K > 64 or self.note_emb_size % 4:
+            raise NotImplementedError('encode_multihot on HIP: note_size <= 64, note_emb_size a multiple of 4')
+        if lengths is None and pad_col is None:
+            raise ValueError('encode_multihot: give lengths [B,%d] or pad_col (the column whose zero marks a live note row)' % S)
+        if lengths is None and not 0 <= int(pad_col) < K:
+            raise ValueError('encode_multihot: pad_col must be in 0..%d' % (K - 1))
+        B = mh.size(0)
+        emb, len32 = F_.EmbedMultihotFn.apply(mh, self.note_embedding.weight, self.note_embedding.bias, self._prec,
+                                              -1 if lengths is not None else int(pad_col))
+        if lengths is not None:
+            if tuple(lengths.shape) != (B, S):
+                raise ValueError('encode_multihot: lengths [%d,%d] expected, got %s' % (B, S, tuple(lengths.shape)))
+            len32 = lengths.t().contiguous().int().reshape(-1)
+        notes = F_.BiGruFinalFn.apply(emb.view(N, S * B, -1), len32, self._prec, *self.enc_notes_gru.weights())       # [S*B, 2Hn]
+        h = F_.BiGruFinalFn.apply(notes.view(S, B, -1), None, self._prec, *self.enc_time_gru.weights())              # [B, 2Ht]
+        mu, sd = F_.EncoderHeadsFn.apply(h, self.linear_mu.weight, self.linear_mu.bias, self.linear_std.weight, self.linear_std.bias,
+                                         self._prec)
+        return HipNormal(mu, sd), emb.permute(2, 1, 0, 3)
+
     def forward(self, x, return_iterators=False):
         _require_cuda(x, 'PtvaeEncoder')
         self._check_grid()

@@ -1,8 +1,10 @@
 """Training entry point with the reference `train.py`'s constants and wiring (train.py:16-72); the two
 deltas SURVEY.md §0.2 calls for: the texture encoder is `TextureEncoder(256, 1024, 256)` (the wiring
-that runs) and batches carry three tensors.  Data is the synthetic generator (no POP909 here).
+that runs) and batches carry three tensors.  `--texture-encoder detrended` builds the reference's own line
+instead, `PtvaeEncoder(z_size=256, max_pitch=39 - 8)` over the detrended grid `dt_x` (four tensors per batch,
+one GPU, eager steps).  Data is the synthetic generator (no POP909 here).
 
-    python -m polyphonic_chord_texture_disentanglement_amd.train [--epochs 1 --batch 128 --precision bf16]
+    python -m polyphonic_chord_texture_disentanglement_amd.train [--epochs 1 --batch 128 --precision bf16 --texture-encoder conv]
     python -m torch.distributed.run --nproc-per-node N -m polyphonic_chord_texture_disentanglement_amd.train
 """
 import argparse
@@ -17,7 +19,7 @@ from .amc_dl.torch_plus.train_utils import kl_anealing
 from .dataset_loaders import SEED, MusicDataLoaders, TrainingVAE
 from .model import DisentangleVAE
 from .optim import FusedClipAdam
-from .ptvae import PtvaeDecoder, RnnDecoder, RnnEncoder, TextureEncoder
+from .ptvae import PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder
 
 batch_size = 128
 n_epoch = 6
@@ -38,6 +40,8 @@ def main():
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--teacher-forced', action='store_true',
                     help='hold tfr=1 (the published schedule decays to free-running after 2 steps)')
+    ap.add_argument('--texture-encoder', default='conv', choices=['conv', 'detrended'],
+                    help='conv: TextureEncoder on the piano-roll (default); detrended: the PtvaeEncoder of the reference\'s train.py:32 on dt_x')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -51,7 +55,10 @@ def main():
     torch.manual_seed(0)                      # identical initial weights on every rank (GradSync also broadcasts rank 0's)
     random.seed(7)                            # teacher-forcing coins are per-step decisions for the WHOLE batch: one shared stream
     chd_encoder = RnnEncoder(36, 1024, 256)
-    rhy_encoder = TextureEncoder(256, 1024, 256)
+    if args.texture_encoder == 'detrended':
+        rhy_encoder = PtvaeEncoder(device=device, z_size=256, max_pitch=39 - 8, min_pitch=0)       # train.py:32
+    else:
+        rhy_encoder = TextureEncoder(256, 1024, 256)
     chd_decoder = RnnDecoder(z_dim=256)
     pt_decoder = PtvaeDecoder(note_embedding=None, dec_dur_hid_size=64, z_size=512)
     model = DisentangleVAE(name, device, chd_encoder, rhy_encoder, pt_decoder, chd_decoder).to(device)
