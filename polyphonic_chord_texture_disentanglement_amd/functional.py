@@ -1085,19 +1085,65 @@ def _fork_events(site, n=2):
     return evs
 
 
-def _bigru_rows_fwd_composite(x3, lengths, perm, w, out, side, T, M, I, H, dev, seg=None):
-    """-> _bigru_forward's result when ptv_bigru_rows_fwd ran its row-kernel branch, else None"""
+class BiGruState:
+    """What a bi-GRU forward leaves for its backward (a plain object: _record_stream walks its __dict__).  branch: the kernels that ran.
+    'persist' (csrc/gru_persist.hip) and 'step' (csrc/gru.hip) keep gates [T,4,M,H] plane-ordered; 'rows' (csrc/notes_persist.hip, H = 128)
+    keeps them unit-blocked and, with lengths, unwritten at skipped panel steps: only the same kernels can go back through them.
+    hall / gates / h16: per direction, the states [T+1,M,H] fp32, the gates, the states' bf16 shadow (or None).  lengths: what the kernels
+    skipped dead steps by (None: they ran dense), perm: the row order of their panels, seg: the live rows of every step in that order."""
+
+    def __init__(self, branch, dirs, lengths=None, perm=None, seg=None):
+        if branch not in ('persist', 'rows', 'step'):
+            raise ValueError('BiGruState: unknown branch %r' % (branch,))
+        self.branch, self.lengths, self.perm, self.seg = branch, lengths, perm, seg
+        self.hall, self.gates, self.h16 = (tuple(t) for t in zip(*dirs))
+        if branch != 'step' and any(g is None or g.dtype != BF16 or h is None for g, h in zip(self.gates, self.h16)):
+            raise ValueError("BiGruState: branch '%s' saves bf16 gates and bf16 states" % branch)
+        if seg is not None and perm is None:
+            raise ValueError('BiGruState: seg counts rows in the order of perm')
+        if perm is not None and lengths is None:
+            raise ValueError('BiGruState: perm orders rows by the lengths the kernels skip by')
+
+
+def _bigru_branch(prec, x3, w16, adt, T, M, I, H):
+    """the kernels a bi-GRU forward runs on -> BiGruState.branch (w16: the two weight_hh as the MFMA operands _W() hands out)"""
+    if prec == 1 and T >= 2 and adt == BF16 and w16[0].dtype == BF16 and w16[1].dtype == BF16 and persist_supported(2, M, H, T):
+        return 'persist'
+    if row_gru_ok(prec, H, I, M, adt) and x3.dtype == F32:
+        return 'rows'
+    return 'step'
+
+
+def _bigru_fwd_buffers(T, M, H, dev, adt, zero):
+    """-> one direction's (hall, gates, h16).  zero: hall[0] cleared here (the composites clear it inside the C call)"""
+    hall = _empty(T + 1, M, H, dev=dev)
+    if zero:
+        hall[0].zero_()
+    h16 = _empty(T + 1, M, H, dev=dev, dtype=BF16) if adt == BF16 else None
+    return hall, _empty(T, 4, M, H, dev=dev, dtype=adt), h16
+
+
+def _bigru_bwd_buffers(state, T, M, H, dev):
+    """-> one direction's bf16 (dgi, dgh, scratch, top) of the 'persist' / 'rows' BPTT; scratch and the `top` word (or None): row kernels only"""
+    dgi, dgh = _empty(T, M, 3 * H, dev=dev, dtype=BF16), _empty(T, M, 3 * H, dev=dev, dtype=BF16)
+    if state.branch != 'rows':
+        return dgi, dgh, None, None
+    scratch = _empty(lib().ptv_row_gru_persist_scratch_elems(H, M), dev=dev, dtype=BF16)
+    return dgi, dgh, scratch, (_ineg1(dev) if (state.lengths is not None and M % 32 == 0) else None)
+
+
+def _bigru_rows_fwd_composite(x3, lengths, skip_by, perm, seg, w, out, side, T, M, I, H, dev):
+    """-> the 'rows' BiGruState when ptv_bigru_rows_fwd ran its row-kernel branch, else None"""
     if (not OVERLAP or side.s == side.main or torch.cuda.is_current_stream_capturing() or not x3.is_contiguous() or x3.dtype != F32
             or H != 128 or I != 128):
         return None
     tens = {'X': x3, 'LENGTHS': lengths, 'PERM': perm, 'OUT': out}
-    saved = []
+    dirs = []
     for d_ in range(2):
         w_ih, w_hh, b_ih, b_hh = w[4 * d_: 4 * d_ + 4]
         pk = notes_packs(w_ih, w_hh, 0)
-        hall, h16 = _empty(T + 1, M, H, dev=dev), _empty(T + 1, M, H, dev=dev, dtype=BF16)
-        gates = _empty(T, 4, M, H, dev=dev, dtype=BF16)
-        saved.append((hall, gates, h16, (lengths if ZERO_SKIP else None), perm, seg))
+        hall, gates, h16 = _bigru_fwd_buffers(T, M, H, dev, BF16, False)
+        dirs.append((hall, gates, h16))
         tens.update({'PK_WG_H%d' % d_: pk['wg_h'], 'PK_WG_T%d' % d_: pk['wg_t'], 'B_HH%d' % d_: b_hh, 'B_IH%d' % d_: b_ih,
                      'HALL%d' % d_: hall, 'H16_%d' % d_: h16, 'GATES%d' % d_: gates})
     evs = _fork_events('BRF')
@@ -1107,41 +1153,35 @@ def _bigru_rows_fwd_composite(x3, lengths, perm, w, out, side, T, M, I, H, dev, 
         return None
     check(rc, 'ptv_bigru_rows_fwd')
     _BRF.count()
-    return out, saved
+    return BiGruState('rows', dirs, skip_by, perm, seg)
 
 
-def _bigru_rows_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, side, T, M, I, H):
-    """-> _bigru_backward's result when ptv_bigru_rows_bwd ran its row-kernel branch, else None"""
+def _bigru_rows_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, side, T, M, I, H):
+    """-> _bigru_backward's result when ptv_bigru_rows_bwd took the 'rows' BiGruState `state` back through the row kernels (launched, or
+    collected while _DEFER is a list), else None (the caller flushes)"""
     dev = x3.device
     if (prec != 1 or not OVERLAP or side.s == side.main or torch.cuda.is_current_stream_capturing() or H != 128 or I != 128 or T * M < 512
             or xf.dtype != F32 or xf.stride(1) != 1 or xf.stride(0) != I or dout.dtype != F32 or dout.stride(1) != 1):
-        _defer_flush()
         return None
     wt_ih = [_WT(w[0], prec), _WT(w[4], prec)] if need_dx else [None, None]
     if need_dx and (wt_ih[0] is None or wt_ih[1] is None):
-        _defer_flush()
         return None
-    lengths = saved[0][3] if len(saved[0]) > 3 else None
-    perm = saved[0][4] if len(saved[0]) > 4 else None
     G = [_gbuf(p_) for p_ in w]
     dx = None
     if need_dx:
         dx = dx_acc if dx_acc is not None else _empty(T * M, I, dev=dev)
-    tens = {'X': xf, 'DOUT': dout, 'LENGTHS': lengths, 'PERM': perm, 'DX': dx, 'SEG': saved[0][5] if len(saved[0]) > 5 else None}
-    n_scr = lib().ptv_row_gru_persist_scratch_elems(H, M)
+    tens = {'X': xf, 'DOUT': dout, 'LENGTHS': state.lengths, 'PERM': state.perm, 'DX': dx, 'SEG': state.seg}
     for d_ in range(2):
-        hall, gates, h16 = saved[d_][:3]
         pk = notes_packs(w[4 * d_], w[4 * d_ + 1], 0)
-        tens.update({'PK_WT%d' % d_: pk['wt'], 'HALL%d' % d_: hall, 'H16_%d' % d_: h16, 'GATES%d' % d_: gates, 'WT_IH%d' % d_: wt_ih[d_],
-                     'DGI%d' % d_: _empty(T, M, 3 * H, dev=dev, dtype=BF16), 'DGH%d' % d_: _empty(T, M, 3 * H, dev=dev, dtype=BF16),
-                     'SCRATCH%d' % d_: _empty(n_scr, dev=dev, dtype=BF16),
-                     'TOP%d' % d_: _ineg1(dev) if (lengths is not None and M % 32 == 0) else None})
+        dgi, dgh, scratch, top = _bigru_bwd_buffers(state, T, M, H, dev)
+        tens.update({'PK_WT%d' % d_: pk['wt'], 'HALL%d' % d_: state.hall[d_], 'H16_%d' % d_: state.h16[d_], 'GATES%d' % d_: state.gates[d_],
+                     'WT_IH%d' % d_: wt_ih[d_], 'DGI%d' % d_: dgi, 'DGH%d' % d_: dgh, 'SCRATCH%d' % d_: scratch, 'TOP%d' % d_: top})
     evs = _fork_events('BRB')
     arr_ = _BRB.pointers(tens, dict(zip(_BIGRU_G, G)),
                          handles={'FORK_EVENT': evs[0].cuda_event, 'JOIN_EVENT': evs[1].cuda_event, 'SIDE_STREAM': side.s.cuda_stream})
     darr_ = _BRB.dims({'M': M, 'T': T, 'H': H, 'I': I, 'DX_ACC': dx_acc is not None, 'DOUT_LD': dout.stride(0)})
     sp_ = stream_ptr()
-    rc = _defer_or_run('rows_bwd', (arr_, darr_, (tens, G, saved, dout, xf)), lambda: lib().ptv_bigru_rows_bwd(arr_, darr_, sp_))
+    rc = _defer_or_run('rows_bwd', (arr_, darr_, (tens, G, state, dout, xf)), lambda: lib().ptv_bigru_rows_bwd(arr_, darr_, sp_))
     _SIDE_DEPTH[1] = 1
     if rc == -3:                          # (H = I = 128 was checked above: ptv_bigru_rows_bwd's only refusal)
         raise RuntimeError('ptv_bigru_rows_bwd refused a configuration its Python-side checks accepted')
@@ -1151,18 +1191,17 @@ def _bigru_rows_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, sid
 
 
 def _bigru_fwd_composite(prec, xf, lengths, w, w16, out, T, M, I, H, dev):
-    """-> _bigru_forward's result when ptv_bigru_final_fwd ran its persistent branch, else None"""
+    """-> the 'persist' BiGruState when ptv_bigru_final_fwd ran its persistent branch, else None"""
     wih16 = [_W(w[0], prec), _W(w[4], prec)]
     if (torch.cuda.is_current_stream_capturing() or xf.dtype not in (F32, BF16) or xf.stride(1) != 1 or xf.stride(0) != I
             or wih16[0].dtype != wih16[1].dtype or not wih16[0].is_contiguous() or not wih16[1].is_contiguous()):
         return None
     dims = {'M': M, 'T': T, 'H': H, 'I': I, 'X_BF16': _bf(xf), 'WIH_F32': wih16[0].dtype == F32}
-    saved = []
+    dirs = []
     tens = {'X': xf, 'LENGTHS': lengths, 'OUT': out, 'SYNC': _persist_sync(2, dev)}
     for d_ in range(2):
-        hall, h16 = _empty(T + 1, M, H, dev=dev), _empty(T + 1, M, H, dev=dev, dtype=BF16)
-        gates = _empty(T, 4, M, H, dev=dev, dtype=BF16)
-        saved.append((hall, gates, h16))
+        hall, gates, h16 = _bigru_fwd_buffers(T, M, H, dev, BF16, False)
+        dirs.append((hall, gates, h16))
         tens.update({'W16_IH%d' % d_: wih16[d_], 'B_IH%d' % d_: w[4 * d_ + 2], 'W16_HH%d' % d_: w16[d_], 'B_HH%d' % d_: w[4 * d_ + 3],
                      'GI%d' % d_: _empty(T * M, 3 * H, dev=dev, dtype=BF16), 'HALL%d' % d_: hall, 'H16_%d' % d_: h16, 'GATES%d' % d_: gates,
                      'XCH%d' % d_: torch.empty((T + 1) * M * H, device=dev, dtype=BF16)})
@@ -1175,61 +1214,52 @@ def _bigru_fwd_composite(prec, xf, lengths, w, w16, out, T, M, I, H, dev):
     check(rc, 'ptv_bigru_final_fwd')
     turn.taken()
     _BGF.count()
-    return out, saved
+    return BiGruState('persist', dirs)
 
 
 def _bigru_forward(prec, x3, lengths, w):
     """x3 [T,M,I] step-major.  w = (w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r).
-    Returns out [M,2H] and the saved state for backward.  The two directions are independent
+    Returns out [M,2H] and the BiGruState for backward.  The two directions are independent
     chains: the reverse one runs on a sibling stream."""
     T, M, I = x3.shape
     H = w[1].shape[1]
     dev = x3.device
     xf = x3.reshape(T * M, I)
     out = _empty(M, 2 * H, dev=dev)
-
-    def direction(d):
-        w_ih, w_hh, b_ih, b_hh = w[4 * d: 4 * d + 4]
-        gi = gemm(xf, _W(w_ih, prec), bias=b_ih, prec=prec, out_dtype=_act_dtype(prec, H))          # [T*M, 3H]
-        hall = _empty(T + 1, M, H, dev=dev)
-        hall[0].zero_()
-        h16 = _hall16(prec, T + 1, M, H, dev)
-        gates = _empty(T, 4, M, H, dev=dev, dtype=_act_dtype(prec, H))
-        gru_fwd(prec, gi, M * 3 * H, 3 * H, w_hh, b_hh, hall, gates, lengths=lengths, reverse=bool(d), hall16=h16)
-        copy2d(out[:, d * H:(d + 1) * H], hall[T])
-        return hall, gates, h16
-
     adt = _act_dtype(prec, H)
     w16 = [_W(w[1], prec), _W(w[5], prec)]
-    if prec == 1 and T >= 2 and adt == BF16 and w16[0].dtype == BF16 and w16[1].dtype == BF16 and persist_supported(2, M, H, T):
+    branch = _bigru_branch(prec, x3, w16, adt, T, M, I, H)
+
+    def gi_of(d):
+        return gemm(xf, _W(w[4 * d], prec), bias=w[4 * d + 2], prec=prec, out_dtype=adt)            # [T*M, 3H]
+
+    if branch == 'persist':
         # both directions in ONE persistent launch (csrc/gru_persist.hip): per step the two chains share the exchange latency
         if BIGRU_BWD_COMPOSITE:
-            res = _bigru_fwd_composite(prec, xf, lengths, w, w16, out, T, M, I, H, dev)
-            if res is not None:
-                return res
-        chains, saved = [], []
+            state = _bigru_fwd_composite(prec, xf, lengths, w, w16, out, T, M, I, H, dev)
+            if state is not None:
+                return out, state
+        chains, dirs = [], []
         for d in range(2):
-            w_ih, w_hh, b_ih, b_hh = w[4 * d: 4 * d + 4]
-            gi = gemm(xf, _W(w_ih, prec), bias=b_ih, prec=prec, out_dtype=adt)
-            hall = _empty(T + 1, M, H, dev=dev)
-            hall[0].zero_()
-            h16 = _hall16(prec, T + 1, M, H, dev)
-            gates = _empty(T, 4, M, H, dev=dev, dtype=adt)
-            chains.append(dict(gi=gi, gi_step=M * 3 * H, gi_ld=3 * H, w16=w16[d], b_hh=b_hh, hall=hall, hall16=h16, gates=gates,
+            gi = gi_of(d)
+            hall, gates, h16 = _bigru_fwd_buffers(T, M, H, dev, adt, True)
+            chains.append(dict(gi=gi, gi_step=M * 3 * H, gi_ld=3 * H, w16=w16[d], b_hh=w[4 * d + 3], hall=hall, hall16=h16, gates=gates,
                                lengths=lengths, reverse=bool(d)))
-            saved.append((hall, gates, h16))
+            dirs.append((hall, gates, h16))
         gru_persist_fwd(M, H, T, chains)
         for d in range(2):
-            copy2d(out[:, d * H:(d + 1) * H], saved[d][0][T])
-        return out, saved
+            copy2d(out[:, d * H:(d + 1) * H], dirs[d][0][T])
+        return out, BiGruState('persist', dirs)
 
     zero_skip_sync()
-    if row_gru_ok(prec, H, I, M, adt) and x3.dtype == F32:
+    side = Side(BIGRU_SLOT)
+    skip_by, perm, seg = None, None, None
+    if branch == 'rows':
         # many short independent rows (dec_notes_emb_gru: 32*B rows x 16 notes): row-partitioned persistent kernels, one launch per
         # direction for the whole sequence (csrc/notes_persist.hip), input product fused; the directions overlap on sibling streams
         # (optional) rows sorted by length: a 64-row panel then holds rows of (almost) one length and passes over the steps that are masked
         # for ALL of them -- in row order a panel's longest row is nearly always the longest of the batch
-        perm, seg = None, None
+        skip_by = lengths if ZERO_SKIP else None         # (the backward must skip the same fully masked panel steps, with the same row order)
         if lengths is not None and ZERO_SKIP and SORT_ROWS and T <= 38:
             perm = torch.empty(M, device=dev, dtype=torch.int32)
             call('ptv_rows_by_length', ptr(lengths), ptr(perm), M, T, stream_ptr())
@@ -1239,45 +1269,41 @@ def _bigru_forward(prec, x3, lengths, w):
                 call('ptv_gather_rows', ptr(len_s), ptr(lengths), ptr(perm), M, 1, 0, 0, 1, stream_ptr())
                 seg = torch.empty(T, device=dev, dtype=torch.int32)
                 call('ptv_rows_seg_counts', ptr(len_s), M, T, ptr(seg), stream_ptr())
+        if BIGRU_BWD_COMPOSITE:
+            state = _bigru_rows_fwd_composite(x3, lengths, skip_by, perm, seg, w, out, side, T, M, I, H, dev)
+            if state is not None:
+                return out, state
 
-        def rows(d):
+        def run(d):
             w_ih, w_hh, b_ih, b_hh = w[4 * d: 4 * d + 4]
             pk = notes_packs(w_ih, w_hh, 0)
-            hall = _empty(T + 1, M, H, dev=dev)
-            hall[0].zero_()
-            h16 = _empty(T + 1, M, H, dev=dev, dtype=BF16)
-            gates = _empty(T, 4, M, H, dev=dev, dtype=BF16)
+            hall, gates, h16 = _bigru_fwd_buffers(T, M, H, dev, BF16, True)
             call('ptv_row_gru_persist_fwd_perm', H, ptr(pk['wg_h']), ptr(pk['wg_t']), ptr(b_hh), ptr(b_ih), None, ptr(x3), M * I,
                  ptr(lengths) if lengths is not None else None, ptr(perm), ptr(hall), ptr(h16), ptr(gates), out.data_ptr() + 4 * d * H,
                  2 * H, M, T, d, stream_ptr())
-            # (the backward must skip the same fully masked panel steps, with the same row order)
-            return hall, gates, h16, (lengths if ZERO_SKIP else None), perm, seg
-        side = Side(BIGRU_SLOT)
-        if BIGRU_BWD_COMPOSITE:
-            res = _bigru_rows_fwd_composite(x3, lengths, perm, w, out, side, T, M, I, H, dev, seg)
-            if res is not None:
-                return res
-        rev = side(lambda: rows(1), x3, out)
-        fwd = rows(0)
-        side.join()
-        return out, [fwd, rev]
-
-    side = Side(BIGRU_SLOT)
-    rev = side(lambda: direction(1), xf, out)
-    fwd = direction(0)
+            return hall, gates, h16
+    else:
+        def run(d):
+            gi = gi_of(d)
+            hall, gates, h16 = _bigru_fwd_buffers(T, M, H, dev, adt, True)
+            gru_fwd(prec, gi, M * 3 * H, 3 * H, w[4 * d + 1], w[4 * d + 3], hall, gates, lengths=lengths, reverse=bool(d), hall16=h16)
+            copy2d(out[:, d * H:(d + 1) * H], hall[T])
+            return hall, gates, h16
+    rev = side(lambda: run(1), x3, out)
+    fwd = run(0)
     side.join()
-    return out, [fwd, rev]
+    return out, BiGruState(branch, [fwd, rev], skip_by, perm, seg)
 
 
 BIGRU_BWD_COMPOSITE = os.environ.get('PTV_BWD_COMPOSITES', '1') != '0'    # the encoders' bi-GRU backward through ptv_bigru_final_bwd (one C call)
 
 
-def _bigru_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, wts, side, T, M, I, H):
-    """-> _bigru_backward's result when ptv_bigru_final_bwd ran its persistent branch, else None"""
+def _bigru_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, wts, side, T, M, I, H):
+    """-> _bigru_backward's result when ptv_bigru_final_bwd took the 'persist' BiGruState `state` back through its persistent branch,
+    else None"""
     dev = x3.device
     if (T * M < 512 or not OVERLAP or side.s == side.main or torch.cuda.is_current_stream_capturing() or xf.stride(1) != 1
-            or xf.stride(0) != I or xf.dtype not in (F32, BF16) or dout.dtype != F32 or dout.stride(1) != 1 or dout.stride(0) != 2 * H
-            or any(sv[0].dtype != F32 or sv[2] is None or sv[1].dtype != BF16 for sv in saved[:2])):
+            or xf.stride(0) != I or xf.dtype not in (F32, BF16) or dout.dtype != F32 or dout.stride(1) != 1 or dout.stride(0) != 2 * H):
         return None
     wt_ih = [_WT(w[0], prec), _WT(w[4], prec)] if need_dx else [None, None]
     if need_dx and (wt_ih[0] is None or wt_ih[1] is None):
@@ -1291,9 +1317,9 @@ def _bigru_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, wts, sid
     n_part = lib().ptv_gru_persist_part_elems(2, M, H, S) if S else 0
     tens = {'X': xf, 'DOUT': dout, 'DX': dx, 'SYNC': _persist_sync(2, dev)}
     for d_ in range(2):
-        hall, gates, h16 = saved[d_][:3]
-        tens.update({'HALL%d' % d_: hall, 'H16_%d' % d_: h16, 'GATES%d' % d_: gates, 'WT_HH%d' % d_: wts[d_], 'WT_IH%d' % d_: wt_ih[d_],
-                     'DGI%d' % d_: _empty(T, M, 3 * H, dev=dev, dtype=BF16), 'DGH%d' % d_: _empty(T, M, 3 * H, dev=dev, dtype=BF16),
+        dgi, dgh, _, _ = _bigru_bwd_buffers(state, T, M, H, dev)
+        tens.update({'HALL%d' % d_: state.hall[d_], 'H16_%d' % d_: state.h16[d_], 'GATES%d' % d_: state.gates[d_], 'WT_HH%d' % d_: wts[d_],
+                     'WT_IH%d' % d_: wt_ih[d_], 'DGI%d' % d_: dgi, 'DGH%d' % d_: dgh,
                      'XCH%d' % d_: torch.empty(T * M * 3 * H, device=dev, dtype=BF16),
                      'PART%d' % d_: torch.empty(n_part, device=dev) if S else None})
     evs = _fork_events('BGB')
@@ -1311,15 +1337,23 @@ def _bigru_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, wts, sid
     return G[0:4] + G[4:8], (dx.view(T, M, I) if need_dx else None)
 
 
-def _bigru_backward(prec, x3, w, saved, dout, need_dx, dx_acc=None, rev_slot=None):
-    """-> ([dw_ih, dw_hh, db_ih, db_hh] x 2 directions, dx [T,M,I] or None).
+def _bigru_backward(prec, x3, w, state, dout, need_dx, dx_acc=None, rev_slot=None):
+    """state: the forward's BiGruState -> ([dw_ih, dw_hh, db_ih, db_hh] x 2 directions, dx [T,M,I] or None).
     dx_acc ([T*M, I] fp32, or None): a gradient that already arrived at x3 from another consumer -- both directions' input-gradient
     products ACCUMULATE into it and it is returned as dx (round 4: autograd used to add the two consumers' 134-MB gradients of the note
     embedding with an ATen kernel, and the two directions' dx met in a copy kernel; now both are the accumulate mode of products that
     run anyway).  The second direction's dx product runs on the caller's stream after the join (its BPTT ran on the sibling stream)."""
     T, M, I = x3.shape
     H = w[1].shape[1]
+    dev = x3.device
     xf = x3.reshape(T * M, I)
+    branch = state.branch
+    if branch == 'rows' and not (NOTES_PERSIST and prec == 1 and BF16_STORAGE):
+        raise RuntimeError("bi-GRU backward: the forward ran on the row kernels (BiGruState.branch == 'rows') and they cannot run now "
+                           '(NOTES_PERSIST / bf16 precision): no other BPTT reads their gate layout')
+    wts = [_WT(w[1], prec), _WT(w[5], prec)]
+    if branch == 'persist' and not (wts[0] is not None and wts[1] is not None and persist_supported(2, M, H, T)):
+        branch = 'step'                   # (e.g. under a capture: states and gates are in the common layout, the per-step BPTT takes them)
     late = {}                                            # the second direction's (dgi, top) for its dx product after the join
 
     def dx_of(d, dgi2, top, first):
@@ -1329,82 +1363,54 @@ def _bigru_backward(prec, x3, w, saved, dout, need_dx, dx_acc=None, rev_slot=Non
             return gemm_dx(dgi2, w[4 * d], prec=prec, m_top=top, m_unit=M if top is not None else 0)
         return gemm_dx(dgi2, w[4 * d], out=dx_acc if first else late['dx'], acc=True, prec=prec, m_top=top, m_unit=M if top is not None else 0)
 
-    def direction(d):
-        w_ih, w_hh, b_ih, b_hh = w[4 * d: 4 * d + 4]
-        hall, gates, h16 = saved[d][:3]
-        dgi, dgh, _ = gru_bwd(prec, hall, gates, w_hh, dh_last=dout[:, d * H:(d + 1) * H], reverse=bool(d),
-                              need_dh0=False)
-        dgi2, dgh2 = dgi.view(T * M, 3 * H), dgh.view(T * M, 3 * H)
-        dw_ih, db_ih = wgrad_bias(dgi2, xf, _gbuf(w_ih), _gbuf(b_ih), prec)
-        dw_hh, db_hh = wgrad_bias(dgh2, (h16 if h16 is not None else hall)[:T].view(T * M, H), _gbuf(w_hh), _gbuf(b_hh), prec)
-        if d:
-            late['dgi'], late['top'] = dgi2, None
-        return [dw_ih, dw_hh, db_ih, db_hh], (dx_of(0, dgi2, None, True) if d == 0 else None)
-
-    def products(d, dgi, dgh, top=None, with_dx=True):
+    def products(d, dgi, dgh, top=None):
         """top (device int, from the BPTT kernel): no row is longer than top + 1, so dgi (indexed by time) is zero after that time
         and dgh (indexed by processing step) after that step -- or, in the reversed direction, BEFORE step T - top - 1"""
         w_ih, w_hh, b_ih, b_hh = w[4 * d: 4 * d + 4]
-        hall, gates, h16 = saved[d][:3]
+        hall, h16 = state.hall[d], state.h16[d]
         dgi2, dgh2 = dgi.view(T * M, 3 * H), dgh.view(T * M, 3 * H)
         dw_ih, db_ih = wgrad_bias(dgi2, xf, _gbuf(w_ih), _gbuf(b_ih), prec, top, M)
-        seg = saved[d][5] if (len(saved[d]) > 5 and top is not None and h16 is not None and saved[d][4] is not None) else None
         dw_hh, db_hh = wgrad_bias(dgh2, (h16 if h16 is not None else hall)[:T].view(T * M, H), _gbuf(w_hh), _gbuf(b_hh), prec, top, M,
-                                  k_rev=T if d else 0, seg=seg, seg_period=-T if d else T)
+                                  k_rev=T if d else 0, seg=state.seg if top is not None else None, seg_period=-T if d else T)
         if d:
             late['dgi'], late['top'] = dgi2, top
-        return [dw_ih, dw_hh, db_ih, db_hh], (dx_of(0, dgi2, top, True) if (d == 0 and with_dx) else None)
+        return [dw_ih, dw_hh, db_ih, db_hh], (dx_of(0, dgi2, top, True) if d == 0 else None)
 
     side = Side(BIGRU_SLOT_BWD if rev_slot is None else rev_slot)
-    wts = [_WT(w[1], prec), _WT(w[5], prec)]
-    adt = _act_dtype(prec, H)
-    rows_branch = len(saved[0]) > 3 and saved[0][1].dtype == BF16 and saved[0][2] is not None
-    if _DEFER is not None and not (rows_branch and BIGRU_BWD_COMPOSITE and not (
-            T >= 2 and adt == BF16 and wts[0] is not None and wts[1] is not None and persist_supported(2, M, H, T))):
-        _defer_flush()                    # (only the row-kernel composite can be collected: everything else below launches at once)
-    if (T >= 2 and adt == BF16 and wts[0] is not None and wts[1] is not None and saved[0][1].dtype == BF16
-            and saved[0][2] is not None and persist_supported(2, M, H, T)):
+    res = None
+    if BIGRU_BWD_COMPOSITE and branch == 'rows':
+        res = _bigru_rows_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, side, T, M, I, H)
+    if res is None:
+        _defer_flush()                    # (only the row-kernel composite can be collected: whatever else runs launches at once)
+        if BIGRU_BWD_COMPOSITE and branch == 'persist':
+            res = _bigru_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, wts, side, T, M, I, H)
+    if res is not None:
+        return res
+    if branch == 'persist':
         # BPTT of both directions in ONE persistent launch, then the weight-gradient products of the two on sibling streams
-        if BIGRU_BWD_COMPOSITE:
-            res = _bigru_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, wts, side, T, M, I, H)
-            if res is not None:
-                return res
         chains = []
         for d in range(2):
-            hall, gates, h16 = saved[d][:3]
-            chains.append(dict(hall=hall, gates=gates, wt16=wts[d], dh_ext=None, dh_last=dout[:, d * H:(d + 1) * H],
-                               dgi=_empty(T, M, 3 * H, dev=x3.device, dtype=adt), dgh=_empty(T, M, 3 * H, dev=x3.device, dtype=adt),
-                               dh0=None, reverse=bool(d)))
+            dgi, dgh, _, _ = _bigru_bwd_buffers(state, T, M, H, dev)
+            chains.append(dict(hall=state.hall[d], gates=state.gates[d], wt16=wts[d], dh_ext=None, dh_last=dout[:, d * H:(d + 1) * H],
+                               dgi=dgi, dgh=dgh, dh0=None, reverse=bool(d)))
         gru_persist_bwd(M, H, T, chains)
-        g1, _ = side(lambda: products(1, chains[1]['dgi'], chains[1]['dgh']), xf, dout, chains[1]['dgi'], chains[1]['dgh'])
-        g0, dx0 = products(0, chains[0]['dgi'], chains[0]['dgh'])
-    elif (len(saved[0]) > 3 and saved[0][1].dtype == BF16 and saved[0][2] is not None):
-        # (a forward that ran on the row kernels -- a 4-entry saved state -- left its gates in their private unit-blocked layout, and with
-        # lengths the gates of skipped panel steps unwritten: same kernels back)
-        if BIGRU_BWD_COMPOSITE:
-            res = _bigru_rows_bwd_composite(prec, x3, xf, w, saved, dout, need_dx, dx_acc, side, T, M, I, H)
-            if res is not None:
-                return res
 
-        def rows(d):
-            w_ih, w_hh = w[4 * d], w[4 * d + 1]
-            hall, gates, h16 = saved[d][:3]
-            lengths = saved[d][3] if len(saved[d]) > 3 else None
-            perm = saved[d][4] if len(saved[d]) > 4 else None
-            pk = notes_packs(w_ih, w_hh, 0)
-            dgi = _empty(T, M, 3 * H, dev=x3.device, dtype=BF16)
-            dgh = _empty(T, M, 3 * H, dev=x3.device, dtype=BF16)
-            scratch = _empty(lib().ptv_row_gru_persist_scratch_elems(H, M), dev=x3.device, dtype=BF16)
-            top = _ineg1(x3.device) if (lengths is not None and M % 32 == 0) else None
-            call('ptv_row_gru_persist_bwd_perm', H, ptr(pk['wt']), ptr(hall), ptr(gates), None, dout.data_ptr() + 4 * d * H, dout.stride(0),
-                 ptr(lengths) if lengths is not None else None, ptr(perm), ptr(dgi), ptr(dgh), None, ptr(scratch), M, T, d, ptr(top),
-                 stream_ptr())
-            return products(d, dgi, dgh, top)
-        g1, _ = side(lambda: rows(1), xf, dout)
-        g0, dx0 = rows(0)
+        def bptt(d):
+            return chains[d]['dgi'], chains[d]['dgh'], None
+    elif branch == 'rows':
+        def bptt(d):
+            pk = notes_packs(w[4 * d], w[4 * d + 1], 0)
+            dgi, dgh, scratch, top = _bigru_bwd_buffers(state, T, M, H, dev)
+            call('ptv_row_gru_persist_bwd_perm', H, ptr(pk['wt']), ptr(state.hall[d]), ptr(state.gates[d]), None,
+                 dout.data_ptr() + 4 * d * H, dout.stride(0), ptr(state.lengths) if state.lengths is not None else None, ptr(state.perm),
+                 ptr(dgi), ptr(dgh), None, ptr(scratch), M, T, d, ptr(top), stream_ptr())
+            return dgi, dgh, top
     else:
-        g1, _ = side(lambda: direction(1), xf, dout)
-        g0, dx0 = direction(0)
+        def bptt(d):
+            return gru_bwd(prec, state.hall[d], state.gates[d], w[4 * d + 1], dh_last=dout[:, d * H:(d + 1) * H], reverse=bool(d),
+                           need_dh0=False)[:2] + (None,)
+    g1, _ = side(lambda: products(1, *bptt(1)), xf, dout)
+    g0, dx0 = products(0, *bptt(0))
     side.join()
     if need_dx:
         late['dx'] = dx_acc if dx_acc is not None else dx0

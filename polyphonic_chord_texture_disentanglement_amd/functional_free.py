@@ -20,7 +20,7 @@ import torch
 
 from . import functional as F_
 from ._lib import SlotTable, call, lib, ptr, stream_ptr
-from .functional import (DEC_PARAM_NAMES, Side, _bgrad, _bigru_backward, _empty, _eye2, _gbuf, _onehot2x5, _zeros,
+from .functional import (DEC_PARAM_NAMES, BiGruState, Side, _bgrad, _bigru_backward, _empty, _eye2, _gbuf, _onehot2x5, _zeros,
                          colsum, copy2d, gemm, gru_bwd, sum_steps)
 
 FREE_PARAM_NAMES = DEC_PARAM_NAMES + ['note_embedding.weight', 'note_embedding.bias']
@@ -538,8 +538,10 @@ class DecoderStepFn(torch.autograd.Function):
             dx_pred = None
             if st['XH'] is not None:
                 wE = [P['dec_notes_emb_gru.' + n] for n in EMB_GRU]
-                saved = [(st['XH'][d_], st['XG'][d_], st['XH16'][d_]) + ((st['plen'] if st['skipped'] else None,) if st['XH16'][d_] is not None else ()) for d_ in range(2)]
-                ge, dx_pred = _bigru_backward(prec, PRED, wE, saved, dxsp.view(R, 2 * He), True)
+                # (the batched recompute ran the row kernels -- they left bf16 states -- and skipped dead panel steps by plen)
+                state = BiGruState('rows' if st['XH16'][0] is not None else 'step', zip(st['XH'], st['XG'], st['XH16']),
+                                   lengths=st['plen'] if st['skipped'] else None)
+                ge, dx_pred = _bigru_backward(prec, PRED, wE, state, dxsp.view(R, 2 * He), True)
                 for n, gg in zip(EMB_GRU, ge):
                     G['dec_notes_emb_gru.' + n] = gg
                 F_._defer_or_run('copy', None, lambda: copy2d(dPRED.view(16 * R, E), dx_pred.view(16 * R, E), acc=True))

@@ -1163,3 +1163,68 @@ def test_fused_heads_kernels_vs_fp32_products_of_the_same_bf16_operands(M, top, 
         got = dn.view(16, M, 32).permute(1, 0, 2).reshape(M, 512) if blocked else dn.view(M, 512)
         assert (got.float() - dn_ref).abs().max() < 1.5e-2 * max(1.0, dn_ref.abs().max().item())
         assert (got[live:] == 0).all()
+
+
+@pytest.mark.parametrize('path', ['rows', 'rows-dense', 'persist', 'step'])
+def test_bigru_node_records_the_branch_it_ran_and_its_composites_equal_the_python_sequencing(path, monkeypatch):
+    """BiGruFinalFn on each of its kernel families, at the smallest shape that still selects the family: the forward's BiGruState names
+    the family (a quiet fall-back to a slower one would pass every parity test), the C composites run exactly when they are switched on,
+    and out, dx and the eight parameter gradients are the same bits with the composites on and off.  rows: the floor of row_gru_ok, sorted
+    panels with K segments, an empty and a full row (and once without lengths); persist: the smallest listed shape of
+    test_gru_persistent_kernels_vs_oracle_and_step_kernels that two chains fit and whose T * M reaches the backward composite's 512."""
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_
+    from polyphonic_chord_texture_disentanglement_amd.optim import FusedClipAdam
+    dev = _dev()
+    T, prec, branch = 3, 1, path.split('-')[0]
+    if branch == 'rows':
+        M, H, I = 4096, 128, 128
+        monkeypatch.setattr(F_, 'SORT_ROWS', True)
+    elif branch == 'persist':
+        listed = next(m.args[1] for m in test_gru_persistent_kernels_vs_oracle_and_step_kernels.pytestmark if m.args[0].startswith('NC,M,H'))
+        fit = [s for s in sorted({(c[1], c[2]) for c in listed}, key=lambda s: s[0] * s[1]) if F_.persist_supported(2, *s)]
+        M, H = next((s for s in fit if T * s[0] >= 512), (max(fit[0][0], -(-512 // T)), fit[0][1]))      # (none listed: more rows, T stays)
+        I = 64
+        assert F_.persist_supported(2, M, H) and T * M >= 512
+    else:
+        M, H, I, prec = 8, 16, 16, 0
+    g = torch.Generator().manual_seed(M + H)
+    k = 1.0 / np.sqrt(H)
+    U = lambda *s: ((torch.rand(*s, generator=g) * 2 - 1) * k)
+    w = [torch.nn.Parameter(U(*s).to(dev)) for _ in range(2) for s in ((3 * H, I), (3 * H, H), (3 * H,), (3 * H,))]
+    opt = FusedClipAdam(w, lr=1e-3)                             # (the bf16 weight shadows the persistent kernels and the composites read)
+    x = (torch.randn(T, M, I, generator=g) * 0.7).to(dev)
+    dout = (torch.randn(M, 2 * H, generator=g) * 0.3).to(dev)
+    lengths = None
+    if path != 'rows-dense':
+        lengths = torch.randint(0, T + 1, (M,), generator=g, dtype=torch.int32)
+        lengths[:2] = torch.tensor([0, T], dtype=torch.int32)
+        lengths = lengths.to(dev)
+    counters = {'rows': (F_._BRF, F_._BRB), 'persist': (F_._BGF, F_._BGB), 'step': ()}[branch]
+    res = {}
+    for comp in (True, False):
+        monkeypatch.setattr(F_, 'BIGRU_BWD_COMPOSITE', comp)
+        opt.zero_grad()
+        n0 = [c.get('calls', 0) for c in counters]
+        xd = x.clone().requires_grad_()
+        out = F_.BiGruFinalFn.apply(xd, lengths, prec, *w)
+        state = out.grad_fn.saved_state
+        assert state.branch == branch
+        if path == 'rows':
+            assert state.lengths.data_ptr() == lengths.data_ptr() and state.perm is not None and state.seg is not None
+        else:
+            assert state.perm is None and state.seg is None
+        out.backward(dout)
+        torch.cuda.synchronize()
+        assert [c.get('calls', 0) - n for c, n in zip(counters, n0)] == [int(comp)] * len(counters)
+        res[comp] = [out.detach().clone(), xd.grad.clone()] + [p.grad.clone() for p in w]
+        F_.persist_check()
+    for a, b in zip(res[True], res[False]):
+        assert torch.isfinite(a).all() and torch.equal(a, b)
+    if path == 'rows':
+        # the row kernels' gates are theirs alone: with the kernels switched off before the backward nothing else may read them
+        opt.zero_grad()
+        out = F_.BiGruFinalFn.apply(x.clone().requires_grad_(), lengths, prec, *w)
+        monkeypatch.setattr(F_, 'NOTES_PERSIST', False)
+        with pytest.raises(RuntimeError, match='row kernels'):
+            out.backward(dout)
+        torch.cuda.synchronize()

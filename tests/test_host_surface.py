@@ -298,3 +298,55 @@ def test_slot_table_fills_the_tables_of_every_composite_enum_pair(tag):
                 lambda: tab.pointers(handles={'COUNT': 1}), lambda: tab.dims({'NO_SUCH_SLOT': 1}), lambda: tab.dims({'COUNT': 1})):
         with pytest.raises(KeyError, match=name):
             bad()
+
+
+def test_bigru_state_refuses_what_its_backward_could_not_read():
+    """functional.BiGruState (what a bi-GRU forward leaves for its backward): the row and the persistent kernels save bf16 gates and bf16
+    states, K segments count rows in the order of a permutation, a permutation sorts by the lengths the kernels skip by -- every other
+    combination is refused at construction; what it holds stays within reach of _record_stream"""
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_
+    T, M, H = 3, 8, 16
+    t = lambda *s, dt=torch.float32: torch.empty(*s, device='meta', dtype=dt)
+    bf = torch.bfloat16
+    d16 = [(t(T + 1, M, H), t(T, 4, M, H, dt=bf), t(T + 1, M, H, dt=bf)) for _ in range(2)]
+    d32 = [(t(T + 1, M, H), t(T, 4, M, H), None) for _ in range(2)]
+    no_h16 = [d16[0], (d16[1][0], d16[1][1], None)]
+    f32_gates = [(d16[0][0], d32[0][1], d16[0][2]), d16[1]]
+    ints = lambda n: t(n, dt=torch.int32)
+    for branch in ('rows', 'persist'):
+        for dirs in (d32, no_h16, f32_gates):
+            with pytest.raises(ValueError, match=branch):
+                F_.BiGruState(branch, dirs)
+    with pytest.raises(ValueError, match='branch'):
+        F_.BiGruState('row', d16)
+    with pytest.raises(ValueError, match='seg'):
+        F_.BiGruState('rows', d16, lengths=ints(M), seg=ints(T))
+    with pytest.raises(ValueError, match='perm'):
+        F_.BiGruState('rows', d16, perm=ints(M))
+    with pytest.raises(ValueError, match='perm'):
+        F_.BiGruState('rows', d16, perm=ints(M), seg=ints(T))
+    s = F_.BiGruState('rows', d16, ints(M), ints(M), ints(T))
+    assert (s.branch, s.hall, s.gates, s.h16) == ('rows',) + tuple(zip(*d16))
+    assert F_.BiGruState('step', d32).h16 == (None, None) and F_.BiGruState('step', d16).lengths is None
+    assert F_.BiGruState('persist', iter(d16)).branch == 'persist' and F_.BiGruState('rows', d16).seg is None
+    # the row kernels switched off between forward and backward: refused before anything is launched (meta tensors: a launch would fail otherwise)
+    w = [t(*sh) for _ in range(2) for sh in ((3 * H, H), (3 * H, H), (3 * H,), (3 * H,))]
+    old, F_.NOTES_PERSIST = F_.NOTES_PERSIST, False
+    try:
+        with pytest.raises(RuntimeError, match='row kernels'):
+            F_._bigru_backward(1, t(T, M, H), w, s, t(M, 2 * H), True)
+    finally:
+        F_.NOTES_PERSIST = old
+    # (Side keeps the state alive and tells the caching allocator about it through _record_stream: all nine tensors must be within its reach)
+    seen = []
+
+    class Probe(torch.Tensor):
+        is_cuda = True
+
+        def record_stream(self, stream):
+            seen.append(self)
+    probe = lambda: torch.Tensor._make_subclass(Probe, torch.empty(1, dtype=bf))
+    dirs = [(probe(), probe(), probe()) for _ in range(2)]
+    extras = [probe(), probe(), probe()]
+    F_._record_stream(F_.BiGruState('rows', dirs, *extras), None)
+    assert {id(x) for x in seen} == {id(x) for x in extras + [x for d in dirs for x in d]}
