@@ -7,6 +7,7 @@ sees one contiguous matrix; API tensors are converted at the boundary (Transpose
 
 Reference call sites are cited per function (paths are into /root/reference).
 """
+import collections
 import contextlib
 import ctypes
 import os
@@ -1765,26 +1766,95 @@ def _eye2(dev):
 # The teacher-forced decoder forward behind ONE C entry point (ptv_decoder_tf_fwd, csrc/composite.hip): launch sequence, the persistent
 # launch's turn and the shape decisions in C++; this side allocates the tensors and fills the two tables.  0 = sequence the launches here.
 DEC_COMPOSITE = True
-# the note tokens' gradient product (194 us, not an input of the time BPTT) on the sibling stream instead of in front of the BPTT on the
-# chain: MEASURED SLOWER (9.0 vs 8.38 ms per step) -- the persistent time BPTT then starts earlier and runs beside more of the bulk
-# products, and a persistent grid with company loses more than the chain gained.  Off.
 CHD_COMPOSITE = True
 _DTF, _CDF = SlotTable('DTF'), SlotTable('CDF')
 
+DecoderSorted = collections.namedtuple('DecoderSorted', 'perm len NS16S TOK_S seg_n')      # a forward on length-sorted rows: see DecoderState
+DecoderPlan = collections.namedtuple('DecoderPlan', 'notes heads dur dur_kernel composite take_top sort')
 
-def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, B, R, E, He, Ht, Hn, Hd, NP):
+
+class DecoderState:
+    """What a PianoTree decoder forward leaves for its backward (a plain object: _record_stream and Side.keep walk its __dict__).
+    Geometry: B, R = 32 B, E, He, Ht, Hn, Hd, NP, prec.  Saved tensors: NS [33,B,Ht] / HN [16,R,Hn] / HD [6,15R,Hd] fp32 states and their
+    bf16 shadows NS16 / HN16 / HD16 (or None), z_in, TOKS, gates_t / gates_n / gates_d, pitch (the logits), idx (the fed duration tokens),
+    dur_tabs = (tab0, tab) of the duration GRU's input side.  The kernels that ran, which decide what can read the state back:
+      notes  'rows': csrc/notes_persist.hip, bf16 gates in that kernel pair's private layout beside HN16 | 'step': plane-ordered gates, gru_bwd
+      heads  'fused': csrc/heads.hip on bf16 states and row-padded logits | 'gemm': three products
+      dur    'fused16': csrc/dur.hip / dur_bwd.hip on HD16, fp32 HD[1:] never written, gates rebuilt (gates_d None) or bf16
+             'fused': csrc/dur_bwd.hip on fp32 states and saved bf16 gates | 'step': plane-ordered gates of any dtype, gru_bwd
+    live_top: the note step the whole chain stopped at (device int; rows beyond it are unwritten), sorted: a DecoderSorted when the rows
+    ran ordered by length (perm, len, the gathered NS16S / TOK_S, seg_n) -- both only with notes, heads and dur all fused."""
+
+    def __init__(self, dims, prec, notes, heads, dur, *, NS, NS16, z_in, TOKS, gates_t, HN, HN16, gates_n, pitch, HD, HD16, gates_d, idx,
+                 dur_tabs, live_top=None, sorted=None):
+        for kind, name, names in (('notes', notes, ('rows', 'step')), ('heads', heads, ('fused', 'gemm')), ('dur', dur, ('fused16', 'fused', 'step'))):
+            if name not in names:
+                raise ValueError('DecoderState: unknown %s branch %r' % (kind, name))
+        self.B, self.R, self.E, self.He, self.Ht, self.Hn, self.Hd, self.NP = dims
+        self.prec, self.notes, self.heads, self.dur = prec, notes, heads, dur
+        self.NS, self.NS16, self.z_in, self.TOKS, self.gates_t = NS, NS16, z_in, TOKS, gates_t
+        self.HN, self.HN16, self.gates_n, self.pitch = HN, HN16, gates_n, pitch
+        self.HD, self.HD16, self.gates_d, self.idx, self.dur_tabs = HD, HD16, gates_d, idx, dur_tabs
+        self.live_top, self.sorted = live_top, sorted
+        if notes == 'rows' and (gates_n is None or gates_n.dtype != BF16 or HN16 is None):
+            raise ValueError("DecoderState: notes branch 'rows' saves bf16 gates and bf16 states")
+        if heads == 'fused' and (HN16 is None or HD16 is None or pitch.stride(0) != _pad8(self.NP)):
+            raise ValueError("DecoderState: heads branch 'fused' reads bf16 states and row-padded logits")
+        if dur == 'fused16' and HD16 is None:
+            raise ValueError("DecoderState: dur branch 'fused16' keeps its states in HD16")
+        if gates_d is None and dur != 'fused16':
+            raise ValueError("DecoderState: gates_d is rebuilt by dur branch 'fused16' only")
+        if dur == 'fused' and gates_d.dtype != BF16:
+            raise ValueError("DecoderState: dur branch 'fused' saves bf16 gates")
+        if (sorted is not None or live_top is not None) and (notes, heads, dur) != ('rows', 'fused', 'fused16'):
+            raise ValueError('DecoderState: sorted rows and live_top need the whole chain to honour them (rows / fused / fused16)')
+        if sorted is not None and not isinstance(sorted, DecoderSorted):
+            raise ValueError('DecoderState: sorted is a DecoderSorted record')
+
+
+def _decoder_plan(prec, dims, P, w16, emb3, z, live, force_dur):
+    """the kernels one teacher-forced decoder forward runs on, decided once -> DecoderPlan: the DecoderState branch names, dur_kernel (the
+    fused forward kernel also serves fp32 storage, where it leaves a 'step' state), composite (ptv_decoder_tf_fwd can take the call),
+    take_top (live's dead-step limit is taken), sort (the composite runs on live's length-sorted rows).  P: the parameters by name, w16:
+    the six weights the composite reads as bf16 MFMA operands, as _W() hands them out"""
+    B, R, E, He, Ht, Hn, Hd, NP = dims
+    bf_n, bf_d = _act_dtype(prec, Hn) == BF16, _act_dtype(prec, Hd) == BF16              # HN16 / HD16 will exist
+    notes = 'rows' if notes_persist_ok(prec, Hn, E, _act_dtype(prec, Hn)) and emb3.dtype == F32 and emb3.is_contiguous() else 'step'
+    heads = 'fused' if heads_ok(prec, Hn, NP, Hd, bf_n or None, bf_d or None) else 'gemm'
+    dur_kernel = 'fused' if prec == 1 and Hd == 64 and FUSED_DUR else 'step'
+    dur = 'fused16' if dur_kernel == 'fused' and bf_d else 'step'
+    fused = (notes, heads, dur) == ('rows', 'fused', 'fused16')
+    # (not inside ANY graph capture: the persistent launch's turn is a raw event pair in the composite, and an event recorded before the
+    # capture must not be waited for inside it -- the launch-by-launch path's wait_event() knows which edges a capture may keep)
+    composite = (fused and not torch.cuda.is_current_stream_capturing() and all(w.dtype == BF16 for w in w16) and _act_dtype(prec, Ht) == BF16
+                 and z.dtype == F32 and persist_supported(1, B, Ht, 32))
+    # the dead-step limit is taken only when EVERY stage of the chain honours it (row kernel, fused heads, fused duration GRU and their
+    # backward halves): the generic heads / per-step duration GRU and their weight-gradient sums read every row, so rows an earlier
+    # launch leaves unwritten would meet zero gradients as NaN bit patterns (round-5 advice)
+    take_top = fused and live is not None
+    # (the backward composite is the only un-sorter: no sorted forward without it)
+    sort = (composite and live is not None and live.sort is not None and force_dur is None and DP_INPLACE
+            and decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P))
+    return DecoderPlan(notes, heads, dur, dur_kernel, composite, take_top, sort)
+
+
+def _decoder_tf_leave(ctx, state, z, emb, params, live):
+    """what every teacher-forced forward leaves on its node"""
+    ctx.save_for_backward(z, emb, *params)
+    # (see _EMB_LINK: only when the summaries really are a function of this very embedding and will receive a gradient from this node)
+    ctx.emb_link = _EMB_LINK.get(emb.data_ptr()) if (ctx.needs_input_grad[2] and ctx.needs_input_grad[1] and emb.is_contiguous()) else None
+    ctx.saved_state = state
+    if live is not None:
+        live.record_order(state.sorted is not None)            # (the loss node takes its targets in the same row order)
+    ctx.mark_non_differentiable(state.idx)
+
+
+def _decoder_tf_composite(ctx, plan, z, emb, xs, force_dur, live, prec, P, w16, params, dims):
     """-> the node's outputs when ptv_decoder_tf_fwd ran (ctx then holds exactly what the launch-by-launch path leaves on it), else None"""
+    B, R, E, He, Ht, Hn, Hd, NP = dims
     dev = z.device
     emb3 = emb.view(16, R, E)
-    w16 = [W[n] for n in ('z2dec_hid_linear.weight', 'z2dec_in_linear.weight', 'dec_time_gru.weight_ih_l0', 'dec_time_gru.weight_hh_l0',
-                          'dec_time_to_notes_hid.weight', 'dec_notes_gru.weight_ih_l0')]
-    # (not inside ANY graph capture: the persistent launch's turn is a raw event pair here, and an event recorded before the capture
-    # must not be waited for inside it -- the launch-by-launch path's wait_event() knows which edges a capture may keep)
-    if (prec != 1 or not BF16_STORAGE or torch.cuda.is_current_stream_capturing() or any(w.dtype != BF16 for w in w16) or emb3.dtype != F32
-            or not emb3.is_contiguous() or not FUSED_DUR or not HEADS_FUSED or not NOTES_PERSIST or _act_dtype(prec, Ht) != BF16
-            or z.dtype != F32 or not persist_supported(1, B, Ht, 32)):
-        return None
-    Zs, Zi = z.shape[1], W['z2dec_in_linear.weight'].shape[0]
+    Zs, Zi = z.shape[1], P['z2dec_in_linear.weight'].shape[0]
     darr = _DTF.dims({'B': B, 'E': E, 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'NP': NP, 'ZS': Zs, 'ZI': Zi, 'LDP': _pad8(NP)})
     if not lib().ptv_decoder_tf_supported(darr):
         return None
@@ -1806,6 +1876,7 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, 
     sync = _persist_sync(1, dev)
     pk = notes_packs(P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0'], Ht)
     hp = heads_packs(P['pitch_out_linear.weight'], P['dur_hid_linear.weight'])
+    top = live.top if plan.take_top else None
     tens = {'Z': z, 'EMB': emb3, 'XS': xs, 'FORCE_DUR': force_dur,
             'B_ZHID': P['z2dec_hid_linear.bias'], 'B_ZIN': P['z2dec_in_linear.bias'], 'INIT_INPUT': P['dec_init_input'],
             'B_IH_T': P['dec_time_gru.bias_ih_l0'], 'B_HH_T': P['dec_time_gru.bias_hh_l0'], 'B_T2N': P['dec_time_to_notes_hid.bias'],
@@ -1817,17 +1888,15 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, 
             'PK_NOTES_H': pk['wg_h'], 'PK_NOTES_T': pk['wg_t'], 'PK_WP': hp['wp'], 'PK_WDH': hp['wdh'], 'PK_WDP': hp['wdp'],
             'NS': NS, 'NS16': NS16, 'Z_IN': z_in, 'TOKS': TOKS, 'GI_T': gi_t, 'ZG': zg, 'GATES_T': gates_t, 'HN': HN, 'HN16': HN16, 'GC': GC,
             'GATES_N': gates_n, 'PITCH': pitch, 'HD': HD, 'HD16': HD16, 'TAB0': tab0, 'TAB': tab, 'GATES_D': gates_d, 'DUR': dur, 'IDX': idx,
-            'XCH': xch, 'SYNC': sync, 'LIVE_TOP': live.top if live is not None else None}
-    srt = live.sort if live is not None else None
-    if srt is not None and not (force_dur is None and decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P)):
-        srt = None                                            # (the backward composite is the only un-sorter: no sorted forward without it)
-    if srt is not None:
-        tens.update(PERM=srt['perm'], ROW_LEN=srt['len'], NS16S=_empty(R, Ht, dev=dev, dtype=BF16), TOK_S=_empty(15, R, E, dev=dev), SEG_N=srt.get('seg_n'))
-    top = tens['LIVE_TOP']
+            'XCH': xch, 'SYNC': sync, 'LIVE_TOP': top}
+    srt = None
+    if plan.sort:
+        srt = DecoderSorted(live.sort['perm'], live.sort['len'], _empty(R, Ht, dev=dev, dtype=BF16), _empty(15, R, E, dev=dev), live.sort.get('seg_n'))
+        tens.update(PERM=srt.perm, ROW_LEN=srt.len, NS16S=srt.NS16S, TOK_S=srt.TOK_S, SEG_N=srt.seg_n)
     if top is not None and POISON_DEAD_STEPS:
         _poison(HN16, gates_n, pitch, HD, HD16, gates_d, dur, idx)
-        if srt is not None and srt.get('seg_n') is not None:
-            _poison(tens['TOK_S'])                            # (gathered for the live blocks only: nobody may read the rest)
+        if srt is not None and srt.seg_n is not None:
+            _poison(srt.TOK_S)                                # (gathered for the live blocks only: nobody may read the rest)
     turn = _CompositeTurn(cur_stream())
     slots = _DTF.pointers(tens, handles=turn.handles)
     _chain_prio()
@@ -1838,18 +1907,12 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, 
     check(rc, 'ptv_decoder_tf_fwd')
     turn.taken()
     mark('dec_fwd:heads')
-    ctx.save_for_backward(z, emb, *params)
-    ctx.emb_link = _EMB_LINK.get(emb.data_ptr()) if (ctx.needs_input_grad[2] and ctx.needs_input_grad[1] and emb.is_contiguous()) else None
-    ctx.st = dict(B=B, R=R, E=E, He=He, Ht=Ht, Hn=Hn, Hd=Hd, NP=NP, prec=prec, NS=NS, z_in=z_in, NS16=NS16, HN16=HN16, HD16=HD16,
-                  TOKS=TOKS, gates_t=gates_t, HN=HN, gates_n=gates_n, gates_n_rowk=True, pitch=pitch, HD=HD, gates_d=gates_d, idx=idx,
-                  dur_tabs=(tab0, tab), dur16_only=True, live_top=top)
-    if live is not None:
-        live.record_order(srt is not None)                    # (the loss node takes its targets in the same row order)
+    _decoder_tf_leave(ctx, DecoderState(dims, prec, plan.notes, plan.heads, plan.dur, NS=NS, NS16=NS16, z_in=z_in, TOKS=TOKS, gates_t=gates_t,
+                                        HN=HN, HN16=HN16, gates_n=gates_n, pitch=pitch, HD=HD, HD16=HD16, gates_d=gates_d, idx=idx,
+                                        dur_tabs=(tab0, tab), live_top=top, sorted=srt), z, emb, params, live)
     if srt is not None:
-        ctx.st['sorted'] = dict(perm=srt['perm'], len=srt['len'], NS16S=tens['NS16S'], TOK_S=tens['TOK_S'], seg_n=srt.get('seg_n'))
         _DTF.count('sorted_calls')
     _DTF.count()
-    ctx.mark_non_differentiable(idx)
     # (returned, never stored on ctx: outputs referenced from their own grad_fn are a cycle that only the garbage collector frees -- at an
     # arbitrary later moment, e.g. inside a graph capture, where releasing blocks that other streams used records events and kills the capture)
     return pitch.view(15, 32, B, NP), dur, idx
@@ -1858,7 +1921,8 @@ def _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, 
 class DecoderTFFn(torch.autograd.Function):
     """(z [B,Zs], emb step-major [16,32,B,E], xs [32B, 2He] ground-truth note summaries (BiGruFinalFn over
     emb, ptvae.py:446-453), force_dur_idx or None, live (loss()'s LiveRows plan) or None, prec, *params)
-    -> pitch logits step-major [15,32,B,130], dur logits [15*32*B, 5, 2], dur argmax indices"""
+    -> pitch logits step-major [15,32,B,130], dur logits [15*32*B, 5, 2], dur argmax indices; the forward's DecoderState is
+    `grad_fn.saved_state`"""
 
     @staticmethod
     def forward(ctx, z, emb, xs, force_dur, live, prec, *params):
@@ -1874,10 +1938,14 @@ class DecoderTFFn(torch.autograd.Function):
         Hn = W['dec_notes_gru.weight_hh_l0'].shape[1]
         Hd = W['dec_dur_gru.weight_hh_l0'].shape[1]
         NP = W['pitch_out_linear.weight'].shape[0]              # 130
-        S = ctx                                                  # stash everything on ctx
+        dims = (B, R, E, He, Ht, Hn, Hd, NP)
+        emb3 = emb.view(16, R, E)
+        w16 = [W[n] for n in ('z2dec_hid_linear.weight', 'z2dec_in_linear.weight', 'dec_time_gru.weight_ih_l0', 'dec_time_gru.weight_hh_l0',
+                              'dec_time_to_notes_hid.weight', 'dec_notes_gru.weight_ih_l0')]
+        plan = _decoder_plan(prec, dims, P, w16, emb3, z, live, force_dur)
 
-        if DEC_COMPOSITE:
-            outs = _decoder_tf_composite(ctx, z, emb, xs, force_dur, live, prec, P, W, params, B, R, E, He, Ht, Hn, Hd, NP)
+        if DEC_COMPOSITE and plan.composite:
+            outs = _decoder_tf_composite(ctx, plan, z, emb, xs, force_dur, live, prec, P, w16, params, dims)
             if outs is not None:
                 return outs
 
@@ -1887,7 +1955,6 @@ class DecoderTFFn(torch.autograd.Function):
         z_in = gemm(z, W['z2dec_in_linear.weight'], bias=P['z2dec_in_linear.bias'], prec=prec)
 
         mark('dec_fwd:start')
-        emb3 = emb.view(16, R, E)
         xs = xs.contiguous()
 
         # --- time GRU inputs: token_t = [init ; xs[t-1]], z_in broadcast over t  (ptvae.py:457-462,476-478)
@@ -1911,26 +1978,20 @@ class DecoderTFFn(torch.autograd.Function):
         gemm(NSf_op, W['dec_time_to_notes_hid.weight'], HN[0], bias=P['dec_time_to_notes_hid.bias'], prec=prec)
         w_ih_n = W['dec_notes_gru.weight_ih_l0']
         adt = _act_dtype(prec, Hn)
-        rowk = notes_persist_ok(prec, Hn, E, adt) and emb3.dtype == F32 and emb3.is_contiguous()
+        rows = plan.notes == 'rows'
         # (the row kernel reads the hoisted part column-blocked by 16: one contiguous kilobyte per wave access instead of half cache lines)
-        GC = gemm(NSf_op, w_ih_n[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec, out_dtype=adt, out_blocked=16 if rowk else False)      # [R, 3Hn]
+        GC = gemm(NSf_op, w_ih_n[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec, out_dtype=adt, out_blocked=16 if rows else False)      # [R, 3Hn]
         gates_n = _empty(15, 4, R, Hn, dev=dev, dtype=adt)
         HN16 = _hall16(prec, 16, R, Hn, dev)
-        gates_n_rowk = rowk
-        if rowk:
+        top = live.top if plan.take_top else None               # (taken by every stage below, or by none)
+        if rows:
             # ONE launch for the 15 note steps, 64 rows per workgroup, token product fused (csrc/notes_persist.hip)
             pk = notes_packs(P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0'], Ht)
-            # the dead-step limit is taken only when EVERY later stage of the chain honours it (fused heads, fused duration GRU with
-            # recomputed gates, and their backward halves): the generic heads / per-step duration GRU and their weight-gradient sums
-            # read every row, so rows this launch leaves unwritten would meet zero gradients as NaN bit patterns (round-5 advice)
-            chain_live = heads_ok(prec, Hn, NP, Hd, HN16, _act_dtype(prec, Hd) == BF16 or None) and prec == 1 and Hd == 64 and FUSED_DUR
-            top = live.top if (live is not None and chain_live) else None
             if top is not None and POISON_DEAD_STEPS:
                 _poison(HN16, gates_n)
             call('ptv_notes_gru_persist_fwd_top', ptr(pk['wg_h']), ptr(pk['wg_t']), ptr(P['dec_notes_gru.bias_hh_l0']), ptr(GC), ptr(emb3),
                  ptr(HN), ptr(HN16), ptr(gates_n), R, 15, ptr(top), stream_ptr())
         else:
-            top = None
             GT = gemm(emb3[:15].view(15 * R, E), w_ih_n[:, Ht:], prec=prec, out_dtype=adt)                    # [15R, 3Hn]
             gru_fwd(prec, GT, R * 3 * Hn, 3 * Hn, W['dec_notes_gru.weight_hh_l0'], P['dec_notes_gru.bias_hh_l0'], HN,
                     gates_n, gi2=GC, gi2_step=0, gi2_ld=3 * Hn, hall16=HN16)
@@ -1945,8 +2006,7 @@ class DecoderTFFn(torch.autograd.Function):
         pitch = _empty(M, _pad8(NP), dev=dev)[:, :NP]
         HD = _empty(6, M, Hd, dev=dev)
         HD16 = _hall16(prec, 6, M, Hd, dev)
-        fused_heads = heads_ok(prec, Hn, NP, Hd, HN16, HD16)
-        if fused_heads:
+        if plan.heads == 'fused':
             # ONE pass over the note summaries for both Linears; the logits feed the second product from LDS (csrc/heads.hip)
             hp = heads_packs(P['pitch_out_linear.weight'], P['dur_hid_linear.weight'])
             if top is not None and POISON_DEAD_STEPS:
@@ -1964,22 +2024,20 @@ class DecoderTFFn(torch.autograd.Function):
         w_ih_d, b_ih_d = W['dec_dur_gru.weight_ih_l0'], P['dec_dur_gru.bias_ih_l0']
         tab0 = gemm(P['dur_sos_token'].view(1, -1), w_ih_d, bias=b_ih_d, prec=0)       # [1, 3Hd]  (tiny: exact)
         tab = gemm(_onehot2x5(dev), w_ih_d, bias=b_ih_d, prec=0)                       # [2, 3Hd]
-        fused_dur = prec == 1 and Hd == 64 and FUSED_DUR
-        gates_d = None if (fused_dur and DUR_RECOMPUTE and HD16 is not None) else _empty(5, 4, M, Hd, dev=dev, dtype=_act_dtype(prec, Hd))
+        gates_d = None if (plan.dur == 'fused16' and DUR_RECOMPUTE) else _empty(5, 4, M, Hd, dev=dev, dtype=_act_dtype(prec, Hd))
         dur = _empty(M, 5, 2, dev=dev)
         idx = torch.empty(5, M, device=dev, dtype=torch.int32)
         dur2 = dur.view(M, 10)
-        if fused_dur:
+        if plan.dur_kernel == 'fused':
             # one kernel for the 5 steps + output layer + argmax feedback (dur.hip)
-            live_d = top                                    # (None unless the fused heads took the limit too: chain_live above)
-            if live_d is not None and POISON_DEAD_STEPS:
+            if top is not None and POISON_DEAD_STEPS:
                 _poison(gates_d, dur, idx)
             call('ptv_dur_gru_fwd_top', Hd, M, ptr(HD[0]), Hd, ptr(P['dec_dur_gru.weight_hh_l0']), ptr(P['dec_dur_gru.bias_hh_l0']),
                  ptr(tab0), ptr(tab), ptr(P['dur_out_linear.weight']), ptr(P['dur_out_linear.bias']),
                  None if HD16 is not None else ptr(HD[1]), M * Hd,          # fp32 states stay in registers when the bf16
                  ptr(HD16[1]) if HD16 is not None else None, ptr(gates_d), M * Hd, 4 * M * Hd, _bf(gates_d),   # copies exist
-                 ptr(dur2), 10, ptr(idx), M, ptr(force_dur) if force_dur is not None else None, M, ptr(live_d), R, stream_ptr())
-            if HD16 is not None and not fused_heads:
+                 ptr(dur2), 10, ptr(idx), M, ptr(force_dur) if force_dur is not None else None, M, ptr(top), R, stream_ptr())
+            if HD16 is not None and plan.heads != 'fused':
                 call('ptv_cast_bf16', ptr(HD[0]), ptr(HD16[0]), M * Hd, stream_ptr())       # slot 0 of the shadow
         else:
             for d in range(5):
@@ -1990,27 +2048,20 @@ class DecoderTFFn(torch.autograd.Function):
                      ptr(dur2[:, 2 * d:]), 10, ptr(idx[d]), ptr(force_dur[d]) if force_dur is not None else None, M,
                      stream_ptr())
 
-        S.save_for_backward(z, emb, *params)
-        # (see _EMB_LINK: only when the summaries really are a function of this very embedding and will receive a gradient from this node)
-        S.emb_link = _EMB_LINK.get(emb.data_ptr()) if (S.needs_input_grad[2] and S.needs_input_grad[1] and emb.is_contiguous()) else None
-        S.st = dict(B=B, R=R, E=E, He=He, Ht=Ht, Hn=Hn, Hd=Hd, NP=NP, prec=prec, NS=NS, z_in=z_in, NS16=NS16, HN16=HN16,
-                    HD16=HD16,
-                    TOKS=TOKS, gates_t=gates_t, HN=HN, gates_n=gates_n, gates_n_rowk=gates_n_rowk, pitch=pitch, HD=HD, gates_d=gates_d, idx=idx,
-                    dur_tabs=(tab0, tab), live_top=top,
-                    dur16_only=bool(prec == 1 and Hd == 64 and FUSED_DUR and HD16 is not None))   # HD[1:] never written
-        if live is not None:
-            live.record_order(False)
-        S.mark_non_differentiable(idx)
+        _decoder_tf_leave(ctx, DecoderState(dims, prec, plan.notes, plan.heads, plan.dur, NS=NS, NS16=NS16, z_in=z_in, TOKS=TOKS, gates_t=gates_t,
+                                            HN=HN, HN16=HN16, gates_n=gates_n, pitch=pitch, HD=HD, HD16=HD16, gates_d=gates_d, idx=idx,
+                                            dur_tabs=(tab0, tab), live_top=top), z, emb, params, live)
         return pitch.view(15, 32, B, NP), dur, idx
 
     @staticmethod
     def backward(ctx, dpitch, ddur, _didx):
         z, emb, *params = ctx.saved_tensors
         P = dict(zip(DEC_PARAM_NAMES, params))
-        st = ctx.st
-        ctx.st = None
-        R, E = st['R'], st['E']
-        dz, demb, dTOKS, G, side = decoder_bwd_core(P, st, z, emb.view(16, R, E)[:15].view(15 * R, E), dpitch, ddur)
+        state = ctx.saved_state
+        ctx.saved_state = None
+        B, R, E, He = state.B, state.R, state.E, state.He
+        res = decoder_bwd_core(P, state, z, emb.view(16, R, E)[:15].view(15 * R, E), dpitch, ddur)
+        dz, demb, dTOKS, G, side = res.dz, res.dtok, res.dTOKS, res.G, res.side
         mark('dec_bwd:end')
         # parameter gradients only: joined when the backward pass ends -- but only if autograd ADOPTS the tensors
         # (p.grad is None and the buffer is this step's arena view); an accumulation `p.grad += g` would run on this
@@ -2023,11 +2074,10 @@ class DecoderTFFn(torch.autograd.Function):
                 GRAD_READY_HOOK([P[n] for n in DEC_PARAM_NAMES if G[n] is not None], streams)
         else:
             side.join()
-        B, He = st['B'], st['He']
-        if st.get('ev_dtoks') is not None:
+        if res.ev_dtoks is not None:
             if len(_SUMMARY_EV) > 8:
                 _SUMMARY_EV.clear()
-            _SUMMARY_EV[dTOKS[1:].data_ptr()] = st['ev_dtoks']
+            _SUMMARY_EV[dTOKS[1:].data_ptr()] = res.ev_dtoks
         demb_out = demb.view(16, 32, B, E)
         if ctx.emb_link is not None and ctx.needs_input_grad[2] and demb.dtype == F32 and demb.is_contiguous():
             ctx.emb_link['demb'] = demb                   # the summary node accumulates into it and returns it (BiGruFinalFn.backward)
@@ -2052,39 +2102,38 @@ _DTB_G = tuple(('G_' + k, n) for k, n in (
 
 
 def decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P=None):
-    """what _decoder_bwd_composite will ask of the configuration (not of the gradients it is handed): a forward on length-sorted rows
-    commits the backward to the composite -- the only place that scatters the row order back"""
+    """what ptv_decoder_tf_bwd asks of the configuration -- the only statement of it: _decoder_bwd_composite adds the forward's
+    DecoderState and the gradients it is handed.  The forward asks before it sorts rows by length, which commits the backward to the
+    composite -- the only place that scatters the row order back.  P None: leave the transposed weight shadows out"""
     return (prec == 1 and ZERO_SKIP and OVERLAP and SUMMARY_FAMILY_SLOT < 0 and DEC_BWD_COMPOSITE and not torch.cuda.is_current_stream_capturing()
             and DUR_RECOMPUTE and HEADS_WGRAD_FUSED and HEADS_FUSED and BF16_STORAGE and (Hn, NP, Hd) == (512, 130, 64)
-            and notes_persist_ok(prec, Hn, E, BF16) and persist_supported(1, B, Ht, 32) and 15 * 32 * B * 5 >= 4096 and DP_INPLACE
+            and notes_persist_ok(prec, Hn, E, BF16) and persist_supported(1, B, Ht, 32)
+            and 15 * 32 * B * 5 >= 4096                   # (_bgrad's 64-column path, as in C)
             and (P is None or all(_WT(P[n], prec) is not None for n in (
                 'dec_notes_gru.weight_ih_l0', 'dec_time_to_notes_hid.weight', 'dec_time_gru.weight_ih_l0', 'dec_time_gru.weight_hh_l0',
                 'z2dec_hid_linear.weight', 'z2dec_in_linear.weight'))))
 
 
+DecoderGrads = collections.namedtuple('DecoderGrads', 'dz dtok dTOKS G side ev_dtoks')       # decoder_bwd_core's result
+
+
 def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
-    """-> decoder_bwd_core's result tuple when ptv_decoder_tf_bwd ran the whole sequence, else None (the caller sequences it: same bits)"""
-    B, R, E, He, Ht, Hn, Hd, NP, prec = (st[k] for k in ('B', 'R', 'E', 'He', 'Ht', 'Hn', 'Hd', 'NP', 'prec'))
+    """-> decoder_bwd_core's result when ptv_decoder_tf_bwd ran the whole sequence, else None (the caller sequences it: same bits)"""
+    B, R, E, He, Ht, Hn, Hd, NP, prec = st.B, st.R, st.E, st.He, st.Ht, st.Hn, st.Hd, st.NP, st.prec
     dev = z.device
     M = 15 * R
-    HN16, HD16, NS16, gates_n, gates_t = st.get('HN16'), st.get('HD16'), st.get('NS16'), st['gates_n'], st['gates_t']
-    if (prec != 1 or not ZERO_SKIP or not OVERLAP or SUMMARY_FAMILY_SLOT >= 0 or torch.cuda.is_current_stream_capturing()
-            or not st.get('dur16_only') or st['gates_d'] is not None or st.get('dur_tabs') is None or HD16 is None or HN16 is None
-            or NS16 is None or not st.get('gates_n_rowk') or gates_n.dtype != BF16 or gates_t.dtype != BF16 or not HEADS_WGRAD_FUSED
-            or not heads_ok(prec, Hn, NP, Hd, HN16, HD16) or not notes_persist_ok(prec, Hn, E, BF16)
+    # (every reason to decline is checked HERE, before a gradient buffer is taken from the arena: GradArena.take hands a view out once per
+    # step, a fallback after it would get fresh non-arena buffers and the deferred join would turn into a join -- round-5 advice)
+    if (not decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P)
+            or (st.notes, st.heads, st.dur) != ('rows', 'fused', 'fused16') or st.gates_d is not None or st.NS16 is None
             or dP.stride(0) != _pad8(NP) or dP.data_ptr() % 16 or not ddur.is_contiguous() or ddur.dtype != F32
-            or tok_op.dtype != F32 or not tok_op.is_contiguous() or z.dtype != F32 or not z.is_contiguous()
-            or not persist_supported(1, B, Ht, 32) or side.s == side.main or M * 5 < 4096):       # (M * 5 >= 4096: _bgrad's 64-column path, as in C)
+            or tok_op.dtype != F32 or not tok_op.is_contiguous() or z.dtype != F32 or not z.is_contiguous() or side.s == side.main):
         _defer_flush()
         return None
     wts = [_WT(P[n], prec) for n in ('dec_notes_gru.weight_ih_l0', 'dec_time_to_notes_hid.weight', 'dec_time_gru.weight_ih_l0',
                                       'dec_time_gru.weight_hh_l0', 'z2dec_hid_linear.weight', 'z2dec_in_linear.weight')]
-    # (every reason to decline is checked HERE, before a gradient buffer is taken from the arena: GradArena.take hands a view out once per
-    # step, a fallback after it would get fresh non-arena buffers and the deferred join would turn into a join -- round-5 advice)
-    if any(w is None for w in wts) or st['pitch'].stride(0) != _pad8(NP) or st['idx'].dtype != torch.int32:
-        _defer_flush()
-        return None
-    Zs, Zi = z.shape[1], st['z_in'].shape[1]
+    HN16, HD16, NS16, gates_n, gates_t = st.HN16, st.HD16, st.NS16, st.gates_n, st.gates_t
+    Zs, Zi = z.shape[1], st.z_in.shape[1]
     S = persist_splitk(1, B, Ht)
     nblk = min(256, (M + 63) // 64)
     psz = lib().ptv_dur_gru_bwd_part_size()
@@ -2094,13 +2143,13 @@ def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
     for _, n in _DTB_G:
         G[n] = _gbuf(P[n])
     dz, dtok, dTOKS = _empty(B, Zs, dev=dev), _empty(16, R, E, dev=dev), _empty(33, B, 2 * He, dev=dev)
-    tab0, tab = st['dur_tabs']
+    tab0, tab = st.dur_tabs
     tens = {'Z': z, 'TOK_OP': tok_op, 'DP': dP, 'DDUR': ddur, 'TOP_H': top_h,
             'W_HH_D': P['dec_dur_gru.weight_hh_l0'], 'B_HH_D': P['dec_dur_gru.bias_hh_l0'], 'W_IH_D': P['dec_dur_gru.weight_ih_l0'],
             'W_OUT_D': P['dur_out_linear.weight'], 'SOS': P['dur_sos_token'], 'PK_WDPT': hp['wdpT'], 'PK_WCAT': hp['wcat'],
             'PK_NOTES_WT': pk['wt'], 'WT_IH_N': wts[0], 'WT_T2N': wts[1], 'WT_IH_T': wts[2], 'WT_HH_T': wts[3], 'WT_ZHID': wts[4],
-            'WT_ZIN': wts[5], 'NS': st['NS'], 'NS16': NS16, 'Z_IN': st['z_in'], 'TOKS': st['TOKS'], 'GATES_T': gates_t, 'HN16': HN16,
-            'GATES_N': gates_n, 'PITCH': st['pitch'], 'HD16': HD16, 'TAB0': tab0, 'TAB': tab, 'IDX': st['idx'],
+            'WT_ZIN': wts[5], 'NS': st.NS, 'NS16': NS16, 'Z_IN': st.z_in, 'TOKS': st.TOKS, 'GATES_T': gates_t, 'HN16': HN16,
+            'GATES_N': gates_n, 'PITCH': st.pitch, 'HD16': HD16, 'TAB0': tab0, 'TAB': tab, 'IDX': st.idx,
             'DZ': dz, 'DTOK': dtok, 'DTOKS': dTOKS,
             'DHD0': _empty(M, Hd, dev=dev), 'PART': _empty(nblk, psz, dev=dev), 'S': _zeros(1, psz, dev=dev), 'TMP64': _zeros(1, 64, dev=dev),
             'DNSUM': _empty(M, Hn, dev=dev, dtype=BF16), 'DY16': _empty(M, 200, dev=dev, dtype=BF16), 'TMP200': _empty(200, Hn, dev=dev),
@@ -2112,11 +2161,11 @@ def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
             'XCH': torch.empty(32 * B * 3 * Ht, device=dev, dtype=BF16),
             'PART_T': torch.empty(lib().ptv_gru_persist_part_elems(1, B, Ht, S), device=dev) if S else None,
             'SYNC': _persist_sync(1, dev)}
-    srt = st.get('sorted')
+    srt = st.sorted
     if srt is not None:                                   # the forward ran on length-sorted rows: operands in that order, dNS / dtok scattered back
-        tens.update(PERM=srt['perm'], ROW_LEN=srt['len'], NS16S=srt['NS16S'], TOK_OP=srt['TOK_S'].view(M, E), DNS_S=_empty(R, Ht, dev=dev),
-                    DTOK_S=_empty(15, R, E, dev=dev), SEG_N=srt.get('seg_n'))
-    if POISON_DEAD_STEPS and top_h is not None and st.get('live_top') is not None:        # (tests: whatever reads a dead row of these gets NaN -- heads_bwd / the BPTT leave them unwritten)
+        tens.update(PERM=srt.perm, ROW_LEN=srt.len, NS16S=srt.NS16S, TOK_OP=srt.TOK_S.view(M, E), DNS_S=_empty(R, Ht, dev=dev),
+                    DTOK_S=_empty(15, R, E, dev=dev), SEG_N=srt.seg_n)
+    if POISON_DEAD_STEPS and top_h is not None and st.live_top is not None:        # (tests: whatever reads a dead row of these gets NaN -- heads_bwd / the BPTT leave them unwritten)
         _poison(tens['DNSUM'], tens['DGI_N'], tens['DGH_N'], tens['DY16'])
     evs = _fork_events('DTB', 4)
     turn = _CompositeTurn(cur_stream())
@@ -2135,33 +2184,35 @@ def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
     check(rc, 'ptv_decoder_tf_bwd')
     turn.taken()
     _DTB.count()
-    st['ev_dtoks'] = None
     # the sibling stream's products are queued, not run: everything they read or write stays referenced until the join (the caller defers
     # it to the end of the backward pass) -- EXCEPT the gradient buffers (a second reference makes AccumulateGrad clone them)
     side.used = True
     side.keep.extend([v for k, v in tens.items() if v is not None] + [st, z, tok_op])
-    return dz, dtok, dTOKS, G, side
+    return DecoderGrads(dz, dtok, dTOKS, G, side, None)
 
 
 def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
-    """BPTT of the PianoTree decoder given the saved forward state `st` -- shared by the teacher-forced node (DecoderTFFn) and
+    """BPTT of the PianoTree decoder given the forward's DecoderState `st`, whose branch names select the code below -- shared by the teacher-forced node (DecoderTFFn) and
     the step-loop node (functional_free.DecoderStepFn: argmax is not differentiable, so with the fed tokens recorded every
     chain is the same batched BPTT).  Chain (duration GRU -> heads -> notes GRU -> time GRU -> z) on the caller's stream; every
     weight / bias gradient product is enqueued on a sibling stream as soon as its operands exist, so the K-deep dW GEMMs
     overlap the latency-bound recurrent steps.
       tok_op [15*R, E]: the note tokens that were FED to the notes GRU (ground-truth embedding rows, or the recorded mix)
-    -> (dz, dtok [16,R,E] gradient w.r.t. the fed note tokens (slot 15 zero), dTOKS [33,B,2He] gradient w.r.t. the time-step
-        tokens, G parameter gradients by name, side stream handle -- the caller joins or defers it)"""
-    B, R, E, He, Ht, Hn, Hd, NP, prec = (st[k] for k in ('B', 'R', 'E', 'He', 'Ht', 'Hn', 'Hd', 'NP', 'prec'))
-    W = P                                             # K-major (dX) products read the fp32 weights
+    -> DecoderGrads(dz, dtok [16,R,E] gradient w.r.t. the fed note tokens (slot 15 zero), dTOKS [33,B,2He] gradient w.r.t. the time-step
+        tokens, G parameter gradients by name, side stream handle -- the caller joins or defers it, ev_dtoks: the event after which dTOKS
+        is final when the note-summary family waits for one, else None)"""
+    B, R, E, He, Ht, Hn, Hd, NP, prec = st.B, st.R, st.E, st.He, st.Ht, st.Hn, st.Hd, st.NP, st.prec
+    if st.notes == 'rows' and not notes_persist_ok(prec, Hn, E):
+        raise RuntimeError("decoder backward: the forward ran on the row kernel (DecoderState.notes == 'rows') and it cannot run now "
+                           '(NOTES_PERSIST or BF16_STORAGE switched off since): only csrc/notes_persist.hip reads its gate planes')
     dev = z.device
     M = 15 * R
     G = {n: None for n in DEC_PARAM_NAMES}
-    NS, HN, HD, TOKS = st['NS'], st['HN'], st['HD'], st['TOKS']
+    NS, HN, HD, TOKS = st.NS, st.HN, st.HD, st.TOKS
     # bf16 shadows of the state buffers (bf16 precision) as the activation operands of the dW products
-    NSo = st['NS16'] if st.get('NS16') is not None else NS
-    HNo = st['HN16'] if st.get('HN16') is not None else HN
-    HDo = st['HD16'] if st.get('HD16') is not None else HD
+    NSo = st.NS16 if st.NS16 is not None else NS
+    HNo = st.HN16 if st.HN16 is not None else HN
+    HDo = st.HD16 if st.HD16 is not None else HD
     NSf_op, NSUM_op = NSo[1:].view(R, Ht), HNo[1:].view(M, Hn)
     side = Side(DEC_WGRAD_SLOT)
 
@@ -2204,11 +2255,11 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
     zero_skip_sync()
     top_h = None
     if ZERO_SKIP:
-        if st.get('live_top') is not None:
+        if st.live_top is not None:
             # the forward stopped at this note step (DisentangleVAE.loss(): the loss ignores everything after it, its gradient there is
             # exactly zero): the limit of everything below -- a scan may report MORE (row padding that is not zero), and the forward
             # tensors hold nothing beyond it
-            top_h = st['live_top']
+            top_h = st.live_top
         elif hint is not None:
             top_h = hint                         # the loss node's own bound (its gradients are zero beyond it by construction)
         else:
@@ -2216,22 +2267,21 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
             call('ptv_last_nonzero_unit', ptr(dP), M, NP, dP.stride(0), R, ptr(top_h), stream_ptr())
             call('ptv_last_nonzero_unit', ptr(ddur), M, 10, 10, R, ptr(top_h), stream_ptr())
 
-    if DEC_BWD_COMPOSITE:
-        res = _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G)
-        if res is not None:
-            return res
-    if st.get('sorted') is not None:
+    res = _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G)
+    if res is not None:
+        return res
+    if st.sorted is not None:
         raise RuntimeError('the decoder forward ran on length-sorted rows (PTV_SORT_DEC_ROWS) but ptv_decoder_tf_bwd, the only place that '
                            'restores the row order, declined this backward pass')
     _defer_flush()                        # (the launch-by-launch sequencing below runs at once)
 
     # ---- duration GRU (5 steps) ----
     w_out = P['dur_out_linear.weight']
-    w_hh_d, w_ih_d = W['dec_dur_gru.weight_hh_l0'], W['dec_dur_gru.weight_ih_l0']
-    if dur_bwd_fusable(prec, Hd, st['gates_d']) or st.get('dur16_only'):
-        dHD0 = dur_bwd_fused(P, G, st['gates_d'], st['idx'], HD, HDo, ddur, wgrad, bgrad, side, tabs=st.get('dur_tabs'))
+    w_hh_d, w_ih_d = P['dec_dur_gru.weight_hh_l0'], P['dec_dur_gru.weight_ih_l0']       # (K-major (dX) products read the fp32 weights)
+    if st.dur != 'step':
+        dHD0 = dur_bwd_fused(P, G, st.gates_d, st.idx, HD, HDo, ddur, wgrad, bgrad, side, tabs=st.dur_tabs)
     else:
-        dgi_d, dgh_d, dHD0 = gru_bwd(prec, HD, st['gates_d'], w_hh_d, lr=(ddur, 2, 10, 2, w_out))
+        dgi_d, dgh_d, dHD0 = gru_bwd(prec, HD, st.gates_d, w_hh_d, lr=(ddur, 2, 10, 2, w_out))
 
         def dur_wgrads():
             for d in range(5):
@@ -2247,22 +2297,21 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
             gemm(cs0, w_ih_d, G['dur_sos_token'].view(1, -1), tb=True, prec=0, splitk=-1)
             sel = _zeros(2, 3 * Hd, dev=dev)                                     # steps 1..4: one-hot tokens {0,1}
             for d in range(1, 5):
-                colsum(sel, dgi_d[d], sel=st['idx'][d - 1], groups=2)
+                colsum(sel, dgi_d[d], sel=st.idx[d - 1], groups=2)
             gemm(sel, _eye2(dev), g[:, 0:2], ta=True, acc=True, prec=0, splitk=-1)
             G['dec_dur_gru.weight_ih_l0'] = g
         side(dur_wgrads, ddur, dgi_d, dgh_d)
 
     mark('dec_bwd:dur_bptt')
     # ---- dur_hid_linear([note_summary | est_pitch]) and pitch_out_linear ----
-    w_dh, w_p = W['dur_hid_linear.weight'], W['pitch_out_linear.weight']
+    w_dh, w_p = P['dur_hid_linear.weight'], P['pitch_out_linear.weight']
     # gradient reaching the notes-GRU states: only ever an addend of the BPTT epilogue -> activation dtype
     dNSUM = _empty(M, Hn, dev=dev, dtype=_act_dtype(prec, Hn))
-    if POISON_DEAD_STEPS and top_h is not None and st.get('live_top') is not None:
+    if POISON_DEAD_STEPS and top_h is not None and st.live_top is not None:
         _poison(dNSUM)
     # (read by the row-partitioned BPTT kernel column-blocked by 32, like its saved gates: whole-kilobyte wave accesses)
-    rowk_bwd = bool(st.get('gates_n_rowk') and notes_persist_ok(prec, Hn, E, st['gates_n'].dtype) and dNSUM.dtype == BF16 and HN.dtype == F32)
-    fused_heads = (heads_ok(prec, Hn, NP, Hd, st.get('HN16'), st.get('HD16')) and dNSUM.dtype == BF16 and dP.stride(0) % 4 == 0
-                   and dP.data_ptr() % 16 == 0 and dHD0.dtype == F32 and dHD0.is_contiguous())
+    rowk_bwd = st.notes == 'rows'
+    fused_heads = st.heads == 'fused' and dP.stride(0) % 4 == 0 and dP.data_ptr() % 16 == 0      # (a misaligned gradient: the products)
     dY16 = None
     if fused_heads:
         # dP += dHD0 . W_dh[:, Hn:] and dNSUM = dP . W_p + dHD0 . W_dh[:, :Hn] in one pass over dP / dHD0 (csrc/heads.hip)
@@ -2292,10 +2341,10 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
                 copy2d(G[bname].view(1, -1), cs[lo:hi].view(1, -1), acc=True)
             # (from the fp32 dHD0, whose dead rows are real zeros: N = 130 sends the last <= 32 rows through the guarded tail launch, which
             # knows no row limit -- the dead rows of dY16 are never written)
-            wgrad_b('dur_hid_linear.weight', None, dHD0, st['pitch'], slice(Hn, None), top_h)
+            wgrad_b('dur_hid_linear.weight', None, dHD0, st.pitch, slice(Hn, None), top_h)
             return
         wgrad_b('dur_hid_linear.weight', 'dur_hid_linear.bias', dHD0, NSUM_op, slice(0, Hn), top_h)
-        wgrad_b('dur_hid_linear.weight', None, dHD0, st['pitch'], slice(Hn, None), top_h)
+        wgrad_b('dur_hid_linear.weight', None, dHD0, st.pitch, slice(Hn, None), top_h)
         wgrad_b('pitch_out_linear.weight', 'pitch_out_linear.bias', dP, NSUM_op, None, top_h)
     if not fused_heads:
         gemm_dx(dHD0, w_dh, slice(0, Hn), out=dNSUM, prec=prec, m_top=top_h, m_unit=R, out_blocked=rowk_bwd)                   # [M, Hn]
@@ -2306,22 +2355,22 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
 
     mark('dec_bwd:head_dx')
     # ---- notes GRU (15 steps, batch 32*B) ----
-    w_hh_n, w_ih_n = W['dec_notes_gru.weight_hh_l0'], W['dec_notes_gru.weight_ih_l0']
+    w_hh_n, w_ih_n = P['dec_notes_gru.weight_hh_l0'], P['dec_notes_gru.weight_ih_l0']
     if rowk_bwd:
         # (the forward ran on the row kernel: its gate planes are in that kernel pair's private layout)
         pk = notes_packs(w_ih_n, w_hh_n, Ht)
         dgi_n = _empty(15, R, 3 * Hn, dev=dev, dtype=BF16)
         dgh_n = _empty(15, R, Hn, dev=dev, dtype=BF16)          # n third only: the r / z thirds of dgh are dgi's
-        if POISON_DEAD_STEPS and top_h is not None and st.get('live_top') is not None:
+        if POISON_DEAD_STEPS and top_h is not None and st.live_top is not None:
             _poison(dgi_n, dgh_n)
         dHN0 = _empty(R, Hn, dev=dev)
         scratch = _empty(lib().ptv_notes_gru_persist_scratch_elems(R), dev=dev, dtype=BF16)
         top_step = _ineg1(dev) if ZERO_SKIP else None   # <- last note step with a gradient
-        call('ptv_notes_gru_persist_bwd_top', ptr(pk['wt']), ptr(st['HN16']), ptr(st['gates_n']), ptr(dNSUM), ptr(dgi_n), ptr(dgh_n), ptr(dHN0),
+        call('ptv_notes_gru_persist_bwd_top', ptr(pk['wt']), ptr(st.HN16), ptr(st.gates_n), ptr(dNSUM), ptr(dgi_n), ptr(dgh_n), ptr(dHN0),
              ptr(scratch), R, 15, ptr(bound_n if fused_heads else None), ptr(top_step), stream_ptr())
     else:
         top_step = None
-        dgi_n, dgh_n, dHN0 = gru_bwd(prec, HN, st['gates_n'], w_hh_n, dh_ext=dNSUM.view(15, R, Hn))
+        dgi_n, dgh_n, dHN0 = gru_bwd(prec, HN, st.gates_n, w_hh_n, dh_ext=dNSUM.view(15, R, Hn))
     mark('dec_bwd:notes_bptt')
     dGC = sum_steps(dgi_n, t_top=top_step)                                    # [R, 3Hn]
 
@@ -2333,7 +2382,7 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
     def notes_dx():
         gemm_dx(dgi_n.view(M, 3 * Hn), w_ih_n, slice(Ht, None), out=dtok[:15].view(M, E), prec=prec, m_top=top_step, m_unit=R)
         dNS = gemm_dx(dGC, w_ih_n, slice(0, Ht), prec=prec)                   # [R, Ht]
-        w_tn = W['dec_time_to_notes_hid.weight']
+        w_tn = P['dec_time_to_notes_hid.weight']
         gemm_dx(dHN0, w_tn, out=dNS, acc=True, prec=prec)
         return dtok, dNS
 
@@ -2368,8 +2417,8 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
 
     mark('dec_bwd:notes_dx')
     # ---- time GRU (32 steps, batch B) ----
-    w_hh_t, w_ih_t = W['dec_time_gru.weight_hh_l0'], W['dec_time_gru.weight_ih_l0']
-    dgi_t, dgh_t, dzhid = gru_bwd(prec, NS, st['gates_t'], w_hh_t, dh_ext=dNS.view(32, B, Ht))
+    w_hh_t, w_ih_t = P['dec_time_gru.weight_hh_l0'], P['dec_time_gru.weight_ih_l0']
+    dgi_t, dgh_t, dzhid = gru_bwd(prec, NS, st.gates_t, w_hh_t, dh_ext=dNS.view(32, B, Ht))
     mark('dec_bwd:time_bptt')
     dZG = sum_steps(dgi_t)                                                    # [B, 3Ht]
     dz_in = gemm_dx(dZG, w_ih_t, slice(2 * He, None), prec=prec)              # [B, Zi]
@@ -2378,8 +2427,8 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
     gemm_dx(dgi_t.view(R, 3 * Ht), w_ih_t, slice(0, 2 * He), out=dTOKS[:32].view(R, 2 * He), prec=prec)
     # (the note-summary node's two inputs -- this gradient and, queued earlier on this stream, the parked embedding gradient -- are final
     # HERE: its BPTT family starts from this event, not from the end of whatever else the step has queued by then)
-    st['ev_dtoks'] = record_event() if SUMMARY_FAMILY_SLOT >= 0 and OVERLAP else None
-    w_zh, w_zi = W['z2dec_hid_linear.weight'], W['z2dec_in_linear.weight']
+    ev_dtoks = record_event() if SUMMARY_FAMILY_SLOT >= 0 and OVERLAP else None
+    w_zh, w_zi = P['z2dec_hid_linear.weight'], P['z2dec_in_linear.weight']
     dz = gemm_dx(dzhid, w_zh, prec=prec)
     gemm_dx(dz_in, w_zi, out=dz, acc=True, prec=prec)
 
@@ -2388,7 +2437,7 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
         # z_in product (the same folds as ptv_decoder_tf_bwd's batch; products the weight-gradient kernel does not take -- fp32 precision,
         # K = B < 512 -- fall back to product + column-sum kernel inside wgrad_bias, as the library's WgradGroup does)
         wgrad_b('dec_time_gru.weight_hh_l0', 'dec_time_gru.bias_hh_l0', dgh_t.view(R, 3 * Ht), NSo[:32].view(R, Ht))
-        wgrad_b('dec_time_gru.weight_ih_l0', 'dec_time_gru.bias_ih_l0', dZG, st['z_in'], slice(2 * He, None))
+        wgrad_b('dec_time_gru.weight_ih_l0', 'dec_time_gru.bias_ih_l0', dZG, st.z_in, slice(2 * He, None))
         wgrad('dec_time_gru.weight_ih_l0', dgi_t.view(R, 3 * Ht), TOKS[:32].view(R, 2 * He), slice(0, 2 * He))
         wgrad_b('z2dec_hid_linear.weight', 'z2dec_hid_linear.bias', dzhid, z)
         wgrad_b('z2dec_in_linear.weight', 'z2dec_in_linear.bias', dz_in, z)
@@ -2397,7 +2446,7 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
     # the caller defers the join to the end of the backward pass; the node's saved forward state (released when the node returns)
     # is still being read by the products queued above
     side.keep.extend((st, z, tok_op))
-    return dz, dtok, dTOKS, G, side
+    return DecoderGrads(dz, dtok, dTOKS, G, side, ev_dtoks)
 
 
 # =============================================================================================

@@ -239,6 +239,18 @@ def _decoder_free_bwd_call(items, dTOK, dTOKS, demb, dPRED, dxs, dxsp, mask_tok,
     return True
 
 
+class DecoderStepState(F_.DecoderState):
+    """DecoderState of the step loop: what decoder_bwd_core reads, and beside it what only DecoderStepFn.backward does -- TOK [15,R,E] the
+    note tokens that were fed, PRED [16,R,E] the predicted ones, xhat the predicted grid, XH / XG / XH16 the re-summarisation bi-GRU's
+    states, gates and bf16 states per direction (XH None: no re-summarisation), plen the predicted rows' lengths and whether the kernels
+    skipped by them, the teacher-forcing coins, has_xs: ground-truth summaries were given"""
+
+    def __init__(self, dims, prec, notes, heads, dur, *, TOK, PRED, xhat, XH, XG, XH16, plen, skipped, coins, has_xs, **saved):
+        super().__init__(dims, prec, notes, heads, dur, **saved)
+        self.TOK, self.PRED, self.xhat, self.XH, self.XG, self.XH16 = TOK, PRED, xhat, XH, XG, XH16
+        self.plen, self.skipped, self.coins, self.has_xs = plen, skipped, coins, has_xs
+
+
 class DecoderStepFn(torch.autograd.Function):
     """(z, emb [16,32,B,E] or None, xs [32B,2He] or None, coins, inference, force, prec, *params)
     -> pitch [15,32,B,130], dur [15*32*B,5,2], xhat int64 [B,32,16,6] (predicted grid), dur idx"""
@@ -490,10 +502,15 @@ class DecoderStepFn(torch.autograd.Function):
                          ptr(plen), ptr(XH[d]), ptr(XH16[d]), ptr(XG[d]), None, 0, R, 16, d, st)
         if train:
             ctx.save_for_backward(z, emb, *params)
-            ctx.st = dict(B=B, R=R, E=E, He=He, Ht=Ht, Hn=Hn, Hd=Hd, NP=NP, prec=prec, NS=NS, z_in=z_in, TOKS=TOKS,
-                          gates_t=gates_t, HN=HN, gates_n=gates_n, gates_n_rowk=bool(replay), pitch=pitch, HD=HD, gates_d=gates_d, idx=idx, TOK=TOK,
-                          PRED=PRED, xhat=xhat, XH=XH, XG=XG, XH16=XH16, plen=plen, skipped=F_.ZERO_SKIP, coins=coins, has_xs=xs is not None,
-                          NS16=NS16, HN16=HN16, HD16=HD16, dur16_only=HD16 is not None, dur_tabs=(tab0, tab))
+            # (the names say which backward halves read the state: the batched recompute ran the row kernel; the loop's own heads and
+            # duration steps leave what csrc/heads.hip / csrc/dur_bwd.hip take back wherever the bf16 copies exist)
+            ctx.saved_state = DecoderStepState(
+                (B, R, E, He, Ht, Hn, Hd, NP), prec, 'rows' if replay else 'step',
+                'fused' if F_.heads_ok(prec, Hn, NP, Hd, HN16, HD16) else 'gemm',
+                'fused16' if HD16 is not None else 'fused' if F_.dur_bwd_fusable(prec, Hd, gates_d) else 'step',
+                NS=NS, NS16=NS16, z_in=z_in, TOKS=TOKS, gates_t=gates_t, HN=HN, HN16=HN16, gates_n=gates_n, pitch=pitch, HD=HD, HD16=HD16,
+                gates_d=gates_d, idx=idx, dur_tabs=(tab0, tab), TOK=TOK, PRED=PRED, xhat=xhat, XH=XH, XG=XG, XH16=XH16, plen=plen,
+                skipped=F_.ZERO_SKIP, coins=coins, has_xs=xs is not None)
         ctx.mark_non_differentiable(xhat, idx)
         return pitch.view(15, 32, B, NP), dur, xhat, idx
 
@@ -501,14 +518,14 @@ class DecoderStepFn(torch.autograd.Function):
     def backward(ctx, dpitch, ddur, _dx, _di):
         z, emb, *params = ctx.saved_tensors
         P = dict(zip(FREE_PARAM_NAMES, params))
-        st = ctx.st
+        st = ctx.saved_state
         if not getattr(ctx, 'keep_state', False):        # a captured forward (GraphedDecoderStepFn) reuses its buffers
-            ctx.st = None
-        B, R, E, He, Ht, Hn, Hd, NP, prec = (st[k] for k in ('B', 'R', 'E', 'He', 'Ht', 'Hn', 'Hd', 'NP', 'prec'))
+            ctx.saved_state = None
+        B, R, E, He, prec = st.B, st.R, st.E, st.He, st.prec
         dev = z.device
         M = 15 * R
-        PRED = st['PRED']
-        coin_notes, coin_time = st['coins']
+        PRED = st.PRED
+        coin_notes, coin_time = st.coins
         sp = stream_ptr()
         # ---- the node behind ONE C entry point (ptv_decoder_free_bwd): its stages are COLLECTED (functional._DEFER) instead of launched -- the
         # decoder's composite backward, the two routings, the re-summarisation bi-GRU's composite backward, the note_embedding gradients --
@@ -520,7 +537,7 @@ class DecoderStepFn(torch.autograd.Function):
             F_._DEFER = []
         try:
             # ---- duration GRU, heads, notes GRU, time GRU: the batched BPTT of the teacher-forced path on the recorded fed tokens
-            dz, dTOK, dTOKS, G0, side = F_.decoder_bwd_core(P, st, z, st['TOK'].view(M, E), dpitch, ddur)
+            dz, dTOK, dTOKS, G0, side, _ = F_.decoder_bwd_core(P, st, z, st.TOK.view(M, E), dpitch, ddur)
             G = {n: None for n in FREE_PARAM_NAMES}
             G.update(G0)
 
@@ -536,11 +553,11 @@ class DecoderStepFn(torch.autograd.Function):
             mask_time = _route_mask(('time', tuple(bool(v) for v in coin_time)), dev)
             F_._defer_or_run('route', None, lambda: call('ptv_route_slices', ptr(dTOKS[1:]), ptr(dxs), ptr(dxsp), ptr(mask_time), B * 2 * He, 32, 0, sp))
             dx_pred = None
-            if st['XH'] is not None:
+            if st.XH is not None:
                 wE = [P['dec_notes_emb_gru.' + n] for n in EMB_GRU]
                 # (the batched recompute ran the row kernels -- they left bf16 states -- and skipped dead panel steps by plen)
-                state = BiGruState('rows' if st['XH16'][0] is not None else 'step', zip(st['XH'], st['XG'], st['XH16']),
-                                   lengths=st['plen'] if st['skipped'] else None)
+                state = BiGruState('rows' if st.XH16[0] is not None else 'step', zip(st.XH, st.XG, st.XH16),
+                                   lengths=st.plen if st.skipped else None)
                 ge, dx_pred = _bigru_backward(prec, PRED, wE, state, dxsp.view(R, 2 * He), True)
                 for n, gg in zip(EMB_GRU, ge):
                     G['dec_notes_emb_gru.' + n] = gg
@@ -556,7 +573,7 @@ class DecoderStepFn(torch.autograd.Function):
             def tail():
                 copy2d(demb[0], dPRED[0], acc=True)
                 dPRED[0].zero_()
-                call('ptv_multihot', ptr(st['xhat']), ptr(mh), 136, B, sp)
+                call('ptv_multihot', ptr(st.xhat), ptr(mh), 136, B, sp)
                 F_.wgrad_bias(dPRED.view(16 * R, E), mh[:, :135], G['note_embedding.weight'], G['note_embedding.bias'], prec)
             F_._defer_or_run('tail', None, tail)
             items = F_._DEFER
@@ -566,7 +583,7 @@ class DecoderStepFn(torch.autograd.Function):
                 F_._DEFER = None
                 kinds = [k for k, _, _ in items]
                 want = ['tf_bwd', 'route', 'route'] + (['rows_bwd', 'copy'] if dx_pred is not None else []) + ['tail']
-                if kinds == want and _decoder_free_bwd_call(items, dTOK, dTOKS, demb, dPRED, dxs, dxsp, mask_tok, mask_time, dx_pred, st['xhat'], mh,
+                if kinds == want and _decoder_free_bwd_call(items, dTOK, dTOKS, demb, dPRED, dxs, dxsp, mask_tok, mask_time, dx_pred, st.xhat, mh,
                                                             G['note_embedding.weight'], G['note_embedding.bias'], B, E, He):
                     pass
                 else:                                       # (not the whole pattern: the collected stages run as they are, in order)
@@ -580,7 +597,7 @@ class DecoderStepFn(torch.autograd.Function):
         for s2 in getattr(side, 'extra', []):
             s2.join()
         grads = tuple(G[n] for n in FREE_PARAM_NAMES)
-        return (dz, demb.view(16, 32, B, E), dxs.view(R, 2 * He) if st['has_xs'] else None, None, None, None, None) + grads
+        return (dz, demb.view(16, 32, B, E), dxs.view(R, 2 * He) if st.has_xs else None, None, None, None, None) + grads
 
 
 # =============================================================================================
@@ -592,7 +609,7 @@ class _CapturedCtx:
     def __init__(self, n_inputs):
         self.needs_input_grad = (True,) * n_inputs
         self.saved_tensors = ()
-        self.st = None
+        self.saved_state = None
         self.keep_state = True
 
     def save_for_backward(self, *tensors):

@@ -1228,3 +1228,125 @@ def test_bigru_node_records_the_branch_it_ran_and_its_composites_equal_the_pytho
         with pytest.raises(RuntimeError, match='row kernels'):
             out.backward(dout)
         torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('case', ['composite', 'python-fused', 'generic', 'step-loop'])
+def test_decoder_node_records_the_kernels_it_ran_and_its_composites_equal_the_python_sequencing(case, monkeypatch):
+    """DecoderTFFn / DecoderStepFn on each kernel family at the smallest batch that still selects it (the decoder grid is 32 x 16 x 130
+    whatever the batch): the forward's DecoderState names the kernels that ran -- a quiet fall-back to a slower family passes every parity
+    test --, the C composites run exactly when the state and decoder_bwd_composite_static_ok say so, and a state whose row kernel is
+    switched off before the backward is refused instead of read by another kernel.
+    composite / python-fused: bf16, full geometry, B = 4, through loss() (the dead-step limit is set); the two agree bit for bit in
+    pitch, dur, idx (their live note steps: nothing writes the others), dz, the embedding gradient and every parameter gradient.  (That comparison runs the composites on rows in (t, b)
+    order: by default the composite forward sorts its rows by length whenever the backward composite can un-sort them, its logits then
+    come in another row order and its K-deep sums in another summation order -- tests/test_gpu_dead_steps.py bounds that difference.)
+    generic: fp32, the reduced model, B = 3.  step-loop: the free-running node at the smallest batch of the free-running model tests."""
+    from helpers import full_params
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_
+    from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
+    from polyphonic_chord_texture_disentanglement_amd import model as M
+    from polyphonic_chord_texture_disentanglement_amd.optim import FusedClipAdam
+    from polyphonic_chord_texture_disentanglement_amd.synthetic import synth_batch
+    from test_host_surface import build_reduced
+    dev = _dev()
+    node = FF_.DecoderStepFn if case == 'step-loop' else F_.DecoderTFFn
+    B = 3 if case == 'generic' else 4
+    if case == 'generic':
+        m = build_reduced(dev).to(dev)
+    else:
+        m = M.DisentangleVAE.init_model(dev)
+        m.load_state_dict(full_params())
+        m.to(dev).set_precision('bf16')
+    opt = FusedClipAdam(m.parameters(), lr=1e-3)                # (the bf16 weight shadows the row kernels and the composites read)
+    x, c, pr = (torch.from_numpy(a).to(dev) for a in synth_batch(B, 31))
+    seen = {}
+    fwd, bwd = node.forward, node.backward
+
+    def forward(ctx, *args):
+        outs = fwd(ctx, *args)
+        seen.update(ctx=ctx, args=args, outs=[o.detach().clone() for o in outs])
+        return outs
+
+    def backward(ctx, *grads):
+        r = bwd(ctx, *grads)
+        link = getattr(ctx, 'emb_link', None)                   # (the embedding gradient parked for the note-summary node, or returned)
+        seen.update(dz=r[0].clone(), demb=(r[1] if r[1] is not None else link['demb']).clone())
+        return r
+    monkeypatch.setattr(node, 'forward', staticmethod(forward))
+    monkeypatch.setattr(node, 'backward', staticmethod(backward))
+
+    def step(tfr=1.):
+        """one loss() + backward -> (the node's DecoderState, composite forward calls, composite backward calls, everything compared)"""
+        seen.clear()
+        m.use_philox(5, 0)
+        opt.zero_grad()
+        n_f, n_b = F_._DTF.get('calls', 0), F_._DTB.get('calls', 0)
+        losses = m.loss(x, c, pr, tfr, tfr, tfr, 0.1, [1, 0.5])
+        state = seen['ctx'].saved_state
+        losses[0].backward()
+        torch.cuda.synchronize()
+        F_.persist_check()
+        bits = seen['outs'] + [seen['dz'], seen['demb']] + [p.grad.clone() for p in m.parameters()]
+        if state.live_top is not None:                          # (the note steps after the limit are not written: only the live ones compare)
+            live = int(state.live_top.item()) + 1
+            pitch, dur, idx = bits[:3]
+            bits[:3] = pitch[:live], dur.view(15, -1, 5, 2)[:live], idx.view(5, 15, -1)[:, :live]
+        assert all(torch.isfinite(t).all() for t in bits if t.dtype.is_floating_point)
+        return state, F_._DTF.get('calls', 0) - n_f, F_._DTB.get('calls', 0) - n_b, bits
+
+    def static_ok(s):
+        P = dict(zip(F_.DEC_PARAM_NAMES, seen['args'][6:]))
+        return F_.decoder_bwd_composite_static_ok(s.prec, s.B, s.Ht, s.Hn, s.NP, s.Hd, s.E, P)
+
+    if case == 'generic':
+        s, n_f, n_b, _ = step()
+        assert (s.notes, s.heads, s.dur) == ('step', 'gemm', 'step') and s.live_top is None and s.sorted is None
+        assert (n_f, n_b) == (0, 0) and s.prec == 0 and s.B == B
+        return
+    if case == 'step-loop':
+        s, _, _, _ = step(0.)
+        assert isinstance(s, FF_.DecoderStepState) and s.notes == 'rows' and s.live_top is None and s.sorted is None
+        assert (s.heads, s.dur) == ('fused', 'fused16')         # (the bf16 state copies exist: the fused backward halves read them)
+        R, E, He = 32 * B, s.E, s.He
+        assert s.TOK.shape == (15, R, E) and s.PRED.shape == (16, R, E) and s.xhat.shape == (B, 32, 16, 6) and s.plen.shape == (R,)
+        assert [len(v) for v in (s.XH, s.XG, s.XH16)] == [2, 2, 2] and s.XH[0].shape == (17, R, He)
+        assert s.skipped == F_.ZERO_SKIP and len(s.coins) == 2 and s.has_xs in (True, False)
+        return
+    comp = case == 'composite'
+    monkeypatch.setattr(F_, 'DEC_COMPOSITE', comp)
+    monkeypatch.setattr(F_, 'DEC_BWD_COMPOSITE', comp)
+    if not comp:
+        monkeypatch.setattr(F_, 'SORT_DEC_ROWS', False)
+    s, n_f, n_b, _ = step()
+    assert (s.notes, s.heads, s.dur) == ('rows', 'fused', 'fused16') and s.live_top is not None
+    assert n_f == int(comp)
+    ok = static_ok(s)
+    assert ok == comp                                           # (B = 4 is within the backward composite's reach: the switch alone decides)
+    assert (s.sorted is None) == (not ok)
+    assert n_b == int(ok and s.gates_d is None)
+    if not comp:
+        return
+    # the same step with the composites on and off, rows in (t, b) order both times: the same bits
+    monkeypatch.setattr(F_, 'SORT_DEC_ROWS', False)
+    s, n_f, n_b, on = step()
+    assert s.sorted is None and (n_f, n_b) == (1, 1)
+    z, emb, xs = (t.detach().clone() for t in seen['args'][:3])
+    params = seen['args'][6:]
+    monkeypatch.setattr(F_, 'DEC_COMPOSITE', False)
+    monkeypatch.setattr(F_, 'DEC_BWD_COMPOSITE', False)
+    s, n_f, n_b, off = step()
+    assert (s.notes, s.heads, s.dur) == ('rows', 'fused', 'fused16') and (n_f, n_b) == (0, 0)
+    assert len(on) == len(off)
+    for a, b in zip(on, off):
+        assert torch.equal(a, b)
+    # the row kernel's gate planes are its own: switched off before the backward, nothing else may read them
+    monkeypatch.setattr(F_, 'DEC_COMPOSITE', True)
+    monkeypatch.setattr(F_, 'DEC_BWD_COMPOSITE', True)
+    opt.zero_grad()
+    pitch, _, _ = F_.DecoderTFFn.apply(z.requires_grad_(), emb, xs, None, None, seen['args'][5], *params)
+    assert pitch.grad_fn.saved_state.notes == 'rows'
+    monkeypatch.setattr(F_, 'NOTES_PERSIST', False)
+    with pytest.raises(RuntimeError, match='row kernel'):
+        pitch.backward(torch.zeros_like(pitch))
+    torch.cuda.synchronize()
+    F_.reset_deferred()

@@ -350,3 +350,79 @@ def test_bigru_state_refuses_what_its_backward_could_not_read():
     extras = [probe(), probe(), probe()]
     F_._record_stream(F_.BiGruState('rows', dirs, *extras), None)
     assert {id(x) for x in seen} == {id(x) for x in extras + [x for d in dirs for x in d]}
+
+
+def test_decoder_state_refuses_what_no_forward_leaves():
+    """functional.DecoderState (what a PianoTree decoder forward leaves for its backward) names the kernels that ran; its constructor takes
+    every combination a forward produces and refuses the others: an unknown name, a 'rows' state without bf16 gates and bf16 states,
+    'fused16' without HD16, rebuilt duration gates (gates_d None) anywhere else, sorted rows or a dead-step limit unless the whole chain
+    honours them.  What it holds -- the sorted record and the step loop's extras too -- stays within reach of _record_stream"""
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_
+    from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
+    B, E, He, Ht, Hn, Hd, NP = 1, 8, 8, 16, 16, 8, 10
+    R, M = 32 * B, 15 * 32 * B
+    dims = (B, R, E, He, Ht, Hn, Hd, NP)
+    bf = torch.bfloat16
+    t = lambda *s, dt=torch.float32: torch.empty(*s, device='meta', dtype=dt)
+    ints = lambda *s: t(*s, dt=torch.int32)
+
+    def saved(dt=bf, pad=True, **over):
+        """the tensors of a bf16-storage forward (dt = bf) or of an fp32 one (no bf16 shadows)"""
+        h16 = (lambda *s: t(*s, dt=bf)) if dt == bf else (lambda *s: None)
+        kw = dict(NS=t(33, B, Ht), NS16=h16(33, B, Ht), z_in=t(B, 4), TOKS=t(33, B, 2 * He), gates_t=t(32, 4, B, Ht, dt=dt),
+                  HN=t(16, R, Hn), HN16=h16(16, R, Hn), gates_n=t(15, 4, R, Hn, dt=dt), pitch=t(M, 16 if pad else NP)[:, :NP],
+                  HD=t(6, M, Hd), HD16=h16(6, M, Hd), gates_d=t(5, 4, M, Hd, dt=dt), idx=ints(5, M), dur_tabs=(t(1, 3 * Hd), t(2, 3 * Hd)))
+        kw.update(over)
+        return kw
+    srt = F_.DecoderSorted(ints(R), ints(R), t(R, Ht, dt=bf), t(15, R, E), ints(16))
+    loop = dict(TOK=t(15, R, E), PRED=t(16, R, E), xhat=t(B, 32, 16, 6, dt=torch.long), XH=[t(17, R, He)] * 2, XG=[t(16, 4, R, He, dt=bf)] * 2,
+                XH16=[None, None], plen=ints(R), skipped=True, coins=([[False] * 14] * 32, [False] * 31), has_xs=True)
+    # what the forwards produce: the composite and the launch-by-launch fused chain (gates rebuilt or saved, with and without the limit and
+    # sorted rows), mixed chains with one stage switched off, fp32 storage, and the step loop with and without its batched recompute
+    S = F_.DecoderState
+    s = S(dims, 1, 'rows', 'fused', 'fused16', **saved(gates_d=None), live_top=ints(1), sorted=srt)
+    assert (s.B, s.R, s.E, s.He, s.Ht, s.Hn, s.Hd, s.NP, s.prec) == dims + (1,) and s.sorted.seg_n is srt.seg_n and s.gates_d is None
+    assert S(dims, 1, 'rows', 'fused', 'fused16', **saved()).live_top is None
+    for names in (('step', 'fused', 'fused16'), ('rows', 'gemm', 'fused16'), ('rows', 'fused', 'step'), ('step', 'gemm', 'step')):
+        assert S(dims, 1, *names, **saved()).sorted is None
+    assert S(dims, 0, 'step', 'gemm', 'step', **saved(torch.float32, pad=False)).HN16 is None
+    assert FF_.DecoderStepState(dims, 1, 'rows', 'fused', 'fused16', **saved(gates_d=None), **loop).plen is loop['plen']
+    assert FF_.DecoderStepState(dims, 1, 'step', 'gemm', 'fused', **saved(NS16=None, HN16=None, HD16=None), **loop).dur == 'fused'
+    # ... and what none of them does
+    for names in (('row', 'fused', 'fused16'), ('rows', 'fuse', 'fused16'), ('rows', 'fused', 'fused32')):
+        with pytest.raises(ValueError, match='unknown'):
+            S(dims, 1, *names, **saved())
+    for over in (dict(HN16=None), dict(gates_n=t(15, 4, R, Hn)), dict(gates_n=None)):
+        with pytest.raises(ValueError, match="'rows'"):
+            S(dims, 1, 'rows', 'gemm', 'fused16', **saved(**over))
+    with pytest.raises(ValueError, match="'fused16'"):
+        S(dims, 1, 'step', 'gemm', 'fused16', **saved(HD16=None))
+    for dur in ('fused', 'step'):
+        with pytest.raises(ValueError, match='gates_d'):
+            S(dims, 1, 'rows', 'fused', dur, **saved(gates_d=None))
+    for extra in (dict(sorted=srt), dict(live_top=ints(1))):
+        for names in (('step', 'fused', 'fused16'), ('rows', 'gemm', 'fused16'), ('rows', 'fused', 'step')):
+            with pytest.raises(ValueError, match='whole chain'):
+                S(dims, 1, *names, **saved(), **extra)
+    with pytest.raises(ValueError, match='DecoderSorted'):
+        S(dims, 1, 'rows', 'fused', 'fused16', **saved(), sorted=dict(srt._asdict()))
+    # (Side keeps the state alive and tells the caching allocator about it through _record_stream: every tensor must be within its reach)
+    seen = []
+
+    class Probe(torch.Tensor):
+        is_cuda = True
+
+        def record_stream(self, stream):
+            seen.append(self)
+    probe = lambda *a, **k: torch.Tensor._make_subclass(Probe, torch.empty(1, dtype=bf))
+    kw = saved(gates_d=None)
+    kw = {k: probe() for k in kw if k not in ('dur_tabs', 'pitch', 'gates_d')}
+    kw.update(dur_tabs=(probe(), probe()), pitch=torch.Tensor._make_subclass(Probe, torch.empty(M, 16)[:, :NP]), gates_d=None)
+    srt_p = F_.DecoderSorted(*[probe() for _ in range(5)])
+    loop_p = dict(loop, **{k: probe() for k in ('TOK', 'PRED', 'xhat', 'plen')}, XH=[probe(), probe()], XG=[probe(), probe()],
+                  XH16=[probe(), probe()])
+    top = probe()
+    F_._record_stream(FF_.DecoderStepState(dims, 1, 'rows', 'fused', 'fused16', **kw, **loop_p, live_top=top, sorted=srt_p), None)
+    want = ([v for k, v in kw.items() if k not in ('dur_tabs', 'gates_d')] + list(kw['dur_tabs']) + list(srt_p) + [top]
+            + [loop_p[k] for k in ('TOK', 'PRED', 'xhat', 'plen')] + loop_p['XH'] + loop_p['XG'] + loop_p['XH16'])
+    assert len(want) == 14 + 5 + 1 + 10 and {id(x) for x in seen} == {id(x) for x in want}
