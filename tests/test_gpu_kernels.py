@@ -316,7 +316,8 @@ def test_gru_bwd_kernel_variants_of_the_b512_step(M, H, T):
 
 def test_fused_duration_kernels_at_the_b512_grid_caps():
     """ptv_dur_gru_fwd / ptv_dur_gru_bwd at M = 245,760 rows (= 480 x 512): the forward's 1024-block cap and the backward's
-    256-block grid-stride regime (functional.dur_bwd_fused), against the fp32 oracle cell with the kernel's argmax replayed"""
+    256-block grid-stride regime (functional.dur_bwd_fused), against the fp32 oracle cell with the kernel's argmax replayed.
+    The small shapes, every entry point and template variant, against an fp64 reference: tests/test_gpu_dur_kernels.py"""
     from polyphonic_chord_texture_disentanglement_amd import functional as F_
     from polyphonic_chord_texture_disentanglement_amd._lib import call, lib, ptr, stream_ptr
     dev = _dev()
