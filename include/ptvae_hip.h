@@ -54,11 +54,14 @@ const char* ptv_header_hash(void);
 /* ------------------------------------------------------------------------------------------------
  * Dense product  C[M,N] = act(alpha * A.B^T + bias) (+ C)      -- every nn.Linear forward
  * (ptvae.py:16-17,37-38,100-101,264-267,286-293), its input gradient (transB) and weight gradient
- * (transA+transB, split-K with atomic accumulation).
+ * (transA+transB, split-K: each split stores its partial into a per-stream workspace and one more launch adds them in split
+ * order; fp32 atomics into C only after ptv_ordered_reductions(0) / when no workspace can be had, see ptv_ordered_fallbacks).
  *   transA = 0: A[m*lda + k]   1: A[k*lda + m]
  *   transB = 0: B[n*ldb + k] (nn.Linear weight layout)   1: B[k*ldb + n]
  *   act: 0 none, 1 exp (linear_var(...).exp_(), ptvae.py:27,120)
- *   splitk: 0 auto, >0 forced number of K splits, <0 never split
+ *   splitk: 0 auto, >0 forced number of K splits, <0 never split.  The count is rounded so that every split covers whole K tiles and
+ *           none is empty (K = 0: one).  act != 0 with splitk > 1 is refused (PTV_ERR_ARG): exp of a partial sum is not a part of the
+ *           result; the automatic split never splits a product with act.  bf16 C and column-blocked C refuse splitk > 1 as well.
  *   dtypes: bit 0 / 1 / 2 = A / B / C hold bf16 (bf16 precision only); bit 3 (8) / bit 4 (16) = C is COLUMN-BLOCKED by w = 32 / 16:
  *           element (m, n) lives at ((n / w) * M + m) * w + n % w (ldc unused, N a multiple of w, no K split) -- the layout in which the
  *           row-partitioned recurrences (ptv_notes_gru_persist_fwd: gc, w = 16; ptv_notes_gru_persist_bwd: ext, w = 32) read their

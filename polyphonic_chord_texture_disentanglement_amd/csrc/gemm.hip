@@ -221,6 +221,7 @@ static int gemm_dispatch(int transA, int transB, GemmArgs g, EpiPlain::Params ep
     if (splits > 192) splits = 192;
     if (splits < 1) splits = 1;
   }
+  if (g.K == 0) splits = 1;                                      // nothing to split: one launch writes C = act(bias) / leaves it (and kper below would be 0)
   int kper = g.K;
   if (splits > 1) {
     if (splits >= 8) splits = (splits + 7) / 8 * 8;            // whole splits per XCD (gemm_body's block map)
@@ -293,7 +294,8 @@ extern "C" int ptv_gemm_mtop_seg(int prec, int transA, int transB, int M, int N,
   if (M == 0 || N == 0) return PTV_OK;
   const bool sa = dtypes & 1, sb = dtypes & 2, sc = dtypes & 4;
   if ((sa || sb) && prec != PTV_PREC_BF16) return PTV_ERR_ARG;       // bf16 operands feed the bf16 MFMA path only
-  if (sc && splitk > 1) return PTV_ERR_ARG;                          // split-K accumulates with fp32 atomics
+  if (sc && splitk > 1) return PTV_ERR_ARG;                          // split-K partials are fp32 (workspace or atomics)
+  if (act != 0 && splitk > 1) return PTV_ERR_ARG;                    // act applies to the whole sum, a split only has a part of it (the automatic split excludes act)
   if ((dtypes & 8) && (dtypes & 16)) return PTV_ERR_ARG;
   if ((dtypes & 8) && ((N & 31) || splitk > 1)) return PTV_ERR_ARG;  // column-blocked C: whole 32- / 16-column blocks, one writer per element
   if ((dtypes & 16) && ((N & 15) || splitk > 1)) return PTV_ERR_ARG;
