@@ -850,6 +850,29 @@ int ptv_pack_mfma_b2(const float* W, long ld, int N, int K, void* out, int pairs
 int ptv_pack_mfma_multi(const long* jobs, int n, void* stream);
 int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitch, int B, int t, unsigned coin_mask, int train,
                        void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Sampled decode: seeded temperature sampling of the free-running decoder's pitch and duration decisions (DESIGN.md "Sampled decode").
+ * The sampling block is 32 bytes of DEVICE memory { uint64 seed, uint64 draw, int64 sample_offset, float T_pitch, float T_dur } that the
+ * kernels read when they run (a captured graph holds the pointer).  The pitch decision of (row b, time step t, note step n) is the first
+ * maximal index over c < 130 of logit[c] + T_pitch * g[b, t, n, c]; duration bit d is 1 iff e1 + T_dur * g1 > e0 + T_dur * g0, with
+ * g = -log(-log(u)) standard Gumbel, u = (top 23 bits of a Philox4x32-10 word + 1/2) * 2^-23, the word a pure function of (seed, draw,
+ * sample_offset + b, t, n, kind, index) (csrc/philox.hpp).  T = 0 is the argmax, ties included.  The logits written out are the plain ones;
+ * force_pitch / force_dur still override.  Inference only: with train != 0 or teacher-forcing coins every entry point returns PTV_ERR_ARG.
+ *   ptv_free_note_loop: bit 23 of train announces the block as io[21] (io then has 22 entries; without the bit io[21] is not read).
+ *   ptv_note_token_sample / ptv_dur_out_token_sample / ptv_dur_gru_fwd_sample: ptv_note_token / ptv_dur_out_token / ptv_dur_gru_fwd with the
+ *     block and the position of the rows: row r is sample sample_offset + r at time step t; note step n = 0..14 for the duration forms,
+ *     the duration bit d for ptv_dur_out_token_sample; ptv_note_token_sample decides note step n - 1 (its n is the slot it fills, 1..15).
+ */
+int ptv_note_token_sample(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
+                          float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
+                          const int* force_pitch, int M, const void* sample, int t, void* stream);
+int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
+                             int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream);
+int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,
+                           const float* tab0, const float* tab, const float* w_out, const float* b_out,
+                           float* hall, long plane_h, void* hall16, void* gates, long plane_g, long step_g, int gates_bf16,
+                           float* dur_out, long ld_out, int* idx, long idx_stride, const int* force, long force_stride,
+                           const void* sample, int t, int n, void* stream);
 int ptv_free_resummarize(const void* const* w, const void* const* io, int B, int t, int train, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -893,6 +916,8 @@ enum PtvDffTensor {
   PTV_DFF_IDX, PTV_DFF_PLEN, PTV_DFF_GC16, PTV_DFF_DUR_SCR, PTV_DFF_IDX_SCR,
   PTV_DFF_XH0, PTV_DFF_XH1, PTV_DFF_XH16_0, PTV_DFF_XH16_1, PTV_DFF_XG0, PTV_DFF_XG1,
   PTV_DFF_WAIT_EVENT, PTV_DFF_RECORD_EVENT,   /* hipEvent_t or NULL: the persistent-launch turn around the cluster-mode note loops */
+  PTV_DFF_SAMPLE,           /* NULL, or the sampling block of a sampled decode (32 bytes on the device, "Sampled decode" below): D_INFERENCE only,
+                             * anything else is PTV_ERR_ARG before the first launch */
   PTV_DFF_COUNT
 };
 enum PtvDffDim {

@@ -40,6 +40,11 @@ int ptv_prof_read_segmented(int tag, double* seg);
  * Process-wide; PTV_WGRAD_BATCH=0 sets it at load. */
 int ptv_wgrad_batch_mode(int batched);
 
+/* test aid of the sampled decode (ptvae_hip.h "Sampled decode"): the Gumbel values the decoder uses for rows [0, rows) -- samples
+ * sample_offset + row of the block -- at time step t, note step n, through the decoder's own device functions: out_pitch [rows, 130],
+ * out_dur [rows, 5, 2] (duration bit d: class 0, class 1) */
+int ptv_debug_sample_noise(const void* block, long rows, int t, int n, float* out_pitch, float* out_dur, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -637,6 +637,7 @@ extern "C" int ptv_decoder_free_fwd(const void* const* t, const long* d, const v
   if (B <= 0 || E != 128 || He != 128 || Hn != 512 || Hd != 64 || NP != 130 || Ht <= 0 || (Ht & 7) || Zs <= 0 || Zi <= 0 || ldp < NP)
     return PTV_ERR_UNSUPPORTED;
   if (replay && !train) return PTV_ERR_ARG;
+  if (t[PTV_DFF_SAMPLE] && (!inference || train)) return PTV_ERR_ARG;           // sampling is inference only
   bool need_resum = inference;
   for (int i = 0; i < 31 && !need_resum; i++) need_resum = !time_coin[i];
   {
@@ -686,7 +687,16 @@ extern "C" int ptv_decoder_free_fwd(const void* const* t, const long* d, const v
   float* h0gc = M_<float>(t, PTV_DFF_H0GC);
   if (io[18] != (const void*)h0gc) return PTV_ERR_ARG;
   __bf16* gates_t = M_<__bf16>(t, PTV_DFF_GATES_T);
-  const int loop_flags = (int)d[PTV_DFF_D_LOOP_FLAGS], cluster = (int)d[PTV_DFF_D_CLUSTER];
+  int loop_flags = (int)d[PTV_DFF_D_LOOP_FLAGS];
+  const int cluster = (int)d[PTV_DFF_D_CLUSTER];
+  // sampled decode: the note loop's io table with the sampling block as its 22nd entry, announced by bit 23 of the `train` word
+  const void* io_s[22];
+  if (t[PTV_DFF_SAMPLE]) {
+    for (int i = 0; i < 21; i++) io_s[i] = io[i];
+    io_s[21] = t[PTV_DFF_SAMPLE];
+    io = io_s;
+    loop_flags |= 0x800000;
+  } else if (loop_flags & 0x800000) return PTV_ERR_ARG;
   const void* ior_[7];
   if (need_resum) for (int i = 0; i < 7; i++) ior_[i] = ior[i];
   if (cluster && t[PTV_DFF_WAIT_EVENT] && hipStreamWaitEvent(s, (hipEvent_t)const_cast<void*>(t[PTV_DFF_WAIT_EVENT]), 0) != hipSuccess) return PTV_ERR_LAUNCH;

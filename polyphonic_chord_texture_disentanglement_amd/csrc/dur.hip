@@ -15,6 +15,7 @@
 // bf16 precision, H = 64 only (the init_model() configuration); other shapes use the per-step kernels.
 #include "common.hpp"
 #include "gemm_core.hpp"
+#include "philox.hpp"
 #include "../../include/ptvae_hip.h"
 
 namespace ptv {
@@ -49,8 +50,10 @@ struct DurArgs {
   const int* m_top; long m_unit;       // or null: only the rows below (*m_top + 1) * m_unit are wanted; the others stay unwritten
   const int* row_len;                  // or null (needs m_top): rows of a step sorted by descending length, [m_unit] live note steps per row -- a
                                        // tile inside a 128-row block whose first row has no target at its note step is passed over
+  const SampleBlock* samp; int t, n;   // SAMP = 1: row r is sample r at (t, n), the five decisions are draws (philox.hpp)
 };
 
+template <int SAMP>
 __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
   __builtin_amdgcn_s_setprio(3);                                         // a launch of the latency chain: wins instruction issue against sibling-stream products
   __shared__ __attribute__((aligned(16))) __bf16 Ws[3 * DH * DLD];       // W_hh as bf16
@@ -155,7 +158,14 @@ __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
       o0 += __shfl_xor(o0, 16, 64); o1 += __shfl_xor(o1, 16, 64);
       o0 += __shfl_xor(o0, 32, 64); o1 += __shfl_xor(o1, 32, 64);
       o0 += wo[2 * DH]; o1 += wo[2 * DH + 1];
-      int id = o1 > o0 ? 1 : 0;                                           // first max wins ties (torch.max)
+      float x0 = o0, x1 = o1;
+      if constexpr (SAMP) {
+        const SampleBlock sb = *a.samp;
+        float g0, g1;
+        dur_gumbel2(sb, sb.sample_offset + row, a.t, a.n, d, g0, g1);
+        x0 = perturbed(o0, sb.t_dur, g0); x1 = perturbed(o1, sb.t_dur, g1);
+      }
+      int id = x1 > x0 ? 1 : 0;                                           // first max wins ties (torch.max)
       if (a.force && ok) id = a.force[d * a.force_stride + row];
       if (ok && lane < 16) {
         a.dur_out[row * a.ld_out + 2 * d] = o0;
@@ -209,11 +219,30 @@ extern "C" int ptv_dur_gru_fwd_rows(int H, long M, const float* h0, long ld_h0, 
   if (M <= 0 || !h0 || !w_hh || !b_hh || !tab0 || !tab || !w_out || !b_out || !dur_out || !idx) return PTV_ERR_ARG;
   if ((ld_h0 & 3) || (plane_h & 7) || (plane_g & 7) || (step_g & 7)) return PTV_ERR_ARG;      // 16-byte bf16 pieces
   DurArgs a{h0, ld_h0, w_hh, b_hh, tab0, tab, w_out, b_out, hall, plane_h, (__bf16*)hall16, gates, plane_g, step_g, gates_bf16,
-            dur_out, ld_out, idx, idx_stride, force, force_stride, M, m_top, m_unit, row_len};
+            dur_out, ld_out, idx, idx_stride, force, force_stride, M, m_top, m_unit, row_len, nullptr, 0, 0};
   // grid: whole rounds of resident blocks (3 per CU: 44.5 KB of LDS each) -- 1024 blocks on 256 CUs were 1 1/3 rounds, the last one a third full
   const int cap = 3 * num_cus();                               // (512 / 768 / 1024 / 2048 blocks: 247 / 276 / 247 / 251 us -- it does not matter)
   long nb = ((M + 15) / 16 + 3) / 4; if (nb > cap) nb = cap; if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(dur_gru_fwd_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(dur_gru_fwd_kernel<0>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// the sampled form of the step loop: rows [0, M) are samples [0, M) of ONE (time step, note step)
+extern "C" int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,
+                                      const float* tab0, const float* tab, const float* w_out, const float* b_out,
+                                      float* hall, long plane_h, void* hall16, void* gates, long plane_g, long step_g, int gates_bf16,
+                                      float* dur_out, long ld_out, int* idx, long idx_stride, const int* force, long force_stride,
+                                      const void* sample, int t, int n, void* stream) {
+  if (H != DH) return PTV_ERR_ARG;
+  if (M <= 0 || !h0 || !w_hh || !b_hh || !tab0 || !tab || !w_out || !b_out || !dur_out || !idx) return PTV_ERR_ARG;
+  if ((ld_h0 & 3) || (plane_h & 7) || (plane_g & 7) || (step_g & 7)) return PTV_ERR_ARG;
+  if (!sample || t < 0 || t >= 32 || n < 0 || n >= 15) return PTV_ERR_ARG;
+  DurArgs a{h0, ld_h0, w_hh, b_hh, tab0, tab, w_out, b_out, hall, plane_h, (__bf16*)hall16, gates, plane_g, step_g, gates_bf16,
+            dur_out, ld_out, idx, idx_stride, force, force_stride, M, nullptr, 0, nullptr, (const SampleBlock*)sample, t, n};
+  const int cap = 3 * num_cus();
+  long nb = ((M + 15) / 16 + 3) / 4; if (nb > cap) nb = cap; if (nb < 1) nb = 1;
+  hipLaunchKernelGGL(dur_gru_fwd_kernel<1>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "prof.hpp"
 #include "gemm_core.hpp"
+#include "philox.hpp"
 #include "../../include/ptvae_hip.h"
 
 namespace ptv {
@@ -210,6 +211,7 @@ struct NoteLoopArgs {
   int S;
   __bf16* xch;                     // [panels][2][16][512] bf16 exchange buffer
   unsigned* cnt;                   // [panels] arrival counters (zeroed by the caller before t = 0) + [1] error word
+  const SampleBlock* samp;         // SAMP instantiations: the sampling parameters (device block); null otherwise
 };
 
 // lane-exchange helpers of the RES = 1 kernel (VALU, no LDS round trip; same operands and the same order of additions as the __shfl_xor forms)
@@ -239,7 +241,9 @@ template <int N> __device__ __forceinline__ void argmax_ror(float& best, int& bi
 // only: 2 KB) and the logits part of dur_hid_linear (20 KB) in LDS, the state part of dur_hid_linear is requested when the head
 // phase begins and consumed two phases later, the predicted token's embedding row right after the argmax.  The head phases then
 // hold no exposed L2 round trip (RES = 0 had 8 + 1 + 1 of them per note step on wave 0).  Same products, same k order: bit-identical.
-template <int RES, int NUK = 2>                                  // NUK = 1: the eight-member cluster's kernel (one unit tile per wave and note step)
+// SAMP = 1: the decisions are draws from softmax(logits / T) -- Gumbel noise keyed by (seed, draw, GLOBAL sample, t, n) is added to the values
+// the argmax reduces (philox.hpp); the logits written out stay the plain ones.  Every member of a cluster draws the same noise for a row.
+template <int RES, int NUK = 2, int SAMP = 0>                    // NUK = 1: the eight-member cluster's kernel (one unit tile per wave and note step)
 __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
   __shared__ __attribute__((aligned(16))) bf16x8 wp8[RES ? 16 * 4 * 2 : 1];   // pitch-head tile 8, rows 128 / 129 only: [kb][quad][row]
   __shared__ __attribute__((aligned(16))) bf16x8 wdp[RES ? 4 * 5 * 64 : 1];   // dur_hid_linear, logits part (4 tiles x 5 k-blocks)
@@ -333,6 +337,8 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
     bdh_r = *reinterpret_cast<const float4*>(a.b_dh + wave * 16 + ckq * 4);
   }
   float4 ew0 = make_float4(0.f, 0.f, 0.f, 0.f), ew1 = ew0;      // RES: embedding row of the decision, requested in P3
+  SampleBlock sb{};
+  if constexpr (SAMP) sb = *a.samp;
   // timing experiments (dbg_out): 100-MHz ticks wave 0 spends per phase, summed over the 15 note steps -> dbg_out[3 * grid + 8 * block + i],
   // i = 0 cell (products + epilogue), 1 barrier + state exchange, 2 pitch head, 3 argmax + dur_hid, 4 duration GRU, 5 token embedding
   long tph[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;
@@ -568,11 +574,23 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
 #pragma unroll
         for (int k = 0; k < 9; k++) pv[k] = pit[row][j + 16 * k];              // (columns 130..143 of the row exist and hold zeros)
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (SAMP) {                                                  // the reduction sees logit + T * gumbel
+          float gum[9];
+          pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
+#pragma unroll
+          for (int k = 0; k < 9; k++) {
+            const int c = j + 16 * k;
+            const float x = perturbed(pv[k], sb.t_pitch, gum[k]);
+            const bool take = c < FNP && x > best;
+            best = take ? x : best; bi = take ? c : bi;
+          }
+        } else {
 #pragma unroll
         for (int k = 0; k < 9; k++) {
           const int c = j + 16 * k;
           const bool take = c < FNP && pv[k] > best;
           best = take ? pv[k] : best; bi = take ? c : bi;
+        }
         }
         argmax_ror<8>(best, bi); argmax_ror<4>(best, bi); argmax_ror<2>(best, bi); argmax_ror<1>(best, bi);
         if (ok) {
@@ -580,13 +598,17 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           for (int k = 0; k < 9; k++) if (j + 16 * k < FNP) a.pitch[pr * a.ld_pitch + j + 16 * k] = pv[k];
         }
       } else {
+      float gum[SAMP ? 9 : 1];
+      if constexpr (SAMP) pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
 #pragma unroll
       for (int k = 0; k < 9; k++) {
         const int c = j + 16 * k;
         if (c < FNP) {
           const float v = pit[row][c];
           if (ok) a.pitch[pr * a.ld_pitch + c] = v;
-          if (v > best) { best = v; bi = c; }
+          float x = v;
+          if constexpr (SAMP) x = perturbed(v, sb.t_pitch, gum[k]);
+          if (x > best) { best = x; bi = c; }
         }
       }
 #pragma unroll
@@ -660,11 +682,20 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
 #pragma unroll
         for (int kb = 0; kb < 2; kb++) av[kb] = *reinterpret_cast<const bf16x8*>(&hd16[0][crow][kb * 32 + ckq * 8]);
         float2 q[4] = {};
+        float dn[SAMP ? 10 : 1];                                               // SAMP: T * gumbel of this lane's row, [2 d + class]
+        if constexpr (SAMP) {
+          float gum[10];
+          dur_gumbel10(sb, sb.sample_offset + rC, t, n, gum);
+#pragma unroll
+          for (int i = 0; i < 10; i++) dn[i] = sb.t_dur * gum[i];
+        }
         int dtk = 0;                                                           // this lane's row: 0 = <sos>, 1 + previous decision
         auto decide = [&](int d) {                                             // logits and decision of duration step d from the four waves' partial sums
           const float e0 = q[0].x + q[1].x + q[2].x + q[3].x + wb0;
           const float e1 = q[0].y + q[1].y + q[2].y + q[3].y + wb1;
-          int id = e1 > e0 ? 1 : 0;                                             // first max wins ties (torch.max)
+          float x0 = e0, x1 = e1;
+          if constexpr (SAMP) { x0 = e0 + dn[2 * d]; x1 = e1 + dn[2 * d + 1]; }
+          int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
           if (a.force_dur) id = a.force_dur[(long)d * M + prC];
           dtk = 1 + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
@@ -796,7 +827,13 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
             e0 = part[dc][0][crow][0] + part[dc][1][crow][0] + part[dc][2][crow][0] + part[dc][3][crow][0] + wo[2 * FHD];
             e1 = part[dc][0][crow][1] + part[dc][1][crow][1] + part[dc][2][crow][1] + part[dc][3][crow][1] + wo[2 * FHD + 1];
           }
-          int id = e1 > e0 ? 1 : 0;                                             // first max wins ties (torch.max)
+          float x0 = e0, x1 = e1;
+          if constexpr (SAMP) {                                                 // (a runtime d: one call per step instead of an indexed register array)
+            float g0, g1;
+            dur_gumbel2(sb, sb.sample_offset + rC, t, n, d, g0, g1);
+            x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
+          }
+          int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
           if (a.force_dur) id = a.force_dur[(long)d * M + prC];
           dtk = 1 + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
@@ -892,6 +929,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
 //   producers: token part + epilogue | B0 | segment 1 | B1 | ... | segment 8 | B8
 //   heads:                      wait | B0 | pitch head | B1 | argmax, dur_hid | B2 | dur step 0..4 | B3..B7 | embedding | B8
 // =============================================================================================
+template <int SAMP = 0>
 __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
   __shared__ __attribute__((aligned(16))) float hf[FP][FHN];                   // notes-GRU state, fp32
   __shared__ __attribute__((aligned(16))) __bf16 h16[2][FP][H16LD];            // its bf16 MFMA-operand copy (double buffered)
@@ -920,6 +958,8 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
   const int rE = min(r0 + erow, B - 1), rC = min(r0 + crow, B - 1);
   const bool okE = r0 + erow < B, okC = r0 + crow < B;
   const long wrowE = (long)t * B + rE, wrowC = (long)t * B + rC;   // row in the [R]-row step-major matrices
+  SampleBlock sb{};
+  if constexpr (SAMP) sb = *a.samp;
 
   // ---- one-time loads: duration GRU weights / tables -> LDS, initial state and first token -> LDS
   for (int i = tid0; i < 12 * 2 * 64; i += 512) wdl[i] = a.wdur[i];
@@ -1063,11 +1103,17 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
     }
   } else {
     // the decision of duration step d for `row` from the four waves' partial sums (complete after that step's barrier)
-    auto dur_decision = [&](int d, int row, long pr) {
+    auto dur_decision = [&](int n, int d, int row, long pr) {
       const int dc = d & 1;
       const float e0 = part[dc][0][row][0] + part[dc][1][row][0] + part[dc][2][row][0] + part[dc][3][row][0] + wo[2 * FHD];
       const float e1 = part[dc][0][row][1] + part[dc][1][row][1] + part[dc][2][row][1] + part[dc][3][row][1] + wo[2 * FHD + 1];
-      int id = e1 > e0 ? 1 : 0;
+      float x0 = e0, x1 = e1;
+      if constexpr (SAMP) {
+        float g0, g1;
+        dur_gumbel2(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, d, g0, g1);
+        x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
+      }
+      int id = x1 > x0 ? 1 : 0;
       if (a.force_dur) id = a.force_dur[(long)d * M + pr];
       return id;
     };
@@ -1101,13 +1147,17 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       float best = -INFINITY; int bi = 0x7fffffff;
       const long pr = (long)n * R + (long)t * B + min(r0 + row, B - 1);
       const bool ok = r0 + row < B;
+      float gum[SAMP ? 9 : 1];
+      if constexpr (SAMP) pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
 #pragma unroll
       for (int k = 0; k < 9; k++) {
         const int c = j + 16 * k;
         if (c < FNP) {
           const float v = pit[row][c];
           if (ok) a.pitch[pr * a.ld_pitch + c] = v;
-          if (v > best) { best = v; bi = c; }
+          float x = v;
+          if constexpr (SAMP) x = perturbed(v, sb.t_pitch, gum[k]);
+          if (x > best) { best = x; bi = c; }
         }
       }
 #pragma unroll
@@ -1185,7 +1235,13 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         {
           const float e0 = part[dc][0][crow][0] + part[dc][1][crow][0] + part[dc][2][crow][0] + part[dc][3][crow][0] + wo[2 * FHD];
           const float e1 = part[dc][0][crow][1] + part[dc][1][crow][1] + part[dc][2][crow][1] + part[dc][3][crow][1] + wo[2 * FHD + 1];
-          int id = e1 > e0 ? 1 : 0;                                             // first max wins ties (torch.max)
+          float x0 = e0, x1 = e1;
+          if constexpr (SAMP) {
+            float g0, g1;
+            dur_gumbel2(sb, sb.sample_offset + rC, t, n, d, g0, g1);
+            x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
+          }
+          int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
           if (a.force_dur) id = a.force_dur[(long)d * M + prC];
           dtk = 1 + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
@@ -1204,7 +1260,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       const bool ok = r0 + row < B;
       const long wr = (long)t * B + min(r0 + row, B - 1);
       const int pch = pidx[row];
-      const int last_bit = dur_decision(4, row, (long)n * R + wr);
+      const int last_bit = dur_decision(n, 4, row, (long)n * R + wr);
       float v[8];
       const float4 b0 = *reinterpret_cast<const float4*>(a.b_emb + e0), b1 = *reinterpret_cast<const float4*>(a.b_emb + e0 + 4);
       const float4 w0 = *reinterpret_cast<const float4*>(a.w_embT + (long)pch * FE + e0), w1 = *reinterpret_cast<const float4*>(a.w_embT + (long)pch * FE + e0 + 4);
@@ -1243,7 +1299,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         xr[0] = pb;
 #pragma unroll
         for (int d = 0; d < 4; d++) xr[1 + d] = bits[tid][d];
-        xr[5] = dur_decision(4, tid, (long)n * R + (long)t * B + rw);
+        xr[5] = dur_decision(n, 4, tid, (long)n * R + (long)t * B + rw);
         int L = a.plen[(long)t * B + rw];
         if (L == 0 && pb == 129) L = n + 1;                                     // first <eos>            (ptvae.py:415-416)
         if (n == 14 && L == 0) L = n + 1;                                       // no <eos> by the end     (ptvae.py:425)
@@ -1466,6 +1522,7 @@ extern "C" int ptv_pack_mfma_b(const float* W, long ld, int N, int K, void* out,
 }
 
 // w[16]: wg_h, wg_t, wp, wd_h, wd_p, wdur (packed bf16), b_hh_n, b_p, b_dh, b_hh_d, tab0, tab, w_out, b_out, w_embT, b_emb
+// train bit 23: io has a 22nd entry, the sampling block (inference only); without the bit io[21] is never read
 // io[21]: gc, emb, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16, dbg words, h0gc,
 //         xch, cnt (cluster mode, train bits 18-20 = S in {2, 4}: S workgroups per 16-sample panel, ptvae_hip.h)
 extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitch, int B, int t, unsigned coin_mask, int train,
@@ -1475,7 +1532,10 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   if ((!io[0] && !io[18]) || !io[2] || !io[4] || !io[7] || !io[8] || !io[9] || !io[10] || !io[11] || !io[12]) return PTV_ERR_ARG;
   if ((train & 3) == 1 && (!io[3] || !io[5] || !io[6])) return PTV_ERR_ARG;
   if (coin_mask && !io[1]) return PTV_ERR_ARG;
+  const bool samp = (train & 0x800000) != 0;
+  if (samp && ((train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG;     // sampling is inference only
   NoteLoopArgs a{};
+  a.samp = samp ? (const SampleBlock*)io[21] : nullptr;
   a.wg_h = (const bf16x8*)w[0]; a.wg_t = (const bf16x8*)w[1]; a.wp = (const bf16x8*)w[2]; a.wd_h = (const bf16x8*)w[3];
   a.wd_p = (const bf16x8*)w[4]; a.wdur = (const bf16x8*)w[5];
   a.b_hh_n = (const float*)w[6]; a.b_p = (const float*)w[7]; a.b_dh = (const float*)w[8]; a.b_hh_d = (const float*)w[9];
@@ -1514,11 +1574,17 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   const int pi = prof::want(7, B, FHN) ? prof::begin((hipStream_t)stream) : -1;
   if (!split) {
     const dim3 grid(a.S > 1 ? (panels + 7) / 8 * 8 * a.S : panels);
-    if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    if (samp) {
+      if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
+      else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL((note_loop_kernel<1, 2, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    }
+    else if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);   // bit 21: head weights streamed (timing comparisons)
     else hipLaunchKernelGGL((note_loop_kernel<1, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
   }
-  else hipLaunchKernelGGL(note_loop2_kernel, dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
+  else if (samp) hipLaunchKernelGGL((note_loop2_kernel<1>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((note_loop2_kernel<0>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
   if (pi >= 0) prof::end(pi, (hipStream_t)stream, 15.0 * B * (2.0 * 3 * FHN * (FHN + 128) + 2.0 * 130 * FHN + 2.0 * 64 * (FHN + 130) + 5 * 2.0 * 3 * 64 * 64 + 2.0 * 128 * 135));
   PTV_CHECK_LAUNCH();
   return PTV_OK;

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include "common.hpp"
 #include "gemm_core.hpp"
+#include "philox.hpp"
 #include "../../include/ptvae_hip.h"
 #include "../../include/ptvae_hip_debug.h"
 
@@ -11,8 +12,10 @@ int g_zero_skip = 1;
 
 // est_dur = dur_out_linear(h) (ptvae.py:361-362), next token index = argmax (ptvae.py:365-367).
 // 16 lanes per row (float4 each covers H <= 64 ... loops for larger H), 4 rows per wave.
+template <int SAMP>                    // SAMP = 1: row r is sample r at (t, n), the decision of duration bit d a draw (philox.hpp)
 __global__ void dur_out_token_kernel(const float* __restrict__ h, int H, const float* __restrict__ w_out, const float* __restrict__ b_out,
-                                     float* __restrict__ dur_out, long ld_out, int* __restrict__ idx, const int* __restrict__ force_idx, long rows) {
+                                     float* __restrict__ dur_out, long ld_out, int* __restrict__ idx, const int* __restrict__ force_idx, long rows,
+                                     const SampleBlock* __restrict__ samp, int t, int n, int d) {
   const int sub = threadIdx.x & 15;
   const long rpb = blockDim.x / 16;
   for (long r = (long)blockIdx.x * rpb + threadIdx.x / 16; r < rows; r += (long)gridDim.x * rpb) {
@@ -23,7 +26,14 @@ __global__ void dur_out_token_kernel(const float* __restrict__ h, int H, const f
     if (sub == 0) {
       s0 += b_out[0]; s1 += b_out[1];
       dur_out[r * ld_out + 0] = s0; dur_out[r * ld_out + 1] = s1;
-      if (idx) idx[r] = force_idx ? force_idx[r] : (s1 > s0 ? 1 : 0);      // first max wins ties (torch.max)
+      float x0 = s0, x1 = s1;
+      if constexpr (SAMP) {
+        const SampleBlock sb = *samp;
+        float g0, g1;
+        dur_gumbel2(sb, sb.sample_offset + r, t, n, d, g0, g1);
+        x0 = perturbed(s0, sb.t_dur, g0); x1 = perturbed(s1, sb.t_dur, g1);
+      }
+      if (idx) idx[r] = force_idx ? force_idx[r] : (x1 > x0 ? 1 : 0);      // first max wins ties (torch.max)
     }
   }
 }
@@ -127,15 +137,21 @@ __global__ void clip_adam_kernel(float* __restrict__ p, const float* __restrict_
 // (pitch, bits) and the running predicted length (first <eos> position; 15 if none by the last step).
 // One wave per row.
 // ---------------------------------------------------------------------------------------------
+template <int SAMP>                    // SAMP = 1: row r is sample r at (t, note step n - 1), the pitch decision a draw (philox.hpp)
 __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch, const int* __restrict__ dur_idx, long dur_stride,
                                   const float* __restrict__ W, const float* __restrict__ bias, int E,
                                   float* __restrict__ pred, long ld_pred, long* __restrict__ xhat, long xhat_stride,
-                                  int* __restrict__ plen, int n, int last, const int* __restrict__ force_pitch, int M) {
+                                  int* __restrict__ plen, int n, int last, const int* __restrict__ force_pitch, int M,
+                                  const SampleBlock* __restrict__ samp, int t) {
   const int lane = threadIdx.x & 63;
   for (int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < M; r += gridDim.x * (blockDim.x >> 6)) {
     const float* lr = pitch + (long)r * ld_pitch;
     float best = -INFINITY; int bi = 0x7fffffff;
-    for (int c = lane; c < 130; c += 64) { float v = lr[c]; if (v > best) { best = v; bi = c; } }
+    for (int c = lane; c < 130; c += 64) {
+      float v = lr[c];
+      if constexpr (SAMP) { const SampleBlock sb = *samp; v = perturbed(v, sb.t_pitch, pitch_gumbel1(sb, sb.sample_offset + r, t, n - 1, c)); }
+      if (v > best) { best = v; bi = c; }
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       float ov = __shfl_xor(best, o, 64); int oi = __shfl_xor(bi, o, 64);
@@ -203,7 +219,19 @@ extern "C" int ptv_dur_out_token(const float* h, int H, const float* w_out, cons
                                  int* idx, const int* force_idx, long rows, void* stream) {
   if (!h || !w_out || !b_out || !dur_out || rows <= 0 || H <= 0) return PTV_ERR_ARG;
   long nb = (rows + 15) / 16; if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(dur_out_token_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, h, H, w_out, b_out, dur_out, ld_out, idx, force_idx, rows);
+  hipLaunchKernelGGL(dur_out_token_kernel<0>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, h, H, w_out, b_out, dur_out, ld_out, idx, force_idx, rows,
+                     nullptr, 0, 0, 0);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+extern "C" int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
+                                        int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream) {
+  if (!h || !w_out || !b_out || !dur_out || rows <= 0 || H <= 0) return PTV_ERR_ARG;
+  if (!sample || t < 0 || t >= 32 || n < 0 || n >= 15 || d < 0 || d >= 5) return PTV_ERR_ARG;
+  long nb = (rows + 15) / 16; if (nb > 8192) nb = 8192;
+  hipLaunchKernelGGL(dur_out_token_kernel<1>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, h, H, w_out, b_out, dur_out, ld_out, idx, force_idx, rows,
+                     (const SampleBlock*)sample, t, n, d);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }
@@ -300,8 +328,20 @@ extern "C" int ptv_note_token(const float* pitch, long ld_pitch, const int* dur_
                               const int* force_pitch, int M, void* stream) {
   if (!pitch || !dur_idx || !W || !bias || !pred || !xhat || !plen || M <= 0 || E <= 0) return PTV_ERR_ARG;
   int nb = (M + 3) / 4; if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(note_token_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
-                     pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M);
+  hipLaunchKernelGGL(note_token_kernel<0>, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
+                     pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M, nullptr, 0);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+extern "C" int ptv_note_token_sample(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
+                                     float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
+                                     const int* force_pitch, int M, const void* sample, int t, void* stream) {
+  if (!pitch || !dur_idx || !W || !bias || !pred || !xhat || !plen || M <= 0 || E <= 0) return PTV_ERR_ARG;
+  if (!sample || t < 0 || t >= 32 || n < 1 || n > 15) return PTV_ERR_ARG;
+  int nb = (M + 3) / 4; if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(note_token_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
+                     pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M, (const SampleBlock*)sample, t);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

@@ -6,20 +6,11 @@
 // four 32-bit words -> two Box-Muller pairs.  One batch on one GPU and the same batch split over N ranks (row_offset =
 // rank * B_local) see identical noise; `stream` separates draws (training step x {chd, rhy}).
 #include "common.hpp"
+#include "philox.hpp"
 #include "../../include/ptvae_hip.h"
+#include "../../include/ptvae_hip_debug.h"
 
 namespace ptv {
-
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 
 __global__ void philox_normal_kernel(float* __restrict__ out, long rows, int Z, unsigned long long seed, unsigned long long stream,
                                      long row_offset) {
@@ -45,6 +36,25 @@ __global__ void philox_normal_kernel(float* __restrict__ out, long rows, int Z, 
   }
 }
 
+// the Gumbel values the sampling decoder uses for rows [0, rows) at (t, n), through the decoder's own device functions (philox.hpp)
+__global__ void sample_noise_kernel(const SampleBlock* __restrict__ blk, long rows, int t, int n, float* __restrict__ out_pitch,
+                                    float* __restrict__ out_dur) {
+  const SampleBlock sb = *blk;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < rows * 16; i += (long)gridDim.x * blockDim.x) {
+    const long r = i >> 4; const int j = (int)(i & 15);
+    float g[9];
+    pitch_gumbel9(sb, sb.sample_offset + r, t, n, j, g);
+#pragma unroll
+    for (int k = 0; k < 9; k++) if (j + 16 * k < 130) out_pitch[r * 130 + j + 16 * k] = g[k];
+    if (j == 0) {
+      float d[10];
+      dur_gumbel10(sb, sb.sample_offset + r, t, n, d);
+#pragma unroll
+      for (int q = 0; q < 10; q++) out_dur[r * 10 + q] = d[q];
+    }
+  }
+}
+
 }  // namespace ptv
 
 extern "C" int ptv_philox_normal(float* out, long rows, int Z, unsigned long long seed, unsigned long long stream_id, long row_offset,
@@ -52,6 +62,15 @@ extern "C" int ptv_philox_normal(float* out, long rows, int Z, unsigned long lon
   if (!out || rows <= 0 || Z <= 0 || Z > 4 * 65536 || row_offset < 0) return PTV_ERR_ARG;
   long nb = (rows * ((Z + 3) / 4) + 255) / 256; if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(ptv::philox_normal_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, out, rows, Z, seed, stream_id, row_offset);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+extern "C" int ptv_debug_sample_noise(const void* block, long rows, int t, int n, float* out_pitch, float* out_dur, void* stream) {
+  if (!block || !out_pitch || !out_dur || rows <= 0 || t < 0 || t >= 32 || n < 0 || n >= 15) return PTV_ERR_ARG;
+  long nb = (rows * 16 + 255) / 256; if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(ptv::sample_noise_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (const ptv::SampleBlock*)block, rows, t, n, out_pitch,
+                     out_dur);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

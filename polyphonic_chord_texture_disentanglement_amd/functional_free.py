@@ -83,6 +83,50 @@ LAST_CLUSTER_COUNTERS = None
 NOTE_LOOP_CLUSTER = None if os.environ.get('PTV_NOTE_CLUSTER') is None else int(os.environ['PTV_NOTE_CLUSTER'])
 
 
+# ---------------------------------------------------------------------------------------------
+# sampled decode (DESIGN.md "Sampled decode"): the decisions of the free-running decoder as seeded draws from softmax(logits / T).
+# The parameters travel as a 32-byte DEVICE block {uint64 seed, uint64 draw, int64 sample_offset, float T_pitch, float T_dur} that the
+# kernels read when they run -- a captured graph holds its address, so seed / draw / temperatures change without a new capture.
+# ---------------------------------------------------------------------------------------------
+SAMPLE_BIT = 0x800000           # ptv_free_note_loop's `train` word: io[21] is the sampling block
+
+
+def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, draw=0):
+    """(T_pitch, T_dur, sample_offset, seed, draw) validated -- ValueError before anything touches a GPU"""
+    import math
+    tp = 0.0 if temperature is None else temperature
+    td = tp if dur_temperature is None else dur_temperature
+    for name, v in (('temperature', tp), ('dur_temperature', td)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or math.isinf(v) or v < 0:
+            raise ValueError('%s must be a finite float >= 0, got %r' % (name, v))
+    for name, v, top in (('sample_offset', sample_offset, 1 << 47), ('seed', seed, 1 << 64), ('draw', draw, 1 << 63)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0 or v >= top:
+            raise ValueError('%s must be an integer in [0, 2^%d), got %r' % (name, top.bit_length() - 1, v))
+    return float(tp), float(td), sample_offset, seed, draw
+
+
+def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0):
+    """the block as four int64 words (host list)"""
+    import struct
+    tp, td, off, seed, draw = check_sampling(temperature, dur_temperature, sample_offset, seed, draw)
+    return [seed - (1 << 64) if seed >= (1 << 63) else seed, draw, off, struct.unpack('<q', struct.pack('<ff', tp, td))[0]]
+
+
+def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0):
+    """the device block of a sampled decode: PtvaeDecoder.decoder(..., sampling=block)"""
+    words = sampling_words(temperature, dur_temperature, seed, draw, sample_offset)
+    if torch.device(device).type != 'cuda':
+        raise RuntimeError('a sampled decode runs on the GPU: the sampling block lives in device memory (got device %s)' % (device,))
+    return torch.tensor(words, dtype=torch.int64, device=device)
+
+
+def _check_block(sampling, dev):
+    if not (torch.is_tensor(sampling) and sampling.dtype == torch.int64 and sampling.numel() == 4 and sampling.is_contiguous()
+            and sampling.device == dev):
+        raise ValueError('sampling must be a block made by functional_free.sampling_block() on the device of z')
+    return sampling
+
+
 def note_loop_cluster(B):
     panels = (B + 15) // 16
     ncu = _num_cu()
@@ -252,13 +296,22 @@ class DecoderStepState(F_.DecoderState):
 
 
 class DecoderStepFn(torch.autograd.Function):
-    """(z, emb [16,32,B,E] or None, xs [32B,2He] or None, coins, inference, force, prec, *params)
+    """(z, emb [16,32,B,E] or None, xs [32B,2He] or None, coins, inference, force, prec, *params[, sampling block])
     -> pitch [15,32,B,130], dur [15*32*B,5,2], xhat int64 [B,32,16,6] (predicted grid), dur idx"""
 
     @staticmethod
     def forward(ctx, z, emb, xs, coins, inference, force, prec, *params):
+        # the optional trailing argument: the sampling block of a sampled decode (inference only); absent = the argmax kernels
+        sampling = None
+        if len(params) == len(FREE_PARAM_NAMES) + 1:
+            sampling, params = params[-1], params[:-1]
         P = dict(zip(FREE_PARAM_NAMES, params))
         dev = z.device
+        if sampling is not None:
+            if not inference or any(any(r) for r in coins[0]) or any(coins[1]):
+                raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
+            _check_block(sampling, dev)
+        samp_bit = SAMPLE_BIT if sampling is not None else 0
         z = z.contiguous()
         B = z.shape[0]
         R = 32 * B
@@ -386,7 +439,7 @@ class DecoderStepFn(torch.autograd.Function):
                 tens=dict(NS=NS, NS16=NS16, Z_IN=z_in, ZG=zg, TOKS=TOKS, GATES_T=gates_t, TOK=TOK, PRED=PRED, PITCH=pitch, HN=HN, HN16=HN16,
                           GATES_N=gates_n, HD=HD, HD16=HD16, GATES_D=gates_d, IDX=idx, PLEN=plen, XH0=XH[0] if XH else None,
                           XH1=XH[1] if XH else None, XH16_0=XH16[0], XH16_1=XH16[1], XG0=XG[0] if XG else None, XG1=XG[1] if XG else None,
-                          TAB0=tab0, TAB=tab),
+                          TAB0=tab0, TAB=tab, SAMPLE=sampling),     # (the composite appends the block to the note loop's io itself)
                 coins=(coin_notes, coin_time), w_hh_t=w_hh_t, w_ih_t16=w_ih_t16, prec=prec, dev=dev, M=M, R=R)
             assert done, 'ptv_decoder_free_fwd declined a configuration free_persist_ok() accepted'
         # the first note token of every time step is the <sos> embedding (ptvae.py:388-392): one copy for all 32 steps
@@ -418,13 +471,13 @@ class DecoderStepFn(torch.autograd.Function):
                     for n in range(14):
                         mask |= int(bool(coin_notes[t][n])) << n
                 io = F_._parr([GCt, emb3, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16,
-                               None, H0GC, xch, xcnt])
+                               None, H0GC, xch, xcnt] + ([sampling] if sampling is not None else []))
                 # (cluster mode: the members of a panel spin on each other -- like every persistent launch it takes its turn, so that
                 # it is never half-resident next to another spinning grid, e.g. the chord decoder's on its sibling stream)
                 with (F_._PersistTurn() if cluster and not capturing else contextlib.nullcontext()):
                     call('ptv_free_note_loop', wl, io, pitch.stride(0), B, t, mask,
                          (2 if replay else int(train)) | (0 if NOTE_LOOP_SPLIT is None else (0x20000 if NOTE_LOOP_SPLIT else 0x10000))
-                         | cluster_bits(cluster), st)
+                         | cluster_bits(cluster) | samp_bit, st)
                 if t == 31:
                     break
                 if (not inference) and coin_time[t]:
@@ -442,22 +495,26 @@ class DecoderStepFn(torch.autograd.Function):
                 gemm(h, P['pitch_out_linear.weight'], pitch[pr], bias=P['pitch_out_linear.bias'], prec=prec)
                 gemm(h, w_dh[:, :Hn], HD[0][pr], bias=P['dur_hid_linear.bias'], prec=prec)
                 gemm(pitch[pr], w_dh[:, Hn:], HD[0][pr], acc=True, prec=prec)
+                smp = () if sampling is None else (ptr(sampling), t, n)          # sampled forms: the block and the (t, n) of the rows
                 if prec == 1 and Hd == 64 and F_.FUSED_DUR:
-                    call('ptv_dur_gru_fwd', Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tab0), ptr(tab),
+                    call('ptv_dur_gru_fwd' if sampling is None else 'ptv_dur_gru_fwd_sample', Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d),
+                         ptr(tab0), ptr(tab),
                          ptr(P['dur_out_linear.weight']), ptr(P['dur_out_linear.bias']), ptr(HD[1][pr]), M * Hd, None,
                          ptr(gates_d[0][0][pr]) if train else None, M * Hd, 4 * M * Hd, F_._bf(gates_d), ptr(dur2[pr]), 10,
-                         ptr(idx[0][pr]), M, ptr(force_dur[0][pr]) if force_dur is not None else None, M, st)
+                         ptr(idx[0][pr]), M, ptr(force_dur[0][pr]) if force_dur is not None else None, M, *smp, st)
                 else:
                     for d in range(5):
                         g_, g_ld, g_idx = (tab0, 0, None) if d == 0 else (tab, 3 * Hd, idx[d - 1][pr])
                         gru_step(prec, HD[d][pr], g_, g_ld, w_hh_d, b_hh_d, HD[d + 1][pr],
                                  gates=gates_d[d][:, pr] if train else None, plane=M * Hd, gi_idx=g_idx)
-                        call('ptv_dur_out_token', ptr(HD[d + 1][pr]), Hd, ptr(P['dur_out_linear.weight']),
+                        call('ptv_dur_out_token' if sampling is None else 'ptv_dur_out_token_sample', ptr(HD[d + 1][pr]), Hd,
+                             ptr(P['dur_out_linear.weight']),
                              ptr(P['dur_out_linear.bias']), ptr(dur2[pr][:, 2 * d:]), 10, ptr(idx[d][pr]),
-                             ptr(force_dur[d][pr]) if force_dur is not None else None, B, st)
-                call('ptv_note_token', ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(w_emb), ptr(b_emb), E,
+                             ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp + ((d,) if smp else ())), st)
+                call('ptv_note_token' if sampling is None else 'ptv_note_token_sample', ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(w_emb),
+                     ptr(b_emb), E,
                      ptr(PRED[n + 1][rows]), E, ptr(xhat[0, t, n + 1]), 32 * 16 * 6, ptr(plen[rows]), n + 1, int(n == 14),
-                     ptr(force_pitch[n][rows]) if force_pitch is not None else None, B, st)
+                     ptr(force_pitch[n][rows]) if force_pitch is not None else None, B, *(smp[:2] if smp else ()), st)
                 if n < 14:
                     use_gt = (not inference) and coin_notes[t][n]
                     copy2d(TOK[n + 1][rows], emb3[n + 1][rows] if use_gt else PRED[n + 1][rows])

@@ -46,6 +46,7 @@ class DisentangleVAE(PytorchModel):
         self.eps_source = None      # optional callable (name, shape, device) -> eps tensor (tests)
         self._philox = None         # (seed, global index of this process's first sample): see use_philox()
         self._draws = 0
+        self._sample_draws = 0      # draw number of the next sampled decode that names none (advances once per sampled decode)
 
     # ---- the texture encoder decides what the texture input is.  A TextureEncoder (init_model) reads the piano-roll pr_mat; a PtvaeEncoder
     # (init_model_detrended: the wiring of the reference's train.py:31-39) reads the detrended PianoTree grid dt_x, uint8 [B,32,16,39]
@@ -228,40 +229,88 @@ class DisentangleVAE(PytorchModel):
 
     # ---- model.py:124-131: free-running decode; est_x = the argmax grid the step loop produced on device
     # (identical to output_to_numpy's argmax of the returned logits, ptvae.py:537-544)
-    def inference_decode(self, z_chd, z_rhy):
+    #
+    # Sampled decode (keyword-only; INTEGRATION.md "Sampled decode").  temperature (pitch) / dur_temperature (duration bits; default: the
+    # pitch temperature), floats >= 0: every decision of the free-running decoder becomes a draw from softmax(logits / T) instead of the
+    # argmax (T = 0 is the argmax).  The draw is Philox noise keyed by (seed, draw, sample_offset + row, time step, note step): reproducible,
+    # independent of how a batch is cut.  seed / sample_offset default to use_philox()'s, else 7 / 0; draw defaults to a per-model counter
+    # that advances once per sampled decode.  temperature=None (default): the argmax decode, unchanged.  The same keywords pass through
+    # decode_to_inputs, reencode, inference, swap, posterior_sample, prior_sample and interp (sample index = row of the decoded batch).
+    @staticmethod
+    def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None):
+        """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode.  No side effect, no GPU"""
+        if temperature is None and dur_temperature is None:
+            if seed is not None or draw is not None or sample_offset is not None:
+                raise ValueError('seed / draw / sample_offset belong to a sampled decode: give a temperature')
+            return False
+        from .functional_free import check_sampling
+        check_sampling(temperature, dur_temperature, 0 if sample_offset is None else sample_offset, 0 if seed is None else seed,
+                       0 if draw is None else draw)
+        return True
+
+    def _sampling_words(self, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None):
+        """None (argmax decode) or the validated sampling block as host words -- ValueError for a bad value before anything is launched"""
+        if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset):
+            return None
+        from .functional_free import sampling_words
+        ph = self._philox or (7, 0)
+        words = sampling_words(temperature, dur_temperature, ph[0] if seed is None else seed, self._sample_draws if draw is None else draw,
+                               ph[1] if sample_offset is None else sample_offset)
+        if draw is None:
+            self._sample_draws += 1
+        return words
+
+    def _decode(self, z_chd, z_rhy, sampling):
+        """the free-running decode of both inference forms; `sampling`: keywords of a sampled decode"""
+        from .ptvae import _require_cuda
+        words = self._sampling_words(**sampling)
+        if words is not None:
+            _require_cuda(z_chd, 'DisentangleVAE sampled decode')
+            _require_cuda(z_rhy, 'DisentangleVAE sampled decode')
+        dec_z = torch.cat([z_chd, z_rhy], dim=-1)
+        block = None if words is None else torch.tensor(words, dtype=torch.int64, device=dec_z.device)
+        return self.decoder(dec_z, True, None, None, 0., 0., sampling=block)
+
+    def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None):
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
-            dec_z = torch.cat([z_chd, z_rhy], dim=-1)
-            self.decoder(dec_z, True, None, None, 0., 0.)
+            self._decode(z_chd, z_rhy, dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw,
+                                            sample_offset=sample_offset))
             est_x = self.decoder.last_xhat[:, :, 1:, :].cpu().numpy()
         return est_x
 
     # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
-    def decode_to_inputs(self, z_chd, z_rhy, max_notes=10):
+    def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
+                         sample_offset=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
-        pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch."""
+        pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
+        inference_decode's (the chord decoder keeps its argmax)."""
         from .ptvae import _require_cuda
+        sampling = dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset)
+        self._check_sampling(**sampling)                                # (bad values are a ValueError whatever device the inputs are on)
         _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
-            self.decoder(torch.cat([z_chd, z_rhy], dim=-1), True, None, None, 0., 0.)
+            self._decode(z_chd, z_rhy, sampling)
             pr_mat, notes, count, x, err = self.decoder.grid_to_pr_and_notes_batch(self.decoder.last_xhat, max_notes)
             c, _ = self.chd_decoder.decode_tokens(z_chd)
         return pr_mat, x, c, notes, count, err
 
-    def reencode(self, z_chd, z_rhy):
-        """(dist_chd, dist_rhy) of the music decoded from (z_chd, z_rhy): decode_to_inputs, then inference_encode"""
-        pr_mat, _, c, _, _, _ = self.decode_to_inputs(z_chd, z_rhy)
+    def reencode(self, z_chd, z_rhy, **sampling):
+        """(dist_chd, dist_rhy) of the music decoded from (z_chd, z_rhy): decode_to_inputs, then inference_encode; **sampling: the
+        keywords of a sampled decode (inference_decode)"""
+        pr_mat, _, c, _, _, _ = self.decode_to_inputs(z_chd, z_rhy, **sampling)
         return self.inference_encode(pr_mat, c)
 
     # ---- model.py:133-142
-    def inference(self, pr_mat, c, sample):
-        """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
+    def inference(self, pr_mat, c, sample, **sampling):
+        """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant; **sampling: the keywords of a sampled
+        decode (inference_decode), here and in swap / posterior_sample / prior_sample / interp"""
         if self.detrended:
             self._check_dt_x(pr_mat)                     # (a piano-roll here is a ValueError, not a shape crash inside a kernel)
         self.eval()
@@ -271,20 +320,20 @@ class DisentangleVAE(PytorchModel):
             dist_rhy = self._encode_texture(pr_mat)
             z_chd = self._rsample('chd', dist_chd) if sample else dist_chd.mean
             z_rhy = self._rsample('rhy', dist_rhy) if sample else dist_rhy.mean
-        return self.inference_decode(z_chd, z_rhy)
+        return self.inference_decode(z_chd, z_rhy, **sampling)
 
     # ---- model.py:144-148
-    def swap(self, pr_mat1, pr_mat2, c1, c2, fix_rhy, fix_chd):
+    def swap(self, pr_mat1, pr_mat2, c1, c2, fix_rhy, fix_chd, **sampling):
         """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant"""
         pr_mat = pr_mat1 if fix_rhy else pr_mat2
         c = c1 if fix_chd else c2
-        return self.inference(pr_mat, c, sample=False)
+        return self.inference(pr_mat, c, sample=False, **sampling)
 
     # ---- model.py:150-172
-    def posterior_sample(self, pr_mat, c, scale=None, sample_chd=True, sample_txt=True):
+    def posterior_sample(self, pr_mat, c, scale=None, sample_chd=True, sample_txt=True, **sampling):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
         if scale is None and sample_chd and sample_txt:
-            return self.inference(pr_mat, c, sample=True)
+            return self.inference(pr_mat, c, sample=True, **sampling)
         dist_chd, dist_rhy = self.inference_encode(pr_mat, c)
         if scale is not None:
             dist_chd = HipNormal(dist_chd.mean, dist_chd.scale * scale)
@@ -298,10 +347,10 @@ class DisentangleVAE(PytorchModel):
                 z_chd = dist_chd.mean
             if not sample_txt:
                 z_rhy = dist_rhy.mean
-        return self.inference_decode(z_chd, z_rhy)
+        return self.inference_decode(z_chd, z_rhy, **sampling)
 
     # ---- model.py:174-184
-    def prior_sample(self, x, c, sample_chd=False, sample_rhy=False, scale=1.):
+    def prior_sample(self, x, c, sample_chd=False, sample_rhy=False, scale=1., **sampling):
         """x: the texture encoder's input (the reference's name for this slot here) -- the piano-roll, or dt_x for the detrended variant"""
         dist_chd, dist_rhy = self.inference_encode(x, c)
         mean = torch.zeros_like(dist_rhy.mean)
@@ -312,15 +361,16 @@ class DisentangleVAE(PytorchModel):
             dist_rhy = HipNormal(mean, loc)
         with torch.no_grad():
             z_chd, z_rhy = self._rsample('chd', dist_chd), self._rsample('rhy', dist_rhy)
-        return self.inference_decode(z_chd, z_rhy)
+        return self.inference_decode(z_chd, z_rhy, **sampling)
 
     # ---- model.py:186-188
     def gt_sample(self, x):
         return x[:, :, 1:].cpu().numpy()
 
     # ---- model.py:190-209: decode int_count points on the path between two items' latent codes
-    def interp(self, pr_mat1, c1, pr_mat2, c2, interp_chd=False, interp_rhy=False, int_count=10):
-        """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant"""
+    def interp(self, pr_mat1, c1, pr_mat2, c2, interp_chd=False, interp_rhy=False, int_count=10, **sampling):
+        """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant; a sampled decode's sample
+        index is the row of the flattened [bs * int_count] batch"""
         dist_chd1, dist_rhy1 = self.inference_encode(pr_mat1, c1)
         dist_chd2, dist_rhy2 = self.inference_encode(pr_mat2, c2)
         z_chd1, z_rhy1, z_chd2, z_rhy2 = dist_chd1.mean, dist_rhy1.mean, dist_chd2.mean, dist_rhy2.mean
@@ -328,7 +378,7 @@ class DisentangleVAE(PytorchModel):
         z_rhys = self.interp_z(z_rhy1, z_rhy2, int_count) if interp_rhy else z_rhy1.unsqueeze(1).repeat(1, int_count, 1)
         bs = z_chds.size(0)
         estxs = self.inference_decode(z_chds.reshape(bs * int_count, -1).contiguous(),
-                                      z_rhys.reshape(bs * int_count, -1).contiguous())
+                                      z_rhys.reshape(bs * int_count, -1).contiguous(), **sampling)
         return estxs.reshape((bs, int_count, 32, 15, -1))
 
     # ---- model.py:211-216: [B,D] x [B,D] -> [B,int_count,D]; the reference loops over numpy rows on the host, here the

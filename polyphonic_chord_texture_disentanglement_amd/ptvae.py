@@ -272,6 +272,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         self.last_xhat = None              # predicted grid [B,32,16,6] int64 of the last step-loop decode
         self.use_graph = False             # replay inference decodes from a captured hipGraph
         self._graphs = {}
+        self.graph_captures = 0            # inference decodes captured so far (a sampled decode's seed / draw / temperatures need no new one)
         self._train_graphs = {}
         self._summary = None
         self.summaries_needed = True       # emb_x() starts the ground-truth note summaries early unless told they are dead values
@@ -281,15 +282,19 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         sd = dict(self.named_parameters())
         return [sd[n] for n in F_.DEC_PARAM_NAMES]
 
-    def _graph_decode(self, z, coins):
+    def _graph_decode(self, z, coins, sampling=None):
         """Free-running decode replayed from a captured hipGraph: the step loop is ~9,000 tiny launches whose
         order and arguments depend only on (B, precision) -- capture once, then one graph launch per call.
-        The graph holds raw parameter pointers, so it is re-captured if the parameter storage moves."""
+        The graph holds raw parameter pointers, so it is re-captured if the parameter storage moves.
+        A sampled decode is a graph of its own (other kernels); its sampling block is a static tensor refreshed before every
+        replay, so the key holds neither seed nor draw nor temperatures."""
         ps = self._params_free()
-        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps))
+        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), sampling is not None)
         ent = self._graphs.get(key)
         if ent is None:
             static_z = z.detach().clone()
+            if sampling is not None:
+                ps = ps + [sampling.clone()]
             cur = torch.cuda.current_stream()
             s = torch.cuda.Stream(device=z.device)
             s.wait_stream(cur)
@@ -299,10 +304,14 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 outs = FF_.DecoderStepFn.apply(static_z, None, None, coins, True, None, self._prec, *ps)
-            self._graphs.clear()
-            ent = self._graphs[key] = (g, static_z, outs)
-        g, static_z, outs = ent
+            for k in [k for k in self._graphs if k[-1] == key[-1]]:         # one graph per kind (argmax, sampled) is kept
+                del self._graphs[k]
+            self.graph_captures += 1
+            ent = self._graphs[key] = (g, static_z, outs, ps[-1] if sampling is not None else None)
+        g, static_z, outs, static_blk = ent
         static_z.copy_(z)
+        if static_blk is not None:
+            static_blk.copy_(sampling)
         g.replay()
         return outs
 
@@ -347,18 +356,23 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
                 time.append(random.random() < tfr1)
         return notes, time
 
-    def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None):
+    def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None):
+        """sampling: None (argmax decisions) or a block of functional_free.sampling_block() -- the decisions of the free-running decode
+        are then seeded draws from softmax(logits / T); inference only (ValueError otherwise, before any launch)"""
+        if sampling is not None and (not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None):
+            raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
         _require_cuda(z, 'PtvaeDecoder')
         B = z.size(0)
         if inference:
             assert x is None and lengths is None
             assert teacher_forcing_ratio1 == 0 and teacher_forcing_ratio2 == 0
             coins = ([[False] * (self.max_simu_note - 2)] * self.num_step, [False] * (self.num_step - 1))
+            smp = () if sampling is None else (FF_._check_block(sampling, z.device),)
             if self.use_graph and not torch.is_grad_enabled() and self.force_trace is None:
-                pitch, dur, xhat, idx = self._graph_decode(z, coins)
+                pitch, dur, xhat, idx = self._graph_decode(z, coins, sampling)
             else:
                 pitch, dur, xhat, idx = FF_.DecoderStepFn.apply(z, None, None, coins, True, self.force_trace, self._prec,
-                                                                *self._params_free())
+                                                                *self._params_free(), *smp)
             self.last_dur_idx, self.last_xhat = idx, xhat
             return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
         if coins is None:
@@ -397,8 +411,8 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         # reference shapes [B,32,15,130] / [B,32,15,5,2] as permuted views of the step-major buffers
         return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
 
-    def forward(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None):
-        return self.decoder(z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=coins, live=live)
+    def forward(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None):
+        return self.decoder(z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=coins, live=live, sampling=sampling)
 
     # ---- the reference's helper METHODS (ptvae.py:292-428), callable by reference-side code.  Forward-only entry points onto the
     # kernels the fused path runs (`decoder()` never calls them: it runs DecoderTFFn / DecoderStepFn); results carry no autograd graph.

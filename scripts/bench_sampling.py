@@ -1,0 +1,68 @@
+"""The sampled free-running decode beside the argmax decode, same process, same batch (BASELINE configs[3]: batch 2048, the step loop
+replayed from a captured hipGraph): --rounds interleaved rounds of --reps decodes each, timed by events after a warm-up; every round uses
+another draw, none needs a new capture.  Prints one JSON line with both ranges and the cost of sampling.
+
+    python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--eager]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_          # noqa: E402
+from polyphonic_chord_texture_disentanglement_amd import model as M                       # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=2048)
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--temperature', type=float, default=1.0)
+    ap.add_argument('--eager', action='store_true', help='no graph replay')
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'needs the MI355X'
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    m = M.DisentangleVAE.init_model(dev).to(dev).set_precision('bf16')
+    m.eval()
+    m.decoder.use_graph = not a.eager
+    z = torch.randn(a.batch, 512, device=dev)
+    blocks = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)]
+
+    def run(block):
+        with torch.no_grad():
+            m.decoder(z, True, None, None, 0., 0., sampling=block)
+
+    def timed(block):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            run(block)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.reps
+
+    for _ in range(2):                                       # warm-up: both graphs captured, allocator settled
+        run(None)
+        run(blocks[-1])
+    torch.cuda.synchronize()
+    captures = m.decoder.graph_captures
+    ms = {'argmax': [], 'sampled': []}
+    for r in range(a.rounds):                                # interleaved: drift of the box hits both alike
+        ms['argmax'].append(timed(None))
+        ms['sampled'].append(timed(blocks[r]))
+    assert m.decoder.graph_captures == captures              # a new draw is not a new capture
+    rate = {k: [round(a.batch / (v * 1e-3), 1) for v in vs] for k, vs in ms.items()}
+    best = {k: max(v) for k, v in rate.items()}
+    print(json.dumps({'what': 'free-running decode, argmax vs sampled decisions', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
+                      'temperature': a.temperature, 'ms_per_decode': {k: [round(x, 3) for x in v] for k, v in ms.items()},
+                      'samples_per_s': rate, 'sampled_over_argmax_best': round(best['sampled'] / best['argmax'], 4),
+                      'device': torch.cuda.get_device_name(0)}))
+
+
+if __name__ == '__main__':
+    main()
