@@ -5,6 +5,8 @@
 // (ptvae.py:14,39,103,262-286):
 //   r = s(gi_r + W_hr h + b_hr)  z = s(gi_z + W_hz h + b_hz)  n = tanh(gi_n + r*(W_hn h + b_hn))
 //   h' = (1-z)*n + z*h            (gi = W_i x + b_i is produced by a batched input-side GEMM)
+// ptv_gru_seq_bwd's low-rank addend is all or nothing: lr_a comes with lr_b and a rank lr_k >= 1, anything else is PTV_ERR_ARG
+// (a NULL lr_b would be read by both epilogues; with lr_k <= 0 the FAST epilogue would add a rank-1 term and the generic one none).
 #include <type_traits>
 #include "common.hpp"
 #include "gemm_core.hpp"
@@ -510,6 +512,7 @@ extern "C" int ptv_gru_seq_bwd(int prec, int M, int H, int T,
   if (dh_ext && ((ext_ld & 3) || (ext_step_stride & 3))) return PTV_ERR_ARG;
   if ((flags & PTV_GRU_EXT_BF16) && prec != PTV_PREC_BF16) return PTV_ERR_ARG;
   if (dh_last && (last_ld & 3)) return PTV_ERR_ARG;
+  if (lr_a && (!lr_b || lr_k <= 0)) return PTV_ERR_ARG;         // the epilogues read lr_b; the FAST one reads lr_a[m*lda] whatever lr_k says
   hipStream_t s = (hipStream_t)stream;
   const long MH = (long)M * H, M3H = 3 * MH;
   for (int step = T - 1; step >= 0; step--) {
