@@ -973,7 +973,9 @@ int ptv_decoder_free_bwd(const void* const* t_tf, const long* d_tf, const void* 
  *        [T+1][R][512] every state, slot 0 included (the operand of the heads, the weight-gradient products and the BPTT); gates bf16
  *        [T][4] planes (r, z, n, W_hn h + b_hn) or NULL -- PRIVATE to this forward / BPTT pair: each plane is unit-blocked by 16,
  *        plane[u / 16][row][u % 16] (whole-kilobyte wave accesses), not the [R][512] of ptv_gru_seq_fwd.
- *        T: bits 0-7 = steps; bits 8-15 = debug flags and bits 16-23 = weight-ring depth of the timing scripts (0 = defaults).
+ *        T: bits 0-7 = steps (1 .. 255; 0 steps: PTV_ERR_ARG); bits 8-15 = debug flags and bits 16-23 = weight-ring depth of the timing
+ *        scripts (0 = defaults); bit 24: see ptv_notes_gru_persist_fwd_rows.  R <= 1048575 (32-bit buffer offsets: R * 2048 bytes of h0
+ *        within one descriptor), PTV_ERR_UNSUPPORTED above.
  *   bwd: wt = pack(W_hh^T [512,1536]) (pairs = 1); HN16 / gates as the forward left them (the previous state enters the gate
  *        gradients at bf16 precision); ext bf16 = gradient arriving at the state after step s, the [T*R][512] matrix of the heads'
  *        input-gradient products stored COLUMN-BLOCKED by 32 ([16][T*R][32], ptv_gemm dtypes bit 3);
@@ -983,11 +985,16 @@ int ptv_decoder_free_bwd(const void* const* t_tf, const long* d_tf, const void* 
  *        arrives (zero rows of ext: the padded note slots the loss ignores) and writes zero rows for them; top_step (or NULL; device int,
  *        initialised to -1 by the caller) receives the last step at which anything arrived for any panel, so that the products over dgi /
  *        dgh can stop after that step's rows (ptv_wgrad k_top).
+ *        T: bits 0-7 = steps on every path (0 steps: PTV_ERR_ARG); bits 8-15 = flags of the timing scripts, bit 16: see
+ *        ptv_notes_gru_persist_bwd_rows (both read by the 8-wave kernel only).  8-wave kernel: R <= 699050 (R * 3072 bytes of a dgi step within
+ *        one buffer descriptor) and R * (16 * steps - 1) <= 67108863 (the 32-bit offset into ext), PTV_ERR_UNSUPPORTED above; the 4-wave kernel
+ *        addresses with 64-bit offsets: R <= 2^31 - 1.
  */
 int ptv_notes_gru_persist_fwd(const void* wg_h, const void* wg_t, const float* b_hh, const void* gc, const float* emb,
                               const float* h0, void* HN16, void* gates, long R, int T, void* stream);
 /* the same with a live-step limit: live_top (device int32, or NULL) -- only the note steps 0 .. *live_top run; the later slots of HN16 and
- * planes of gates stay unwritten (the BPTT must then be given a top_step limit <= *live_top: ptv_notes_gru_persist_bwd) */
+ * planes of gates stay unwritten (the BPTT must then be given a top_step limit <= *live_top: ptv_notes_gru_persist_bwd).  Step 0 always
+ * runs: *live_top < 0 is taken as 0; *live_top >= steps - 1 is the whole sequence. */
 int ptv_notes_gru_persist_fwd_top(const void* wg_h, const void* wg_t, const float* b_hh, const void* gc, const float* emb,
                                   const float* h0, void* HN16, void* gates, long R, int T, const int* live_top, void* stream);
 long ptv_notes_gru_persist_scratch_elems(long R);
@@ -1017,17 +1024,29 @@ int ptv_notes_bwd_variant(int eight_waves);
 
 /* The same kernels for any GRU whose rows are many and independent; H = 512 (above) or H = 128 with 128 inputs, which is one
  * direction of dec_notes_emb_gru, the note-summary bi-GRU over the 16 notes of each of the 32*B steps (ptvae.py:446-453,480-486).
- *   fwd: w_hh = pack(W_hh [3H,H]), w_x = pack(W_ih [3H,128]) (pairs = 1); b_ih NULL when folded into gc; gc bf16 [R][3H] or NULL;
- *        x fp32, row m of step t at x + t*x_step + m*128; lengths int32 [R] or NULL (row m is updated at time t iff t < lengths[m],
+ *   fwd: w_hh = pack(W_hh [3H,H]), w_x = pack(W_ih [3H,128]) (H = 128: pairs = 1; H = 512: pairs = 0, as above); b_ih NULL when folded
+ *        into gc; gc: H = 512 only, the column-blocked-by-16 matrix of ptv_notes_gru_persist_fwd, NULL for H = 128;
+ *        x fp32, row m of step t at x + t*x_step + m*128 (x, HN and out 16-byte aligned, x_step % 4 == 0: PTV_ERR_ARG otherwise);
+ *        HN fp32 [T+1][R][H], slot 0 = the initial state, written by the caller (H = 512: only slot 0 exists, it is h0); HN16 bf16
+ *        [T+1][R][H], slot 0 included, written here; gates bf16 [T][4] planes or NULL, PRIVATE to the forward / BPTT pair: H = 128
+ *        unit-blocked by 32, plane[u / 32][row][u % 32]; H = 512 by 16 (above);
+ *        lengths int32 [R] or NULL (row m is updated at time t iff t < lengths[m],
  *        as nn.utils.rnn.pack_padded_sequence does); reverse = 1 walks time T-1..0; out (or NULL) receives the final state,
  *        row m at out + m*out_ld (out_ld % 4 == 0).
  *        The two instances are specialised: H = 512 needs gc and takes no b_ih / lengths / reverse / out; H = 128 needs b_ih and no
  *        gc (PTV_ERR_UNSUPPORTED otherwise).
- *   bwd: ext bf16 [T][R][H] (H = 512 only, required there); dh_last fp32 (row stride last_ld) = gradient of the final state (H = 128
+ *        T = steps, 1 .. 255; H = 128 defines no flag bits (any bit above bit 7: PTV_ERR_ARG), H = 512 as ptv_notes_gru_persist_fwd.
+ *        With lengths (and ptv_zero_skip on) the time indices at or beyond the longest row of the whole launch are dead when R % 32 == 0:
+ *        their HN / HN16 slots and gate planes stay unwritten, except the slot in front of the first live step of the reversed direction.
+ *        R <= 2^31 - 1 for H = 128.
+ *   bwd: ext bf16 = the [T*R][H] matrix column-blocked by 32 as above (H = 512 only, required there); dh_last fp32 (row stride last_ld) = gradient of the final state (H = 128
  *        only), or NULL; lengths: the lengths the forward ran with, or NULL -- with lengths both kernels pass over the steps that lie
  *        beyond the longest row of a 64-row panel (identity for the whole panel, as pack_padded_sequence leaves them out;
  *        the forward then leaves that step's gates unwritten, so the backward MUST be given the same lengths); H = 512 writes only the n third of dgh ([T][R][512], see above); dgi is indexed by
  *        TIME, dgh by processing step (so dgh pairs with HN16[:T] and dgi with x in the weight-gradient products).
+ *        T = steps as in the forward (0 steps or, for H = 128, any bit above bit 7: PTV_ERR_ARG).  H = 128 with lengths: top_step (or NULL)
+ *        is atomicMax'ed with the last TIME index any row reaches; given top_step and R % 32 == 0, the dgi / dgh rows of the time indices
+ *        beyond it stay unwritten.  dh0 of a row that never ran (length 0) is its dh_last.
  */
 int ptv_row_gru_persist_fwd(int H, const void* w_hh, const void* w_x, const float* b_hh, const float* b_ih, const void* gc,
                             const float* x, long x_step, const int* lengths, float* HN, void* HN16, void* gates,

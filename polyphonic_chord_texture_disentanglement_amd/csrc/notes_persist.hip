@@ -94,7 +94,8 @@ __device__ __forceinline__ void st_f32x8(float* p, const float (&v)[8]) {
 struct RowGruFwdArgs {
   const bf16x8 *w_hh, *w_x;        // pair-interleaved packing: W_hh [3H/16 tiles][H/32 kb][64], W_x [3H/16][4][64]
   const float* b_hh; const float* b_ih;   // [3H]; b_ih may be null (folded into gc)
-  const __bf16* gc;                // the [R][3H] hoisted input part (b_ih included), COLUMN-BLOCKED by 32: [3H/32][R][32] (ptv_gemm dtypes bit 3), or null
+  const __bf16* gc;                // EMB = false only (an instance no entry point launches since the wave-role forward, whose gc is blocked by 16):
+                                   // the [R][3H] hoisted input part (b_ih included), COLUMN-BLOCKED by 32: [3H/32][R][32]; null for H = 128
   const float* x; long x_step;     // fed tokens fp32: x + t*x_step + row*128
   const int* lengths;              // [R] or null: row m is updated at time t iff t < lengths[m]
   float* HN; __bf16* HN16;         // [T+1][R][H]; slot 0 of HN written by the caller
@@ -472,6 +473,7 @@ __device__ __forceinline__ void row_gru_bwd_body(const RowGruBwdArgs& a, const l
   for (int i = tid; i < NRP * H; i += 256) dhz[i] = 0.f;
   __syncthreads();
   bool first_active = true;                                               // no later step has handed a dgh over yet
+  int par = 0;                                                            // flips with every step passed over below: the scratch halves alternate per COMPUTED step
   int s_top = a.T - 1;
   if constexpr (!EMB) {
     // A step whose arriving gradient is zero for all 64 rows, with nothing arriving from later steps either, produces exactly zero
@@ -508,7 +510,7 @@ __device__ __forceinline__ void row_gru_bwd_body(const RowGruBwdArgs& a, const l
   for (int s = s_top; s >= (a.dh0 ? -1 : 0); s--) {
     const int tt = s < 0 ? 0 : ((EMB && a.reverse) ? a.T - 1 - s : s);
     if constexpr (EMB) {
-      if (s >= 0 && tt >= gmax) continue;                                  // beyond the launch-wide limit: rows nobody reads
+      if (s >= 0 && tt >= gmax) { par ^= 1; continue; }                    // beyond the launch-wide limit: rows nobody reads
       if (s >= 0 && tt >= pmax) {                                          // the forward passed the state through: zero gate gradients
         for (int i = tid; i < NRP * (3 * H / 8); i += 256) {
           const int row = i / (3 * H / 8), c8 = (i % (3 * H / 8)) * 8;
@@ -518,13 +520,15 @@ __device__ __forceinline__ void row_gru_bwd_body(const RowGruBwdArgs& a, const l
             *reinterpret_cast<bf16x8*>(a.dgi + (long)tt * R3H + (a.perm ? (long)a.perm[r0 + row] : r0 + row) * (3 * H) + c8) = zz;
           }
         }
+        // (reversed direction: these are the steps in front of s = -1, and the dh0 product must find dgh of the last computed step)
+        par ^= 1;
         continue;
       }
     }
     const bool last = first_active;
     first_active = false;
-    const __bf16* scr = sc + ((s + 1) & 1) * (NCH * NRP * 8);             // dgh_{s+1}, written by the previous iteration
-    __bf16* scw = sc + (s & 1) * (NCH * NRP * 8);
+    const __bf16* scr = sc + ((s + 1 + par) & 1) * (NCH * NRP * 8);       // dgh of the step computed last, written by that iteration
+    __bf16* scw = sc + ((s + par) & 1) * (NCH * NRP * 8);
     // HBM operands of the epilogue items (tile pairs x 4 M tiles; saved gates, previous state, external gradient) run 2 items
     // ahead of the arithmetic through a ring of 3 register sets; the first two are requested before the products
     struct Ops { bf16x8 g[4]; bf16x8 ex; float4 hp[2]; bf16x8 hp16; };
@@ -593,6 +597,14 @@ __device__ __forceinline__ void row_gru_bwd_body(const RowGruBwdArgs& a, const l
       if (s < 0) {                                                       // dh0 = dhz_0 + dgh_0 . W_hh
 #pragma unroll
         for (int e = 0; e < 8; e++) dh[e] += cz[e];
+        if constexpr (EMB) {
+          if (last && a.dh_last) {                                         // no step of the panel ran (every row empty): the final state IS h0
+            float lg[8];
+            ld_f32x8(a.dh_last + gnat[i] * a.last_ld + u, lg);
+#pragma unroll
+            for (int e = 0; e < 8; e++) dh[e] += lg[e];
+          }
+        }
         if (ok[i]) st_f32x8(a.dh0 + grow[i] * H + u, dh);
         continue;
       }
@@ -645,6 +657,10 @@ __global__ __launch_bounds__(256, H == 128 ? 2 : 1) void row_gru_bwd_kernel(RowG
   extern __shared__ __attribute__((aligned(16))) char nsm[];
   row_gru_bwd_body<H, EMB>(a, blockIdx.x, nsm);
 }
+
+// the kernels of this file address with 64-bit offsets throughout; the row count itself travels as an int
+constexpr long ROW_GRU_MAX_R = 0x7fffffffL;
+static inline bool aligned16(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15) == 0; }
 
 template <int H, bool EMB>
 static int launch_fwd(const RowGruFwdArgs& a, hipStream_t s) {
@@ -747,8 +763,12 @@ extern "C" int ptv_row_gru_persist_fwd(int H, const void* w_hh, const void* w_x,
 extern "C" int ptv_row_gru_persist_fwd_perm(int H, const void* w_hh, const void* w_x, const float* b_hh, const float* b_ih, const void* gc,
                                             const float* x, long x_step, const int* lengths, const int* perm, float* HN, void* HN16,
                                             void* gates, float* out, long out_ld, long R, int T, int reverse, void* stream) {
-  if (!w_hh || !w_x || !b_hh || !x || !HN || !HN16 || R <= 0 || T <= 0 || (H != 512 && H != 128)) return PTV_ERR_ARG;
+  if (!w_hh || !w_x || !b_hh || !x || !HN || !HN16 || R <= 0 || T <= 0 || (T & 0xff) == 0 || (H != 512 && H != 128)) return PTV_ERR_ARG;
   if (out && (out_ld & 3)) return PTV_ERR_ARG;
+  // x, HN and out move as 16-byte vectors
+  if ((x_step & 3) || !aligned16(x) || !aligned16(HN) || !aligned16(out)) return PTV_ERR_ARG;
+  if (H == 128 && (T & ~0xff)) return PTV_ERR_ARG;                          // (no flag bits are defined for this instance)
+  if (R > ROW_GRU_MAX_R) return PTV_ERR_UNSUPPORTED;
   // H = 512 is the notes GRU (gc given, bias folded, dense): the wave-role kernel of notes_roles.hip; H = 128 the note-summary GRU (b_ih
   // given, mask / reverse / final state)
   if (H == 512) {
@@ -756,7 +776,7 @@ extern "C" int ptv_row_gru_persist_fwd_perm(int H, const void* w_hh, const void*
     return ptv_notes_gru_persist_fwd(w_hh, w_x, b_hh, gc, x, HN, HN16, gates, R, T, stream);
   }
   RowGruFwdArgs a{(const bf16x8*)w_hh, (const bf16x8*)w_x, b_hh, b_ih, (const __bf16*)gc, x, x_step, lengths, HN, (__bf16*)HN16,
-                  (__bf16*)gates, out, out_ld, (int)R, T & 0xff, reverse, T >> 8, g_zero_skip, g_gemm_prio, perm};
+                  (__bf16*)gates, out, out_ld, (int)R, T & 0xff, reverse, 0, g_zero_skip, g_gemm_prio, perm};
   const int pi = prof::want(3, (int)R, H) ? prof::begin((hipStream_t)stream) : -1;
   if (gc || !b_ih) return PTV_ERR_UNSUPPORTED;
   PTV_TRY((launch_fwd<128, true>(a, (hipStream_t)stream)));
@@ -788,8 +808,11 @@ extern "C" int ptv_row_gru_persist_bwd_perm(int H, const void* wt, const void* H
 static int row_gru_bwd_any(int H, const void* wt, const void* HN, const void* gates, const void* ext, const float* dh_last, long last_ld,
                            const int* lengths, const int* perm, void* dgi, void* dgh, float* dh0, void* scratch, long R, int T, int reverse,
                            const int* bound, const int* row_len, int* top_step, void* stream) {
-  if (!wt || !HN || !gates || !dgi || !dgh || !scratch || R <= 0 || T <= 0 || (H != 512 && H != 128)) return PTV_ERR_ARG;
+  if (!wt || !HN || !gates || !dgi || !dgh || !scratch || R <= 0 || T <= 0 || (T & 0xff) == 0 || (H != 512 && H != 128)) return PTV_ERR_ARG;
   if (dh_last && (last_ld & 3)) return PTV_ERR_ARG;
+  if (H == 128 && ((T & ~0xff) || !aligned16(HN))) return PTV_ERR_ARG;      // (no flag bits are defined for this instance; fp32 states in 16-byte vectors)
+  if (R > ROW_GRU_MAX_R) return PTV_ERR_UNSUPPORTED;
+  T &= 0xff;                                                                // the step count, as in the forward (H = 512: the flag bits are the 8-wave kernel's)
   if (H == 512 && (lengths || perm)) return PTV_ERR_UNSUPPORTED;
   if (perm && dh0) return PTV_ERR_UNSUPPORTED;                            // (dh0 would be indexed by position)
   RowGruBwdArgs a{(const bf16x8*)wt, H == 512 ? nullptr : (const float*)HN, H == 512 ? (const __bf16*)HN : nullptr, (const __bf16*)gates, (const __bf16*)ext, dh_last, last_ld, lengths, top_step, (__bf16*)dgi, (__bf16*)dgh, dh0,
@@ -810,7 +833,7 @@ extern "C" int ptv_notes_gru_persist_bwd_rows(const void* wt, const void* HN16, 
                                               void* stream) {
   if (!ext || (bound && !top_step) || (row_len && !bound)) return PTV_ERR_ARG;
   if (g_notes_bwd8) return ptv_notes_bwd8(wt, HN16, gates, ext, dgi, dgh, dh0, scratch, R, T, bound, row_len, top_step, stream);
-  return row_gru_bwd_any(512, wt, HN16, gates, ext, nullptr, 0, nullptr, nullptr, dgi, dgh, dh0, scratch, R, T & 0xffff, 0, bound, row_len, top_step,
+  return row_gru_bwd_any(512, wt, HN16, gates, ext, nullptr, 0, nullptr, nullptr, dgi, dgh, dh0, scratch, R, T & 0xff, 0, bound, row_len, top_step,
                          stream);                                 // (this kernel always writes the zero rows: T bit 16 is a permission, not an order)
 }
 extern "C" int ptv_notes_gru_persist_bwd_top(const void* wt, const void* HN16, const void* gates, const void* ext, void* dgi, void* dgh,

@@ -401,6 +401,11 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
     }
 }
 
+// The cell waves address through buffer descriptors with 32-bit offsets.  The binding one is h0 ([R][512] fp32): a descriptor holds at most
+// 2^31 - 1 bytes and the per-lane offset row * 2048 + 48 is checked against it, so R * 2048 <= 2^31 - 1.  The others allow more: gate planes,
+// lane offset row * 32 + 16 and scalar offset (tile * 32 + 3 * 1024) * R <= 4064 * R < 2^32 (scalar offsets are outside the range check).
+constexpr long MAX_R = 0x7fffffffL / (H * 4);                                  // 1048575
+
 template <int DF, int ABL>
 static int launch(const Args& a, hipStream_t s) {
   static bool attr = false;
@@ -441,6 +446,7 @@ extern "C" int ptv_notes_gru_persist_fwd_rows(const void* wg_h, const void* wg_t
                                               const float* h0, void* HN16, void* gates, long R, int T, const int* live_top, const int* row_len,
                                               void* stream) {
   if (!wg_h || !wg_t || !b_hh || !gc || !emb || !h0 || !HN16 || R <= 0 || (T & 0xff) <= 0) return PTV_ERR_ARG;
+  if (R > nr::MAX_R) return PTV_ERR_UNSUPPORTED;
   nr::Args a{(const bf16x8*)wg_h, (const bf16x8*)wg_t, b_hh, (const __bf16*)gc, emb, R * nr::E, h0, (__bf16*)HN16, (__bf16*)gates,
              (int)R, T & 0xff, (T >> 8) & 0xff, g_notes_trace, live_top, row_len, (T >> 24) & 1};
   const int depth = (T >> 16) & 0xff, abl = a.dbg & 7;
@@ -481,6 +487,8 @@ constexpr int H = 512, ROWS = 64, KT = 3 * H / 32, KL = 36;           // k-block
 constexpr int LDS_A = KL * 4 * ROWS * 16;                             // 147456 bytes
 constexpr int SCR_CH = (KT - KL) * 4;                                 // chunks per step that go through the global scratch: 48
 constexpr int DW = 3;                                                  // weight ring depth in k-blocks
+constexpr long MAX_R = 0x7fffffffL / (3 * H * 2);                      // 699050: [R][1536] bf16 within one buffer descriptor
+constexpr long MAX_R_STEPS = 0xffffffffL / 64;                         // 67108863 >= R * (16 T - 1): the scalar offset into ext within 32 bits
 
 typedef __attribute__((ext_vector_type(4))) float f4v;
 typedef __attribute__((ext_vector_type(4))) unsigned u4v;
@@ -706,6 +714,9 @@ extern "C" int ptv_notes_bwd8(const void* wt, const void* HN16, const void* gate
                               long R, int T, const int* bound, const int* row_len, int* top_step, void* stream) {
   if (!wt || !HN16 || !gates || !ext || !dgi || !dgh || !scratch || R <= 0 || (T & 0xff) <= 0) return PTV_ERR_ARG;
   if ((bound && !top_step) || (row_len && !bound)) return PTV_ERR_ARG;   // (rows beyond the bound stay unwritten: the consumers need the limit)
+  // 32-bit offsets: dgi's lane offset row * 3072 + 48 is checked against a descriptor of at most 2^31 - 1 bytes, and the scalar offset into
+  // ext, ((tile / 2) * T * R + s * R) * 64 <= (16 T - 1) * R * 64, must not wrap
+  if (R > nb::MAX_R || R * (16L * (T & 0xff) - 1) > nb::MAX_R_STEPS) return PTV_ERR_UNSUPPORTED;
   nb::Args a{(const bf16x8*)wt, (const __bf16*)HN16, (const __bf16*)gates, (const __bf16*)ext, (__bf16*)dgi, (__bf16*)dgh, dh0, (__bf16*)scratch,
              top_step, (int)R, T & 0xff, g_zero_skip, bound, row_len, (T >> 16) & 1};
   const int abl = (T >> 8) & 6;
