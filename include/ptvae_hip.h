@@ -152,6 +152,22 @@ int ptv_gru_seq_bwd(int prec, int M, int H, int T,
  * Returns PTV_ERR_UNSUPPORTED (-3) when the shape does not fit one workgroup per CU (H % 256, H <= 1024,
  * rows per workgroup <= 256): the caller then uses the per-step entry points.  At most ONE persistent launch may
  * be in flight on the device at a time (chain them with events across streams).
+ * The plan (row groups RG, rows per workgroup 64 / 128 / 256, split-K: up to 512) is made from NC, M, H AND from the device's CU count
+ *   minus ptv_gru_persist_cu_reserve: the same shape may be supported on one device or reserve and not on another, so ask
+ *   ptv_gru_persist_supported / _splitk_supported (and _part_elems) after the reserve is set, on the device that runs the launch.
+ *   RG is a power of two and M need not fill it: row groups that hold no row at all are legal (M = 257, H = 256 at 256 CUs: 4 groups
+ *   of 128 rows, the last one empty); their workgroups only take part in the hand-offs.
+ * Limits of `sync`: NC * RG <= 32 row-group counters and, split-K, NC * RG * (H / 16 / S) <= 128 team counters; a plan beyond either
+ *   is PTV_ERR_UNSUPPORTED from every entry point below (neither can happen with 512 CUs or fewer).
+ * Refused with PTV_ERR_ARG (-1) before any launch: T <= 0; a NULL table or entry among gi, gi_step, gi_ld, w_hh16, b_hh, hall, hall16,
+ *   reverse, xch, sync (BPTT: hall, gates, w_t16, dgi, dgh, reverse, xch, sync; split-K: part too); a stride table missing for a
+ *   pointer that is given; gi_ld, gi_step, gi2_ld, gi2_step, ext_ld, ext_step or last_ld not a multiple of 4; a misaligned pointer.
+ *   Alignment: 16 bytes for w_hh16, w_t16, b_hh, hall, xch, part, fp32 dh_ext, dh_last and dh0 (float4 / 8 x bf16 accesses), 8 bytes
+ *   for gi, gi2, hall16, gates, dgi, dgh and bf16 dh_ext (4 x bf16), 4 bytes for lengths and sync.
+ *   NC outside 1 .. 4, M <= 0, H not 256 / 512 / 768 / 1024 and (split-K) S not 2 or 4 are PTV_ERR_UNSUPPORTED.
+ * Optional: gi2 (table or entry NULL; gi2_step = 0 broadcasts one [M][3H] addend), gates (table NULL: none saved), lengths, dh_ext,
+ *   dh_last, dh0.  dh0 may be given for some chains of a launch and be NULL for others: a chain's step count and its row groups'
+ *   counters are its own.  A row whose step is dead (t >= lengths[row]) copies its state and saves the gates (0, 1, 0, hn).
  */
 int ptv_gru_persist_supported(int NC, int M, int H);
 /* CUs the persistent grids leave free (default 0 = size to every CU): a data-parallel run may set it so that RCCL's channel kernels

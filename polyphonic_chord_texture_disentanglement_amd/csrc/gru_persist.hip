@@ -39,6 +39,8 @@ typedef __attribute__((address_space(1))) unsigned long long gu64;
 
 constexpr int PU = 16;                      // hidden units per workgroup
 constexpr int PMAXC = 4;                    // chains per launch
+constexpr int PMAXG = 32;                   // row groups per launch (chains x RG): arrival counters in `sync`
+constexpr int PMAXT = 128;                  // split-K teams per launch: team counters in `sync`
 constexpr int PLDS = 96 * 1024;             // W slice: 48 x H (fwd) or 16 x 3H (bwd) bf16, H <= 1024
 constexpr unsigned SPIN_LIMIT = 4000000u;   // ~ seconds: a stranded grid gives up instead of hanging the GPU
 
@@ -636,10 +638,22 @@ static int plan(int NC, int M, int H, int& RG, int& rows_wg, int& FM, int fm_max
   if (fm == 3) fm = 4;
   if (fm > 4 && fm <= 8) fm = 8;
   if (fm > fm_max) return PTV_ERR_UNSUPPORTED;
+  if (NC * rg > PMAXG) return PTV_ERR_UNSUPPORTED;             // `sync` holds PMAXG row-group counters (more than 512 CUs: no device has them)
   RG = rg; rows_wg = fm * 64; FM = fm;
   return PTV_OK;
 }
 static bool splitk_ok(int H, int S) { return (S == 2 || S == 4) && (H / PU) % S == 0 && (3 * H / S) % 192 == 0; }
+// the split-K plan: what ptv_gru_persist_bwd_splitk launches, and so what _splitk_supported and _part_elems answer for
+static int plan_splitk(int NC, int M, int H, int S, int& RG, int& rows_wg, int& FM) {
+  if (!splitk_ok(H, S)) return PTV_ERR_UNSUPPORTED;
+  PTV_TRY(plan(NC, M, H, RG, rows_wg, FM, 8));
+  if (NC * RG * (H / PU / S) > PMAXT) return PTV_ERR_UNSUPPORTED;     // `sync` holds PMAXT team counters behind the row groups'
+  return PTV_OK;
+}
+// the kernels move float4 / bf16x8 (16 bytes) and bf16x4 (8 bytes); NULL passes (optional pointers are tested where they are required)
+static inline bool al16(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15) == 0; }
+static inline bool al8(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 7) == 0; }
+static inline bool al4(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 3) == 0; }
 
 }  // namespace ptv
 
@@ -670,6 +684,7 @@ extern "C" int ptv_gru_persist_fwd(int NC, int M, int H, int T,
                                    float* const* hall, void* const* hall16, void* const* gates,
                                    const int* const* lengths, const int* reverse, void* const* xch, unsigned* sync, void* stream) {
   if (T <= 0 || !gi || !gi_step || !gi_ld || !w_hh16 || !b_hh || !hall || !hall16 || !reverse || !xch || !sync) return PTV_ERR_ARG;
+  if (!al4(sync)) return PTV_ERR_ARG;
   int RG, rows, FM;
   PTV_TRY(plan(NC, M, H, RG, rows, FM));
   PGruFwdArgs a{};
@@ -677,7 +692,9 @@ extern "C" int ptv_gru_persist_fwd(int NC, int M, int H, int T,
     if (!gi[i] || !w_hh16[i] || !b_hh[i] || !hall[i] || !hall16[i] || !xch[i]) return PTV_ERR_ARG;
     if ((gi_ld[i] & 3) || (gi_step[i] & 3)) return PTV_ERR_ARG;
     const bool has2 = gi2 && gi2[i];
-    if (has2 && ((gi2_ld[i] & 3) || (gi2_step[i] & 3))) return PTV_ERR_ARG;
+    if (has2 && (!gi2_ld || !gi2_step || (gi2_ld[i] & 3) || (gi2_step[i] & 3) || !al8(gi2[i]))) return PTV_ERR_ARG;
+    if (!al8(gi[i]) || !al16(w_hh16[i]) || !al16(b_hh[i]) || !al16(hall[i]) || !al8(hall16[i]) || !al16(xch[i]) ||
+        (gates && !al8(gates[i])) || (lengths && !al4(lengths[i]))) return PTV_ERR_ARG;
     a.c[i] = PChainF{(const __bf16*)w_hh16[i], b_hh[i], (const __bf16*)gi[i], gi_step[i], gi_ld[i],
                      has2 ? (const __bf16*)gi2[i] : nullptr, has2 ? gi2_step[i] : 0, has2 ? gi2_ld[i] : 0,
                      hall[i], (__bf16*)hall16[i], gates ? (__bf16*)gates[i] : nullptr, (__bf16*)xch[i],
@@ -714,22 +731,27 @@ extern "C" int ptv_gru_persist_bwd(int NC, int M, int H, int T,
                                    const float* const* dh_last, const long* last_ld,
                                    void* const* dgi, void* const* dgh, float* const* dh0,
                                    const int* reverse, void* const* xch, unsigned* sync, void* stream) {
-  if (T <= 0 || !hall || !gates || !w_t16 || !dgi || !dgh || !reverse || !xch || !sync) return PTV_ERR_ARG;
+  if (T <= 0 || !hall || !gates || !w_t16 || !dgi || !dgh || !reverse || !xch || !sync || !al4(sync)) return PTV_ERR_ARG;
   int RG, rows, FM;
   PTV_TRY(plan(NC, M, H, RG, rows, FM));
   PGruBwdArgs a{};
   for (int i = 0; i < NC; i++) {
     if (!hall[i] || !gates[i] || !w_t16[i] || !dgi[i] || !dgh[i] || !xch[i]) return PTV_ERR_ARG;
     const bool hext = dh_ext && dh_ext[i];
-    if (hext && ((ext_ld[i] & 3) || (ext_step[i] & 3))) return PTV_ERR_ARG;
+    if (hext && (!ext_ld || !ext_step || (ext_ld[i] & 3) || (ext_step[i] & 3))) return PTV_ERR_ARG;
+    if (hext && !(ext_bf16 && ext_bf16[i] ? al8(dh_ext[i]) : al16(dh_ext[i]))) return PTV_ERR_ARG;
     const bool hl = dh_last && dh_last[i];
-    if (hl && (last_ld[i] & 3)) return PTV_ERR_ARG;
+    if (hl && (!last_ld || (last_ld[i] & 3) || !al16(dh_last[i]))) return PTV_ERR_ARG;
+    if (!al16(hall[i]) || !al8(gates[i]) || !al16(w_t16[i]) || !al8(dgi[i]) || !al8(dgh[i]) || !al16(xch[i]) ||
+        (dh0 && !al16(dh0[i]))) return PTV_ERR_ARG;
     a.c[i] = PChainB{(const __bf16*)w_t16[i], hall[i], (const __bf16*)gates[i],
                      hext ? dh_ext[i] : nullptr, hext ? ext_step[i] : 0, hext ? ext_ld[i] : 0, hext && ext_bf16 ? ext_bf16[i] : 0,
                      hl ? dh_last[i] : nullptr, hl ? last_ld[i] : 0,
                      (__bf16*)dgi[i], (__bf16*)dgh[i], dh0 ? dh0[i] : nullptr, (__bf16*)xch[i], reverse[i]};
   }
-  // every chain of one launch takes the dh0 tail or none does (the step loop bound is per chain, the counters are not shared)
+  // dh0 may be given for some chains and not for others: the step loop bound is per chain and a row group's counter is bumped and
+  // polled by workgroups of that one chain only, so a chain that runs the extra item waits for nobody who does not
+  // (tests/test_gpu_pgru_kernels.py runs mixed launches through all three kernels)
   a.NC = NC; a.M = M; a.H = H; a.T = T; a.RG = RG; a.UG = H / PU; a.rows_wg = rows; a.sync = sync;
   const dim3 grid(NC * RG * a.UG), block(NTHREADS);
   hipStream_t s = (hipStream_t)stream;
@@ -745,12 +767,12 @@ extern "C" int ptv_gru_persist_bwd(int NC, int M, int H, int T,
 // ---- split-K teams (pgru_bwd_sk_kernel): S = 2 or 4 workgroups share 16*S units and split K = 3H
 extern "C" int ptv_gru_persist_splitk_supported(int NC, int M, int H, int S) {
   int RG, rows, FM;
-  return splitk_ok(H, S) && plan(NC, M, H, RG, rows, FM, 8) == PTV_OK ? 1 : 0;
+  return plan_splitk(NC, M, H, S, RG, rows, FM) == PTV_OK ? 1 : 0;
 }
 
 extern "C" long ptv_gru_persist_part_elems(int NC, int M, int H, int S) {
   int RG, rows, FM;
-  if (!splitk_ok(H, S) || plan(NC, M, H, RG, rows, FM, 8) != PTV_OK) return 0;
+  if (plan_splitk(NC, M, H, S, RG, rows, FM) != PTV_OK) return 0;
   return 2L * RG * rows * H * S;                               // [2][RG][H/(16 S) teams][S][S][rows][16]
 }
 
@@ -760,24 +782,25 @@ extern "C" int ptv_gru_persist_bwd_splitk(int S, int NC, int M, int H, int T,
                                           const float* const* dh_last, const long* last_ld,
                                           void* const* dgi, void* const* dgh, float* const* dh0,
                                           const int* reverse, void* const* xch, float* const* part, unsigned* sync, void* stream) {
-  if (T <= 0 || !hall || !gates || !w_t16 || !dgi || !dgh || !reverse || !xch || !part || !sync) return PTV_ERR_ARG;
-  if (!splitk_ok(H, S)) return PTV_ERR_UNSUPPORTED;
+  if (T <= 0 || !hall || !gates || !w_t16 || !dgi || !dgh || !reverse || !xch || !part || !sync || !al4(sync)) return PTV_ERR_ARG;
   int RG, rows, FM;
-  PTV_TRY(plan(NC, M, H, RG, rows, FM, 8));
+  PTV_TRY(plan_splitk(NC, M, H, S, RG, rows, FM));
   PGruBwdArgs a{};
   for (int i = 0; i < NC; i++) {
-    if (!hall[i] || !gates[i] || !w_t16[i] || !dgi[i] || !dgh[i] || !xch[i] || !part[i]) return PTV_ERR_ARG;
+    if (!hall[i] || !gates[i] || !w_t16[i] || !dgi[i] || !dgh[i] || !xch[i] || !part[i] || !al16(part[i])) return PTV_ERR_ARG;
     const bool hext = dh_ext && dh_ext[i];
-    if (hext && ((ext_ld[i] & 3) || (ext_step[i] & 3))) return PTV_ERR_ARG;
+    if (hext && (!ext_ld || !ext_step || (ext_ld[i] & 3) || (ext_step[i] & 3))) return PTV_ERR_ARG;
+    if (hext && !(ext_bf16 && ext_bf16[i] ? al8(dh_ext[i]) : al16(dh_ext[i]))) return PTV_ERR_ARG;
     const bool hl = dh_last && dh_last[i];
-    if (hl && (last_ld[i] & 3)) return PTV_ERR_ARG;
+    if (hl && (!last_ld || (last_ld[i] & 3) || !al16(dh_last[i]))) return PTV_ERR_ARG;
+    if (!al16(hall[i]) || !al8(gates[i]) || !al16(w_t16[i]) || !al8(dgi[i]) || !al8(dgh[i]) || !al16(xch[i]) ||
+        (dh0 && !al16(dh0[i]))) return PTV_ERR_ARG;
     a.c[i] = PChainB{(const __bf16*)w_t16[i], hall[i], (const __bf16*)gates[i],
                      hext ? dh_ext[i] : nullptr, hext ? ext_step[i] : 0, hext ? ext_ld[i] : 0, hext && ext_bf16 ? ext_bf16[i] : 0,
                      hl ? dh_last[i] : nullptr, hl ? last_ld[i] : 0,
                      (__bf16*)dgi[i], (__bf16*)dgh[i], dh0 ? dh0[i] : nullptr, (__bf16*)xch[i], reverse[i], part[i]};
   }
   a.NC = NC; a.M = M; a.H = H; a.T = T; a.RG = RG; a.UG = H / PU; a.rows_wg = rows; a.sync = sync;
-  if (NC * RG > 32 || NC * RG * (a.UG / S) > 128) return PTV_ERR_UNSUPPORTED;            // counters: 16 * (33 + 128) words
   const dim3 grid(NC * RG * a.UG), block(NTHREADS);
   hipStream_t s = (hipStream_t)stream;
 #define PTV_SK_LAUNCH(S_)                                                                                  \
