@@ -82,6 +82,19 @@ int ptv_gemm_mtop(int prec, int transA, int transB, int M, int N, int K, const v
 int ptv_gemm_mtop_seg(int prec, int transA, int transB, int M, int N, int K, const void* A, long lda, const void* B, long ldb,
                       void* C, long ldc, const float* bias, float alpha, int accumulate, int act, int splitk, int dtypes,
                       const int* m_top, long m_unit, const int* seg_n, long seg_unit, int seg_period, void* stream);
+/* ... and with a ROW MAP on C (round 7; c_rows or NULL = ptv_gemm_mtop_seg): product row m is stored at -- and with accumulate read from --
+ * C row (m / c_unit) * c_unit + c_rows[m % c_unit] (device ints); K order and epilogue arithmetic are those of the unmapped product, dead
+ * row tiles put their zero / bias rows through the map (or return early where they change nothing).  THE CALLER GUARANTEES that c_rows is a
+ * permutation of [0, c_unit): nothing checks it, a repeated index leaves a row unwritten and races on another, an index outside writes
+ * outside C.  Refused (PTV_ERR_ARG, nothing launched): c_rows with column-blocked C (dtypes bits 3 / 4), with splitk > 1, with transA,
+ * c_unit <= 0, M not a multiple of c_unit.  With splitk = 0 the product takes the K split the unmapped call would take (shallow grids of
+ * deep products; the ordered reduction then stores through the map), so at every shape the result equals the unmapped product's bit for
+ * bit.  The decoder's backward writes the gradients it computes in length-sorted row order straight into their natural-order tensors
+ * this way. */
+int ptv_gemm_mtop_seg_map(int prec, int transA, int transB, int M, int N, int K, const void* A, long lda, const void* B, long ldb,
+                          void* C, long ldc, const float* bias, float alpha, int accumulate, int act, int splitk, int dtypes,
+                          const int* m_top, long m_unit, const int* seg_n, long seg_unit, int seg_period,
+                          const int* c_rows, long c_unit, void* stream);
 /* plain products enqueued after this call raise their wave priority (p != 0) or run at the default one (0): host-side marker for the
  * launches of a latency chain that share the GPU with weight-gradient products on sibling streams.  Process-wide, read at enqueue time. */
 int ptv_gemm_priority(int p);
@@ -621,12 +634,11 @@ enum PtvDtbTensor {
   PTV_DTB_SIDE_STREAM,    /* hipStream_t of the sibling stream */
   PTV_DTB_FORK_EVENT0, PTV_DTB_FORK_EVENT1, PTV_DTB_FORK_EVENT2, PTV_DTB_FORK_EVENT3,   /* hipEvent_t, one per fork */
   /* the forward ran on rows sorted by length (PTV_DTF_PERM ...): all or none.  NS16 / TOK_OP are then the gathered copies the forward left
-   * (NS16: slot 0 unused, rows from NS16S - B*Ht ... the table holds NS16S itself in PTV_DTB_NS16S), DNS / DTOK come out in natural row order */
+   * (NS16: slot 0 unused, rows from NS16S - B*Ht ... the table holds NS16S itself in PTV_DTB_NS16S), DNS / DTOK come out in natural row order
+   * (their products store through PERM: ptv_gemm_mtop_seg_map) */
   PTV_DTB_PERM, PTV_DTB_ROW_LEN,
   PTV_DTB_NS16S,          /* [R, Ht] bf16 gathered time states (operand of the weight_ih / time_to_notes gradients) */
-  PTV_DTB_DNS_S,          /* scratch [R, Ht] fp32: the gradient of the time states in sorted row order, scattered into DNS */
-  PTV_DTB_DTOK_S,         /* scratch [15, R, E] fp32: the token gradient in sorted row order, scattered into DTOK */
-  PTV_DTB_SEG_N,          /* int32 [15] (ptv_rows_seg_counts of ROW_LEN) or NULL: the weight-gradient products over (note step, row) skip the dead
+  PTV_DTB_SEG_N,         /* int32 [15] (ptv_rows_seg_counts of ROW_LEN) or NULL: the weight-gradient products over (note step, row) skip the dead
                              blocks of every step (sorted mode only) */
   PTV_DTB_COUNT
 };
@@ -1085,6 +1097,14 @@ int ptv_row_gru_persist_bwd_perm(int H, const void* wt, const void* HN, const vo
 /* perm [R] = the rows in order of DESCENDING lengths[row] (0 <= length <= max_len <= 38), ties in row order: a stable counting sort in one
  * workgroup (deterministic: the order of the K rows of the weight-gradient products depends on it) */
 int ptv_rows_by_length(const int* lengths, int* perm, long R, int max_len, void* stream);
+/* The row plan of a length-sorted pass in ONE launch of many workgroups (round 7): perm as ptv_rows_by_length writes it, bit for bit;
+ * len_sorted[p] (or NULL) = the clamped length min(max(lengths[perm[p]], 0), max_len) that perm orders by; seg_n[s], s < steps (or NULL) =
+ * ptv_rows_seg_counts of len_sorted = 128 * ceil(#{rows: length > s} / 128).  Every workgroup of 256 rows counts all R lengths itself
+ * (no workgroup waits for or adds to another: no counters, no global atomics), work quadratic in R: R above PTV_ROWS_PLAN_MAX_R returns
+ * PTV_ERR_UNSUPPORTED with nothing written -- then call ptv_rows_by_length, ptv_gather_rows and ptv_rows_seg_counts.  max_len <= 38.
+ * seg_n needs R a multiple of 128 and 0 < steps <= 64 (PTV_ERR_ARG otherwise). */
+#define PTV_ROWS_PLAN_MAX_R 65536
+int ptv_rows_plan(const int* lengths, long R, int max_len, int steps, int* perm, int* len_sorted, int* seg_n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * clip_grad_norm_ (module.py:142-143) + torch.optim.Adam.step (train.py:50, scheduler.py:69-74) over

@@ -275,13 +275,13 @@ extern "C" int ptv_decoder_tf_bwd(const void* const* t, const long* d, void* str
   if (!t || !d) return PTV_ERR_ARG;
   for (int i = 0; i < PTV_DTB_COUNT; i++)
     if (!t[i] && i != PTV_DTB_TOP_H && i != PTV_DTB_PART_T && i != PTV_DTB_WAIT_EVENT && i != PTV_DTB_RECORD_EVENT && i != PTV_DTB_PERM &&
-        i != PTV_DTB_ROW_LEN && i != PTV_DTB_NS16S && i != PTV_DTB_DNS_S && i != PTV_DTB_DTOK_S && i != PTV_DTB_SEG_N)
+        i != PTV_DTB_ROW_LEN && i != PTV_DTB_NS16S && i != PTV_DTB_SEG_N)
       return PTV_ERR_ARG;
   // the forward ran on rows sorted by length: every per-row tensor here is in that order; the two gradients that leave the node for
-  // row-order-aware consumers (the time states', the fed tokens') are scattered back
+  // row-order-aware consumers (the time states', the fed tokens') are stored in natural row order by the products that compute them
+  // (ptv_gemm_mtop_seg_map: C row perm[sorted row])
   const bool sorted = t[PTV_DTB_PERM] != nullptr;
-  if (sorted != (t[PTV_DTB_ROW_LEN] != nullptr) || sorted != (t[PTV_DTB_NS16S] != nullptr) || sorted != (t[PTV_DTB_DNS_S] != nullptr) ||
-      sorted != (t[PTV_DTB_DTOK_S] != nullptr) || (sorted && !t[PTV_DTB_TOP_H]))
+  if (sorted != (t[PTV_DTB_ROW_LEN] != nullptr) || sorted != (t[PTV_DTB_NS16S] != nullptr) || (sorted && !t[PTV_DTB_TOP_H]))
     return PTV_ERR_ARG;
   const int* perm = (const int*)T_(t, PTV_DTB_PERM);
   const int* row_len = (const int*)T_(t, PTV_DTB_ROW_LEN);
@@ -353,23 +353,20 @@ extern "C" int ptv_decoder_tf_bwd(const void* const* t, const long* d, void* str
   void* dgi_n = M_<void>(t, PTV_DTB_DGI_N); void* dgh_n = M_<void>(t, PTV_DTB_DGH_N);
   float* dHN0 = GB(PTV_DTB_DHN0); int* top_step = M_<int>(t, PTV_DTB_TOP_STEP);
   float* dGC = GB(PTV_DTB_DGC);
-  float* dNS_out = GB(PTV_DTB_DNS); float* dtok_out = GB(PTV_DTB_DTOK);     // what leaves the node, natural row order
-  float* dNS = sorted ? GB(PTV_DTB_DNS_S) : dNS_out;                       // what the products below write
-  float* dtok = sorted ? GB(PTV_DTB_DTOK_S) : dtok_out;
+  float* dNS = GB(PTV_DTB_DNS); float* dtok = GB(PTV_DTB_DTOK);             // what leaves the node, natural row order (perm null: the rows are)
   const __bf16* wt_ih_n = (const __bf16*)T_(t, PTV_DTB_WT_IH_N);   // [Ht + E, 3Hn]
   ptv_gemm_priority(1);
   PTV_TRY(ptv_notes_gru_persist_bwd_rows(T_(t, PTV_DTB_PK_NOTES_WT), T_(t, PTV_DTB_HN16), T_(t, PTV_DTB_GATES_N), dNSUM, dgi_n, dgh_n, dHN0,
                                          M_<void>(t, PTV_DTB_SCRATCH_N), R, 15 | (seg_n ? 0x10000 : 0), top_h, row_len, top_step, stream));
   PTV_TRY(ptv_sum_steps_seg(dGC, dgi_n, (long)R * 3 * Hn, 15, (long)R * 3 * Hn, 0, 1, top_step, seg_n, 3L * Hn, stream));
-  if (hipMemsetAsync(dtok_out + 15L * R * E, 0, sizeof(float) * R * E, s) != hipSuccess) return PTV_ERR_LAUNCH;
-  PTV_TRY(ptv_gemm_mtop_seg(P, 0, 0, (int)M, E, 3 * Hn, dgi_n, 3L * Hn, wt_ih_n + (long)Ht * 3 * Hn, 3L * Hn, dtok, E, nullptr, 1.f, 0, 0, 0, A16 | B16,
-                            top_step, R, seg_n, R, 15, stream));
-  PTV_TRY(ptv_gemm(P, 0, 0, R, Ht, 3 * Hn, dGC, 3L * Hn, wt_ih_n, 3L * Hn, dNS, Ht, nullptr, 1.f, 0, 0, 0, B16, stream));
-  PTV_TRY(ptv_gemm(P, 0, 0, R, Ht, Hn, dHN0, Hn, T_(t, PTV_DTB_WT_T2N), Hn, dNS, Ht, nullptr, 1.f, 1, 0, 0, B16, stream));
-  if (sorted) {
-    PTV_TRY(ptv_scatter_rows(dNS_out, dNS, perm, R, Ht, 0, 0, 1, stream));
-    PTV_TRY(ptv_scatter_rows_seg(dtok_out, dtok, perm, R, E, (long)R * E, (long)R * E, 15, seg_n, stream));
-  }
+  if (hipMemsetAsync(dtok + 15L * R * E, 0, sizeof(float) * R * E, s) != hipSuccess) return PTV_ERR_LAUNCH;
+  // (the dead row tiles of the token product store their zeros through the map too: every row of the 15 planes is written exactly once)
+  PTV_TRY(ptv_gemm_mtop_seg_map(P, 0, 0, (int)M, E, 3 * Hn, dgi_n, 3L * Hn, wt_ih_n + (long)Ht * 3 * Hn, 3L * Hn, dtok, E, nullptr, 1.f, 0, 0, 0, A16 | B16,
+                                top_step, R, seg_n, R, 15, perm, R, stream));
+  PTV_TRY(ptv_gemm_mtop_seg_map(P, 0, 0, R, Ht, 3 * Hn, dGC, 3L * Hn, wt_ih_n, 3L * Hn, dNS, Ht, nullptr, 1.f, 0, 0, 0, B16, nullptr, 0, nullptr, 0, 0,
+                                perm, R, stream));
+  PTV_TRY(ptv_gemm_mtop_seg_map(P, 0, 0, R, Ht, Hn, dHN0, Hn, T_(t, PTV_DTB_WT_T2N), Hn, dNS, Ht, nullptr, 1.f, 1, 0, 0, B16, nullptr, 0, nullptr, 0, 0,
+                                perm, R, stream));
   PTV_TRY(fork(2));
   ptv_gemm_priority(0);
   {
@@ -396,7 +393,7 @@ extern "C" int ptv_decoder_tf_bwd(const void* const* t, const long* d, void* str
   {
     const float* hall_[1] = {(const float*)T_(t, PTV_DTB_NS)}; const void* gates_[1] = {T_(t, PTV_DTB_GATES_T)};
     const void* wt_[1] = {T_(t, PTV_DTB_WT_HH_T)};
-    const void* ext_[1] = {dNS_out}; const long ext_step[1] = {(long)B * Ht}, ext_ld[1] = {(long)Ht}; const int ext_bf[1] = {0};
+    const void* ext_[1] = {dNS}; const long ext_step[1] = {(long)B * Ht}, ext_ld[1] = {(long)Ht}; const int ext_bf[1] = {0};
     const float* last_[1] = {nullptr}; const long last_ld[1] = {0};
     void* dgi_[1] = {dgi_t}; void* dgh_[1] = {dgh_t}; float* dh0_[1] = {dzhid}; const int rev[1] = {0};
     void* xch_[1] = {M_<void>(t, PTV_DTB_XCH)}; float* part_[1] = {M_<float>(t, PTV_DTB_PART_T)};

@@ -10,33 +10,57 @@
 namespace ptv {
 
 // C[m,n] = act(alpha*acc + bias[n]) (+ C[m,n] when accumulate); atomic adds when split-K
-struct EpiPlain {
-  struct Params {
-    void* C; long ldc;
-    const float* bias;
-    float alpha;
-    int accumulate;   // C += ...
-    int act;          // 0 none, 1 exp
-    int atomic;       // split-K partial sums: atomicAdd into C (C pre-initialised, fp32 only)
-    int c_bf16;       // C holds bf16
-    int c_blocked;    // C is COLUMN-BLOCKED by w = 32 or 16 (log2 here, 0 = row-major): element (m, n) at ((n / w) * c_rows + m) * w + n % w (ldc unused) -- the layout the
-    int c_rows;       // row-partitioned recurrences read their per-row operands in (one contiguous kilobyte per wave access)
-    long split_stride;   // ordered split-K: split z stores its partial at C + z * split_stride floats (C = a workspace, ldc = N);
-                         // splitk_reduce_kernel adds the partials in split order
-  };
+struct EpiPlainParams {
+  void* C; long ldc;
+  const float* bias;
+  float alpha;
+  int accumulate;   // C += ...
+  int act;          // 0 none, 1 exp
+  int atomic;       // split-K partial sums: atomicAdd into C (C pre-initialised, fp32 only)
+  int c_bf16;       // C holds bf16
+  int c_blocked;    // C is COLUMN-BLOCKED by w = 32 or 16 (log2 here, 0 = row-major): element (m, n) at ((n / w) * c_brows + m) * w + n % w (ldc unused) -- the layout the
+  int c_brows;      // row-partitioned recurrences read their per-row operands in (one contiguous kilobyte per wave access)
+  long split_stride;   // ordered split-K: split z stores its partial at C + z * split_stride floats (C = a workspace, ldc = N);
+                       // splitk_reduce_kernel adds the partials in split order
+  // row map (or null; MAP kernels only): product row m lives in C row (m / c_unit) * c_unit + c_rows[m % c_unit] -- c_rows a permutation of
+  // [0, c_unit), M a multiple of c_unit, row-major C, no forced K split (ptv_gemm_mtop_seg_map checks the last three, the caller owns the
+  // first); under the automatic split the partials go to the workspace unmapped and splitk_reduce_kernel takes the map
+  const int* c_rows; int c_unit;
+};
+// MAP = the kernel stores (and with accumulate reads) through Params::c_rows; the unmapped kernels carry none of it
+template <bool MAP>
+struct EpiPlainT {
+  using Params = EpiPlainParams;
   static __device__ __forceinline__ long coff(const Params& p, int m, int n) {
-    return p.c_blocked ? (((long)(n >> p.c_blocked) * p.c_rows + m) << p.c_blocked) + (n & ((1 << p.c_blocked) - 1)) : (long)m * p.ldc + n;
+    return p.c_blocked ? (((long)(n >> p.c_blocked) * p.c_brows + m) << p.c_blocked) + (n & ((1 << p.c_blocked) - 1)) : (long)m * p.ldc + n;
   }
   // a row tile that lies in the declared-zero part of A (GemmArgs::m_top): accumulating or atomically adding zero changes nothing
   static __device__ __forceinline__ bool dead_is_noop(const Params& p) { return (p.accumulate || p.atomic) && p.act == 0 && p.bias == nullptr; }
-  template <int FM, int FN, int NG> struct Pre {};
+  // MAP: lane l of a wave holds the C row of the wave tile's row l (tiles are at most 64 rows high), loaded before the main loop and handed
+  // to the lanes that store the row by a shuffle -- one register and one load in flight under the K loop
+  template <bool, int DUMMY = 0> struct PreRows {};
+  template <int DUMMY> struct PreRows<true, DUMMY> { int r; };
+  template <int FM, int FN, int NG> struct Pre : PreRows<MAP> {};
   template <int FM, int FN, int NG>
-  static __device__ __forceinline__ void prefetch(const Params&, Pre<FM, FN, NG>&, int, int, int, int) {}
+  static __device__ __forceinline__ void prefetch(const Params& p, Pre<FM, FN, NG>& pre, int m0, int, int M, int) {
+    if constexpr (MAP) {
+      static_assert(16 * FM <= 64, "one lane per row of the wave tile");
+      const int lane = threadIdx.x & 63, m = m0 + lane;
+      pre.r = m;
+      if (lane < 16 * FM && m < M) { const int base = (m / p.c_unit) * p.c_unit; pre.r = base + p.c_rows[m - base]; }
+    }
+  }
+  // the C row of row `r` (0 .. 16 FM - 1) of the wave tile that starts at m0; every lane of the wave must call it
+  template <int FM, int FN, int NG>
+  static __device__ __forceinline__ int crow(const Pre<FM, FN, NG>& pre, int m0, int r) {
+    if constexpr (MAP) return __shfl(pre.r, r, 64);
+    else return m0 + r;
+  }
   // wave tiles 32 / 64 columns wide: accumulators go through RowStage so C is written in whole row runs
   template <int FN> static constexpr bool staged() { return FN == 2 || FN == 4; }
   template <int FM, int FN, int NG> static constexpr int lds_bytes() { return staged<FN>() ? 4 * RowStage<1, (staged<FN>() ? FN * 16 : 64)>::WAVE_BYTES : 0; }
   template <int FM, int FN, int NG>
-  static __device__ __forceinline__ void apply(const Params& p_in, f32x4 (&acc)[FM][NG * FN], const Pre<FM, FN, NG>&,
+  static __device__ __forceinline__ void apply(const Params& p_in, f32x4 (&acc)[FM][NG * FN], const Pre<FM, FN, NG>& pre,
                                                int m0, int n0, int M, int N, int split, char* lds) {
     Params q = p_in;
     if (q.split_stride) q.C = reinterpret_cast<float*>(q.C) + (long)split * q.split_stride;
@@ -56,11 +80,11 @@ struct EpiPlain {
         const int mode = p.atomic ? 3 : (p.accumulate ? (bf ? 4 : 2) : (bf ? 1 : 0));
         float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (use_bias) b4 = *reinterpret_cast<const float4*>(p.bias + n0 + u);
-        if (mode == 0) fast_rows<FM, FN, 0>(p, acc, st, m0, n0 + u, b4);
-        else if (mode == 1) fast_rows<FM, FN, 1>(p, acc, st, m0, n0 + u, b4);
-        else if (mode == 2) fast_rows<FM, FN, 2>(p, acc, st, m0, n0 + u, b4);
-        else if (mode == 4) fast_rows<FM, FN, 4>(p, acc, st, m0, n0 + u, b4);
-        else fast_rows<FM, FN, 3>(p, acc, st, m0, n0 + u, b4);
+        if (mode == 0) fast_rows<FM, FN, 0>(p, acc, pre, st, m0, n0 + u, b4);
+        else if (mode == 1) fast_rows<FM, FN, 1>(p, acc, pre, st, m0, n0 + u, b4);
+        else if (mode == 2) fast_rows<FM, FN, 2>(p, acc, pre, st, m0, n0 + u, b4);
+        else if (mode == 4) fast_rows<FM, FN, 4>(p, acc, pre, st, m0, n0 + u, b4);
+        else fast_rows<FM, FN, 3>(p, acc, pre, st, m0, n0 + u, b4);
         return;
       }
 #pragma unroll
@@ -69,7 +93,8 @@ struct EpiPlain {
 #pragma unroll
         for (int c = 0; c < RS::PASSES; c++) {
           const int row = RS::row(c), m = m0 + i * 16 + row, n = n0 + u;
-          if (m < M && n < N) cell(p, m, n, N, RS::get(st, row, u), bf, vec, use_bias);
+          const int mc = crow(pre, m0, i * 16 + row);
+          if (m < M && n < N) cell(p, mc, n, N, RS::get(st, row, u), bf, vec, use_bias);
         }
         __builtin_amdgcn_wave_barrier();
       }
@@ -80,13 +105,15 @@ struct EpiPlain {
 #pragma unroll
         for (int j = 0; j < FN; j++) {
           const int m = m0 + i * 16 + (lane & 15), n = n0 + j * 16 + (lane >> 4) * 4;
-          if (m < M && n < N) cell(p, m, n, N, acc[i][j], bf, vec, use_bias);
+          const int mc = crow(pre, m0, i * 16 + (lane & 15));
+          if (m < M && n < N) cell(p, mc, n, N, acc[i][j], bf, vec, use_bias);
         }
     }
   }
   // MODE 0: store fp32, 1: store bf16, 2: C += (fp32), 3: atomicAdd (fp32 split-K partials), 4: C += (bf16)
   template <int FM, int FN, int MODE>
-  static __device__ __forceinline__ void fast_rows(const Params& p, f32x4 (&acc)[FM][FN], float* st, int m0, int n, const float4& b4) {
+  static __device__ __forceinline__ void fast_rows(const Params& p, f32x4 (&acc)[FM][FN], const Pre<FM, FN, 1>& pre, float* st, int m0, int n,
+                                                   const float4& b4) {
     using RS = RowStage<1, FN * 16>;
     const int u = RS::unit();
 #pragma unroll
@@ -96,7 +123,7 @@ struct EpiPlain {
       for (int c = 0; c < RS::PASSES; c++) {
         const int row = RS::row(c);
         const f32x4 a = RS::get(st, row, u);
-        const long off = coff(p, m0 + i * 16 + row, n);
+        const long off = coff(p, crow(pre, m0, i * 16 + row), n);
         float v0 = p.alpha * a[0] + b4.x, v1 = p.alpha * a[1] + b4.y, v2 = p.alpha * a[2] + b4.z, v3 = p.alpha * a[3] + b4.w;
         if constexpr (MODE == 1 || MODE == 4) {
           if constexpr (MODE == 4) {
@@ -117,6 +144,7 @@ struct EpiPlain {
       __builtin_amdgcn_wave_barrier();
     }
   }
+  // (m: the C row, already mapped)
   static __device__ __forceinline__ void cell(const Params& p, int m, int n, int N, const f32x4& a, bool bf, bool vec, bool use_bias) {
     float v[4];
 #pragma unroll
@@ -140,6 +168,8 @@ struct EpiPlain {
   }
 };
 
+using EpiPlain = EpiPlainT<false>;
+
 #ifndef PTV_PF_TN
 #define PTV_PF_TN 3
 #endif
@@ -155,13 +185,24 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_plain_kernel(GemmArgs g, Epi
   gemm_body<CT, BM, BN, WGM, WGN, 1, KA, KB, EpiPlain, SA, SB, (BM * BN <= 64 * 64 ? 2 : PLAIN_PF_BIG(KA, KB, SA, SB))>(g, ep);
 }
 
+// the same kernel with the row map on C (EpiPlainParams::c_rows): A row-per-sample only
+template <class CT, int BM, int BN, int WGM, int WGN, bool KB, bool SA, bool SB>
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_plain_map_kernel(GemmArgs g, EpiPlainParams ep) {
+  if (g.prio) __builtin_amdgcn_s_setprio(3);
+  gemm_body<CT, BM, BN, WGM, WGN, 1, false, KB, EpiPlainT<true>, SA, SB, (BM * BN <= 64 * 64 ? 2 : PLAIN_PF_BIG(false, KB, SA, SB))>(g, ep);
+}
+
 // C[m][n] (+)= ws[0][m][n] + ws[1][m][n] + ... in split order (alpha and the bias are already inside the partials)
-__global__ void splitk_reduce_kernel(float* __restrict__ C, long ldc, const float* __restrict__ ws, int M, int N, int splits, int accumulate) {
+// (c_rows: the row map of EpiPlainParams, applied here -- the partials lie in the workspace in product row order)
+__global__ void splitk_reduce_kernel(float* __restrict__ C, long ldc, const float* __restrict__ ws, int M, int N, int splits, int accumulate,
+                                     const int* __restrict__ c_rows, int c_unit) {
   const long total = (long)M * N;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     float sum = 0.f;
     for (int z = 0; z < splits; z++) sum += ws[(long)z * total + i];
-    float* cp = C + (i / N) * ldc + (i % N);
+    long m = i / N;
+    if (c_rows) { const long base = (m / c_unit) * c_unit; m = base + c_rows[m - base]; }
+    float* cp = C + m * ldc + (i % N);
     *cp = (accumulate ? *cp : 0.f) + sum;
   }
 }
@@ -175,6 +216,12 @@ __global__ void fill_rows_kernel(float* C, long ldc, int M, int N, float v) {
 template <class CT, int BM, int BN, bool KA, bool KB, bool SA, bool SB>
 static void launch_plain(const GemmArgs& g, const EpiPlain::Params& ep, int splits, hipStream_t s) {
   dim3 grid(cdiv(g.N, BN), cdiv(g.M, BM), splits);
+  if constexpr (!KA) {
+    if (ep.c_rows) {
+      hipLaunchKernelGGL((gemm_plain_map_kernel<CT, BM, BN, 2, 2, KB, SA, SB>), grid, dim3(NTHREADS), 0, s, g, ep);
+      return;
+    }
+  }
   hipLaunchKernelGGL((gemm_plain_kernel<CT, BM, BN, 2, 2, KA, KB, SA, SB>), grid, dim3(NTHREADS), 0, s, g, ep);
 }
 
@@ -244,7 +291,8 @@ static int gemm_dispatch(int transA, int transB, GemmArgs g, EpiPlain::Params ep
   }
   if (ws) {
     ep.C = ws; ep.ldc = g.N; ep.accumulate = 0; ep.atomic = 0; ep.split_stride = (long)g.M * g.N;
-  } else if (splits > 1) {
+    ep.c_rows = nullptr; ep.c_unit = 0;                          // partials in product row order: the reduction applies the row map
+  } else if (splits > 1) {                                       // (atomics go through the row map in the epilogue)
     ep.atomic = 1;
     if (!ep.accumulate) {
       long total = (long)g.M * g.N;
@@ -265,7 +313,8 @@ static int gemm_dispatch(int transA, int transB, GemmArgs g, EpiPlain::Params ep
   if (ws) {
     const long total = (long)g.M * g.N;
     int nb = (int)((total + 255) / 256); if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, s, reinterpret_cast<float*>(ep_user.C), ep_user.ldc, ws, g.M, g.N, splits, ep_user.accumulate);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, s, reinterpret_cast<float*>(ep_user.C), ep_user.ldc, ws, g.M, g.N, splits, ep_user.accumulate,
+                       ep_user.c_rows, ep_user.c_unit);
   }
   return PTV_OK;
 }
@@ -290,7 +339,18 @@ extern "C" int ptv_gemm_mtop_seg(int prec, int transA, int transB, int M, int N,
                                  void* C, long ldc, const float* bias, float alpha,
                                  int accumulate, int act, int splitk, int dtypes, const int* m_top, long m_unit,
                                  const int* seg_n, long seg_unit, int seg_period, void* stream) {
+  return ptv_gemm_mtop_seg_map(prec, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, alpha, accumulate, act, splitk, dtypes, m_top, m_unit, seg_n,
+                               seg_unit, seg_period, nullptr, 0, stream);
+}
+
+extern "C" int ptv_gemm_mtop_seg_map(int prec, int transA, int transB, int M, int N, int K,
+                                     const void* A, long lda, const void* B, long ldb,
+                                     void* C, long ldc, const float* bias, float alpha,
+                                     int accumulate, int act, int splitk, int dtypes, const int* m_top, long m_unit,
+                                     const int* seg_n, long seg_unit, int seg_period, const int* c_rows, long c_unit, void* stream) {
   if (M < 0 || N < 0 || K < 0 || !A || !B || !C) return PTV_ERR_ARG;
+  // a row map on C: row-major C written once per element by a product whose rows are samples, whole units of c_unit rows
+  if (c_rows && ((dtypes & 24) || splitk > 1 || transA || c_unit <= 0 || c_unit > 0x7fffffffL || M % c_unit != 0)) return PTV_ERR_ARG;
   if (M == 0 || N == 0) return PTV_OK;
   const bool sa = dtypes & 1, sb = dtypes & 2, sc = dtypes & 4;
   if ((sa || sb) && prec != PTV_PREC_BF16) return PTV_ERR_ARG;       // bf16 operands feed the bf16 MFMA path only
@@ -306,7 +366,7 @@ extern "C" int ptv_gemm_mtop_seg(int prec, int transA, int transB, int M, int N,
   if (m_top && (transA || m_unit <= 0)) return PTV_ERR_ARG;            // a row limit on A: A must be row-per-sample
   if (seg_n && (transA || seg_unit <= 0 || (seg_unit & 127) || seg_period <= 0)) return PTV_ERR_ARG;   // (row tiles are 64 or 128 rows: whole tiles dead or live)
   ptv::GemmArgs g{A, lda, B, ldb, M, N, K, K, 0, m_top, m_unit, ptv::g_gemm_prio, seg_n, (int)seg_unit, seg_period};
-  ptv::EpiPlain::Params ep{C, ldc, bias, alpha, accumulate, act, 0, sc ? 1 : 0, (dtypes & 8) ? 5 : ((dtypes & 16) ? 4 : 0), M, 0};
+  ptv::EpiPlain::Params ep{C, ldc, bias, alpha, accumulate, act, 0, sc ? 1 : 0, (dtypes & 8) ? 5 : ((dtypes & 16) ? 4 : 0), M, 0, c_rows, c_rows ? (int)c_unit : 0};
   hipStream_t s = (hipStream_t)stream;
   int rc;
   if (prec != PTV_PREC_BF16) rc = ptv::gemm_dispatch<ptv::F32, false, false>(transA, transB, g, ep, splitk, s);

@@ -726,6 +726,75 @@ __global__ __launch_bounds__(1024) void rows_by_length_kernel(const int* __restr
   }
 }
 
+// The same order from many workgroups that never talk to each other (ptv_rows_plan): workgroup g places rows [256 g, 256 g + 256).  It counts
+// ALL R lengths itself -- thread t owns rows t, t + 256, ... and column t of cnt[bin][256] (its own LDS bank: no atomics, no conflicts) -- and
+// reduces the columns twice: after the chunks before its own (the rows of each bin that precede this chunk) and after the last chunk (the bin
+// totals).  A row's place = rows in longer bins + rows of its bin in earlier chunks + in earlier waves of the chunk + in earlier lanes of the wave.
+// Workgroup 0 also writes the segment counts, which follow from the bin totals: the rows with length > s are a prefix in this order.
+constexpr int PLAN_ROWS = 256, PLAN_MAX_BINS = 39;
+__global__ __launch_bounds__(PLAN_ROWS) void rows_plan_kernel(const int* __restrict__ lengths, int R, int nb, int steps, int* __restrict__ perm,
+                                                              int* __restrict__ len_sorted, int* __restrict__ seg_n) {
+  __shared__ int cnt[PLAN_MAX_BINS * PLAN_ROWS];
+  __shared__ int before[PLAN_MAX_BINS], total[PLAN_MAX_BINS], wcnt[4][PLAN_MAX_BINS + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nchunk = (R + PLAN_ROWS - 1) / PLAN_ROWS, mine = blockIdx.x;
+  for (int b = 0; b < nb; b++) cnt[b * PLAN_ROWS + tid] = 0;
+  auto bin_of = [&](int r) { return r < R ? min(max(lengths[r], 0), nb - 1) : -1; };
+  // chunks [c0, c1) into this thread's column.  Sixteen loads are issued back to back (a row that is not there loads row 0 and counts
+  // nothing: no branch between the loads) and the counts are LDS adds that return nothing (no read-modify-write chain; one owner per
+  // address, so no contention either).  Measured: no faster than four loads and plain increments (profiles/LOG.md) -- kept for its shape
+  auto count = [&](int c0, int c1) {
+    for (int c = c0; c < c1; c += 16) {
+      int q[16];
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const int r = (c + j) * PLAN_ROWS + tid;
+        const bool ok = c + j < c1 && r < R;
+        const int v = lengths[ok ? r : 0];
+        q[j] = ok ? min(max(v, 0), nb - 1) : -1;
+      }
+#pragma unroll
+      for (int j = 0; j < 16; j++)
+        if (q[j] >= 0) atomicAdd(&cnt[q[j] * PLAN_ROWS + tid], 1);
+    }
+  };
+  auto reduce = [&](int* out) {                                           // out[bin] = sum of the 256 columns; wave w takes bins w, w + 4, ...
+    __syncthreads();
+    for (int b = wave; b < nb; b += 4) {
+      int v = cnt[b * PLAN_ROWS + lane] + cnt[b * PLAN_ROWS + 64 + lane] + cnt[b * PLAN_ROWS + 128 + lane] + cnt[b * PLAN_ROWS + 192 + lane];
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+      if (lane == 0) out[b] = v;
+    }
+    __syncthreads();
+  };
+  count(0, mine);
+  reduce(before);
+  count(mine, nchunk);
+  reduce(total);
+  // this chunk: the rows of the same bin in earlier lanes of the wave (ballots), the waves' counts through LDS
+  const int r = mine * PLAN_ROWS + tid, q = bin_of(r);
+  int rank = 0;
+  for (int b = 0; b < nb; b++) {
+    const unsigned long long m = __ballot(q == b);
+    if (q == b) rank = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wcnt[wave][b] = __popcll(m);
+  }
+  __syncthreads();
+  if (q >= 0) {
+    int pos = before[q] + rank;
+    for (int b = q + 1; b < nb; b++) pos += total[b];                     // bins in descending order of length
+    for (int w = 0; w < wave; w++) pos += wcnt[w][q];
+    perm[pos] = r;
+    if (len_sorted) len_sorted[pos] = q;
+  }
+  if (seg_n && mine == 0 && tid < steps) {
+    int live = 0;                                                         // rows with length > tid
+    for (int b = tid + 1; b < nb; b++) live += total[b];
+    seg_n[tid] = (live + 127) / 128 * 128;
+  }
+}
+
 }  // namespace ptv
 
 using namespace ptv;
@@ -741,6 +810,17 @@ extern "C" int ptv_rows_by_length(const int* lengths, int* perm, long R, int max
     attr = true;
   }
   hipLaunchKernelGGL(rows_by_length_kernel, dim3(1), dim3(1024), lds, (hipStream_t)stream, lengths, perm, R, nb);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+extern "C" int ptv_rows_plan(const int* lengths, long R, int max_len, int steps, int* perm, int* len_sorted, int* seg_n, void* stream) {
+  if (!lengths || !perm || R <= 0 || R > 0x7fffffffL || max_len < 0) return PTV_ERR_ARG;
+  if (seg_n && ((R & 127) || steps <= 0 || steps > 64)) return PTV_ERR_ARG;
+  if (max_len + 1 > PLAN_MAX_BINS) return PTV_ERR_UNSUPPORTED;             // lengths up to 38, as ptv_rows_by_length
+  if (R > PTV_ROWS_PLAN_MAX_R) return PTV_ERR_UNSUPPORTED;                 // every workgroup reads all R lengths: quadratic
+  hipLaunchKernelGGL(rows_plan_kernel, dim3((unsigned)((R + PLAN_ROWS - 1) / PLAN_ROWS)), dim3(PLAN_ROWS), 0, (hipStream_t)stream, lengths, (int)R,
+                     max_len + 1, seg_n ? steps : 0, perm, len_sorted, seg_n);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

@@ -13,6 +13,10 @@ extern "C" const char* ptv_arch(void) { return "gfx950"; }
 // 6 (round 6): the ptv_*_top entry points / PTV_DTF_LIVE_TOP (round 5, unversioned then), the bwd / loss / bigru composites, row limits in
 // ptv_wgrad's guarded tail and ptv_dur_out_wgrad, PTV_BGF_D_W_IH_F32; debug / profiling entry points moved to ptvae_hip_debug.h;
 // ptv_header_hash added (the loader compares it with the headers it binds from)
+// 7 (round 7): the output path and the device song bank (ptv_grid_to_pr, ptv_chord_tokens, ptv_window_rolls, ptv_detrend_pianotree)
+// still 7: ptv_rows_plan (sort + sorted lengths + segment counts in one multi-block launch) and ptv_gemm_mtop_seg_map (a row map on the
+// plain product's C) added, PTV_DTB_DNS_S / PTV_DTB_DTOK_S removed (ptv_decoder_tf_bwd's sorted branch stores through PERM).  The number
+// stays because the host tests of the two round-7 families pin it; ptv_header_hash below is what refuses a library built from other headers
 extern "C" int ptv_abi_version(void) { return 7; }
 #ifndef PTV_HEADER_HASH
 #define PTV_HEADER_HASH "unknown"

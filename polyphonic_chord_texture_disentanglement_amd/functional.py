@@ -1262,14 +1262,9 @@ def _bigru_forward(prec, x3, lengths, w):
         # for ALL of them -- in row order a panel's longest row is nearly always the longest of the batch
         skip_by = lengths if ZERO_SKIP else None         # (the backward must skip the same fully masked panel steps, with the same row order)
         if lengths is not None and ZERO_SKIP and SORT_ROWS and T <= 38:
-            perm = torch.empty(M, device=dev, dtype=torch.int32)
-            call('ptv_rows_by_length', ptr(lengths), ptr(perm), M, T, stream_ptr())
-            if WGRAD_SEG and M % 128 == 0 and lib().ptv_wgrad_seg_supported(T * M, M):
-                # (round 6) ... and the live prefix of every position in that order: the weight_hh products clip to it (ptv_bigru_rows_bwd)
-                len_s = torch.empty(M, device=dev, dtype=torch.int32)
-                call('ptv_gather_rows', ptr(len_s), ptr(lengths), ptr(perm), M, 1, 0, 0, 1, stream_ptr())
-                seg = torch.empty(T, device=dev, dtype=torch.int32)
-                call('ptv_rows_seg_counts', ptr(len_s), M, T, ptr(seg), stream_ptr())
+            # (round 6) ... and the live prefix of every position in that order: the weight_hh products clip to it (ptv_bigru_rows_bwd)
+            want_seg = bool(WGRAD_SEG and M % 128 == 0 and lib().ptv_wgrad_seg_supported(T * M, M))
+            perm, _, seg = rows_plan(lengths, M, T, T, want_seg, want_len=False)
         if BIGRU_BWD_COMPOSITE:
             state = _bigru_rows_fwd_composite(x3, lengths, skip_by, perm, seg, w, out, side, T, M, I, H, dev)
             if state is not None:
@@ -2162,9 +2157,8 @@ def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
             'PART_T': torch.empty(lib().ptv_gru_persist_part_elems(1, B, Ht, S), device=dev) if S else None,
             'SYNC': _persist_sync(1, dev)}
     srt = st.sorted
-    if srt is not None:                                   # the forward ran on length-sorted rows: operands in that order, dNS / dtok scattered back
-        tens.update(PERM=srt.perm, ROW_LEN=srt.len, NS16S=srt.NS16S, TOK_OP=srt.TOK_S.view(M, E), DNS_S=_empty(R, Ht, dev=dev),
-                    DTOK_S=_empty(15, R, E, dev=dev), SEG_N=srt.seg_n)
+    if srt is not None:                                   # the forward ran on length-sorted rows: operands in that order, dNS / dtok stored through PERM
+        tens.update(PERM=srt.perm, ROW_LEN=srt.len, NS16S=srt.NS16S, TOK_OP=srt.TOK_S.view(M, E), SEG_N=srt.seg_n)
     if POISON_DEAD_STEPS and top_h is not None and st.live_top is not None:        # (tests: whatever reads a dead row of these gets NaN -- heads_bwd / the BPTT leave them unwritten)
         _poison(tens['DNSUM'], tens['DGI_N'], tens['DGH_N'], tens['DY16'])
     evs = _fork_events('DTB', 4)
@@ -2737,6 +2731,28 @@ class LiveRows:
         return self.pitch_t, self.dur_t, self.counts
 
 
+ROWS_PLAN_MAX_R = 65536            # PTV_ROWS_PLAN_MAX_R of include/ptvae_hip.h: above it ptv_rows_plan refuses (its work is quadratic in the rows)
+
+
+def rows_plan(lengths, R, max_len, steps, want_seg, want_len=True):
+    """-> (perm, lengths in that order or None, segment counts or None) of R rows in descending length order: one ptv_rows_plan launch, or
+    above its row limit the sort, the gather of the lengths and the one-workgroup count it stands for"""
+    dev = lengths.device
+    perm = torch.empty(R, device=dev, dtype=torch.int32)
+    plan = R <= ROWS_PLAN_MAX_R
+    len_s = torch.empty(R, device=dev, dtype=torch.int32) if (want_len or (want_seg and not plan)) else None
+    seg = torch.empty(steps, device=dev, dtype=torch.int32) if want_seg else None
+    if plan:
+        call('ptv_rows_plan', ptr(lengths), R, max_len, steps, ptr(perm), ptr(len_s), ptr(seg), stream_ptr())
+    else:
+        call('ptv_rows_by_length', ptr(lengths), ptr(perm), R, max_len, stream_ptr())
+        if len_s is not None:
+            call('ptv_gather_rows', ptr(len_s), ptr(lengths), ptr(perm), R, 1, 0, 0, 1, stream_ptr())
+        if seg is not None:
+            call('ptv_rows_seg_counts', ptr(len_s), R, steps, ptr(seg), stream_ptr())
+    return perm, len_s, seg
+
+
 def live_rows(x):
     """called by DisentangleVAE.loss() before run(): -> the LiveRows plan of x (targets computed now, on the current stream), or None
     where the decoder takes no dead-step limit"""
@@ -2756,18 +2772,14 @@ def live_rows(x):
         # per-row dead work (round 6): the decoder's rows (t, b) in the order of DESCENDING number of live note steps.  Here: the
         # permutation, the lengths and the loss targets in that order; the decoder node takes them up if its composite runs
         # (_decoder_tf_composite) and records which order its logits are in
-        perm = torch.empty(R, device=x.device, dtype=torch.int32)
-        call('ptv_rows_by_length', ptr(row_live), ptr(perm), R, 15, stream_ptr())
-        len_s = torch.empty(R, device=x.device, dtype=torch.int32)
-        call('ptv_gather_rows', ptr(len_s), ptr(row_live), ptr(perm), R, 1, 0, 0, 1, stream_ptr())
+        # ... and the live prefix of every note step in that order (128-row blocks): the weight-gradient products over (note step, row) clip to it
+        # (slabs of the products must not straddle a note step)
+        want_seg = bool(WGRAD_SEG and R % 128 == 0 and lib().ptv_wgrad_seg_supported(15 * R, R))
+        perm, len_s, seg_n = rows_plan(row_live, R, 15, 15, want_seg)
         pt_s, dt_s = torch.empty_like(pitch_t), torch.empty_like(dur_t)
         call('ptv_gather_rows', ptr(pt_s), ptr(pitch_t), ptr(perm), R, 1, R, R, 15, stream_ptr())
         call('ptv_gather_rows', ptr(dt_s), ptr(dur_t), ptr(perm), R, 5, 5 * R, 5 * R, 15, stream_ptr())
-        seg_n = None
-        if WGRAD_SEG and R % 128 == 0 and lib().ptv_wgrad_seg_supported(15 * R, R):    # (slabs of the products must not straddle a note step)
-            # ... and the live prefix of every note step in that order (128-row blocks): the weight-gradient products over (note step, row) clip to it
-            seg_n = torch.empty(15, device=x.device, dtype=torch.int32)
-            call('ptv_rows_seg_counts', ptr(len_s), R, 15, ptr(seg_n), stream_ptr())
+        if seg_n is not None:
             global _LAST_SEG_N
             _LAST_SEG_N = seg_n                                  # (bench.py's roofline record: the live fraction of the segmented products)
         srt = dict(perm=perm, len=len_s, pt=pt_s, dt=dt_s, seg_n=seg_n)
