@@ -795,6 +795,39 @@ int ptv_grid_to_pr(const long* grid, int B, int R, int max_notes, int min_pitch,
 int ptv_chord_tokens(const float* root, const float* chroma, const float* bass, float* c, float* chord14, int T, int B, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-sample scores (csrc/score.hip; forward only): what the loss node above reduces to 11 batch means, kept per sample, plus the arg-max
+ * hit counts behind the reconstruction accuracies.  Every output element has one writer and one fixed summation order (no float atomics,
+ * no workspace): results are bit-identical from run to run and do not depend on the layout the logits come in.
+ * ptv_recon_step_scores: pitch / dur fp32 logits; row i of pitch starts at pitch + i * ld_pitch (ld_pitch >= 130; 16-byte loads when
+ *   ld_pitch % 4 == 0, ld_pitch >= 132 and pitch is 16-byte aligned, 4-byte loads of the same values otherwise), row i of dur is 10
+ *   contiguous floats (5 bits x 2 classes); i = (n*32 + t)*B + b if step_major, else (b*32 + t)*15 + n (ptv_pianotree_targets' orders).
+ *   Targets are read from x (int64 [B,32,16,6]), row n + 1: pitch x[..,0] (130 = ignored), duration bits x[..,1..5] (2 = ignored).
+ *   A row or bit whose target is ignored is never loaded; a pitch target outside 0..130 / a bit outside 0..2 is skipped the same way.
+ *   -> step_scores [B,32,2] f32 = (pitch NLL sum, duration NLL sum) of the step, rows added in ascending n, bits in ascending order;
+ *      NLL = -(l[target] - max - log(sum exp(l - max))) in fp32
+ *      step_counts [B,32,6] int32 = pitch_n (pitch targets != 130), pitch_hit (those whose arg-max over the 130 classes is the target),
+ *      dur_n (bit targets != 2), dur_hit (those whose arg-max of the two classes is the target), note_n (pitch targets < 128),
+ *      note_hit (those with the pitch hit and all five bits hit; an ignored bit is not a hit).  Arg-max ties resolve to the lowest
+ *      index (a tied duration pair is class 0).  A step without targets writes zeros.  Both outputs are batch-major whatever the input.
+ * ptv_score_fold: scores [B,2] f32 / counts [B,6] int32 = the sums over t = 0..31 in ascending order (fp32, sequential).
+ * ptv_kl_rows: out[b] = sum_z (-log sd + (sd^2 + mu^2)/2 - 1/2) over mu / sd [B,Z]; one wave per row, lane l adds z = l, l + 64, ...
+ *   and a xor tree folds the lanes: the order depends on Z only, not on B.
+ * ptv_chord_step_scores: root [.,12], chroma [.,12,2], bass [.,12] logits with rows [8][B] if step_major else [B][8]; targets derived from
+ *   c [B,8,36] as ptv_chord_targets derives them -> scores [B,3] f32 = root / chroma / bass NLL sums over the 8 steps (ascending step,
+ *   chroma bits ascending), counts [B,3] int32 = root hits of 8, chroma-bit hits of 96, bass hits of 8.  The tie rules as above.
+ * ptv_roll_match: est_pr / ref_pr f32 [B,32,128] (ptv_grid_to_pr's pr_mat) -> counts [B,4] int32 = cells > 0 in est, cells > 0 in ref,
+ *   cells > 0 in both (onset matches), cells > 0 in both and equal (onset and duration match).
+ * All five return PTV_ERR_ARG for a NULL pointer or B <= 0 and write nothing then.
+ */
+int ptv_recon_step_scores(const float* pitch, long ld_pitch, const float* dur, const long* x, int B, int step_major, float* step_scores,
+                          int* step_counts, void* stream);
+int ptv_score_fold(const float* step_scores, const int* step_counts, int B, float* scores, int* counts, void* stream);
+int ptv_kl_rows(const float* mu, const float* sd, int B, int Z, float* out, void* stream);
+int ptv_chord_step_scores(const float* root, const float* chroma, const float* bass, const float* c, int B, int step_major, float* scores,
+                          int* counts, void* stream);
+int ptv_roll_match(const float* est_pr, const float* ref_pr, int B, int* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Note-matrix song bank on device (csrc/dataset.hip): what ArrangementDataset.__getitem__ does BEFORE the data contract above, from
  * the per-bar note matrices (dataset.py:67-93 over converter.py:35-76), and detrend_pianotree (dataset.py:123-213) after it.
  * Bank: the bars of all songs in order.  acc_rec / mel_rec hold one 32-bit record per note, bar after bar, acc_off / mel_off [n_bar+1]

@@ -99,7 +99,9 @@ class SummaryWriters:
     """One writer per loss name (writer_names[0] must be 'loss'); `tags` maps a tag key to the indices of the
     writers that log it (None = all); the written tag is '<task>_<key>' for task in ('train', 'val')."""
 
-    def __init__(self, writer_names, tags, log_path, tasks=('train', 'val')):
+    def __init__(self, writer_names, tags, log_path, tasks=('train', 'val'), extra=None):
+        """extra: {task: names} -- scalars outside the loss table (the trainer's 'val_metrics'): one writer per name, written under
+        the tag `task` by write_task(task, {name: value}, step)"""
         assert writer_names[0] == 'loss'
         self.log_path, self.writer_names = log_path, writer_names
         everything = tuple(range(len(writer_names)))
@@ -107,6 +109,14 @@ class SummaryWriters:
         sink = _TensorboardWriter or _JsonlWriter
         self.writers = {name: sink(os.path.join(log_path, name)) for name in writer_names}
         self.all_tags = {task: {task + '_' + key: ids for key, ids in self.tags.items()} for task in tasks}
+        self.extra = {task: tuple(names) for task, names in (extra or {}).items()}
+        for names in self.extra.values():
+            for name in names:
+                if name not in self.writers:
+                    self.writers[name] = sink(os.path.join(log_path, name))
+
+    def accepts(self, task):
+        return task in self.all_tags or task in self.extra
 
     def single_write(self, name, tag, val, step):
         self.writers[name].add_scalar(tag, val, step)
@@ -118,5 +128,9 @@ class SummaryWriters:
             self.single_write(self.writer_names[index], tag, val, step)
 
     def write_task(self, task, vals_dic, step):
+        if task in self.extra:
+            for name in self.extra[task]:
+                self.single_write(name, task, vals_dic[name], step)
+            return
         for tag, ids in self.all_tags[task].items():
             self.write_tag(task, tag, [vals_dic[self.writer_names[index]] for index in ids], step)

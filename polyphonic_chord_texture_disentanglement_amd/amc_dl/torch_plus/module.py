@@ -221,19 +221,35 @@ class TrainingInterface:
         self._flush_logs()
         return epoch_loss_dic
 
+    # ---- eval_metrics=True (a keyword of the constructor): every validation batch additionally goes through the model's
+    # reconstruction_counts (teacher-forced accuracies, the free-running reconstruction's onset / exact F1, NLL per note); the integer
+    # counts are pooled over the batches -- the counts, not the ratios -- and the report is kept in self.val_metrics
+    eval_metrics = False
+    val_metrics = None
+
     def eval(self):
         """validation pass: same call as training (mode 'train', module.py:170) without gradients; the
         parameter schedulers are frozen in 'val' mode"""
         self.model.eval()
         self.param_scheduler.eval()
         epoch_loss_dic = self._init_loss_dic()
+        tally = None
         for batch in self.data_loaders.val_loader:
             inputs = self._batch_to_inputs(batch)
             with torch.no_grad():
                 outputs = self.model('train', *inputs, **self.param_scheduler.step())
             self._log('val', outputs, epoch_loss_dic, self.val_step)
             self.val_step += 1
+            if self.eval_metrics:
+                counts = self.model.reconstruction_counts(*inputs)
+                tally = counts if tally is None else {k: tally[k] + v for k, v in counts.items()}
         self._flush_logs()
+        if self.eval_metrics and tally is not None:
+            self.val_counts = tally
+            self.val_metrics = self.model.report_from_counts(tally)
+            accepts = getattr(self.summary_writers, 'accepts', None)
+            if self.is_main and accepts is not None and accepts('val_metrics'):      # (a writer built with that extra task; else: the attribute only)
+                self.summary_writers.write_task('val_metrics', self.val_metrics, self.val_step)
         return epoch_loss_dic
 
     @property
@@ -346,6 +362,8 @@ class TrainingInterface:
         for line in (f'Epoch: {self.epoch + 1:02} | Time: {mins}m {secs}s', f'\tTrain Loss: {train_loss:.3f}',
                      f'\t Valid. Loss: {valid_loss:.3f}'):
             print(line, flush=True)
+        if self.eval_metrics and self.val_metrics:
+            print('\t Valid. ' + ' | '.join(f'{k}: {v:.4f}' for k, v in self.val_metrics.items()), flush=True)
 
     def run(self, start_epoch=None, start_train_step=None, start_val_step=None):
         """n_epoch x (train, eval); checkpoints '<name>_epoch.pt' every epoch, '<name>_valid.pt' on a new

@@ -17,6 +17,8 @@ extern "C" const char* ptv_arch(void) { return "gfx950"; }
 // still 7: ptv_rows_plan (sort + sorted lengths + segment counts in one multi-block launch) and ptv_gemm_mtop_seg_map (a row map on the
 // plain product's C) added, PTV_DTB_DNS_S / PTV_DTB_DTOK_S removed (ptv_decoder_tf_bwd's sorted branch stores through PERM).  The number
 // stays because the host tests of the two round-7 families pin it; ptv_header_hash below is what refuses a library built from other headers
+// still 7: the per-sample scores (csrc/score.hip: ptv_recon_step_scores, ptv_score_fold, ptv_kl_rows, ptv_chord_step_scores, ptv_roll_match)
+// added; no existing entry point changed, and the same host tests pin the number
 extern "C" int ptv_abi_version(void) { return 7; }
 #ifndef PTV_HEADER_HASH
 #define PTV_HEADER_HASH "unknown"

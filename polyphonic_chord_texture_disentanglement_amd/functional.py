@@ -3089,3 +3089,94 @@ class ChordLossFn(torch.autograd.Function):
         if ctx.sm:
             droot, dchroma, dbass = (t.permute(*_chord_perm(t)) for t in (droot, dchroma, dbass))
         return droot, dchroma, dbass, None
+
+
+# =============================================================================================
+# Per-sample scores (csrc/score.hip): forward only, no autograd node; every result is a fresh, detached device tensor and nothing
+# synchronises.  The logits are taken as run() returns them: the decoders' permuted views are consumed in place (step-major).
+# =============================================================================================
+def _need(t, name, shape, dtypes=None):
+    """ValueError (before any launch) unless t is a device tensor of trailing shape `shape`; -> its batch size"""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError('%s: a device tensor expected, got %s' % (name, 'a CPU tensor' if torch.is_tensor(t) else type(t).__name__))
+    if t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != tuple(shape) or t.shape[0] < 1 or (dtypes is not None and t.dtype not in dtypes):
+        raise ValueError('%s: [B,%s]%s expected, got %s %s' % (name, ','.join(str(s) for s in shape),
+                                                                '' if dtypes is None else ' of ' + ' / '.join(str(d) for d in dtypes),
+                                                                t.dtype, tuple(t.shape)))
+    return t.shape[0]
+
+
+def _same_batch(**sizes):
+    if len(set(sizes.values())) > 1:
+        raise ValueError('batch sizes differ: ' + ', '.join('%s %d' % kv for kv in sizes.items()))
+
+
+_INT_GRID = (torch.int64, torch.int32, torch.uint8, torch.int8)
+
+
+def score_fold(step_scores, step_counts):
+    """step_scores f32 [B,32,2], step_counts int32 [B,32,6] -> (scores f32 [B,2], counts int32 [B,6]): the time steps added in ascending order"""
+    B = _need(step_scores, 'step_scores', (32, 2), (F32,))
+    _same_batch(step_scores=B, step_counts=_need(step_counts, 'step_counts', (32, 6), (torch.int32,)))
+    step_scores, step_counts = step_scores.detach().contiguous(), step_counts.contiguous()
+    scores = _empty(B, 2, dev=step_scores.device)
+    counts = torch.empty(B, 6, device=step_scores.device, dtype=torch.int32)
+    call('ptv_score_fold', ptr(step_scores), ptr(step_counts), B, ptr(scores), ptr(counts), stream_ptr())
+    return scores, counts
+
+
+def recon_scores(x, pitch, dur):
+    """x int [B,32,16,6], pitch f32 [B,32,15,130], dur f32 [B,32,15,5,2] (API shapes; the decoder's step-major views are read in place)
+    -> step_scores f32 [B,32,2], step_counts int32 [B,32,6], scores f32 [B,2], counts int32 [B,6]   (include/ptvae_hip.h "Per-sample scores")"""
+    B = _need(x, 'x', (32, 16, 6), _INT_GRID)
+    _same_batch(x=B, pitch_outs=_need(pitch, 'pitch_outs', (32, 15, 130), (F32,)), dur_outs=_need(dur, 'dur_outs', (32, 15, 5, 2), (F32,)))
+    x = x.detach().long().contiguous()
+    (pitch_m, dur_m), sm = _mem_order([pitch.detach(), dur.detach()], [_PERM[4], _PERM[5]])
+    if sm and not dur_m.is_contiguous():                     # (a duration row is 10 packed floats: nothing less)
+        (pitch_m, dur_m), sm = [pitch.detach().contiguous(), dur.detach().contiguous()], False
+    dev = x.device
+    step_scores = _empty(B, 32, 2, dev=dev)
+    step_counts = torch.empty(B, 32, 6, device=dev, dtype=torch.int32)
+    call('ptv_recon_step_scores', ptr(pitch_m), pitch_m.stride(-2), ptr(dur_m), ptr(x), B, int(sm), ptr(step_scores), ptr(step_counts),
+         stream_ptr())
+    return (step_scores, step_counts) + score_fold(step_scores, step_counts)
+
+
+def kl_rows(mu, sd):
+    """mu, sd f32 [B,Z] -> f32 [B]: KL(N(mu, sd) || N(0, 1)) summed over the latent (a sum, where kl_loss is the mean over B * Z)"""
+    for n, t in (('mu', mu), ('sd', sd)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dim() != 2 or t.dtype != F32:
+            raise ValueError('%s: a device f32 [B,Z] tensor expected' % n)
+    if mu.shape != sd.shape or mu.shape[0] < 1 or mu.shape[1] < 1:
+        raise ValueError('mu %s and sd %s differ or are empty' % (tuple(mu.shape), tuple(sd.shape)))
+    mu, sd = mu.detach().contiguous(), sd.detach().contiguous()
+    out = _empty(mu.shape[0], dev=mu.device)
+    call('ptv_kl_rows', ptr(mu), ptr(sd), mu.shape[0], mu.shape[1], ptr(out), stream_ptr())
+    return out
+
+
+def chord_scores(c, root, chroma, bass):
+    """c f32 [B,8,36], root / bass f32 [B,8,12], chroma f32 [B,8,12,2] (API shapes, ChordLossFn's two layouts)
+    -> scores f32 [B,3] = root / chroma / bass NLL sums, counts int32 [B,3] = root hits of 8, chroma-bit hits of 96, bass hits of 8"""
+    B = _need(c, 'c', (8, 36))
+    _same_batch(c=B, recon_root=_need(root, 'recon_root', (8, 12), (F32,)), recon_chroma=_need(chroma, 'recon_chroma', (8, 12, 2), (F32,)),
+                recon_bass=_need(bass, 'recon_bass', (8, 12), (F32,)))
+    c = c.detach().float().contiguous()
+    (root_m, chroma_m, bass_m), sm = _mem_order([root.detach(), chroma.detach(), bass.detach()],
+                                                [_chord_perm(root), _chord_perm(chroma), _chord_perm(bass)])
+    if sm and not all(t.is_contiguous() for t in (root_m, chroma_m, bass_m)):          # (rows of 12 / 24 floats, densely packed: nothing less)
+        (root_m, chroma_m, bass_m), sm = [t.contiguous() for t in (root.detach(), chroma.detach(), bass.detach())], False
+    scores = _empty(B, 3, dev=c.device)
+    counts = torch.empty(B, 3, device=c.device, dtype=torch.int32)
+    call('ptv_chord_step_scores', ptr(root_m), ptr(chroma_m), ptr(bass_m), ptr(c), B, int(sm), ptr(scores), ptr(counts), stream_ptr())
+    return scores, counts
+
+
+def roll_match(est_pr, ref_pr):
+    """two f32 [B,32,128] rolls (grid_to_pr_and_notes_batch's pr_mat) -> int32 [B,4] = cells > 0 in est, in ref, in both, in both and equal"""
+    B = _need(est_pr, 'est_pr', (32, 128), (F32,))
+    _same_batch(est_pr=B, ref_pr=_need(ref_pr, 'ref_pr', (32, 128), (F32,)))
+    est_pr, ref_pr = est_pr.detach().contiguous(), ref_pr.detach().contiguous()
+    counts = torch.empty(B, 4, device=est_pr.device, dtype=torch.int32)
+    call('ptv_roll_match', ptr(est_pr), ptr(ref_pr), B, ptr(counts), stream_ptr())
+    return counts

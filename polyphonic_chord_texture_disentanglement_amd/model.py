@@ -47,6 +47,7 @@ class DisentangleVAE(PytorchModel):
         self._philox = None         # (seed, global index of this process's first sample): see use_philox()
         self._draws = 0
         self._sample_draws = 0      # draw number of the next sampled decode that names none (advances once per sampled decode)
+        self._mean_only = False     # set by score(sample=False) around its run()
 
     # ---- the texture encoder decides what the texture input is.  A TextureEncoder (init_model) reads the piano-roll pr_mat; a PtvaeEncoder
     # (init_model_detrended: the wiring of the reference's train.py:31-39) reads the detrended PianoTree grid dt_x, uint8 [B,32,16,39]
@@ -86,6 +87,8 @@ class DisentangleVAE(PytorchModel):
         return self
 
     def _rsample(self, name, dist):
+        if self._mean_only:                              # score(sample=False): z is the posterior mean, no draw is consumed
+            return dist.mean
         eps = None
         if self.eps_source is not None:
             eps = self.eps_source(name, dist.mean.shape, dist.mean.device)
@@ -212,6 +215,121 @@ class DisentangleVAE(PytorchModel):
         else:
             outputs = self.run(x, c, pr_mat, p['tfr1'], p['tfr2'], p['tfr3'], live=live)
         return self.loss_function(x, c, *outputs, p['beta'], p['weights'], live=live)
+
+    # ---- per-sample scores and reconstruction accuracy (INTEGRATION.md "Per-sample scores"; forward only, csrc/score.hip)
+    def _score_inputs(self, x, c, pr_mat, dt_x, who):
+        """ValueError for a CPU tensor, a wrong trailing shape or differing batch sizes, before anything is launched -> the texture
+        encoder's input (pr_mat; for the detrended variant dt_x, or a dt_x grid in the pr_mat slot, or None = derived from x and c)"""
+        B = F_._need(x, who + ' x', (32, 16, 6), F_._INT_GRID)
+        sizes = dict(x=B, c=F_._need(c, who + ' c', (8, 36)))
+        tex = pr_mat
+        if self.detrended:
+            tex = dt_x if dt_x is not None else (pr_mat if torch.is_tensor(pr_mat) and pr_mat.dtype == torch.uint8 else None)
+            if tex is not None:
+                if not torch.is_tensor(tex) or not tex.is_cuda:
+                    raise ValueError(who + ' dt_x: a device tensor expected')
+                sizes['dt_x'] = self._check_dt_x(tex).shape[0]
+            elif pr_mat is not None:
+                sizes['pr_mat'] = F_._need(pr_mat, who + ' pr_mat', (32, 128))
+        else:
+            sizes['pr_mat'] = F_._need(pr_mat, who + ' pr_mat', (32, 128))
+        F_._same_batch(**sizes)
+        return tex
+
+    def score(self, x, c, pr_mat, dt_x=None, *, sample=False, beta=1.0):
+        """One teacher-forced pass (all ratios 1) without gradients -> a dict of detached device tensors, one entry per sample; nothing
+        synchronises.  pitch_nll, dur_nll, kl_chd, kl_rhy, root_nll, chroma_nll, bass_nll: f32 [B], SUMS over the sample's targets /
+        latent (loss() reports their batch means); elbo = -(pitch_nll + dur_nll) - beta * (kl_chd + kl_rhy); counts int32 [B,6] =
+        (pitch_n, pitch_hit, dur_n, dur_hit, note_n, note_hit); chord_counts int32 [B,3] = root hits of 8, chroma-bit hits of 96, bass
+        hits of 8; step_scores f32 [B,32,2] / step_counts int32 [B,32,6]: the reconstruction terms per time step.
+        sample=False: z is the posterior mean (deterministic); True: the model's usual noise (eps_source / use_philox / torch).
+        pr_mat: the texture encoder's input as in the inference family (for the detrended variant dt_x, here or as the 4th argument;
+        neither: derived from x and c).  The teacher-forcing coins it draws are put back: the `random` stream is left as it was."""
+        import random
+        tex = self._score_inputs(x, c, pr_mat, dt_x, 'score()')
+        coins = random.getstate()
+        self._mean_only = not sample
+        try:
+            with torch.no_grad():
+                if self.detrended:
+                    outs = self.run(x, c, pr_mat, 1., 1., 1., dt_x=tex)
+                else:
+                    outs = self.run(x, c, tex, 1., 1., 1.)
+                pitch, dur, dist_chd, dist_rhy, root, chroma, bass = outs
+                step_scores, step_counts, scores, counts = F_.recon_scores(x, pitch, dur)
+                kl_chd, kl_rhy = F_.kl_rows(dist_chd.mean, dist_chd.scale), F_.kl_rows(dist_rhy.mean, dist_rhy.scale)
+                chord, chord_counts = F_.chord_scores(c, root, chroma, bass)
+                B = scores.shape[0]
+                elbo = torch.empty(B, device=scores.device, dtype=torch.float32)
+                col = lambda t, j: t[:, j:j + 1]
+                F_.copy2d(elbo.view(B, 1), col(scores, 0), alpha=-1.0)
+                F_.copy2d(elbo.view(B, 1), col(scores, 1), alpha=-1.0, acc=True)
+                F_.copy2d(elbo.view(B, 1), kl_chd.view(B, 1), alpha=-float(beta), acc=True)
+                F_.copy2d(elbo.view(B, 1), kl_rhy.view(B, 1), alpha=-float(beta), acc=True)
+        finally:
+            self._mean_only = False
+            random.setstate(coins)
+        return dict(pitch_nll=scores[:, 0], dur_nll=scores[:, 1], kl_chd=kl_chd, kl_rhy=kl_rhy, root_nll=chord[:, 0],
+                    chroma_nll=chord[:, 1], bass_nll=chord[:, 2], elbo=elbo, counts=counts, chord_counts=chord_counts,
+                    step_scores=step_scores, step_counts=step_counts)
+
+    TALLY_NAMES = ('pitch_n', 'pitch_hit', 'dur_n', 'dur_hit', 'note_n', 'note_hit', 'root_hit', 'chroma_hit', 'bass_hit', 'chord_steps',
+                   'est_n', 'ref_n', 'onset_tp', 'exact_tp', 'nll')
+
+    REPORT_NAMES = ('pitch_acc', 'dur_acc', 'note_acc', 'root_acc', 'chroma_acc', 'bass_acc', 'onset_precision', 'onset_recall', 'onset_f1',
+                    'exact_f1', 'nll_per_note')
+
+    def reconstruction_counts(self, x, c, pr_mat, dt_x=None):
+        """The pooled counts behind reconstruction_report, as Python numbers from ONE host read (a trainer adds them over batches:
+        pool the counts, not the ratios).  Keys TALLY_NAMES: score(sample=False)'s six counts and three chord hit counts summed over the
+        batch, chord_steps = 8 B, the four roll-match counts of the free-running reconstruction inference(pr_mat, c, sample=False)
+        against the roll the same output path makes of x itself (so both sides carry the same 14-note and duration clipping), and
+        nll = sum(pitch_nll + dur_nll)."""
+        tex = self._score_inputs(x, c, pr_mat, dt_x, 'reconstruction_counts()')
+        s = self.score(x, c, pr_mat, dt_x, sample=False)
+        mode = self.training
+        with torch.no_grad():
+            if self.detrended and tex is None:
+                from .dataset import detrend_pianotree
+                tex = detrend_pianotree(x.long(), c)
+            dist_chd, dist_rhy = self.inference_encode(tex, c)
+            self._decode(dist_chd.mean, dist_rhy.mean, {})
+            # the decoded grid goes through the output path's canonical form first (x_clean: a step's first 14 readable notes, <eos>,
+            # <pad>), the layout x itself has: both rolls are then made from grids with the same clipping
+            to_pr = lambda grid: self.decoder.grid_to_pr_and_notes_batch(grid, 15, check=False)
+            est_pr = to_pr(to_pr(self.decoder.last_xhat)[3])[0]
+            ref_pr = to_pr(x)[0]
+            roll = F_.roll_match(est_pr, ref_pr)
+            flat = torch.cat([s['counts'].reshape(-1), s['chord_counts'].reshape(-1), roll.reshape(-1),
+                              s['pitch_nll'].contiguous().view(torch.int32), s['dur_nll'].contiguous().view(torch.int32)])
+        self.train(mode)
+        import numpy as np
+        B = x.shape[0]
+        h = flat.cpu().numpy()
+        cnt = h[:6 * B].reshape(B, 6).astype(np.int64).sum(0)
+        chd = h[6 * B:9 * B].reshape(B, 3).astype(np.int64).sum(0)
+        rm = h[9 * B:13 * B].reshape(B, 4).astype(np.int64).sum(0)
+        nll = float(h[13 * B:].view(np.float32).astype(np.float64).sum())
+        vals = [int(v) for v in cnt] + [int(v) for v in chd] + [8 * B] + [int(v) for v in rm] + [nll]
+        return dict(zip(self.TALLY_NAMES, vals))
+
+    @staticmethod
+    def report_from_counts(t):
+        """reconstruction_counts' tally (or the sum of several) -> the report: pooled ratios, total hits over total targets; a zero
+        denominator gives 0.0"""
+        div = lambda a, b: float(a) / float(b) if b else 0.0
+        f1 = lambda tp: div(2 * tp, t['est_n'] + t['ref_n'])
+        return dict(pitch_acc=div(t['pitch_hit'], t['pitch_n']), dur_acc=div(t['dur_hit'], t['dur_n']),
+                    note_acc=div(t['note_hit'], t['note_n']), root_acc=div(t['root_hit'], t['chord_steps']),
+                    chroma_acc=div(t['chroma_hit'], 12 * t['chord_steps']), bass_acc=div(t['bass_hit'], t['chord_steps']),
+                    onset_precision=div(t['onset_tp'], t['est_n']), onset_recall=div(t['onset_tp'], t['ref_n']),
+                    onset_f1=f1(t['onset_tp']), exact_f1=f1(t['exact_tp']), nll_per_note=div(t['nll'], t['note_n']))
+
+    def reconstruction_report(self, x, c, pr_mat, dt_x=None):
+        """Pitch / duration / note / chord accuracies of the teacher-forced pass, onset and exact (onset + duration) precision / recall / F1
+        of the free-running reconstruction, and the NLL per note, as Python floats from one host read (report_from_counts of
+        reconstruction_counts)."""
+        return self.report_from_counts(self.reconstruction_counts(x, c, pr_mat, dt_x))
 
     # ---- model.py:117-122.  In the whole inference family (inference_encode, inference, swap, posterior_sample, prior_sample, interp) the
     # argument the reference names `pr_mat` (`x` in prior_sample) is the texture encoder's input: the piano-roll f32 [B,32,128] for a

@@ -495,6 +495,15 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         out = F_.recon_loss(x.long(), recon_pitch, recon_dur, float(weights[0]), float(weights[1]), bool(weighted_dur))
         return out[0], out[1], out[2]
 
+    # ---- per-sample scores of logits the caller already holds (INTEGRATION.md "Per-sample scores"; forward only)
+    def score_outputs(self, x, pitch_outs, dur_outs):
+        """x int [B,32,16,6], pitch_outs [B,32,15,130], dur_outs [B,32,15,5,2] (what decoder() returns, consumed in place) -> dict of
+        detached device tensors: step_scores f32 [B,32,2] = (pitch NLL sum, duration NLL sum) per time step, step_counts int32 [B,32,6] =
+        (pitch_n, pitch_hit, dur_n, dur_hit, note_n, note_hit), and their sums over the time steps scores [B,2] / counts [B,6].  Rows and
+        bits whose target is <pad> are never read.  ValueError for CPU tensors or wrong shapes, before any launch."""
+        step_scores, step_counts, scores, counts = F_.recon_scores(x, pitch_outs, dur_outs)
+        return dict(step_scores=step_scores, step_counts=step_counts, scores=scores, counts=counts)
+
     # ---- ptvae.py:546-575, MIDI-free: notes come back as (pitch, start, end) tuples (velocity is the constant 100 of the
     # reference's pretty_midi.Note calls); pretty_midi is not needed
     def pr_to_notes(self, pr, bpm=80, start=0., one_hot=False):

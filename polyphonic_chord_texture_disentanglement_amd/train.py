@@ -42,6 +42,8 @@ def main():
                     help='hold tfr=1 (the published schedule decays to free-running after 2 steps)')
     ap.add_argument('--texture-encoder', default='conv', choices=['conv', 'detrended'],
                     help='conv: TextureEncoder on the piano-roll (default); detrended: the PtvaeEncoder of the reference\'s train.py:32 on dt_x')
+    ap.add_argument('--eval-metrics', action='store_true',
+                    help='validation additionally reports reconstruction accuracies, onset / exact F1 and NLL per note (DisentangleVAE.reconstruction_report)')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -75,7 +77,8 @@ def main():
     optimizer = FusedClipAdam(model.parameters(), lr=lr)
     scheduler = MinExponentialLR(optimizer, gamma=0.9999, minimum=1e-5)
     optimizer_scheduler = OptimizerScheduler(optimizer, scheduler, clip)
-    summary_writers = SummaryWriters(writer_names, {'loss': None}, log_path_mng.writer_path)
+    summary_writers = SummaryWriters(writer_names, {'loss': None}, log_path_mng.writer_path,
+                                     extra={'val_metrics': DisentangleVAE.REPORT_NAMES} if args.eval_metrics else None)
     if args.teacher_forced:
         tfr = [ConstantScheduler(1.0) for _ in range(3)]
     else:
@@ -84,7 +87,7 @@ def main():
                                          beta=TeacherForcingScheduler(beta, 0., f=kl_anealing),
                                          weights=ConstantScheduler(weights))
     training = TrainingVAE(device, model, world > 1, log_path_mng, data_loaders, summary_writers, optimizer_scheduler,
-                           param_scheduler, args.epochs)
+                           param_scheduler, args.epochs, eval_metrics=args.eval_metrics)
     if training.grad_sync is not None:
         training.grad_sync.optimizer = optimizer
     training.run()
