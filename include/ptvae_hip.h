@@ -923,10 +923,29 @@ int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitc
  *   ptv_note_token_sample / ptv_dur_out_token_sample / ptv_dur_gru_fwd_sample: ptv_note_token / ptv_dur_out_token / ptv_dur_gru_fwd with the
  *     block and the position of the rows: row r is sample sample_offset + r at time step t; note step n = 0..14 for the duration forms,
  *     the duration bit d for ptv_dur_out_token_sample; ptv_note_token_sample decides note step n - 1 (its n is the slot it fills, 1..15).
+ * Truncated sampling (top_k / min_p) bounds the support of the PITCH draw; the duration bits keep T_dur as their only control.  The block
+ * is then 48 bytes: the 32 above unchanged, followed by { int32 top_k, float ln_min_p, 8 reserved bytes (zero) }.
+ *   top_k >= 1: class c is kept iff logit[c] >= v_k, the k-th largest of the row's 130 logits counted with multiplicity -- classes tied
+ *     with the k-th value are ALL kept (so more than k may survive), whatever their column; top_k >= 130 keeps every class; 0 = off.
+ *   ln_min_p = ln(min_p) rounded from float64 to fp32, min_p in (0, 1]: class c is kept iff logit[c] >= m + T_pitch * ln_min_p in fp32
+ *     (the product rounded, then the sum), m the row's largest logit: p_c >= min_p * p_max under softmax(logits / T_pitch).  Any value
+ *     > 0 (write 1.0f) = off: the kernels test the word and never multiply an infinity by T.
+ *   Both: a class must pass both.  All comparisons are fp32 comparisons of the emitted logits (-0.0 == +0.0); the best class passes
+ *   either rule, so the kept set is never empty.  The decision is the first maximal index over the KEPT classes of logit + T_pitch * g with
+ *   exactly the noise words above (a dropped class leaves its word unused, nothing is re-keyed): an exact draw from the renormalised
+ *   truncated softmax, still a pure function of (seed, draw, global sample, t, n) and the row's logits.  T_pitch = 0 is the argmax.
+ *   Not built: nucleus (top-p) truncation -- it needs the cumulative mass of the sorted row; min_p adapts to the row's sharpness instead.
+ *   ptv_free_note_loop: bit 24 of train, together with bit 23, says io[21] is the 48-byte block; bit 24 without bit 23, with
+ *     train & 3 != 0, a coin mask or a NULL block is PTV_ERR_ARG before any launch.
+ *   ptv_note_token_sample_trunc: ptv_note_token_sample with the 48-byte block.
+ *   ptv_decoder_free_fwd: PTV_DFF_D_SAMPLE_TRUNC != 0 says PTV_DFF_SAMPLE is the 48-byte block.
  */
 int ptv_note_token_sample(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
                           float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
                           const int* force_pitch, int M, const void* sample, int t, void* stream);
+int ptv_note_token_sample_trunc(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
+                                float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
+                                const int* force_pitch, int M, const void* sample48, int t, void* stream);
 int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
                              int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream);
 int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,
@@ -977,7 +996,7 @@ enum PtvDffTensor {
   PTV_DFF_IDX, PTV_DFF_PLEN, PTV_DFF_GC16, PTV_DFF_DUR_SCR, PTV_DFF_IDX_SCR,
   PTV_DFF_XH0, PTV_DFF_XH1, PTV_DFF_XH16_0, PTV_DFF_XH16_1, PTV_DFF_XG0, PTV_DFF_XG1,
   PTV_DFF_WAIT_EVENT, PTV_DFF_RECORD_EVENT,   /* hipEvent_t or NULL: the persistent-launch turn around the cluster-mode note loops */
-  PTV_DFF_SAMPLE,           /* NULL, or the sampling block of a sampled decode (32 bytes on the device, "Sampled decode" below): D_INFERENCE only,
+  PTV_DFF_SAMPLE,           /* NULL, or the sampling block of a sampled decode (32 bytes on the device, 48 with D_SAMPLE_TRUNC; "Sampled decode" above): D_INFERENCE only,
                              * anything else is PTV_ERR_ARG before the first launch */
   PTV_DFF_COUNT
 };
@@ -990,6 +1009,7 @@ enum PtvDffDim {
   PTV_DFF_D_RESUM_TRAIN,    /* the `train` word of ptv_free_resummarize */
   PTV_DFF_D_TOK0_LDS,       /* row stride of TOK0_SRC (0 = one row for all) */
   PTV_DFF_D_W_IH_T_BF16, PTV_DFF_D_W_HH_T_BF16,
+  PTV_DFF_D_SAMPLE_TRUNC,   /* != 0: PTV_DFF_SAMPLE is the 48-byte block of a truncated sampled decode (top_k / min_p); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
   PTV_DFF_D_COUNT
 };
 int ptv_decoder_free_fwd(const void* const* t, const long* d, const void* const* wl, const void* const* io, const void* const* wr,

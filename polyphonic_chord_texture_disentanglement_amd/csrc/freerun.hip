@@ -243,6 +243,9 @@ template <int N> __device__ __forceinline__ void argmax_ror(float& best, int& bi
 // hold no exposed L2 round trip (RES = 0 had 8 + 1 + 1 of them per note step on wave 0).  Same products, same k order: bit-identical.
 // SAMP = 1: the decisions are draws from softmax(logits / T) -- Gumbel noise keyed by (seed, draw, GLOBAL sample, t, n) is added to the values
 // the argmax reduces (philox.hpp); the logits written out stay the plain ones.  Every member of a cluster draws the same noise for a row.
+// SAMP = 2: truncated sampling (top_k / min_p) -- the draw runs over the classes whose logit reaches pitch_keep_threshold() of the row
+// (philox.hpp: ONE function for every decision site).  Cluster mode: every member runs that function on the same logits (each computed the
+// whole head redundantly, same products, same order) with the same block, so all members reach the same decision; nobody is told it.
 template <int RES, int NUK = 2, int SAMP = 0>                    // NUK = 1: the eight-member cluster's kernel (one unit tile per wave and note step)
 __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
   __shared__ __attribute__((aligned(16))) bf16x8 wp8[RES ? 16 * 4 * 2 : 1];   // pitch-head tile 8, rows 128 / 129 only: [kb][quad][row]
@@ -339,6 +342,9 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
   float4 ew0 = make_float4(0.f, 0.f, 0.f, 0.f), ew1 = ew0;      // RES: embedding row of the decision, requested in P3
   SampleBlock sb{};
   if constexpr (SAMP) sb = *a.samp;
+  Trunc tr{};                                                   // SAMP = 2: a.samp is the 48-byte block, these its last words
+  if constexpr (SAMP == 2) { const SampleBlockT* q = reinterpret_cast<const SampleBlockT*>(a.samp); tr.top_k = q->top_k; tr.ln_min_p = q->ln_min_p; }
+  (void)tr;
   // timing experiments (dbg_out): 100-MHz ticks wave 0 spends per phase, summed over the 15 note steps -> dbg_out[3 * grid + 8 * block + i],
   // i = 0 cell (products + epilogue), 1 barrier + state exchange, 2 pitch head, 3 argmax + dur_hid, 4 duration GRU, 5 token embedding
   long tph[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;
@@ -574,7 +580,21 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
 #pragma unroll
         for (int k = 0; k < 9; k++) pv[k] = pit[row][j + 16 * k];              // (columns 130..143 of the row exist and hold zeros)
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (SAMP) {                                                  // the reduction sees logit + T * gumbel
+        if constexpr (SAMP == 2) {                                             // ... over the classes that reach the row's threshold
+          float tv[9];
+#pragma unroll
+          for (int k = 0; k < 9; k++) tv[k] = j + 16 * k < FNP ? pv[k] : -INFINITY;
+          const float thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);   // (the noise is drawn after the select: nine registers less across it)
+          float gum[9];
+          pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
+#pragma unroll
+          for (int k = 0; k < 9; k++) {
+            const int c = j + 16 * k;
+            const float x = perturbed(pv[k], sb.t_pitch, gum[k]);
+            const bool take = c < FNP && pv[k] >= thr && x > best;
+            best = take ? x : best; bi = take ? c : bi;
+          }
+        } else if constexpr (SAMP) {                                           // the reduction sees logit + T * gumbel
           float gum[9];
           pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
 #pragma unroll
@@ -598,6 +618,13 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           for (int k = 0; k < 9; k++) if (j + 16 * k < FNP) a.pitch[pr * a.ld_pitch + j + 16 * k] = pv[k];
         }
       } else {
+      float thr = -INFINITY;
+      if constexpr (SAMP == 2) {
+        float tv[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) tv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
+        thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
+      }
       float gum[SAMP ? 9 : 1];
       if constexpr (SAMP) pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
 #pragma unroll
@@ -608,7 +635,8 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           if (ok) a.pitch[pr * a.ld_pitch + c] = v;
           float x = v;
           if constexpr (SAMP) x = perturbed(v, sb.t_pitch, gum[k]);
-          if (x > best) { best = x; bi = c; }
+          if constexpr (SAMP == 2) { if (v >= thr && x > best) { best = x; bi = c; } }
+          else if (x > best) { best = x; bi = c; }
         }
       }
 #pragma unroll
@@ -960,6 +988,9 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
   const long wrowE = (long)t * B + rE, wrowC = (long)t * B + rC;   // row in the [R]-row step-major matrices
   SampleBlock sb{};
   if constexpr (SAMP) sb = *a.samp;
+  Trunc tr{};                                                   // SAMP = 2: a.samp is the 48-byte block, these its last words
+  if constexpr (SAMP == 2) { const SampleBlockT* q = reinterpret_cast<const SampleBlockT*>(a.samp); tr.top_k = q->top_k; tr.ln_min_p = q->ln_min_p; }
+  (void)tr;
 
   // ---- one-time loads: duration GRU weights / tables -> LDS, initial state and first token -> LDS
   for (int i = tid0; i < 12 * 2 * 64; i += 512) wdl[i] = a.wdur[i];
@@ -1147,6 +1178,13 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       float best = -INFINITY; int bi = 0x7fffffff;
       const long pr = (long)n * R + (long)t * B + min(r0 + row, B - 1);
       const bool ok = r0 + row < B;
+      float thr = -INFINITY;
+      if constexpr (SAMP == 2) {                                 // (all 256 head threads are here: whole DPP rows)
+        float tv[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) tv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
+        thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
+      }
       float gum[SAMP ? 9 : 1];
       if constexpr (SAMP) pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
 #pragma unroll
@@ -1157,7 +1195,8 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
           if (ok) a.pitch[pr * a.ld_pitch + c] = v;
           float x = v;
           if constexpr (SAMP) x = perturbed(v, sb.t_pitch, gum[k]);
-          if (x > best) { best = x; bi = c; }
+          if constexpr (SAMP == 2) { if (v >= thr && x > best) { best = x; bi = c; } }
+          else if (x > best) { best = x; bi = c; }
         }
       }
 #pragma unroll
@@ -1523,6 +1562,7 @@ extern "C" int ptv_pack_mfma_b(const float* W, long ld, int N, int K, void* out,
 
 // w[16]: wg_h, wg_t, wp, wd_h, wd_p, wdur (packed bf16), b_hh_n, b_p, b_dh, b_hh_d, tab0, tab, w_out, b_out, w_embT, b_emb
 // train bit 23: io has a 22nd entry, the sampling block (inference only); without the bit io[21] is never read
+// train bit 24 (with bit 23): io[21] is the 48-byte block of a truncated sampled decode (top_k / min_p; philox.hpp SampleBlockT)
 // io[21]: gc, emb, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16, dbg words, h0gc,
 //         xch, cnt (cluster mode, train bits 18-20 = S in {2, 4}: S workgroups per 16-sample panel, ptvae_hip.h)
 extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitch, int B, int t, unsigned coin_mask, int train,
@@ -1532,8 +1572,9 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   if ((!io[0] && !io[18]) || !io[2] || !io[4] || !io[7] || !io[8] || !io[9] || !io[10] || !io[11] || !io[12]) return PTV_ERR_ARG;
   if ((train & 3) == 1 && (!io[3] || !io[5] || !io[6])) return PTV_ERR_ARG;
   if (coin_mask && !io[1]) return PTV_ERR_ARG;
-  const bool samp = (train & 0x800000) != 0;
+  const bool samp = (train & 0x800000) != 0, trunc = (train & 0x1000000) != 0;
   if (samp && ((train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG;     // sampling is inference only
+  if (trunc && (!samp || (train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG;   // truncation belongs to a sampled decode (io[21]: the 48-byte block)
   NoteLoopArgs a{};
   a.samp = samp ? (const SampleBlock*)io[21] : nullptr;
   a.wg_h = (const bf16x8*)w[0]; a.wg_t = (const bf16x8*)w[1]; a.wp = (const bf16x8*)w[2]; a.wd_h = (const bf16x8*)w[3];
@@ -1574,7 +1615,12 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   const int pi = prof::want(7, B, FHN) ? prof::begin((hipStream_t)stream) : -1;
   if (!split) {
     const dim3 grid(a.S > 1 ? (panels + 7) / 8 * 8 * a.S : panels);
-    if (samp) {
+    if (trunc) {
+      if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
+      else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL((note_loop_kernel<1, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    }
+    else if (samp) {
       if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
       else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
       else hipLaunchKernelGGL((note_loop_kernel<1, 2, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -1583,6 +1629,7 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
     else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);   // bit 21: head weights streamed (timing comparisons)
     else hipLaunchKernelGGL((note_loop_kernel<1, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
   }
+  else if (trunc) hipLaunchKernelGGL((note_loop2_kernel<2>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
   else if (samp) hipLaunchKernelGGL((note_loop2_kernel<1>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL((note_loop2_kernel<0>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
   if (pi >= 0) prof::end(pi, (hipStream_t)stream, 15.0 * B * (2.0 * 3 * FHN * (FHN + 128) + 2.0 * 130 * FHN + 2.0 * 64 * (FHN + 130) + 5 * 2.0 * 3 * 64 * 64 + 2.0 * 128 * 135));

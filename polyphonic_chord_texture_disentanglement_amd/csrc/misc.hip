@@ -138,6 +138,7 @@ __global__ void clip_adam_kernel(float* __restrict__ p, const float* __restrict_
 // One wave per row.
 // ---------------------------------------------------------------------------------------------
 template <int SAMP>                    // SAMP = 1: row r is sample r at (t, note step n - 1), the pitch decision a draw (philox.hpp)
+                                       // SAMP = 2: ... over the classes pitch_keep_threshold() keeps; `samp` is then the 48-byte block
 __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch, const int* __restrict__ dur_idx, long dur_stride,
                                   const float* __restrict__ W, const float* __restrict__ bias, int E,
                                   float* __restrict__ pred, long ld_pred, long* __restrict__ xhat, long xhat_stride,
@@ -147,10 +148,28 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
   for (int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < M; r += gridDim.x * (blockDim.x >> 6)) {
     const float* lr = pitch + (long)r * ld_pitch;
     float best = -INFINITY; int bi = 0x7fffffff;
+    if constexpr (SAMP == 2) {                                     // truncated: the draw over the classes that reach the row's threshold
+      const SampleBlockT* q = reinterpret_cast<const SampleBlockT*>(samp);
+      const SampleBlock sb = q->s;
+      const Trunc tr{q->top_k, q->ln_min_p};
+      float tv[3];
+#pragma unroll
+      for (int i = 0; i < 3; i++) tv[i] = lane + 64 * i < 130 ? lr[lane + 64 * i] : -INFINITY;
+      const float thr = pitch_keep_threshold<3, 64>(tr, sb.t_pitch, tv);      // (the whole wave is here: r is uniform over it)
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const int c = lane + 64 * i;
+        if (c < 130 && tv[i] >= thr) {
+          const float x = perturbed(tv[i], sb.t_pitch, pitch_gumbel1(sb, sb.sample_offset + r, t, n - 1, c));
+          if (x > best) { best = x; bi = c; }
+        }
+      }
+    } else {
     for (int c = lane; c < 130; c += 64) {
       float v = lr[c];
       if constexpr (SAMP) { const SampleBlock sb = *samp; v = perturbed(v, sb.t_pitch, pitch_gumbel1(sb, sb.sample_offset + r, t, n - 1, c)); }
       if (v > best) { best = v; bi = c; }
+    }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -342,6 +361,19 @@ extern "C" int ptv_note_token_sample(const float* pitch, long ld_pitch, const in
   int nb = (M + 3) / 4; if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(note_token_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
                      pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M, (const SampleBlock*)sample, t);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// ... with the 48-byte block of a truncated sampled decode (top_k / min_p)
+extern "C" int ptv_note_token_sample_trunc(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
+                                           float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
+                                           const int* force_pitch, int M, const void* sample48, int t, void* stream) {
+  if (!pitch || !dur_idx || !W || !bias || !pred || !xhat || !plen || M <= 0 || E <= 0) return PTV_ERR_ARG;
+  if (!sample48 || t < 0 || t >= 32 || n < 1 || n > 15) return PTV_ERR_ARG;
+  int nb = (M + 3) / 4; if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(note_token_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
+                     pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M, (const SampleBlock*)sample48, t);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

@@ -88,4 +88,82 @@ __device__ __forceinline__ void dur_gumbel2(const SampleBlock& s, long long g, i
 // the decision rules, shared by every kernel: the first maximal index of logit + T * g (T = 0: logit + 0 = the plain argmax, ties included)
 __device__ __forceinline__ float perturbed(float logit, float T, float g) { return logit + T * g; }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Truncated sampling (DESIGN.md "Sampled decode": the select): the pitch draw over the classes whose logit reaches a per-row threshold.
+// The extended block is the 32 bytes above, unchanged, followed by 16 more: 48 bytes.
+//   top_k:    keep the classes >= the k-th largest logit of the row (counted with multiplicity; ties with it are all kept); 0 = off,
+//             k >= 130 keeps everything
+//   ln_min_p: keep the classes >= m + T_pitch * ln(min_p), m the row's largest logit (p_c >= min_p * p_max under softmax(logits / T));
+//             any value > 0 = off (the host writes LN_MIN_P_OFF; ln(min_p) <= 0 for every min_p in (0, 1]) -- the test is on the
+//             word itself, no infinity is ever multiplied by T
+// Both: the larger threshold.  The row's best class passes either rule, so the kept set is never empty.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct SampleBlockT {
+  SampleBlock s;
+  int top_k;
+  float ln_min_p;
+  unsigned reserved[2];
+};
+static_assert(sizeof(SampleBlock) == 32 && sizeof(SampleBlockT) == 48, "sampling blocks: 32 / 48 bytes (include/ptvae_hip.h)");
+constexpr float LN_MIN_P_OFF = 1.f;
+struct Trunc { int top_k; float ln_min_p; };                       // what a kernel keeps of the extension
+
+// order-preserving integer key of a float (-0.0 is +0.0: they compare equal) and its inverse
+__device__ __forceinline__ unsigned order_key(float v) {
+  unsigned u = __builtin_bit_cast(unsigned, v);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float order_key_value(unsigned k) { return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// reductions over the W lanes that hold a row, every lane ends with the result.  W = 16: a DPP row (the note loops: lane j of the 16 owns
+// columns j + 16 i), the rotations of the argmax; W = 64: the wave (the step loop: lane l owns columns l + 64 i), two more exchanges
+template <int N> __device__ __forceinline__ int dpp_row_ror(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x120 + N, 0xf, 0xf, false); }
+template <int W> __device__ __forceinline__ int row_sum(int x) {
+  x += dpp_row_ror<8>(x); x += dpp_row_ror<4>(x); x += dpp_row_ror<2>(x); x += dpp_row_ror<1>(x);
+  if constexpr (W == 64) { x += __shfl_xor(x, 16, 64); x += __shfl_xor(x, 32, 64); }
+  return x;
+}
+template <int W> __device__ __forceinline__ float row_max(float x) {
+  x = fmaxf(x, __builtin_bit_cast(float, dpp_row_ror<8>(__builtin_bit_cast(int, x))));
+  x = fmaxf(x, __builtin_bit_cast(float, dpp_row_ror<4>(__builtin_bit_cast(int, x))));
+  x = fmaxf(x, __builtin_bit_cast(float, dpp_row_ror<2>(__builtin_bit_cast(int, x))));
+  x = fmaxf(x, __builtin_bit_cast(float, dpp_row_ror<1>(__builtin_bit_cast(int, x))));
+  if constexpr (W == 64) { x = fmaxf(x, __shfl_xor(x, 16, 64)); x = fmaxf(x, __shfl_xor(x, 32, 64)); }
+  return x;
+}
+
+// THE keep rule, shared by every decision site (and ptv_debug_pitch_keep): class c of the row is kept iff logit[c] >= the value returned.
+// v: the NV logits this lane owns, -INFINITY where the column does not exist; all W lanes of the row call it together (tr and T are
+// uniform over the block: both tests below are scalar branches).
+// top_k: a 32-round bitwise select of the k-th largest order key -- a round counts the row's keys >= the candidate (NV compares per
+// lane, one W-lane sum) and keeps the bit if there are at least k; fixed cost, no LDS, independent of the lane layout.  The padding
+// keys are below every real one and k < 130 real values exist, so the selected key is a real logit's.
+template <int NV, int W>
+__device__ __forceinline__ float pitch_keep_threshold(const Trunc tr, float T, const float (&v)[NV]) {
+  float thr = -INFINITY;
+  if (tr.top_k > 0 && tr.top_k < 130) {
+    unsigned key[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) key[i] = order_key(v[i]);
+    unsigned sel = 0u;
+#pragma unroll 1
+    for (int b = 31; b >= 0; b--) {
+      const unsigned cand = sel | (1u << b);
+      int cnt = 0;
+#pragma unroll
+      for (int i = 0; i < NV; i++) cnt += key[i] >= cand ? 1 : 0;
+      if (row_sum<W>(cnt) >= tr.top_k) sel = cand;
+    }
+    thr = order_key_value(sel);
+  }
+  if (tr.ln_min_p <= 0.f) {
+    float m = v[0];
+#pragma unroll
+    for (int i = 1; i < NV; i++) m = fmaxf(m, v[i]);
+    thr = fmaxf(thr, row_max<W>(m) + T * tr.ln_min_p);
+  }
+  return thr + 0.f;                                                // (a zero threshold is +0.0)
+}
+
 }  // namespace ptv

@@ -55,7 +55,47 @@ __global__ void sample_noise_kernel(const SampleBlock* __restrict__ blk, long ro
   }
 }
 
+// test aid: pitch_keep_threshold() on caller-supplied rows in the two lane layouts of the decision sites.  LAYOUT 0: 16 lanes per row, lane j
+// owns columns j + 16 i (the note loops); LAYOUT 1: a wave per row, lane l owns columns l + 64 i (the step loop).  Every lane of a wave
+// stays in the loop (rows past the end are clamped and store nothing): the row reductions want whole rows of lanes.
+template <int LAYOUT>
+__global__ void pitch_keep_kernel(const SampleBlockT* __restrict__ blk, const float* __restrict__ logits, long rows,
+                                  unsigned char* __restrict__ keep_out, float* __restrict__ thr_out) {
+  constexpr int W = LAYOUT ? 64 : 16, NV = LAYOUT ? 3 : 9;
+  const Trunc tr{blk->top_k, blk->ln_min_p};
+  const float T = blk->s.t_pitch;
+  const long per = blockDim.x / W, total = (rows + per - 1) / per * per;
+  for (long r_ = (long)blockIdx.x * per + threadIdx.x / W; r_ < total; r_ += (long)gridDim.x * per) {
+    const bool ok = r_ < rows;
+    const long r = ok ? r_ : rows - 1;
+    const int j = threadIdx.x % W;
+    float v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) v[i] = j + W * i < 130 ? logits[r * 130 + j + W * i] : -INFINITY;
+    const float thr = pitch_keep_threshold<NV, W>(tr, T, v);
+    if (ok) {
+#pragma unroll
+      for (int i = 0; i < NV; i++) if (j + W * i < 130) keep_out[r * 130 + j + W * i] = v[i] >= thr ? 1 : 0;
+      if (j == 0) thr_out[r] = thr;
+    }
+  }
+}
+
 }  // namespace ptv
+
+extern "C" int ptv_debug_pitch_keep(const void* block48, const float* logits, long rows, int layout, unsigned char* keep_out, float* thr_out,
+                                    void* stream) {
+  if (!block48 || !logits || !keep_out || !thr_out || rows <= 0 || (layout != 0 && layout != 1)) return PTV_ERR_ARG;
+  long nb = (rows + 3) / 4; if (nb > 4096) nb = 4096;
+  if (layout == 0)
+    hipLaunchKernelGGL(ptv::pitch_keep_kernel<0>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (const ptv::SampleBlockT*)block48, logits, rows,
+                       keep_out, thr_out);
+  else
+    hipLaunchKernelGGL(ptv::pitch_keep_kernel<1>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (const ptv::SampleBlockT*)block48, logits, rows,
+                       keep_out, thr_out);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
 
 extern "C" int ptv_philox_normal(float* out, long rows, int Z, unsigned long long seed, unsigned long long stream_id, long row_offset,
                                  void* stream) {

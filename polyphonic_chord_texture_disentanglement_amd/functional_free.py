@@ -89,11 +89,16 @@ NOTE_LOOP_CLUSTER = None if os.environ.get('PTV_NOTE_CLUSTER') is None else int(
 # kernels read when they run -- a captured graph holds its address, so seed / draw / temperatures change without a new capture.
 # ---------------------------------------------------------------------------------------------
 SAMPLE_BIT = 0x800000           # ptv_free_note_loop's `train` word: io[21] is the sampling block
+# truncated sampling (top_k / min_p bound the support of the PITCH draw): the block grows to 48 bytes -- the 32 above, then {int32 top_k
+# (0 = off), float ln(min_p) (LN_MIN_P_OFF = off), 8 reserved bytes} -- and the word count of the tensor (4 or 6) picks the instantiation
+TRUNC_BIT = 0x1000000           # ... io[21] is the 48-byte block (only together with SAMPLE_BIT)
+LN_MIN_P_OFF = 1.0              # any ln_min_p > 0 switches the min_p rule off (ln(min_p) <= 0 for every min_p in (0, 1])
 
 
-def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, draw=0):
-    """(T_pitch, T_dur, sample_offset, seed, draw) validated -- ValueError before anything touches a GPU"""
+def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, draw=0, *, top_k=None, min_p=None):
+    """(T_pitch, T_dur, sample_offset, seed, draw) validated -- ValueError before anything touches a GPU (top_k / min_p: check_truncation)"""
     import math
+    check_truncation(top_k, min_p)
     tp = 0.0 if temperature is None else temperature
     td = tp if dur_temperature is None else dur_temperature
     for name, v in (('temperature', tp), ('dur_temperature', td)):
@@ -105,23 +110,49 @@ def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, d
     return float(tp), float(td), sample_offset, seed, draw
 
 
-def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0):
-    """the block as four int64 words (host list)"""
+def check_truncation(top_k=None, min_p=None):
+    """(top_k word, ln_min_p) validated, or None when neither rule is given -- ValueError before anything touches a GPU.
+    top_k: an integer >= 1 (stored clipped to 130: k >= 130 keeps every class); min_p: a finite float in [0, 1], 0 = off;
+    ln(min_p) is taken in float64 (the block stores it rounded to fp32)"""
+    import math
+    if top_k is None and min_p is None:
+        return None
+    k = 0
+    if top_k is not None:
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1:
+            raise ValueError('top_k must be an integer >= 1, got %r' % (top_k,))
+        k = min(top_k, 130)
+    ln = LN_MIN_P_OFF
+    if min_p is not None:
+        if isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or math.isnan(min_p) or math.isinf(min_p) or not 0 <= min_p <= 1:
+            raise ValueError('min_p must be a finite float in [0, 1], got %r' % (min_p,))
+        if min_p > 0:
+            ln = math.log(float(min_p))
+    return k, ln
+
+
+def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None):
+    """the block as four int64 words (host list); six with top_k / min_p"""
     import struct
     tp, td, off, seed, draw = check_sampling(temperature, dur_temperature, sample_offset, seed, draw)
-    return [seed - (1 << 64) if seed >= (1 << 63) else seed, draw, off, struct.unpack('<q', struct.pack('<ff', tp, td))[0]]
+    words = [seed - (1 << 64) if seed >= (1 << 63) else seed, draw, off, struct.unpack('<q', struct.pack('<ff', tp, td))[0]]
+    tr = check_truncation(top_k, min_p)
+    if tr is not None:
+        words += [struct.unpack('<q', struct.pack('<if', *tr))[0], 0]
+    return words
 
 
-def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0):
-    """the device block of a sampled decode: PtvaeDecoder.decoder(..., sampling=block)"""
-    words = sampling_words(temperature, dur_temperature, seed, draw, sample_offset)
+def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None):
+    """the device block of a sampled decode: PtvaeDecoder.decoder(..., sampling=block).  Four int64 words; six with top_k / min_p
+    (truncated sampling, INTEGRATION.md "Sampled decode")"""
+    words = sampling_words(temperature, dur_temperature, seed, draw, sample_offset, top_k=top_k, min_p=min_p)
     if torch.device(device).type != 'cuda':
         raise RuntimeError('a sampled decode runs on the GPU: the sampling block lives in device memory (got device %s)' % (device,))
     return torch.tensor(words, dtype=torch.int64, device=device)
 
 
 def _check_block(sampling, dev):
-    if not (torch.is_tensor(sampling) and sampling.dtype == torch.int64 and sampling.numel() == 4 and sampling.is_contiguous()
+    if not (torch.is_tensor(sampling) and sampling.dtype == torch.int64 and sampling.numel() in (4, 6) and sampling.is_contiguous()
             and sampling.device == dev):
         raise ValueError('sampling must be a block made by functional_free.sampling_block() on the device of z')
     return sampling
@@ -240,7 +271,8 @@ def _decoder_free_fwd_composite(P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of,
     dvals = _DFF.dims({'B': B, 'ZS': dims['Zs'], 'ZI': dims['Zi'], 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'E': E, 'NP': dims['NP'],
                        'LDP': dims['ldp'], 'TRAIN': dims['train'], 'REPLAY': dims['replay'], 'INFERENCE': dims['inference'],
                        'LOOP_FLAGS': dims['loop_flags'], 'CLUSTER': dims['cluster'], 'RESUM_TRAIN': dims['resum_train'], 'TOK0_LDS': tok0_lds,
-                       'W_IH_T_BF16': w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': w_hh_t.dtype == torch.bfloat16})
+                       'W_IH_T_BF16': w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': w_hh_t.dtype == torch.bfloat16,
+                       'SAMPLE_TRUNC': dims.get('sample_trunc', 0)})
     coin_notes, coin_time = coins
     masks = (ctypes.c_uint * 32)()
     tc = (ctypes.c_ubyte * 31)()
@@ -311,7 +343,8 @@ class DecoderStepFn(torch.autograd.Function):
             if not inference or any(any(r) for r in coins[0]) or any(coins[1]):
                 raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
             _check_block(sampling, dev)
-        samp_bit = SAMPLE_BIT if sampling is not None else 0
+        samp_bit = 0 if sampling is None else (SAMPLE_BIT | (TRUNC_BIT if sampling.numel() == 6 else 0))
+        trunc = bool(samp_bit & TRUNC_BIT)
         z = z.contiguous()
         B = z.shape[0]
         R = 32 * B
@@ -433,7 +466,7 @@ class DecoderStepFn(torch.autograd.Function):
                      xch, xcnt]),
                 ior=F_._parr([PRED, plen, XH[0], XH[1], XG[0], XG[1], None]) if need_resum else None,
                 dims=dict(B=B, Zs=z.shape[1], Zi=Zi, He=He, Ht=Ht, Hn=Hn, Hd=Hd, E=E, NP=NP, ldp=pitch.stride(0), train=int(train), replay=int(bool(replay)),
-                          inference=int(bool(inference)), cluster=int(cluster and not capturing),
+                          inference=int(bool(inference)), cluster=int(cluster and not capturing), sample_trunc=int(trunc),
                           loop_flags=(2 if replay else int(train)) | (0 if NOTE_LOOP_SPLIT is None else (0x20000 if NOTE_LOOP_SPLIT else 0x10000))
                           | cluster_bits(cluster), resum_train=int(train and not replay)),
                 tens=dict(NS=NS, NS16=NS16, Z_IN=z_in, ZG=zg, TOKS=TOKS, GATES_T=gates_t, TOK=TOK, PRED=PRED, PITCH=pitch, HN=HN, HN16=HN16,
@@ -511,8 +544,8 @@ class DecoderStepFn(torch.autograd.Function):
                              ptr(P['dur_out_linear.weight']),
                              ptr(P['dur_out_linear.bias']), ptr(dur2[pr][:, 2 * d:]), 10, ptr(idx[d][pr]),
                              ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp + ((d,) if smp else ())), st)
-                call('ptv_note_token' if sampling is None else 'ptv_note_token_sample', ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(w_emb),
-                     ptr(b_emb), E,
+                call('ptv_note_token' if sampling is None else ('ptv_note_token_sample_trunc' if trunc else 'ptv_note_token_sample'),
+                     ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(w_emb), ptr(b_emb), E,
                      ptr(PRED[n + 1][rows]), E, ptr(xhat[0, t, n + 1]), 32 * 16 * 6, ptr(plen[rows]), n + 1, int(n == 14),
                      ptr(force_pitch[n][rows]) if force_pitch is not None else None, B, *(smp[:2] if smp else ()), st)
                 if n < 14:

@@ -354,26 +354,32 @@ class DisentangleVAE(PytorchModel):
     # independent of how a batch is cut.  seed / sample_offset default to use_philox()'s, else 7 / 0; draw defaults to a per-model counter
     # that advances once per sampled decode.  temperature=None (default): the argmax decode, unchanged.  The same keywords pass through
     # decode_to_inputs, reencode, inference, swap, posterior_sample, prior_sample and interp (sample index = row of the decoded batch).
+    # Truncated sampling bounds the support of the PITCH draw (the duration bits keep dur_temperature, the chord decoder its argmax):
+    # top_k (int >= 1) keeps the classes >= the k-th largest logit of the row, ties with it included; min_p (float in [0, 1], 0 / None =
+    # off) keeps the classes with p >= min_p * p_max under softmax(logits / temperature); both: a class must pass both.  The draw is then
+    # exact from the renormalised truncated softmax, with the same noise words.  Nucleus (top-p) truncation is not built.
     @staticmethod
-    def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None):
+    def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None):
         """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode.  No side effect, no GPU"""
         if temperature is None and dur_temperature is None:
             if seed is not None or draw is not None or sample_offset is not None:
                 raise ValueError('seed / draw / sample_offset belong to a sampled decode: give a temperature')
+            if top_k is not None or min_p is not None:
+                raise ValueError('top_k / min_p belong to a sampled decode: give a temperature')
             return False
         from .functional_free import check_sampling
         check_sampling(temperature, dur_temperature, 0 if sample_offset is None else sample_offset, 0 if seed is None else seed,
-                       0 if draw is None else draw)
+                       0 if draw is None else draw, top_k=top_k, min_p=min_p)
         return True
 
-    def _sampling_words(self, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None):
+    def _sampling_words(self, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None):
         """None (argmax decode) or the validated sampling block as host words -- ValueError for a bad value before anything is launched"""
-        if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset):
+        if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset, top_k, min_p):
             return None
         from .functional_free import sampling_words
         ph = self._philox or (7, 0)
         words = sampling_words(temperature, dur_temperature, ph[0] if seed is None else seed, self._sample_draws if draw is None else draw,
-                               ph[1] if sample_offset is None else sample_offset)
+                               ph[1] if sample_offset is None else sample_offset, top_k=top_k, min_p=min_p)
         if draw is None:
             self._sample_draws += 1
         return words
@@ -389,25 +395,27 @@ class DisentangleVAE(PytorchModel):
         block = None if words is None else torch.tensor(words, dtype=torch.int64, device=dec_z.device)
         return self.decoder(dec_z, True, None, None, 0., 0., sampling=block)
 
-    def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None):
+    def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None,
+                         top_k=None, min_p=None):
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
             self._decode(z_chd, z_rhy, dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw,
-                                            sample_offset=sample_offset))
+                                            sample_offset=sample_offset, top_k=top_k, min_p=min_p))
             est_x = self.decoder.last_xhat[:, :, 1:, :].cpu().numpy()
         return est_x
 
     # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
-                         sample_offset=None):
+                         sample_offset=None, top_k=None, min_p=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
         inference_decode's (the chord decoder keeps its argmax)."""
         from .ptvae import _require_cuda
-        sampling = dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset)
+        sampling = dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset,
+                        top_k=top_k, min_p=min_p)
         self._check_sampling(**sampling)                                # (bad values are a ValueError whatever device the inputs are on)
         _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')

@@ -272,6 +272,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         self.last_xhat = None              # predicted grid [B,32,16,6] int64 of the last step-loop decode
         self.use_graph = False             # replay inference decodes from a captured hipGraph
         self._graphs = {}
+        self._graph_stream = None          # warm-up and capture stream of _graph_decode (one per decoder: the library keeps a workspace per stream)
         self.graph_captures = 0            # inference decodes captured so far (a sampled decode's seed / draw / temperatures need no new one)
         self._train_graphs = {}
         self._summary = None
@@ -287,24 +288,31 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         order and arguments depend only on (B, precision) -- capture once, then one graph launch per call.
         The graph holds raw parameter pointers, so it is re-captured if the parameter storage moves.
         A sampled decode is a graph of its own (other kernels); its sampling block is a static tensor refreshed before every
-        replay, so the key holds neither seed nor draw nor temperatures."""
+        replay, so the key holds neither seed nor draw nor temperatures.  A truncated sampled decode (a 6-word block: top_k / min_p)
+        is a third kind: the key gains that one bit, the values of top_k / min_p live in the block like seed and draw -- one capture
+        serves them all."""
         ps = self._params_free()
-        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), sampling is not None)
+        kind = 0 if sampling is None else (2 if sampling.numel() == 6 else 1)
+        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind)
         ent = self._graphs.get(key)
         if ent is None:
             static_z = z.detach().clone()
             if sampling is not None:
                 ps = ps + [sampling.clone()]
             cur = torch.cuda.current_stream()
-            s = torch.cuda.Stream(device=z.device)
+            # warm-up and capture share ONE stream (as graph_step.py): the library's split-K workspaces are per stream and cannot be
+            # allocated inside a capture -- captured on another stream the small products fell back to fp32 atomics, and the replayed
+            # logits differed from the eager ones in the last bits from replay to replay (which a truncation threshold turns into
+            # other decisions)
+            s = self._graph_stream = self._graph_stream or torch.cuda.Stream(device=z.device)
             s.wait_stream(cur)
             with torch.cuda.stream(s):                         # warm-up outside capture (lazy inits, allocator)
                 FF_.DecoderStepFn.apply(static_z, None, None, coins, True, None, self._prec, *ps)
             cur.wait_stream(s)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with torch.cuda.graph(g, stream=s):
                 outs = FF_.DecoderStepFn.apply(static_z, None, None, coins, True, None, self._prec, *ps)
-            for k in [k for k in self._graphs if k[-1] == key[-1]]:         # one graph per kind (argmax, sampled) is kept
+            for k in [k for k in self._graphs if k[-1] == key[-1]]:         # one graph per kind (argmax, sampled, truncated) is kept
                 del self._graphs[k]
             self.graph_captures += 1
             ent = self._graphs[key] = (g, static_z, outs, ps[-1] if sampling is not None else None)
@@ -358,7 +366,8 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
 
     def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None):
         """sampling: None (argmax decisions) or a block of functional_free.sampling_block() -- the decisions of the free-running decode
-        are then seeded draws from softmax(logits / T); inference only (ValueError otherwise, before any launch)"""
+        are then seeded draws from softmax(logits / T), with top_k / min_p in the block over the truncated support of the pitch row;
+        inference only (ValueError otherwise, before any launch)"""
         if sampling is not None and (not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None):
             raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
         _require_cuda(z, 'PtvaeDecoder')

@@ -1,8 +1,11 @@
-"""The sampled free-running decode beside the argmax decode, same process, same batch (BASELINE configs[3]: batch 2048, the step loop
-replayed from a captured hipGraph): --rounds interleaved rounds of --reps decodes each, timed by events after a warm-up; every round uses
-another draw, none needs a new capture.  Prints one JSON line with both ranges and the cost of sampling.
+"""The sampled and the truncated-sampled free-running decode beside the argmax decode, same process, same batch (BASELINE configs[3]: batch
+2048, the step loop replayed from a captured hipGraph): --rounds interleaved rounds of --reps decodes each, timed by events after a warm-up;
+every round uses another draw, none needs a new capture.  Prints one JSON line with the three ranges, the cost of sampling and the cost of
+truncation (top_k / min_p: the 32-round select and the row maximum in the pitch phase of every note step).
 
-    python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--eager]
+    python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--top-k 8] [--min-p 0.9] [--eager]
+
+--top-k 0 and --min-p 0 switch the rule off; with both off the truncated decode is not timed.
 """
 import argparse
 import json
@@ -22,6 +25,8 @@ def main():
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--temperature', type=float, default=1.0)
+    ap.add_argument('--top-k', type=int, default=8, help='0 = off')
+    ap.add_argument('--min-p', type=float, default=0.9, help='0 = off')
     ap.add_argument('--eager', action='store_true', help='no graph replay')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the MI355X'
@@ -31,7 +36,11 @@ def main():
     m.eval()
     m.decoder.use_graph = not a.eager
     z = torch.randn(a.batch, 512, device=dev)
-    blocks = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)]
+    trunc = dict(top_k=a.top_k or None, min_p=a.min_p or None)
+    kinds = ['argmax', 'sampled'] + (['truncated'] if a.top_k or a.min_p else [])
+    blocks = {'argmax': [None] * (a.rounds + 1),
+              'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
+              'truncated': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **trunc) for d in range(a.rounds + 1)]}
 
     def run(block):
         with torch.no_grad():
@@ -46,22 +55,26 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.reps
 
-    for _ in range(2):                                       # warm-up: both graphs captured, allocator settled
-        run(None)
-        run(blocks[-1])
+    for _ in range(2):                                       # warm-up: every graph captured, allocator settled
+        for k in kinds:
+            run(blocks[k][-1])
     torch.cuda.synchronize()
     captures = m.decoder.graph_captures
-    ms = {'argmax': [], 'sampled': []}
-    for r in range(a.rounds):                                # interleaved: drift of the box hits both alike
-        ms['argmax'].append(timed(None))
-        ms['sampled'].append(timed(blocks[r]))
+    ms = {k: [] for k in kinds}
+    for r in range(a.rounds):                                # interleaved: drift of the box hits all alike
+        for k in kinds:
+            ms[k].append(timed(blocks[k][r]))
     assert m.decoder.graph_captures == captures              # a new draw is not a new capture
     rate = {k: [round(a.batch / (v * 1e-3), 1) for v in vs] for k, vs in ms.items()}
     best = {k: max(v) for k, v in rate.items()}
-    print(json.dumps({'what': 'free-running decode, argmax vs sampled decisions', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
-                      'temperature': a.temperature, 'ms_per_decode': {k: [round(x, 3) for x in v] for k, v in ms.items()},
-                      'samples_per_s': rate, 'sampled_over_argmax_best': round(best['sampled'] / best['argmax'], 4),
-                      'device': torch.cuda.get_device_name(0)}))
+    out = {'what': 'free-running decode: argmax, sampled and truncated-sampled decisions', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
+           'temperature': a.temperature, 'top_k': a.top_k, 'min_p': a.min_p, 'ms_per_decode': {k: [round(x, 3) for x in v] for k, v in ms.items()},
+           'samples_per_s': rate, 'sampled_over_argmax_best': round(best['sampled'] / best['argmax'], 4)}
+    if 'truncated' in kinds:
+        out['truncated_over_sampled_best'] = round(best['truncated'] / best['sampled'], 4)
+        out['truncated_over_argmax_best'] = round(best['truncated'] / best['argmax'], 4)
+    out['device'] = torch.cuda.get_device_name(0)
+    print(json.dumps(out))
 
 
 if __name__ == '__main__':
