@@ -923,18 +923,28 @@ int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitc
  *   ptv_note_token_sample / ptv_dur_out_token_sample / ptv_dur_gru_fwd_sample: ptv_note_token / ptv_dur_out_token / ptv_dur_gru_fwd with the
  *     block and the position of the rows: row r is sample sample_offset + r at time step t; note step n = 0..14 for the duration forms,
  *     the duration bit d for ptv_dur_out_token_sample; ptv_note_token_sample decides note step n - 1 (its n is the slot it fills, 1..15).
- * Truncated sampling (top_k / min_p) bounds the support of the PITCH draw; the duration bits keep T_dur as their only control.  The block
- * is then 48 bytes: the 32 above unchanged, followed by { int32 top_k, float ln_min_p, 8 reserved bytes (zero) }.
+ * Truncated sampling (top_k / min_p / top_p) bounds the support of the PITCH draw; the duration bits keep T_dur as their only control.  The
+ * block is then 48 bytes: the 32 above unchanged, followed by { int32 top_k, float ln_min_p, uint32 top_p_q24, 4 reserved bytes (zero) }.
  *   top_k >= 1: class c is kept iff logit[c] >= v_k, the k-th largest of the row's 130 logits counted with multiplicity -- classes tied
  *     with the k-th value are ALL kept (so more than k may survive), whatever their column; top_k >= 130 keeps every class; 0 = off.
  *   ln_min_p = ln(min_p) rounded from float64 to fp32, min_p in (0, 1]: class c is kept iff logit[c] >= m + T_pitch * ln_min_p in fp32
  *     (the product rounded, then the sum), m the row's largest logit: p_c >= min_p * p_max under softmax(logits / T_pitch).  Any value
  *     > 0 (write 1.0f) = off: the kernels test the word and never multiply an infinity by T.
- *   Both: a class must pass both.  All comparisons are fp32 comparisons of the emitted logits (-0.0 == +0.0); the best class passes
- *   either rule, so the kept set is never empty.  The decision is the first maximal index over the KEPT classes of logit + T_pitch * g with
+ *   top_p_q24 = round(top_p * 2^24) in [1, 2^24], top_p in (0, 1) (nucleus); 0 = off, which is what top_p = 1 is written as (the word was
+ *     reserved and zero before: every block written then keeps its meaning).  Under softmax(logits / T_pitch) of the UNTRUNCATED row, keep
+ *     the smallest set of best classes whose mass reaches top_p; classes tied with the last kept value are ALL kept (the tie rule of
+ *     top_k).  As a threshold: the largest value t with mass{c: logit[c] >= t} >= top_p * Z; class c is kept iff logit[c] >= t, i.e. iff
+ *     the mass of the classes strictly above it is < top_p * Z.  The masses are integers, so that every lane layout and every member of
+ *     a cluster forms the same sums: w_c = trunc(e * 2^20), e = the device's fast fp32 exponential (v_exp_f32 of x * log2(e)) of
+ *     x = (logit[c] - m) / T_pitch, the difference and the quotient each correctly rounded to fp32, m the row's largest logit (w = 2^20
+ *     there; a class whose w is 0 carries no mass); Z = sum of w_c; the test is mass * 2^24 >= Z * top_p_q24 in 64-bit integers.
+ *     T_pitch = 0: no nucleus rule (the decode is the argmax decode).
+ *   Several rules: a class must pass every one, each judged on the untruncated row -- the largest of the thresholds.  This is NOT the
+ *   sequential chain of other libraries (top_k first, then top_p on the renormalised survivors, ...).  All comparisons are fp32
+ *   comparisons of the emitted logits (-0.0 == +0.0); the best class passes every rule, so the kept set is never empty.
+ *   The decision is the first maximal index over the KEPT classes of logit + T_pitch * g with
  *   exactly the noise words above (a dropped class leaves its word unused, nothing is re-keyed): an exact draw from the renormalised
  *   truncated softmax, still a pure function of (seed, draw, global sample, t, n) and the row's logits.  T_pitch = 0 is the argmax.
- *   Not built: nucleus (top-p) truncation -- it needs the cumulative mass of the sorted row; min_p adapts to the row's sharpness instead.
  *   ptv_free_note_loop: bit 24 of train, together with bit 23, says io[21] is the 48-byte block; bit 24 without bit 23, with
  *     train & 3 != 0, a coin mask or a NULL block is PTV_ERR_ARG before any launch.
  *   ptv_note_token_sample_trunc: ptv_note_token_sample with the 48-byte block.
@@ -1009,7 +1019,7 @@ enum PtvDffDim {
   PTV_DFF_D_RESUM_TRAIN,    /* the `train` word of ptv_free_resummarize */
   PTV_DFF_D_TOK0_LDS,       /* row stride of TOK0_SRC (0 = one row for all) */
   PTV_DFF_D_W_IH_T_BF16, PTV_DFF_D_W_HH_T_BF16,
-  PTV_DFF_D_SAMPLE_TRUNC,   /* != 0: PTV_DFF_SAMPLE is the 48-byte block of a truncated sampled decode (top_k / min_p); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
+  PTV_DFF_D_SAMPLE_TRUNC,   /* != 0: PTV_DFF_SAMPLE is the 48-byte block of a truncated sampled decode (top_k / min_p / top_p); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
   PTV_DFF_D_COUNT
 };
 int ptv_decoder_free_fwd(const void* const* t, const long* d, const void* const* wl, const void* const* io, const void* const* wr,

@@ -45,9 +45,9 @@ int ptv_wgrad_batch_mode(int batched);
  * out_dur [rows, 5, 2] (duration bit d: class 0, class 1) */
 int ptv_debug_sample_noise(const void* block, long rows, int t, int n, float* out_pitch, float* out_dur, void* stream);
 
-/* test aid of truncated sampling (ptvae_hip.h "Sampled decode", top_k / min_p): the decoder's own keep-threshold function
+/* test aid of truncated sampling (ptvae_hip.h "Sampled decode", top_k / min_p / top_p): the decoder's own keep-threshold function
  * (csrc/philox.hpp pitch_keep_threshold) on caller-supplied rows, logits [rows, 130] fp32, under the 48-byte block (its T_pitch, top_k,
- * ln_min_p are read).  layout 0: 16 lanes per row, lane j owns columns j + 16 i (the note loops); layout 1: a wave per row, lane l owns
+ * ln_min_p, top_p_q24 are read).  layout 0: 16 lanes per row, lane j owns columns j + 16 i (the note loops); layout 1: a wave per row, lane l owns
  * columns l + 64 i (the step loop).  keep_out [rows, 130] uint8 = logit >= threshold, thr_out [rows] fp32 = the threshold (-inf: no rule) */
 int ptv_debug_pitch_keep(const void* block48, const float* logits, long rows, int layout, unsigned char* keep_out, float* thr_out, void* stream);
 

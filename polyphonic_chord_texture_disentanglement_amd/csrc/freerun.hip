@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
   SampleBlock sb{};
   if constexpr (SAMP) sb = *a.samp;
   Trunc tr{};                                                   // SAMP = 2: a.samp is the 48-byte block, these its last words
-  if constexpr (SAMP == 2) { const SampleBlockT* q = reinterpret_cast<const SampleBlockT*>(a.samp); tr.top_k = q->top_k; tr.ln_min_p = q->ln_min_p; }
+  if constexpr (SAMP == 2) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(a.samp));
   (void)tr;
   // timing experiments (dbg_out): 100-MHz ticks wave 0 spends per phase, summed over the 15 note steps -> dbg_out[3 * grid + 8 * block + i],
   // i = 0 cell (products + epilogue), 1 barrier + state exchange, 2 pitch head, 3 argmax + dur_hid, 4 duration GRU, 5 token embedding
@@ -989,7 +989,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
   SampleBlock sb{};
   if constexpr (SAMP) sb = *a.samp;
   Trunc tr{};                                                   // SAMP = 2: a.samp is the 48-byte block, these its last words
-  if constexpr (SAMP == 2) { const SampleBlockT* q = reinterpret_cast<const SampleBlockT*>(a.samp); tr.top_k = q->top_k; tr.ln_min_p = q->ln_min_p; }
+  if constexpr (SAMP == 2) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(a.samp));
   (void)tr;
 
   // ---- one-time loads: duration GRU weights / tables -> LDS, initial state and first token -> LDS

@@ -151,7 +151,7 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
     if constexpr (SAMP == 2) {                                     // truncated: the draw over the classes that reach the row's threshold
       const SampleBlockT* q = reinterpret_cast<const SampleBlockT*>(samp);
       const SampleBlock sb = q->s;
-      const Trunc tr{q->top_k, q->ln_min_p};
+      const Trunc tr = load_trunc(q);
       float tv[3];
 #pragma unroll
       for (int i = 0; i < 3; i++) tv[i] = lane + 64 * i < 130 ? lr[lane + 64 * i] : -INFINITY;

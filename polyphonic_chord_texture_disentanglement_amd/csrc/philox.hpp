@@ -96,17 +96,27 @@ __device__ __forceinline__ float perturbed(float logit, float T, float g) { retu
 //   ln_min_p: keep the classes >= m + T_pitch * ln(min_p), m the row's largest logit (p_c >= min_p * p_max under softmax(logits / T));
 //             any value > 0 = off (the host writes LN_MIN_P_OFF; ln(min_p) <= 0 for every min_p in (0, 1]) -- the test is on the
 //             word itself, no infinity is ever multiplied by T
-// Both: the larger threshold.  The row's best class passes either rule, so the kept set is never empty.
+//   top_p_q24: nucleus -- round(top_p * 2^24) in [1, 2^24], 0 = off (the first of the two words that were reserved and zero: every
+//             block written before keeps its meaning).  Keep the smallest set of best classes whose mass under softmax(logits / T) reaches
+//             top_p, ties with the last kept value all kept: class c is kept iff the mass of the classes strictly above it is < top_p * Z.
+//             The masses are INTEGERS, w_c = trunc(__expf((logit_c - m) / T) * 2^20) (fp32 difference and quotient, each correctly
+//             rounded), so Z and every partial mass are exact sums, the same on every lane layout and in every cluster member
+//             (a class whose w truncates to 0 carries no mass).  T = 0: no rule (the decode is the argmax decode anyway)
+// All given: the largest threshold -- every rule is judged on the untruncated row.  The row's best class passes each rule, so the kept
+// set is never empty.
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct SampleBlockT {
   SampleBlock s;
   int top_k;
   float ln_min_p;
-  unsigned reserved[2];
+  unsigned top_p_q24;
+  unsigned reserved;
 };
 static_assert(sizeof(SampleBlock) == 32 && sizeof(SampleBlockT) == 48, "sampling blocks: 32 / 48 bytes (include/ptvae_hip.h)");
 constexpr float LN_MIN_P_OFF = 1.f;
-struct Trunc { int top_k; float ln_min_p; };                       // what a kernel keeps of the extension
+struct Trunc { int top_k; float ln_min_p; unsigned top_p_q24; };   // what a kernel keeps of the extension
+__device__ __forceinline__ Trunc load_trunc(const SampleBlockT* q) { return Trunc{q->top_k, q->ln_min_p, q->top_p_q24}; }
+constexpr int TOP_P_MASS_BITS = 20;                                // a class's integer mass is <= 2^20: 130 of them stay below 2^28
 
 // order-preserving integer key of a float (-0.0 is +0.0: they compare equal) and its inverse
 __device__ __forceinline__ unsigned order_key(float v) {
@@ -139,6 +149,9 @@ template <int W> __device__ __forceinline__ float row_max(float x) {
 // top_k: a 32-round bitwise select of the k-th largest order key -- a round counts the row's keys >= the candidate (NV compares per
 // lane, one W-lane sum) and keeps the bit if there are at least k; fixed cost, no LDS, independent of the lane layout.  The padding
 // keys are below every real one and k < 130 real values exist, so the selected key is a real logit's.
+// top_p: the same select with masses in place of counts -- a round keeps the bit iff mass{key >= candidate} * 2^24 >= Z * top_p_q24 (64-bit;
+// the right side is formed once).  The largest such candidate is the key of a class with w > 0 (the mass changes only there; the best
+// class has w = 2^20, so Z > 0 and the padding, w = 0, is never selected).  Same cost for every row, no LDS.
 template <int NV, int W>
 __device__ __forceinline__ float pitch_keep_threshold(const Trunc tr, float T, const float (&v)[NV]) {
   float thr = -INFINITY;
@@ -156,6 +169,31 @@ __device__ __forceinline__ float pitch_keep_threshold(const Trunc tr, float T, c
       if (row_sum<W>(cnt) >= tr.top_k) sel = cand;
     }
     thr = order_key_value(sel);
+  }
+  if (tr.top_p_q24 != 0u && T > 0.f) {
+    float m = v[0];
+#pragma unroll
+    for (int i = 1; i < NV; i++) m = fmaxf(m, v[i]);
+    m = row_max<W>(m);
+    unsigned key[NV];
+    int w[NV], z = 0;
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+      key[i] = order_key(v[i]);
+      w[i] = (int)(__expf((v[i] - m) / T) * (float)(1 << TOP_P_MASS_BITS));   // (-inf: 0; the best class: exactly 2^20)
+      z += w[i];
+    }
+    const unsigned long long need = (unsigned long long)(unsigned)row_sum<W>(z) * tr.top_p_q24;
+    unsigned sel = 0u;
+#pragma unroll 1
+    for (int b = 31; b >= 0; b--) {
+      const unsigned cand = sel | (1u << b);
+      int g = 0;
+#pragma unroll
+      for (int i = 0; i < NV; i++) g += key[i] >= cand ? w[i] : 0;
+      if (((unsigned long long)(unsigned)row_sum<W>(g) << 24) >= need) sel = cand;
+    }
+    thr = fmaxf(thr, order_key_value(sel));
   }
   if (tr.ln_min_p <= 0.f) {
     float m = v[0];

@@ -62,7 +62,7 @@ template <int LAYOUT>
 __global__ void pitch_keep_kernel(const SampleBlockT* __restrict__ blk, const float* __restrict__ logits, long rows,
                                   unsigned char* __restrict__ keep_out, float* __restrict__ thr_out) {
   constexpr int W = LAYOUT ? 64 : 16, NV = LAYOUT ? 3 : 9;
-  const Trunc tr{blk->top_k, blk->ln_min_p};
+  const Trunc tr = load_trunc(blk);
   const float T = blk->s.t_pitch;
   const long per = blockDim.x / W, total = (rows + per - 1) / per * per;
   for (long r_ = (long)blockIdx.x * per + threadIdx.x / W; r_ < total; r_ += (long)gridDim.x * per) {

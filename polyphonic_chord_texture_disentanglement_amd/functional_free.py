@@ -90,15 +90,18 @@ NOTE_LOOP_CLUSTER = None if os.environ.get('PTV_NOTE_CLUSTER') is None else int(
 # ---------------------------------------------------------------------------------------------
 SAMPLE_BIT = 0x800000           # ptv_free_note_loop's `train` word: io[21] is the sampling block
 # truncated sampling (top_k / min_p bound the support of the PITCH draw): the block grows to 48 bytes -- the 32 above, then {int32 top_k
-# (0 = off), float ln(min_p) (LN_MIN_P_OFF = off), 8 reserved bytes} -- and the word count of the tensor (4 or 6) picks the instantiation
+# (0 = off), float ln(min_p) (LN_MIN_P_OFF = off), uint32 round(top_p * 2^24) (0 = off), 4 reserved bytes} -- and the word count of the
+# tensor (4 or 6) picks the instantiation
 TRUNC_BIT = 0x1000000           # ... io[21] is the 48-byte block (only together with SAMPLE_BIT)
 LN_MIN_P_OFF = 1.0              # any ln_min_p > 0 switches the min_p rule off (ln(min_p) <= 0 for every min_p in (0, 1])
+TOP_P_ONE = 1 << 24             # nucleus: the block holds top_p as round(top_p * 2^24) in [1, 2^24]; 0 = off (top_p = 1.0 or None)
 
 
-def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, draw=0, *, top_k=None, min_p=None):
-    """(T_pitch, T_dur, sample_offset, seed, draw) validated -- ValueError before anything touches a GPU (top_k / min_p: check_truncation)"""
+def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, draw=0, *, top_k=None, min_p=None, top_p=None):
+    """(T_pitch, T_dur, sample_offset, seed, draw) validated -- ValueError before anything touches a GPU (top_k / min_p / top_p:
+    check_truncation)"""
     import math
-    check_truncation(top_k, min_p)
+    check_truncation(top_k, min_p, top_p)
     tp = 0.0 if temperature is None else temperature
     td = tp if dur_temperature is None else dur_temperature
     for name, v in (('temperature', tp), ('dur_temperature', td)):
@@ -110,12 +113,13 @@ def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, d
     return float(tp), float(td), sample_offset, seed, draw
 
 
-def check_truncation(top_k=None, min_p=None):
-    """(top_k word, ln_min_p) validated, or None when neither rule is given -- ValueError before anything touches a GPU.
+def check_truncation(top_k=None, min_p=None, top_p=None):
+    """(top_k word, ln_min_p, top_p word) validated, or None when no rule is given -- ValueError before anything touches a GPU.
     top_k: an integer >= 1 (stored clipped to 130: k >= 130 keeps every class); min_p: a finite float in [0, 1], 0 = off;
-    ln(min_p) is taken in float64 (the block stores it rounded to fp32)"""
+    ln(min_p) is taken in float64 (the block stores it rounded to fp32); top_p (nucleus): a finite float in (0, 1], stored as
+    round(top_p * 2^24) but never below 1, and 1.0 = off (the word 0)"""
     import math
-    if top_k is None and min_p is None:
+    if top_k is None and min_p is None and top_p is None:
         return None
     k = 0
     if top_k is not None:
@@ -128,24 +132,30 @@ def check_truncation(top_k=None, min_p=None):
             raise ValueError('min_p must be a finite float in [0, 1], got %r' % (min_p,))
         if min_p > 0:
             ln = math.log(float(min_p))
-    return k, ln
+    q = 0
+    if top_p is not None:
+        if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or math.isnan(top_p) or math.isinf(top_p) or not 0 < top_p <= 1:
+            raise ValueError('top_p must be a finite float in (0, 1], got %r' % (top_p,))
+        if top_p < 1:
+            q = min(max(int(math.floor(float(top_p) * TOP_P_ONE + 0.5)), 1), TOP_P_ONE)
+    return k, ln, q
 
 
-def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None):
-    """the block as four int64 words (host list); six with top_k / min_p"""
+def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None):
+    """the block as four int64 words (host list); six with top_k / min_p / top_p"""
     import struct
     tp, td, off, seed, draw = check_sampling(temperature, dur_temperature, sample_offset, seed, draw)
     words = [seed - (1 << 64) if seed >= (1 << 63) else seed, draw, off, struct.unpack('<q', struct.pack('<ff', tp, td))[0]]
-    tr = check_truncation(top_k, min_p)
+    tr = check_truncation(top_k, min_p, top_p)
     if tr is not None:
-        words += [struct.unpack('<q', struct.pack('<if', *tr))[0], 0]
+        words += [struct.unpack('<q', struct.pack('<if', *tr[:2]))[0], tr[2]]
     return words
 
 
-def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None):
-    """the device block of a sampled decode: PtvaeDecoder.decoder(..., sampling=block).  Four int64 words; six with top_k / min_p
-    (truncated sampling, INTEGRATION.md "Sampled decode")"""
-    words = sampling_words(temperature, dur_temperature, seed, draw, sample_offset, top_k=top_k, min_p=min_p)
+def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None):
+    """the device block of a sampled decode: PtvaeDecoder.decoder(..., sampling=block).  Four int64 words; six with top_k / min_p /
+    top_p (truncated sampling, INTEGRATION.md "Sampled decode")"""
+    words = sampling_words(temperature, dur_temperature, seed, draw, sample_offset, top_k=top_k, min_p=min_p, top_p=top_p)
     if torch.device(device).type != 'cuda':
         raise RuntimeError('a sampled decode runs on the GPU: the sampling block lives in device memory (got device %s)' % (device,))
     return torch.tensor(words, dtype=torch.int64, device=device)

@@ -357,29 +357,34 @@ class DisentangleVAE(PytorchModel):
     # Truncated sampling bounds the support of the PITCH draw (the duration bits keep dur_temperature, the chord decoder its argmax):
     # top_k (int >= 1) keeps the classes >= the k-th largest logit of the row, ties with it included; min_p (float in [0, 1], 0 / None =
     # off) keeps the classes with p >= min_p * p_max under softmax(logits / temperature); both: a class must pass both.  The draw is then
-    # exact from the renormalised truncated softmax, with the same noise words.  Nucleus (top-p) truncation is not built.
+    # exact from the renormalised truncated softmax, with the same noise words.  top_p (float in (0, 1], 1.0 / None = off) is nucleus
+    # truncation: the smallest set of best classes whose mass under softmax(logits / temperature) reaches top_p, ties with the last kept
+    # value included.  Every rule is judged on the untruncated row and a class must pass all that are given -- not the sequential
+    # renormalising chain of other libraries.
     @staticmethod
-    def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None):
+    def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
+                        top_p=None):
         """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode.  No side effect, no GPU"""
         if temperature is None and dur_temperature is None:
             if seed is not None or draw is not None or sample_offset is not None:
                 raise ValueError('seed / draw / sample_offset belong to a sampled decode: give a temperature')
-            if top_k is not None or min_p is not None:
-                raise ValueError('top_k / min_p belong to a sampled decode: give a temperature')
+            if top_k is not None or min_p is not None or top_p is not None:
+                raise ValueError('top_k / min_p / top_p belong to a sampled decode: give a temperature')
             return False
         from .functional_free import check_sampling
         check_sampling(temperature, dur_temperature, 0 if sample_offset is None else sample_offset, 0 if seed is None else seed,
-                       0 if draw is None else draw, top_k=top_k, min_p=min_p)
+                       0 if draw is None else draw, top_k=top_k, min_p=min_p, top_p=top_p)
         return True
 
-    def _sampling_words(self, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None):
+    def _sampling_words(self, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
+                        top_p=None):
         """None (argmax decode) or the validated sampling block as host words -- ValueError for a bad value before anything is launched"""
-        if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset, top_k, min_p):
+        if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset, top_k, min_p, top_p):
             return None
         from .functional_free import sampling_words
         ph = self._philox or (7, 0)
         words = sampling_words(temperature, dur_temperature, ph[0] if seed is None else seed, self._sample_draws if draw is None else draw,
-                               ph[1] if sample_offset is None else sample_offset, top_k=top_k, min_p=min_p)
+                               ph[1] if sample_offset is None else sample_offset, top_k=top_k, min_p=min_p, top_p=top_p)
         if draw is None:
             self._sample_draws += 1
         return words
@@ -396,26 +401,26 @@ class DisentangleVAE(PytorchModel):
         return self.decoder(dec_z, True, None, None, 0., 0., sampling=block)
 
     def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None,
-                         top_k=None, min_p=None):
+                         top_k=None, min_p=None, top_p=None):
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
             self._decode(z_chd, z_rhy, dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw,
-                                            sample_offset=sample_offset, top_k=top_k, min_p=min_p))
+                                            sample_offset=sample_offset, top_k=top_k, min_p=min_p, top_p=top_p))
             est_x = self.decoder.last_xhat[:, :, 1:, :].cpu().numpy()
         return est_x
 
     # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
-                         sample_offset=None, top_k=None, min_p=None):
+                         sample_offset=None, top_k=None, min_p=None, top_p=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
         inference_decode's (the chord decoder keeps its argmax)."""
         from .ptvae import _require_cuda
         sampling = dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset,
-                        top_k=top_k, min_p=min_p)
+                        top_k=top_k, min_p=min_p, top_p=top_p)
         self._check_sampling(**sampling)                                # (bad values are a ValueError whatever device the inputs are on)
         _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')
@@ -436,7 +441,9 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:133-142
     def inference(self, pr_mat, c, sample, **sampling):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant; **sampling: the keywords of a sampled
-        decode (inference_decode), here and in swap / posterior_sample / prior_sample / interp"""
+        decode (inference_decode), here and in swap / posterior_sample / prior_sample / interp -- a bad value is a ValueError before
+        anything is encoded"""
+        self._check_sampling(**sampling)
         if self.detrended:
             self._check_dt_x(pr_mat)                     # (a piano-roll here is a ValueError, not a shape crash inside a kernel)
         self.eval()
@@ -458,6 +465,7 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:150-172
     def posterior_sample(self, pr_mat, c, scale=None, sample_chd=True, sample_txt=True, **sampling):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
+        self._check_sampling(**sampling)
         if scale is None and sample_chd and sample_txt:
             return self.inference(pr_mat, c, sample=True, **sampling)
         dist_chd, dist_rhy = self.inference_encode(pr_mat, c)
@@ -478,6 +486,7 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:174-184
     def prior_sample(self, x, c, sample_chd=False, sample_rhy=False, scale=1., **sampling):
         """x: the texture encoder's input (the reference's name for this slot here) -- the piano-roll, or dt_x for the detrended variant"""
+        self._check_sampling(**sampling)
         dist_chd, dist_rhy = self.inference_encode(x, c)
         mean = torch.zeros_like(dist_rhy.mean)
         loc = torch.ones_like(dist_rhy.mean) * scale
@@ -497,6 +506,7 @@ class DisentangleVAE(PytorchModel):
     def interp(self, pr_mat1, c1, pr_mat2, c2, interp_chd=False, interp_rhy=False, int_count=10, **sampling):
         """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant; a sampled decode's sample
         index is the row of the flattened [bs * int_count] batch"""
+        self._check_sampling(**sampling)
         dist_chd1, dist_rhy1 = self.inference_encode(pr_mat1, c1)
         dist_chd2, dist_rhy2 = self.inference_encode(pr_mat2, c2)
         z_chd1, z_rhy1, z_chd2, z_rhy2 = dist_chd1.mean, dist_rhy1.mean, dist_chd2.mean, dist_rhy2.mean

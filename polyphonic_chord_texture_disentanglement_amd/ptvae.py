@@ -288,9 +288,9 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         order and arguments depend only on (B, precision) -- capture once, then one graph launch per call.
         The graph holds raw parameter pointers, so it is re-captured if the parameter storage moves.
         A sampled decode is a graph of its own (other kernels); its sampling block is a static tensor refreshed before every
-        replay, so the key holds neither seed nor draw nor temperatures.  A truncated sampled decode (a 6-word block: top_k / min_p)
-        is a third kind: the key gains that one bit, the values of top_k / min_p live in the block like seed and draw -- one capture
-        serves them all."""
+        replay, so the key holds neither seed nor draw nor temperatures.  A truncated sampled decode (a 6-word block: top_k / min_p /
+        top_p) is a third kind: the key gains that one bit, the values of top_k / min_p / top_p live in the block like seed and draw --
+        one capture serves them all."""
         ps = self._params_free()
         kind = 0 if sampling is None else (2 if sampling.numel() == 6 else 1)
         key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind)
@@ -366,7 +366,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
 
     def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None):
         """sampling: None (argmax decisions) or a block of functional_free.sampling_block() -- the decisions of the free-running decode
-        are then seeded draws from softmax(logits / T), with top_k / min_p in the block over the truncated support of the pitch row;
+        are then seeded draws from softmax(logits / T), with top_k / min_p / top_p in the block over the truncated support of the pitch row;
         inference only (ValueError otherwise, before any launch)"""
         if sampling is not None and (not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None):
             raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')

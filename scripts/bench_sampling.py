@@ -1,11 +1,14 @@
 """The sampled and the truncated-sampled free-running decode beside the argmax decode, same process, same batch (BASELINE configs[3]: batch
 2048, the step loop replayed from a captured hipGraph): --rounds interleaved rounds of --reps decodes each, timed by events after a warm-up;
-every round uses another draw, none needs a new capture.  Prints one JSON line with the three ranges, the cost of sampling and the cost of
-truncation (top_k / min_p: the 32-round select and the row maximum in the pitch phase of every note step).
+every round uses another draw, none needs a new capture.  Prints one JSON line with the ranges, the cost of sampling and the cost of
+truncation (top_k / min_p: the 32-round select and the row maximum in the pitch phase of every note step; top_p: nine exponentials and
+the 32-round select on integer masses), the nucleus rows -- top_p alone and top_k + top_p -- beside the others in the same process.
 
-    python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--top-k 8] [--min-p 0.9] [--eager]
+    python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--top-k 8] [--min-p 0.9] [--top-p 0.9]
+                                     [--eager]
 
---top-k 0 and --min-p 0 switch the rule off; with both off the truncated decode is not timed.
+--top-k 0, --min-p 0 and --top-p 0 switch the rule off; with top_k and min_p both off the 'truncated' decode is not timed, with top_p
+off the two nucleus rows are not.
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ def main():
     ap.add_argument('--temperature', type=float, default=1.0)
     ap.add_argument('--top-k', type=int, default=8, help='0 = off')
     ap.add_argument('--min-p', type=float, default=0.9, help='0 = off')
+    ap.add_argument('--top-p', type=float, default=0.9, help='0 = off')
     ap.add_argument('--eager', action='store_true', help='no graph replay')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the MI355X'
@@ -38,9 +42,17 @@ def main():
     z = torch.randn(a.batch, 512, device=dev)
     trunc = dict(top_k=a.top_k or None, min_p=a.min_p or None)
     kinds = ['argmax', 'sampled'] + (['truncated'] if a.top_k or a.min_p else [])
+    nucleus = {}
+    if a.top_p:
+        nucleus['top_p'] = dict(top_p=a.top_p)
+        if a.top_k:
+            nucleus['top_k+top_p'] = dict(top_k=a.top_k, top_p=a.top_p)
+    kinds += list(nucleus)
     blocks = {'argmax': [None] * (a.rounds + 1),
               'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
               'truncated': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **trunc) for d in range(a.rounds + 1)]}
+    for k, kw in nucleus.items():
+        blocks[k] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **kw) for d in range(a.rounds + 1)]
 
     def run(block):
         with torch.no_grad():
@@ -67,12 +79,14 @@ def main():
     assert m.decoder.graph_captures == captures              # a new draw is not a new capture
     rate = {k: [round(a.batch / (v * 1e-3), 1) for v in vs] for k, vs in ms.items()}
     best = {k: max(v) for k, v in rate.items()}
-    out = {'what': 'free-running decode: argmax, sampled and truncated-sampled decisions', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
-           'temperature': a.temperature, 'top_k': a.top_k, 'min_p': a.min_p, 'ms_per_decode': {k: [round(x, 3) for x in v] for k, v in ms.items()},
+    out = {'what': 'free-running decode: argmax, sampled, truncated-sampled and nucleus-sampled decisions', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
+           'temperature': a.temperature, 'top_k': a.top_k, 'min_p': a.min_p, 'top_p': a.top_p, 'ms_per_decode': {k: [round(x, 3) for x in v] for k, v in ms.items()},
            'samples_per_s': rate, 'sampled_over_argmax_best': round(best['sampled'] / best['argmax'], 4)}
     if 'truncated' in kinds:
         out['truncated_over_sampled_best'] = round(best['truncated'] / best['sampled'], 4)
         out['truncated_over_argmax_best'] = round(best['truncated'] / best['argmax'], 4)
+    for k in nucleus:
+        out[k + '_over_sampled_best'] = round(best[k] / best['sampled'], 4)
     out['device'] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
 
