@@ -949,6 +949,26 @@ int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitc
  *     train & 3 != 0, a coin mask or a NULL block is PTV_ERR_ARG before any launch.
  *   ptv_note_token_sample_trunc: ptv_note_token_sample with the 48-byte block.
  *   ptv_decoder_free_fwd: PTV_DFF_D_SAMPLE_TRUNC != 0 says PTV_DFF_SAMPLE is the 48-byte block.
+ * Constrained decode (pitch masks, ascending notes) restricts the SUPPORT of the pitch decision before any truncation.  The block is then 64
+ * bytes: the 48 above unchanged, followed by { uint32 flags, uint32 reserved (zero), uint64 device address of the mask or 0 }.
+ *   flags bit 0 (ascending): a pitch c < 128 is allowed iff c > lo, lo the largest pitch < 128 already decided in this time step (after
+ *     force_pitch where it overrides; -1 at note step 0); <sos> (128) is never allowed.
+ *   flags bit 1: the mask has one row [32, 4] that serves every row of the batch.
+ *   mask: int32 [B, 32, 4] on the device, rows as the rows of the decoded batch (sample_offset moves only the noise): bit p & 31 of word
+ *     p >> 5 of [b, t] set = grid pitch p (0..127) is allowed at time step t.  Classes 128 / 129 are not covered by it.
+ *   <eos> (129) is always allowed, so the allowed set is never empty.  A disallowed class enters the truncation rules as -infinity: top_k
+ *   counts the k best ALLOWED classes (fewer than k allowed: all of them), the nucleus mass, Z and min_p's maximum are those of the allowed
+ *   classes.  The decision is the first maximal index of logit + T_pitch * g over the classes that are allowed and kept, with exactly the
+ *   noise words above: an exact draw from the softmax renormalised over that set, a pure function of (seed, draw, global sample, t, n), the
+ *   row's logits, its mask words and lo.  T_pitch = T_dur = 0 is the constrained argmax.  The emitted logits stay the plain ones.
+ *   ptv_free_note_loop: bit 25 of train, together with bit 23, says io[21] is the 64-byte block (bit 24 then adds nothing); the guards of
+ *     bit 24 apply.  The mask row of a sample is loaded once per launch.
+ *   ptv_note_token_sample_cons: ptv_note_token_sample with the 64-byte block; M is the batch, row r takes mask row r.  xhat points at
+ *     slot n of row 0 of a [M, 32, 16, 6] grid as in the other forms, and under `ascending` the slots 1 .. n - 1 before it are read.
+ *   ptv_decoder_free_fwd: PTV_DFF_D_SAMPLE_CONS != 0 says PTV_DFF_SAMPLE is the 64-byte block.
+ *   ptv_pitch_mask_build: mask [B, 32, 4] from a pitch range lo <= p <= hi (0, 127 = no restriction), a 12-bit pitch-class set (bit p % 12;
+ *     0xfff = no restriction) and, unless NULL, the chroma of chroma [B, 8, 36] fp32: p at step t passes iff chroma[b, t / 4, 12 + p % 12]
+ *     != 0.  The three are ANDed.  lo / hi outside 0 <= lo <= hi <= 127 or a set outside 0..0xfff: PTV_ERR_ARG.
  */
 int ptv_note_token_sample(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
                           float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
@@ -956,6 +976,10 @@ int ptv_note_token_sample(const float* pitch, long ld_pitch, const int* dur_idx,
 int ptv_note_token_sample_trunc(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
                                 float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
                                 const int* force_pitch, int M, const void* sample48, int t, void* stream);
+int ptv_note_token_sample_cons(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
+                               float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
+                               const int* force_pitch, int M, const void* sample64, int t, void* stream);
+int ptv_pitch_mask_build(int* mask, long B, int lo, int hi, int pitch_classes, const float* chroma, void* stream);
 int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
                              int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream);
 int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,
@@ -1006,7 +1030,7 @@ enum PtvDffTensor {
   PTV_DFF_IDX, PTV_DFF_PLEN, PTV_DFF_GC16, PTV_DFF_DUR_SCR, PTV_DFF_IDX_SCR,
   PTV_DFF_XH0, PTV_DFF_XH1, PTV_DFF_XH16_0, PTV_DFF_XH16_1, PTV_DFF_XG0, PTV_DFF_XG1,
   PTV_DFF_WAIT_EVENT, PTV_DFF_RECORD_EVENT,   /* hipEvent_t or NULL: the persistent-launch turn around the cluster-mode note loops */
-  PTV_DFF_SAMPLE,           /* NULL, or the sampling block of a sampled decode (32 bytes on the device, 48 with D_SAMPLE_TRUNC; "Sampled decode" above): D_INFERENCE only,
+  PTV_DFF_SAMPLE,           /* NULL, or the sampling block of a sampled decode (32 bytes on the device, 48 with D_SAMPLE_TRUNC, 64 with D_SAMPLE_CONS; "Sampled decode" above): D_INFERENCE only,
                              * anything else is PTV_ERR_ARG before the first launch */
   PTV_DFF_COUNT
 };
@@ -1020,6 +1044,7 @@ enum PtvDffDim {
   PTV_DFF_D_TOK0_LDS,       /* row stride of TOK0_SRC (0 = one row for all) */
   PTV_DFF_D_W_IH_T_BF16, PTV_DFF_D_W_HH_T_BF16,
   PTV_DFF_D_SAMPLE_TRUNC,   /* != 0: PTV_DFF_SAMPLE is the 48-byte block of a truncated sampled decode (top_k / min_p / top_p); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
+  PTV_DFF_D_SAMPLE_CONS,    /* != 0: PTV_DFF_SAMPLE is the 64-byte block of a constrained decode (pitch mask / ascending notes); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
   PTV_DFF_D_COUNT
 };
 int ptv_decoder_free_fwd(const void* const* t, const long* d, const void* const* wl, const void* const* io, const void* const* wr,

@@ -51,6 +51,13 @@ int ptv_debug_sample_noise(const void* block, long rows, int t, int n, float* ou
  * columns l + 64 i (the step loop).  keep_out [rows, 130] uint8 = logit >= threshold, thr_out [rows] fp32 = the threshold (-inf: no rule) */
 int ptv_debug_pitch_keep(const void* block48, const float* logits, long rows, int layout, unsigned char* keep_out, float* thr_out, void* stream);
 
+/* test aid of the constrained decode (ptvae_hip.h "Constrained decode"): the decoder's own allowed rule (csrc/philox.hpp pitch_constrain)
+ * followed by pitch_keep_threshold on caller-supplied rows: logits [rows, 130] fp32, masks [rows, 4] int32 (the four mask words of each
+ * row), lo [rows] int32, under the 64-byte block (its T_pitch, top_k, ln_min_p, top_p_q24 and flags are read, its mask address is not).
+ * Layouts as above.  keep_out [rows, 130] uint8 = allowed and logit >= threshold, thr_out [rows] fp32 = the threshold */
+int ptv_debug_pitch_constrain(const void* block64, const float* logits, const int* masks, const int* lo, long rows, int layout,
+                              unsigned char* keep_out, float* thr_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

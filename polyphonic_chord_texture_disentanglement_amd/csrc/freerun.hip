@@ -244,8 +244,10 @@ template <int N> __device__ __forceinline__ void argmax_ror(float& best, int& bi
 // SAMP = 1: the decisions are draws from softmax(logits / T) -- Gumbel noise keyed by (seed, draw, GLOBAL sample, t, n) is added to the values
 // the argmax reduces (philox.hpp); the logits written out stay the plain ones.  Every member of a cluster draws the same noise for a row.
 // SAMP = 2: truncated sampling (top_k / min_p) -- the draw runs over the classes whose logit reaches pitch_keep_threshold() of the row
-// (philox.hpp: ONE function for every decision site).  Cluster mode: every member runs that function on the same logits (each computed the
-// whole head redundantly, same products, same order) with the same block, so all members reach the same decision; nobody is told it.
+// (philox.hpp: ONE function for every decision site).  SAMP = 3: ... and that are ALLOWED (pitch mask / ascending notes: pitch_constrain(),
+// philox.hpp) -- the mask bitmap and the running `lo` are integer registers every member forms from the same decisions.
+// Cluster mode: every member runs those functions on the same logits (each computed the whole head redundantly, same products, same
+// order) with the same block, so all members reach the same decision; nobody is told it.
 template <int RES, int NUK = 2, int SAMP = 0>                    // NUK = 1: the eight-member cluster's kernel (one unit tile per wave and note step)
 __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
   __shared__ __attribute__((aligned(16))) bf16x8 wp8[RES ? 16 * 4 * 2 : 1];   // pitch-head tile 8, rows 128 / 129 only: [kb][quad][row]
@@ -342,9 +344,21 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
   float4 ew0 = make_float4(0.f, 0.f, 0.f, 0.f), ew1 = ew0;      // RES: embedding row of the decision, requested in P3
   SampleBlock sb{};
   if constexpr (SAMP) sb = *a.samp;
-  Trunc tr{};                                                   // SAMP = 2: a.samp is the 48-byte block, these its last words
-  if constexpr (SAMP == 2) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(a.samp));
+  Trunc tr{};                                                   // SAMP >= 2: a.samp is the 48-byte block, these its last words
+  if constexpr (SAMP >= 2) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(a.samp));
   (void)tr;
+  // SAMP = 3: the 64-byte block.  The row's mask is fixed over the 15 note steps: its 16 bytes are loaded here, once, and reduced to the
+  // bitmap of the nine columns this lane owns in P3; `lo` runs with the decisions
+  Cons cn{};
+  unsigned own = 0u;
+  int lo = -1;
+  if constexpr (SAMP == 3) {
+    cn = load_cons(reinterpret_cast<const SampleBlockC*>(a.samp));
+    unsigned mw[4];
+    pitch_mask_words(cn, min(r0 + (tid >> 4), B - 1), t, mw);
+    own = pitch_mask_own<9, 16>(mw, tid & 15);
+  }
+  (void)cn; (void)own; (void)lo;
   // timing experiments (dbg_out): 100-MHz ticks wave 0 spends per phase, summed over the 15 note steps -> dbg_out[3 * grid + 8 * block + i],
   // i = 0 cell (products + epilogue), 1 barrier + state exchange, 2 pitch head, 3 argmax + dur_hid, 4 duration GRU, 5 token embedding
   long tph[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;
@@ -580,7 +594,20 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
 #pragma unroll
         for (int k = 0; k < 9; k++) pv[k] = pit[row][j + 16 * k];              // (columns 130..143 of the row exist and hold zeros)
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (SAMP == 2) {                                             // ... over the classes that reach the row's threshold
+        if constexpr (SAMP == 3) {                                             // ... over the ALLOWED classes that reach the threshold of the allowed
+          float tv[9];
+          const unsigned al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv);
+          const float thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
+          float gum[9];
+          pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
+#pragma unroll
+          for (int k = 0; k < 9; k++) {
+            const int c = j + 16 * k;
+            const float x = perturbed(pv[k], sb.t_pitch, gum[k]);
+            const bool take = ((al >> k) & 1u) && pv[k] >= thr && x > best;
+            best = take ? x : best; bi = take ? c : bi;
+          }
+        } else if constexpr (SAMP == 2) {                                      // ... over the classes that reach the row's threshold
           float tv[9];
 #pragma unroll
           for (int k = 0; k < 9; k++) tv[k] = j + 16 * k < FNP ? pv[k] : -INFINITY;
@@ -619,7 +646,15 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
         }
       } else {
       float thr = -INFINITY;
-      if constexpr (SAMP == 2) {
+      unsigned al = 0u;
+      (void)al;
+      if constexpr (SAMP == 3) {
+        float pv[9], tv[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) pv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
+        al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv);
+        thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
+      } else if constexpr (SAMP == 2) {
         float tv[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) tv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
@@ -635,7 +670,8 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           if (ok) a.pitch[pr * a.ld_pitch + c] = v;
           float x = v;
           if constexpr (SAMP) x = perturbed(v, sb.t_pitch, gum[k]);
-          if constexpr (SAMP == 2) { if (v >= thr && x > best) { best = x; bi = c; } }
+          if constexpr (SAMP == 3) { if (((al >> k) & 1u) && v >= thr && x > best) { best = x; bi = c; } }
+          else if constexpr (SAMP == 2) { if (v >= thr && x > best) { best = x; bi = c; } }
           else if (x > best) { best = x; bi = c; }
         }
       }
@@ -646,6 +682,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
       }
       }
       if (a.force_pitch) bi = a.force_pitch[(long)n * R + (long)t * B + min(r0 + row, B - 1)];
+      if constexpr (SAMP == 3) lo = pitch_lo_next(lo, bi);       // (every lane of the row holds the decision)
       if (j == 0) pidx[row] = bi;
       if constexpr (RES) {                                        // (every lane of the row holds the decision; P6 maps threads the same way)
         const float* wr_ = a.w_embT + (long)bi * FE + j * 8;
@@ -988,9 +1025,21 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
   const long wrowE = (long)t * B + rE, wrowC = (long)t * B + rC;   // row in the [R]-row step-major matrices
   SampleBlock sb{};
   if constexpr (SAMP) sb = *a.samp;
-  Trunc tr{};                                                   // SAMP = 2: a.samp is the 48-byte block, these its last words
-  if constexpr (SAMP == 2) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(a.samp));
+  Trunc tr{};                                                   // SAMP >= 2: a.samp is the 48-byte block, these its last words
+  if constexpr (SAMP >= 2) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(a.samp));
   (void)tr;
+  // SAMP = 3: the 64-byte block.  The row's mask is fixed over the 15 note steps: its 16 bytes are loaded here, once, and reduced to the
+  // bitmap of the nine columns this lane owns in P3; `lo` runs with the decisions
+  Cons cn{};
+  unsigned own = 0u;
+  int lo = -1;
+  if constexpr (SAMP == 3) {
+    cn = load_cons(reinterpret_cast<const SampleBlockC*>(a.samp));
+    unsigned mw[4];
+    pitch_mask_words(cn, min(r0 + (tid >> 4), B - 1), t, mw);
+    own = pitch_mask_own<9, 16>(mw, tid & 15);
+  }
+  (void)cn; (void)own; (void)lo;
 
   // ---- one-time loads: duration GRU weights / tables -> LDS, initial state and first token -> LDS
   for (int i = tid0; i < 12 * 2 * 64; i += 512) wdl[i] = a.wdur[i];
@@ -1179,7 +1228,15 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       const long pr = (long)n * R + (long)t * B + min(r0 + row, B - 1);
       const bool ok = r0 + row < B;
       float thr = -INFINITY;
-      if constexpr (SAMP == 2) {                                 // (all 256 head threads are here: whole DPP rows)
+      unsigned al = 0u;
+      (void)al;
+      if constexpr (SAMP == 3) {                                        // (all 256 head threads are here: whole DPP rows)
+        float pv[9], tv[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) pv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
+        al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv);
+        thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
+      } else if constexpr (SAMP == 2) {
         float tv[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) tv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
@@ -1195,7 +1252,8 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
           if (ok) a.pitch[pr * a.ld_pitch + c] = v;
           float x = v;
           if constexpr (SAMP) x = perturbed(v, sb.t_pitch, gum[k]);
-          if constexpr (SAMP == 2) { if (v >= thr && x > best) { best = x; bi = c; } }
+          if constexpr (SAMP == 3) { if (((al >> k) & 1u) && v >= thr && x > best) { best = x; bi = c; } }
+          else if constexpr (SAMP == 2) { if (v >= thr && x > best) { best = x; bi = c; } }
           else if (x > best) { best = x; bi = c; }
         }
       }
@@ -1205,6 +1263,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
       }
       if (a.force_pitch) bi = a.force_pitch[(long)n * R + (long)t * B + min(r0 + row, B - 1)];
+      if constexpr (SAMP == 3) lo = pitch_lo_next(lo, bi);       // (every lane of the row holds the decision)
       if (j == 0) pidx[row] = bi;
     }
     // ================= P4: dur_hid_linear([h | logits]) -> initial duration state (wave w = units w*16..) =================
@@ -1563,6 +1622,7 @@ extern "C" int ptv_pack_mfma_b(const float* W, long ld, int N, int K, void* out,
 // w[16]: wg_h, wg_t, wp, wd_h, wd_p, wdur (packed bf16), b_hh_n, b_p, b_dh, b_hh_d, tab0, tab, w_out, b_out, w_embT, b_emb
 // train bit 23: io has a 22nd entry, the sampling block (inference only); without the bit io[21] is never read
 // train bit 24 (with bit 23): io[21] is the 48-byte block of a truncated sampled decode (top_k / min_p; philox.hpp SampleBlockT)
+// train bit 25 (with bit 23): io[21] is the 64-byte block of a constrained decode (pitch mask / ascending notes + truncation; SampleBlockC)
 // io[21]: gc, emb, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16, dbg words, h0gc,
 //         xch, cnt (cluster mode, train bits 18-20 = S in {2, 4}: S workgroups per 16-sample panel, ptvae_hip.h)
 extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitch, int B, int t, unsigned coin_mask, int train,
@@ -1575,6 +1635,8 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   const bool samp = (train & 0x800000) != 0, trunc = (train & 0x1000000) != 0;
   if (samp && ((train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG;     // sampling is inference only
   if (trunc && (!samp || (train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG;   // truncation belongs to a sampled decode (io[21]: the 48-byte block)
+  const bool cons = (train & 0x2000000) != 0;
+  if (cons && (!samp || (train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG;    // ... and so do constraints (io[21]: the 64-byte block)
   NoteLoopArgs a{};
   a.samp = samp ? (const SampleBlock*)io[21] : nullptr;
   a.wg_h = (const bf16x8*)w[0]; a.wg_t = (const bf16x8*)w[1]; a.wp = (const bf16x8*)w[2]; a.wd_h = (const bf16x8*)w[3];
@@ -1615,7 +1677,12 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   const int pi = prof::want(7, B, FHN) ? prof::begin((hipStream_t)stream) : -1;
   if (!split) {
     const dim3 grid(a.S > 1 ? (panels + 7) / 8 * 8 * a.S : panels);
-    if (trunc) {
+    if (cons) {
+      if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);
+      else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL((note_loop_kernel<1, 2, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    }
+    else if (trunc) {
       if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
       else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
       else hipLaunchKernelGGL((note_loop_kernel<1, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -1629,6 +1696,7 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
     else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);   // bit 21: head weights streamed (timing comparisons)
     else hipLaunchKernelGGL((note_loop_kernel<1, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
   }
+  else if (cons) hipLaunchKernelGGL((note_loop2_kernel<3>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
   else if (trunc) hipLaunchKernelGGL((note_loop2_kernel<2>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
   else if (samp) hipLaunchKernelGGL((note_loop2_kernel<1>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL((note_loop2_kernel<0>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);

@@ -139,6 +139,7 @@ __global__ void clip_adam_kernel(float* __restrict__ p, const float* __restrict_
 // ---------------------------------------------------------------------------------------------
 template <int SAMP>                    // SAMP = 1: row r is sample r at (t, note step n - 1), the pitch decision a draw (philox.hpp)
                                        // SAMP = 2: ... over the classes pitch_keep_threshold() keeps; `samp` is then the 48-byte block
+                                       // SAMP = 3: ... that pitch_constrain() allows; `samp` is then the 64-byte block
 __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch, const int* __restrict__ dur_idx, long dur_stride,
                                   const float* __restrict__ W, const float* __restrict__ bias, int E,
                                   float* __restrict__ pred, long ld_pred, long* __restrict__ xhat, long xhat_stride,
@@ -148,7 +149,33 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
   for (int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < M; r += gridDim.x * (blockDim.x >> 6)) {
     const float* lr = pitch + (long)r * ld_pitch;
     float best = -INFINITY; int bi = 0x7fffffff;
-    if constexpr (SAMP == 2) {                                     // truncated: the draw over the classes that reach the row's threshold
+    if constexpr (SAMP == 3) {                                     // constrained: ... over the ALLOWED classes (pitch_constrain, philox.hpp)
+      const SampleBlockC* q = reinterpret_cast<const SampleBlockC*>(samp);
+      const SampleBlock sb = q->s.s;
+      const Trunc tr = load_trunc(&q->s);
+      const Cons cn = load_cons(q);
+      // lo: the largest pitch < 128 among the slots 1 .. n - 1 of this row's step, already filled by the launches before (xhat points at slot n)
+      const long* xr = xhat + (long)r * xhat_stride;
+      int lo = -1;
+      if (lane + 1 < n) { const long p = xr[(long)(lane + 1 - n) * 6]; if (p < 128) lo = (int)p; }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lo = max(lo, __shfl_xor(lo, o, 64));
+      unsigned mw[4];
+      pitch_mask_words(cn, r, t, mw);
+      float pv[3], tv[3];
+#pragma unroll
+      for (int i = 0; i < 3; i++) pv[i] = lane + 64 * i < 130 ? lr[lane + 64 * i] : -INFINITY;
+      const unsigned al = pitch_constrain<3, 64>(pv, mw, lo, cn.flags, lane, tv);
+      const float thr = pitch_keep_threshold<3, 64>(tr, sb.t_pitch, tv);      // (the whole wave is here: r is uniform over it)
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const int c = lane + 64 * i;
+        if (((al >> i) & 1u) && pv[i] >= thr) {
+          const float x = perturbed(pv[i], sb.t_pitch, pitch_gumbel1(sb, sb.sample_offset + r, t, n - 1, c));
+          if (x > best) { best = x; bi = c; }
+        }
+      }
+    } else if constexpr (SAMP == 2) {                              // truncated: the draw over the classes that reach the row's threshold
       const SampleBlockT* q = reinterpret_cast<const SampleBlockT*>(samp);
       const SampleBlock sb = q->s;
       const Trunc tr = load_trunc(q);
@@ -374,6 +401,47 @@ extern "C" int ptv_note_token_sample_trunc(const float* pitch, long ld_pitch, co
   int nb = (M + 3) / 4; if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(note_token_kernel<2>, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
                      pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M, (const SampleBlock*)sample48, t);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// ... with the 64-byte block of a constrained decode (pitch mask / ascending notes; its mask rows are the M rows here).  xhat points at slot
+// n of row 0 of a [M, 32, 16, 6] grid as in the forms above: under `ascending` the slots 1 .. n - 1 before it are READ
+extern "C" int ptv_note_token_sample_cons(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
+                                          float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
+                                          const int* force_pitch, int M, const void* sample64, int t, void* stream) {
+  if (!pitch || !dur_idx || !W || !bias || !pred || !xhat || !plen || M <= 0 || E <= 0) return PTV_ERR_ARG;
+  if (!sample64 || t < 0 || t >= 32 || n < 1 || n > 15) return PTV_ERR_ARG;
+  int nb = (M + 3) / 4; if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(note_token_kernel<3>, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
+                     pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M, (const SampleBlock*)sample64, t);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// pitch masks of a constrained decode: word w of [b, t] from a pitch range, a pitch-class set and the chroma of the chord, ANDed.
+// One thread per word.
+__global__ void pitch_mask_build_kernel(int* __restrict__ mask, long B, int lo, int hi, unsigned pcs, const float* __restrict__ c) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * 32 * 4) return;
+  const int w = (int)(i & 3), t = (int)((i >> 2) & 31);
+  const long b = i >> 7;
+  const float* cr = c ? c + (b * 8 + (t >> 2)) * 36 + 12 : nullptr;
+  unsigned word = 0u;
+  for (int k = 0; k < 32; k++) {
+    const int p = w * 32 + k, pc = p % 12;
+    bool ok = p >= lo && p <= hi && ((pcs >> pc) & 1u);
+    if (ok && cr) ok = cr[pc] != 0.f;
+    word |= (ok ? 1u : 0u) << k;
+  }
+  mask[i] = (int)word;
+}
+
+extern "C" int ptv_pitch_mask_build(int* mask, long B, int lo, int hi, int pitch_classes, const float* chroma, void* stream) {
+  if (!mask || B <= 0 || lo < 0 || hi > 127 || lo > hi || pitch_classes < 0 || pitch_classes > 0xfff) return PTV_ERR_ARG;
+  const long n = B * 32 * 4;
+  hipLaunchKernelGGL(pitch_mask_build_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mask, B, lo, hi,
+                     (unsigned)pitch_classes, chroma);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

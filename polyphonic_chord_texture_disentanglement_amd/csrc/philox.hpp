@@ -204,4 +204,76 @@ __device__ __forceinline__ float pitch_keep_threshold(const Trunc tr, float T, c
   return thr + 0.f;                                                // (a zero threshold is +0.0)
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Constrained decode: restrictions on the SUPPORT of the pitch decision, applied before the truncation above.  The block is
+// the 48 bytes above, unchanged, followed by 16 more: 64 bytes.
+//   flags bit 0 (CONS_ASCENDING): a pitch c < 128 is allowed iff c > lo, lo the largest pitch < 128 already decided in this time step
+//             (after force_pitch; -1 at note step 0); <sos> (128) is never allowed
+//   flags bit 1 (CONS_MASK_ROW1): the mask has ONE row [32, 4] for the whole batch (row stride 0)
+//   mask:     0, or the device address of int32 [B, 32, 4]: bit p & 31 of word p >> 5 of [b, t] set = grid pitch p allowed at time step t;
+//             classes 128 / 129 are not covered by it
+// <eos> (129) is always allowed: the allowed set is never empty.  A disallowed class enters pitch_keep_threshold() as -INFINITY (top_k counts
+// the k best ALLOWED classes, the nucleus mass, Z and min_p's maximum are those of the allowed classes; with fewer than k allowed the
+// select ends at the -INFINITY key: all of them are kept), and the draw tests the returned bitmap beside the threshold.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct SampleBlockC {
+  SampleBlockT s;
+  unsigned flags;
+  unsigned reserved;
+  const unsigned* mask;
+};
+static_assert(sizeof(SampleBlockC) == 64, "constrained sampling block: 64 bytes (include/ptvae_hip.h)");
+constexpr unsigned CONS_ASCENDING = 1u, CONS_MASK_ROW1 = 2u;
+struct Cons { unsigned flags; const unsigned* mask; };             // what a kernel keeps of the extension
+__device__ __forceinline__ Cons load_cons(const SampleBlockC* q) { return Cons{q->flags, q->mask}; }
+
+// the four mask words of row b at time step t (all ones without a mask): ONE 16-byte row, loaded once per launch by the note loops
+__device__ __forceinline__ void pitch_mask_words(const Cons cn, long b, int t, unsigned (&m)[4]) {
+  m[0] = m[1] = m[2] = m[3] = 0xffffffffu;
+  if (cn.mask) {
+    const unsigned* p = cn.mask + (((cn.flags & CONS_MASK_ROW1) ? 0 : b) * 32 + t) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++) m[i] = p[i];
+  }
+}
+// ... reduced to what a lane needs: bit i = the mask's verdict on the lane's column j + W i (classes 128 / 129: set; columns >= 130: clear)
+template <int NV, int W>
+__device__ __forceinline__ unsigned pitch_mask_own(const unsigned (&m)[4], int j) {
+  unsigned own = 0u;
+#pragma unroll
+  for (int i = 0; i < NV; i++) {
+    const int c = j + W * i, w = c >> 5;                           // (W = 16: w = i >> 1, a constant)
+    const unsigned word = w == 0 ? m[0] : w == 1 ? m[1] : w == 2 ? m[2] : m[3];
+    const unsigned bit = c < 128 ? (word >> (c & 31)) & 1u : (c < 130 ? 1u : 0u);
+    own |= bit << i;
+  }
+  return own;
+}
+// largest pitch < 128 among the decisions so far: the running `lo` of a lane
+__device__ __forceinline__ int pitch_lo_next(int lo, int decision) { return decision < 128 && decision > lo ? decision : lo; }
+
+// THE allowed rule, shared by every decision site (and ptv_debug_pitch_constrain).  v: the NV logits of this lane's columns j + W i;
+// own: pitch_mask_own() of the row's mask words; lo, flags as above (flags is uniform over the block: a scalar branch).
+// tv: v with the disallowed classes (and the columns >= 130) at -INFINITY -- the input of pitch_keep_threshold(); returns the bitmap of the
+// lane's allowed columns: the draw takes column i iff bit i is set and v[i] >= the threshold.
+template <int NV, int W>
+__device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], unsigned own, int lo, unsigned flags, int j, float (&tv)[NV]) {
+  unsigned al = own;
+  if (flags & CONS_ASCENDING) {
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+      const int c = j + W * i;
+      if (!(c == 129 || (c < 128 && c > lo))) al &= ~(1u << i);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; i++) tv[i] = (al >> i) & 1u ? v[i] : -INFINITY;
+  return al;
+}
+// ... from the row's four mask words (the step loop and the debug entry, which see a row once)
+template <int NV, int W>
+__device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], const unsigned (&m)[4], int lo, unsigned flags, int j, float (&tv)[NV]) {
+  return pitch_constrain<NV, W>(v, pitch_mask_own<NV, W>(m, j), lo, flags, j, tv);
+}
+
 }  // namespace ptv

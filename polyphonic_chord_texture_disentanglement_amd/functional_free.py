@@ -95,6 +95,12 @@ SAMPLE_BIT = 0x800000           # ptv_free_note_loop's `train` word: io[21] is t
 TRUNC_BIT = 0x1000000           # ... io[21] is the 48-byte block (only together with SAMPLE_BIT)
 LN_MIN_P_OFF = 1.0              # any ln_min_p > 0 switches the min_p rule off (ln(min_p) <= 0 for every min_p in (0, 1])
 TOP_P_ONE = 1 << 24             # nucleus: the block holds top_p as round(top_p * 2^24) in [1, 2^24]; 0 = off (top_p = 1.0 or None)
+# constrained decode (pitch masks, ascending notes: restrictions on the SUPPORT of the pitch decision, applied before any truncation): the
+# block grows to 64 bytes -- the 48 above (without a truncation rule: top_k 0, LN_MIN_P_OFF, 0), then {uint32 flags, uint32 reserved, uint64
+# device address of the mask or 0} -- eight words
+CONS_BIT = 0x2000000            # ... io[21] is the 64-byte block (only together with SAMPLE_BIT)
+CONS_ASCENDING = 1              # flags bit 0: a pitch < 128 must exceed the largest pitch < 128 already decided in the time step; never <sos>
+CONS_MASK_ROW1 = 2              # flags bit 1: the mask has one row [32, 4] for the whole batch
 
 
 def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, draw=0, *, top_k=None, min_p=None, top_p=None):
@@ -141,30 +147,80 @@ def check_truncation(top_k=None, min_p=None, top_p=None):
     return k, ln, q
 
 
-def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None):
-    """the block as four int64 words (host list); six with top_k / min_p / top_p"""
+def check_constraints(pitch_mask=None, ascending=None, batch=None):
+    """flags word of a constrained decode, or None when neither keyword is given -- ValueError before anything is launched.
+    pitch_mask: an int32 device tensor [B, 32, 4] or [1, 32, 4] (bit p & 31 of word p >> 5 of [b, t]: grid pitch p allowed at step t);
+    batch: the rows of the decode when the caller knows them (a mask of another row count, 1 excepted, is refused);
+    ascending: a bool -- False alone still selects the constrained kernels (a vacuous constraint)"""
+    if pitch_mask is None and ascending is None:
+        return None
+    if ascending is not None and not isinstance(ascending, bool):
+        raise ValueError('ascending must be a bool, got %r' % (ascending,))
+    flags = CONS_ASCENDING if ascending else 0
+    if pitch_mask is not None:
+        if not torch.is_tensor(pitch_mask) or pitch_mask.device.type != 'cuda':
+            raise ValueError('pitch_mask must be a device tensor (DisentangleVAE.pitch_mask builds one)')
+        if pitch_mask.dtype != torch.int32:
+            raise ValueError('pitch_mask must be int32, got %s' % (pitch_mask.dtype,))
+        if pitch_mask.dim() != 3 or tuple(pitch_mask.shape[1:]) != (32, 4) or pitch_mask.shape[0] < 1:
+            raise ValueError('pitch_mask must have shape [B, 32, 4] or [1, 32, 4], got %s' % (tuple(pitch_mask.shape),))
+        if batch is not None and pitch_mask.shape[0] not in (1, batch):
+            raise ValueError('pitch_mask has %d rows, the decoded batch has %d' % (pitch_mask.shape[0], batch))
+        if pitch_mask.shape[0] == 1:
+            flags |= CONS_MASK_ROW1
+    return flags
+
+
+def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None,
+                   pitch_mask=None, ascending=None):
+    """the block as four int64 words (host list); six with top_k / min_p / top_p; eight with pitch_mask / ascending (the last word is
+    the address of pitch_mask as given: the caller keeps that tensor alive and contiguous -- sampling_block does)"""
     import struct
     tp, td, off, seed, draw = check_sampling(temperature, dur_temperature, sample_offset, seed, draw)
     words = [seed - (1 << 64) if seed >= (1 << 63) else seed, draw, off, struct.unpack('<q', struct.pack('<ff', tp, td))[0]]
     tr = check_truncation(top_k, min_p, top_p)
+    flags = check_constraints(pitch_mask, ascending)
+    if flags is not None and tr is None:
+        tr = (0, LN_MIN_P_OFF, 0)
     if tr is not None:
         words += [struct.unpack('<q', struct.pack('<if', *tr[:2]))[0], tr[2]]
+    if flags is not None:
+        if pitch_mask is not None and not pitch_mask.is_contiguous():
+            raise ValueError('pitch_mask must be contiguous')
+        words += [flags, 0 if pitch_mask is None else pitch_mask.data_ptr()]
     return words
 
 
-def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None):
+def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None,
+                   pitch_mask=None, ascending=None):
     """the device block of a sampled decode: PtvaeDecoder.decoder(..., sampling=block).  Four int64 words; six with top_k / min_p /
-    top_p (truncated sampling, INTEGRATION.md "Sampled decode")"""
-    words = sampling_words(temperature, dur_temperature, seed, draw, sample_offset, top_k=top_k, min_p=min_p, top_p=top_p)
+    top_p (truncated sampling, INTEGRATION.md "Sampled decode"); eight with pitch_mask / ascending (INTEGRATION.md "Constrained
+    decode"; temperature 0 is then the constrained argmax).  The word count selects the kernels.  An eight-word block carries the mask
+    it points at as its attribute `pitch_mask` (None without one): that keeps the mask alive, and tells the decoder its row count"""
+    if pitch_mask is not None and torch.is_tensor(pitch_mask):
+        pitch_mask = pitch_mask.contiguous()
+    words = sampling_words(temperature, dur_temperature, seed, draw, sample_offset, top_k=top_k, min_p=min_p, top_p=top_p,
+                           pitch_mask=pitch_mask, ascending=ascending)
     if torch.device(device).type != 'cuda':
         raise RuntimeError('a sampled decode runs on the GPU: the sampling block lives in device memory (got device %s)' % (device,))
-    return torch.tensor(words, dtype=torch.int64, device=device)
+    blk = torch.tensor(words, dtype=torch.int64, device=device)
+    if pitch_mask is not None and pitch_mask.device != blk.device:
+        raise ValueError('pitch_mask is on %s, the block on %s' % (pitch_mask.device, blk.device))
+    if len(words) == 8:
+        blk.pitch_mask = pitch_mask
+    return blk
 
 
-def _check_block(sampling, dev):
-    if not (torch.is_tensor(sampling) and sampling.dtype == torch.int64 and sampling.numel() in (4, 6) and sampling.is_contiguous()
+def _check_block(sampling, dev, B=None):
+    if not (torch.is_tensor(sampling) and sampling.dtype == torch.int64 and sampling.numel() in (4, 6, 8) and sampling.is_contiguous()
             and sampling.device == dev):
         raise ValueError('sampling must be a block made by functional_free.sampling_block() on the device of z')
+    if sampling.numel() == 8:
+        if not hasattr(sampling, 'pitch_mask'):
+            raise ValueError('a constrained block must come from functional_free.sampling_block(): it carries the mask it points at')
+        mask = sampling.pitch_mask
+        if mask is not None and (mask.device != dev or (B is not None and mask.shape[0] not in (1, B))):
+            raise ValueError('pitch_mask has %d rows on %s, the decoded batch has %s rows on %s' % (mask.shape[0], mask.device, B, dev))
     return sampling
 
 
@@ -282,7 +338,7 @@ def _decoder_free_fwd_composite(P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of,
                        'LDP': dims['ldp'], 'TRAIN': dims['train'], 'REPLAY': dims['replay'], 'INFERENCE': dims['inference'],
                        'LOOP_FLAGS': dims['loop_flags'], 'CLUSTER': dims['cluster'], 'RESUM_TRAIN': dims['resum_train'], 'TOK0_LDS': tok0_lds,
                        'W_IH_T_BF16': w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': w_hh_t.dtype == torch.bfloat16,
-                       'SAMPLE_TRUNC': dims.get('sample_trunc', 0)})
+                       'SAMPLE_TRUNC': dims.get('sample_trunc', 0), 'SAMPLE_CONS': dims.get('sample_cons', 0)})
     coin_notes, coin_time = coins
     masks = (ctypes.c_uint * 32)()
     tc = (ctypes.c_ubyte * 31)()
@@ -352,9 +408,10 @@ class DecoderStepFn(torch.autograd.Function):
         if sampling is not None:
             if not inference or any(any(r) for r in coins[0]) or any(coins[1]):
                 raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
-            _check_block(sampling, dev)
-        samp_bit = 0 if sampling is None else (SAMPLE_BIT | (TRUNC_BIT if sampling.numel() == 6 else 0))
+            _check_block(sampling, dev, z.shape[0])
+        samp_bit = 0 if sampling is None else (SAMPLE_BIT | {4: 0, 6: TRUNC_BIT, 8: TRUNC_BIT | CONS_BIT}[sampling.numel()])
         trunc = bool(samp_bit & TRUNC_BIT)
+        cons = bool(samp_bit & CONS_BIT)
         z = z.contiguous()
         B = z.shape[0]
         R = 32 * B
@@ -476,7 +533,7 @@ class DecoderStepFn(torch.autograd.Function):
                      xch, xcnt]),
                 ior=F_._parr([PRED, plen, XH[0], XH[1], XG[0], XG[1], None]) if need_resum else None,
                 dims=dict(B=B, Zs=z.shape[1], Zi=Zi, He=He, Ht=Ht, Hn=Hn, Hd=Hd, E=E, NP=NP, ldp=pitch.stride(0), train=int(train), replay=int(bool(replay)),
-                          inference=int(bool(inference)), cluster=int(cluster and not capturing), sample_trunc=int(trunc),
+                          inference=int(bool(inference)), cluster=int(cluster and not capturing), sample_trunc=int(trunc), sample_cons=int(cons),
                           loop_flags=(2 if replay else int(train)) | (0 if NOTE_LOOP_SPLIT is None else (0x20000 if NOTE_LOOP_SPLIT else 0x10000))
                           | cluster_bits(cluster), resum_train=int(train and not replay)),
                 tens=dict(NS=NS, NS16=NS16, Z_IN=z_in, ZG=zg, TOKS=TOKS, GATES_T=gates_t, TOK=TOK, PRED=PRED, PITCH=pitch, HN=HN, HN16=HN16,
@@ -554,7 +611,8 @@ class DecoderStepFn(torch.autograd.Function):
                              ptr(P['dur_out_linear.weight']),
                              ptr(P['dur_out_linear.bias']), ptr(dur2[pr][:, 2 * d:]), 10, ptr(idx[d][pr]),
                              ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp + ((d,) if smp else ())), st)
-                call('ptv_note_token' if sampling is None else ('ptv_note_token_sample_trunc' if trunc else 'ptv_note_token_sample'),
+                call('ptv_note_token' if sampling is None else 'ptv_note_token_sample_cons' if cons else
+                     'ptv_note_token_sample_trunc' if trunc else 'ptv_note_token_sample',
                      ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(w_emb), ptr(b_emb), E,
                      ptr(PRED[n + 1][rows]), E, ptr(xhat[0, t, n + 1]), 32 * 16 * 6, ptr(plen[rows]), n + 1, int(n == 14),
                      ptr(force_pitch[n][rows]) if force_pitch is not None else None, B, *(smp[:2] if smp else ()), st)

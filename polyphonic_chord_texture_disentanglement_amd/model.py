@@ -361,30 +361,41 @@ class DisentangleVAE(PytorchModel):
     # truncation: the smallest set of best classes whose mass under softmax(logits / temperature) reaches top_p, ties with the last kept
     # value included.  Every rule is judged on the untruncated row and a class must pass all that are given -- not the sequential
     # renormalising chain of other libraries.
+    # Constrained decode (INTEGRATION.md "Constrained decode") restricts the SUPPORT of the pitch decision, before any truncation:
+    # pitch_mask (int32 device tensor [B, 32, 4] or [1, 32, 4]; pitch_mask() below builds one) says which grid pitches a time step may
+    # use, ascending=True makes the notes of a time step strictly increasing and never <sos> -- the PianoTree grammar.  <eos> is always
+    # allowed.  The mask's rows are the rows of the decoded batch (sample_offset moves only the noise).  With temperature=None the decode
+    # is the constrained ARGMAX (the draw counter does not advance; seed / draw / sample_offset stay a ValueError).
     @staticmethod
     def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
-                        top_p=None):
-        """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode.  No side effect, no GPU"""
+                        top_p=None, pitch_mask=None, ascending=None, batch=None):
+        """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode (constrained or not).  No side
+        effect, no launch.  batch: the rows of the decoded batch where the caller knows them (pitch_mask's row count is held to it)"""
+        from .functional_free import check_constraints, check_sampling
+        check_constraints(pitch_mask, ascending, batch)
         if temperature is None and dur_temperature is None:
             if seed is not None or draw is not None or sample_offset is not None:
                 raise ValueError('seed / draw / sample_offset belong to a sampled decode: give a temperature')
             if top_k is not None or min_p is not None or top_p is not None:
                 raise ValueError('top_k / min_p / top_p belong to a sampled decode: give a temperature')
             return False
-        from .functional_free import check_sampling
         check_sampling(temperature, dur_temperature, 0 if sample_offset is None else sample_offset, 0 if seed is None else seed,
                        0 if draw is None else draw, top_k=top_k, min_p=min_p, top_p=top_p)
         return True
 
     def _sampling_words(self, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
-                        top_p=None):
+                        top_p=None, pitch_mask=None, ascending=None, batch=None):
         """None (argmax decode) or the validated sampling block as host words -- ValueError for a bad value before anything is launched"""
-        if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset, top_k, min_p, top_p):
-            return None
         from .functional_free import sampling_words
+        if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset, top_k, min_p, top_p, pitch_mask, ascending,
+                                    batch):
+            if pitch_mask is None and ascending is None:
+                return None
+            return sampling_words(0.0, 0.0, 0, 0, 0, pitch_mask=pitch_mask, ascending=ascending)   # the constrained argmax: no noise, no draw used
         ph = self._philox or (7, 0)
         words = sampling_words(temperature, dur_temperature, ph[0] if seed is None else seed, self._sample_draws if draw is None else draw,
-                               ph[1] if sample_offset is None else sample_offset, top_k=top_k, min_p=min_p, top_p=top_p)
+                               ph[1] if sample_offset is None else sample_offset, top_k=top_k, min_p=min_p, top_p=top_p,
+                               pitch_mask=pitch_mask, ascending=ascending)
         if draw is None:
             self._sample_draws += 1
         return words
@@ -392,36 +403,83 @@ class DisentangleVAE(PytorchModel):
     def _decode(self, z_chd, z_rhy, sampling):
         """the free-running decode of both inference forms; `sampling`: keywords of a sampled decode"""
         from .ptvae import _require_cuda
-        words = self._sampling_words(**sampling)
+        self._check_sampling(**sampling, batch=z_chd.shape[0])
+        mask = sampling.get('pitch_mask')
+        if mask is not None:
+            mask = mask.contiguous()                                    # (the block holds its address)
+            sampling = dict(sampling, pitch_mask=mask)
+        words = self._sampling_words(**sampling, batch=z_chd.shape[0])
         if words is not None:
             _require_cuda(z_chd, 'DisentangleVAE sampled decode')
             _require_cuda(z_rhy, 'DisentangleVAE sampled decode')
         dec_z = torch.cat([z_chd, z_rhy], dim=-1)
         block = None if words is None else torch.tensor(words, dtype=torch.int64, device=dec_z.device)
+        if block is not None and len(words) == 8:
+            block.pitch_mask = mask
         return self.decoder(dec_z, True, None, None, 0., 0., sampling=block)
 
+    def pitch_mask(self, c=None, pitch_classes=None, lo=None, hi=None, batch=None):
+        """int32 device tensor [B, 32, 4] for pitch_mask= (ptv_pitch_mask_build): bit p & 31 of word p >> 5 of [b, t] set = grid pitch p
+        allowed at time step t.  The constraints given are ANDed: c (f32 [B, 8, 36] on the device, the chord input): the chord tones --
+        p passes at step t iff c[b, t // 4, 12 + p % 12] != 0; pitch_classes: the allowed pitch classes, an iterable of 0..11 or a 12-bit
+        set; lo / hi: the pitch range lo <= p <= hi.  B = c.shape[0], else batch, else 1 (one row serves every batch)."""
+        k = 0xfff
+        if pitch_classes is not None:
+            if isinstance(pitch_classes, bool):
+                raise ValueError('pitch_classes must be a 12-bit set or an iterable of pitch classes 0..11')
+            if isinstance(pitch_classes, int):
+                k = pitch_classes
+            else:
+                k = 0
+                for q in pitch_classes:
+                    if isinstance(q, bool) or not isinstance(q, int) or not 0 <= q < 12:
+                        raise ValueError('a pitch class must be an integer in 0..11, got %r' % (q,))
+                    k |= 1 << q
+            if not 0 <= k <= 0xfff:
+                raise ValueError('pitch_classes must be a 12-bit set, got %r' % (pitch_classes,))
+        lo_, hi_ = 0 if lo is None else lo, 127 if hi is None else hi
+        for name, v in (('lo', lo_), ('hi', hi_)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 127:
+                raise ValueError('%s must be an integer in 0..127, got %r' % (name, v))
+        if lo_ > hi_:
+            raise ValueError('lo must not exceed hi, got [%d, %d]' % (lo_, hi_))
+        if c is not None:
+            if not torch.is_tensor(c) or c.device.type != 'cuda' or c.dtype != torch.float32 or c.dim() != 3 or tuple(c.shape[1:]) != (8, 36):
+                raise ValueError('c must be a float32 device tensor [B, 8, 36]')
+            if batch is not None and batch != c.shape[0]:
+                raise ValueError('batch is %r, c has %d rows' % (batch, c.shape[0]))
+            c = c.contiguous()
+        B = c.shape[0] if c is not None else (1 if batch is None else batch)
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError('batch must be an integer >= 1, got %r' % (batch,))
+        from ._lib import call, ptr, stream_ptr
+        out = torch.empty(B, 32, 4, dtype=torch.int32, device=c.device if c is not None else self.device)
+        call('ptv_pitch_mask_build', ptr(out), B, lo_, hi_, k, ptr(c) if c is not None else None, stream_ptr())
+        return out
+
     def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None,
-                         top_k=None, min_p=None, top_p=None):
+                         top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None):
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
             self._decode(z_chd, z_rhy, dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw,
-                                            sample_offset=sample_offset, top_k=top_k, min_p=min_p, top_p=top_p))
+                                            sample_offset=sample_offset, top_k=top_k, min_p=min_p, top_p=top_p,
+                                            pitch_mask=pitch_mask, ascending=ascending))
             est_x = self.decoder.last_xhat[:, :, 1:, :].cpu().numpy()
         return est_x
 
     # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
-                         sample_offset=None, top_k=None, min_p=None, top_p=None):
+                         sample_offset=None, top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
         inference_decode's (the chord decoder keeps its argmax)."""
         from .ptvae import _require_cuda
         sampling = dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset,
-                        top_k=top_k, min_p=min_p, top_p=top_p)
-        self._check_sampling(**sampling)                                # (bad values are a ValueError whatever device the inputs are on)
+                        top_k=top_k, min_p=min_p, top_p=top_p, pitch_mask=pitch_mask, ascending=ascending)
+        self._check_sampling(**sampling, batch=z_chd.shape[0])          # (bad values are a ValueError whatever device the inputs are on)
         _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')
         self.eval()
@@ -443,7 +501,7 @@ class DisentangleVAE(PytorchModel):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant; **sampling: the keywords of a sampled
         decode (inference_decode), here and in swap / posterior_sample / prior_sample / interp -- a bad value is a ValueError before
         anything is encoded"""
-        self._check_sampling(**sampling)
+        self._check_sampling(**sampling, batch=pr_mat.shape[0])
         if self.detrended:
             self._check_dt_x(pr_mat)                     # (a piano-roll here is a ValueError, not a shape crash inside a kernel)
         self.eval()
@@ -465,7 +523,7 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:150-172
     def posterior_sample(self, pr_mat, c, scale=None, sample_chd=True, sample_txt=True, **sampling):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
-        self._check_sampling(**sampling)
+        self._check_sampling(**sampling, batch=pr_mat.shape[0])
         if scale is None and sample_chd and sample_txt:
             return self.inference(pr_mat, c, sample=True, **sampling)
         dist_chd, dist_rhy = self.inference_encode(pr_mat, c)
@@ -486,7 +544,7 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:174-184
     def prior_sample(self, x, c, sample_chd=False, sample_rhy=False, scale=1., **sampling):
         """x: the texture encoder's input (the reference's name for this slot here) -- the piano-roll, or dt_x for the detrended variant"""
-        self._check_sampling(**sampling)
+        self._check_sampling(**sampling, batch=x.shape[0])
         dist_chd, dist_rhy = self.inference_encode(x, c)
         mean = torch.zeros_like(dist_rhy.mean)
         loc = torch.ones_like(dist_rhy.mean) * scale
@@ -505,8 +563,8 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:190-209: decode int_count points on the path between two items' latent codes
     def interp(self, pr_mat1, c1, pr_mat2, c2, interp_chd=False, interp_rhy=False, int_count=10, **sampling):
         """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant; a sampled decode's sample
-        index is the row of the flattened [bs * int_count] batch"""
-        self._check_sampling(**sampling)
+        index is the row of the flattened [bs * int_count] batch, and so are the rows of a pitch_mask (or it has one row)"""
+        self._check_sampling(**sampling, batch=pr_mat1.shape[0] * int_count)
         dist_chd1, dist_rhy1 = self.inference_encode(pr_mat1, c1)
         dist_chd2, dist_rhy2 = self.inference_encode(pr_mat2, c2)
         z_chd1, z_rhy1, z_chd2, z_rhy2 = dist_chd1.mean, dist_rhy1.mean, dist_chd2.mean, dist_rhy2.mean

@@ -290,15 +290,23 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         A sampled decode is a graph of its own (other kernels); its sampling block is a static tensor refreshed before every
         replay, so the key holds neither seed nor draw nor temperatures.  A truncated sampled decode (a 6-word block: top_k / min_p /
         top_p) is a third kind: the key gains that one bit, the values of top_k / min_p / top_p live in the block like seed and draw --
-        one capture serves them all."""
+        one capture serves them all.  A constrained decode (an 8-word block: pitch_mask / ascending) is a fourth kind: its mask is copied
+        into a static tensor before every replay and the static block's address word points at that tensor, so one capture serves every
+        mask, flag, seed and draw."""
         ps = self._params_free()
-        kind = 0 if sampling is None else (2 if sampling.numel() == 6 else 1)
+        kind = 0 if sampling is None else {4: 1, 6: 2, 8: 3}[sampling.numel()]
         key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind)
         ent = self._graphs.get(key)
         if ent is None:
             static_z = z.detach().clone()
+            static_mask = mask_addr = None
             if sampling is not None:
                 ps = ps + [sampling.clone()]
+                if kind == 3:                                  # (captured with every pitch allowed; the flags are the first caller's)
+                    static_mask = torch.full((z.shape[0], 32, 4), -1, dtype=torch.int32, device=z.device)
+                    mask_addr = torch.tensor([static_mask.data_ptr()], dtype=torch.int64, device=z.device)
+                    ps[-1].pitch_mask = static_mask
+                    ps[-1][7:8].copy_(mask_addr if sampling.pitch_mask is not None else torch.zeros_like(mask_addr))
             cur = torch.cuda.current_stream()
             # warm-up and capture share ONE stream (as graph_step.py): the library's split-K workspaces are per stream and cannot be
             # allocated inside a capture -- captured on another stream the small products fell back to fp32 atomics, and the replayed
@@ -312,14 +320,17 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
                 outs = FF_.DecoderStepFn.apply(static_z, None, None, coins, True, None, self._prec, *ps)
-            for k in [k for k in self._graphs if k[-1] == key[-1]]:         # one graph per kind (argmax, sampled, truncated) is kept
+            for k in [k for k in self._graphs if k[-1] == key[-1]]:         # one graph per kind (argmax, sampled, truncated, constrained) is kept
                 del self._graphs[k]
             self.graph_captures += 1
-            ent = self._graphs[key] = (g, static_z, outs, ps[-1] if sampling is not None else None)
-        g, static_z, outs, static_blk = ent
+            ent = self._graphs[key] = (g, static_z, outs, ps[-1] if sampling is not None else None, static_mask, mask_addr)
+        g, static_z, outs, static_blk, static_mask, mask_addr = ent
         static_z.copy_(z)
         if static_blk is not None:
             static_blk.copy_(sampling)
+            if static_mask is not None and sampling.pitch_mask is not None:
+                static_mask[:sampling.pitch_mask.shape[0]].copy_(sampling.pitch_mask)   # (a one-row mask: row 0, the block's flag says so)
+                static_blk[7:8].copy_(mask_addr)
         g.replay()
         return outs
 
@@ -366,7 +377,8 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
 
     def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None):
         """sampling: None (argmax decisions) or a block of functional_free.sampling_block() -- the decisions of the free-running decode
-        are then seeded draws from softmax(logits / T), with top_k / min_p / top_p in the block over the truncated support of the pitch row;
+        are then seeded draws from softmax(logits / T), with top_k / min_p / top_p in the block over the truncated support of the pitch row,
+        and with pitch_mask / ascending over the allowed classes only (temperature 0: the constrained argmax);
         inference only (ValueError otherwise, before any launch)"""
         if sampling is not None and (not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None):
             raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
@@ -376,7 +388,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             assert x is None and lengths is None
             assert teacher_forcing_ratio1 == 0 and teacher_forcing_ratio2 == 0
             coins = ([[False] * (self.max_simu_note - 2)] * self.num_step, [False] * (self.num_step - 1))
-            smp = () if sampling is None else (FF_._check_block(sampling, z.device),)
+            smp = () if sampling is None else (FF_._check_block(sampling, z.device, B),)
             if self.use_graph and not torch.is_grad_enabled() and self.force_trace is None:
                 pitch, dur, xhat, idx = self._graph_decode(z, coins, sampling)
             else:

@@ -3,12 +3,15 @@
 every round uses another draw, none needs a new capture.  Prints one JSON line with the ranges, the cost of sampling and the cost of
 truncation (top_k / min_p: the 32-round select and the row maximum in the pitch phase of every note step; top_p: nine exponentials and
 the 32-round select on integer masses), the nucleus rows -- top_p alone and top_k + top_p -- beside the others in the same process.
+The constrained rows (pitch masks / ascending notes: one 16-byte mask load per row and launch, a few integer operations per class) are
+the chord-tone mask of a synthetic batch's c, `ascending`, and both with top_k + top_p; they are reported against the plain sampled
+decode of the same process.
 
     python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--top-k 8] [--min-p 0.9] [--top-p 0.9]
-                                     [--eager]
+                                     [--constrained 1] [--eager]
 
 --top-k 0, --min-p 0 and --top-p 0 switch the rule off; with top_k and min_p both off the 'truncated' decode is not timed, with top_p
-off the two nucleus rows are not.
+off the two nucleus rows are not; --constrained 0 leaves the constrained rows out.
 """
 import argparse
 import json
@@ -31,6 +34,7 @@ def main():
     ap.add_argument('--top-k', type=int, default=8, help='0 = off')
     ap.add_argument('--min-p', type=float, default=0.9, help='0 = off')
     ap.add_argument('--top-p', type=float, default=0.9, help='0 = off')
+    ap.add_argument('--constrained', type=int, default=1, help='0 = no constrained rows')
     ap.add_argument('--eager', action='store_true', help='no graph replay')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the MI355X'
@@ -48,10 +52,21 @@ def main():
         if a.top_k:
             nucleus['top_k+top_p'] = dict(top_k=a.top_k, top_p=a.top_p)
     kinds += list(nucleus)
+    constrained = {}
+    if a.constrained:
+        from polyphonic_chord_texture_disentanglement_amd.synthetic import synth_batch
+        c = torch.from_numpy(synth_batch(64, 5)[1]).to(dev)
+        mask = m.pitch_mask(c=c[torch.arange(a.batch, device=dev) % 64].contiguous())        # [batch, 32, 4]: every row its own chord tones
+        constrained['mask'] = dict(pitch_mask=mask)
+        constrained['ascending'] = dict(ascending=True)
+        constrained['mask+ascending+top_k+top_p'] = dict(pitch_mask=mask, ascending=True, top_k=a.top_k or None, top_p=a.top_p or None)
+    kinds += list(constrained)
     blocks = {'argmax': [None] * (a.rounds + 1),
               'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
               'truncated': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **trunc) for d in range(a.rounds + 1)]}
     for k, kw in nucleus.items():
+        blocks[k] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **kw) for d in range(a.rounds + 1)]
+    for k, kw in constrained.items():
         blocks[k] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **kw) for d in range(a.rounds + 1)]
 
     def run(block):
@@ -79,13 +94,13 @@ def main():
     assert m.decoder.graph_captures == captures              # a new draw is not a new capture
     rate = {k: [round(a.batch / (v * 1e-3), 1) for v in vs] for k, vs in ms.items()}
     best = {k: max(v) for k, v in rate.items()}
-    out = {'what': 'free-running decode: argmax, sampled, truncated-sampled and nucleus-sampled decisions', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
+    out = {'what': 'free-running decode: argmax, sampled, truncated-sampled, nucleus-sampled and constrained decisions', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
            'temperature': a.temperature, 'top_k': a.top_k, 'min_p': a.min_p, 'top_p': a.top_p, 'ms_per_decode': {k: [round(x, 3) for x in v] for k, v in ms.items()},
            'samples_per_s': rate, 'sampled_over_argmax_best': round(best['sampled'] / best['argmax'], 4)}
     if 'truncated' in kinds:
         out['truncated_over_sampled_best'] = round(best['truncated'] / best['sampled'], 4)
         out['truncated_over_argmax_best'] = round(best['truncated'] / best['argmax'], 4)
-    for k in nucleus:
+    for k in list(nucleus) + list(constrained):
         out[k + '_over_sampled_best'] = round(best[k] / best['sampled'], 4)
     out['device'] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
