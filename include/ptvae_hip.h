@@ -446,6 +446,10 @@ int ptv_dur_bwd_finalize(const float* S, float* g_whh, float* g_bhh, float* g_bi
  *        `blocked` set (blocked = 3), left unwritten: the consumer is ptv_notes_gru_persist_bwd_top with the same limit as its bound.
  *        dy16 (or NULL): [M][200] bf16 = [dp (130) | 0 (6) | dhd0 (64)] of the live rows -- ONE ptv_wgrad operand for the weight gradients
  *        of both Linears over the note summaries (one pass over the [M][512] summaries instead of two).
+ *   The logits and dp as operands of the second products (130 columns in k-blocks of 32: 160) have their columns 130 .. 159 zeroed by the
+ *        kernels themselves, whatever the packs hold beyond their N and K: the staging memory there holds stale bits.
+ *   Alignment (checked on the host before the launch, PTV_ERR_ARG otherwise -- the kernels make float4 / bf16x8 accesses): 16 bytes for
+ *        hn16, pitch, dp (ldp a multiple of 4), b_dh, hd0, dhd0, dnsum16, dy16 and every pack; 8 bytes for hd16.  b_p is read by element.
  */
 int ptv_heads_fwd(const void* hn16, const void* wp_packed, const void* wdh_packed, const void* wdp_packed, const float* b_p,
                   const float* b_dh, float* pitch, long ldp, float* hd0, void* hd16, long M, void* stream);

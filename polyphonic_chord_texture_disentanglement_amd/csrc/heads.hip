@@ -359,6 +359,9 @@ __global__ __launch_bounds__(256, 1) void heads_bwd_kernel(HeadsBwdArgs a) {
 
 using namespace ptv;
 
+// (a NULL pointer is aligned: the optional outputs)
+static inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
 extern "C" int ptv_heads_fwd_top(const void* hn16, const void* wp_packed, const void* wdh_packed, const void* wdp_packed, const float* b_p,
                                  const float* b_dh, float* pitch, long ldp, float* hd0, void* hd16, long M, const int* m_top, long m_unit,
                                  void* stream);
@@ -382,6 +385,9 @@ extern "C" int ptv_heads_fwd_rows(const void* hn16, const void* wp_packed, const
   if (m_top && (m_unit <= 0 || (m_unit & 127))) return PTV_ERR_ARG;        // (whole 128-row blocks on either side of the limit)
   if (!hn16 || !wp_packed || !wdh_packed || !wdp_packed || !b_p || !b_dh || !pitch || !hd0 || M <= 0 || ldp < HNP || (ldp & 3)) return PTV_ERR_ARG;
   if ((reinterpret_cast<uintptr_t>(pitch) & 15) || (reinterpret_cast<uintptr_t>(hn16) & 15)) return PTV_ERR_ARG;
+  // float4 / bf16x8 accesses: the bias of the duration state, the state itself and the 1-KB fragments of the packs; bf16x4 stores to hd16
+  if (misaligned(b_dh, 16) || misaligned(hd0, 16) || misaligned(wp_packed, 16) || misaligned(wdh_packed, 16) || misaligned(wdp_packed, 16) ||
+      misaligned(hd16, 8)) return PTV_ERR_ARG;
   HeadsFwdArgs a{(const __bf16*)hn16, (const bf16x8*)wp_packed, (const bf16x8*)wdh_packed, (const bf16x8*)wdp_packed, b_p, b_dh,
                  pitch, ldp, hd0, (__bf16*)hd16, M, m_top, m_unit, row_len};
   const int lds = 2 * HCH * HNT * 64 * 16;                                // 104 KB (the staged logits, 42 KB, reuse it)
@@ -403,6 +409,9 @@ extern "C" int ptv_heads_bwd_rows(float* dp, long ldp, const float* dhd0, const 
   if (row_len && (!m_top || (m_unit & 127))) return PTV_ERR_ARG;
   if (!dp || !dhd0 || !wdpT_packed || !wcat_packed || !dnsum16 || M <= 0 || ldp < HNP || (ldp & 3) || (m_top && m_unit <= 0)) return PTV_ERR_ARG;
   if (reinterpret_cast<uintptr_t>(dp) & 15) return PTV_ERR_ARG;
+  // float4 loads of dhd0, bf16x8 stores to dnsum16 / dy16 (rows of 400 bytes, the dHD0 part 272 bytes in), the 1-KB fragments of the packs
+  if (misaligned(dhd0, 16) || misaligned(dnsum16, 16) || misaligned(dy16, 16) || misaligned(wdpT_packed, 16) || misaligned(wcat_packed, 16))
+    return PTV_ERR_ARG;
   HeadsBwdArgs a{dp, ldp, dhd0, (const bf16x8*)wdpT_packed, (const bf16x8*)wcat_packed, (__bf16*)dnsum16, blocked, (__bf16*)dy16, m_top, m_unit, M, row_len};
   const int lds = 2 * HGT * HBK * 64 * 16 + 4 * 32 * HPLD * 2;            // 112 KB + 42 KB
   static bool attr = false;
