@@ -373,7 +373,7 @@ int ptv_loss_bwd_scales(const float* gout11, const int* counts, float beta, floa
 
 /* ------------------------------------------------------------------------------------------------
  * Duration head (ptvae.py:361-367): dur_out[r*ld_out + 0..1] = dur_out_linear(h[r]); idx[r] = argmax
- * (force_idx, if given, overrides the argmax: replay mode for parity checks).
+ * (force_idx, if given, overrides the argmax where its entry is >= 0: replay mode for parity checks, kept steps).
  */
 int ptv_dur_out_token(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
                       int* idx, const int* force_idx, long rows, void* stream);
@@ -901,6 +901,12 @@ int ptv_detrend_pianotree(const long* x, const float* c, unsigned char* dt_x, in
  *     waiting (results void).
  *     Bit 21 of train: the 4-wave kernel streams the head weights from L2 every note step instead of keeping them in registers / LDS
  *     for the whole launch (the kernel before round 6; timing comparisons, bit-identical results).
+ *     force_pitch / force_dur (replay mode of the tests, kept steps of a decode): PER DECISION.  Row t*B + b of force_pitch[n] holds the
+ *     pitch decision of (b, t, note step n), row n*R + t*B + b of force_dur[d] duration bit d of that note; an entry >= 0 overrides the
+ *     decision (the value is fed back and written out as if decided), A NEGATIVE ENTRY MEANS "FREE": the decision is taken as without
+ *     the array -- argmax or draw.  The same holds for force_pitch of ptv_note_token*, force_idx of ptv_dur_out_token* and force of
+ *     ptv_dur_gru_fwd*.  The words of a note step are requested at its top, before the cell's products; the members of a cluster read
+ *     the same words.
  *   ptv_free_resummarize: w = { pack(W_ih), pack(W_hh), pack(W_ih_reverse), pack(W_hh_reverse), b_ih, b_hh, b_ih_r, b_hh_r } of
  *     dec_notes_emb_gru; io = { PRED, plen, XH fwd [17][R][128] (slot 0 zero), XH bwd, XG fwd [16][4][R][128] bf16, XG bwd,
  *     tok_next = TOKS[t+1] [B][256] }.  train bit 0: save states and gates (XH, XG) for the backward; bit 1: stream the weights from L2
@@ -922,7 +928,8 @@ int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitc
  * maximal index over c < 130 of logit[c] + T_pitch * g[b, t, n, c]; duration bit d is 1 iff e1 + T_dur * g1 > e0 + T_dur * g0, with
  * g = -log(-log(u)) standard Gumbel, u = (top 23 bits of a Philox4x32-10 word + 1/2) * 2^-23, the word a pure function of (seed, draw,
  * sample_offset + b, t, n, kind, index) (csrc/philox.hpp).  T = 0 is the argmax, ties included.  The logits written out are the plain ones;
- * force_pitch / force_dur still override.  Inference only: with train != 0 or teacher-forcing coins every entry point returns PTV_ERR_ARG.
+ * force_pitch / force_dur still override where their entry is >= 0 (a negative entry leaves the decision to the draw; a forced decision
+ * leaves its noise words unused, nothing is re-keyed; under `ascending` a forced pitch is not checked but does update lo).  Inference only: with train != 0 or teacher-forcing coins every entry point returns PTV_ERR_ARG.
  *   ptv_free_note_loop: bit 23 of train announces the block as io[21] (io then has 22 entries; without the bit io[21] is not read).
  *   ptv_note_token_sample / ptv_dur_out_token_sample / ptv_dur_gru_fwd_sample: ptv_note_token / ptv_dur_out_token / ptv_dur_gru_fwd with the
  *     block and the position of the rows: row r is sample sample_offset + r at time step t; note step n = 0..14 for the duration forms,
@@ -984,6 +991,15 @@ int ptv_note_token_sample_cons(const float* pitch, long ld_pitch, const int* dur
                                float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
                                const int* force_pitch, int M, const void* sample64, int t, void* stream);
 int ptv_pitch_mask_build(int* mask, long B, int lo, int hi, int pitch_classes, const float* chroma, void* stream);
+/* Kept steps: the force arrays of a free-running decode that keeps some time steps of a grid and decides the rest (INTEGRATION.md "Kept
+ * steps").  x: int64 [B][32][16][6], the model's grid (slot 0 <sos>, pitches 0..127, <eos> 129, <pad> 130; duration bits 0 / 1, 2 = pad);
+ * steps: uint8 [steps_rows][32], steps_rows = 1 (one row serves every sample) or B; != 0 = time step kept.  For a kept (b, t): L = the first
+ * slot s in 1..15 with x[b][t][s][0] == 129, else 15; for n < L force_pitch[n][t*B + b] = x[b][t][n+1][0] if that lies in 0..129, else -1 and
+ * bit 0 of err[b] is set; force_dur[d][n*R + t*B + b] = x[b][t][n+1][1+d] if that is 0 or 1, else -1; n >= L and steps not kept: -1.
+ * EVERY element of force_pitch [15][32B] and force_dur [5][480B] and every err[b] (int32 [B]) is written, by one thread each.
+ * B < 1, steps_rows not in {1, B} or a NULL pointer: PTV_ERR_ARG before any launch. */
+int ptv_keep_force_build(const long* x, const unsigned char* steps, int steps_rows, long B, int* force_pitch, int* force_dur, int* err,
+                         void* stream);
 int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
                              int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream);
 int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,

@@ -634,6 +634,9 @@ extern "C" int ptv_decoder_free_fwd(const void* const* t, const long* d, const v
   if (B <= 0 || E != 128 || He != 128 || Hn != 512 || Hd != 64 || NP != 130 || Ht <= 0 || (Ht & 7) || Zs <= 0 || Zi <= 0 || ldp < NP)
     return PTV_ERR_UNSUPPORTED;
   if (replay && !train) return PTV_ERR_ARG;
+  // force arrays (io[13] / io[14]: replay mode of the tests, kept steps of a decode) pass through to the note loop with any sampling block
+  // in inference; the batched recompute of a replayed training forward knows nothing of them
+  if (replay && (io[13] || io[14])) return PTV_ERR_ARG;
   if (t[PTV_DFF_SAMPLE] && (!inference || train)) return PTV_ERR_ARG;           // sampling is inference only
   const bool trunc = d[PTV_DFF_D_SAMPLE_TRUNC] != 0;                            // ... and truncation belongs to a sampled decode
   if (trunc && !t[PTV_DFF_SAMPLE]) return PTV_ERR_ARG;

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
         x0 = perturbed(o0, sb.t_dur, g0); x1 = perturbed(o1, sb.t_dur, g1);
       }
       int id = x1 > x0 ? 1 : 0;                                           // first max wins ties (torch.max)
-      if (a.force && ok) id = a.force[d * a.force_stride + row];
+      if (a.force && ok) { const int fw = a.force[d * a.force_stride + row]; id = fw >= 0 ? fw : id; }   // (negative: a free decision)
       if (ok && lane < 16) {
         a.dur_out[row * a.ld_out + 2 * d] = o0;
         a.dur_out[row * a.ld_out + 2 * d + 1] = o1;

@@ -236,6 +236,13 @@ template <int N> __device__ __forceinline__ void argmax_ror(float& best, int& bi
   best = take ? ov : best; bi = take ? oi : bi;
 }
 
+// force words (replay mode / kept steps): a word >= 0 overrides the decision, a negative word leaves it free.  Every member of a cluster
+// loads the same word for a row, so all of them take the same branch.
+__device__ __forceinline__ int forced(int w, int decided) { return w >= 0 ? w : decided; }
+__device__ __forceinline__ int force_word5(const int (&w)[5], int d) {   // (selects, not an indexed register array: d may be a runtime value)
+  return d == 0 ? w[0] : d == 1 ? w[1] : d == 2 ? w[2] : d == 3 ? w[3] : w[4];
+}
+
 // RES = 1 (round 6): the weights of the HEAD phases never change over the 15 x 32 note steps, and a wave is alone on its SIMD (512
 // registers): the two pitch-head tiles of a wave stay in registers for the whole launch, the third tile of wave 0 (columns 128 / 129
 // only: 2 KB) and the logits part of dur_hid_linear (20 KB) in LDS, the state part of dur_hid_linear is requested when the head
@@ -248,7 +255,13 @@ template <int N> __device__ __forceinline__ void argmax_ror(float& best, int& bi
 // philox.hpp) -- the mask bitmap and the running `lo` are integer registers every member forms from the same decisions.
 // Cluster mode: every member runs those functions on the same logits (each computed the whole head redundantly, same products, same
 // order) with the same block, so all members reach the same decision; nobody is told it.
-template <int RES, int NUK = 2, int SAMP = 0>                    // NUK = 1: the eight-member cluster's kernel (one unit tile per wave and note step)
+// FORCE = 1: the launch has force arrays (replay mode / kept steps) and requests the six force words of a note step ahead of the decisions.
+// An instantiation of its own: the launches without force arrays run FORCE = 0, the kernel as it was -- no force word in a register (the
+// constrained resident kernel sits at the register limit), its force reads behind a pointer test after the decision.  The launcher sends
+// every launch with force arrays to FORCE = 1, so those reads are never taken; they stay (with the same per-decision rule) so that the
+// FORCE = 0 kernels compile to the instructions they had, but for the select inside those branches -- without them the compiler allocates
+// the scalar registers of the whole kernel differently (profiles/LOG.md "Kept steps").
+template <int RES, int NUK = 2, int SAMP = 0, int FORCE = 0>     // NUK = 1: the eight-member cluster's kernel (one unit tile per wave and note step)
 __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
   __shared__ __attribute__((aligned(16))) bf16x8 wp8[RES ? 16 * 4 * 2 : 1];   // pitch-head tile 8, rows 128 / 129 only: [kb][quad][row]
   __shared__ __attribute__((aligned(16))) bf16x8 wdp[RES ? 4 * 5 * 64 : 1];   // dur_hid_linear, logits part (4 tiles x 5 k-blocks)
@@ -377,6 +390,13 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(S > 1 ? (void*)(a.xch + ((long)panel * 2 + (n & 1)) * (FP * FHN * 2)) : nullptr, 0,
                                                                         S > 1 ? FP * FHN * 4 : 0, 0x00020000);
     const unsigned xseq = (unsigned)(t * 15 + n + 1);
+    // force words of this note step (negative = free): the pitch word of the row this thread decides in P3 and the five duration words of
+    // its row in P5.  Their addresses are known from the top of the note step, so each is requested before products it can hide under and
+    // has long landed when its decision needs it (a load issued after the argmax is a whole L2 round trip on the chain, six per note step):
+    // the pitch word after the cell, in flight across the state exchange and the head products; the duration words when P4 begins, under
+    // dur_hid_linear, its barrier and the first duration step.  (All six at the very top: six registers more across the cell, the head and
+    // the constrained select of P3, and the constrained resident kernel, 507 of 512 registers without them, spilled.)
+    int fpw = -1, fdw[5] = {-1, -1, -1, -1, -1};
     // ================= P1: notes-GRU cell.  wave w owns units [w*128, w*128+128) = 8 tiles of 16, two per pass =================
     // one pass = NU unit tiles (of 16 units) x 3 gates of this wave: two for 1 / 2 / 4 members per panel, ONE for eight (member m: tile m of the wave's 8)
     auto cell_pass = [&](auto nu_c, const int ut0) {
@@ -461,6 +481,9 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
     if constexpr (RES) {                                         // flight across the state exchange, consumed in the head phase
 #pragma unroll
       for (int kb = 0; kb < 16; kb++) wdh[kb] = a.wd_h[((long)wave * 16 + kb) * 64 + lane];
+    }
+    if constexpr (FORCE) {
+      if (a.force_pitch) fpw = a.force_pitch[(long)n * R + (long)t * B + min(r0 + (tid >> 4), B - 1)];
     }
     PH(0);
     if (S == 1) lds_barrier();
@@ -681,7 +704,8 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
       }
       }
-      if (a.force_pitch) bi = a.force_pitch[(long)n * R + (long)t * B + min(r0 + row, B - 1)];
+      if constexpr (FORCE) bi = forced(fpw, bi);
+      else if (a.force_pitch) bi = forced(a.force_pitch[(long)n * R + (long)t * B + min(r0 + row, B - 1)], bi);
       if constexpr (SAMP == 3) lo = pitch_lo_next(lo, bi);       // (every lane of the row holds the decision)
       if (j == 0) pidx[row] = bi;
       if constexpr (RES) {                                        // (every lane of the row holds the decision; P6 maps threads the same way)
@@ -690,6 +714,12 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
       }
     }
     // ================= P4: dur_hid_linear([h | logits]) -> initial duration state (wave w = units w*16..) =================
+    if constexpr (FORCE) {
+      if (a.force_dur) {
+#pragma unroll
+        for (int d = 0; d < 5; d++) fdw[d] = a.force_dur[(long)d * M + (long)n * R + wrowC];
+      }
+    }
     {
       if constexpr (RES) {
         const int rl = lane & 15, kq = (lane >> 4) * 8;
@@ -761,7 +791,8 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           float x0 = e0, x1 = e1;
           if constexpr (SAMP) { x0 = e0 + dn[2 * d]; x1 = e1 + dn[2 * d + 1]; }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
-          if (a.force_dur) id = a.force_dur[(long)d * M + prC];
+          if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
+          else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
@@ -899,7 +930,8 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
             x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
           }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
-          if (a.force_dur) id = a.force_dur[(long)d * M + prC];
+          if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
+          else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
@@ -994,7 +1026,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
 //   producers: token part + epilogue | B0 | segment 1 | B1 | ... | segment 8 | B8
 //   heads:                      wait | B0 | pitch head | B1 | argmax, dur_hid | B2 | dur step 0..4 | B3..B7 | embedding | B8
 // =============================================================================================
-template <int SAMP = 0>
+template <int SAMP = 0, int FORCE = 0>
 __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
   __shared__ __attribute__((aligned(16))) float hf[FP][FHN];                   // notes-GRU state, fp32
   __shared__ __attribute__((aligned(16))) __bf16 h16[2][FP][H16LD];            // its bf16 MFMA-operand copy (double buffered)
@@ -1183,7 +1215,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
     }
   } else {
     // the decision of duration step d for `row` from the four waves' partial sums (complete after that step's barrier)
-    auto dur_decision = [&](int n, int d, int row, long pr) {
+    auto dur_decision = [&](int n, int d, int row, long pr, int fw) {   // fw: the force word of (d, row), prefetched (FORCE)
       const int dc = d & 1;
       const float e0 = part[dc][0][row][0] + part[dc][1][row][0] + part[dc][2][row][0] + part[dc][3][row][0] + wo[2 * FHD];
       const float e1 = part[dc][0][row][1] + part[dc][1][row][1] + part[dc][2][row][1] + part[dc][3][row][1] + wo[2 * FHD + 1];
@@ -1194,12 +1226,24 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
       }
       int id = x1 > x0 ? 1 : 0;
-      if (a.force_dur) id = a.force_dur[(long)d * M + pr];
+      if constexpr (FORCE) id = forced(fw, id);
+      else if (a.force_dur) id = forced(a.force_dur[(long)d * M + pr], id);
       return id;
     };
     for (int n = 0; n < 15; n++) {
       const int cur = n & 1, nxt = cur ^ 1;
       (void)cur;
+      // force words of this note step (negative = free), requested while the heads wait for the producers' state at B0: the pitch word of
+      // the row this thread decides in P3, the five duration words of its row in P5, and the last duration word of its P6 row
+      int fpw = -1, fdw[5] = {-1, -1, -1, -1, -1}, fd4r = -1;
+      if constexpr (FORCE) {
+        if (a.force_pitch) fpw = a.force_pitch[(long)n * R + (long)t * B + min(r0 + (tid >> 4), B - 1)];
+        if (a.force_dur) {
+#pragma unroll
+          for (int d = 0; d < 5; d++) fdw[d] = a.force_dur[(long)d * M + (long)n * R + wrowC];
+          fd4r = a.force_dur[4 * M + (long)n * R + (long)t * B + min(r0 + (tid >> 4), B - 1)];
+        }
+      }
       lds_barrier();                                             // B0
     // ================= P2: pitch head (9 tiles over 4 waves) + the state part of dur_hid_linear (one tile per wave) =================
     f32x4 accD[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -1262,7 +1306,8 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
       }
-      if (a.force_pitch) bi = a.force_pitch[(long)n * R + (long)t * B + min(r0 + row, B - 1)];
+      if constexpr (FORCE) bi = forced(fpw, bi);
+      else if (a.force_pitch) bi = forced(a.force_pitch[(long)n * R + (long)t * B + min(r0 + row, B - 1)], bi);
       if constexpr (SAMP == 3) lo = pitch_lo_next(lo, bi);       // (every lane of the row holds the decision)
       if (j == 0) pidx[row] = bi;
     }
@@ -1340,7 +1385,8 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
             x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
           }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
-          if (a.force_dur) id = a.force_dur[(long)d * M + prC];
+          if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
+          else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
@@ -1358,7 +1404,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       const bool ok = r0 + row < B;
       const long wr = (long)t * B + min(r0 + row, B - 1);
       const int pch = pidx[row];
-      const int last_bit = dur_decision(n, 4, row, (long)n * R + wr);
+      const int last_bit = dur_decision(n, 4, row, (long)n * R + wr, fd4r);
       float v[8];
       const float4 b0 = *reinterpret_cast<const float4*>(a.b_emb + e0), b1 = *reinterpret_cast<const float4*>(a.b_emb + e0 + 4);
       const float4 w0 = *reinterpret_cast<const float4*>(a.w_embT + (long)pch * FE + e0), w1 = *reinterpret_cast<const float4*>(a.w_embT + (long)pch * FE + e0 + 4);
@@ -1397,7 +1443,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         xr[0] = pb;
 #pragma unroll
         for (int d = 0; d < 4; d++) xr[1 + d] = bits[tid][d];
-        xr[5] = dur_decision(n, 4, tid, (long)n * R + (long)t * B + rw);
+        xr[5] = dur_decision(n, 4, tid, (long)n * R + (long)t * B + rw, fdw[4]);   // (tid < FP: crow == tid, rC == rw)
         int L = a.plen[(long)t * B + rw];
         if (L == 0 && pb == 129) L = n + 1;                                     // first <eos>            (ptvae.py:415-416)
         if (n == 14 && L == 0) L = n + 1;                                       // no <eos> by the end     (ptvae.py:425)
@@ -1619,6 +1665,21 @@ extern "C" int ptv_pack_mfma_b(const float* W, long ld, int N, int K, void* out,
   return PTV_OK;
 }
 
+// the kernel of a launch: 8 waves (split) or 4; of the 4-wave kernel the eight-member form (NUK = 1), the one that streams the head weights
+// (bit 21 of train: timing comparisons) or the resident one; each with and without force arrays
+template <int SAMP, int FORCE>
+static void launch_note_loop_f(const NoteLoopArgs& a, bool split, bool streamed, dim3 grid, hipStream_t s) {
+  if (split) hipLaunchKernelGGL((note_loop2_kernel<SAMP, FORCE>), grid, dim3(512), 0, s, a);
+  else if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, SAMP, FORCE>), grid, dim3(256), 0, s, a);
+  else if (streamed) hipLaunchKernelGGL((note_loop_kernel<0, 2, SAMP, FORCE>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((note_loop_kernel<1, 2, SAMP, FORCE>), grid, dim3(256), 0, s, a);
+}
+template <int SAMP>
+static void launch_note_loop(const NoteLoopArgs& a, bool split, bool force, bool streamed, dim3 grid, hipStream_t s) {
+  if (force) launch_note_loop_f<SAMP, 1>(a, split, streamed, grid, s);
+  else launch_note_loop_f<SAMP, 0>(a, split, streamed, grid, s);
+}
+
 // w[16]: wg_h, wg_t, wp, wd_h, wd_p, wdur (packed bf16), b_hh_n, b_p, b_dh, b_hh_d, tab0, tab, w_out, b_out, w_embT, b_emb
 // train bit 23: io has a 22nd entry, the sampling block (inference only); without the bit io[21] is never read
 // train bit 24 (with bit 23): io[21] is the 48-byte block of a truncated sampled decode (top_k / min_p; philox.hpp SampleBlockT)
@@ -1675,31 +1736,12 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   // bench.py's roofline record of the step loop (tag 7): 15 note steps per launch; algorithmic MFMA work of a launch = 15 note steps x B rows x
   // (gate products 2*3Hn*(Hn+E) + pitch head 2*130*Hn + dur_hid 2*64*(Hn+130) + 5 duration steps 2*3*64*64 + token embedding 2*128*135)
   const int pi = prof::want(7, B, FHN) ? prof::begin((hipStream_t)stream) : -1;
-  if (!split) {
-    const dim3 grid(a.S > 1 ? (panels + 7) / 8 * 8 * a.S : panels);
-    if (cons) {
-      if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((note_loop_kernel<1, 2, 3>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    }
-    else if (trunc) {
-      if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((note_loop_kernel<1, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    }
-    else if (samp) {
-      if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((note_loop_kernel<1, 2, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    }
-    else if (a.S == 8) hipLaunchKernelGGL((note_loop_kernel<1, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    else if (train & 0x200000) hipLaunchKernelGGL((note_loop_kernel<0, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);   // bit 21: head weights streamed (timing comparisons)
-    else hipLaunchKernelGGL((note_loop_kernel<1, 2>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  }
-  else if (cons) hipLaunchKernelGGL((note_loop2_kernel<3>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
-  else if (trunc) hipLaunchKernelGGL((note_loop2_kernel<2>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
-  else if (samp) hipLaunchKernelGGL((note_loop2_kernel<1>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((note_loop2_kernel<0>), dim3(panels), dim3(512), 0, (hipStream_t)stream, a);
+  const dim3 grid(split ? panels : a.S > 1 ? (panels + 7) / 8 * 8 * a.S : panels);
+  const bool force = a.force_pitch || a.force_dur;               // the FORCE instantiations: replay mode / kept steps
+  if (cons) launch_note_loop<3>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
+  else if (trunc) launch_note_loop<2>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
+  else if (samp) launch_note_loop<1>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
+  else launch_note_loop<0>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
   if (pi >= 0) prof::end(pi, (hipStream_t)stream, 15.0 * B * (2.0 * 3 * FHN * (FHN + 128) + 2.0 * 130 * FHN + 2.0 * 64 * (FHN + 130) + 5 * 2.0 * 3 * 64 * 64 + 2.0 * 128 * 135));
   PTV_CHECK_LAUNCH();
   return PTV_OK;

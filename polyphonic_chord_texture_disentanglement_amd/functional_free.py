@@ -11,6 +11,7 @@ teacher-forced path; token gradients are routed to the ground-truth embedding or
 buffer (whose gradient reaches `note_embedding` and, through the re-summarising bi-GRU,
 `dec_notes_emb_gru`) -- never into the logits that produced the argmax.
 """
+import collections
 import contextlib
 import os
 
@@ -169,6 +170,72 @@ def check_constraints(pitch_mask=None, ascending=None, batch=None):
         if pitch_mask.shape[0] == 1:
             flags |= CONS_MASK_ROW1
     return flags
+
+
+class Keep(collections.namedtuple('Keep', 'pitch dur err batch')):
+    """the kept time steps of a free-running decode as its force arrays on the device (ptv_keep_force_build; INTEGRATION.md "Kept steps"):
+    pitch int32 [15, 32 B], dur int32 [5, 480 B] (>= 0: the decision is forced to that value, negative: free), err int32 [B] (bit 0: a kept
+    step held a pitch outside 0..129 before its <eos> -- that decision stays free), batch = B"""
+    __slots__ = ()
+
+
+def keep_steps_row(steps):
+    """a host selection of time steps (an iterable of indices 0..31, or a slice) -> 32 bytes, one per step -- ValueError for anything else"""
+    row = bytearray(32)
+    if isinstance(steps, slice):
+        steps = range(*steps.indices(32))
+    try:
+        items = list(steps)
+    except TypeError:
+        raise ValueError('steps must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice, got %r'
+                         % (steps,)) from None
+    for t in items:
+        if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 32:
+            raise ValueError('a kept time step must be an integer in 0..31, got %r' % (t,))
+        row[t] = 1
+    return bytes(row)
+
+
+def build_keep(x, steps):
+    """(x int64 device [B, 32, 16, 6] in the model's grid layout, steps) -> Keep; steps: a device bool / uint8 tensor [B, 32] or [1, 32], or
+    a host selection (keep_steps_row) that becomes one [1, 32] row.  ValueError before any launch; nothing is copied to the host."""
+    if not torch.is_tensor(x) or x.device.type != 'cuda':
+        raise ValueError('x must be a device tensor: the grid int64 [B, 32, 16, 6]')
+    if x.dtype != torch.int64 or x.dim() != 4 or tuple(x.shape[1:]) != (32, 16, 6) or x.shape[0] < 1:
+        raise ValueError('x must be int64 [B, 32, 16, 6], got %s %s' % (x.dtype, tuple(x.shape)))
+    B = x.shape[0]
+    if torch.is_tensor(steps):
+        if steps.device.type != 'cuda':
+            raise ValueError('steps must be a device tensor (or a host iterable of step indices / a slice)')
+        if steps.dtype not in (torch.bool, torch.uint8):
+            raise ValueError('steps must be bool or uint8, got %s' % (steps.dtype,))
+        if steps.dim() != 2 or steps.shape[1] != 32 or steps.shape[0] not in (1, B):
+            raise ValueError('steps must have shape [B, 32] or [1, 32] with B = %d, got %s' % (B, tuple(steps.shape)))
+        steps = steps.contiguous()
+        steps = steps.view(torch.uint8) if steps.dtype == torch.bool else steps
+    else:
+        steps = torch.frombuffer(bytearray(keep_steps_row(steps)), dtype=torch.uint8).view(1, 32).to(x.device)
+    x = x.contiguous()
+    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=x.device)
+    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=x.device)
+    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    call('ptv_keep_force_build', ptr(x), ptr(steps), steps.shape[0], B, ptr(pitch), ptr(dur), ptr(err), stream_ptr())
+    return Keep(pitch, dur, err, B)
+
+
+def check_keep(keep, batch=None):
+    """ValueError unless keep is None or a Keep whose arrays fit its batch (and `batch`, the rows of the decode, where the caller knows them)"""
+    if keep is None:
+        return
+    if not isinstance(keep, Keep):
+        raise ValueError('keep must be what DisentangleVAE.keep(x, steps) returns, got %r' % (type(keep).__name__,))
+    B = keep.batch
+    for name, t_, shape in (('pitch', keep.pitch, (15, 32 * B)), ('dur', keep.dur, (5, 480 * B))):
+        if (not torch.is_tensor(t_) or t_.device.type != 'cuda' or t_.dtype != torch.int32 or tuple(t_.shape) != shape
+                or not t_.is_contiguous()):
+            raise ValueError('keep.%s must be a contiguous int32 device tensor %s' % (name, list(shape)))
+    if batch is not None and B != batch:
+        raise ValueError('keep was built for a batch of %d, the decoded batch has %d rows' % (B, batch))
 
 
 def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None,

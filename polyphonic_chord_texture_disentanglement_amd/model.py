@@ -368,11 +368,13 @@ class DisentangleVAE(PytorchModel):
     # is the constrained ARGMAX (the draw counter does not advance; seed / draw / sample_offset stay a ValueError).
     @staticmethod
     def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
-                        top_p=None, pitch_mask=None, ascending=None, batch=None):
+                        top_p=None, pitch_mask=None, ascending=None, keep=None, batch=None):
         """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode (constrained or not).  No side
-        effect, no launch.  batch: the rows of the decoded batch where the caller knows them (pitch_mask's row count is held to it)"""
-        from .functional_free import check_constraints, check_sampling
+        effect, no launch.  batch: the rows of the decoded batch where the caller knows them (pitch_mask's row count and keep's batch are
+        held to it)"""
+        from .functional_free import check_constraints, check_keep, check_sampling
         check_constraints(pitch_mask, ascending, batch)
+        check_keep(keep, batch)
         if temperature is None and dur_temperature is None:
             if seed is not None or draw is not None or sample_offset is not None:
                 raise ValueError('seed / draw / sample_offset belong to a sampled decode: give a temperature')
@@ -383,12 +385,21 @@ class DisentangleVAE(PytorchModel):
                        0 if draw is None else draw, top_k=top_k, min_p=min_p, top_p=top_p)
         return True
 
+    def _check_decode(self, sampling, batch):
+        """_check_sampling of a decode's keywords, and what only this model knows: kept steps and the decoder's replay mode exclude each
+        other.  ValueError before anything is encoded or launched."""
+        sampled = self._check_sampling(**sampling, batch=batch)
+        if sampling.get('keep') is not None and self.decoder.force_trace is not None:
+            raise ValueError('keep cannot be combined with decoder.force_trace: both fill the force arrays')
+        return sampled
+
     def _sampling_words(self, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
-                        top_p=None, pitch_mask=None, ascending=None, batch=None):
-        """None (argmax decode) or the validated sampling block as host words -- ValueError for a bad value before anything is launched"""
+                        top_p=None, pitch_mask=None, ascending=None, keep=None, batch=None):
+        """None (argmax decode) or the validated sampling block as host words -- ValueError for a bad value before anything is launched
+        (keep puts nothing into the block: it travels beside it)"""
         from .functional_free import sampling_words
         if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset, top_k, min_p, top_p, pitch_mask, ascending,
-                                    batch):
+                                    keep, batch):
             if pitch_mask is None and ascending is None:
                 return None
             return sampling_words(0.0, 0.0, 0, 0, 0, pitch_mask=pitch_mask, ascending=ascending)   # the constrained argmax: no noise, no draw used
@@ -403,7 +414,8 @@ class DisentangleVAE(PytorchModel):
     def _decode(self, z_chd, z_rhy, sampling):
         """the free-running decode of both inference forms; `sampling`: keywords of a sampled decode"""
         from .ptvae import _require_cuda
-        self._check_sampling(**sampling, batch=z_chd.shape[0])
+        self._check_decode(sampling, z_chd.shape[0])
+        keep = sampling.get('keep')
         mask = sampling.get('pitch_mask')
         if mask is not None:
             mask = mask.contiguous()                                    # (the block holds its address)
@@ -416,7 +428,19 @@ class DisentangleVAE(PytorchModel):
         block = None if words is None else torch.tensor(words, dtype=torch.int64, device=dec_z.device)
         if block is not None and len(words) == 8:
             block.pitch_mask = mask
-        return self.decoder(dec_z, True, None, None, 0., 0., sampling=block)
+        if keep is not None:
+            _require_cuda(dec_z, 'DisentangleVAE decode with kept steps')
+        return self.decoder(dec_z, True, None, None, 0., 0., sampling=block, keep=keep)
+
+    def keep(self, x, steps):
+        """The kept time steps of a decode -> functional_free.Keep(pitch, dur, err, batch) for keep= (ptv_keep_force_build; INTEGRATION.md
+        "Kept steps").  x: int64 device tensor [B, 32, 16, 6], the model's grid (what decode_to_inputs, the dataset path and synth_batch
+        give); steps: a device bool / uint8 tensor [B, 32] or [1, 32], or a host iterable of step indices / a slice (one row for every
+        sample: range(16) = the first bar).  The notes of a kept step up to its <eos> are forced where the decoder takes its decisions
+        and fed back like decisions; everything else is decided as without it.  err[b] bit 0: a kept step of sample b held a pitch outside
+        0..129 before its <eos>; that decision stays free.  Nothing is copied to the host."""
+        from .functional_free import build_keep
+        return build_keep(x, steps)
 
     def pitch_mask(self, c=None, pitch_classes=None, lo=None, hi=None, batch=None):
         """int32 device tensor [B, 32, 4] for pitch_mask= (ptv_pitch_mask_build): bit p & 31 of word p >> 5 of [b, t] set = grid pitch p
@@ -458,28 +482,31 @@ class DisentangleVAE(PytorchModel):
         return out
 
     def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None,
-                         top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None):
+                         top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None, keep=None):
+        self._check_decode(dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset,
+                                top_k=top_k, min_p=min_p, top_p=top_p, pitch_mask=pitch_mask, ascending=ascending, keep=keep),
+                           z_chd.shape[0])
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
             self._decode(z_chd, z_rhy, dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw,
                                             sample_offset=sample_offset, top_k=top_k, min_p=min_p, top_p=top_p,
-                                            pitch_mask=pitch_mask, ascending=ascending))
+                                            pitch_mask=pitch_mask, ascending=ascending, keep=keep))
             est_x = self.decoder.last_xhat[:, :, 1:, :].cpu().numpy()
         return est_x
 
     # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
-                         sample_offset=None, top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None):
+                         sample_offset=None, top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None, keep=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
         inference_decode's (the chord decoder keeps its argmax)."""
         from .ptvae import _require_cuda
         sampling = dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset,
-                        top_k=top_k, min_p=min_p, top_p=top_p, pitch_mask=pitch_mask, ascending=ascending)
-        self._check_sampling(**sampling, batch=z_chd.shape[0])          # (bad values are a ValueError whatever device the inputs are on)
+                        top_k=top_k, min_p=min_p, top_p=top_p, pitch_mask=pitch_mask, ascending=ascending, keep=keep)
+        self._check_decode(sampling, z_chd.shape[0])                    # (bad values are a ValueError whatever device the inputs are on)
         _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')
         self.eval()
@@ -501,7 +528,7 @@ class DisentangleVAE(PytorchModel):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant; **sampling: the keywords of a sampled
         decode (inference_decode), here and in swap / posterior_sample / prior_sample / interp -- a bad value is a ValueError before
         anything is encoded"""
-        self._check_sampling(**sampling, batch=pr_mat.shape[0])
+        self._check_decode(sampling, pr_mat.shape[0])
         if self.detrended:
             self._check_dt_x(pr_mat)                     # (a piano-roll here is a ValueError, not a shape crash inside a kernel)
         self.eval()
@@ -523,7 +550,7 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:150-172
     def posterior_sample(self, pr_mat, c, scale=None, sample_chd=True, sample_txt=True, **sampling):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
-        self._check_sampling(**sampling, batch=pr_mat.shape[0])
+        self._check_decode(sampling, pr_mat.shape[0])
         if scale is None and sample_chd and sample_txt:
             return self.inference(pr_mat, c, sample=True, **sampling)
         dist_chd, dist_rhy = self.inference_encode(pr_mat, c)
@@ -544,7 +571,7 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:174-184
     def prior_sample(self, x, c, sample_chd=False, sample_rhy=False, scale=1., **sampling):
         """x: the texture encoder's input (the reference's name for this slot here) -- the piano-roll, or dt_x for the detrended variant"""
-        self._check_sampling(**sampling, batch=x.shape[0])
+        self._check_decode(sampling, x.shape[0])
         dist_chd, dist_rhy = self.inference_encode(x, c)
         mean = torch.zeros_like(dist_rhy.mean)
         loc = torch.ones_like(dist_rhy.mean) * scale
@@ -564,7 +591,7 @@ class DisentangleVAE(PytorchModel):
     def interp(self, pr_mat1, c1, pr_mat2, c2, interp_chd=False, interp_rhy=False, int_count=10, **sampling):
         """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant; a sampled decode's sample
         index is the row of the flattened [bs * int_count] batch, and so are the rows of a pitch_mask (or it has one row)"""
-        self._check_sampling(**sampling, batch=pr_mat1.shape[0] * int_count)
+        self._check_decode(sampling, pr_mat1.shape[0] * int_count)
         dist_chd1, dist_rhy1 = self.inference_encode(pr_mat1, c1)
         dist_chd2, dist_rhy2 = self.inference_encode(pr_mat2, c2)
         z_chd1, z_rhy1, z_chd2, z_rhy2 = dist_chd1.mean, dist_rhy1.mean, dist_chd2.mean, dist_rhy2.mean

@@ -283,7 +283,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         sd = dict(self.named_parameters())
         return [sd[n] for n in F_.DEC_PARAM_NAMES]
 
-    def _graph_decode(self, z, coins, sampling=None):
+    def _graph_decode(self, z, coins, sampling=None, keep=None):
         """Free-running decode replayed from a captured hipGraph: the step loop is ~9,000 tiny launches whose
         order and arguments depend only on (B, precision) -- capture once, then one graph launch per call.
         The graph holds raw parameter pointers, so it is re-captured if the parameter storage moves.
@@ -292,14 +292,17 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         top_p) is a third kind: the key gains that one bit, the values of top_k / min_p / top_p live in the block like seed and draw --
         one capture serves them all.  A constrained decode (an 8-word block: pitch_mask / ascending) is a fourth kind: its mask is copied
         into a static tensor before every replay and the static block's address word points at that tensor, so one capture serves every
-        mask, flag, seed and draw."""
+        mask, flag, seed and draw.  A decode with kept steps (keep: functional_free.Keep) doubles the kinds: the key gains one bit beside the
+        kind, the capture holds static force arrays into which the caller's are copied before every replay, so one capture serves every
+        keep; without a keep the keys and the graphs are what they were."""
         ps = self._params_free()
         kind = 0 if sampling is None else {4: 1, 6: 2, 8: 3}[sampling.numel()]
-        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind)
+        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind) + ((True,) if keep is not None else ())
         ent = self._graphs.get(key)
         if ent is None:
             static_z = z.detach().clone()
             static_mask = mask_addr = None
+            static_force = None if keep is None else {'pitch': keep.pitch.clone(), 'dur': keep.dur.clone()}
             if sampling is not None:
                 ps = ps + [sampling.clone()]
                 if kind == 3:                                  # (captured with every pitch allowed; the flags are the first caller's)
@@ -315,17 +318,20 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             s = self._graph_stream = self._graph_stream or torch.cuda.Stream(device=z.device)
             s.wait_stream(cur)
             with torch.cuda.stream(s):                         # warm-up outside capture (lazy inits, allocator)
-                FF_.DecoderStepFn.apply(static_z, None, None, coins, True, None, self._prec, *ps)
+                FF_.DecoderStepFn.apply(static_z, None, None, coins, True, static_force, self._prec, *ps)
             cur.wait_stream(s)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
-                outs = FF_.DecoderStepFn.apply(static_z, None, None, coins, True, None, self._prec, *ps)
-            for k in [k for k in self._graphs if k[-1] == key[-1]]:         # one graph per kind (argmax, sampled, truncated, constrained) is kept
-                del self._graphs[k]
+                outs = FF_.DecoderStepFn.apply(static_z, None, None, coins, True, static_force, self._prec, *ps)
+            for k in [k for k in self._graphs if k[4:] == key[4:]]:         # one graph per kind (argmax, sampled, truncated, constrained; each
+                del self._graphs[k]                                         # with and without kept steps) is kept
             self.graph_captures += 1
-            ent = self._graphs[key] = (g, static_z, outs, ps[-1] if sampling is not None else None, static_mask, mask_addr)
-        g, static_z, outs, static_blk, static_mask, mask_addr = ent
+            ent = self._graphs[key] = (g, static_z, outs, ps[-1] if sampling is not None else None, static_mask, mask_addr, static_force)
+        g, static_z, outs, static_blk, static_mask, mask_addr, static_force = ent
         static_z.copy_(z)
+        if static_force is not None:
+            static_force['pitch'].copy_(keep.pitch)
+            static_force['dur'].copy_(keep.dur)
         if static_blk is not None:
             static_blk.copy_(sampling)
             if static_mask is not None and sampling.pitch_mask is not None:
@@ -375,13 +381,23 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
                 time.append(random.random() < tfr1)
         return notes, time
 
-    def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None):
+    def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None,
+                keep=None):
         """sampling: None (argmax decisions) or a block of functional_free.sampling_block() -- the decisions of the free-running decode
         are then seeded draws from softmax(logits / T), with top_k / min_p / top_p in the block over the truncated support of the pitch row,
         and with pitch_mask / ascending over the allowed classes only (temperature 0: the constrained argmax);
-        inference only (ValueError otherwise, before any launch)"""
+        inference only (ValueError otherwise, before any launch).
+        keep: None or a functional_free.Keep (DisentangleVAE.keep) -- the decisions of its kept time steps are forced where they are taken,
+        so they reach the following steps as if decided; everything else is decided as without it.  Its rows are the rows of z.  Inference
+        only, and not together with force_trace (ValueError before any launch)"""
         if sampling is not None and (not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None):
             raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
+        if keep is not None:
+            if not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None:
+                raise ValueError('keep is inference only: it cannot be combined with training or teacher forcing')
+            FF_.check_keep(keep, z.size(0))
+            if self.force_trace is not None:
+                raise ValueError('keep cannot be combined with force_trace: both fill the force arrays')
         _require_cuda(z, 'PtvaeDecoder')
         B = z.size(0)
         if inference:
@@ -389,10 +405,11 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             assert teacher_forcing_ratio1 == 0 and teacher_forcing_ratio2 == 0
             coins = ([[False] * (self.max_simu_note - 2)] * self.num_step, [False] * (self.num_step - 1))
             smp = () if sampling is None else (FF_._check_block(sampling, z.device, B),)
+            force = self.force_trace if keep is None else {'pitch': keep.pitch, 'dur': keep.dur}
             if self.use_graph and not torch.is_grad_enabled() and self.force_trace is None:
-                pitch, dur, xhat, idx = self._graph_decode(z, coins, sampling)
+                pitch, dur, xhat, idx = self._graph_decode(z, coins, sampling, keep)
             else:
-                pitch, dur, xhat, idx = FF_.DecoderStepFn.apply(z, None, None, coins, True, self.force_trace, self._prec,
+                pitch, dur, xhat, idx = FF_.DecoderStepFn.apply(z, None, None, coins, True, force, self._prec,
                                                                 *self._params_free(), *smp)
             self.last_dur_idx, self.last_xhat = idx, xhat
             return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
@@ -432,8 +449,10 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         # reference shapes [B,32,15,130] / [B,32,15,5,2] as permuted views of the step-major buffers
         return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
 
-    def forward(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None):
-        return self.decoder(z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=coins, live=live, sampling=sampling)
+    def forward(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None,
+                keep=None):
+        return self.decoder(z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=coins, live=live, sampling=sampling,
+                            keep=keep)
 
     # ---- the reference's helper METHODS (ptvae.py:292-428), callable by reference-side code.  Forward-only entry points onto the
     # kernels the fused path runs (`decoder()` never calls them: it runs DecoderTFFn / DecoderStepFn); results carry no autograd graph.

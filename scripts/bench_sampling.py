@@ -6,9 +6,12 @@ the 32-round select on integer masses), the nucleus rows -- top_p alone and top_
 The constrained rows (pitch masks / ascending notes: one 16-byte mask load per row and launch, a few integer operations per class) are
 the chord-tone mask of a synthetic batch's c, `ascending`, and both with top_k + top_p; they are reported against the plain sampled
 decode of the same process.
+The keep rows (kept time steps, keep=: six force words per row and note step, one select per decision) decode the same batch with the
+first bar of a synthetic grid kept under plain sampling, and with a per-row alternating pattern ((t + b) % 4 < 2) kept under mask +
+ascending + top_k + top_p; each is reported against the same setting without a keep.
 
     python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--top-k 8] [--min-p 0.9] [--top-p 0.9]
-                                     [--constrained 1] [--eager]
+                                     [--constrained 1] [--keep 1] [--eager]
 
 --top-k 0, --min-p 0 and --top-p 0 switch the rule off; with top_k and min_p both off the 'truncated' decode is not timed, with top_p
 off the two nucleus rows are not; --constrained 0 leaves the constrained rows out.
@@ -35,6 +38,7 @@ def main():
     ap.add_argument('--min-p', type=float, default=0.9, help='0 = off')
     ap.add_argument('--top-p', type=float, default=0.9, help='0 = off')
     ap.add_argument('--constrained', type=int, default=1, help='0 = no constrained rows')
+    ap.add_argument('--keep', type=int, default=1, help='0 = no keep rows')
     ap.add_argument('--eager', action='store_true', help='no graph replay')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the MI355X'
@@ -61,6 +65,16 @@ def main():
         constrained['ascending'] = dict(ascending=True)
         constrained['mask+ascending+top_k+top_p'] = dict(pitch_mask=mask, ascending=True, top_k=a.top_k or None, top_p=a.top_p or None)
     kinds += list(constrained)
+    keeps = {}                                               # kind -> (the kind it is compared with, its Keep)
+    if a.keep:
+        from polyphonic_chord_texture_disentanglement_amd.synthetic import synth_batch
+        rows = torch.arange(a.batch, device=dev)
+        x = torch.from_numpy(synth_batch(64, 5)[0]).to(dev)[rows % 64].contiguous()          # [batch, 32, 16, 6]
+        keeps['keep first bar'] = ('sampled', m.keep(x, range(16)))
+        if a.constrained:
+            alt = ((torch.arange(32, device=dev)[None, :] + rows[:, None]) % 4 < 2)
+            keeps['keep alternating+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.keep(x, alt))
+    kinds += list(keeps)
     blocks = {'argmax': [None] * (a.rounds + 1),
               'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
               'truncated': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **trunc) for d in range(a.rounds + 1)]}
@@ -69,32 +83,35 @@ def main():
     for k, kw in constrained.items():
         blocks[k] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **kw) for d in range(a.rounds + 1)]
 
-    def run(block):
-        with torch.no_grad():
-            m.decoder(z, True, None, None, 0., 0., sampling=block)
+    for k, (base, _) in keeps.items():
+        blocks[k] = blocks[base]
 
-    def timed(block):
+    def run(block, keep=None):
+        with torch.no_grad():
+            m.decoder(z, True, None, None, 0., 0., sampling=block, keep=keep)
+
+    def timed(block, keep=None):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.reps):
-            run(block)
+            run(block, keep)
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.reps
 
     for _ in range(2):                                       # warm-up: every graph captured, allocator settled
         for k in kinds:
-            run(blocks[k][-1])
+            run(blocks[k][-1], keeps[k][1] if k in keeps else None)
     torch.cuda.synchronize()
     captures = m.decoder.graph_captures
     ms = {k: [] for k in kinds}
     for r in range(a.rounds):                                # interleaved: drift of the box hits all alike
         for k in kinds:
-            ms[k].append(timed(blocks[k][r]))
+            ms[k].append(timed(blocks[k][r], keeps[k][1] if k in keeps else None))
     assert m.decoder.graph_captures == captures              # a new draw is not a new capture
     rate = {k: [round(a.batch / (v * 1e-3), 1) for v in vs] for k, vs in ms.items()}
     best = {k: max(v) for k, v in rate.items()}
-    out = {'what': 'free-running decode: argmax, sampled, truncated-sampled, nucleus-sampled and constrained decisions', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
+    out = {'what': 'free-running decode: argmax, sampled, truncated-sampled, nucleus-sampled and constrained decisions, kept steps', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
            'temperature': a.temperature, 'top_k': a.top_k, 'min_p': a.min_p, 'top_p': a.top_p, 'ms_per_decode': {k: [round(x, 3) for x in v] for k, v in ms.items()},
            'samples_per_s': rate, 'sampled_over_argmax_best': round(best['sampled'] / best['argmax'], 4)}
     if 'truncated' in kinds:
@@ -102,6 +119,9 @@ def main():
         out['truncated_over_argmax_best'] = round(best['truncated'] / best['argmax'], 4)
     for k in list(nucleus) + list(constrained):
         out[k + '_over_sampled_best'] = round(best[k] / best['sampled'], 4)
+    for k, (base, _) in keeps.items():
+        out[k + '_over_' + base + '_best'] = round(best[k] / best[base], 4)
+        out[k + '_over_' + base + '_by_round'] = [round(x / y, 4) for x, y in zip(rate[k], rate[base])]
     out['device'] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
 
