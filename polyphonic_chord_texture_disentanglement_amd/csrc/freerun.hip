@@ -1725,6 +1725,7 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   const int S = (train & 0x400000) ? 8 : ((train >> 18) & 7);     // (bit 22: eight members)
   const bool split = (train & 0x20000) || (!(train & 0x10000) && panels >= 96 && S <= 1);      // (a cluster request means the 4-wave kernel)
   a.S = 1;
+  if (S > 1 && (train & 0x20000)) return PTV_ERR_ARG;            // a cluster is made of 4-wave workgroups: the two requests contradict each other
   if (S > 1) {
     // (round 4: up to one member per CU -- 64 panels x 4 members at B = 1024, the per-GPU batch of BASELINE configs[4]; the launch takes
     // its turn among the persistent launches, so nothing else that spins is resident beside it)
