@@ -832,6 +832,44 @@ int ptv_chord_step_scores(const float* root, const float* chroma, const float* b
 int ptv_roll_match(const float* est_pr, const float* ref_pr, int B, int* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Log-probabilities of a free-running decode and best-of-n (csrc/decode_score.hip; DESIGN.md 7e, INTEGRATION.md "Decode log-probabilities").
+ * A post-pass over what a decode leaves on the device; forward only, no atomics, no workspace: every output element has one writer and one
+ * fixed summation order, so the results are bit-identical from run to run, across the two row orders and across the load paths.
+ * ptv_decode_logprob: one wave per (sample b, time step t).
+ *   pitch / ld_pitch / step_major / dur: the plain logits a decode wrote, rows and load rule as ptv_recon_step_scores (row of (b, t, n) =
+ *     (n*32 + t)*B + b if step_major else (b*32 + t)*15 + n; 16-byte loads iff ld_pitch % 4 == 0, ld_pitch >= 132 and the base is 16-byte
+ *     aligned, else 4-byte loads of the same classes); xhat: the decided grid int64 [B][32][16][6].
+ *   sample / sample_bytes: NULL / 0 (an argmax decode) or the decode's sampling block of 32, 48 or 64 bytes ("Sampled decode" above);
+ *     anything else is PTV_ERR_ARG.  force_pitch [15][32B] / force_dur [5][480B] (ptv_keep_force_build's layout), or NULL, each on its own.
+ *   What counts: for (b, t) L = the first slot s in 1..15 with xhat[b][t][s][0] == 129, else 15 (ptv_keep_force_build's rule).  The pitch
+ *     decisions of the note steps n = 0..L-1 count (the <eos> among them); the five duration bits of those notes whose pitch is < 128
+ *     count.  Logit rows and bits that do not count are never loaded.  A counted pitch outside 0..129 or a counted bit outside {0, 1}
+ *     names no class: it is skipped (not counted), and the pitch sets bit 0 of err[b].
+ *   For a counted decision with decided class d:
+ *     logp = log softmax(logits)[d] over all 130 classes (both classes of a bit): temperature 1, no truncation, no constraint; forced
+ *       decisions included.
+ *     logq = the log-probability under the distribution the decode drew from.  Pitch: (v[d] - m) / T_pitch - log sum exp((v - m) /
+ *       T_pitch) over the classes that are allowed and kept, m their maximum -- the set is the decoder's own (pitch_constrain and
+ *       pitch_keep_threshold of csrc/philox.hpp on the block's mask row, flags, top_k, ln_min_p, top_p_q24, with lo = the largest decided
+ *       pitch < 128 before n in the step).  Bit: log softmax of the pair divided by T_dur.  0 when the temperature is 0 or sample is NULL
+ *       (the argmax is certain).  A forced decision (force word >= 0) contributes 0 and is counted in forced_*.  A free decision outside
+ *       the recomputed set sets bit 0 of err[b] and contributes 0: it never happens on a decode's own outputs.
+ *   step_logp [B][32][4] f32 = (logp pitch, logp dur, logq pitch, logq dur), each added over ascending n, a note's pitch term before its
+ *     bits (ascending); step_counts [B][32][4] int32 = (pitch_n, dur_n, forced_pitch_n, forced_dur_n); err [B] int32.
+ * ptv_decode_logprob_fold: sums [B][4] f32 / counts [B][4] int32 = the sums over t = 0..31 in ascending order (fp32, sequential).
+ * ptv_best_of_gather: score f32 [n][B], grids int64 [n*B][32][16][6], sums f32 [n*B][4], candidate k of row b at row k*B + b ->
+ *   best [B] int32 = the first k whose score is maximal (a NaN never wins; all NaN: k = 0 and err[b] = 2, else err[b] = 0),
+ *   out_grid [B][32][16][6] = grids[best*B + b], out_sums [B][4] = sums[best*B + b].
+ * All three return PTV_ERR_ARG for a NULL pointer (those marked optional excepted), B < 1 or n < 1 and write nothing then.
+ */
+int ptv_decode_logprob(const float* pitch, long ld_pitch, const float* dur, const long* xhat, int B, int step_major, const void* sample,
+                       int sample_bytes, const int* force_pitch, const int* force_dur, float* step_logp, int* step_counts, int* err,
+                       void* stream);
+int ptv_decode_logprob_fold(const float* step_logp, const int* step_counts, int B, float* sums, int* counts, void* stream);
+int ptv_best_of_gather(const float* score, const long* grids, const float* sums, int n, int B, int* best, long* out_grid, float* out_sums,
+                       int* err, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Note-matrix song bank on device (csrc/dataset.hip): what ArrangementDataset.__getitem__ does BEFORE the data contract above, from
  * the per-bar note matrices (dataset.py:67-93 over converter.py:35-76), and detrend_pianotree (dataset.py:123-213) after it.
  * Bank: the bars of all songs in order.  acc_rec / mel_rec hold one 32-bit record per note, bar after bar, acc_off / mel_off [n_bar+1]

@@ -498,11 +498,13 @@ class DisentangleVAE(PytorchModel):
     # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
-                         sample_offset=None, top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None, keep=None):
+                         sample_offset=None, top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None, keep=None,
+                         return_logprob=False):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
-        inference_decode's (the chord decoder keeps its argmax)."""
+        inference_decode's (the chord decoder keeps its argmax).  return_logprob=True appends the decode's log-probabilities
+        (PtvaeDecoder.decode_logprob: a DecodeLogprob of device tensors) as a seventh element."""
         from .ptvae import _require_cuda
         sampling = dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset,
                         top_k=top_k, min_p=min_p, top_p=top_p, pitch_mask=pitch_mask, ascending=ascending, keep=keep)
@@ -515,7 +517,74 @@ class DisentangleVAE(PytorchModel):
             self._decode(z_chd, z_rhy, sampling)
             pr_mat, notes, count, x, err = self.decoder.grid_to_pr_and_notes_batch(self.decoder.last_xhat, max_notes)
             c, _ = self.chd_decoder.decode_tokens(z_chd)
+            if return_logprob:
+                return pr_mat, x, c, notes, count, err, self.decoder.decode_logprob()
         return pr_mat, x, c, notes, count, err
+
+    def decode_logprob(self, z_chd, z_rhy, max_notes=10, **sampling):
+        """decode_to_inputs' tuple plus the log-probabilities of that decode (INTEGRATION.md "Decode log-probabilities"): a
+        DecodeLogprob(logp [B,2], logq [B,2], counts [B,4], err [B], step_logp [B,32,4], step_counts [B,32,4]) of device tensors --
+        log p under the model's own softmax and log q under the distribution the decode drew from, (pitch, duration) sums over the
+        decisions taken.  **sampling: the keywords of a sampled decode (inference_decode)."""
+        return self.decode_to_inputs(z_chd, z_rhy, max_notes, return_logprob=True, **sampling)
+
+    @staticmethod
+    def _check_best_of(n, rank_by='logp', length_normalize=False, temperature=None, dur_temperature=None, **_):
+        """ValueError for a bad decode_best_of argument; no side effect, no launch"""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError('n must be an integer >= 1, got %r' % (n,))
+        if rank_by not in ('logp', 'logq'):
+            raise ValueError("rank_by must be 'logp' or 'logq', got %r" % (rank_by,))
+        if not isinstance(length_normalize, bool):
+            raise ValueError('length_normalize must be a bool, got %r' % (length_normalize,))
+        if temperature is None and dur_temperature is None:
+            raise ValueError('decode_best_of ranks draws of a sampled decode: give a temperature (an argmax decode has one candidate)')
+
+    def decode_best_of(self, z_chd, z_rhy, n, *, rank_by='logp', length_normalize=False, max_notes=10, **sampling):
+        """n sampled decodes of every row, the best of them by log-probability (INTEGRATION.md "Best of n") -> decode_to_inputs' tuple of
+        the winners plus (best int32 [B], sums f32 [B,4] = the winner's (logp pitch, logp dur, logq pitch, logq dur)); all on the device.
+        The batch is tiled n times: candidate k of row b is row k*B + b and draws the noise of global sample sample_offset + k*B + b, so
+        the candidates are bit-equal to a plain decode of the tiled batch with the same keywords; a pitch_mask or keep with B rows is
+        tiled alike.  rank_by: 'logp' (the model's own probability of what was drawn) or 'logq' (the proposal's); length_normalize
+        divides the score by the number of counted decisions.  The first maximal candidate wins (ptv_best_of_gather); a NaN score never
+        wins.  err is the output path's, with two bits above it: bit 8 = a candidate of the row held a decision outside the recomputed kept
+        set (never on the decoder's own outputs), bit 9 = every score of the row was NaN (candidate 0 is returned).  A temperature
+        is required: without one there is one candidate."""
+        from .functional_free import Keep
+        from .ptvae import _require_cuda
+        from ._lib import call, ptr, stream_ptr
+        self._check_best_of(n, rank_by, length_normalize, **sampling)
+        B = z_chd.shape[0]
+        self._check_decode(sampling, B)
+        _require_cuda(z_chd, 'DisentangleVAE.decode_best_of')
+        _require_cuda(z_rhy, 'DisentangleVAE.decode_best_of')
+        tiled = dict(sampling)
+        mask, keep = sampling.get('pitch_mask'), sampling.get('keep')
+        if mask is not None and mask.shape[0] == B and B > 1:
+            tiled['pitch_mask'] = mask.repeat(n, 1, 1)
+        if keep is not None:
+            tiled['keep'] = Keep(keep.pitch.view(15, 32, 1, B).expand(15, 32, n, B).reshape(15, 32 * n * B),
+                                 keep.dur.view(5, 15, 32, 1, B).expand(5, 15, 32, n, B).reshape(5, 480 * n * B), keep.err.repeat(n), n * B)
+        self.eval()
+        refresh_weight_shadows()
+        with torch.no_grad():
+            self._decode(z_chd.repeat(n, 1), z_rhy.repeat(n, 1), tiled)
+            lp = self.decoder.decode_logprob()
+            sums = torch.cat([lp.logp, lp.logq], dim=1)
+            score = (lp.logp if rank_by == 'logp' else lp.logq).sum(1)
+            if length_normalize:
+                score = score / (lp.counts[:, 0] + lp.counts[:, 1]).clamp(min=1).float()
+            grids = self.decoder.last_xhat
+            dev = grids.device
+            best = torch.empty(B, dtype=torch.int32, device=dev)
+            berr = torch.empty(B, dtype=torch.int32, device=dev)
+            grid = torch.empty(B, 32, 16, 6, dtype=torch.int64, device=dev)
+            bsums = torch.empty(B, 4, dtype=torch.float32, device=dev)
+            call('ptv_best_of_gather', ptr(score.contiguous()), ptr(grids), ptr(sums), n, B, ptr(best), ptr(grid), ptr(bsums), ptr(berr),
+                 stream_ptr())
+            pr_mat, notes, count, x, err = self.decoder.grid_to_pr_and_notes_batch(grid, max_notes)
+            c, _ = self.chd_decoder.decode_tokens(z_chd)
+        return pr_mat, x, c, notes, count, err | ((berr | lp.err.view(n, B).amax(0)) << 8), best, bsums
 
     def reencode(self, z_chd, z_rhy, **sampling):
         """(dist_chd, dist_rhy) of the music decoded from (z_chd, z_rhy): decode_to_inputs, then inference_encode; **sampling: the

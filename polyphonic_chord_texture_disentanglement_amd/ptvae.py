@@ -9,6 +9,7 @@ module with CPU tensors raises.
 Reference: /root/reference/ptvae.py  (RnnEncoder :11-29, RnnDecoder :32-87, TextureEncoder :90-122,
 PtvaeEncoder :125-215, PtvaeDecoder :218-575).
 """
+import collections
 import math
 import os
 import random
@@ -232,6 +233,9 @@ def chord_tokens(root, chroma, bass):
     return c, chord14
 
 
+DecodeLogprob = collections.namedtuple('DecodeLogprob', 'logp logq counts err step_logp step_counts')
+
+
 class PtvaeDecoder(nn.Module, _PrecMixin):
     """PianoTree decoder (ptvae.py:218-575): time GRU (32) -> notes GRU (15) -> pitch head +
     5-step duration GRU."""
@@ -278,6 +282,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         self._summary = None
         self.summaries_needed = True       # emb_x() starts the ground-truth note summaries early unless told they are dead values
         self.last_dur_idx = None
+        self._last_decode = None           # (pitch, dur, xhat, sampling block, force arrays) of the last inference decode: decode_logprob()
 
     def _params(self):
         sd = dict(self.named_parameters())
@@ -412,6 +417,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
                 pitch, dur, xhat, idx = FF_.DecoderStepFn.apply(z, None, None, coins, True, force, self._prec,
                                                                 *self._params_free(), *smp)
             self.last_dur_idx, self.last_xhat = idx, xhat
+            self._last_decode = (pitch, dur, xhat, sampling, force)      # what decode_logprob() reads: references, nothing copied (an eager decode's logits live until the next decode)
             return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
         if coins is None:
             coins = self.draw_coins(teacher_forcing_ratio1, teacher_forcing_ratio2)
@@ -448,6 +454,35 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         self.last_dur_idx = idx
         # reference shapes [B,32,15,130] / [B,32,15,5,2] as permuted views of the step-major buffers
         return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
+
+    def decode_logprob(self):
+        """Log-probabilities of the LAST inference decode (ptv_decode_logprob + ptv_decode_logprob_fold; INTEGRATION.md "Decode
+        log-probabilities") -> DecodeLogprob(logp [B,2], logq [B,2], counts int32 [B,4], err int32 [B], step_logp [B,32,4],
+        step_counts int32 [B,32,4]): per sample the (pitch, duration) sums of log p -- the model's own softmax at the decided classes
+        -- and of log q -- the distribution the decode drew from (temperature, pitch_mask / ascending, top_k / min_p / top_p; 0 where
+        the decision was the argmax or forced by keep) --, counts = (pitch_n, dur_n, forced_pitch_n, forced_dur_n), err bit 0 = a free
+        decision outside the recomputed kept set (never on a decode's own outputs); step_logp = (logp pitch, logp dur, logq pitch,
+        logq dur) per time step.  A post-pass over the logits, grid, block and keep the decode left on the device: launched eagerly on
+        the current stream, never captured (graph keys and capture counts stay what they were); everything stays on the device.  The
+        tensors of a graph-replayed decode are the graph's own: call this before the next decode."""
+        last = self._last_decode
+        if last is None:
+            raise RuntimeError('decode_logprob() follows an inference decode: there is none yet')
+        pitch, dur, xhat, sampling, force = last
+        fp, fd = (None, None) if not force else (force.get('pitch'), force.get('dur'))
+        B, dev = xhat.shape[0], xhat.device
+        assert pitch.shape == (15, 32, B, 130) and pitch.stride(3) == 1 and pitch.stride(1) == B * pitch.stride(2) \
+            and pitch.stride(0) == 32 * B * pitch.stride(2) and dur.is_contiguous() and xhat.is_contiguous()
+        step_logp = torch.empty(B, 32, 4, device=dev, dtype=torch.float32)
+        step_counts = torch.empty(B, 32, 4, device=dev, dtype=torch.int32)
+        sums = torch.empty(B, 4, device=dev, dtype=torch.float32)
+        counts = torch.empty(B, 4, device=dev, dtype=torch.int32)
+        err = torch.empty(B, device=dev, dtype=torch.int32)
+        F_.call('ptv_decode_logprob', F_.ptr(pitch), pitch.stride(2), F_.ptr(dur), F_.ptr(xhat), B, 1, F_.ptr(sampling),
+                0 if sampling is None else 8 * sampling.numel(), F_.ptr(fp), F_.ptr(fd), F_.ptr(step_logp), F_.ptr(step_counts),
+                F_.ptr(err), F_.stream_ptr())
+        F_.call('ptv_decode_logprob_fold', F_.ptr(step_logp), F_.ptr(step_counts), B, F_.ptr(sums), F_.ptr(counts), F_.stream_ptr())
+        return DecodeLogprob(sums[:, 0:2], sums[:, 2:4], counts, err, step_logp, step_counts)
 
     def forward(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None,
                 keep=None):

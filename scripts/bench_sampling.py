@@ -9,9 +9,12 @@ decode of the same process.
 The keep rows (kept time steps, keep=: six force words per row and note step, one select per decision) decode the same batch with the
 first bar of a synthetic grid kept under plain sampling, and with a per-row alternating pattern ((t + b) % 4 < 2) kept under mask +
 ascending + top_k + top_p; each is reported against the same setting without a keep.
+The logprob rows (--logprob 1; PtvaeDecoder.decode_logprob, DisentangleVAE.decode_best_of) time the log-probability pass ALONE -- the two
+launches after a plain sampled decode, and after the mask + ascending + top_k + top_p decode, where every row also runs the allowed rule
+and both 32-round selects -- and decode_best_of(n=4) at a quarter of the batch (as many decoded rows as one plain decode of the batch).
 
     python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--top-k 8] [--min-p 0.9] [--top-p 0.9]
-                                     [--constrained 1] [--keep 1] [--eager]
+                                     [--constrained 1] [--keep 1] [--logprob 1] [--eager]
 
 --top-k 0, --min-p 0 and --top-p 0 switch the rule off; with top_k and min_p both off the 'truncated' decode is not timed, with top_p
 off the two nucleus rows are not; --constrained 0 leaves the constrained rows out.
@@ -39,6 +42,7 @@ def main():
     ap.add_argument('--top-p', type=float, default=0.9, help='0 = off')
     ap.add_argument('--constrained', type=int, default=1, help='0 = no constrained rows')
     ap.add_argument('--keep', type=int, default=1, help='0 = no keep rows')
+    ap.add_argument('--logprob', type=int, default=1, help='0 = no logprob / best-of rows')
     ap.add_argument('--eager', action='store_true', help='no graph replay')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the MI355X'
@@ -122,6 +126,38 @@ def main():
     for k, (base, _) in keeps.items():
         out[k + '_over_' + base + '_best'] = round(best[k] / best[base], 4)
         out[k + '_over_' + base + '_by_round'] = [round(x / y, 4) for x, y in zip(rate[k], rate[base])]
+    if a.logprob:
+        def timed_pass():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            m.decoder.decode_logprob()                       # (warm-up of the pass itself)
+            e0.record()
+            for _ in range(a.reps):
+                m.decoder.decode_logprob()
+            e1.record()
+            torch.cuda.synchronize()
+            return round(e0.elapsed_time(e1) / a.reps, 4)
+
+        lp = {}
+        full = 'mask+ascending+top_k+top_p'
+        for k in ['sampled'] + ([full] if full in blocks else []):
+            lp[k] = []
+            for r in range(a.rounds):
+                run(blocks[k][r])
+                lp[k].append(timed_pass())
+        out['logprob_pass_ms'] = lp
+        out['logprob_pass_over_sampled_decode'] = {k: round(min(v) / min(ms['sampled']), 5) for k, v in lp.items()}
+        nb, n = max(a.batch // 4, 1), 4
+        zc, zr = z[:nb, :256].contiguous(), z[:nb, 256:].contiguous()
+        bo = []
+        for r in range(a.rounds + 1):                        # (round 0: warm-up and the capture of the tiled batch, dropped)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(a.reps):
+                m.decode_best_of(zc, zr, n, temperature=a.temperature, seed=7, draw=r * a.reps + i)
+            e1.record()
+            torch.cuda.synchronize()
+            bo.append(round(e0.elapsed_time(e1) / a.reps, 3))
+        out['best_of_4_ms'] = {'batch': nb, 'decoded_rows': nb * n, 'ms_per_call': bo[1:]}
     out['device'] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
 
