@@ -13,8 +13,10 @@ buffer (whose gradient reaches `note_embedding` and, through the re-summarising 
 """
 import collections
 import contextlib
+import ctypes
+import math
 import os
-
+import struct
 import weakref
 
 import torch
@@ -28,11 +30,7 @@ FREE_PARAM_NAMES = DEC_PARAM_NAMES + ['note_embedding.weight', 'note_embedding.b
 EMB_GRU = ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0', 'weight_ih_l0_reverse', 'weight_hh_l0_reverse',
            'bias_ih_l0_reverse', 'bias_hh_l0_reverse')
 
-
 _SOS = {}
-
-
-
 _ROUTE_MASKS = {}
 
 
@@ -53,6 +51,7 @@ def _route_mask(key, dev):
             t_ = torch.tensor([1 if c else 0 for c in key[1]] + [1], dtype=torch.int32)
         m = _ROUTE_MASKS[k] = t_.to(dev)
     return m
+
 
 def _sos_grid(dev):
     """a [1,32,16,6] grid whose every row is <sos> (ptvae.py:315-320); cached so graph capture sees no H2D copy"""
@@ -103,11 +102,30 @@ CONS_BIT = 0x2000000            # ... io[21] is the 64-byte block (only together
 CONS_ASCENDING = 1              # flags bit 0: a pitch < 128 must exceed the largest pitch < 128 already decided in the time step; never <sos>
 CONS_MASK_ROW1 = 2              # flags bit 1: the mask has one row [32, 4] for the whole batch
 
+# the four variants of a decode, each stated once: words of the block, its bits in ptv_free_note_loop's `train` word, the composite's
+# SAMPLE_TRUNC / SAMPLE_CONS dims, the kind number of PtvaeDecoder's graph keys, the bytes ptv_decode_logprob reads, and the entry points
+# of the non-persistent loop (note token, fused duration GRU, per-step duration token)
+BlockKind = collections.namedtuple('BlockKind', 'words bits trunc cons kind nbytes note_token dur_gru dur_token')
+ARGMAX = BlockKind(0, 0, 0, 0, 0, 0, 'ptv_note_token', 'ptv_dur_gru_fwd', 'ptv_dur_out_token')
+SAMPLED = BlockKind(4, SAMPLE_BIT, 0, 0, 1, 32, 'ptv_note_token_sample', 'ptv_dur_gru_fwd_sample', 'ptv_dur_out_token_sample')
+TRUNCATED = SAMPLED._replace(words=6, bits=SAMPLE_BIT | TRUNC_BIT, trunc=1, kind=2, nbytes=48, note_token='ptv_note_token_sample_trunc')
+CONSTRAINED = TRUNCATED._replace(words=8, bits=SAMPLE_BIT | TRUNC_BIT | CONS_BIT, cons=1, kind=3, nbytes=64,
+                                 note_token='ptv_note_token_sample_cons')
+
+
+def block_kind(sampling):
+    """the BlockKind of a sampling block by its word count; None is the argmax decode"""
+    if sampling is None:
+        return ARGMAX
+    for k in (SAMPLED, TRUNCATED, CONSTRAINED):
+        if sampling.numel() == k.words:
+            return k
+    raise ValueError('sampling must be a block made by functional_free.sampling_block() on the device of z')
+
 
 def check_sampling(temperature, dur_temperature=None, sample_offset=0, seed=0, draw=0, *, top_k=None, min_p=None, top_p=None):
     """(T_pitch, T_dur, sample_offset, seed, draw) validated -- ValueError before anything touches a GPU (top_k / min_p / top_p:
     check_truncation)"""
-    import math
     check_truncation(top_k, min_p, top_p)
     tp = 0.0 if temperature is None else temperature
     td = tp if dur_temperature is None else dur_temperature
@@ -125,7 +143,6 @@ def check_truncation(top_k=None, min_p=None, top_p=None):
     top_k: an integer >= 1 (stored clipped to 130: k >= 130 keeps every class); min_p: a finite float in [0, 1], 0 = off;
     ln(min_p) is taken in float64 (the block stores it rounded to fp32); top_p (nucleus): a finite float in (0, 1], stored as
     round(top_p * 2^24) but never below 1, and 1.0 = off (the word 0)"""
-    import math
     if top_k is None and min_p is None and top_p is None:
         return None
     k = 0
@@ -242,7 +259,6 @@ def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_off
                    pitch_mask=None, ascending=None):
     """the block as four int64 words (host list); six with top_k / min_p / top_p; eight with pitch_mask / ascending (the last word is
     the address of pitch_mask as given: the caller keeps that tensor alive and contiguous -- sampling_block does)"""
-    import struct
     tp, td, off, seed, draw = check_sampling(temperature, dur_temperature, sample_offset, seed, draw)
     words = [seed - (1 << 64) if seed >= (1 << 63) else seed, draw, off, struct.unpack('<q', struct.pack('<ff', tp, td))[0]]
     tr = check_truncation(top_k, min_p, top_p)
@@ -270,19 +286,33 @@ def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sa
                            pitch_mask=pitch_mask, ascending=ascending)
     if torch.device(device).type != 'cuda':
         raise RuntimeError('a sampled decode runs on the GPU: the sampling block lives in device memory (got device %s)' % (device,))
-    blk = torch.tensor(words, dtype=torch.int64, device=device)
+    blk = make_block(words, pitch_mask, device)
     if pitch_mask is not None and pitch_mask.device != blk.device:
         raise ValueError('pitch_mask is on %s, the block on %s' % (pitch_mask.device, blk.device))
-    if len(words) == 8:
+    return blk
+
+
+def make_block(words, pitch_mask, device):
+    """validated host words (sampling_words) and the contiguous mask their last word points at -> the device block; the eight-word form
+    gets the mask as its attribute"""
+    blk = torch.tensor(words, dtype=torch.int64, device=device)
+    if len(words) == CONSTRAINED.words:
         blk.pitch_mask = pitch_mask
     return blk
 
 
+def clone_block(blk, pitch_mask=None):
+    """a copy of a block (clone() alone drops the attribute); an eight-word copy carries `pitch_mask`, or the original's when none is given"""
+    out = blk.clone()
+    if hasattr(blk, 'pitch_mask'):
+        out.pitch_mask = blk.pitch_mask if pitch_mask is None else pitch_mask
+    return out
+
+
 def _check_block(sampling, dev, B=None):
-    if not (torch.is_tensor(sampling) and sampling.dtype == torch.int64 and sampling.numel() in (4, 6, 8) and sampling.is_contiguous()
-            and sampling.device == dev):
+    if not (torch.is_tensor(sampling) and sampling.dtype == torch.int64 and sampling.is_contiguous() and sampling.device == dev):
         raise ValueError('sampling must be a block made by functional_free.sampling_block() on the device of z')
-    if sampling.numel() == 8:
+    if block_kind(sampling).cons:
         if not hasattr(sampling, 'pitch_mask'):
             raise ValueError('a constrained block must come from functional_free.sampling_block(): it carries the mask it points at')
         mask = sampling.pitch_mask
@@ -291,9 +321,21 @@ def _check_block(sampling, dev, B=None):
     return sampling
 
 
-def note_loop_cluster(B):
+NOTE_CLUSTER4_MAX_WGS = 0      # 0 = the CU count
+NOTE_CLUSTER8 = os.environ.get('PTV_NOTE_CLUSTER8', '1') != '0'
+_NCU = []
+
+
+def _num_cu():
+    if not _NCU:
+        _NCU.append(torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count)
+    return _NCU[0]
+
+
+def note_loop_cluster(B, ncu=None):
+    """members per 16-sample panel of the note loop's cluster mode (0 = off) on a device of `ncu` compute units (None: the current one)"""
     panels = (B + 15) // 16
-    ncu = _num_cu()
+    ncu = _num_cu() if ncu is None else ncu
     # round 6: from 96 panels on the 8-wave producer / head kernel used to take over; with the head weights resident and the state exchange
     # flag-in-data, two members per panel on the 4-wave kernel win up to one member per CU (B = 2048: 34.9 vs 41.7 us per note step)
     if NOTE_LOOP_SPLIT or (NOTE_LOOP_SPLIT is None and panels >= 96 and panels * 2 > ncu):
@@ -308,20 +350,51 @@ def note_loop_cluster(B):
     return 4 if panels * 4 <= cap4 else (2 if panels * 2 <= ncu else 0)
 
 
-NOTE_CLUSTER4_MAX_WGS = 0      # 0 = the CU count
-NOTE_CLUSTER8 = os.environ.get('PTV_NOTE_CLUSTER8', '1') != '0'
-
-
 def cluster_bits(c):
     """the cluster size in ptv_free_note_loop's `train` word: bits 18-20 = 2 / 4, bit 22 = eight members"""
     return 0x400000 if c == 8 else (c << 18)
-_NCU = []
 
 
-def _num_cu():
-    if not _NCU:
-        _NCU.append(torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count)
-    return _NCU[0]
+def note_loop_word(train, replay, split, cluster, kind=ARGMAX):
+    """ptv_free_note_loop's `train` word: 2 = the replayed training forward (decisions, logits and fed tokens only), else the train flag;
+    split = NOTE_LOOP_SPLIT; the cluster size; the kind's sampling bits (the composite takes the word without them: they travel as dims)"""
+    return (2 if replay else int(train)) | (0 if split is None else (0x20000 if split else 0x10000)) | cluster_bits(cluster) | kind.bits
+
+
+def coin_masks(coins, inference):
+    """the teacher-forcing coins as the kernels take them -> (32 words: bit n = note coin n of the time step, 31 bytes: the time coins),
+    as the C arrays ptv_decoder_free_fwd reads; all zero at inference"""
+    masks, time = (ctypes.c_uint * 32)(), (ctypes.c_ubyte * 31)()
+    if not inference:
+        masks[:] = [sum(int(bool(c)) << n for n, c in enumerate(row[:14])) for row in coins[0]]
+        time[:] = [int(bool(c)) for c in coins[1]]
+    return masks, time
+
+
+FreePlan = collections.namedtuple('FreePlan', 'train fast comp replay need_resum cluster capturing kind state16 ns16')
+
+
+def _free_plan(prec, dims, z_dtype, coins, inference, needs_grad, forced, kind, ncu, capturing):
+    """the path one DecoderStepFn.forward takes, decided once before anything is allocated or launched -> FreePlan: train (the backward's
+    state is saved), fast (the persistent kernels of csrc/freerun.hip), comp (all of it behind ptv_decoder_free_fwd), replay (the loop
+    stores decisions and tokens only, a batched recompute leaves what the backward reads), need_resum (a time token is re-summarised
+    from predicted notes), cluster (members per panel of the note loop, 0 = off), capturing, kind (BlockKind), state16 / ns16 (bf16
+    copies of the note and duration states / of the time states exist).  forced: force arrays were given; ncu, capturing: device facts"""
+    B, R, E, He, Ht, Hn, Hd, NP = dims
+    train = (not inference) and needs_grad
+    fast = free_persist_ok(prec, E, He, Hn, Hd, NP) and (not train or F_._act_dtype(prec, Hn) == torch.bfloat16)
+    ns16 = fast and Ht % 8 == 0                              # ... operands of the time GRU / the per-step products in the loop
+    state16 = fast and train                                 # MFMA operands of the batched backward
+    # the persistent path as ONE library call (ptv_decoder_free_fwd): then nothing is launched from Python before that call
+    comp = FREE_COMPOSITE and ns16 and z_dtype == torch.float32
+    replay = (state16 and FREE_REPLAY and F_.notes_persist_ok(prec, Hn, E) and Hd == 64 and F_.FUSED_DUR and ns16 and not forced)
+    need_resum = inference or not all(coins[1])
+    cluster = note_loop_cluster(B, ncu) if fast else 0
+    if capturing and torch.is_grad_enabled():
+        cluster = 0              # a captured training forward replays next to other streams' persistent launches, unordered with them
+    return FreePlan(train, fast, comp, replay, need_resum, cluster, capturing, kind, state16, ns16)
+
+
 _PACKS = F_.PackCache()
 _PACK_SRC = ('dec_notes_gru.weight_hh_l0', 'dec_notes_gru.weight_ih_l0', 'pitch_out_linear.weight', 'dur_hid_linear.weight',
              'dec_dur_gru.weight_hh_l0', 'note_embedding.weight', 'dec_notes_emb_gru.weight_ih_l0', 'dec_notes_emb_gru.weight_hh_l0',
@@ -376,18 +449,16 @@ def gru_step(prec, hprev, gi, gi_ld, w_hh, b_hh, hout, *, gi2=None, gates=None, 
          ptr(lengths), t, ptr(gi_idx), F_._gru_flags(gates, gi, gi2, w=w_hh), stream_ptr())
 
 
-def _decoder_free_fwd_composite(P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of, ior, dims, tens, coins, w_hh_t, w_ih_t16, prec, dev, M, R):
+def _decoder_free_fwd_composite(plan, P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of, ior, dims, tens, coins, w_hh_t, w_ih_t16, dev, M, R):
     """DecoderStepFn.forward's persistent path through ptv_decoder_free_fwd (one C call); True when it ran"""
-    import ctypes
     B, He, Ht, Hn, Hd, E = (dims[k] for k in ('B', 'He', 'Ht', 'Hn', 'Hd', 'E'))
-    replay, need_resum = bool(dims['replay']), ior is not None
     w_ih_n, w_hh_n = P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0']
     t = dict(tens)
     t.update(Z=z, XS=xs, TOK0_SRC=tok0_src, W_ZHID=P['z2dec_hid_linear.weight'], B_ZHID=P['z2dec_hid_linear.bias'],
              W_ZIN=P['z2dec_in_linear.weight'], B_ZIN=P['z2dec_in_linear.bias'], W_IH_T=P['dec_time_gru.weight_ih_l0'],
              B_IH_T=P['dec_time_gru.bias_ih_l0'], INIT_INPUT=P['dec_init_input'], B_HH_T=P['dec_time_gru.bias_hh_l0'], W_IH_T_OP=w_ih_t16,
              W_HH_T_OP=w_hh_t, W_CAT=pk['w_cat'], B_CAT=pk['b_cat'], GI=_empty(B, 3 * Ht, dev=dev), H0GC=_empty(B, 4 * Hn, dev=dev))
-    if replay:
+    if plan.replay:
         F_.zero_skip_sync()
         pkn = F_.notes_packs(w_ih_n, w_hh_n, Ht)
         t.update(W_IH_N=w_ih_n, B_IH_N=P['dec_notes_gru.bias_ih_l0'], B_HH_N=P['dec_notes_gru.bias_hh_l0'], W_DH=P['dur_hid_linear.weight'],
@@ -395,30 +466,22 @@ def _decoder_free_fwd_composite(P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of,
                  W_OUT_D=P['dur_out_linear.weight'], B_OUT_D=P['dur_out_linear.bias'], PK_NOTES_H=pkn['wg_h'], PK_NOTES_T=pkn['wg_t'],
                  GC16=_empty(R, 3 * Hn, dev=dev, dtype=torch.bfloat16), DUR_SCR=_empty(M, 10, dev=dev),
                  IDX_SCR=torch.empty(5, M, device=dev, dtype=torch.int32))
-        if need_resum:
+        if plan.need_resum:
             wE = [P['dec_notes_emb_gru.' + n] for n in EMB_GRU]
             for d_ in range(2):
                 w_ih_e, w_hh_e, b_ih_e, b_hh_e = wE[4 * d_: 4 * d_ + 4]
                 pke = F_.notes_packs(w_ih_e, w_hh_e, 0)
                 t.update({'PK_E_H%d' % d_: pke['wg_h'], 'PK_E_T%d' % d_: pke['wg_t'], 'B_HH_E%d' % d_: b_hh_e, 'B_IH_E%d' % d_: b_ih_e})
+    cluster = int(bool(plan.cluster) and not plan.capturing)
     dvals = _DFF.dims({'B': B, 'ZS': dims['Zs'], 'ZI': dims['Zi'], 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'E': E, 'NP': dims['NP'],
-                       'LDP': dims['ldp'], 'TRAIN': dims['train'], 'REPLAY': dims['replay'], 'INFERENCE': dims['inference'],
-                       'LOOP_FLAGS': dims['loop_flags'], 'CLUSTER': dims['cluster'], 'RESUM_TRAIN': dims['resum_train'], 'TOK0_LDS': tok0_lds,
+                       'LDP': dims['ldp'], 'TRAIN': int(plan.train), 'REPLAY': int(plan.replay), 'INFERENCE': dims['inference'],
+                       'LOOP_FLAGS': note_loop_word(plan.train, plan.replay, NOTE_LOOP_SPLIT, plan.cluster), 'CLUSTER': cluster,
+                       'RESUM_TRAIN': int(plan.train and not plan.replay), 'TOK0_LDS': tok0_lds,
                        'W_IH_T_BF16': w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': w_hh_t.dtype == torch.bfloat16,
-                       'SAMPLE_TRUNC': dims.get('sample_trunc', 0), 'SAMPLE_CONS': dims.get('sample_cons', 0)})
-    coin_notes, coin_time = coins
-    masks = (ctypes.c_uint * 32)()
-    tc = (ctypes.c_ubyte * 31)()
-    if not dims['inference']:
-        for ts in range(32):
-            m_ = 0
-            for n in range(14):
-                m_ |= int(bool(coin_notes[ts][n])) << n
-            masks[ts] = m_
-        for ts in range(31):
-            tc[ts] = int(bool(coin_time[ts]))
+                       'SAMPLE_TRUNC': plan.kind.trunc, 'SAMPLE_CONS': plan.kind.cons})
+    masks, tc = coins
     # the cluster-mode note loops take the persistent-launch turn (functional._PersistTurn): the library records again after the last one
-    turn = F_._CompositeTurn(F_.cur_stream()) if dims['cluster'] else None
+    turn = F_._CompositeTurn(F_.cur_stream()) if cluster else None
     slots = _DFF.pointers(t, handles=turn.handles if turn else None)
     F_._chain_prio()
     rc = lib().ptv_decoder_free_fwd(slots, dvals, wl, io_of(t['H0GC']), wr, ior, masks, tc, stream_ptr())
@@ -452,10 +515,11 @@ class DecoderStepState(F_.DecoderState):
     """DecoderState of the step loop: what decoder_bwd_core reads, and beside it what only DecoderStepFn.backward does -- TOK [15,R,E] the
     note tokens that were fed, PRED [16,R,E] the predicted ones, xhat the predicted grid, XH / XG / XH16 the re-summarisation bi-GRU's
     states, gates and bf16 states per direction (XH None: no re-summarisation), plen the predicted rows' lengths and whether the kernels
-    skipped by them, the teacher-forcing coins, has_xs: ground-truth summaries were given"""
+    skipped by them, the teacher-forcing coins, has_xs: ground-truth summaries were given; plan: the FreePlan the forward ran by"""
 
-    def __init__(self, dims, prec, notes, heads, dur, *, TOK, PRED, xhat, XH, XG, XH16, plen, skipped, coins, has_xs, **saved):
+    def __init__(self, dims, prec, notes, heads, dur, *, TOK, PRED, xhat, XH, XG, XH16, plen, skipped, coins, has_xs, plan=None, **saved):
         super().__init__(dims, prec, notes, heads, dur, **saved)
+        self.plan = plan
         self.TOK, self.PRED, self.xhat, self.XH, self.XG, self.XH16 = TOK, PRED, xhat, XH, XG, XH16
         self.plen, self.skipped, self.coins, self.has_xs = plen, skipped, coins, has_xs
 
@@ -476,31 +540,27 @@ class DecoderStepFn(torch.autograd.Function):
             if not inference or any(any(r) for r in coins[0]) or any(coins[1]):
                 raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
             _check_block(sampling, dev, z.shape[0])
-        samp_bit = 0 if sampling is None else (SAMPLE_BIT | {4: 0, 6: TRUNC_BIT, 8: TRUNC_BIT | CONS_BIT}[sampling.numel()])
-        trunc = bool(samp_bit & TRUNC_BIT)
-        cons = bool(samp_bit & CONS_BIT)
         z = z.contiguous()
         B = z.shape[0]
         R = 32 * B
-        E = P['note_embedding.weight'].shape[0]
-        He = P['dec_notes_emb_gru.weight_hh_l0'].shape[1]
-        Ht = P['dec_time_gru.weight_hh_l0'].shape[1]
-        Hn = P['dec_notes_gru.weight_hh_l0'].shape[1]
-        Hd = P['dec_dur_gru.weight_hh_l0'].shape[1]
-        NP = P['pitch_out_linear.weight'].shape[0]
+        E, NP, Zi = (P[n + '.weight'].shape[0] for n in ('note_embedding', 'pitch_out_linear', 'z2dec_in_linear'))
+        He, Ht, Hn, Hd = (P['dec_%s_gru.weight_hh_l0' % n].shape[1] for n in ('notes_emb', 'time', 'notes', 'dur'))
         M = 15 * R
-        train = (not inference) and any(ctx.needs_input_grad)
-        coin_notes, coin_time = coins
+        force_pitch = force.get('pitch') if force else None          # [15, R] int32
+        force_dur = force.get('dur') if force else None              # [5, 15R] int32
+        plan = _free_plan(prec, (B, R, E, He, Ht, Hn, Hd, NP), z.dtype, coins, inference, any(ctx.needs_input_grad),
+                          force_pitch is not None or force_dur is not None, block_kind(sampling), _num_cu(),
+                          torch.cuda.is_current_stream_capturing())
+        train, fast, comp, replay, need_resum, cluster, capturing, kind = plan[:8]
+        masks, time_coins = coin_masks(coins, inference)
         w_emb, b_emb = P['note_embedding.weight'], P['note_embedding.bias']
         st = stream_ptr()
+        bf16 = torch.bfloat16
 
+        # ---- allocate by the plan (the composite launches nothing from here before its call: it runs the prologue itself)
         NS = _empty(33, B, Ht, dev=dev)
         w_ih_t = P['dec_time_gru.weight_ih_l0']
-        Zi = P['z2dec_in_linear.weight'].shape[0]
         TOKS = _empty(33, B, 2 * He, dev=dev)
-        # the persistent path as ONE library call (ptv_decoder_free_fwd): then nothing is launched from here before that call
-        comp = (FREE_COMPOSITE and free_persist_ok(prec, E, He, Hn, Hd, NP) and Ht % 8 == 0
-                and (not train or F_._act_dtype(prec, Hn) == torch.bfloat16) and z.dtype == torch.float32)
         if comp:
             z_in, zg = _empty(B, Zi, dev=dev), _empty(B, 3 * Ht, dev=dev)
         else:
@@ -509,29 +569,24 @@ class DecoderStepFn(torch.autograd.Function):
             zg = gemm(z_in, w_ih_t[:, 2 * He:], bias=P['dec_time_gru.bias_ih_l0'], prec=prec)
             copy2d(TOKS[0], P['dec_init_input'].view(1, -1), lds=0)
         gates_t = _empty(32, 4, B, Ht, dev=dev, dtype=F_._act_dtype(prec, Ht)) if train else None
-
         HN = _empty(16, R, Hn, dev=dev)
         gates_n = _empty(15, 4, R, Hn, dev=dev, dtype=F_._act_dtype(prec, Hn)) if train else None
         TOK = _empty(15, R, E, dev=dev)
-        PRED = None                                                # allocated below (zero-filled only where something may stay unwritten)
         xhat = torch.full((B, 32, 16, 6), 2, device=dev, dtype=torch.long)
         xhat[:, :, :, 0] = 130
         xhat[:, :, 0, 0] = 128
         plen = torch.zeros(R, device=dev, dtype=torch.int32)
-        fast = free_persist_ok(prec, E, He, Hn, Hd, NP) and (not train or F_._act_dtype(prec, Hn) == torch.bfloat16)
         PRED = _empty(16, R, E, dev=dev) if fast else _zeros(16, R, E, dev=dev)      # the persistent note loop writes every slot
         pitch = _empty(M, F_._pad8(NP), dev=dev)[:, :NP] if fast else _empty(M, NP, dev=dev)
         HD = _empty(6, M, Hd, dev=dev)
-        gates_d = _empty(5, 4, M, Hd, dev=dev, dtype=F_._act_dtype(prec, Hd)) if train else None
+        # (the batched recompute's duration GRU saves no gates: csrc/dur_bwd.hip rebuilds them)
+        gates_d = _empty(5, 4, M, Hd, dev=dev, dtype=F_._act_dtype(prec, Hd)) if train and not (replay and F_.DUR_RECOMPUTE) else None
         idx = torch.empty(5, M, device=dev, dtype=torch.int32)
         dur = _empty(M, 5, 2, dev=dev)
         dur2 = dur.view(M, 10)
-        need_resum = inference or not all(coin_time)
-
         if inference:
-            sos = _sos_grid(dev)
             sos_emb = _empty(16, 32, 1, E, dev=dev)
-            call('ptv_embed_fwd', ptr(sos), ptr(w_emb), ptr(b_emb), ptr(sos_emb), None, 1, E, st)
+            call('ptv_embed_fwd', ptr(_sos_grid(dev)), ptr(w_emb), ptr(b_emb), ptr(sos_emb), None, 1, E, st)
             sos_row = sos_emb.view(-1, E)[0:1]
         w_ih_n, w_hh_n, b_hh_n = P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0'], P['dec_notes_gru.bias_hh_l0']
         w_dh = P['dur_hid_linear.weight']
@@ -541,82 +596,66 @@ class DecoderStepFn(torch.autograd.Function):
         tab = gemm(_onehot2x5(dev), w_ih_d, bias=b_ih_d, prec=0)
         emb3 = emb.view(16, R, E) if emb is not None else None
         wE = [P['dec_notes_emb_gru.' + n] for n in EMB_GRU]
-        force_pitch = force.get('pitch') if force else None          # [15, R] int32
-        force_dur = force.get('dur') if force else None              # [5, 15R] int32
-
-        HN16 = HD16 = NS16 = None
-        if fast and train:                                       # bf16 state copies: MFMA operands of the batched backward
-            HN16 = _empty(16, R, Hn, dev=dev, dtype=torch.bfloat16)
-            HD16 = _empty(6, M, Hd, dev=dev, dtype=torch.bfloat16)
-        if fast and Ht % 8 == 0:                                 # ... and of the time GRU / the per-step products in the loop
-            NS16 = _empty(33, B, Ht, dev=dev, dtype=torch.bfloat16)
-            if not comp:
-                call('ptv_cast_bf16', ptr(NS[0]), ptr(NS16[0]), B * Ht, st)
+        # bf16 state copies: MFMA operands of the batched backward, and of the time GRU / the per-step products in the loop
+        HN16 = _empty(16, R, Hn, dev=dev, dtype=bf16) if plan.state16 else None
+        HD16 = _empty(6, M, Hd, dev=dev, dtype=bf16) if plan.state16 else None
+        NS16 = _empty(33, B, Ht, dev=dev, dtype=bf16) if plan.ns16 else None
+        if plan.ns16 and not comp:
+            call('ptv_cast_bf16', ptr(NS[0]), ptr(NS16[0]), B * Ht, st)
         # per time step the loop runs four M = B products whose cost is reading the weights: their bf16 shadows halve it
-        w_hh_t = F_._W(P['dec_time_gru.weight_hh_l0'], prec) if NS16 is not None else P['dec_time_gru.weight_hh_l0']
+        w_hh_t = F_._W(P['dec_time_gru.weight_hh_l0'], prec) if plan.ns16 else P['dec_time_gru.weight_hh_l0']
         w_ih_t16, w_tn16, w_ih_n16 = (F_._W(w_ih_t, prec), F_._W(P['dec_time_to_notes_hid.weight'], prec), F_._W(w_ih_n, prec)) if fast \
             else (w_ih_t, P['dec_time_to_notes_hid.weight'], w_ih_n)
-        replay = (fast and train and FREE_REPLAY and F_.notes_persist_ok(prec, Hn, E) and Hd == 64 and F_.FUSED_DUR and NS16 is not None
-                  and force_dur is None and force_pitch is None)
         XH = XG = None
-        if replay and F_.DUR_RECOMPUTE and HD16 is not None:
-            gates_d = None                                         # the batched recompute's duration GRU saves no gates (csrc/dur_bwd.hip rebuilds them)
+        XH16 = [None, None]
         if need_resum and replay:                                # the batched recompute writes every row of every slot but slot 0
             XH = [_empty(17, R, He, dev=dev) for _ in range(2)]
             for d in range(2):
                 XH[d][0].zero_()
-            XG = [_empty(16, 4, R, He, dev=dev, dtype=torch.bfloat16) for _ in range(2)]
+            XG = [_empty(16, 4, R, He, dev=dev, dtype=bf16) for _ in range(2)]
+            XH16 = [_empty(17, R, He, dev=dev, dtype=bf16) for _ in range(2)]
         elif need_resum:
             XH = [_zeros(17, R, He, dev=dev) for _ in range(2)]
             XG = [torch.zeros(16, 4, R, He, device=dev, dtype=F_._act_dtype(prec, He)) for _ in range(2)] if train else [None, None]
-        cluster, xch, xcnt = 0, None, None
+        xch = xcnt = None
+        if cluster:
+            global LAST_CLUSTER_COUNTERS
+            xch = torch.zeros((B + 15) // 16 * 2 * 16 * Hn * 2, device=dev, dtype=bf16)   # 8-byte words {2 units, step tag}: tag 0 = nothing sent yet
+            xcnt = torch.zeros((B + 15) // 16 + 1, device=dev, dtype=torch.int32)    # arrival counters of t = 0..31 + error word
+            LAST_CLUSTER_COUNTERS = xcnt             # (tests: every panel counts 32 * 15 * S arrivals, the error word stays 0)
+            F_._CLUSTER_SYNC.append(xcnt)
+            if len(F_._CLUSTER_SYNC) > 64:
+                del F_._CLUSTER_SYNC[:32]
         if fast:
-            cluster = note_loop_cluster(B)
-            capturing = torch.cuda.is_current_stream_capturing()
-            if capturing and torch.is_grad_enabled():
-                cluster = 0          # a captured training forward replays next to other streams' persistent launches, unordered with them
-            if cluster:
-                global LAST_CLUSTER_COUNTERS
-                xch = torch.zeros((B + 15) // 16 * 2 * 16 * Hn * 2, device=dev, dtype=torch.bfloat16)   # 8-byte words {2 units, step tag}: tag 0 = nothing sent yet
-                xcnt = torch.zeros((B + 15) // 16 + 1, device=dev, dtype=torch.int32)    # arrival counters of t = 0..31 + error word
-                LAST_CLUSTER_COUNTERS = xcnt             # (tests: every panel counts 32 * 15 * S arrivals, the error word stays 0)
-                F_._CLUSTER_SYNC.append(xcnt)
-                if len(F_._CLUSTER_SYNC) > 64:
-                    del F_._CLUSTER_SYNC[:32]
             pk = _free_packs(P, Ht)
             wl = F_._parr([pk['wg_h'], pk['wg_t'], pk['wp'], pk['wd_h'], pk['wd_p'], pk['wdur'], b_hh_n, P['pitch_out_linear.bias'],
                            P['dur_hid_linear.bias'], b_hh_d, tab0, tab, P['dur_out_linear.weight'], P['dur_out_linear.bias'],
                            pk['w_embT'], b_emb])
             wr = F_._parr([pk['e_ih'], pk['e_hh'], pk['e_ih_r'], pk['e_hh_r'], wE[2], wE[3], wE[6], wE[7]])
-        XH16 = [None, None]
-        done = False
+
+        # ---- the composite (one C call), or the same launches sequenced from here
         if comp:
-            assert fast and NS16 is not None
-            if replay and need_resum:
-                XH16 = [_empty(17, R, He, dev=dev, dtype=torch.bfloat16) for _ in range(2)]
             done = _decoder_free_fwd_composite(
-                P, z, xs, sos_row if inference else emb3[0], 0 if inference else E, pk, wl, wr, io_of=lambda h0gc: F_._parr(
+                plan, P, z, xs, sos_row if inference else emb3[0], 0 if inference else E, pk, wl, wr, io_of=lambda h0gc: F_._parr(
                     [None, emb3, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16, None, h0gc,
                      xch, xcnt]),
                 ior=F_._parr([PRED, plen, XH[0], XH[1], XG[0], XG[1], None]) if need_resum else None,
-                dims=dict(B=B, Zs=z.shape[1], Zi=Zi, He=He, Ht=Ht, Hn=Hn, Hd=Hd, E=E, NP=NP, ldp=pitch.stride(0), train=int(train), replay=int(bool(replay)),
-                          inference=int(bool(inference)), cluster=int(cluster and not capturing), sample_trunc=int(trunc), sample_cons=int(cons),
-                          loop_flags=(2 if replay else int(train)) | (0 if NOTE_LOOP_SPLIT is None else (0x20000 if NOTE_LOOP_SPLIT else 0x10000))
-                          | cluster_bits(cluster), resum_train=int(train and not replay)),
+                dims=dict(B=B, Zs=z.shape[1], Zi=Zi, He=He, Ht=Ht, Hn=Hn, Hd=Hd, E=E, NP=NP, ldp=pitch.stride(0), inference=int(bool(inference))),
                 tens=dict(NS=NS, NS16=NS16, Z_IN=z_in, ZG=zg, TOKS=TOKS, GATES_T=gates_t, TOK=TOK, PRED=PRED, PITCH=pitch, HN=HN, HN16=HN16,
                           GATES_N=gates_n, HD=HD, HD16=HD16, GATES_D=gates_d, IDX=idx, PLEN=plen, XH0=XH[0] if XH else None,
                           XH1=XH[1] if XH else None, XH16_0=XH16[0], XH16_1=XH16[1], XG0=XG[0] if XG else None, XG1=XG[1] if XG else None,
                           TAB0=tab0, TAB=tab, SAMPLE=sampling),     # (the composite appends the block to the note loop's io itself)
-                coins=(coin_notes, coin_time), w_hh_t=w_hh_t, w_ih_t16=w_ih_t16, prec=prec, dev=dev, M=M, R=R)
+                coins=(masks, time_coins), w_hh_t=w_hh_t, w_ih_t16=w_ih_t16, dev=dev, M=M, R=R)
             assert done, 'ptv_decoder_free_fwd declined a configuration free_persist_ok() accepted'
-        # the first note token of every time step is the <sos> embedding (ptvae.py:388-392): one copy for all 32 steps
-        if not done:
+        else:
+            # the first note token of every time step is the <sos> embedding (ptvae.py:388-392): one copy for all 32 steps
             if inference:
                 copy2d(TOK[0], sos_row, lds=0)
             else:
                 copy2d(TOK[0], emb3[0])
             copy2d(PRED[0], TOK[0])
-        for t in range(0 if not done else 32, 32):
+        smp = () if sampling is None else (ptr(sampling),)          # sampled forms of the non-persistent loop: the block, then (t, n) of the rows
+        for t in range(32 if comp else 0, 32):
             rows = slice(t * B, (t + 1) * B)
             gi = gemm(TOKS[t], w_ih_t16[:, :2 * He], prec=prec)
             gru_step(prec, NS[t], gi, 3 * Ht, w_hh_t, P['dec_time_gru.bias_hh_l0'], NS[t + 1], gi2=zg,
@@ -625,34 +664,26 @@ class DecoderStepFn(torch.autograd.Function):
             ns = NS16[t + 1] if NS16 is not None else NS[t + 1]
             if fast:
                 # initial notes-GRU state and the hoisted input part in ONE product against the stacked weights ([512 | 1536] rows):
-                # 256 blocks, no split-K, no zero fill
+                # 256 blocks, no split-K, no zero fill; then all 15 note steps of this time step in ONE launch (csrc/freerun.hip)
                 H0GC = gemm(ns, pk['w_cat'], bias=pk['b_cat'], prec=prec)
-                GCt = None
-            else:
-                gemm(ns, w_tn16, HN[0][rows], bias=P['dec_time_to_notes_hid.bias'], prec=prec)
-                GCt = gemm(ns, w_ih_n16[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec)
-            if fast:
-                # all 15 note steps of this time step in ONE launch (csrc/freerun.hip); then the next time-step token
-                mask = 0
-                if not inference:
-                    for n in range(14):
-                        mask |= int(bool(coin_notes[t][n])) << n
-                io = F_._parr([GCt, emb3, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16,
+                io = F_._parr([None, emb3, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16,
                                None, H0GC, xch, xcnt] + ([sampling] if sampling is not None else []))
                 # (cluster mode: the members of a panel spin on each other -- like every persistent launch it takes its turn, so that
                 # it is never half-resident next to another spinning grid, e.g. the chord decoder's on its sibling stream)
                 with (F_._PersistTurn() if cluster and not capturing else contextlib.nullcontext()):
-                    call('ptv_free_note_loop', wl, io, pitch.stride(0), B, t, mask,
-                         (2 if replay else int(train)) | (0 if NOTE_LOOP_SPLIT is None else (0x20000 if NOTE_LOOP_SPLIT else 0x10000))
-                         | cluster_bits(cluster) | samp_bit, st)
+                    call('ptv_free_note_loop', wl, io, pitch.stride(0), B, t, masks[t],
+                         note_loop_word(train, replay, NOTE_LOOP_SPLIT, cluster, kind), st)
                 if t == 31:
                     break
-                if (not inference) and coin_time[t]:
+                # ... and the next time-step token
+                if time_coins[t]:
                     copy2d(TOKS[t + 1], xs[rows])
                 else:
                     io = F_._parr([PRED, plen, XH[0], XH[1], XG[0], XG[1], TOKS[t + 1]])
                     call('ptv_free_resummarize', wr, io, B, t, int(train and not replay), st)
                 continue
+            gemm(ns, w_tn16, HN[0][rows], bias=P['dec_time_to_notes_hid.bias'], prec=prec)
+            GCt = gemm(ns, w_ih_n16[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec)
             for n in range(15):
                 gi_tok = gemm(TOK[n][rows], w_ih_n[:, Ht:], prec=prec)
                 gru_step(prec, HN[n][rows], gi_tok, 3 * Hn, w_hh_n, b_hh_n, HN[n + 1][rows], gi2=GCt,
@@ -662,33 +693,28 @@ class DecoderStepFn(torch.autograd.Function):
                 gemm(h, P['pitch_out_linear.weight'], pitch[pr], bias=P['pitch_out_linear.bias'], prec=prec)
                 gemm(h, w_dh[:, :Hn], HD[0][pr], bias=P['dur_hid_linear.bias'], prec=prec)
                 gemm(pitch[pr], w_dh[:, Hn:], HD[0][pr], acc=True, prec=prec)
-                smp = () if sampling is None else (ptr(sampling), t, n)          # sampled forms: the block and the (t, n) of the rows
                 if prec == 1 and Hd == 64 and F_.FUSED_DUR:
-                    call('ptv_dur_gru_fwd' if sampling is None else 'ptv_dur_gru_fwd_sample', Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d),
-                         ptr(tab0), ptr(tab),
+                    call(kind.dur_gru, Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tab0), ptr(tab),
                          ptr(P['dur_out_linear.weight']), ptr(P['dur_out_linear.bias']), ptr(HD[1][pr]), M * Hd, None,
                          ptr(gates_d[0][0][pr]) if train else None, M * Hd, 4 * M * Hd, F_._bf(gates_d), ptr(dur2[pr]), 10,
-                         ptr(idx[0][pr]), M, ptr(force_dur[0][pr]) if force_dur is not None else None, M, *smp, st)
+                         ptr(idx[0][pr]), M, ptr(force_dur[0][pr]) if force_dur is not None else None, M, *(smp and smp + (t, n)), st)
                 else:
                     for d in range(5):
                         g_, g_ld, g_idx = (tab0, 0, None) if d == 0 else (tab, 3 * Hd, idx[d - 1][pr])
                         gru_step(prec, HD[d][pr], g_, g_ld, w_hh_d, b_hh_d, HD[d + 1][pr],
                                  gates=gates_d[d][:, pr] if train else None, plane=M * Hd, gi_idx=g_idx)
-                        call('ptv_dur_out_token' if sampling is None else 'ptv_dur_out_token_sample', ptr(HD[d + 1][pr]), Hd,
-                             ptr(P['dur_out_linear.weight']),
+                        call(kind.dur_token, ptr(HD[d + 1][pr]), Hd, ptr(P['dur_out_linear.weight']),
                              ptr(P['dur_out_linear.bias']), ptr(dur2[pr][:, 2 * d:]), 10, ptr(idx[d][pr]),
-                             ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp + ((d,) if smp else ())), st)
-                call('ptv_note_token' if sampling is None else 'ptv_note_token_sample_cons' if cons else
-                     'ptv_note_token_sample_trunc' if trunc else 'ptv_note_token_sample',
-                     ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(w_emb), ptr(b_emb), E,
+                             ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp and smp + (t, n, d)), st)
+                call(kind.note_token, ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(w_emb), ptr(b_emb), E,
                      ptr(PRED[n + 1][rows]), E, ptr(xhat[0, t, n + 1]), 32 * 16 * 6, ptr(plen[rows]), n + 1, int(n == 14),
-                     ptr(force_pitch[n][rows]) if force_pitch is not None else None, B, *(smp[:2] if smp else ()), st)
+                     ptr(force_pitch[n][rows]) if force_pitch is not None else None, B, *(smp and smp + (t,)), st)
                 if n < 14:
-                    use_gt = (not inference) and coin_notes[t][n]
+                    use_gt = (not inference) and coins[0][t][n]
                     copy2d(TOK[n + 1][rows], emb3[n + 1][rows] if use_gt else PRED[n + 1][rows])
             if t == 31:
                 break
-            if (not inference) and coin_time[t]:
+            if time_coins[t]:
                 copy2d(TOKS[t + 1], xs[rows])
             else:
                 # token = final states of dec_notes_emb_gru over the predicted notes (ptvae.py:480-486)
@@ -702,10 +728,10 @@ class DecoderStepFn(torch.autograd.Function):
                                  gates=XG[d][s_][:, rows] if train else None, plane=R * He, lengths=plen[rows], t=tt)
                     copy2d(TOKS[t + 1][:, d * He:(d + 1) * He], XH[d][16][rows])
 
-        if replay and not done:
+        if replay and not comp:
             F_.zero_skip_sync()
             # ---- recompute what the backward reads, batched over all rows (the step loop above stored decisions and tokens only)
-            GC16 = gemm(NS16[1:].view(R, Ht), w_ih_n[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec, out_dtype=torch.bfloat16,
+            GC16 = gemm(NS16[1:].view(R, Ht), w_ih_n[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec, out_dtype=bf16,
                         out_blocked=16)      # (column-blocked by 16: the layout the row kernel reads)
             pkn = F_.notes_packs(w_ih_n, w_hh_n, Ht)
             call('ptv_notes_gru_persist_fwd', ptr(pkn['wg_h']), ptr(pkn['wg_t']), ptr(b_hh_n), ptr(GC16), ptr(TOK), ptr(HN), ptr(HN16),
@@ -722,7 +748,6 @@ class DecoderStepFn(torch.autograd.Function):
                 for d in range(2):
                     w_ih_e, w_hh_e, b_ih_e, b_hh_e = wE[4 * d: 4 * d + 4]
                     pke = F_.notes_packs(w_ih_e, w_hh_e, 0)
-                    XH16[d] = _empty(17, R, He, dev=dev, dtype=torch.bfloat16)
                     call('ptv_row_gru_persist_fwd', He, ptr(pke['wg_h']), ptr(pke['wg_t']), ptr(b_hh_e), ptr(b_ih_e), None, ptr(PRED), R * E,
                          ptr(plen), ptr(XH[d]), ptr(XH16[d]), ptr(XG[d]), None, 0, R, 16, d, st)
         if train:
@@ -731,8 +756,8 @@ class DecoderStepFn(torch.autograd.Function):
             # duration steps leave what csrc/heads.hip / csrc/dur_bwd.hip take back wherever the bf16 copies exist)
             ctx.saved_state = DecoderStepState(
                 (B, R, E, He, Ht, Hn, Hd, NP), prec, 'rows' if replay else 'step',
-                'fused' if F_.heads_ok(prec, Hn, NP, Hd, HN16, HD16) else 'gemm',
-                'fused16' if HD16 is not None else 'fused' if F_.dur_bwd_fusable(prec, Hd, gates_d) else 'step',
+                'fused' if F_.heads_ok(prec, Hn, NP, Hd, plan.state16 or None, plan.state16 or None) else 'gemm',
+                'fused16' if plan.state16 else 'fused' if F_.dur_bwd_fusable(prec, Hd, gates_d) else 'step', plan=plan,
                 NS=NS, NS16=NS16, z_in=z_in, TOKS=TOKS, gates_t=gates_t, HN=HN, HN16=HN16, gates_n=gates_n, pitch=pitch, HD=HD, HD16=HD16,
                 gates_d=gates_d, idx=idx, dur_tabs=(tab0, tab), TOK=TOK, PRED=PRED, xhat=xhat, XH=XH, XG=XG, XH16=XH16, plen=plen,
                 skipped=F_.ZERO_SKIP, coins=coins, has_xs=xs is not None)

@@ -5,14 +5,17 @@ init_model :244-265): same constructor, `forward(mode, ...)` dispatch, `run` / `
 `loss_function` / `kl_loss` / `chord_loss` signatures and return tuples, same `state_dict` keys.
 All arithmetic runs in libptvae_hip.so kernels.
 """
+import collections
 import os
 
 import torch
 
 from . import functional as F_
+from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
+from .functional_free import Keep, build_keep, check_constraints, check_keep, check_sampling, make_block, sampling_words
 from .optim import refresh_weight_shadows
-from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder
+from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
 LOSS_NAMES = ['loss', 'recon_loss', 'pl', 'dl', 'kl_loss', 'kl_chd', 'kl_rhy', 'chord_loss', 'root_loss',
               'chroma_loss', 'bass_loss']                       # train.py:54-55
@@ -32,6 +35,23 @@ CHD_DEC_SLOT = 4        # the chord decoder beside the PianoTree decoder
 ENC_CHAIN = True
 DT_PAD_COL = 3          # column of dt_x that is set for a <pad> row (is_note class 3, dataset.py:194-195): its zeros count the live rows
 DT_SHAPE = (32, 16, 39)
+# the keywords of a free-running decode (inference_decode); the last two are device objects, the rest host values
+DECODE_KEYS = ('temperature', 'dur_temperature', 'seed', 'draw', 'sample_offset', 'top_k', 'min_p', 'top_p', 'ascending', 'pitch_mask', 'keep')
+
+
+class DecodeRequest(collections.namedtuple('DecodeRequest', 'sampled kw mask keep batch')):
+    """the validated keywords of one decode (DisentangleVAE._request): sampled (a temperature was given), kw (the host keywords), mask
+    (pitch_mask made contiguous -- the block holds its address -- or None), keep (functional_free.Keep or None), batch (the decoded rows)"""
+
+    def tiled(self, n):
+        """the request of the batch repeated n times (decode_best_of): a mask or keep with one row per sample is tiled alike"""
+        mask, keep, B = self.mask, self.keep, self.batch
+        if mask is not None and mask.shape[0] == B and B > 1:
+            mask = mask.repeat(n, 1, 1)
+        if keep is not None:
+            keep = Keep(keep.pitch.view(15, 32, 1, B).expand(15, 32, n, B).reshape(15, 32 * n * B),
+                        keep.dur.view(5, 15, 32, 1, B).expand(5, 15, 32, n, B).reshape(5, 480 * n * B), keep.err.repeat(n), n * B)
+        return self._replace(mask=mask, keep=keep, batch=n * B)
 
 
 class DisentangleVAE(PytorchModel):
@@ -127,7 +147,6 @@ class DisentangleVAE(PytorchModel):
         # the two encoders are independent of each other and of the embedding: sibling HIP streams
         # (autograd replays each branch's backward on the stream its forward ran on).  They fork FIRST: a sibling stream waits for
         # what its parent has queued so far, and the embedding (queued on the parent next) is not their input
-        from .ptvae import _require_cuda
         _require_cuda(x, 'DisentangleVAE.run')               # (fails loudly off-GPU before any stream is touched)
         if self.detrended:
             if dt_x is None:
@@ -293,7 +312,7 @@ class DisentangleVAE(PytorchModel):
                 from .dataset import detrend_pianotree
                 tex = detrend_pianotree(x.long(), c)
             dist_chd, dist_rhy = self.inference_encode(tex, c)
-            self._decode(dist_chd.mean, dist_rhy.mean, {})
+            self._decode(dist_chd.mean, dist_rhy.mean, self._request(x.shape[0]))
             # the decoded grid goes through the output path's canonical form first (x_clean: a step's first 14 readable notes, <eos>,
             # <pad>), the layout x itself has: both rolls are then made from grids with the same clipping
             to_pr = lambda grid: self.decoder.grid_to_pr_and_notes_batch(grid, 15, check=False)
@@ -372,7 +391,6 @@ class DisentangleVAE(PytorchModel):
         """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode (constrained or not).  No side
         effect, no launch.  batch: the rows of the decoded batch where the caller knows them (pitch_mask's row count and keep's batch are
         held to it)"""
-        from .functional_free import check_constraints, check_keep, check_sampling
         check_constraints(pitch_mask, ascending, batch)
         check_keep(keep, batch)
         if temperature is None and dur_temperature is None:
@@ -385,52 +403,44 @@ class DisentangleVAE(PytorchModel):
                        0 if draw is None else draw, top_k=top_k, min_p=min_p, top_p=top_p)
         return True
 
-    def _check_decode(self, sampling, batch):
-        """_check_sampling of a decode's keywords, and what only this model knows: kept steps and the decoder's replay mode exclude each
-        other.  ValueError before anything is encoded or launched."""
+    def _request(self, batch, **sampling):
+        """the keywords of a decode of `batch` rows, validated once -> DecodeRequest.  _check_sampling's ValueErrors, and what only this
+        model knows: kept steps and the decoder's replay mode exclude each other.  Before anything is encoded or launched, and before the
+        draw counter moves."""
         sampled = self._check_sampling(**sampling, batch=batch)
-        if sampling.get('keep') is not None and self.decoder.force_trace is not None:
+        keep, mask = sampling.get('keep'), sampling.get('pitch_mask')
+        if keep is not None and self.decoder.force_trace is not None:
             raise ValueError('keep cannot be combined with decoder.force_trace: both fill the force arrays')
-        return sampled
+        return DecodeRequest(sampled, {k: sampling.get(k) for k in DECODE_KEYS[:-2]}, None if mask is None else mask.contiguous(), keep, batch)
 
-    def _sampling_words(self, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
-                        top_p=None, pitch_mask=None, ascending=None, keep=None, batch=None):
-        """None (argmax decode) or the validated sampling block as host words -- ValueError for a bad value before anything is launched
-        (keep puts nothing into the block: it travels beside it)"""
-        from .functional_free import sampling_words
-        if not self._check_sampling(temperature, dur_temperature, seed, draw, sample_offset, top_k, min_p, top_p, pitch_mask, ascending,
-                                    keep, batch):
-            if pitch_mask is None and ascending is None:
+    def _sampling_words(self, req):
+        """None (argmax decode) or the request's sampling block as host words (keep puts nothing into the block: it travels beside it);
+        a sampled decode that names no draw takes the model's counter and advances it"""
+        kw = req.kw
+        if not req.sampled:
+            if req.mask is None and kw['ascending'] is None:
                 return None
-            return sampling_words(0.0, 0.0, 0, 0, 0, pitch_mask=pitch_mask, ascending=ascending)   # the constrained argmax: no noise, no draw used
+            return sampling_words(0.0, 0.0, 0, 0, 0, pitch_mask=req.mask, ascending=kw['ascending'])   # the constrained argmax: no noise, no draw used
         ph = self._philox or (7, 0)
-        words = sampling_words(temperature, dur_temperature, ph[0] if seed is None else seed, self._sample_draws if draw is None else draw,
-                               ph[1] if sample_offset is None else sample_offset, top_k=top_k, min_p=min_p, top_p=top_p,
-                               pitch_mask=pitch_mask, ascending=ascending)
+        seed, draw, offset = kw['seed'], kw['draw'], kw['sample_offset']
+        words = sampling_words(kw['temperature'], kw['dur_temperature'], ph[0] if seed is None else seed,
+                               self._sample_draws if draw is None else draw, ph[1] if offset is None else offset, top_k=kw['top_k'],
+                               min_p=kw['min_p'], top_p=kw['top_p'], pitch_mask=req.mask, ascending=kw['ascending'])
         if draw is None:
             self._sample_draws += 1
         return words
 
-    def _decode(self, z_chd, z_rhy, sampling):
-        """the free-running decode of both inference forms; `sampling`: keywords of a sampled decode"""
-        from .ptvae import _require_cuda
-        self._check_decode(sampling, z_chd.shape[0])
-        keep = sampling.get('keep')
-        mask = sampling.get('pitch_mask')
-        if mask is not None:
-            mask = mask.contiguous()                                    # (the block holds its address)
-            sampling = dict(sampling, pitch_mask=mask)
-        words = self._sampling_words(**sampling, batch=z_chd.shape[0])
+    def _decode(self, z_chd, z_rhy, req):
+        """the free-running decode of both inference forms; req: the DecodeRequest of its keywords"""
+        words = self._sampling_words(req)
         if words is not None:
             _require_cuda(z_chd, 'DisentangleVAE sampled decode')
             _require_cuda(z_rhy, 'DisentangleVAE sampled decode')
         dec_z = torch.cat([z_chd, z_rhy], dim=-1)
-        block = None if words is None else torch.tensor(words, dtype=torch.int64, device=dec_z.device)
-        if block is not None and len(words) == 8:
-            block.pitch_mask = mask
-        if keep is not None:
+        block = None if words is None else make_block(words, req.mask, dec_z.device)
+        if req.keep is not None:
             _require_cuda(dec_z, 'DisentangleVAE decode with kept steps')
-        return self.decoder(dec_z, True, None, None, 0., 0., sampling=block, keep=keep)
+        return self.decoder(dec_z, True, None, None, 0., 0., sampling=block, keep=req.keep)
 
     def keep(self, x, steps):
         """The kept time steps of a decode -> functional_free.Keep(pitch, dur, err, batch) for keep= (ptv_keep_force_build; INTEGRATION.md
@@ -439,7 +449,6 @@ class DisentangleVAE(PytorchModel):
         sample: range(16) = the first bar).  The notes of a kept step up to its <eos> are forced where the decoder takes its decisions
         and fed back like decisions; everything else is decided as without it.  err[b] bit 0: a kept step of sample b held a pitch outside
         0..129 before its <eos>; that decision stays free.  Nothing is copied to the host."""
-        from .functional_free import build_keep
         return build_keep(x, steps)
 
     def pitch_mask(self, c=None, pitch_classes=None, lo=None, hi=None, batch=None):
@@ -476,22 +485,20 @@ class DisentangleVAE(PytorchModel):
         B = c.shape[0] if c is not None else (1 if batch is None else batch)
         if isinstance(B, bool) or not isinstance(B, int) or B < 1:
             raise ValueError('batch must be an integer >= 1, got %r' % (batch,))
-        from ._lib import call, ptr, stream_ptr
         out = torch.empty(B, 32, 4, dtype=torch.int32, device=c.device if c is not None else self.device)
         call('ptv_pitch_mask_build', ptr(out), B, lo_, hi_, k, ptr(c) if c is not None else None, stream_ptr())
         return out
 
     def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None,
                          top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None, keep=None):
-        self._check_decode(dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset,
-                                top_k=top_k, min_p=min_p, top_p=top_p, pitch_mask=pitch_mask, ascending=ascending, keep=keep),
-                           z_chd.shape[0])
+        kw = locals()
+        return self._inference_decode(z_chd, z_rhy, self._request(z_chd.shape[0], **{k: kw[k] for k in DECODE_KEYS}))
+
+    def _inference_decode(self, z_chd, z_rhy, req):
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
-            self._decode(z_chd, z_rhy, dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw,
-                                            sample_offset=sample_offset, top_k=top_k, min_p=min_p, top_p=top_p,
-                                            pitch_mask=pitch_mask, ascending=ascending, keep=keep))
+            self._decode(z_chd, z_rhy, req)
             est_x = self.decoder.last_xhat[:, :, 1:, :].cpu().numpy()
         return est_x
 
@@ -505,16 +512,14 @@ class DisentangleVAE(PytorchModel):
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
         inference_decode's (the chord decoder keeps its argmax).  return_logprob=True appends the decode's log-probabilities
         (PtvaeDecoder.decode_logprob: a DecodeLogprob of device tensors) as a seventh element."""
-        from .ptvae import _require_cuda
-        sampling = dict(temperature=temperature, dur_temperature=dur_temperature, seed=seed, draw=draw, sample_offset=sample_offset,
-                        top_k=top_k, min_p=min_p, top_p=top_p, pitch_mask=pitch_mask, ascending=ascending, keep=keep)
-        self._check_decode(sampling, z_chd.shape[0])                    # (bad values are a ValueError whatever device the inputs are on)
+        kw = locals()
+        req = self._request(z_chd.shape[0], **{k: kw[k] for k in DECODE_KEYS})   # (bad values are a ValueError whatever device the inputs are on)
         _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
-            self._decode(z_chd, z_rhy, sampling)
+            self._decode(z_chd, z_rhy, req)
             pr_mat, notes, count, x, err = self.decoder.grid_to_pr_and_notes_batch(self.decoder.last_xhat, max_notes)
             c, _ = self.chd_decoder.decode_tokens(z_chd)
             if return_logprob:
@@ -550,25 +555,15 @@ class DisentangleVAE(PytorchModel):
         wins.  err is the output path's, with two bits above it: bit 8 = a candidate of the row held a decision outside the recomputed kept
         set (never on the decoder's own outputs), bit 9 = every score of the row was NaN (candidate 0 is returned).  A temperature
         is required: without one there is one candidate."""
-        from .functional_free import Keep
-        from .ptvae import _require_cuda
-        from ._lib import call, ptr, stream_ptr
         self._check_best_of(n, rank_by, length_normalize, **sampling)
         B = z_chd.shape[0]
-        self._check_decode(sampling, B)
+        req = self._request(B, **sampling)
         _require_cuda(z_chd, 'DisentangleVAE.decode_best_of')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_best_of')
-        tiled = dict(sampling)
-        mask, keep = sampling.get('pitch_mask'), sampling.get('keep')
-        if mask is not None and mask.shape[0] == B and B > 1:
-            tiled['pitch_mask'] = mask.repeat(n, 1, 1)
-        if keep is not None:
-            tiled['keep'] = Keep(keep.pitch.view(15, 32, 1, B).expand(15, 32, n, B).reshape(15, 32 * n * B),
-                                 keep.dur.view(5, 15, 32, 1, B).expand(5, 15, 32, n, B).reshape(5, 480 * n * B), keep.err.repeat(n), n * B)
         self.eval()
         refresh_weight_shadows()
         with torch.no_grad():
-            self._decode(z_chd.repeat(n, 1), z_rhy.repeat(n, 1), tiled)
+            self._decode(z_chd.repeat(n, 1), z_rhy.repeat(n, 1), req.tiled(n))
             lp = self.decoder.decode_logprob()
             sums = torch.cat([lp.logp, lp.logq], dim=1)
             score = (lp.logp if rank_by == 'logp' else lp.logq).sum(1)
@@ -597,7 +592,7 @@ class DisentangleVAE(PytorchModel):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant; **sampling: the keywords of a sampled
         decode (inference_decode), here and in swap / posterior_sample / prior_sample / interp -- a bad value is a ValueError before
         anything is encoded"""
-        self._check_decode(sampling, pr_mat.shape[0])
+        req = self._request(pr_mat.shape[0], **sampling)
         if self.detrended:
             self._check_dt_x(pr_mat)                     # (a piano-roll here is a ValueError, not a shape crash inside a kernel)
         self.eval()
@@ -607,7 +602,7 @@ class DisentangleVAE(PytorchModel):
             dist_rhy = self._encode_texture(pr_mat)
             z_chd = self._rsample('chd', dist_chd) if sample else dist_chd.mean
             z_rhy = self._rsample('rhy', dist_rhy) if sample else dist_rhy.mean
-        return self.inference_decode(z_chd, z_rhy, **sampling)
+        return self._inference_decode(z_chd, z_rhy, req)
 
     # ---- model.py:144-148
     def swap(self, pr_mat1, pr_mat2, c1, c2, fix_rhy, fix_chd, **sampling):
@@ -619,9 +614,9 @@ class DisentangleVAE(PytorchModel):
     # ---- model.py:150-172
     def posterior_sample(self, pr_mat, c, scale=None, sample_chd=True, sample_txt=True, **sampling):
         """pr_mat: the texture encoder's input -- the piano-roll, or dt_x for the detrended variant"""
-        self._check_decode(sampling, pr_mat.shape[0])
         if scale is None and sample_chd and sample_txt:
             return self.inference(pr_mat, c, sample=True, **sampling)
+        req = self._request(pr_mat.shape[0], **sampling)
         dist_chd, dist_rhy = self.inference_encode(pr_mat, c)
         if scale is not None:
             dist_chd = HipNormal(dist_chd.mean, dist_chd.scale * scale)
@@ -635,12 +630,12 @@ class DisentangleVAE(PytorchModel):
                 z_chd = dist_chd.mean
             if not sample_txt:
                 z_rhy = dist_rhy.mean
-        return self.inference_decode(z_chd, z_rhy, **sampling)
+        return self._inference_decode(z_chd, z_rhy, req)
 
     # ---- model.py:174-184
     def prior_sample(self, x, c, sample_chd=False, sample_rhy=False, scale=1., **sampling):
         """x: the texture encoder's input (the reference's name for this slot here) -- the piano-roll, or dt_x for the detrended variant"""
-        self._check_decode(sampling, x.shape[0])
+        req = self._request(x.shape[0], **sampling)
         dist_chd, dist_rhy = self.inference_encode(x, c)
         mean = torch.zeros_like(dist_rhy.mean)
         loc = torch.ones_like(dist_rhy.mean) * scale
@@ -650,7 +645,7 @@ class DisentangleVAE(PytorchModel):
             dist_rhy = HipNormal(mean, loc)
         with torch.no_grad():
             z_chd, z_rhy = self._rsample('chd', dist_chd), self._rsample('rhy', dist_rhy)
-        return self.inference_decode(z_chd, z_rhy, **sampling)
+        return self._inference_decode(z_chd, z_rhy, req)
 
     # ---- model.py:186-188
     def gt_sample(self, x):
@@ -660,15 +655,14 @@ class DisentangleVAE(PytorchModel):
     def interp(self, pr_mat1, c1, pr_mat2, c2, interp_chd=False, interp_rhy=False, int_count=10, **sampling):
         """pr_mat1 / pr_mat2: texture encoder inputs -- piano-rolls, or dt_x grids for the detrended variant; a sampled decode's sample
         index is the row of the flattened [bs * int_count] batch, and so are the rows of a pitch_mask (or it has one row)"""
-        self._check_decode(sampling, pr_mat1.shape[0] * int_count)
+        req = self._request(pr_mat1.shape[0] * int_count, **sampling)
         dist_chd1, dist_rhy1 = self.inference_encode(pr_mat1, c1)
         dist_chd2, dist_rhy2 = self.inference_encode(pr_mat2, c2)
         z_chd1, z_rhy1, z_chd2, z_rhy2 = dist_chd1.mean, dist_rhy1.mean, dist_chd2.mean, dist_rhy2.mean
         z_chds = self.interp_z(z_chd1, z_chd2, int_count) if interp_chd else z_chd1.unsqueeze(1).repeat(1, int_count, 1)
         z_rhys = self.interp_z(z_rhy1, z_rhy2, int_count) if interp_rhy else z_rhy1.unsqueeze(1).repeat(1, int_count, 1)
         bs = z_chds.size(0)
-        estxs = self.inference_decode(z_chds.reshape(bs * int_count, -1).contiguous(),
-                                      z_rhys.reshape(bs * int_count, -1).contiguous(), **sampling)
+        estxs = self._inference_decode(z_chds.reshape(bs * int_count, -1).contiguous(), z_rhys.reshape(bs * int_count, -1).contiguous(), req)
         return estxs.reshape((bs, int_count, 32, 15, -1))
 
     # ---- model.py:211-216: [B,D] x [B,D] -> [B,int_count,D]; the reference loops over numpy rows on the host, here the

@@ -234,6 +234,25 @@ def chord_tokens(root, chroma, bass):
 
 
 DecodeLogprob = collections.namedtuple('DecodeLogprob', 'logp logq counts err step_logp step_counts')
+LastDecode = collections.namedtuple('LastDecode', 'pitch dur xhat sampling force')      # what an inference decode leaves for decode_logprob()
+
+
+class _DecodeGraph(collections.namedtuple('_DecodeGraph', 'graph z outs block mask mask_addr force')):
+    """one captured inference decode: graph, z (static input), outs (static outputs), block / mask / mask_addr (static sampling block, the
+    static pitch mask of a constrained one and the one-word tensor holding that mask's address; None where the kind has none), force (the
+    static force arrays of a decode with kept steps, or None)"""
+
+    def refresh(self, z, sampling, keep):
+        """the caller's inputs into the static tensors, before every replay"""
+        self.z.copy_(z)
+        if self.force is not None:
+            self.force['pitch'].copy_(keep.pitch)
+            self.force['dur'].copy_(keep.dur)
+        if self.block is not None:
+            self.block.copy_(sampling)
+            if self.mask is not None and sampling.pitch_mask is not None:
+                self.mask[:sampling.pitch_mask.shape[0]].copy_(sampling.pitch_mask)   # (a one-row mask: row 0, the block's flag says so)
+                self.block[7:8].copy_(self.mask_addr)
 
 
 class PtvaeDecoder(nn.Module, _PrecMixin):
@@ -282,39 +301,36 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         self._summary = None
         self.summaries_needed = True       # emb_x() starts the ground-truth note summaries early unless told they are dead values
         self.last_dur_idx = None
-        self._last_decode = None           # (pitch, dur, xhat, sampling block, force arrays) of the last inference decode: decode_logprob()
+        self._last_decode = None           # LastDecode of the last inference decode: decode_logprob()
 
     def _params(self):
         sd = dict(self.named_parameters())
         return [sd[n] for n in F_.DEC_PARAM_NAMES]
 
     def _graph_decode(self, z, coins, sampling=None, keep=None):
-        """Free-running decode replayed from a captured hipGraph: the step loop is ~9,000 tiny launches whose
-        order and arguments depend only on (B, precision) -- capture once, then one graph launch per call.
-        The graph holds raw parameter pointers, so it is re-captured if the parameter storage moves.
-        A sampled decode is a graph of its own (other kernels); its sampling block is a static tensor refreshed before every
-        replay, so the key holds neither seed nor draw nor temperatures.  A truncated sampled decode (a 6-word block: top_k / min_p /
-        top_p) is a third kind: the key gains that one bit, the values of top_k / min_p / top_p live in the block like seed and draw --
-        one capture serves them all.  A constrained decode (an 8-word block: pitch_mask / ascending) is a fourth kind: its mask is copied
-        into a static tensor before every replay and the static block's address word points at that tensor, so one capture serves every
-        mask, flag, seed and draw.  A decode with kept steps (keep: functional_free.Keep) doubles the kinds: the key gains one bit beside the
-        kind, the capture holds static force arrays into which the caller's are copied before every replay, so one capture serves every
-        keep; without a keep the keys and the graphs are what they were."""
+        """Free-running decode replayed from a captured hipGraph: the step loop is ~9,000 tiny launches whose order and arguments depend
+        only on (B, precision) -- capture once, then one graph launch per call.  The graph holds raw parameter pointers, so it is
+        re-captured if the parameter storage moves.  Each kind of decode (functional_free.BlockKind: argmax, sampled, truncated,
+        constrained) is a graph of its own (other kernels), and kept steps (keep: functional_free.Keep) double the kinds: the key holds
+        the kind number and, only with a keep, one more element.  What a caller may vary -- z, seed / draw / temperatures / top_k / min_p
+        / top_p / flags in the block, the pitch mask, the force arrays of a keep -- lives in static tensors that _DecodeGraph.refresh
+        fills before every replay, so one capture per key serves them all."""
         ps = self._params_free()
-        kind = 0 if sampling is None else {4: 1, 6: 2, 8: 3}[sampling.numel()]
-        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind) + ((True,) if keep is not None else ())
+        kind = FF_.block_kind(sampling)
+        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind.kind) + ((True,) if keep is not None else ())
         ent = self._graphs.get(key)
         if ent is None:
-            static_z = z.detach().clone()
-            static_mask = mask_addr = None
-            static_force = None if keep is None else {'pitch': keep.pitch.clone(), 'dur': keep.dur.clone()}
+            block = mask = mask_addr = None
+            if kind.cons:                                      # (captured with every pitch allowed; the flags are the first caller's)
+                mask = torch.full((z.shape[0], 32, 4), -1, dtype=torch.int32, device=z.device)
+                mask_addr = torch.tensor([mask.data_ptr()], dtype=torch.int64, device=z.device)
             if sampling is not None:
-                ps = ps + [sampling.clone()]
-                if kind == 3:                                  # (captured with every pitch allowed; the flags are the first caller's)
-                    static_mask = torch.full((z.shape[0], 32, 4), -1, dtype=torch.int32, device=z.device)
-                    mask_addr = torch.tensor([static_mask.data_ptr()], dtype=torch.int64, device=z.device)
-                    ps[-1].pitch_mask = static_mask
-                    ps[-1][7:8].copy_(mask_addr if sampling.pitch_mask is not None else torch.zeros_like(mask_addr))
+                block = FF_.clone_block(sampling, mask)
+                ps = ps + [block]
+            if kind.cons:
+                block[7:8].copy_(mask_addr if sampling.pitch_mask is not None else torch.zeros_like(mask_addr))
+            static_z = z.detach().clone()
+            force = None if keep is None else {'pitch': keep.pitch.clone(), 'dur': keep.dur.clone()}
             cur = torch.cuda.current_stream()
             # warm-up and capture share ONE stream (as graph_step.py): the library's split-K workspaces are per stream and cannot be
             # allocated inside a capture -- captured on another stream the small products fell back to fp32 atomics, and the replayed
@@ -323,27 +339,18 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             s = self._graph_stream = self._graph_stream or torch.cuda.Stream(device=z.device)
             s.wait_stream(cur)
             with torch.cuda.stream(s):                         # warm-up outside capture (lazy inits, allocator)
-                FF_.DecoderStepFn.apply(static_z, None, None, coins, True, static_force, self._prec, *ps)
+                FF_.DecoderStepFn.apply(static_z, None, None, coins, True, force, self._prec, *ps)
             cur.wait_stream(s)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
-                outs = FF_.DecoderStepFn.apply(static_z, None, None, coins, True, static_force, self._prec, *ps)
+                outs = FF_.DecoderStepFn.apply(static_z, None, None, coins, True, force, self._prec, *ps)
             for k in [k for k in self._graphs if k[4:] == key[4:]]:         # one graph per kind (argmax, sampled, truncated, constrained; each
                 del self._graphs[k]                                         # with and without kept steps) is kept
             self.graph_captures += 1
-            ent = self._graphs[key] = (g, static_z, outs, ps[-1] if sampling is not None else None, static_mask, mask_addr, static_force)
-        g, static_z, outs, static_blk, static_mask, mask_addr, static_force = ent
-        static_z.copy_(z)
-        if static_force is not None:
-            static_force['pitch'].copy_(keep.pitch)
-            static_force['dur'].copy_(keep.dur)
-        if static_blk is not None:
-            static_blk.copy_(sampling)
-            if static_mask is not None and sampling.pitch_mask is not None:
-                static_mask[:sampling.pitch_mask.shape[0]].copy_(sampling.pitch_mask)   # (a one-row mask: row 0, the block's flag says so)
-                static_blk[7:8].copy_(mask_addr)
-        g.replay()
-        return outs
+            ent = self._graphs[key] = _DecodeGraph(g, static_z, outs, block, mask, mask_addr, force)
+        ent.refresh(z, sampling, keep)
+        ent.graph.replay()
+        return ent.outs
 
     def _params_free(self):
         sd = dict(self.named_parameters())
@@ -417,7 +424,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
                 pitch, dur, xhat, idx = FF_.DecoderStepFn.apply(z, None, None, coins, True, force, self._prec,
                                                                 *self._params_free(), *smp)
             self.last_dur_idx, self.last_xhat = idx, xhat
-            self._last_decode = (pitch, dur, xhat, sampling, force)      # what decode_logprob() reads: references, nothing copied (an eager decode's logits live until the next decode)
+            self._last_decode = LastDecode(pitch, dur, xhat, sampling, force)      # what decode_logprob() reads: references, nothing copied (an eager decode's logits live until the next decode)
             return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
         if coins is None:
             coins = self.draw_coins(teacher_forcing_ratio1, teacher_forcing_ratio2)
@@ -479,7 +486,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         counts = torch.empty(B, 4, device=dev, dtype=torch.int32)
         err = torch.empty(B, device=dev, dtype=torch.int32)
         F_.call('ptv_decode_logprob', F_.ptr(pitch), pitch.stride(2), F_.ptr(dur), F_.ptr(xhat), B, 1, F_.ptr(sampling),
-                0 if sampling is None else 8 * sampling.numel(), F_.ptr(fp), F_.ptr(fd), F_.ptr(step_logp), F_.ptr(step_counts),
+                FF_.block_kind(sampling).nbytes, F_.ptr(fp), F_.ptr(fd), F_.ptr(step_logp), F_.ptr(step_counts),
                 F_.ptr(err), F_.stream_ptr())
         F_.call('ptv_decode_logprob_fold', F_.ptr(step_logp), F_.ptr(step_counts), B, F_.ptr(sums), F_.ptr(counts), F_.stream_ptr())
         return DecodeLogprob(sums[:, 0:2], sums[:, 2:4], counts, err, step_logp, step_counts)

@@ -48,7 +48,8 @@ def scale_mask():
 
 def last_decode(m):
     """the decode's own logits and grid in the API shapes (host)"""
-    pitch, dur, xhat, _, _ = m.decoder._last_decode
+    last = m.decoder._last_decode
+    pitch, dur, xhat = last.pitch, last.dur, last.xhat
     n = xhat.shape[0]
     return (KT.host(pitch.permute(2, 1, 0, 3)), KT.host(dur.view(15, 32, n, 5, 2).permute(2, 1, 0, 3, 4)), KT.host(xhat))
 

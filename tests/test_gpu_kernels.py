@@ -1305,13 +1305,24 @@ def test_decoder_node_records_the_kernels_it_ran_and_its_composites_equal_the_py
         assert (n_f, n_b) == (0, 0) and s.prec == 0 and s.B == B
         return
     if case == 'step-loop':
-        s, _, _, _ = step(0.)
+        s, _, _, on = step(0.)
         assert isinstance(s, FF_.DecoderStepState) and s.notes == 'rows' and s.live_top is None and s.sorted is None
         assert (s.heads, s.dur) == ('fused', 'fused16')         # (the bf16 state copies exist: the fused backward halves read them)
         R, E, He = 32 * B, s.E, s.He
         assert s.TOK.shape == (15, R, E) and s.PRED.shape == (16, R, E) and s.xhat.shape == (B, 32, 16, 6) and s.plen.shape == (R,)
         assert [len(v) for v in (s.XH, s.XG, s.XH16)] == [2, 2, 2] and s.XH[0].shape == (17, R, He)
         assert s.skipped == F_.ZERO_SKIP and len(s.coins) == 2 and s.has_xs in (True, False)
+        # the plan the forward ran by, and the same step sequenced from Python instead of through ptv_decoder_free_fwd / _bwd: the plan names
+        # the same path in everything but `comp`, the outputs and every gradient carry the same bits
+        p = s.plan
+        assert isinstance(p, FF_.FreePlan) and (p.train, p.fast, p.comp, p.replay, p.need_resum) == (True, True, True, True, True)
+        assert p.kind is FF_.ARGMAX and p.state16 and p.ns16 and not p.capturing and p.cluster == FF_.note_loop_cluster(B)
+        monkeypatch.setattr(FF_, 'FREE_COMPOSITE', False)
+        s2, _, _, off = step(0.)
+        assert s2.plan == p._replace(comp=False) and (s2.notes, s2.heads, s2.dur) == (s.notes, s.heads, s.dur)
+        assert len(on) == len(off)
+        for a, b in zip(on, off):
+            assert torch.equal(a, b)
         return
     comp = case == 'composite'
     monkeypatch.setattr(F_, 'DEC_COMPOSITE', comp)

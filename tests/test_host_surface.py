@@ -1,5 +1,6 @@
 """CPU: the host-side mirror keeps the reference's class surface, state_dict keys, default
 initialisation and schedules.  No kernels run here (the model refuses CPU tensors)."""
+import ctypes
 import warnings
 
 import numpy as np
@@ -426,3 +427,183 @@ def test_decoder_state_refuses_what_no_forward_leaves():
     want = ([v for k, v in kw.items() if k not in ('dur_tabs', 'gates_d')] + list(kw['dur_tabs']) + list(srt_p) + [top]
             + [loop_p[k] for k in ('TOK', 'PRED', 'xhat', 'plen')] + loop_p['XH'] + loop_p['XG'] + loop_p['XH16'])
     assert len(want) == 14 + 5 + 1 + 10 and {id(x) for x in seen} == {id(x) for x in want}
+
+
+# ---- the free-running decode's host path: the kind of a block, the note loop's word, the coin masks, the decode request, the plan
+KIND_TABLE = {None: (0, 0, 0, 0, 0, 0, 'ptv_note_token', 'ptv_dur_gru_fwd', 'ptv_dur_out_token'),
+              4: (4, 0x800000, 0, 0, 1, 32, 'ptv_note_token_sample', 'ptv_dur_gru_fwd_sample', 'ptv_dur_out_token_sample'),
+              6: (6, 0x1800000, 1, 0, 2, 48, 'ptv_note_token_sample_trunc', 'ptv_dur_gru_fwd_sample', 'ptv_dur_out_token_sample'),
+              8: (8, 0x3800000, 1, 1, 3, 64, 'ptv_note_token_sample_cons', 'ptv_dur_gru_fwd_sample', 'ptv_dur_out_token_sample')}
+
+
+def _kind_of(words):
+    from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
+    return FF_.block_kind(None if words is None else torch.zeros(words, dtype=torch.int64))
+
+
+def test_block_kind_states_every_variant_once():
+    from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
+    for words, want in KIND_TABLE.items():
+        k = _kind_of(words)
+        assert tuple(k) == want
+        assert (k.words, k.bits, k.trunc, k.cons, k.kind, k.nbytes, k.note_token, k.dur_gru, k.dur_token) == want
+        with pytest.raises(AttributeError):
+            k.bits = 0                                                   # (immutable)
+    assert [_kind_of(w).kind for w in KIND_TABLE] == [0, 1, 2, 3]
+    assert (FF_.SAMPLE_BIT, FF_.TRUNC_BIT, FF_.CONS_BIT) == (0x800000, 0x1000000, 0x2000000)
+    for words in (0, 1, 3, 5, 7, 9, 16):
+        with pytest.raises(ValueError, match='sampling_block'):
+            _kind_of(words)
+    # the words sampling_words makes are the counts the kinds name
+    assert _kind_of(len(FF_.sampling_words(1.0))).kind == 1 and _kind_of(len(FF_.sampling_words(1.0, top_k=3))).kind == 2
+    assert _kind_of(len(FF_.sampling_words(1.0, ascending=True))).kind == 3
+
+
+def test_note_loop_word_is_the_parents_expression():
+    import itertools
+    from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
+    seen = set()
+    for train, replay, split, cluster, words in itertools.product((0, 1), (0, 1), (None, True, False), (0, 2, 4, 8), KIND_TABLE):
+        kind = _kind_of(words)
+        samp_bit = 0 if words is None else (0x800000 | {4: 0, 6: 0x1000000, 8: 0x1000000 | 0x2000000}[words])
+        want = ((2 if replay else int(train)) | (0 if split is None else (0x20000 if split else 0x10000))
+                | (0x400000 if cluster == 8 else (cluster << 18)) | samp_bit)
+        eager = FF_.note_loop_word(train, replay, split, cluster, kind)
+        assert eager == want
+        # the composite's form: the same word without the sampling bits (they travel as dims)
+        assert FF_.note_loop_word(train, replay, split, cluster) == want & ~0x3800000 == eager & ~kind.bits
+        assert FF_.note_loop_word(bool(train), bool(replay), split, cluster, kind) == want
+        seen.add((want, replay or train, split, cluster, words))
+    assert len(seen) == 2 * 3 * 4 * 4 + 3 * 4 * 4                        # (replay hides train: 3 distinct low fields, nothing else collides)
+
+
+def test_coin_masks():
+    from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
+    none = ([[False] * 14] * 32, [False] * 31)
+    every = ([[True] * 14] * 32, [True] * 31)
+    odd = ([[(t * 5 + n * 3) % 7 < 3 for n in range(14)] for t in range(32)], [t % 3 == 1 for t in range(31)])
+
+    def lists(coins, inference):
+        masks, time = FF_.coin_masks(coins, inference)
+        assert len(masks) == 32 and len(time) == 31 and masks._type_ is ctypes.c_uint and time._type_ is ctypes.c_ubyte
+        assert bytes(time) == bytes(list(time)) and all(type(masks[t]) is int for t in range(32))
+        return list(masks), list(time)
+    assert lists(none, False) == ([0] * 32, [0] * 31)
+    assert lists(every, False) == ([0x3fff] * 32, [1] * 31)
+    masks, time = lists(odd, False)
+    for t in range(32):
+        want = 0
+        for n in range(14):
+            want |= int(bool(odd[0][t][n])) << n
+        assert masks[t] == want and 0 <= want < 1 << 14
+    assert time == [int(t % 3 == 1) for t in range(31)] and len(set(masks)) > 4
+    for coins in (none, every, odd):                                     # inference: the kernels see no coin
+        assert lists(coins, True) == ([0] * 32, [0] * 31)
+    assert lists(([np.ones(14)] * 32, np.ones(31)), False) == ([0x3fff] * 32, [1] * 31)   # numpy / 0-1 coins count like bools
+
+
+NAN, INF = float('nan'), float('inf')
+BAD_DECODE_KEYWORDS = [
+    # sampling (test_sample_ref_host)
+    dict(temperature=-0.5), dict(temperature=NAN), dict(temperature=INF), dict(temperature=1.0, dur_temperature=-1.0),
+    dict(temperature=1.0, dur_temperature=NAN), dict(temperature=1.0, sample_offset=-1), dict(temperature='1'), dict(seed=3), dict(draw=1),
+    dict(sample_offset=4), dict(temperature=1.0, seed=-1), dict(temperature=1.0, seed=1 << 64), dict(temperature=1.0, draw=1 << 63),
+    dict(temperature=1.0, sample_offset=1 << 47), dict(temperature=True),
+    # truncation (test_gpu_truncated_sampling, test_nucleus_ref)
+    dict(top_k=8), dict(min_p=0.5), dict(top_p=0.5), dict(temperature=1.0, top_k=0), dict(temperature=1.0, top_k=-3),
+    dict(temperature=1.0, top_k=True), dict(temperature=1.0, top_k=2.0), dict(temperature=1.0, min_p=1.5), dict(temperature=1.0, min_p=-0.1),
+    dict(temperature=1.0, min_p=NAN), dict(temperature=1.0, min_p=INF), dict(temperature=1.0, min_p=True), dict(temperature=1.0, top_p=0.0),
+    dict(temperature=1.0, top_p=1.5), dict(temperature=1.0, top_p=NAN), dict(temperature=1.0, top_p=True), dict(ascending=True, top_k=3),
+    # constraints (test_gpu_constrained_decode): what needs no device
+    dict(pitch_mask=torch.zeros(2, 32, 4, dtype=torch.int32)), dict(pitch_mask=np.zeros((2, 32, 4), dtype=np.int32)), dict(ascending=1),
+    dict(ascending='yes'), dict(temperature=1.0, ascending=0), dict(temperature=1.0, pitch_mask=torch.zeros(1, 32, 4, dtype=torch.int32)),
+    # keep (test_keep_ref_host)
+    dict(keep={'pitch': None, 'dur': None}), dict(keep=(1, 2, 3, 4)), dict(temperature=1.0, keep='first bar')]
+
+
+@pytest.mark.parametrize('kw', BAD_DECODE_KEYWORDS, ids=lambda kw: ','.join('%s=%s' % (k, type(v).__name__ if hasattr(v, 'shape') else v)
+                                                                         for k, v in kw.items()))
+def test_decode_request_raises_what_the_keywords_always_raised_and_moves_nothing(kw):
+    m = M.DisentangleVAE.init_model(torch.device('cpu'))
+    m._sample_draws = 5
+    m.train()
+    with pytest.raises(ValueError) as direct:
+        M.DisentangleVAE._check_sampling(**kw, batch=2)
+    z, tex, c = torch.zeros(2, 256), torch.zeros(2, 32, 128), torch.zeros(2, 8, 36)
+    calls = [lambda: m._request(2, **kw), lambda: m.inference_decode(z, z, **kw), lambda: m.decode_to_inputs(z, z, **kw),
+             lambda: m.decode_logprob(z, z, **kw), lambda: m.reencode(z, z, **kw), lambda: m.inference(tex, c, False, **kw),
+             lambda: m.swap(tex, tex, c, c, True, True, **kw), lambda: m.posterior_sample(tex, c, **kw),
+             lambda: m.posterior_sample(tex, c, scale=2.0, **kw), lambda: m.prior_sample(tex, c, **kw),
+             lambda: m.interp(tex, c, tex, c, int_count=1, **kw)]
+    if kw.get('temperature') is not None or kw.get('dur_temperature') is not None:
+        calls.append(lambda: m.decode_best_of(z, z, 2, **kw))
+    for fn in calls:
+        with pytest.raises(ValueError) as got:
+            fn()
+        assert str(got.value) == str(direct.value)                       # the validator's own text, whichever entry point was asked
+        assert m._sample_draws == 5 and m.training                       # before eval(), before the draw counter moves
+
+
+def test_decode_request_carries_the_validated_keywords():
+    m = M.DisentangleVAE.init_model(torch.device('cpu'))
+    req = m._request(3)
+    assert isinstance(req, M.DecodeRequest) and req.sampled is False and req.mask is None and req.keep is None and req.batch == 3
+    assert set(req.kw) == set(M.DECODE_KEYS[:-2]) and all(v is None for v in req.kw.values())
+    assert m._sampling_words(req) is None and m._sample_draws == 0
+    req = m._request(3, temperature=0.5, top_k=4, seed=9)
+    assert req.sampled is True and req.kw['temperature'] == 0.5 and req.kw['top_k'] == 4 and req.kw['seed'] == 9 and req.kw['draw'] is None
+    from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
+    assert m._sampling_words(req) == FF_.sampling_words(0.5, None, 9, 0, 0, top_k=4) and m._sample_draws == 1
+    assert m._sampling_words(req) == FF_.sampling_words(0.5, None, 9, 1, 0, top_k=4) and m._sample_draws == 2
+    assert m._sampling_words(m._request(3, temperature=0.5, draw=7)) == FF_.sampling_words(0.5, None, 7, 7, 0) and m._sample_draws == 2
+    assert m._sampling_words(m._request(3, ascending=False)) == FF_.sampling_words(0.0, 0.0, 0, 0, 0, ascending=False) and m._sample_draws == 2
+    assert req.tiled(4).batch == 12 and req.tiled(4).kw is req.kw and req.tiled(4).mask is None and req.tiled(4).keep is None
+    with pytest.raises(TypeError):
+        m._request(3, temperatur=1.0)
+
+
+def test_free_plan_decides_the_step_loops_path_once(monkeypatch):
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_, functional_free as FF_
+    for mod, name, v in ((FF_, 'FREE_COMPOSITE', True), (FF_, 'FREE_PERSIST', True), (FF_, 'FREE_REPLAY', True), (FF_, 'NOTE_LOOP_SPLIT', None),
+                         (FF_, 'NOTE_LOOP_CLUSTER', None), (FF_, 'NOTE_CLUSTER8', True), (FF_, 'NOTE_CLUSTER4_MAX_WGS', 0),
+                         (F_, 'BF16_STORAGE', True), (F_, 'NOTES_PERSIST', True), (F_, 'FUSED_DUR', True)):
+        monkeypatch.setattr(mod, name, v)
+    B = 17
+    dims = (B, 32 * B, 128, 128, 1024, 512, 64, 130)                    # init_model()
+    none = ([[False] * 14] * 32, [False] * 31)
+    mixed = ([[n % 2 == 0 for n in range(14)]] * 32, [t % 2 == 0 for t in range(31)])
+    every_time = ([[False] * 14] * 32, [True] * 31)
+    f32, kind = torch.float32, FF_.ARGMAX
+
+    def plan(prec=1, coins=none, inference=False, needs_grad=True, forced=False, kind=kind, ncu=256, capturing=False, z=f32, dims=dims):
+        return FF_._free_plan(prec, dims, z, coins, inference, needs_grad, forced, kind, ncu, capturing)
+    assert FF_.FreePlan._fields[:8] == ('train', 'fast', 'comp', 'replay', 'need_resum', 'cluster', 'capturing', 'kind')
+    # inference: nothing is saved, the composite runs, every time token is re-summarised, two panels take eight members each
+    p = plan(inference=True, needs_grad=False, kind=FF_.SAMPLED)
+    assert tuple(p) == (False, True, True, False, True, 8, False, FF_.SAMPLED, False, True)
+    assert tuple(plan(inference=True)) [:6] == (False, True, True, False, True, 8)            # (a z that needs a gradient changes nothing)
+    # training, all coins false: the replayed loop and the batched recompute on bf16 state copies
+    p = plan()
+    assert tuple(p) == (True, True, True, True, True, 8, False, kind, True, True)
+    assert plan(needs_grad=False).train is False and plan(needs_grad=False).replay is False
+    # training, mixed coins: the same path; only with every time coin true no token is re-summarised
+    assert tuple(plan(coins=mixed)) == tuple(p)
+    assert plan(coins=every_time)._replace(need_resum=True) == p and plan(coins=every_time).need_resum is False
+    # force arrays: no replay
+    assert plan(forced=True) == p._replace(replay=False)
+    # prec = 0: the plain loop
+    p0 = plan(prec=0)
+    assert tuple(p0) == (True, False, False, False, True, 0, False, kind, False, False)
+    assert tuple(plan(prec=0, inference=True, needs_grad=False))[:6] == (False, False, False, False, True, 0)
+    # the composite needs an fp32 z and the switch; another geometry takes the plain loop
+    assert plan(z=torch.float64) == p._replace(comp=False)
+    monkeypatch.setattr(FF_, 'FREE_COMPOSITE', False)
+    assert plan() == p._replace(comp=False)
+    monkeypatch.setattr(FF_, 'FREE_COMPOSITE', True)
+    assert plan(dims=(B, 32 * B, 20, 12, 40, 28, 8, 130)).fast is False
+    # the cluster choice by panels and compute units, and the capture rule that zeroes it (a captured TRAINING forward only)
+    assert [plan(dims=(b,) + dims[1:]).cluster for b in (16, 512, 528, 1024, 1040, 2048, 2064)] == [8, 8, 4, 4, 2, 2, 0]
+    assert plan(ncu=8).cluster == 4 and plan(ncu=4).cluster == 2 and plan(ncu=2).cluster == 0
+    assert plan(capturing=True) == p._replace(cluster=0, capturing=True)
+    with torch.no_grad():
+        assert plan(capturing=True, inference=True, needs_grad=False).cluster == 8
