@@ -1148,7 +1148,11 @@ int ptv_decoder_free_bwd(const void* const* t_tf, const long* d_tf, const void* 
  *        [T][4] planes (r, z, n, W_hn h + b_hn) or NULL -- PRIVATE to this forward / BPTT pair: each plane is unit-blocked by 16,
  *        plane[u / 16][row][u % 16] (whole-kilobyte wave accesses), not the [R][512] of ptv_gru_seq_fwd.
  *        T: bits 0-7 = steps (1 .. 255; 0 steps: PTV_ERR_ARG); bits 8-15 = debug flags and bits 16-23 = weight-ring depth of the timing
- *        scripts (0 = defaults); bit 24: see ptv_notes_gru_persist_fwd_rows.  R <= 1048575 (32-bit buffer offsets: R * 2048 bytes of h0
+ *        scripts (0 = defaults); bit 24: see ptv_notes_gru_persist_fwd_rows; bits 25-26 = panel height (rows per workgroup): 0 = 64
+ *        (what every caller that does not set them gets), 1 = 32, 2 = the library's rule (32 rows when 64-row panels would leave the
+ *        dispatcher nothing to balance with: ceil(R / 64) <= CUs / 2, or row_len given and ceil(R / 64) <= CUs; else 64), 3: PTV_ERR_ARG.
+ *        Both heights write the same bits to the same slots; the timing variants (bits 8-10, 16-23) exist at 64 rows only
+ *        (PTV_ERR_UNSUPPORTED with 32).  R <= 1048575 (32-bit buffer offsets: R * 2048 bytes of h0
  *        within one descriptor), PTV_ERR_UNSUPPORTED above.
  *   bwd: wt = pack(W_hh^T [512,1536]) (pairs = 1); HN16 / gates as the forward left them (the previous state enters the gate
  *        gradients at bf16 precision); ext bf16 = gradient arriving at the state after step s, the [T*R][512] matrix of the heads'
@@ -1160,7 +1164,10 @@ int ptv_decoder_free_bwd(const void* const* t_tf, const long* d_tf, const void* 
  *        initialised to -1 by the caller) receives the last step at which anything arrived for any panel, so that the products over dgi /
  *        dgh can stop after that step's rows (ptv_wgrad k_top).
  *        T: bits 0-7 = steps on every path (0 steps: PTV_ERR_ARG); bits 8-15 = flags of the timing scripts, bit 16: see
- *        ptv_notes_gru_persist_bwd_rows (both read by the 8-wave kernel only).  8-wave kernel: R <= 699050 (R * 3072 bytes of a dgi step within
+ *        ptv_notes_gru_persist_bwd_rows; bits 17-18 = panel height, as bits 25-26 of the forward's T (0 = 64 rows, 1 = 32, 2 = the
+ *        library's rule): same dgi / dgh / dh0 / top_step, except that the zero-row scan is per panel -- a 32-row panel may write as
+ *        zero rows what the 64-row panel around it computes as zeros of either sign; the 32-row kernel does not touch `scratch` (all
+ *        read by the 8-wave kernel only).  8-wave kernel: R <= 699050 (R * 3072 bytes of a dgi step within
  *        one buffer descriptor) and R * (16 * steps - 1) <= 67108863 (the 32-bit offset into ext), PTV_ERR_UNSUPPORTED above; the 4-wave kernel
  *        addresses with 64-bit offsets: R <= 2^31 - 1.
  */

@@ -36,6 +36,11 @@ int ptv_prof_read_limited(int tag, double* lim15, double* lim16);
 /* the part of lim15 whose products also skip the dead 128-row blocks of every note step (ptv_wgrad_job.seg_n) */
 int ptv_prof_read_segmented(int tag, double* seg);
 
+/* A/B / test aid: what "the library's rule" of the notes GRU panel height (ptvae_hip.h, T bits 25-26 of ptv_notes_gru_persist_fwd*, bits
+ * 17-18 of ptv_notes_gru_persist_bwd*) answers: 0 (default) = the rule itself, 64 / 32 = that height.  Callers that force a height
+ * are not affected.  Process-wide. */
+int ptv_debug_notes_panel_rule(int rows);
+
 /* A/B aid: 0 = ptv_wgrad_batch issues its products one by one (same bits, one product + one reduction launch each); 1 (default) = batched.
  * Process-wide; PTV_WGRAD_BATCH=0 sets it at load. */
 int ptv_wgrad_batch_mode(int batched);

@@ -130,7 +130,8 @@ extern "C" int ptv_decoder_tf_fwd(const void* const* t, const long* d, void* str
   // note slots; the three launches below then leave the later steps' rows of their outputs unwritten)
   const int* live = (const int*)T_(t, PTV_DTF_LIVE_TOP);
   PTV_TRY(ptv_notes_gru_persist_fwd_rows(T_(t, PTV_DTF_PK_NOTES_H), T_(t, PTV_DTF_PK_NOTES_T), (const float*)T_(t, PTV_DTF_B_HH_N), T_(t, PTV_DTF_GC),
-                                         tok, HN, HN16, M_<void>(t, PTV_DTF_GATES_N), R, 15 | (sorted && t[PTV_DTF_SEG_N] ? (1 << 24) : 0), live, row_len, stream));
+                                         tok, HN, HN16, M_<void>(t, PTV_DTF_GATES_N), R, 15 | (sorted && t[PTV_DTF_SEG_N] ? (1 << 24) : 0) | (2 << 25), live, row_len,
+                                         stream));                           // (bits 25-26 = 2: panel height by the library's rule)
   // ---- pitch head + initial duration state in one pass over the note states (ptvae.py:343-352)
   PTV_TRY(ptv_heads_fwd_rows(HN16 + (long)R * Hn, T_(t, PTV_DTF_PK_WP), T_(t, PTV_DTF_PK_WDH), T_(t, PTV_DTF_PK_WDP), (const float*)T_(t, PTV_DTF_B_P),
                              (const float*)T_(t, PTV_DTF_B_DH), M_<float>(t, PTV_DTF_PITCH), ldp, HD, HD16, M, live, R, row_len, stream));
@@ -357,7 +358,7 @@ extern "C" int ptv_decoder_tf_bwd(const void* const* t, const long* d, void* str
   const __bf16* wt_ih_n = (const __bf16*)T_(t, PTV_DTB_WT_IH_N);   // [Ht + E, 3Hn]
   ptv_gemm_priority(1);
   PTV_TRY(ptv_notes_gru_persist_bwd_rows(T_(t, PTV_DTB_PK_NOTES_WT), T_(t, PTV_DTB_HN16), T_(t, PTV_DTB_GATES_N), dNSUM, dgi_n, dgh_n, dHN0,
-                                         M_<void>(t, PTV_DTB_SCRATCH_N), R, 15 | (seg_n ? 0x10000 : 0), top_h, row_len, top_step, stream));
+                                         M_<void>(t, PTV_DTB_SCRATCH_N), R, 15 | (seg_n ? 0x10000 : 0) | (2 << 17), top_h, row_len, top_step, stream));   // (bits 17-18 = 2: as the forward)
   PTV_TRY(ptv_sum_steps_seg(dGC, dgi_n, (long)R * 3 * Hn, 15, (long)R * 3 * Hn, 0, 1, top_step, seg_n, 3L * Hn, stream));
   if (hipMemsetAsync(dtok + 15L * R * E, 0, sizeof(float) * R * E, s) != hipSuccess) return PTV_ERR_LAUNCH;
   // (the dead row tiles of the token product store their zeros through the map too: every row of the 15 planes is written exactly once)

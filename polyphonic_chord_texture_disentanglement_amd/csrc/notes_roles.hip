@@ -20,6 +20,11 @@
 // Hand-off: two monotonic counters per pair in LDS (filled / drained), polled with s_sleep; LDS serves a wave's requests in order, so
 // data-then-flag needs no wait.  Two workgroup barriers per note step bracket the rewrite of the operand copy.
 //
+// Panel height (round 8): both kernels exist for panels of 64 rows (as described here) and of 32 rows -- half the row fragments per
+// mini-pass / M tiles per wave, one row per cell lane instead of two -- chosen per launch by notes_panel_rows below: a launch lasts as
+// long as its longest panel, and with ragged (length-sorted) rows twice as many, shorter panels give the dispatcher something to
+// balance.  Same bits at both heights.
+//
 // Layouts private to this kernel and its BPTT twin: GC and the four gate planes are UNIT-BLOCKED BY 16 ([u / 16][row][16] bf16): a cell
 // lane owns 8 consecutive units of two rows, so one wave access is one contiguous kilobyte.  Weights: ptv_pack_mfma_b with pairs = 0.
 #include "common.hpp"
@@ -34,16 +39,21 @@ extern int g_gemm_prio;
 
 namespace nr {
 
-constexpr int H = 512, E = 128, ROWS = 64, NUT = H / 16, KBH = H / 32, KBX = E / 32, KT = KBH + KBX;
+constexpr int H = 512, E = 128, NUT = H / 16, KBH = H / 32, KBX = E / 32, KT = KBH + KBX;
 constexpr int HLD = H + 16, TLD = E + 16;                 // bf16 LDS row strides (+16: conflict-free b128 fragment reads)
 constexpr int MPS = 8;                                    // mini-passes per product wave and step: 4 waves x 8 x 16 units = 512
-constexpr int SLOT_BYTES = 4 * ROWS * 16 * 4;             // [gate r z hn in][64 rows][16 units] fp32
-constexpr int OFF_H16 = 0;
-constexpr int OFF_TOK = OFF_H16 + ROWS * HLD * 2;
-constexpr int OFF_SLOT = OFF_TOK + ROWS * TLD * 2;
-constexpr int OFF_FLAG = OFF_SLOT + 4 * SLOT_BYTES;
-constexpr int OFF_BIAS = OFF_FLAG + 64;                    // b_hh fp32 [1536]: the product waves' vector-memory queue holds weights only
-constexpr int LDS_BYTES = OFF_BIAS + 3 * H * 4;
+// the LDS of a panel of ROWS rows (64: 156,736 bytes; 32: 33,792 + 9,216 + 32,768 + 64 + 6,144 = 81,984 bytes)
+template <int ROWS>
+struct Lds {
+  static_assert(ROWS == 64 || ROWS == 32, "panel height");
+  static constexpr int SLOT_BYTES = 4 * ROWS * 16 * 4;    // [gate r z hn in][ROWS rows][16 units] fp32
+  static constexpr int OFF_H16 = 0;
+  static constexpr int OFF_TOK = OFF_H16 + ROWS * HLD * 2;
+  static constexpr int OFF_SLOT = OFF_TOK + ROWS * TLD * 2;
+  static constexpr int OFF_FLAG = OFF_SLOT + 4 * SLOT_BYTES;
+  static constexpr int OFF_BIAS = OFF_FLAG + 64;           // b_hh fp32 [1536]: the product waves' vector-memory queue holds weights only
+  static constexpr int LDS_BYTES = OFF_BIAS + 3 * H * 4;
+};
 
 typedef __attribute__((ext_vector_type(4))) float f4v;
 typedef __attribute__((ext_vector_type(4))) unsigned u4v;
@@ -96,13 +106,19 @@ struct Args {
 
 // slot address of the 16-byte chunk j (units 4j .. 4j+3) of (gate, row): chunks are XOR-swizzled so that both the product wave's
 // fragment-shaped stores (16 rows x one chunk per instruction) and the cell wave's reads (32 rows x two chunks) are conflict-free
+template <int ROWS>
 __device__ __forceinline__ int slot_off(int gate, int row, int j) { return gate * (ROWS * 64) + row * 64 + ((j ^ ((row >> 2) & 1)) << 4); }
 
-template <int DF, int ABL>
+// ROWS = panel height, 64 or 32 (ptv_notes_panel_rows): M = ROWS / 16 row fragments per mini-pass, a cell lane owns 8 units of ROWS / 32
+// rows.  Rows are independent and every row's products accumulate over k in the same order: both heights give the same bits.
+template <int DF, int ABL, int ROWS>
 __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
+  constexpr int MT = ROWS / 16, NC = ROWS / 32;
+  constexpr int SLOT_BYTES = Lds<ROWS>::SLOT_BYTES, OFF_H16 = Lds<ROWS>::OFF_H16, OFF_TOK = Lds<ROWS>::OFF_TOK, OFF_SLOT = Lds<ROWS>::OFF_SLOT,
+                OFF_FLAG = Lds<ROWS>::OFF_FLAG, OFF_BIAS = Lds<ROWS>::OFF_BIAS;
   extern __shared__ __attribute__((aligned(16))) char nsm[];
-  __bf16* h16 = reinterpret_cast<__bf16*>(nsm + OFF_H16);                 // [64][HLD] the state as MFMA operand (single buffer)
-  __bf16* tok16 = reinterpret_cast<__bf16*>(nsm + OFF_TOK);               // [64][TLD] this step's fed tokens
+  __bf16* h16 = reinterpret_cast<__bf16*>(nsm + OFF_H16);                 // [ROWS][HLD] the state as MFMA operand (single buffer)
+  __bf16* tok16 = reinterpret_cast<__bf16*>(nsm + OFF_TOK);               // [ROWS][TLD] this step's fed tokens
   volatile int* flags = reinterpret_cast<volatile int*>(nsm + OFF_FLAG);  // [pair][0 = filled, 1 = drained]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -179,9 +195,9 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
       for (int f = 0; f < DF - 3; f++) ldw(ring[f], ut, f);
     }
     int cnt = 0;                                                              // mini-passes handed over so far
-    u4v tk[8];                                                                // the next step's fed tokens (fp32), this wave's quarter of the panel
+    u4v tk[ROWS / 8];                                                         // the next step's fed tokens (fp32), this wave's quarter of the panel
     for (int n = 0; n < T; n++) {
-      // next step's tokens of the panel: 32 KB contiguous, rows beyond R read as zero (descriptor bounds)
+      // next step's tokens of the panel: ROWS x 512 bytes contiguous, rows beyond R read as zero (descriptor bounds)
       const __amdgpu_buffer_rsrc_t rs_x = rsrc(a.x + (long)(n + 1 < T ? n + 1 : n) * a.x_step + r0 * E, min((long)ROWS, R - r0) * E * 4);
 #pragma unroll 1
       for (int mp = 0; mp < MPS; mp++) {
@@ -190,26 +206,26 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
         // waits for these), and by the loop's end all but the newest DF - 3 requests of the wave have returned -- these among them
         if (mp == MPS - 1 && n + 1 < T) {
 #pragma unroll
-          for (int j = 0; j < 8; j++) tk[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, (unsigned)(wave * 64 + lane) * 16u, (unsigned)j * 4096u, 0);
+          for (int j = 0; j < ROWS / 8; j++) tk[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, (unsigned)(wave * 64 + lane) * 16u, (unsigned)j * 4096u, 0);
         }
         const int u = ut * 16 + q * 4;                                         // this lane's 4 units of the tile (MFMA C layout)
         stamp(1);
-        f32x4 acc[4][4];                                                       // [M tile][r, z, W_hn h, W_in x]
+        f32x4 acc[MT][4];                                                      // [M tile][r, z, W_hn h, W_in x]
         {
           const float* bl = reinterpret_cast<const float*>(nsm + OFF_BIAS);
           const f32x4 bR = *reinterpret_cast<const f32x4*>(bl + u), bZ = *reinterpret_cast<const f32x4*>(bl + H + u),
                       bN = *reinterpret_cast<const f32x4*>(bl + 2 * H + u);
 #pragma unroll
-          for (int i = 0; i < 4; i++) { acc[i][0] = bR; acc[i][1] = bZ; acc[i][2] = bN; acc[i][3] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+          for (int i = 0; i < MT; i++) { acc[i][0] = bR; acc[i][1] = bZ; acc[i][2] = bN; acc[i][3] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         }
         // A fragments (state / token operand, LDS) run one k-block ahead of the MFMAs that consume them
-        bf16x8 av[2][4];
-        auto lda_ = [&](bf16x8 (&d)[4], int k) {
+        bf16x8 av[2][MT];
+        auto lda_ = [&](bf16x8 (&d)[MT], int k) {
           const bool tokpart = k >= KBH;
           const __bf16* A = tokpart ? tok16 : h16;
           const int lda = tokpart ? TLD : HLD, kb = tokpart ? k - KBH : k;
 #pragma unroll
-          for (int i = 0; i < 4; i++) d[i] = *reinterpret_cast<const bf16x8*>(A + (i * 16 + rl) * lda + kb * 32 + q * 8);
+          for (int i = 0; i < MT; i++) d[i] = *reinterpret_cast<const bf16x8*>(A + (i * 16 + rl) * lda + kb * 32 + q * 8);
         };
         lda_(av[0], 0);
 #pragma unroll
@@ -227,7 +243,7 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
           for (int g = 0; g < 3; g++) {
             const int slot_ = g < 2 ? g : (tokpart ? 3 : 2);
 #pragma unroll
-            for (int i = 0; i < 4; i++) acc[i][slot_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[(3 * k + g) % DF], av[k & 1][i], acc[i][slot_], 0, 0, 0);
+            for (int i = 0; i < MT; i++) acc[i][slot_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[(3 * k + g) % DF], av[k & 1][i], acc[i][slot_], 0, 0, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -236,9 +252,9 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
         flag_wait(f_drain, cnt);
         stamp(3);
 #pragma unroll
-        for (int i = 0; i < 4; i++)
+        for (int i = 0; i < MT; i++)
 #pragma unroll
-          for (int g = 0; g < 4; g++) *reinterpret_cast<f32x4*>(slot + slot_off(g, i * 16 + rl, q)) = acc[i][g];
+          for (int g = 0; g < 4; g++) *reinterpret_cast<f32x4*>(slot + slot_off<ROWS>(g, i * 16 + rl, q)) = acc[i][g];
         cnt++;
         flag_set(f_fill, cnt);
         stamp(4);
@@ -247,7 +263,7 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
       stamp(5);
       if (n + 1 < T) {
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
+        for (int j = 0; j < ROWS / 8; j++) {
           const int li = wave * 64 + lane, row = j * 8 + (li >> 5), c4 = (li & 31) * 4;
           bf16x4 o; o[0] = (__bf16)__uint_as_float(tk[j][0]); o[1] = (__bf16)__uint_as_float(tk[j][1]); o[2] = (__bf16)__uint_as_float(tk[j][2]); o[3] = (__bf16)__uint_as_float(tk[j][3]);
           *reinterpret_cast<bf16x4*>(tok16 + row * TLD + c4) = o;
@@ -258,14 +274,14 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
     }
   } else {
     // =========================================================================================================================
-    // CELL wave: lane = (row pair rr / rr + 32, unit half hh): 8 consecutive units of two rows per mini-pass
+    // CELL wave: lane = (row pair rr / rr + 32, unit half hh): 8 consecutive units of two rows per mini-pass (32-row panels: of row rr)
     // =========================================================================================================================
     const int cw = wave - 4;
     const int rr = lane >> 1, hh = lane & 1;
     const char* slot = nsm + OFF_SLOT + cw * SLOT_BYTES;
     volatile int* f_fill = flags + 2 * cw;
     volatile int* f_drain = flags + 2 * cw + 1;
-    long grow[2]; bool ok[2];
+    long grow[2]; bool ok[2];                                                 // (32-row panels: entry 0 only, c < NC below)
 #pragma unroll
     for (int c = 0; c < 2; c++) { ok[c] = r0 + rr + 32 * c < R; grow[c] = min(r0 + rr + 32 * c, R - 1); }
     int rotv = rot;                                                           // (re-read per step through an opaque copy: hipcc would hoist
@@ -275,12 +291,12 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
     const unsigned vo16[2] = {(unsigned)(grow[0] * 32 + hh * 16), (unsigned)(grow[1] * 32 + hh * 16)};       // unit-blocked bf16 planes
     const unsigned plane = (unsigned)(RH * 2);                                  // bytes of one [32][R][16] bf16 plane
     const __amdgpu_buffer_rsrc_t rs_gc = rsrc(a.gc, 3L * RH * 2);
-    struct Ops { u4v g[2][3]; };
+    struct Ops { u4v g[NC][3]; };
     auto ldops = [&](Ops& o, int mp) {
       const int ut = tile_of(mp);
       if constexpr (ABL & 2) return;
 #pragma unroll
-      for (int c = 0; c < 2; c++) {
+      for (int c = 0; c < NC; c++) {
 #pragma unroll
         for (int g = 0; g < 3; g++) o.g[c][g] = __builtin_amdgcn_raw_buffer_load_b128(rs_gc, vo16[c], (unsigned)g * plane + (unsigned)ut * (unsigned)(R * 32), 2);
       }
@@ -288,13 +304,13 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
     int cnt = 0;
     // the fp32 state of this lane's 128 cells lives in registers for the whole sequence: no per-step store + read-back of [R][512] fp32
     // (68 MB per step at B = 512 -- a third of the kernel's HBM traffic; the backward reads the bf16 copy HN16)
-    f4v st[MPS][2][2];
+    f4v st[MPS][NC][2];
     {
       const __amdgpu_buffer_rsrc_t rs_h0 = rsrc(a.h0, RH * 4);
 #pragma unroll
       for (int mp = 0; mp < MPS; mp++)
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
+        for (int c = 0; c < NC; c++) {
           const unsigned vo = (unsigned)(grow[c] * (H * 4) + hh * 32), so = (unsigned)tile_of(mp) * 64u;
           const u4v v0 = __builtin_amdgcn_raw_buffer_load_b128(rs_h0, vo, so, 0), v1 = __builtin_amdgcn_raw_buffer_load_b128(rs_h0, vo + 16u, so, 0);
 #pragma unroll
@@ -326,7 +342,7 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
         flag_wait(f_fill, cnt);
         stamp(12);
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
+        for (int c = 0; c < NC; c++) {
           const int row = rr + 32 * c;
           // two halves of 4 units: half the live values (the cell waves hold 64 registers of new state for the whole step)
           u4v r8, z8, n8, q8;
@@ -334,8 +350,8 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
           for (int hf = 0; hf < 2; hf++) {
             f4v ac[4];
 #pragma unroll
-            for (int g = 0; g < 4; g++) ac[g] = *reinterpret_cast<const f4v*>(slot + slot_off(g, row, 2 * hh + hf));
-            if (c == 1 && hf == 1) flag_set(f_drain, cnt);                     // (queued behind this wave's reads: LDS serves a wave in order)
+            for (int g = 0; g < 4; g++) ac[g] = *reinterpret_cast<const f4v*>(slot + slot_off<ROWS>(g, row, 2 * hh + hf));
+            if (c == NC - 1 && hf == 1) flag_set(f_drain, cnt);                     // (queued behind this wave's reads: LDS serves a wave in order)
             float r[4], z[4], nn[4], hn[4];
             f4v nv;
 #pragma unroll
@@ -374,7 +390,7 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
 #pragma unroll
       for (int mp = 0; mp < MPS; mp++)
 #pragma unroll
-        for (int c = 0; c < 2; c++)
+        for (int c = 0; c < NC; c++)
           *reinterpret_cast<u4v*>(h16 + (rr + 32 * c) * HLD + tile_of(mp) * 16 + hh * 8) =
               u4v{pk2(st[mp][c][0][0], st[mp][c][0][1]), pk2(st[mp][c][0][2], st[mp][c][0][3]), pk2(st[mp][c][1][0], st[mp][c][1][1]), pk2(st[mp][c][1][2], st[mp][c][1][3])};
       stamp(15);
@@ -401,26 +417,60 @@ __global__ __launch_bounds__(512, 2) void notes_fwd_kernel(Args a) {
     }
 }
 
+// (None of these offsets depends on the panel height: one bound for both.)
 // The cell waves address through buffer descriptors with 32-bit offsets.  The binding one is h0 ([R][512] fp32): a descriptor holds at most
 // 2^31 - 1 bytes and the per-lane offset row * 2048 + 48 is checked against it, so R * 2048 <= 2^31 - 1.  The others allow more: gate planes,
 // lane offset row * 32 + 16 and scalar offset (tile * 32 + 3 * 1024) * R <= 4064 * R < 2^32 (scalar offsets are outside the range check).
 constexpr long MAX_R = 0x7fffffffL / (H * 4);                                  // 1048575
 
-template <int DF, int ABL>
+template <int DF, int ABL, int ROWS = 64>
 static int launch(const Args& a, hipStream_t s) {
+  constexpr int LDS_BYTES = Lds<ROWS>::LDS_BYTES;
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(notes_fwd_kernel<DF, ABL>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return PTV_ERR_LAUNCH;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(notes_fwd_kernel<DF, ABL, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return PTV_ERR_LAUNCH;
     attr = true;
   }
-  hipLaunchKernelGGL((notes_fwd_kernel<DF, ABL>), dim3((unsigned)((a.R + ROWS - 1) / ROWS)), dim3(512), LDS_BYTES, s, a);
+  // workgroups are dispatched in index order = descending length (sorted rows): the dispatcher's next-free-CU order is the schedule
+  hipLaunchKernelGGL((notes_fwd_kernel<DF, ABL, ROWS>), dim3((unsigned)((a.R + ROWS - 1) / ROWS)), dim3(512), LDS_BYTES, s, a);
   return PTV_OK;
 }
 
 }  // namespace nr
+
+// ---- panel height of the notes GRU kernels, both directions.  sel = the two T bits of the entry points (forward bits 25-26, BPTT bits
+// 17-18): 0 = 64 rows, 1 = 32 rows, 2 = the rule below; 3 is refused (returns 0).
+// The rule: one workgroup is resident per CU, and a launch lasts as long as its longest-running CU.  64-row panels leave the dispatcher
+// nothing to balance with when there are no more panels than CUs -- with sorted rows (row_len given) the panels' step counts differ and
+// a CU that finishes a short panel early has nothing to take up -- and they leave half the chip idle when there are at most CUs / 2 of
+// them.  32-row panels are twice as many, dispatched longest first (index order = descending length), and their step is shorter (the
+// 32-row BPTT also keeps its whole A operand in LDS and does not spill).  Above those counts the 64-row kernels stay: twice the rows per
+// streamed weight byte.  Measured thresholds and t32 / t64: profiles/LOG.md, "notes panels".
+static int g_panel_override = 0;                                                 // ptv_debug_notes_panel_rule: 0 = the rule, 64 / 32
+int notes_panel_rows(int sel, long R, bool have_row_len) {
+  if (sel == 0) return 64;
+  if (sel == 1) return 32;
+  if (sel != 2) return 0;
+  if (g_panel_override) return g_panel_override;
+  static int ncu = 0;
+  if (ncu == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 64;
+    ncu = n;
+  }
+  const long p64 = (R + 63) / 64;
+  return (p64 <= ncu / 2 || (have_row_len && p64 <= ncu)) ? 32 : 64;
+}
+
 }  // namespace ptv
 
 using namespace ptv;
+
+extern "C" int ptv_debug_notes_panel_rule(int rows) {
+  if (rows != 0 && rows != 32 && rows != 64) return PTV_ERR_ARG;
+  g_panel_override = rows;
+  return PTV_OK;
+}
 
 static unsigned long long* g_notes_trace = nullptr;
 // timing experiments (round-5 probe, retired): device buffer of 8 x 2048 uint64 that workgroup 8 of the next launches fills with event stamps
@@ -434,7 +484,8 @@ extern "C" int ptv_notes_gru_persist_fwd(const void* wg_h, const void* wg_t, con
 }
 
 // T: bits 0-7 = steps, bits 8-15 = debug flags (8: no stagger), bits 16-23 = ring depth (0 = default), bit 24 = leave the HN16 slots of a
-// panel's dead steps unwritten (rows variant: the caller's products clip to the same segments)
+// panel's dead steps unwritten (rows variant: the caller's products clip to the same segments), bits 25-26 = panel height
+// (notes_panel_rows: 0 = 64 rows, 1 = 32 rows, 2 = the library's rule; the debug and ring-depth variants exist at 64 rows only)
 extern "C" int ptv_notes_gru_persist_fwd_rows(const void* wg_h, const void* wg_t, const float* b_hh, const void* gc, const float* emb,
                                               const float* h0, void* HN16, void* gates, long R, int T, const int* live_top, const int* row_len,
                                               void* stream);
@@ -447,13 +498,17 @@ extern "C" int ptv_notes_gru_persist_fwd_rows(const void* wg_h, const void* wg_t
                                               void* stream) {
   if (!wg_h || !wg_t || !b_hh || !gc || !emb || !h0 || !HN16 || R <= 0 || (T & 0xff) <= 0) return PTV_ERR_ARG;
   if (R > nr::MAX_R) return PTV_ERR_UNSUPPORTED;
+  const int rows = notes_panel_rows((T >> 25) & 3, R, row_len != nullptr);
+  if (rows == 0) return PTV_ERR_ARG;
   nr::Args a{(const bf16x8*)wg_h, (const bf16x8*)wg_t, b_hh, (const __bf16*)gc, emb, R * nr::E, h0, (__bf16*)HN16, (__bf16*)gates,
              (int)R, T & 0xff, (T >> 8) & 0xff, g_notes_trace, live_top, row_len, (T >> 24) & 1};
   const int depth = (T >> 16) & 0xff, abl = a.dbg & 7;
+  if (rows == 32 && (abl || depth)) return PTV_ERR_UNSUPPORTED;                 // (the timing variants exist at 64 rows only)
   const int pi = prof::want(3, (int)R, nr::H) ? prof::begin((hipStream_t)stream) : -1;
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  if (abl == 1) rc = nr::launch<15, 1>(a, s);
+  if (rows == 32) rc = nr::launch<15, 0, 32>(a, s);
+  else if (abl == 1) rc = nr::launch<15, 1>(a, s);
   else if (abl == 2) rc = nr::launch<15, 2>(a, s);
   else if (abl == 3) rc = nr::launch<15, 3>(a, s);
   else if (abl == 4) rc = nr::launch<15, 4>(a, s);
@@ -483,9 +538,16 @@ extern "C" int ptv_notes_gru_persist_fwd_rows(const void* wg_h, const void* wg_t
 namespace ptv {
 namespace nb {
 
-constexpr int H = 512, ROWS = 64, KT = 3 * H / 32, KL = 36;           // k-blocks: all / held in LDS
-constexpr int LDS_A = KL * 4 * ROWS * 16;                             // 147456 bytes
-constexpr int SCR_CH = (KT - KL) * 4;                                 // chunks per step that go through the global scratch: 48
+constexpr int H = 512, KT = 3 * H / 32;                               // k-blocks of the product
+// a panel of ROWS rows: KL of the KT k-blocks of the A operand are held in LDS (64 rows: 36, 147456 bytes, the other 12 go through the
+// global scratch ring; 32 rows: all 48, 98304 bytes -- that kernel neither reads nor writes the scratch)
+template <int ROWS>
+struct Pan {
+  static_assert(ROWS == 64 || ROWS == 32, "panel height");
+  static constexpr int KL = ROWS == 64 ? 36 : KT;
+  static constexpr int LDS_A = KL * 4 * ROWS * 16;
+  static constexpr int SCR_CH = (KT - KL) * 4;                        // chunks per step that go through the global scratch: 48 / 0
+};
 constexpr int DW = 3;                                                  // weight ring depth in k-blocks
 constexpr long MAX_R = 0x7fffffffL / (3 * H * 2);                      // 699050: [R][1536] bf16 within one buffer descriptor
 constexpr long MAX_R_STEPS = 0xffffffffL / 64;                         // 67108863 >= R * (16 T - 1): the scalar offset into ext within 32 bits
@@ -520,10 +582,13 @@ __device__ __forceinline__ unsigned pk2b(float a, float b) {
 }
 __device__ __forceinline__ u4v pk8(const float (&v)[8]) { return u4v{pk2b(v[0], v[1]), pk2b(v[2], v[3]), pk2b(v[4], v[5]), pk2b(v[6], v[7])}; }
 
-template <int ABL>                 // timing experiments (scripts/bench_notes.py): 2 = no products, 4 = no cell loads / stores
+// ABL: timing experiments (scripts/bench_notes.py): 2 = no products, 4 = no cell loads / stores.  ROWS = panel height, 64 or 32
+// (ptv_notes_panel_rows): ROWS / 16 M tiles per wave, 2 x ROWS / 16 cell items per step; same bits for every row at both heights
+template <int ABL, int ROWS>
 __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
+  constexpr int MT = ROWS / 16, NIT = 2 * MT, KL = Pan<ROWS>::KL, SCR_CH = Pan<ROWS>::SCR_CH;
   __builtin_amdgcn_s_setprio(3);
-  extern __shared__ __attribute__((aligned(16))) char bsm[];           // A operand chunks 0 .. 143: (chunk * 64 + row) * 16 bytes
+  extern __shared__ __attribute__((aligned(16))) char bsm[];           // A operand chunks 0 .. 4 KL - 1: (chunk * ROWS + row) * 16 bytes
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rl = lane & 15, q = lane >> 4;                              // fragment / epilogue coordinates: row in tile, k quad = unit octet
@@ -531,11 +596,11 @@ __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
   const long r0 = (long)blockIdx.x * ROWS;
   const int T = a.T;
   __bf16* sc = a.scratch + (long)blockIdx.x * 2 * (SCR_CH * ROWS * 8);
-  long grow[4]; bool ok[4];
+  long grow[MT]; bool ok[MT];
 #pragma unroll
-  for (int i = 0; i < 4; i++) { ok[i] = r0 + i * 16 + rl < R; grow[i] = min(r0 + i * 16 + rl, R - 1); }
+  for (int i = 0; i < MT; i++) { ok[i] = r0 + i * 16 + rl < R; grow[i] = min(r0 + i * 16 + rl, R - 1); }
 
-  // ---- zero-skip: steps at which no gradient arrives for any of the 64 rows, with nothing arriving from later steps either, produce exact
+  // ---- zero-skip: steps at which no gradient arrives for any of the panel's rows, with nothing arriving from later steps either, produce exact
   // zeros (the loss ignores the padded note slots, ptvae.py:498-511): tested on the arriving gradient itself, panel by panel
   // (with a caller-given bound the search starts there: until round 6 every panel read 64 KB and wrote 256 KB of zeros for each of the 8 dead
   // steps of the benchmark batch -- 0.13 GB read, 0.52 GB written per launch for rows nobody reads, a third of the launch's time)
@@ -567,9 +632,9 @@ __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
   if (a.top_step && tid == 0 && s_top >= 0) atomicMax(a.top_step, s_top);    // consumers of dgi / dgh may stop after this step's rows
 
   // ONE lane offset per M tile and operand family (the unit-tile part of every address is a scalar offset of the buffer instruction)
-  unsigned g_off[4], e_off[4], h_off[4], d_off[4];
+  unsigned g_off[MT], e_off[MT], h_off[MT], d_off[MT];
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < MT; i++) {
     g_off[i] = (unsigned)(grow[i] * 32 + (q & 1) * 16 + (long)(q >> 1) * R * 32);      // unit-blocked by 16: [u / 16][R][16] bf16
     e_off[i] = (unsigned)(grow[i] * 64 + q * 16);                                       // column-blocked by 32
     h_off[i] = (unsigned)(grow[i] * (H * 2) + q * 16);                                  // row-major [R][512] bf16 (HN16, dgh)
@@ -578,9 +643,9 @@ __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
   // acc[M tile][unit tile]: the accumulators of the products START each step at the carry dh (x) z the cells left in them (same lane
   // layout: a cell's carry is its own accumulator element) -- d = carry + dgh . W_hh comes out of the MFMAs, and the carry costs no
   // registers of its own (it took 128 KB of LDS in the 4-wave kernel, 64 registers in the first version of this one: 118 spills)
-  f32x4 acc[4][4];
+  f32x4 acc[MT][4];
 #pragma unroll
-  for (int i = 0; i < 4; i++)
+  for (int i = 0; i < MT; i++)
 #pragma unroll
     for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int lds_w = ((wave * 8 + q) * ROWS + rl) * 16;                  // this lane's place in the A operand: chunk wave * 8 + q, row rl
@@ -602,7 +667,7 @@ __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
     const __amdgpu_buffer_rsrc_t rs_e = nr::rsrc(a.ext, (long)T * RH * 2);
     const __amdgpu_buffer_rsrc_t rs_h = nr::rsrc(a.HN16 + (long)(s < 0 ? 0 : s) * RH, RH * 2);
     auto ldops = [&](Ops& o, int it) {
-      const int pr = it >> 2, i = it & 3;
+      const int pr = it / MT, i = it % MT;
       if constexpr (ABL & 4) return;
       const unsigned ut = (unsigned)(wave * 4 + pr * 2);                  // first unit tile of the item (scalar)
 #pragma unroll
@@ -614,16 +679,16 @@ __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
     const __amdgpu_buffer_rsrc_t rs_scr = nr::rsrc(scr, (long)SCR_CH * ROWS * 16), rs_scw = nr::rsrc(scw, (long)SCR_CH * ROWS * 16);
     const __amdgpu_buffer_rsrc_t rs_di = nr::rsrc(a.dgi + (long)(s < 0 ? 0 : s) * R3H, R3H * 2), rs_dh = nr::rsrc(a.dgh + (long)(s < 0 ? 0 : s) * RH, RH * 2);
     if (!first && !(ABL & 2)) {
-      // ---- dh = dgh_{s+1} . W_hh: 48 k-blocks, this wave's 4 unit tiles x 4 M tiles
-      bf16x8 bw[DW][4], aw[2][4];
+      // ---- dh = dgh_{s+1} . W_hh: 48 k-blocks, this wave's 4 unit tiles x ROWS / 16 M tiles
+      bf16x8 bw[DW][4], aw[2][MT];
       auto ldw = [&](int kb) {
 #pragma unroll
         for (int j = 0; j < 4; j++) bw[kb % DW][j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, lane16, (unsigned)((j * KT + kb) * 1024), 0));
       };
       auto lda_ = [&](int kb) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-          if (kb < KL) aw[kb & 1][i] = *reinterpret_cast<const bf16x8*>(bsm + (((kb * 4 + q) * ROWS) + i * 16 + rl) * 16);
+        for (int i = 0; i < MT; i++) {
+          if (KL == KT || kb < KL) aw[kb & 1][i] = *reinterpret_cast<const bf16x8*>(bsm + (((kb * 4 + q) * ROWS) + i * 16 + rl) * 16);
           else aw[kb & 1][i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_scr, (unsigned)((q * ROWS + i * 16 + rl) * 16), (unsigned)((kb - KL) * 4 * ROWS * 16), 0));
         }
       };
@@ -638,7 +703,7 @@ __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
         if (kb == KT - 1 && s >= 0) ldops(ops[1], 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int i = 0; i < 4; i++)
+        for (int i = 0; i < MT; i++)
 #pragma unroll
           for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[kb % DW][j], aw[kb & 1][i], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -646,10 +711,10 @@ __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
     }
     lds_barrier();                                                        // every wave is done with dgh_{s+1} in LDS: the cells may overwrite it
     first = false;
-    // ---- cells: 8 items of 16 rows x 32 units, MFMA lane layout
+    // ---- cells: 2 x ROWS / 16 items of 16 rows x 32 units, MFMA lane layout
 #pragma unroll
-    for (int it = 0; it < 8; it++) {
-      const int pr = it >> 2, i = it & 3;
+    for (int it = 0; it < NIT; it++) {
+      const int pr = it / MT, i = it % MT;
       const int u = (wave * 4 + pr * 2) * 16 + q * 8;
       if (s < 0) {                                                        // dh0 = carry + dgh_0 . W_hh
         if (ok[i]) {
@@ -685,14 +750,14 @@ __global__ __launch_bounds__(512, 2) void notes_bwd_kernel(Args a) {
         pq_[2 * hf] = pk2b(dnr[0], dnr[1]); pq_[2 * hf + 1] = pk2b(dnr[2], dnr[3]);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (it + 2 < 8) ldops(ops[it & 1], it + 2);                          // (this item's operands are consumed: request the one after next)
-      // the next step's A operand: chunk (gate * 512 + u) / 8 of this row -- LDS for chunks 0 .. 143, the scratch beyond
-      // (chunk = wave * 8 + pr * 4 + q, row = i * 16 + rl: ONE lane address per gate, the item's part is an immediate; the dn (x) r chunks of
-      // waves 2 .. 7 lie beyond the LDS-resident 144)
+      if (it + 2 < NIT) ldops(ops[it & 1], it + 2);                          // (this item's operands are consumed: request the one after next)
+      // the next step's A operand: chunk (gate * 512 + u) / 8 of this row -- LDS for chunks 0 .. 4 KL - 1, the scratch beyond
+      // (chunk = wave * 8 + pr * 4 + q, row = i * 16 + rl: ONE lane address per gate, the item's part is an immediate; 64-row panels: the
+      // dn (x) r chunks of waves 2 .. 7 lie beyond the LDS-resident 144)
       char* la = bsm + lds_w + (pr * 4 * ROWS + i * 16) * 16;
       *reinterpret_cast<u4v*>(la) = pr_;
       *reinterpret_cast<u4v*>(la + 64 * ROWS * 16) = pz_;
-      if (wave < 2) *reinterpret_cast<u4v*>(la + 128 * ROWS * 16) = pq_;
+      if (KL == KT || wave < 2) *reinterpret_cast<u4v*>(la + 128 * ROWS * 16) = pq_;
       else __builtin_amdgcn_raw_buffer_store_b128(pq_, rs_scw, (unsigned)((q * ROWS + rl) * 16), (unsigned)(((wave * 8 + pr * 4 - 16) * ROWS + i * 16) * 16), 0);
       if (ok[i] && !(ABL & 4)) {
         const unsigned so = (unsigned)((wave * 4 + pr * 2) * 32);
@@ -717,21 +782,25 @@ extern "C" int ptv_notes_bwd8(const void* wt, const void* HN16, const void* gate
   // 32-bit offsets: dgi's lane offset row * 3072 + 48 is checked against a descriptor of at most 2^31 - 1 bytes, and the scalar offset into
   // ext, ((tile / 2) * T * R + s * R) * 64 <= (16 T - 1) * R * 64, must not wrap
   if (R > nb::MAX_R || R * (16L * (T & 0xff) - 1) > nb::MAX_R_STEPS) return PTV_ERR_UNSUPPORTED;
+  const int rows = notes_panel_rows((T >> 17) & 3, R, row_len != nullptr);
+  if (rows == 0) return PTV_ERR_ARG;
   nb::Args a{(const bf16x8*)wt, (const __bf16*)HN16, (const __bf16*)gates, (const __bf16*)ext, (__bf16*)dgi, (__bf16*)dgh, dh0, (__bf16*)scratch,
              top_step, (int)R, T & 0xff, g_zero_skip, bound, row_len, (T >> 16) & 1};
   const int abl = (T >> 8) & 6;
+  if (rows == 32 && abl) return PTV_ERR_UNSUPPORTED;                       // (the timing variants exist at 64 rows only)
   const int pi = prof::want(4, (int)R, 512) ? prof::begin((hipStream_t)stream) : -1;
-  const dim3 grid((unsigned)((R + nb::ROWS - 1) / nb::ROWS));
-#define NB_LAUNCH(A_)                                                                                                                   \
+  const dim3 grid((unsigned)((R + rows - 1) / rows));      // index order = descending length (sorted rows): the dispatcher's next-free-CU order is the schedule
+#define NB_LAUNCH(A_, R_)                                                                                                                   \
   do {                                                                                                                                  \
     static bool attr = false;                                                                                                           \
     if (!attr) {                                                                                                                        \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(nb::notes_bwd_kernel<A_>), hipFuncAttributeMaxDynamicSharedMemorySize, nb::LDS_A) != hipSuccess) return PTV_ERR_LAUNCH; \
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(nb::notes_bwd_kernel<A_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, nb::Pan<R_>::LDS_A) != hipSuccess) return PTV_ERR_LAUNCH; \
       attr = true;                                                                                                                      \
     }                                                                                                                                   \
-    hipLaunchKernelGGL(nb::notes_bwd_kernel<A_>, grid, dim3(512), nb::LDS_A, (hipStream_t)stream, a);                                   \
+    hipLaunchKernelGGL((nb::notes_bwd_kernel<A_, R_>), grid, dim3(512), nb::Pan<R_>::LDS_A, (hipStream_t)stream, a);                    \
   } while (0)
-  if (abl == 2) NB_LAUNCH(2); else if (abl == 4) NB_LAUNCH(4); else if (abl == 6) NB_LAUNCH(6); else NB_LAUNCH(0);
+  if (rows == 32) NB_LAUNCH(0, 32);
+  else if (abl == 2) NB_LAUNCH(2, 64); else if (abl == 4) NB_LAUNCH(4, 64); else if (abl == 6) NB_LAUNCH(6, 64); else NB_LAUNCH(0, 64);
 #undef NB_LAUNCH
   if (pi >= 0) prof::end(pi, (hipStream_t)stream, 2.0 * R * 3.0 * 512 * 512 * ((T & 0xff) - 1 + (dh0 ? 1 : 0)));
   PTV_CHECK_LAUNCH();

@@ -803,6 +803,9 @@ DP_INPLACE = True        # decoder backward accumulates into the loss node's dpi
 # results do not change; PTV_ZERO_SKIP=0 runs everything dense (bench.py reports that figure next to the headline)
 ZERO_SKIP = os.environ.get('PTV_ZERO_SKIP', '1') != '0'
 _ZERO_SKIP_SET = []
+# panel height of the notes GRU kernels: "the library's rule" (include/ptvae_hip.h: forward T bits 25-26, BPTT T bits 17-18), the word
+# the composites ptv_decoder_tf_fwd / _bwd pass -- both sequencings launch the same kernels
+NOTES_PANELS_FWD, NOTES_PANELS_BWD = 2 << 25, 2 << 17
 
 
 def zero_skip_sync():
@@ -1985,7 +1988,7 @@ class DecoderTFFn(torch.autograd.Function):
             if top is not None and POISON_DEAD_STEPS:
                 _poison(HN16, gates_n)
             call('ptv_notes_gru_persist_fwd_top', ptr(pk['wg_h']), ptr(pk['wg_t']), ptr(P['dec_notes_gru.bias_hh_l0']), ptr(GC), ptr(emb3),
-                 ptr(HN), ptr(HN16), ptr(gates_n), R, 15, ptr(top), stream_ptr())
+                 ptr(HN), ptr(HN16), ptr(gates_n), R, 15 | NOTES_PANELS_FWD, ptr(top), stream_ptr())
         else:
             GT = gemm(emb3[:15].view(15 * R, E), w_ih_n[:, Ht:], prec=prec, out_dtype=adt)                    # [15R, 3Hn]
             gru_fwd(prec, GT, R * 3 * Hn, 3 * Hn, W['dec_notes_gru.weight_hh_l0'], P['dec_notes_gru.bias_hh_l0'], HN,
@@ -2361,7 +2364,7 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
         scratch = _empty(lib().ptv_notes_gru_persist_scratch_elems(R), dev=dev, dtype=BF16)
         top_step = _ineg1(dev) if ZERO_SKIP else None   # <- last note step with a gradient
         call('ptv_notes_gru_persist_bwd_top', ptr(pk['wt']), ptr(st.HN16), ptr(st.gates_n), ptr(dNSUM), ptr(dgi_n), ptr(dgh_n), ptr(dHN0),
-             ptr(scratch), R, 15, ptr(bound_n if fused_heads else None), ptr(top_step), stream_ptr())
+             ptr(scratch), R, 15 | NOTES_PANELS_BWD, ptr(bound_n if fused_heads else None), ptr(top_step), stream_ptr())
     else:
         top_step = None
         dgi_n, dgh_n, dHN0 = gru_bwd(prec, HN, st.gates_n, w_hh_n, dh_ext=dNSUM.view(15, R, Hn))
