@@ -41,9 +41,18 @@ int ptv_prof_read_segmented(int tag, double* seg);
  * are not affected.  Process-wide. */
 int ptv_debug_notes_panel_rule(int rows);
 
-/* A/B aid: 0 = ptv_wgrad_batch issues its products one by one (same bits, one product + one reduction launch each); 1 (default) = batched.
- * Process-wide; PTV_WGRAD_BATCH=0 sets it at load. */
+/* A/B aid: how ptv_wgrad_batch issues its products (same bits in every mode): 0 = one by one (one product + one reduction launch each);
+ * 1 = one product launch for all + one reduction launch; 2 = one product launch each + one reduction launch; 3 (default) = the small
+ * products in one launch, the deep ones alone, one reduction launch.  Anything else is refused.  Process-wide; PTV_WGRAD_BATCH sets it at load. */
 int ptv_wgrad_batch_mode(int batched);
+
+/* test aid: the plan ptv_wgrad / ptv_wgrad_batch would run `job` (a ptv_wgrad_job of ptvae_hip.h) on, without running it.  Host only: launches
+ * nothing and reads no device memory; the job's pointers are looked at for null and for alignment only.  out[10] =
+ * {kfast, tiles_m, tiles_n, nslab_fast, kper_fast, map_fast, nslab_tail, kper_tail, map_tail, total_slabs}: rows [0, kfast) go to the unguarded
+ * launch, the rest to the guarded one; a part that does not exist reports 0, 0, 0; all zero for M, N or K = 0.  Maps: 0 = slab-major, 1 =
+ * whole slabs per XCD, 2 = tile ranges per XCD (csrc/wgrad.hip).  Returns what the product call would return for a job it refuses. */
+struct ptv_wgrad_job;
+int ptv_debug_wgrad_plan(const struct ptv_wgrad_job* job, int* out);
 
 /* test aid of the sampled decode (ptvae_hip.h "Sampled decode"): the Gumbel values the decoder uses for rows [0, rows) -- samples
  * sample_offset + row of the block -- at time step t, note step n, through the decoder's own device functions: out_pitch [rows, 130],

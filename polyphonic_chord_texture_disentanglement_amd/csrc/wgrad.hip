@@ -56,6 +56,7 @@ struct WgArgs {
   const void* A2; long lda2; int split;
   int k_base;                    // this launch's first row in the numbering of the k_top limits (the guarded tail launch starts at kfast)
   const int* seg_n; int seg_unit, seg_period;   // K segments (ptv_wgrad_job): of unit q = row / seg_unit only the first seg_n[q % seg_period] rows are live
+  int sole;                      // this launch's one slab is the only slab of the whole PRODUCT (set by wgrad_run, not by plan_job): see wgrad_store
 };
 
 // which part of a slab's K range survives the k_top limits: shared by the product kernel and the ordered reduction (a slab that is
@@ -224,7 +225,10 @@ __device__ __forceinline__ void wgrad_store(const WgArgs& g, wf32x4 (&acc)[4][4]
           }
     return;
   }
-  const bool single = g.nslab == 1;
+  // Without a workspace a part may add into C with a plain read-modify-write only when it is the product's SOLE writer.  One slab in this
+  // part is not enough: the guarded tail always has one, and in wgrad_batch_kernel it runs in the same launch as the fast part's blocks,
+  // whose atomicAdd (or, with one slab there too, plain add) meets the same elements.  A lone writer's atomic and plain adds give the same bits.
+  const bool single = g.sole != 0;
   const bool inner = m_blk + WBM <= g.M && n_blk + WBN <= g.N;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
@@ -764,6 +768,14 @@ int plan_job(const Job& j, Plan& p) {
   return PTV_OK;
 }
 
+// the jobs wgrad_run refuses (shared with the plan probe, ptv_debug_wgrad_plan)
+int job_check(const Job& j) {
+  if (j.M < 0 || j.N < 0 || j.K < 0 || !j.A || !j.B || !j.C) return PTV_ERR_ARG;
+  if (j.k_top && (j.k_unit <= 0 || j.k_unit % WBK)) return PTV_ERR_ARG;
+  if (j.seg_n && (j.seg_period == 0 || j.A2 || !ptv_wgrad_seg_supported(j.K, j.seg_unit))) return PTV_ERR_ARG;
+  return PTV_OK;
+}
+
 void zero_c(const Job& j, hipStream_t s) {
   const long total = (long)j.M * j.N;
   int nb = (int)((total + 255) / 256); if (nb > 2048) nb = 2048;
@@ -796,9 +808,7 @@ int wgrad_run(const Job* jobs, int njobs, hipStream_t s) {
   double flops = 0.0, lim15 = 0.0, lim16 = 0.0, seg = 0.0; int pm = 0, pn = 0;
   for (int i = 0; i < njobs; i++) {
     const Job& j = jobs[i];
-    if (j.M < 0 || j.N < 0 || j.K < 0 || !j.A || !j.B || !j.C) return PTV_ERR_ARG;
-    if (j.k_top && (j.k_unit <= 0 || j.k_unit % WBK)) return PTV_ERR_ARG;
-    if (j.seg_n && (j.seg_period == 0 || j.A2 || !ptv_wgrad_seg_supported(j.K, j.seg_unit))) return PTV_ERR_ARG;
+    PTV_TRY(job_check(j));
     if (j.M == 0 || j.N == 0) continue;
     if (j.K == 0) { if (!j.accumulate) zero_c(j, s); continue; }
     live[n] = j; PTV_TRY(plan_job(j, plan[n]));
@@ -835,6 +845,7 @@ int wgrad_run(const Job* jobs, int njobs, hipStream_t s) {
     for (int k = 0; k < 2; k++) if (plan[i].has[k]) {
       WgArgs& g = plan[i].part[k];
       if (wsp[i]) { g.ws = wsp[i]; g.ws_csum = wsc[i]; g.slab0 = k ? plan[i].nslab[0] : 0; }
+      g.sole = plan[i].total_slabs == 1 ? 1 : 0;
     }
     if (!wsp[i] && !live[i].accumulate) zero_c(live[i], s);          // (atomics / single slab: the product adds into C)
   }
@@ -960,15 +971,35 @@ extern "C" int ptv_wgrad_cat(int M1, const void* A1, long lda1, int M2, const vo
   return wgrad_run(&j, 1, (hipStream_t)stream);
 }
 
+namespace {
+Job job_of(const ptv_wgrad_job& q) {
+  return Job{q.M, q.N, q.K, q.A, q.lda, nullptr, 0, 0, q.B, q.ldb, q.C, q.ldc, q.alpha, q.accumulate, q.dtypes, q.slabs, q.colsum_a, q.k_top,
+             q.k_unit, q.k_rev, q.seg_n, q.seg_unit, q.seg_period};
+}
+}  // namespace
+
 // several products, one launch (+ one reduction launch): include/ptvae_hip.h
 extern "C" int ptv_wgrad_batch(const ptv_wgrad_job* jobs, int njobs, void* stream) {
   if (njobs < 0 || (njobs > 0 && !jobs)) return PTV_ERR_ARG;
   if (njobs > 64) return PTV_ERR_ARG;
   Job js[64];
-  for (int i = 0; i < njobs; i++) {
-    const ptv_wgrad_job& q = jobs[i];
-    js[i] = Job{q.M, q.N, q.K, q.A, q.lda, nullptr, 0, 0, q.B, q.ldb, q.C, q.ldc, q.alpha, q.accumulate, q.dtypes, q.slabs, q.colsum_a, q.k_top,
-                q.k_unit, q.k_rev, q.seg_n, q.seg_unit, q.seg_period};
-  }
+  for (int i = 0; i < njobs; i++) js[i] = job_of(jobs[i]);
   return wgrad_run(js, njobs, (hipStream_t)stream);
+}
+
+// test aid (include/ptvae_hip_debug.h): the plan wgrad_run would run this job on.  Host only: launches nothing and reads no device memory
+// (the job's pointers are looked at for null and for alignment).
+extern "C" int ptv_debug_wgrad_plan(const ptv_wgrad_job* job, int* out) {
+  if (!job || !out) return PTV_ERR_ARG;
+  const Job j = job_of(*job);
+  PTV_TRY(job_check(j));
+  for (int i = 0; i < 10; i++) out[i] = 0;
+  if (j.M == 0 || j.N == 0 || j.K == 0) return PTV_OK;              // (nothing to plan: wgrad_run launches no product)
+  Plan p;
+  PTV_TRY(plan_job(j, p));
+  out[0] = p.has[1] ? p.part[1].k_base : j.K;
+  out[1] = cdiv(j.M, WBM); out[2] = cdiv(j.N, WBN);
+  for (int k = 0; k < 2; k++) if (p.has[k]) { out[3 + 3 * k] = p.nslab[k]; out[4 + 3 * k] = p.part[k].kper; out[5 + 3 * k] = p.part[k].map; }
+  out[9] = p.total_slabs;
+  return PTV_OK;
 }
