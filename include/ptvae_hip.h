@@ -870,6 +870,73 @@ int ptv_best_of_gather(const float* score, const long* grids, const float* sums,
                        int* err, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Row-independent free-running chord decode (csrc/chord_decode.hip; DESIGN.md 7f, INTEGRATION.md "Chord decode"): seeded sampling, kept
+ * chords and log-probabilities of the chord decoder (RnnDecoder, ptvae.py:32-87).  Every row feeds back its OWN token (root one-hot | 12
+ * chroma bits | bass one-hot): the union over the batch that ptv_chord_token forms for parity with the reference's training step is not
+ * formed here, so a row's chords do not depend on what else is in the batch.  Inference only; every output element has one writer, no
+ * atomics: results are bit-identical from run to run.
+ * ptv_chord_decide: the decisions of ONE chord step t (0..7) for B rows, 16 lanes per row, lane j < 12 owns root class j, bass class j and
+ *   chroma pair j.
+ *   root [B][12], chroma [B][24] (12 pairs: class 0, class 1), bass [B][12]: the step's fp32 logits.
+ *   sample: NULL (argmax, logq = 0) or the 32-byte sampling block ("Sampled decode" above): seed, draw, sample_offset, T_chord in the
+ *     t_pitch word, T_chroma in the t_dur word.  A decision is the first maximal index of logit + T * gumbel(word) (T = 0: the plain
+ *     argmax, ties to the lowest index); chroma bit j is 1 iff e1 + T g1 > e0 + T g0.  Root and bass take T_chord, the bits T_chroma.
+ *     The words are those of the decoder's Philox domain at the note step nothing else uses, n = 15, kind 0, sub = j, global sample
+ *     sample_offset + b: word 0 perturbs root class j, word 1 bass class j, word 2 / 3 class 0 / 1 of chroma bit j.
+ *   keep_c f32 [B][8][36] or NULL (no keep), keep_steps uint8 [keep_rows][8] with keep_rows = B or 1 (required with keep_c): at a step
+ *     whose byte is non-zero the decisions are forced from keep_c[b][t] -- root = the index of the single non-zero entry of [0:12], bass
+ *     the same of [24:36], chroma bit k = keep_c[b][t][12 + k] != 0.  A root / bass block without exactly one non-zero entry forces
+ *     nothing for that head (the decision stays free) and sets bit 0 of step_err[b][t].  keep_c of a step that is not kept is not read.
+ *   -> tok [B][36] (or NULL: the last step) the token of the next step; row [b][t] of c [B][8][36] (the same token) and of chord14
+ *      [B][8][14] (ptv_chord_tokens' layout: root index, 12 bits, bass index); row [b][t] of step_logp / step_logq f32 [B][8][3], of
+ *      step_forced int32 [B][8][3] and of step_err int32 [B][8], heads in the order (root, chroma, bass):
+ *        logp = log softmax(logits) at the decided class, the chroma figure the sum over its 12 bits in ascending order; forced
+ *          decisions included
+ *        logq = log softmax(logits / T) at the decided class; 0 where T = 0 or sample is NULL, and 0 for a forced decision
+ *        forced = the number of forced decisions: 0 / 1, 0 / 12, 0 / 1
+ *   PTV_ERR_ARG (nothing launched): a NULL logit array or output (tok excepted), B < 1, t outside 0..7, keep_c without keep_steps,
+ *   keep_rows other than 1 or B.
+ * ptv_chord_logprob_fold: logp / logq f32 [B][3] = the sums of step_logp / step_logq over t = 0..7 in ascending order (fp32, sequential),
+ *   forced int32 [B][3] the same of step_forced, err int32 [B] the OR of step_err.  One thread per output element.
+ * ptv_chord_decode: the whole decode of z [B][Z] in one call -- z2dec_hid, z2dec_in and the z part of the input product once, then per
+ *   step the token part of the input product (K = 36), ptv_gru_step_fwd, the three head products and ptv_chord_decide, then the fold:
+ *   4 + 8 * 6 + 1 launches.  fp32 or bf16 precision as ptv_chord_decoder_fwd (fp32 tensors either way); no gates are saved.  The geometry
+ *   is the model's: 8 steps, tokens of 36, heads of 12 / 24 / 12; H a multiple of 4.  Optional slots (NULL): SAMPLE, KEEP_C, KEEP_STEPS.
+ *   ROOT / CHROMA / BASS keep the step-major logits of the decode.
+ */
+int ptv_chord_decide(const float* root, const float* chroma, const float* bass, int B, int t, const void* sample, const float* keep_c,
+                     const unsigned char* keep_steps, int keep_rows, float* tok, float* c, float* chord14, float* step_logp,
+                     float* step_logq, int* step_forced, int* step_err, void* stream);
+int ptv_chord_logprob_fold(const float* step_logp, const float* step_logq, const int* step_forced, const int* step_err, int B,
+                           float* logp, float* logq, int* forced, int* err, void* stream);
+enum PtvCdsTensor {
+  PTV_CDS_Z = 0,          /* [B, Z] */
+  PTV_CDS_W_ZHID, PTV_CDS_B_ZHID, PTV_CDS_W_ZIN, PTV_CDS_B_ZIN, PTV_CDS_INIT_INPUT,
+  PTV_CDS_W_IH,           /* [3H, 36 + Zi] */
+  PTV_CDS_B_IH, PTV_CDS_W_HH, PTV_CDS_B_HH, PTV_CDS_W_ROOT, PTV_CDS_B_ROOT, PTV_CDS_W_CHROMA, PTV_CDS_B_CHROMA, PTV_CDS_W_BASS, PTV_CDS_B_BASS,
+  PTV_CDS_SAMPLE,         /* the 32-byte sampling block, or NULL */
+  PTV_CDS_KEEP_C,         /* [B, 8, 36], or NULL */
+  PTV_CDS_KEEP_STEPS,     /* uint8 [KEEP_ROWS, 8], with KEEP_C */
+  PTV_CDS_HALL,           /* out [9, B, H] states (slot 0 = z2dec_hid(z)) */
+  PTV_CDS_Z_IN,           /* out [B, Zi] */
+  PTV_CDS_ZG,             /* out [B, 3H] */
+  PTV_CDS_GI,             /* scratch [B, 3H] */
+  PTV_CDS_TOK,            /* scratch [B, 36] */
+  PTV_CDS_ROOT, PTV_CDS_CHROMA, PTV_CDS_BASS,   /* out [8, B, 12 / 24 / 12] logits, step-major */
+  PTV_CDS_C,              /* out [B, 8, 36] */
+  PTV_CDS_CHORD14,        /* out [B, 8, 14] */
+  PTV_CDS_STEP_LOGP, PTV_CDS_STEP_LOGQ,   /* out f32 [B, 8, 3] */
+  PTV_CDS_STEP_FORCED,    /* out int32 [B, 8, 3] */
+  PTV_CDS_STEP_ERR,       /* out int32 [B, 8] */
+  PTV_CDS_LOGP, PTV_CDS_LOGQ,   /* out f32 [B, 3] */
+  PTV_CDS_FORCED,         /* out int32 [B, 3] */
+  PTV_CDS_ERR,            /* out int32 [B] */
+  PTV_CDS_COUNT
+};
+enum PtvCdsDim { PTV_CDS_D_B = 0, PTV_CDS_D_H, PTV_CDS_D_Z, PTV_CDS_D_ZI, PTV_CDS_D_PREC, PTV_CDS_D_KEEP_ROWS, PTV_CDS_D_COUNT };
+int ptv_chord_decode(const void* const* tensors, const long* dims, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Note-matrix song bank on device (csrc/dataset.hip): what ArrangementDataset.__getitem__ does BEFORE the data contract above, from
  * the per-bar note matrices (dataset.py:67-93 over converter.py:35-76), and detrend_pianotree (dataset.py:123-213) after it.
  * Bank: the bars of all songs in order.  acc_rec / mel_rec hold one 32-bit record per note, bar after bar, acc_off / mel_off [n_bar+1]

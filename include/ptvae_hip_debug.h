@@ -72,6 +72,11 @@ int ptv_debug_pitch_keep(const void* block48, const float* logits, long rows, in
 int ptv_debug_pitch_constrain(const void* block64, const float* logits, const int* masks, const int* lo, long rows, int layout,
                               unsigned char* keep_out, float* thr_out, void* stream);
 
+/* test aid of the chord decode (ptvae_hip.h "Row-independent free-running chord decode"): the Gumbel values ptv_chord_decide uses for rows
+ * [0, rows) -- samples sample_offset + row of the 32-byte block -- at chord step t, through the device function that kernel calls:
+ * out [rows, 12, 4], lane j's four values in word order (root class j, bass class j, class 0 and class 1 of chroma bit j) */
+int ptv_debug_chord_noise(const void* block, long rows, int t, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1095,3 +1095,134 @@ class ChordDecoderStepFn(torch.autograd.Function):
         # tokens are constants (ground truth or argmax one-hots): same BPTT as the teacher-forced path
         g = F_.ChordDecoderTFFn.backward(ctx, droot, dchroma, dbass)
         return (g[0], None, None, None, None) + tuple(g[3:])
+
+
+# =============================================================================================
+# Row-independent free-running chord decode (csrc/chord_decode.hip): every row feeds back its OWN token, decisions may be
+# seeded draws, kept or scored.  Inference only; ChordDecoderStepFn above keeps the reference's union-over-the-batch token.
+# =============================================================================================
+CHORD_STEPS = 8
+_CDS = SlotTable('CDS')
+
+ChordLogprob = collections.namedtuple('ChordLogprob', 'logp logq forced err step_logp step_logq step_forced')
+ChordDecode = collections.namedtuple('ChordDecode', 'c chord14 root chroma bass logprob')      # root / chroma / bass: step-major logits
+
+
+class ChordKeep(collections.namedtuple('ChordKeep', 'c steps batch')):
+    """the kept chord steps of a chord decode (INTEGRATION.md "Chord decode"): c f32 [B, 8, 36] and steps uint8 [B, 8] or [1, 8] on the
+    device (a non-zero byte: the step's decisions are forced from c[b, t]), batch = B"""
+    __slots__ = ()
+
+
+def chord_keep_steps_row(steps):
+    """a host selection of chord steps (an iterable of indices 0..7, or a slice) -> 8 bytes, one per step -- ValueError for anything else"""
+    row = bytearray(CHORD_STEPS)
+    if isinstance(steps, slice):
+        steps = range(*steps.indices(CHORD_STEPS))
+    try:
+        items = list(steps)
+    except TypeError:
+        raise ValueError('steps must be a device bool / uint8 tensor [B, 8] or [1, 8], an iterable of step indices or a slice, got %r'
+                         % (steps,)) from None
+    for t in items:
+        if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < CHORD_STEPS:
+            raise ValueError('a kept chord step must be an integer in 0..7, got %r' % (t,))
+        row[t] = 1
+    return bytes(row)
+
+
+def build_chord_keep(c, steps):
+    """(c f32 device [B, 8, 36] as decode_chords / decode_to_inputs give it, steps) -> ChordKeep; steps: a device bool / uint8 tensor
+    [B, 8] or [1, 8], or a host selection (chord_keep_steps_row) that becomes one [1, 8] row.  ValueError before any launch; nothing is
+    copied to the host (the contents of c are judged by the kernel: ChordLogprob.err)."""
+    if not torch.is_tensor(c) or c.device.type != 'cuda':
+        raise ValueError('c must be a device tensor: the chords f32 [B, 8, 36]')
+    if c.dtype != torch.float32 or c.dim() != 3 or tuple(c.shape[1:]) != (CHORD_STEPS, 36) or c.shape[0] < 1:
+        raise ValueError('c must be float32 [B, 8, 36], got %s %s' % (c.dtype, tuple(c.shape)))
+    B = c.shape[0]
+    if torch.is_tensor(steps):
+        if steps.device != c.device:
+            raise ValueError('steps must be on the device of c (or a host iterable of step indices / a slice)')
+        if steps.dtype not in (torch.bool, torch.uint8):
+            raise ValueError('steps must be bool or uint8, got %s' % (steps.dtype,))
+        if steps.dim() != 2 or steps.shape[1] != CHORD_STEPS or steps.shape[0] not in (1, B):
+            raise ValueError('steps must have shape [B, 8] or [1, 8] with B = %d, got %s' % (B, tuple(steps.shape)))
+        steps = steps.contiguous()
+        steps = steps.view(torch.uint8) if steps.dtype == torch.bool else steps
+    else:
+        steps = torch.frombuffer(bytearray(chord_keep_steps_row(steps)), dtype=torch.uint8).view(1, CHORD_STEPS).to(c.device)
+    return ChordKeep(c.detach().contiguous(), steps, B)
+
+
+def check_chord_keep(keep, batch=None):
+    """ValueError unless keep is None or a ChordKeep whose arrays fit its batch (and `batch`, the rows of the decode, where known)"""
+    if keep is None:
+        return
+    if not isinstance(keep, ChordKeep):
+        raise ValueError('keep_chords must be what DisentangleVAE.keep_chords(c, steps) returns, got %r' % (type(keep).__name__,))
+    B = keep.batch
+    c, steps = keep.c, keep.steps
+    if (not torch.is_tensor(c) or c.device.type != 'cuda' or c.dtype != torch.float32 or tuple(c.shape) != (B, CHORD_STEPS, 36)
+            or not c.is_contiguous()):
+        raise ValueError('keep_chords.c must be a contiguous float32 device tensor [%d, 8, 36]' % B)
+    if (not torch.is_tensor(steps) or steps.device != c.device or steps.dtype != torch.uint8 or steps.dim() != 2
+            or steps.shape[1] != CHORD_STEPS or steps.shape[0] not in (1, B) or not steps.is_contiguous()):
+        raise ValueError('keep_chords.steps must be a contiguous uint8 tensor [%d, 8] or [1, 8] on the device of c' % B)
+    if batch is not None and B != batch:
+        raise ValueError('keep_chords was built for a batch of %d, the decoded batch has %d rows' % (B, batch))
+
+
+def check_chord_sampling(temperature=None, chroma_temperature=None, seed=None, draw=None, sample_offset=None):
+    """ValueError for a bad keyword of a chord decode; True for a sampled decode, False for the argmax decode.  No side effect, no launch.
+    temperature (root and bass) / chroma_temperature (the 12 bits; default: temperature): finite floats >= 0"""
+    if temperature is None:
+        if chroma_temperature is not None:
+            raise ValueError('chroma_temperature belongs to a sampled chord decode: give chord_temperature as well')
+        if seed is not None or draw is not None or sample_offset is not None:
+            raise ValueError('seed / draw / sample_offset belong to a sampled decode: give a temperature')
+        return False
+    try:
+        check_sampling(temperature, chroma_temperature, 0 if sample_offset is None else sample_offset, 0 if seed is None else seed,
+                       0 if draw is None else draw)
+    except ValueError as e:
+        raise ValueError(str(e).replace('dur_temperature', 'chroma_temperature')) from None
+    return True
+
+
+def chord_decode(z, P, prec, sampling=None, keep=None):
+    """z f32 [B, Z] on the device, P {CHD_PARAM_NAMES: parameter} -> ChordDecode, through ptv_chord_decode (ONE C call: 53 launches).
+    sampling: None (argmax) or the 32-byte sampling_block(device, T_chord, T_chroma, seed, draw, sample_offset); keep: None or a checked
+    ChordKeep of B rows.  No autograd, no synchronisation."""
+    dev = z.device
+    z = z.detach().float().contiguous()
+    B, Z = z.shape
+    w_ih = P['gru.weight_ih_l0'].detach()
+    H, Zi = P['gru.weight_hh_l0'].shape[1], P['z2dec_in.weight'].shape[0]
+    if (P['init_input'].shape[0] != 36 or w_ih.shape[1] != 36 + Zi or P['root_out.weight'].shape[0] != 12
+            or P['chroma_out.weight'].shape[0] != 24 or P['bass_out.weight'].shape[0] != 12):
+        raise ValueError('the chord decode is built for tokens of 36 and heads of 12 / 24 / 12')
+    if sampling is not None and not (torch.is_tensor(sampling) and sampling.dtype == torch.int64 and sampling.numel() == SAMPLED.words
+                                     and sampling.is_contiguous() and sampling.device == dev):
+        raise ValueError('sampling must be a four-word block made by functional_free.sampling_block() on the device of z')
+    T = CHORD_STEPS
+    i32 = dict(device=dev, dtype=torch.int32)
+    out = dict(HALL=_empty(T + 1, B, H, dev=dev), Z_IN=_empty(B, Zi, dev=dev), ZG=_empty(B, 3 * H, dev=dev), GI=_empty(B, 3 * H, dev=dev),
+               TOK=_empty(B, 36, dev=dev), ROOT=_empty(T, B, 12, dev=dev), CHROMA=_empty(T, B, 24, dev=dev), BASS=_empty(T, B, 12, dev=dev),
+               C=_empty(B, T, 36, dev=dev), CHORD14=_empty(B, T, 14, dev=dev), STEP_LOGP=_empty(B, T, 3, dev=dev),
+               STEP_LOGQ=_empty(B, T, 3, dev=dev), STEP_FORCED=torch.empty(B, T, 3, **i32), STEP_ERR=torch.empty(B, T, **i32),
+               LOGP=_empty(B, 3, dev=dev), LOGQ=_empty(B, 3, dev=dev), FORCED=torch.empty(B, 3, **i32), ERR=torch.empty(B, **i32))
+    tens = {'Z': z, 'W_ZHID': P['z2dec_hid.weight'], 'B_ZHID': P['z2dec_hid.bias'], 'W_ZIN': P['z2dec_in.weight'],
+            'B_ZIN': P['z2dec_in.bias'], 'INIT_INPUT': P['init_input'], 'W_IH': w_ih, 'B_IH': P['gru.bias_ih_l0'],
+            'W_HH': P['gru.weight_hh_l0'], 'B_HH': P['gru.bias_hh_l0'], 'W_ROOT': P['root_out.weight'], 'B_ROOT': P['root_out.bias'],
+            'W_CHROMA': P['chroma_out.weight'], 'B_CHROMA': P['chroma_out.bias'], 'W_BASS': P['bass_out.weight'],
+            'B_BASS': P['bass_out.bias'], 'SAMPLE': sampling, 'KEEP_C': None if keep is None else keep.c,
+            'KEEP_STEPS': None if keep is None else keep.steps}
+    for k, v in tens.items():
+        if v is not None and k not in ('SAMPLE', 'KEEP_STEPS') and (v.dtype != torch.float32 or not v.is_contiguous()):
+            raise ValueError('ptv_chord_decode takes contiguous float32 tensors (%s is %s)' % (k, v.dtype))
+    dims = {'B': B, 'H': H, 'Z': Z, 'ZI': Zi, 'PREC': prec, 'KEEP_ROWS': 0 if keep is None else keep.steps.shape[0]}
+    F_._chain_prio()
+    F_.check(lib().ptv_chord_decode(_CDS.pointers(tens, out), _CDS.dims(dims), stream_ptr()), 'ptv_chord_decode')
+    _CDS.count()
+    lp = ChordLogprob(out['LOGP'], out['LOGQ'], out['FORCED'], out['ERR'], out['STEP_LOGP'], out['STEP_LOGQ'], out['STEP_FORCED'])
+    return ChordDecode(out['C'], out['CHORD14'], out['ROOT'], out['CHROMA'], out['BASS'], lp)

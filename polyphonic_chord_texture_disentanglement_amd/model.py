@@ -13,7 +13,8 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import Keep, build_keep, check_constraints, check_keep, check_sampling, make_block, sampling_words
+from .functional_free import (Keep, build_chord_keep, build_keep, check_chord_keep, check_chord_sampling, check_constraints, check_keep,
+                              check_sampling, make_block, sampling_words)
 from .optim import refresh_weight_shadows
 from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
@@ -52,6 +53,11 @@ class DecodeRequest(collections.namedtuple('DecodeRequest', 'sampled kw mask kee
             keep = Keep(keep.pitch.view(15, 32, 1, B).expand(15, 32, n, B).reshape(15, 32 * n * B),
                         keep.dur.view(5, 15, 32, 1, B).expand(5, 15, 32, n, B).reshape(5, 480 * n * B), keep.err.repeat(n), n * B)
         return self._replace(mask=mask, keep=keep, batch=n * B)
+
+
+class ChordRequest(collections.namedtuple('ChordRequest', 'sampled temperature chroma_temperature seed draw sample_offset keep')):
+    """the validated keywords of one row-independent chord decode (DisentangleVAE._chord_request); seed / draw / sample_offset None = the
+    model's (use_philox, the draw counter)"""
 
 
 class DisentangleVAE(PytorchModel):
@@ -502,35 +508,105 @@ class DisentangleVAE(PytorchModel):
             est_x = self.decoder.last_xhat[:, :, 1:, :].cpu().numpy()
         return est_x
 
+    # ---- the row-independent chord decode (INTEGRATION.md "Chord decode"; ptv_chord_decode).  decode_tokens -- the default of the output path
+    # below -- feeds back the reference's union over the batch of the rows' root / bass decisions (ptvae.py:74-77): right for parity with the
+    # training step, but a row's chords then depend on the rest of the batch.  chord_temperature / chroma_temperature / keep_chords select the
+    # decode in which every row feeds back its own token: sharding-invariant like the note decode, sampled from the same Philox domain
+    # (note step 15: a slot no note decision uses), with kept chords and log-probabilities.
+    def _chord_request(self, batch, chord_temperature=None, chroma_temperature=None, keep_chords=None, seed=None, draw=None,
+                       sample_offset=None, note_sampled=False, required=False):
+        """None when no chord keyword is given (the caller keeps decode_tokens), else the ChordRequest; every bad value is a ValueError
+        here: no launch, no side effect.  note_sampled: the note decode of the same call is sampled (seed / draw / sample_offset then
+        belong to it as well and are no error without a chord temperature); required: the caller runs the chord decode whatever is given"""
+        if chord_temperature is None and chroma_temperature is None and keep_chords is None and not required:
+            return None
+        given = (seed, draw, sample_offset)
+        sampled = check_chord_sampling(chord_temperature, chroma_temperature, *((None, None, None) if note_sampled and chord_temperature is None
+                                                                                 else given))
+        check_chord_keep(keep_chords, batch)
+        return ChordRequest(sampled, chord_temperature, chroma_temperature, seed, draw, sample_offset, keep_chords)
+
+    def _decode_chords(self, z_chd, creq, draw, return_logprob=False):
+        """the chord decode of a ChordRequest; draw: the draw number a request that names none uses"""
+        ph = self._philox or (7, 0)
+        return self.chd_decoder.decode_chords(
+            z_chd, temperature=creq.temperature, chroma_temperature=creq.chroma_temperature, seed=ph[0] if creq.seed is None else creq.seed,
+            draw=draw if creq.draw is None else creq.draw, sample_offset=ph[1] if creq.sample_offset is None else creq.sample_offset,
+            keep=creq.keep, return_logprob=return_logprob)
+
+    def keep_chords(self, c, steps):
+        """The kept chord steps of a chord decode -> functional_free.ChordKeep(c, steps, batch) for keep_chords= (INTEGRATION.md "Chord
+        decode").  c: f32 device tensor [B, 8, 36] (what decode_chords, decode_to_inputs and the dataset path give); steps: a device
+        bool / uint8 tensor [B, 8] or [1, 8], or a host iterable of step indices / a slice (one row for every sample: range(4) = the
+        first bar).  At a kept step root, chroma bits and bass are forced from c[b, t] and fed back like decisions.  A root or bass block
+        without exactly one non-zero entry forces nothing for that head and sets bit 0 of ChordLogprob.err[b].  Nothing is copied to the
+        host."""
+        return build_chord_keep(c, steps)
+
+    def decode_chords(self, z_chd, *, chord_temperature=None, chroma_temperature=None, seed=None, draw=None, sample_offset=None,
+                      keep_chords=None, return_logprob=False):
+        """Row-independent free-running chord decode of z_chd -> (c f32 [B,8,36], chord14 f32 [B,8,14]), with return_logprob=True also a
+        ChordLogprob (RnnDecoder.decode_chords).  seed / sample_offset default to use_philox()'s, else 7 / 0; draw defaults to the
+        model's draw counter, which a sampled decode that names none advances.  Without a temperature: the argmax (of each row's own
+        trajectory).  Bad values are a ValueError before anything is launched and before the counter moves."""
+        if not torch.is_tensor(z_chd) or z_chd.dim() != 2:
+            raise ValueError('z_chd must be a tensor [B, z_dim]')
+        creq = self._chord_request(z_chd.shape[0], chord_temperature, chroma_temperature, keep_chords, seed, draw, sample_offset, required=True)
+        _require_cuda(z_chd, 'DisentangleVAE.decode_chords')
+        self.eval()
+        out = self._decode_chords(z_chd, creq, self._sample_draws, return_logprob)
+        if creq.sampled and draw is None:
+            self._sample_draws += 1
+        return out
+
     # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
                          sample_offset=None, top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None, keep=None,
-                         return_logprob=False):
+                         return_logprob=False, chord_temperature=None, chroma_temperature=None, keep_chords=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
-        inference_decode's (the chord decoder keeps its argmax).  return_logprob=True appends the decode's log-probabilities
-        (PtvaeDecoder.decode_logprob: a DecodeLogprob of device tensors) as a seventh element."""
+        inference_decode's (they leave the chord decoder at its argmax).  return_logprob=True appends the decode's log-probabilities
+        (PtvaeDecoder.decode_logprob: a DecodeLogprob of device tensors) as a seventh element.
+        chord_temperature / chroma_temperature / keep_chords (any of them given): c comes from the row-independent chord decode
+        (decode_chords above) instead of decode_tokens, and return_logprob appends its ChordLogprob as an eighth element.  One call is one
+        draw: both decoders take seed / draw / sample_offset, and when no draw is named both use the counter's value and it advances
+        once.  With none of the three the call is what it was: the same launches, the same bits."""
         kw = locals()
-        req = self._request(z_chd.shape[0], **{k: kw[k] for k in DECODE_KEYS})   # (bad values are a ValueError whatever device the inputs are on)
+        B = z_chd.shape[0]
+        note_sampled = temperature is not None or dur_temperature is not None
+        creq = self._chord_request(B, chord_temperature, chroma_temperature, keep_chords, seed, draw, sample_offset, note_sampled)
+        note_kw = {k: kw[k] for k in DECODE_KEYS}
+        if creq is not None and creq.sampled and not note_sampled:
+            note_kw.update(seed=None, draw=None, sample_offset=None)                # (they belong to the chord decode alone)
+        req = self._request(B, **note_kw)                                           # (bad values are a ValueError whatever device the inputs are on)
         _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')
         self.eval()
         refresh_weight_shadows()
+        draw0 = self._sample_draws
         with torch.no_grad():
             self._decode(z_chd, z_rhy, req)
             pr_mat, notes, count, x, err = self.decoder.grid_to_pr_and_notes_batch(self.decoder.last_xhat, max_notes)
-            c, _ = self.chd_decoder.decode_tokens(z_chd)
+            if creq is None:
+                c, _ = self.chd_decoder.decode_tokens(z_chd)
+                if return_logprob:
+                    return pr_mat, x, c, notes, count, err, self.decoder.decode_logprob()
+                return pr_mat, x, c, notes, count, err
+            out = self._decode_chords(z_chd, creq, draw0, return_logprob)
+            if creq.sampled and draw is None and self._sample_draws == draw0:
+                self._sample_draws += 1
             if return_logprob:
-                return pr_mat, x, c, notes, count, err, self.decoder.decode_logprob()
-        return pr_mat, x, c, notes, count, err
+                return pr_mat, x, out[0], notes, count, err, self.decoder.decode_logprob(), out[2]
+        return pr_mat, x, out[0], notes, count, err
 
     def decode_logprob(self, z_chd, z_rhy, max_notes=10, **sampling):
         """decode_to_inputs' tuple plus the log-probabilities of that decode (INTEGRATION.md "Decode log-probabilities"): a
         DecodeLogprob(logp [B,2], logq [B,2], counts [B,4], err [B], step_logp [B,32,4], step_counts [B,32,4]) of device tensors --
         log p under the model's own softmax and log q under the distribution the decode drew from, (pitch, duration) sums over the
-        decisions taken.  **sampling: the keywords of a sampled decode (inference_decode)."""
+        decisions taken.  **sampling: the keywords of a sampled decode (inference_decode); with chord_temperature / chroma_temperature /
+        keep_chords the ChordLogprob of the row-independent chord decode follows the DecodeLogprob."""
         return self.decode_to_inputs(z_chd, z_rhy, max_notes, return_logprob=True, **sampling)
 
     @staticmethod
@@ -583,7 +659,7 @@ class DisentangleVAE(PytorchModel):
 
     def reencode(self, z_chd, z_rhy, **sampling):
         """(dist_chd, dist_rhy) of the music decoded from (z_chd, z_rhy): decode_to_inputs, then inference_encode; **sampling: the
-        keywords of a sampled decode (inference_decode)"""
+        keywords of a sampled decode (inference_decode) and of the chord decode (chord_temperature, chroma_temperature, keep_chords)"""
         pr_mat, _, c, _, _, _ = self.decode_to_inputs(z_chd, z_rhy, **sampling)
         return self.inference_encode(pr_mat, c)
 
