@@ -1105,6 +1105,37 @@ int ptv_pitch_mask_build(int* mask, long B, int lo, int hi, int pitch_classes, c
  * B < 1, steps_rows not in {1, B} or a NULL pointer: PTV_ERR_ARG before any launch. */
 int ptv_keep_force_build(const long* x, const unsigned char* steps, int steps_rows, long B, int* force_pitch, int* force_dur, int* err,
                          void* stream);
+/* Kept voices: the force arrays of a decode that keeps the LOWEST notes of a time step and decides the rest of it (csrc/keep_voice.hip;
+ * INTEGRATION.md "Kept voices").  The grammar orders the notes of a step by ascending pitch, so the lowest voice is a PREFIX of
+ * the step's note decisions: the note loop is forced through it and goes on freely.  x as in "Kept steps".  mode: uint8 [mode_rows][32],
+ * mode_rows = 1 (one row serves every sample) or B, per (b, t):
+ *   0  the step is free: every word -1.
+ *   1  the whole step is kept: ptv_keep_force_build's rule element for element, the <eos> included.
+ *   2  the voice of the step is kept.  Scan the slots s = 1, 2, ..., 15 with K = 0; at each slot, in this order:
+ *        (1) K == lowest[b][t]: stop;  (2) p = x[b][t][s][0]; p == 129: stop;  (3) p outside 0..127: set bit 0 of err[b] and stop (the bit's
+ *        meaning in "Kept steps": a kept step held an unforcible pitch before its <eos>);  (4) p >= below[b][t]: stop;  (5) the note is
+ *        kept: K += 1.
+ *      For n < K force_pitch[n][t*B + b] = x[b][t][n+1][0] and force_dur[d][n*R + t*B + b] = x[b][t][n+1][1+d] where that is 0 or 1 (else
+ *      -1) -- unless bit 0 of flags ("durations stay free") is set: then every duration word of a voice step is -1.  Every other word of
+ *      the step is -1: the <eos> of a voice step is never forced, after the voice the decoder decides as without a keep and may add notes
+ *      or end the step.
+ *   any other value: the step is free and bit 1 of err[b] is set.
+ * below / lowest: int32 [below_rows][32] / [lowest_rows][32], each with its own row count in {1, B}; NULL = no limit (its row count
+ * must still be 1 or B).  below is clamped to 0..128 and lowest to 0..15 on the device; 128 / 15 are no limit.  flags: bit 0 as above (it does not
+ * touch the steps of mode 1).  kept_n int32 [B][32] = the number of forced pitch decisions of the step (the >= 0 words of its force_pitch
+ * column), in every mode.  EVERY element of force_pitch [15][32B], force_dur [5][480B], kept_n and err [B] is written, by one thread each.
+ * ptv_grid_split_voice: the same selection as two model grids, voice and rest int64 [B][32][16][6].  Slot 0 of both is slot 0 of x; unused
+ * slots are <pad> (130) with duration bits 2; an <eos> slot written here has duration bits 2.
+ *   mode 2: voice = the K kept slots 1..K of x, then <eos> (none when K = 15); rest = the slots K+1.. of x moved down to slot 1, up to and
+ *     including its first <eos>; where x holds none, all of them and, while a slot is left, an <eos> behind them.
+ *   mode 1: voice = the step of x as it is (all 16 slots), rest = the empty step (<eos> in slot 1).  Mode 0 and any other value: the
+ *     reverse.  kept_n and err are the builder's (flags = 0).
+ * A NULL required pointer (below / lowest are optional), B < 1, a row count outside {1, B} or flags outside 0..1:
+ * PTV_ERR_ARG before any launch. */
+int ptv_keep_voice_force_build(const long* x, const unsigned char* mode, int mode_rows, const int* below, int below_rows, const int* lowest,
+                               int lowest_rows, int flags, long B, int* force_pitch, int* force_dur, int* kept_n, int* err, void* stream);
+int ptv_grid_split_voice(const long* x, const unsigned char* mode, int mode_rows, const int* below, int below_rows, const int* lowest,
+                         int lowest_rows, long B, long* voice, long* rest, int* kept_n, int* err, void* stream);
 int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
                              int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream);
 int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,

@@ -240,6 +240,97 @@ def build_keep(x, steps):
     return Keep(pitch, dur, err, B)
 
 
+def _check_grid(x):
+    if not torch.is_tensor(x) or x.device.type != 'cuda':
+        raise ValueError('x must be a device tensor: the grid int64 [B, 32, 16, 6]')
+    if x.dtype != torch.int64 or x.dim() != 4 or tuple(x.shape[1:]) != (32, 16, 6) or x.shape[0] < 1:
+        raise ValueError('x must be int64 [B, 32, 16, 6], got %s %s' % (x.dtype, tuple(x.shape)))
+
+
+def _voice_selection(x, voice_steps, below, lowest, whole_steps):
+    """the arguments both kept-voice entry points share, validated -- every ValueError before any launch -- and then put on the device:
+    -> (x contiguous, mode uint8 [rows, 32] (2 = voice step, 1 = whole step: a step in both selections is a whole step), below, lowest:
+    int32 [rows, 32] or None = no limit)"""
+    limits = [below, lowest]
+    for name, v, top in (('below', below, 128), ('lowest', lowest, 15)):
+        if v is not None and not torch.is_tensor(v) and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top):
+            raise ValueError('%s must be an integer in 0..%d or an int32 device tensor [B, 32] / [1, 32], got %r' % (name, top, v))
+    if below is None and lowest is None:
+        raise ValueError('a kept voice needs below (keep the notes under that pitch) or lowest (keep that many notes), or both')
+    sels = [s if s is None or torch.is_tensor(s) else keep_steps_row(s) for s in (voice_steps, whole_steps)]
+    if sels[0] is None:
+        raise ValueError('voice_steps must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice')
+    _check_grid(x)
+    B = x.shape[0]
+    for name, s in (('voice_steps', sels[0]), ('whole_steps', sels[1])):
+        if torch.is_tensor(s):
+            if s.device != x.device:
+                raise ValueError('%s must be on the device of x (or a host iterable of step indices / a slice)' % name)
+            if s.dtype not in (torch.bool, torch.uint8):
+                raise ValueError('%s must be bool or uint8, got %s' % (name, s.dtype))
+            if s.dim() != 2 or s.shape[1] != 32 or s.shape[0] not in (1, B):
+                raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(s.shape)))
+    for name, v in (('below', limits[0]), ('lowest', limits[1])):
+        if torch.is_tensor(v):
+            if v.device != x.device or v.dtype != torch.int32:
+                raise ValueError('%s must be int32 on the device of x, got %s on %s' % (name, v.dtype, v.device))
+            if v.dim() != 2 or v.shape[1] != 32 or v.shape[0] not in (1, B):
+                raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(v.shape)))
+    # ---- nothing below raises
+    voice, whole = sels
+    if not torch.is_tensor(voice) and not torch.is_tensor(whole):
+        row = bytearray(2 * v for v in voice)
+        for t, w in enumerate(whole or b''):
+            if w:
+                row[t] = 1
+        mode = torch.frombuffer(row, dtype=torch.uint8).view(1, 32).to(x.device)
+    else:
+        voice, whole = (s if s is None or torch.is_tensor(s) else torch.frombuffer(bytearray(s), dtype=torch.uint8).view(1, 32).to(x.device)
+                        for s in (voice, whole))
+        mode = (voice != 0).to(torch.uint8) * 2
+        if whole is not None:
+            mode = torch.where(whole != 0, torch.ones_like(mode[:1, :1]), mode)
+        mode = mode.contiguous()
+    limits = [v.contiguous() if torch.is_tensor(v) else (None if v is None else torch.full((1, 32), v, dtype=torch.int32, device=x.device))
+              for v in limits]
+    return x.contiguous(), mode, limits[0], limits[1]
+
+
+def build_keep_voice(x, voice_steps, below=None, lowest=None, durations=True, whole_steps=None, return_counts=False):
+    """the kept VOICE of a free-running decode -> Keep (ptv_keep_voice_force_build; INTEGRATION.md "Kept voices"): at the steps of
+    voice_steps the lowest notes of x's step -- those under pitch `below`, at most `lowest` of them, a prefix of the step -- are forced
+    and the decoder goes on above them; the steps of whole_steps are kept whole as by build_keep (a step in both is a whole step).
+    voice_steps / whole_steps: selections as build_keep's steps; below / lowest: a host int (0..128 / 0..15; 128 / 15 = no limit) or an
+    int32 device tensor [B, 32] / [1, 32], at least one of the two; durations=False leaves the duration bits of the voice steps free.
+    return_counts: -> (Keep, kept_n int32 [B, 32], the forced pitch decisions per step).  ValueError before any launch; nothing is
+    copied to the host."""
+    if not isinstance(durations, bool):
+        raise ValueError('durations must be a bool, got %r' % (durations,))
+    x, mode, below, lowest = _voice_selection(x, voice_steps, below, lowest, whole_steps)
+    B = x.shape[0]
+    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=x.device)
+    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=x.device)
+    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
+    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    call('ptv_keep_voice_force_build', ptr(x), ptr(mode), mode.shape[0], ptr(below), 1 if below is None else below.shape[0], ptr(lowest),
+         1 if lowest is None else lowest.shape[0], 0 if durations else 1, B, ptr(pitch), ptr(dur), ptr(kept_n), ptr(err), stream_ptr())
+    keep = Keep(pitch, dur, err, B)
+    return (keep, kept_n) if return_counts else keep
+
+
+def split_voice(x, voice_steps, below=None, lowest=None, whole_steps=None):
+    """the selection of build_keep_voice as two model grids (ptv_grid_split_voice) -> (x_voice, x_rest int64 [B, 32, 16, 6], kept_n int32
+    [B, 32], err int32 [B]): per step the kept notes and what the decoder would re-draw, each a valid step"""
+    x, mode, below, lowest = _voice_selection(x, voice_steps, below, lowest, whole_steps)
+    B = x.shape[0]
+    voice, rest = torch.empty_like(x), torch.empty_like(x)
+    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
+    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    call('ptv_grid_split_voice', ptr(x), ptr(mode), mode.shape[0], ptr(below), 1 if below is None else below.shape[0], ptr(lowest),
+         1 if lowest is None else lowest.shape[0], B, ptr(voice), ptr(rest), ptr(kept_n), ptr(err), stream_ptr())
+    return voice, rest, kept_n, err
+
+
 def check_keep(keep, batch=None):
     """ValueError unless keep is None or a Keep whose arrays fit its batch (and `batch`, the rows of the decode, where the caller knows them)"""
     if keep is None:

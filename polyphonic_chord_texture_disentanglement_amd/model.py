@@ -13,8 +13,8 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import (Keep, build_chord_keep, build_keep, check_chord_keep, check_chord_sampling, check_constraints, check_keep,
-                              check_sampling, make_block, sampling_words)
+from .functional_free import (Keep, build_chord_keep, build_keep, build_keep_voice, check_chord_keep, check_chord_sampling,
+                              check_constraints, check_keep, check_sampling, make_block, sampling_words, split_voice)
 from .optim import refresh_weight_shadows
 from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
@@ -456,6 +456,27 @@ class DisentangleVAE(PytorchModel):
         and fed back like decisions; everything else is decided as without it.  err[b] bit 0: a kept step of sample b held a pitch outside
         0..129 before its <eos>; that decision stays free.  Nothing is copied to the host."""
         return build_keep(x, steps)
+
+    def keep_voice(self, x, voice_steps, below=None, lowest=None, durations=True, whole_steps=None, return_counts=False):
+        """The kept voice of a decode -> functional_free.Keep for keep=, as keep() gives it (ptv_keep_voice_force_build; INTEGRATION.md
+        "Kept voices").  x: the grid as in keep(); voice_steps / whole_steps: selections as keep()'s steps.  At a voice step the LOWEST
+        notes of x's step are forced -- the notes under pitch `below` (0..128), at most `lowest` of them (0..15): a prefix of the step,
+        which the grammar orders by ascending pitch -- with their duration bits (durations=False: pitches only); the <eos> is not forced,
+        so above the voice the decoder decides as without a keep: it may add notes or end the step.  A whole step is kept as by keep(); a
+        step in both selections is a whole step.  below / lowest: a host int or an int32 device tensor [B, 32] / [1, 32]; at least one is
+        given.  A pitch_mask or ascending never checks a forced decision, and ascending continues strictly above the kept voice.
+        err[b] bit 0: a kept step of sample b held an unforcible pitch before its <eos> (the voice ends there); bit 1: a mode byte that
+        is none of 0 / 1 / 2 (never from here).  return_counts=True: -> (Keep, kept_n int32 [B, 32], the forced pitch decisions per
+        step).  Nothing is copied to the host."""
+        return build_keep_voice(x, voice_steps, below, lowest, durations, whole_steps, return_counts)
+
+    def split_voice(self, x, voice_steps, below=None, lowest=None, whole_steps=None):
+        """The selection of keep_voice as two grids -> (x_voice, x_rest, kept_n, err) (ptv_grid_split_voice): x_voice holds per step the
+        notes keep_voice forces (a voice step: the kept notes and an <eos>; a whole step: the step; a free step: the empty step), x_rest
+        the others moved down to slot 1, both int64 [B, 32, 16, 6] in the model's layout -- what score, reconstruction_report, keep and
+        grid_to_pr_and_notes_batch take; kept_n int32 [B, 32] and err int32 [B] as keep_voice's.  Split x and a decode that kept its voice
+        with the same arguments to compare the re-drawn upper voices with the original ones.  Nothing is copied to the host."""
+        return split_voice(x, voice_steps, below, lowest, whole_steps)
 
     def pitch_mask(self, c=None, pitch_classes=None, lo=None, hi=None, batch=None):
         """int32 device tensor [B, 32, 4] for pitch_mask= (ptv_pitch_mask_build): bit p & 31 of word p >> 5 of [b, t] set = grid pitch p
