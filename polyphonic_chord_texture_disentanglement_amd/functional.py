@@ -791,7 +791,8 @@ SHADOW_T_SLOT = 7       # pool stream of the transposed bf16 weight shadows' ref
 # note-summary bi-GRU: panels of rows sorted by length (ptv_rows_by_length + the *_perm entry points).  Measured, round 5 (profiles/
 # r05_ab_runs.txt): the launches do half the work (mean length 3.8 against a panel maximum of 8) but stay as long as their longest panel --
 # 225 / 242 us against 210 / 233 us in situ, step 7.69-7.71 against 7.64-7.67 ms: they are latency-bound per step, and what they leave
-# free nobody needs at that moment.  Off; the capability stays (it is the sequence packing of pack_padded_sequence, ptvae.py:446-453).
+# free nobody needs at that moment.  On by default since round 6, when the step had become throughput-bound (6.29-6.32 -> 6.23-6.26 ms;
+# PTV_SORT_ROWS=0 = off); it is the sequence packing of pack_padded_sequence, ptvae.py:446-453.
 SORT_ROWS = os.environ.get('PTV_SORT_ROWS', '1') == '1'
 # (Round-4 scheduling experiments on the step's tail -- chain-first bi-GRU backward, parameter-gradient products launched when the backward
 # pass ends, row kernels taking turns with the persistent launches, forks before / after the chain's dX products -- all measured slower
@@ -2453,17 +2454,49 @@ CHD_PARAM_NAMES = ['init_input', 'z2dec_hid.weight', 'z2dec_hid.bias', 'z2dec_in
                    'gru.weight_ih_l0', 'gru.weight_hh_l0', 'gru.bias_ih_l0', 'gru.bias_hh_l0',
                    'root_out.weight', 'root_out.bias', 'chroma_out.weight', 'chroma_out.bias',
                    'bass_out.weight', 'bass_out.bias']
+# parameter -> its slot in the chord decoder's tables: enum PtvCdfTensor and PtvCdsTensor name all 15, PtvCdbTensor the weight matrices
+# and, as G_<slot>, every gradient
+_CHD_SLOTS = dict(zip(CHD_PARAM_NAMES, ('INIT_INPUT', 'W_ZHID', 'B_ZHID', 'W_ZIN', 'B_ZIN', 'W_IH', 'W_HH', 'B_IH', 'B_HH', 'W_ROOT', 'B_ROOT',
+                                        'W_CHROMA', 'B_CHROMA', 'W_BASS', 'B_BASS')))
 
 
-CHD_BWD_COMPOSITE = os.environ.get('PTV_BWD_COMPOSITES', '1') != '0'     # ChordDecoderTFFn.backward through ptv_chord_decoder_bwd (one C call: 26 launches + the persistent launch's turn)
+def _chd_slots(P, pre='', biases=True):
+    """{pre + slot: tensor} of P {CHD_PARAM_NAMES: tensor}: the parameters or, with pre = 'G_', their gradient buffers; biases=False: the
+    weight matrices alone (no bias, no start token)"""
+    return {pre + s: P[n] for n, s in _CHD_SLOTS.items() if biases or s.startswith('W_')}
+
+
+class ChordDecoderState:
+    """What a chord decoder forward (teacher-forced or the step loop) leaves for its backward (a plain object: _record_stream and
+    Side.keep walk its __dict__).  Geometry: T, B, H, I, prec.  Saved tensors: hall [T+1,B,H] fp32 states (slot 0 = z2dec_hid(z)),
+    gates [T,4,B,H] of _act_dtype(prec, H), toks [T,B,I] the tokens that were fed, z_in [B,Zi]."""
+
+    def __init__(self, T, B, H, I, prec, *, hall, gates, toks, z_in):
+        self.T, self.B, self.H, self.I, self.prec = T, B, H, I, prec
+        self.hall, self.gates, self.toks, self.z_in = hall, gates, toks, z_in
+        for name, t, shape in (('hall', hall, (T + 1, B, H)), ('gates', gates, (T, 4, B, H)), ('toks', toks, (T, B, I)), ('z_in', z_in, (B,))):
+            if t.dim() != max(len(shape), 2) or tuple(t.shape[:len(shape)]) != shape or not t.is_contiguous():
+                raise ValueError('ChordDecoderState: %s %s, strides %s: no contiguous [%s%s]'
+                                 % (name, tuple(t.shape), t.stride(), ','.join(map(str, shape)), ',Zi' * (name == 'z_in')))
+        for name, t, dt in (('hall', hall, F32), ('gates', gates, _act_dtype(prec, H))):
+            if t.dtype != dt:
+                raise ValueError('ChordDecoderState: %s is %s, with prec %d and H %d it holds %s' % (name, t.dtype, prec, H, dt))
+
+
+def _chord_decoder_leave(ctx, state, z, params):
+    """what every chord decoder forward leaves on its node"""
+    ctx.save_for_backward(z, *params)
+    ctx.saved_state = state
+
+
+CHD_BWD_COMPOSITE = os.environ.get('PTV_BWD_COMPOSITES', '1') != '0'     # chord_decoder_bwd through ptv_chord_decoder_bwd (one C call: 26 launches + the persistent launch's turn)
 _CDB = SlotTable('CDB')
 
 
 def _chord_decoder_bwd_composite(P, st, z, droot, dchroma, dbass):
     """-> (dz, {name: gradient}) when ptv_chord_decoder_bwd ran, else None (the caller sequences the launches itself: same bits)"""
-    prec, T, B, H, I = st['prec'], st['T'], st['B'], st['H'], st['I']
+    prec, T, B, H, I = st.prec, st.T, st.B, st.H, st.I
     dev = z.device
-    hall, gates, toks, z_in = st['hall'], st['gates'], st['toks'], st['z_in']
     dls = []
     for dl in (droot, dchroma, dbass):
         if dl is not None:
@@ -2472,33 +2505,27 @@ def _chord_decoder_bwd_composite(P, st, z, droot, dchroma, dbass):
                 return None
         dls.append(dl)
     adt = _act_dtype(prec, H)
-    if (torch.cuda.is_current_stream_capturing() or hall.dtype != F32 or gates.dtype != adt or z.dtype != F32 or not z.is_contiguous()
-            or not hall.is_contiguous() or not gates.is_contiguous() or not toks.is_contiguous() or not z_in.is_contiguous()):
+    # (fp32 states and four contiguous tensors are the state's own guarantee; its gates were checked against the storage switch of the forward)
+    if torch.cuda.is_current_stream_capturing() or st.gates.dtype != adt or z.dtype != F32 or not z.is_contiguous():
         return None                      # (inside a capture the persistent launch's turn must go through wait_event(): the Python path)
     w_hh = P['gru.weight_hh_l0']
     wt = _WT(w_hh, prec) if adt == BF16 else None
     persist = bool(adt == BF16 and wt is not None and T >= 2 and persist_supported(1, B, H, T))
     S = persist_splitk(1, B, H) if persist else 0
-    Z, Zi = z.shape[1], z_in.shape[1]
+    Z, Zi = z.shape[1], st.z_in.shape[1]
     dims = {'B': B, 'T': T, 'H': H, 'I': I, 'Z': Z, 'ZI': Zi, 'PREC': prec, 'ACT_BF16': adt == BF16, 'NROOT': P['root_out.weight'].shape[0],
             'NCHROMA': P['chroma_out.weight'].shape[0], 'NBASS': P['bass_out.weight'].shape[0], 'PERSIST': persist, 'SPLITK': S}
     G = {n: _gbuf(P[n]) for n in CHD_PARAM_NAMES}
     dz = _empty(B, Z, dev=dev)
-    tens = {'Z': z, 'W_ZHID': P['z2dec_hid.weight'], 'W_ZIN': P['z2dec_in.weight'], 'W_IH': P['gru.weight_ih_l0'], 'W_HH': w_hh,
-            'W_ROOT': P['root_out.weight'], 'W_CHROMA': P['chroma_out.weight'], 'W_BASS': P['bass_out.weight'], 'WT16_HH': wt,
-            'HALL': hall, 'GATES': gates, 'TOKS': toks, 'Z_IN': z_in, 'DROOT': dls[0], 'DCHROMA': dls[1], 'DBASS': dls[2], 'DZ': dz,
-            'G_INIT_INPUT': G['init_input'], 'G_W_ZHID': G['z2dec_hid.weight'], 'G_B_ZHID': G['z2dec_hid.bias'], 'G_W_ZIN': G['z2dec_in.weight'],
-            'G_B_ZIN': G['z2dec_in.bias'], 'G_W_IH': G['gru.weight_ih_l0'], 'G_B_IH': G['gru.bias_ih_l0'], 'G_W_HH': G['gru.weight_hh_l0'],
-            'G_B_HH': G['gru.bias_hh_l0'], 'G_W_ROOT': G['root_out.weight'], 'G_B_ROOT': G['root_out.bias'], 'G_W_CHROMA': G['chroma_out.weight'],
-            'G_B_CHROMA': G['chroma_out.bias'], 'G_W_BASS': G['bass_out.weight'], 'G_B_BASS': G['bass_out.bias'],
-            'DHS': _empty(T * B, H, dev=dev), 'DGI': _empty(T, B, 3 * H, dev=dev, dtype=adt), 'DGH': _empty(T, B, 3 * H, dev=dev, dtype=adt),
+    tens = {'Z': z, 'WT16_HH': wt, 'HALL': st.hall, 'GATES': st.gates, 'TOKS': st.toks, 'Z_IN': st.z_in, 'DROOT': dls[0], 'DCHROMA': dls[1],
+            'DBASS': dls[2], 'DZ': dz, 'DHS': _empty(T * B, H, dev=dev), 'DGI': _empty(T, B, 3 * H, dev=dev, dtype=adt), 'DGH': _empty(T, B, 3 * H, dev=dev, dtype=adt),
             'DHZ': None if persist else _empty(2, B, H, dev=dev), 'DH0': _empty(B, H, dev=dev), 'DZG': _empty(B, 3 * H, dev=dev),
             'DZ_IN': _empty(B, Zi, dev=dev), 'DTOK0': _empty(B, I, dev=dev),
             'XCH': torch.empty(T * B * 3 * H, device=dev, dtype=BF16) if persist else None,
             'PART': torch.empty(lib().ptv_gru_persist_part_elems(1, B, H, S), device=dev) if S else None,
             'SYNC': _persist_sync(1, dev) if persist else None}
     turn = _CompositeTurn(cur_stream()) if persist else None
-    slots = _CDB.pointers(tens, handles=turn.handles if turn else None)
+    slots = _CDB.pointers(_chd_slots(P, biases=False), _chd_slots(G, 'G_'), tens, handles=turn.handles if turn else None)
     _chain_prio()
     rc = lib().ptv_chord_decoder_bwd(slots, _CDB.dims(dims), stream_ptr())
     if rc == -3:                          # (persist_supported() was asked before the arena views were taken)
@@ -2512,115 +2539,126 @@ def _chord_decoder_bwd_composite(P, st, z, droot, dchroma, dbass):
     return dz, G
 
 
+def _chord_decoder_tf_composite(P, z, c_sm, prec, T, B, H, I):
+    """-> (ChordDecoderState, root, chroma, bass [T*B, n]) when ptv_chord_decoder_fwd took the call (the whole forward behind ONE C call,
+    csrc/composite.hip), else None"""
+    if not (c_sm.is_contiguous() and c_sm.dtype == F32 and z.dtype == F32) or capturing_part():
+        return None
+    dev = z.device
+    Zi = P['z2dec_in.weight'].shape[0]
+    adt = _act_dtype(prec, H)
+    hall, z_in, toks = _empty(T + 1, B, H, dev=dev), _empty(B, Zi, dev=dev), _empty(T, B, I, dev=dev)
+    gi, zg = _empty(T * B, 3 * H, dev=dev), _empty(B, 3 * H, dev=dev)
+    gates = _empty(T, 4, B, H, dev=dev, dtype=adt)
+    nr, nc, nb = (P[n + '_out.weight'].shape[0] for n in ('root', 'chroma', 'bass'))
+    root, chroma, bass = _empty(T * B, nr, dev=dev), _empty(T * B, nc, dev=dev), _empty(T * B, nb, dev=dev)
+    tens = {'Z': z, 'C_SM': c_sm, 'HALL': hall, 'Z_IN': z_in, 'TOKS': toks, 'GI': gi, 'ZG': zg, 'GATES': gates, 'ROOT': root,
+            'CHROMA': chroma, 'BASS': bass}
+    dims = {'B': B, 'T': T, 'H': H, 'I': I, 'Z': z.shape[1], 'ZI': Zi, 'PREC': prec, 'GATES_BF16': adt == BF16, 'NROOT': nr,
+            'NCHROMA': nc, 'NBASS': nb}
+    slots = _CDF.pointers(_chd_slots(P), tens)
+    _chain_prio()
+    check(lib().ptv_chord_decoder_fwd(slots, _CDF.dims(dims), stream_ptr()), 'ptv_chord_decoder_fwd')
+    _DTF.count('chd_calls')              # (counted beside the note decoder's forward)
+    return ChordDecoderState(T, B, H, I, prec, hall=hall, gates=gates, toks=toks, z_in=z_in), root, chroma, bass
+
+
+def _chord_decoder_tf_launches(P, z, c_sm, prec, T, B, H, I):
+    """the same forward launch by launch -> (ChordDecoderState, root, chroma, bass [T*B, n])"""
+    dev = z.device
+    hall = _empty(T + 1, B, H, dev=dev)
+    gemm(z, P['z2dec_hid.weight'], hall[0], bias=P['z2dec_hid.bias'], prec=prec)
+    z_in = gemm(z, P['z2dec_in.weight'], bias=P['z2dec_in.bias'], prec=prec)
+    toks = _empty(T, B, I, dev=dev)
+    copy2d(toks[0], P['init_input'].view(1, -1), lds=0)
+    if T > 1:
+        copy2d(toks[1:].view((T - 1) * B, I), c_sm[:T - 1].reshape((T - 1) * B, I))
+    w_ih = P['gru.weight_ih_l0']
+    gi = gemm(toks.view(T * B, I), w_ih[:, :I], prec=prec)
+    zg = gemm(z_in, w_ih[:, I:], bias=P['gru.bias_ih_l0'], prec=prec)
+    gates = _empty(T, 4, B, H, dev=dev, dtype=_act_dtype(prec, H))
+    gru_fwd(prec, gi, B * 3 * H, 3 * H, P['gru.weight_hh_l0'], P['gru.bias_hh_l0'], hall, gates, gi2=zg, gi2_step=0,
+            gi2_ld=3 * H)
+    hs = hall[1:].view(T * B, H)
+    root = gemm(hs, P['root_out.weight'], bias=P['root_out.bias'], prec=prec)
+    chroma = gemm(hs, P['chroma_out.weight'], bias=P['chroma_out.bias'], prec=prec)
+    bass = gemm(hs, P['bass_out.weight'], bias=P['bass_out.bias'], prec=prec)
+    return ChordDecoderState(T, B, H, I, prec, hall=hall, gates=gates, toks=toks, z_in=z_in), root, chroma, bass
+
+
+def chord_decoder_bwd(P, st, z, droot, dchroma, dbass):
+    """the backward of either chord decoder node (the fed tokens are constants: ground truth or argmax one-hots) from the
+    ChordDecoderState st its forward left -> (dz, {CHD_PARAM_NAMES: gradient})"""
+    mark('chd_dec_bwd:start')
+    prec, T, B, H, I = st.prec, st.T, st.B, st.H, st.I
+    dev = z.device
+    hall, toks = st.hall, st.toks
+    if CHD_BWD_COMPOSITE:
+        res = _chord_decoder_bwd_composite(P, st, z, droot, dchroma, dbass)
+        if res is not None:
+            mark('chd_dec_bwd:end')
+            return res
+    hs = hall[1:].view(T * B, H)
+    G = {}
+    dhs = None
+    for name, dlog in (('root_out', droot), ('chroma_out', dchroma), ('bass_out', dbass)):
+        w = P[name + '.weight']
+        if dlog is None:
+            G[name + '.weight'], G[name + '.bias'] = _gbuf(w), _gbuf(P[name + '.bias'])
+            continue
+        d2 = dlog.contiguous().view(T * B, -1)
+        if dhs is None:
+            dhs = gemm(d2, w, tb=True, prec=prec)
+        else:
+            gemm(d2, w, dhs, tb=True, acc=True, prec=prec)
+        # (weight and bias gradient in one pass over the logits' gradient: ptv_wgrad's colsum_a, as ptv_chord_decoder_bwd's batch does)
+        G[name + '.weight'], G[name + '.bias'] = wgrad_bias(d2, hs, _gbuf(w), _gbuf(P[name + '.bias']), prec)
+    if dhs is None:
+        dhs = _zeros(T * B, H, dev=dev)
+    w_hh, w_ih = P['gru.weight_hh_l0'], P['gru.weight_ih_l0']
+    # (per-step kernels, not the persistent launch: persistent launches take turns, and this short chain on its sibling stream had
+    # to wait for the decoder's 32-step time BPTT -- its dz then reached the chord encoder 0.3 ms after the decoder's own, round 4)
+    dgi, dgh, dh0 = gru_bwd(prec, hall, st.gates, w_hh, dh_ext=dhs.view(T, B, H), allow_persist=True)
+    G['gru.weight_hh_l0'], G['gru.bias_hh_l0'] = wgrad_bias(dgh.view(T * B, 3 * H), hall[:T].view(T * B, H), _gbuf(w_hh),
+                                                            _gbuf(P['gru.bias_hh_l0']), prec)
+    dzg = sum_steps(dgi)
+    g = _gbuf(w_ih)
+    _, G['gru.bias_ih_l0'] = wgrad_bias(dzg, st.z_in, g[:, I:], _gbuf(P['gru.bias_ih_l0']), prec)
+    gemm(dgi.view(T * B, 3 * H), toks.view(T * B, I), g[:, :I], ta=True, tb=True, acc=True, prec=prec)
+    G['gru.weight_ih_l0'] = g
+    dz_in = gemm(dzg, w_ih[:, I:], tb=True, prec=prec)
+    dtok0 = gemm(dgi[0], w_ih[:, :I], tb=True, prec=prec)                     # only the learned start token
+    G['init_input'] = _bgrad(P['init_input'], dtok0)
+    w_zh, w_zi = P['z2dec_hid.weight'], P['z2dec_in.weight']
+    dz = gemm(dh0, w_zh, tb=True, prec=prec)
+    gemm(dz_in, w_zi, dz, tb=True, acc=True, prec=prec)
+    G['z2dec_hid.weight'], G['z2dec_hid.bias'] = wgrad_bias(dh0, z, _gbuf(w_zh), _gbuf(P['z2dec_hid.bias']), prec)
+    G['z2dec_in.weight'], G['z2dec_in.bias'] = wgrad_bias(dz_in, z, _gbuf(w_zi), _gbuf(P['z2dec_in.bias']), prec)
+    mark('chd_dec_bwd:end')
+    return dz, G
+
+
 class ChordDecoderTFFn(torch.autograd.Function):
-    """(z_chd [B,Z], c_sm [8,B,36] step-major, *params) -> root [8,B,12], chroma [8,B,24], bass [8,B,12]"""
+    """(z_chd [B,Z], c_sm [8,B,36] step-major, *params) -> root [8,B,12], chroma [8,B,24], bass [8,B,12]; the forward's ChordDecoderState is
+    `grad_fn.saved_state`"""
 
     @staticmethod
     def forward(ctx, z, c_sm, prec, *params):
         P = dict(zip(CHD_PARAM_NAMES, params))
-        dev = z.device
         z = z.contiguous()
-        B = z.shape[0]
-        T = c_sm.shape[0]
-        H = P['gru.weight_hh_l0'].shape[1]
-        I = c_sm.shape[2]
-        if CHD_COMPOSITE and c_sm.is_contiguous() and c_sm.dtype == F32 and z.dtype == F32 and not capturing_part():
-            # the whole forward behind ONE C call (ptv_chord_decoder_fwd, csrc/composite.hip)
-            Zi = P['z2dec_in.weight'].shape[0]
-            adt = _act_dtype(prec, H)
-            hall, z_in, toks = _empty(T + 1, B, H, dev=dev), _empty(B, Zi, dev=dev), _empty(T, B, I, dev=dev)
-            gi, zg = _empty(T * B, 3 * H, dev=dev), _empty(B, 3 * H, dev=dev)
-            gates = _empty(T, 4, B, H, dev=dev, dtype=adt)
-            nr, nc, nb = (P[n + '_out.weight'].shape[0] for n in ('root', 'chroma', 'bass'))
-            root, chroma, bass = _empty(T * B, nr, dev=dev), _empty(T * B, nc, dev=dev), _empty(T * B, nb, dev=dev)
-            tens = {'Z': z, 'C_SM': c_sm, 'W_ZHID': P['z2dec_hid.weight'], 'B_ZHID': P['z2dec_hid.bias'], 'W_ZIN': P['z2dec_in.weight'],
-                    'B_ZIN': P['z2dec_in.bias'], 'INIT_INPUT': P['init_input'], 'W_IH': P['gru.weight_ih_l0'], 'B_IH': P['gru.bias_ih_l0'],
-                    'W_HH': P['gru.weight_hh_l0'], 'B_HH': P['gru.bias_hh_l0'], 'W_ROOT': P['root_out.weight'], 'B_ROOT': P['root_out.bias'],
-                    'W_CHROMA': P['chroma_out.weight'], 'B_CHROMA': P['chroma_out.bias'], 'W_BASS': P['bass_out.weight'],
-                    'B_BASS': P['bass_out.bias'], 'HALL': hall, 'Z_IN': z_in, 'TOKS': toks, 'GI': gi, 'ZG': zg, 'GATES': gates, 'ROOT': root,
-                    'CHROMA': chroma, 'BASS': bass}
-            dims = {'B': B, 'T': T, 'H': H, 'I': I, 'Z': z.shape[1], 'ZI': Zi, 'PREC': prec, 'GATES_BF16': adt == BF16, 'NROOT': nr,
-                    'NCHROMA': nc, 'NBASS': nb}
-            slots = _CDF.pointers(tens)
-            _chain_prio()
-            check(lib().ptv_chord_decoder_fwd(slots, _CDF.dims(dims), stream_ptr()), 'ptv_chord_decoder_fwd')
-            _DTF.count('chd_calls')              # (counted beside the note decoder's forward)
-            ctx.save_for_backward(z, *params)
-            ctx.st = dict(hall=hall, gates=gates, toks=toks, z_in=z_in, prec=prec, T=T, B=B, H=H, I=I)
-            return root.view(T, B, -1), chroma.view(T, B, -1), bass.view(T, B, -1)
-        hall = _empty(T + 1, B, H, dev=dev)
-        gemm(z, P['z2dec_hid.weight'], hall[0], bias=P['z2dec_hid.bias'], prec=prec)
-        z_in = gemm(z, P['z2dec_in.weight'], bias=P['z2dec_in.bias'], prec=prec)
-        toks = _empty(T, B, I, dev=dev)
-        copy2d(toks[0], P['init_input'].view(1, -1), lds=0)
-        if T > 1:
-            copy2d(toks[1:].view((T - 1) * B, I), c_sm[:T - 1].reshape((T - 1) * B, I))
-        w_ih = P['gru.weight_ih_l0']
-        gi = gemm(toks.view(T * B, I), w_ih[:, :I], prec=prec)
-        zg = gemm(z_in, w_ih[:, I:], bias=P['gru.bias_ih_l0'], prec=prec)
-        gates = _empty(T, 4, B, H, dev=dev, dtype=_act_dtype(prec, H))
-        gru_fwd(prec, gi, B * 3 * H, 3 * H, P['gru.weight_hh_l0'], P['gru.bias_hh_l0'], hall, gates, gi2=zg, gi2_step=0,
-                gi2_ld=3 * H)
-        hs = hall[1:].view(T * B, H)
-        root = gemm(hs, P['root_out.weight'], bias=P['root_out.bias'], prec=prec)
-        chroma = gemm(hs, P['chroma_out.weight'], bias=P['chroma_out.bias'], prec=prec)
-        bass = gemm(hs, P['bass_out.weight'], bias=P['bass_out.bias'], prec=prec)
-        ctx.save_for_backward(z, *params)
-        ctx.st = dict(hall=hall, gates=gates, toks=toks, z_in=z_in, prec=prec, T=T, B=B, H=H, I=I)
+        T, B, H, I = c_sm.shape[0], z.shape[0], P['gru.weight_hh_l0'].shape[1], c_sm.shape[2]
+        res = _chord_decoder_tf_composite(P, z, c_sm, prec, T, B, H, I) if CHD_COMPOSITE else None
+        if res is None:
+            res = _chord_decoder_tf_launches(P, z, c_sm, prec, T, B, H, I)
+        state, root, chroma, bass = res
+        _chord_decoder_leave(ctx, state, z, params)
         return root.view(T, B, -1), chroma.view(T, B, -1), bass.view(T, B, -1)
 
     @staticmethod
     def backward(ctx, droot, dchroma, dbass):
         z, *params = ctx.saved_tensors
-        mark('chd_dec_bwd:start')
-        P = dict(zip(CHD_PARAM_NAMES, params))
-        st = ctx.st
-        ctx.st = None
-        prec, T, B, H, I = st['prec'], st['T'], st['B'], st['H'], st['I']
-        dev = z.device
-        hall, toks = st['hall'], st['toks']
-        if CHD_BWD_COMPOSITE:
-            res = _chord_decoder_bwd_composite(P, st, z, droot, dchroma, dbass)
-            if res is not None:
-                mark('chd_dec_bwd:end')
-                return (res[0], None, None) + tuple(res[1][n] for n in CHD_PARAM_NAMES)
-        hs = hall[1:].view(T * B, H)
-        G = {}
-        dhs = None
-        for name, dlog in (('root_out', droot), ('chroma_out', dchroma), ('bass_out', dbass)):
-            w = P[name + '.weight']
-            if dlog is None:
-                G[name + '.weight'], G[name + '.bias'] = _gbuf(w), _gbuf(P[name + '.bias'])
-                continue
-            d2 = dlog.contiguous().view(T * B, -1)
-            if dhs is None:
-                dhs = gemm(d2, w, tb=True, prec=prec)
-            else:
-                gemm(d2, w, dhs, tb=True, acc=True, prec=prec)
-            # (weight and bias gradient in one pass over the logits' gradient: ptv_wgrad's colsum_a, as ptv_chord_decoder_bwd's batch does)
-            G[name + '.weight'], G[name + '.bias'] = wgrad_bias(d2, hs, _gbuf(w), _gbuf(P[name + '.bias']), prec)
-        if dhs is None:
-            dhs = _zeros(T * B, H, dev=dev)
-        w_hh, w_ih = P['gru.weight_hh_l0'], P['gru.weight_ih_l0']
-        # (per-step kernels, not the persistent launch: persistent launches take turns, and this short chain on its sibling stream had
-        # to wait for the decoder's 32-step time BPTT -- its dz then reached the chord encoder 0.3 ms after the decoder's own, round 4)
-        dgi, dgh, dh0 = gru_bwd(prec, hall, st['gates'], w_hh, dh_ext=dhs.view(T, B, H), allow_persist=True)
-        G['gru.weight_hh_l0'], G['gru.bias_hh_l0'] = wgrad_bias(dgh.view(T * B, 3 * H), hall[:T].view(T * B, H), _gbuf(w_hh),
-                                                                _gbuf(P['gru.bias_hh_l0']), prec)
-        dzg = sum_steps(dgi)
-        g = _gbuf(w_ih)
-        _, G['gru.bias_ih_l0'] = wgrad_bias(dzg, st['z_in'], g[:, I:], _gbuf(P['gru.bias_ih_l0']), prec)
-        gemm(dgi.view(T * B, 3 * H), toks.view(T * B, I), g[:, :I], ta=True, tb=True, acc=True, prec=prec)
-        G['gru.weight_ih_l0'] = g
-        dz_in = gemm(dzg, w_ih[:, I:], tb=True, prec=prec)
-        dtok0 = gemm(dgi[0], w_ih[:, :I], tb=True, prec=prec)                     # only the learned start token
-        G['init_input'] = _bgrad(P['init_input'], dtok0)
-        w_zh, w_zi = P['z2dec_hid.weight'], P['z2dec_in.weight']
-        dz = gemm(dh0, w_zh, tb=True, prec=prec)
-        gemm(dz_in, w_zi, dz, tb=True, acc=True, prec=prec)
-        G['z2dec_hid.weight'], G['z2dec_hid.bias'] = wgrad_bias(dh0, z, _gbuf(w_zh), _gbuf(P['z2dec_hid.bias']), prec)
-        G['z2dec_in.weight'], G['z2dec_in.bias'] = wgrad_bias(dz_in, z, _gbuf(w_zi), _gbuf(P['z2dec_in.bias']), prec)
-        mark('chd_dec_bwd:end')
+        state, ctx.saved_state = ctx.saved_state, None
+        dz, G = chord_decoder_bwd(dict(zip(CHD_PARAM_NAMES, params)), state, z, droot, dchroma, dbass)
         return (dz, None, None) + tuple(G[n] for n in CHD_PARAM_NAMES)
 
 
@@ -2647,36 +2685,50 @@ def _mem_order(ts, perms):
 WDUR = (1.0, 0.6, 0.4, 0.3, 0.3)          # ptvae.py:519-520
 
 
-def _pianotree_ce_fwd(pitch_m, dur_m, sm, x, sums, st, weighted=False, targets=None):
-    """targets: (pitch_t, dur_t, counts) in the logits' row order, or None = computed here  -> (pitch_t, dur_t, counts, gcnt)"""
+def _pianotree_target_buffers(B, dev):
+    """-> (pitch_t [480 B], dur_t [2400 B], counts [3] = valid pitch / duration targets, last note step with any: the zero-skip limit)"""
+    return torch.empty(B * 480, device=dev, dtype=torch.int32), torch.empty(B * 2400, device=dev, dtype=torch.int32), _izeros(3, dev)
+
+
+def _chord_target_buffers(B, dev):
+    """-> (root_t [8 B], chroma_t [96 B], bass_t [8 B]) for ptv_chord_targets to fill"""
+    return tuple(torch.empty(B * n, device=dev, dtype=torch.int32) for n in (8, 96, 8))
+
+
+def _pianotree_ce_fwd(pitch_m, dur_m, sm, x, sums, st, weighted, targets, fill):
+    """targets: (pitch_t, dur_t, counts) in the logits' row order; fill: they are _pianotree_target_buffers, computed here from x
+    -> gcnt (the weighted form's five group counts) or None"""
     dev = pitch_m.device
-    B = x.shape[0]
-    rows = B * 480
+    pitch_t, dur_t, counts = targets
+    rows = pitch_t.numel()
     NP = pitch_m.shape[-1]
-    if targets is not None:
-        pitch_t, dur_t, counts = targets
-    else:
-        pitch_t = torch.empty(rows, device=dev, dtype=torch.int32)
-        dur_t = torch.empty(rows * 5, device=dev, dtype=torch.int32)
-        counts = _izeros(3, dev)                             # valid pitch / duration targets; last note step with any (zero-skip limit)
-        call('ptv_pianotree_targets', ptr(x), B, int(sm), ptr(pitch_t), ptr(dur_t), ptr(counts), st)
+    if fill:
+        call('ptv_pianotree_targets', ptr(x), x.shape[0], int(sm), ptr(pitch_t), ptr(dur_t), ptr(counts), st)
     call('ptv_ce_fwd', ptr(pitch_m), pitch_m.stride(-2), ptr(pitch_t), rows, NP, 130, ptr(sums[0:]), st)
     if weighted:                              # 5 per-bit-position means, weighted (ptvae.py:512-527)
         gsum = _zeros(5, dev=dev)
         gcnt = _izeros(5, dev)
         call('ptv_ce_group_fwd', ptr(dur_m), 2, ptr(dur_t), rows * 5, 2, 2, 5, ptr(gsum), ptr(gcnt), st)
         call('ptv_wdur_finalize', ptr(gsum), ptr(gcnt), *WDUR, ptr(sums[1:]), ptr(counts[1:]), st)
-        return pitch_t, dur_t, counts, gcnt
+        return gcnt
     call('ptv_ce_fwd', ptr(dur_m), 2, ptr(dur_t), rows * 5, 2, 2, ptr(sums[1:]), st)
-    return pitch_t, dur_t, counts, None
+    return None
 
 
-def _pianotree_ce_bwd(pitch_m, dur_m, sm, pitch_t, dur_t, gs, st, gcnt=None):
+def _pianotree_grad_buffers(pitch_m, dur_m, sm):
+    """-> (dpitch, ddur) as the kernels write them, in the logits' memory layout (dpitch with their possibly padded row stride), and the
+    same two as a node returns them: permuted back when step-major"""
+    NP, ld = pitch_m.shape[-1], pitch_m.stride(-2)
+    dpitch = torch.empty(pitch_m.numel() // NP, ld, device=pitch_m.device)[:, :NP].as_strided(pitch_m.shape, pitch_m.stride())
+    ddur = torch.empty_like(dur_m)
+    return (dpitch, ddur), ((dpitch.permute(*_PERM[4]), ddur.permute(*_PERM[5])) if sm else (dpitch, ddur))
+
+
+def _pianotree_ce_bwd(pitch_m, dur_m, pitch_t, dur_t, gs, st, gcnt, dpitch, ddur):
+    """dpitch, ddur: _pianotree_grad_buffers' memory-layout pair"""
     NP = pitch_m.shape[-1]
     rows = pitch_t.numel()
-    ld = pitch_m.stride(-2)                                  # gradient in the logits' (possibly row-padded) layout
-    dpitch = torch.empty(rows, ld, device=pitch_m.device)[:, :NP].as_strided(pitch_m.shape, pitch_m.stride())
-    ddur = torch.empty_like(dur_m)
+    ld = pitch_m.stride(-2)
     call('ptv_ce_bwd', ptr(pitch_m), ld, ptr(pitch_t), rows, NP, 130, ptr(gs[0:]), ptr(dpitch), ld, st)
     if gcnt is not None:
         gs5 = _empty(5, dev=pitch_m.device)
@@ -2684,9 +2736,19 @@ def _pianotree_ce_bwd(pitch_m, dur_m, sm, pitch_t, dur_t, gs, st, gcnt=None):
         call('ptv_ce_group_bwd', ptr(dur_m), 2, ptr(dur_t), rows * 5, 2, 2, 5, ptr(gs5), ptr(ddur), 2, st)
     else:
         call('ptv_ce_bwd', ptr(dur_m), 2, ptr(dur_t), rows * 5, 2, 2, ptr(gs[1:]), ptr(ddur), 2, st)
-    if sm:
-        dpitch, ddur = dpitch.permute(*_PERM[4]), ddur.permute(*_PERM[5])
-    return dpitch, ddur
+
+
+def _chord_ce_fwd(root_m, chroma_m, bass_m, targets, sums, st):
+    """the three chord cross-entropies (12 root, 2 chroma, 12 bass classes; no ignored target) of targets = (root_t, chroma_t, bass_t)
+    into sums[4:7]"""
+    for k, (m, t, n) in enumerate(zip((root_m, chroma_m, bass_m), targets, (12, 2, 12))):
+        call('ptv_ce_fwd', ptr(m), n, ptr(t), t.numel(), n, -1, ptr(sums[4 + k:]), st)
+
+
+def _chord_ce_bwd(root_m, chroma_m, bass_m, targets, gs, grads, st):
+    """... and their gradients, scaled by gs[4:7], into grads = (droot, dchroma, dbass) laid out like the logits"""
+    for k, (m, t, g, n) in enumerate(zip((root_m, chroma_m, bass_m), targets, grads, (12, 2, 12))):
+        call('ptv_ce_bwd', ptr(m), n, ptr(t), t.numel(), n, -1, ptr(gs[4 + k:]), ptr(g), n, st)
 
 
 _LOSS_TOP = {}
@@ -2766,9 +2828,7 @@ def live_rows(x):
     R = 32 * B
     sort = SORT_DEC_ROWS and DEC_COMPOSITE and DEC_BWD_COMPOSITE and not torch.cuda.is_current_stream_capturing()
     row_live = _izeros(R, x.device) if sort else None
-    pitch_t = torch.empty(B * 480, device=x.device, dtype=torch.int32)
-    dur_t = torch.empty(B * 2400, device=x.device, dtype=torch.int32)
-    counts = _izeros(3, x.device)
+    pitch_t, dur_t, counts = _pianotree_target_buffers(B, x.device)
     call('ptv_pianotree_targets_rows', ptr(x), B, 1, ptr(pitch_t), ptr(dur_t), ptr(counts), ptr(row_live), stream_ptr())
     srt = None
     if sort:
@@ -2829,43 +2889,43 @@ def _vl_ok(*ts):
     return all(t.is_cuda and t.dtype == F32 and t.is_contiguous() for t in ts)
 
 
-def _vae_loss_fwd_composite(pitch_m, dur_m, sm_p, x, c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, sm_c, root_t, chroma_t, bass_t,
-                            targets, sums, out, scal, st):
-    """-> (pitch_t, dur_t, counts) when ptv_vae_loss_fwd ran (targets None: it computed them), else None"""
+# What VaeLossFn saves, in saved order: the logits in memory order (step-major or batch-major, see _mem_order), the two posteriors, the six
+# targets in the logits' row order -- and the nine gradients its backward returns, laid out like their inputs.  A field's name in upper
+# case is its slot of enum PtvVlTensor.
+LossTensors = collections.namedtuple('LossTensors', 'pitch dur mu_c sd_c mu_r sd_r root chroma bass pitch_t dur_t counts root_t chroma_t bass_t')
+LossGrads = collections.namedtuple('LossGrads', 'dpitch ddur dmu_c dsd_c dmu_r dsd_r droot dchroma dbass')
+# What a loss node's backward needs beyond tensors: scal (the six scalars of ptv_loss_finalize / ptv_loss_bwd_scales), gcnt (the weighted
+# duration form's group counts, else None), sm_p / sm_c (the PianoTree / chord logits are step-major); None where a node has no such input
+LossState = collections.namedtuple('LossState', 'scal gcnt sm_p sm_c')
+
+
+def _vl_slots(rec):
+    return {k.upper(): v for k, v in zip(rec._fields, rec)}
+
+
+def _vae_loss_fwd_composite(L, x, c, sm_p, sm_c, have_targets, sums, out, scal, st):
+    """-> True when ptv_vae_loss_fwd ran on the LossTensors L (have_targets False: it computed pitch_t, dur_t and counts too)"""
     B = x.shape[0]
-    NP = pitch_m.shape[-1]
-    if (x.dtype != torch.int64 or not _vl_ok(c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m) or pitch_m.dtype != F32 or dur_m.dtype != F32
-            or not dur_m.is_contiguous() or not _row_dense(pitch_m) or pitch_m.numel() != B * 480 * NP or dur_m.numel() != B * 4800):
-        return None
-    dev = pitch_m.device
-    if targets is not None:
-        pitch_t, dur_t, counts = targets
-    else:
-        pitch_t = torch.empty(B * 480, device=dev, dtype=torch.int32)
-        dur_t = torch.empty(B * 2400, device=dev, dtype=torch.int32)
-        counts = _izeros(3, dev)
-    dims = _VL.dims({'B': B, 'Z': mu_c.shape[1], 'NP': NP, 'LDP': pitch_m.stride(-2), 'SM_P': sm_p, 'SM_C': sm_c,
-                     'HAVE_TARGETS': targets is not None})
-    slots = _VL.pointers({'X': x, 'C': c, 'PITCH': pitch_m, 'DUR': dur_m, 'MU_C': mu_c, 'SD_C': sd_c, 'MU_R': mu_r, 'SD_R': sd_r,
-                          'ROOT': root_m, 'CHROMA': chroma_m, 'BASS': bass_m, 'PITCH_T': pitch_t, 'DUR_T': dur_t, 'COUNTS': counts,
-                          'ROOT_T': root_t, 'CHROMA_T': chroma_t, 'BASS_T': bass_t, 'SUMS': sums, 'OUT': out})
+    NP = L.pitch.shape[-1]
+    if (x.dtype != torch.int64 or not _vl_ok(c, L.mu_c, L.sd_c, L.mu_r, L.sd_r, L.root, L.chroma, L.bass) or L.pitch.dtype != F32
+            or L.dur.dtype != F32 or not L.dur.is_contiguous() or not _row_dense(L.pitch) or L.pitch.numel() != B * 480 * NP
+            or L.dur.numel() != B * 4800):
+        return False
+    dims = _VL.dims({'B': B, 'Z': L.mu_c.shape[1], 'NP': NP, 'LDP': L.pitch.stride(-2), 'SM_P': sm_p, 'SM_C': sm_c,
+                     'HAVE_TARGETS': have_targets})
+    slots = _VL.pointers(_vl_slots(L), {'X': x, 'C': c, 'SUMS': sums, 'OUT': out})
     rc = lib().ptv_vae_loss_fwd(slots, dims, (ctypes.c_double * 6)(*scal), st)
     check(rc, 'ptv_vae_loss_fwd')
     _VL.count()
-    return pitch_t, dur_t, counts
+    return True
 
 
-def _vae_loss_bwd_composite(gout, gs, pitch_m, dur_m, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, pitch_t, dur_t, counts, root_t, chroma_t,
-                            bass_t, dpitch, ddur, dmu_c, dsd_c, dmu_r, dsd_r, droot, dchroma, dbass, scal, st):
-    B = root_t.numel() // 8
-    NP = pitch_m.shape[-1]
-    if gout.dtype != F32 or not _row_dense(pitch_m) or not dur_m.is_contiguous():
+def _vae_loss_bwd_composite(gout, gs, L, D, scal, st):
+    """-> True when ptv_vae_loss_bwd wrote the LossGrads D of the LossTensors L"""
+    if gout.dtype != F32 or not _row_dense(L.pitch) or not L.dur.is_contiguous():
         return False
-    dims = _VL.dims({'B': B, 'Z': mu_c.shape[1], 'NP': NP, 'LDP': pitch_m.stride(-2)})
-    slots = _VL.pointers({'PITCH': pitch_m, 'DUR': dur_m, 'MU_C': mu_c, 'SD_C': sd_c, 'MU_R': mu_r, 'SD_R': sd_r, 'ROOT': root_m,
-                          'CHROMA': chroma_m, 'BASS': bass_m, 'PITCH_T': pitch_t, 'DUR_T': dur_t, 'COUNTS': counts, 'ROOT_T': root_t,
-                          'CHROMA_T': chroma_t, 'BASS_T': bass_t, 'GOUT': gout, 'GS': gs, 'DPITCH': dpitch, 'DDUR': ddur, 'DMU_C': dmu_c,
-                          'DSD_C': dsd_c, 'DMU_R': dmu_r, 'DSD_R': dsd_r, 'DROOT': droot, 'DCHROMA': dchroma, 'DBASS': dbass})
+    dims = _VL.dims({'B': L.root_t.numel() // 8, 'Z': L.mu_c.shape[1], 'NP': L.pitch.shape[-1], 'LDP': L.pitch.stride(-2)})
+    slots = _VL.pointers(_vl_slots(L), _vl_slots(D), {'GOUT': gout, 'GS': gs})
     rc = lib().ptv_vae_loss_bwd(slots, dims, (ctypes.c_double * 6)(*scal), st)
     check(rc, 'ptv_vae_loss_bwd')
     _VL.count('bwd_calls')
@@ -2890,83 +2950,56 @@ class VaeLossFn(torch.autograd.Function):
         targets = live.targets(x, sm_p) if live is not None else None
         (root_m, chroma_m, bass_m), sm_c = _mem_order([root, chroma, bass], [_chord_perm(root), _chord_perm(chroma),
                                                                               _chord_perm(bass)])
-        root_t = torch.empty(B * 8, device=dev, dtype=torch.int32)
-        chroma_t = torch.empty(B * 96, device=dev, dtype=torch.int32)
-        bass_t = torch.empty(B * 8, device=dev, dtype=torch.int32)
-        Z = mu_c.shape[1]
+        have = targets is not None
+        L = LossTensors(pitch_m, dur_m, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, *(targets if have else _pianotree_target_buffers(B, dev)),
+                        *_chord_target_buffers(B, dev))
 
         def small():
             # the two KL terms and the three chord cross-entropies: six ~5-us launches, next to the PianoTree cross-entropy instead of behind it
             st2 = stream_ptr()
-            call('ptv_chord_targets', ptr(c), B, int(sm_c), ptr(root_t), ptr(chroma_t), ptr(bass_t), st2)
+            call('ptv_chord_targets', ptr(c), B, int(sm_c), ptr(L.root_t), ptr(L.chroma_t), ptr(L.bass_t), st2)
             call('ptv_kl_fwd', ptr(mu_c), ptr(sd_c), mu_c.numel(), ptr(sums[2:]), st2)
             call('ptv_kl_fwd', ptr(mu_r), ptr(sd_r), mu_r.numel(), ptr(sums[3:]), st2)
-            call('ptv_ce_fwd', ptr(root_m), 12, ptr(root_t), B * 8, 12, -1, ptr(sums[4:]), st2)
-            call('ptv_ce_fwd', ptr(chroma_m), 2, ptr(chroma_t), B * 96, 2, -1, ptr(sums[5:]), st2)
-            call('ptv_ce_fwd', ptr(bass_m), 12, ptr(bass_t), B * 8, 12, -1, ptr(sums[6:]), st2)
+            _chord_ce_fwd(root_m, chroma_m, bass_m, (L.root_t, L.chroma_t, L.bass_t), sums, st2)
         out = _empty(11, dev=dev)
-        ctx.scal = (float(beta), float(w0), float(w1), float(B * Z), float(B * 8), float(B * 96))
-        comp = None
-        if LOSS_COMPOSITE and not weighted_dur:
-            comp = _vae_loss_fwd_composite(pitch_m, dur_m, sm_p, x, c, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, sm_c, root_t, chroma_t,
-                                           bass_t, targets, sums, out, ctx.scal, st)
-        if comp is not None:
-            pitch_t, dur_t, counts = comp
-            ctx.gcnt = None
-        else:
-            pitch_t, dur_t, counts, gcnt = _pianotree_ce_fwd(pitch_m, dur_m, sm_p, x, sums, st, weighted_dur, targets)
-            ctx.gcnt = gcnt
+        scal = (float(beta), float(w0), float(w1), float(B * mu_c.shape[1]), float(B * 8), float(B * 96))
+        gcnt = None
+        if not (LOSS_COMPOSITE and not weighted_dur and _vae_loss_fwd_composite(L, x, c, sm_p, sm_c, have, sums, out, scal, st)):
+            gcnt = _pianotree_ce_fwd(pitch_m, dur_m, sm_p, x, sums, st, weighted_dur, (L.pitch_t, L.dur_t, L.counts), not have)
             small()                               # (on a sibling stream beside the PianoTree cross-entropy: 8.298 against 8.302 ms -- in line)
-            call('ptv_loss_finalize', ptr(sums), ptr(counts), *ctx.scal, ptr(out), st)
-        ctx.save_for_backward(pitch_m, dur_m, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, pitch_t, dur_t, counts,
-                              root_t, chroma_t, bass_t)
-        ctx.sm = (sm_p, sm_c)
+            call('ptv_loss_finalize', ptr(sums), ptr(L.counts), *scal, ptr(out), st)
+        ctx.save_for_backward(*L)
+        ctx.saved_state = LossState(scal, gcnt, sm_p, sm_c)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        (pitch_m, dur_m, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, pitch_t, dur_t, counts, root_t, chroma_t,
-         bass_t) = ctx.saved_tensors
-        sm_p, sm_c = ctx.sm
-        dev = pitch_m.device
+        L, S = LossTensors(*ctx.saved_tensors), ctx.saved_state
         st = stream_ptr()
         reset_deferred()                        # first node of the backward pass: nothing may be left from an aborted one
-        gs = _empty(8, dev=dev)
-        dmu_c, dsd_c = torch.empty_like(mu_c), torch.empty_like(sd_c)
-        dmu_r, dsd_r = torch.empty_like(mu_r), torch.empty_like(sd_r)
-        droot, dchroma, dbass = torch.empty_like(root_m), torch.empty_like(chroma_m), torch.empty_like(bass_m)
-        done = False
-        if LOSS_COMPOSITE and ctx.gcnt is None:
-            NP = pitch_m.shape[-1]
-            ld = pitch_m.stride(-2)
-            dpitch = torch.empty(pitch_t.numel(), ld, device=dev)[:, :NP].as_strided(pitch_m.shape, pitch_m.stride())
-            ddur = torch.empty_like(dur_m)
-            done = _vae_loss_bwd_composite(gout.contiguous(), gs, pitch_m, dur_m, mu_c, sd_c, mu_r, sd_r, root_m, chroma_m, bass_m, pitch_t, dur_t,
-                                           counts, root_t, chroma_t, bass_t, dpitch, ddur, dmu_c, dsd_c, dmu_r, dsd_r, droot, dchroma, dbass,
-                                           ctx.scal, st)
-            if done and sm_p:
-                dpitch, ddur = dpitch.permute(*_PERM[4]), ddur.permute(*_PERM[5])
-        if not done:
-            call('ptv_loss_bwd_scales', ptr(gout.contiguous()), ptr(counts), *ctx.scal, ptr(gs), st)
+        gs = _empty(8, dev=L.pitch.device)
+        mem, (dpitch, ddur) = _pianotree_grad_buffers(L.pitch, L.dur, S.sm_p)
+        D = LossGrads(*mem, *(torch.empty_like(t) for t in (L.mu_c, L.sd_c, L.mu_r, L.sd_r, L.root, L.chroma, L.bass)))
+        gout = gout.contiguous()
 
         def small():
             st2 = stream_ptr()
-            call('ptv_kl_bwd', ptr(mu_c), ptr(sd_c), mu_c.numel(), ptr(gs[2:]), ptr(dmu_c), ptr(dsd_c), st2)
-            call('ptv_kl_bwd', ptr(mu_r), ptr(sd_r), mu_r.numel(), ptr(gs[3:]), ptr(dmu_r), ptr(dsd_r), st2)
-            call('ptv_ce_bwd', ptr(root_m), 12, ptr(root_t), root_t.numel(), 12, -1, ptr(gs[4:]), ptr(droot), 12, st2)
-            call('ptv_ce_bwd', ptr(chroma_m), 2, ptr(chroma_t), chroma_t.numel(), 2, -1, ptr(gs[5:]), ptr(dchroma), 2, st2)
-            call('ptv_ce_bwd', ptr(bass_m), 12, ptr(bass_t), bass_t.numel(), 12, -1, ptr(gs[6:]), ptr(dbass), 12, st2)
-        if not done:
-            dpitch, ddur = _pianotree_ce_bwd(pitch_m, dur_m, sm_p, pitch_t, dur_t, gs, st, ctx.gcnt)
+            call('ptv_kl_bwd', ptr(L.mu_c), ptr(L.sd_c), L.mu_c.numel(), ptr(gs[2:]), ptr(D.dmu_c), ptr(D.dsd_c), st2)
+            call('ptv_kl_bwd', ptr(L.mu_r), ptr(L.sd_r), L.mu_r.numel(), ptr(gs[3:]), ptr(D.dmu_r), ptr(D.dsd_r), st2)
+            _chord_ce_bwd(L.root, L.chroma, L.bass, (L.root_t, L.chroma_t, L.bass_t), gs, (D.droot, D.dchroma, D.dbass), st2)
+        if not (LOSS_COMPOSITE and S.gcnt is None and _vae_loss_bwd_composite(gout, gs, L, D, S.scal, st)):
+            call('ptv_loss_bwd_scales', ptr(gout), ptr(L.counts), *S.scal, ptr(gs), st)
+            _pianotree_ce_bwd(L.pitch, L.dur, L.pitch_t, L.dur_t, gs, st, S.gcnt, *mem)
             small()
-        if sm_c:
+        droot, dchroma, dbass = D.droot, D.dchroma, D.dbass
+        if S.sm_c:
             droot, dchroma, dbass = (t.permute(*_chord_perm(t)) for t in (droot, dchroma, dbass))
         # zero-skip limit for whoever consumes exactly these two gradients (DecoderTFFn / DecoderStepFn): the last note step with a
         # non-ignored target bounds where they can be non-zero -- known from the forward's target pass, no scan of the gradients
         _LOSS_TOP.clear()
-        if LOSS_TOP_HINT and sm_p:
-            _LOSS_TOP['hint'] = (dpitch, ddur, dpitch._version, ddur._version, counts[2:3])
-        return (dpitch, ddur, dmu_c, dsd_c, dmu_r, dsd_r, droot, dchroma, dbass) + (None,) * 7
+        if LOSS_TOP_HINT and S.sm_p:
+            _LOSS_TOP['hint'] = (dpitch, ddur, dpitch._version, ddur._version, L.counts[2:3])
+        return (dpitch, ddur, D.dmu_c, D.dsd_c, D.dmu_r, D.dsd_r, droot, dchroma, dbass) + (None,) * 7
 
 
 class SplitScalarsFn(torch.autograd.Function):
@@ -3001,25 +3034,27 @@ class ReconLossFn(torch.autograd.Function):
         x = x.contiguous()
         sums = _zeros(8, dev=dev)
         (pitch_m, dur_m), sm = _mem_order([pitch, dur], [_PERM[4], _PERM[5]])
-        pitch_t, dur_t, counts, gcnt = _pianotree_ce_fwd(pitch_m, dur_m, sm, x, sums, st, weighted_dur)
-        ctx.gcnt = gcnt
+        pitch_t, dur_t, counts = _pianotree_target_buffers(x.shape[0], dev)
+        gcnt = _pianotree_ce_fwd(pitch_m, dur_m, sm, x, sums, st, weighted_dur, (pitch_t, dur_t, counts), True)
         out = _empty(11, dev=dev)
-        ctx.scal = (0.0, float(w0), float(w1), 1.0, 1.0, 1.0)
-        call('ptv_loss_finalize', ptr(sums), ptr(counts), *ctx.scal, ptr(out), st)
+        scal = (0.0, float(w0), float(w1), 1.0, 1.0, 1.0)
+        call('ptv_loss_finalize', ptr(sums), ptr(counts), *scal, ptr(out), st)
         ctx.save_for_backward(pitch_m, dur_m, pitch_t, dur_t, counts)
-        ctx.sm = sm
+        ctx.saved_state = LossState(scal, gcnt, sm, None)
         return out[1:4].clone()
 
     @staticmethod
     def backward(ctx, g3):
         pitch_m, dur_m, pitch_t, dur_t, counts = ctx.saved_tensors
+        S = ctx.saved_state
         dev = pitch_m.device
         st = stream_ptr()
         g11 = _zeros(11, dev=dev)
         copy2d(g11[1:4].view(1, 3), g3.contiguous().view(1, 3))
         gs = _empty(8, dev=dev)
-        call('ptv_loss_bwd_scales', ptr(g11), ptr(counts), *ctx.scal, ptr(gs), st)
-        dpitch, ddur = _pianotree_ce_bwd(pitch_m, dur_m, ctx.sm, pitch_t, dur_t, gs, st, ctx.gcnt)
+        call('ptv_loss_bwd_scales', ptr(g11), ptr(counts), *S.scal, ptr(gs), st)
+        mem, (dpitch, ddur) = _pianotree_grad_buffers(pitch_m, dur_m, S.sm_p)
+        _pianotree_ce_bwd(pitch_m, dur_m, pitch_t, dur_t, gs, st, S.gcnt, *mem)
         return dpitch, ddur, None, None, None, None
 
 
@@ -3060,36 +3095,31 @@ class ChordLossFn(torch.autograd.Function):
         c = c.contiguous()
         (root_m, chroma_m, bass_m), sm = _mem_order([root, chroma, bass], [_chord_perm(root), _chord_perm(chroma),
                                                                             _chord_perm(bass)])
-        root_t = torch.empty(B * 8, device=dev, dtype=torch.int32)
-        chroma_t = torch.empty(B * 96, device=dev, dtype=torch.int32)
-        bass_t = torch.empty(B * 8, device=dev, dtype=torch.int32)
-        call('ptv_chord_targets', ptr(c), B, int(sm), ptr(root_t), ptr(chroma_t), ptr(bass_t), st)
+        targets = _chord_target_buffers(B, dev)
+        call('ptv_chord_targets', ptr(c), B, int(sm), *(ptr(t) for t in targets), st)
         sums = _zeros(8, dev=dev)
         counts = torch.ones(2, device=dev, dtype=torch.int32)
-        call('ptv_ce_fwd', ptr(root_m), 12, ptr(root_t), B * 8, 12, -1, ptr(sums[4:]), st)
-        call('ptv_ce_fwd', ptr(chroma_m), 2, ptr(chroma_t), B * 96, 2, -1, ptr(sums[5:]), st)
-        call('ptv_ce_fwd', ptr(bass_m), 12, ptr(bass_t), B * 8, 12, -1, ptr(sums[6:]), st)
+        _chord_ce_fwd(root_m, chroma_m, bass_m, targets, sums, st)
         out = _empty(11, dev=dev)
-        ctx.scal = (0.0, 0.0, 0.0, 1.0, float(B * 8), float(B * 96))
-        call('ptv_loss_finalize', ptr(sums), ptr(counts), *ctx.scal, ptr(out), st)
-        ctx.save_for_backward(root_m, chroma_m, bass_m, root_t, chroma_t, bass_t, counts)
-        ctx.sm = sm
+        scal = (0.0, 0.0, 0.0, 1.0, float(B * 8), float(B * 96))
+        call('ptv_loss_finalize', ptr(sums), ptr(counts), *scal, ptr(out), st)
+        ctx.save_for_backward(root_m, chroma_m, bass_m, *targets, counts)
+        ctx.saved_state = LossState(scal, None, None, sm)
         return out[7:11].clone()
 
     @staticmethod
     def backward(ctx, g4):
         root_m, chroma_m, bass_m, root_t, chroma_t, bass_t, counts = ctx.saved_tensors
+        S = ctx.saved_state
         dev = root_m.device
         st = stream_ptr()
         g11 = _zeros(11, dev=dev)
         copy2d(g11[7:11].view(1, 4), g4.contiguous().view(1, 4))
         gs = _empty(8, dev=dev)
-        call('ptv_loss_bwd_scales', ptr(g11), ptr(counts), *ctx.scal, ptr(gs), st)
+        call('ptv_loss_bwd_scales', ptr(g11), ptr(counts), *S.scal, ptr(gs), st)
         droot, dchroma, dbass = torch.empty_like(root_m), torch.empty_like(chroma_m), torch.empty_like(bass_m)
-        call('ptv_ce_bwd', ptr(root_m), 12, ptr(root_t), root_t.numel(), 12, -1, ptr(gs[4:]), ptr(droot), 12, st)
-        call('ptv_ce_bwd', ptr(chroma_m), 2, ptr(chroma_t), chroma_t.numel(), 2, -1, ptr(gs[5:]), ptr(dchroma), 2, st)
-        call('ptv_ce_bwd', ptr(bass_m), 12, ptr(bass_t), bass_t.numel(), 12, -1, ptr(gs[6:]), ptr(dbass), 12, st)
-        if ctx.sm:
+        _chord_ce_bwd(root_m, chroma_m, bass_m, (root_t, chroma_t, bass_t), gs, (droot, dchroma, dbass), st)
+        if S.sm_c:
             droot, dchroma, dbass = (t.permute(*_chord_perm(t)) for t in (droot, dchroma, dbass))
         return droot, dchroma, dbass, None
 

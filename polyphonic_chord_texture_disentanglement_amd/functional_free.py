@@ -1177,15 +1177,16 @@ class ChordDecoderStepFn(torch.autograd.Function):
                     src = (force['root'], force['chroma'], force['bass']) if force else (root, chroma, bass)
                     call('ptv_chord_token', ptr(src[0][t]), ptr(src[1][t]), ptr(src[2][t]), ptr(masks), ptr(toks[t + 1]), B,
                          stream_ptr())
-        ctx.save_for_backward(z, *params)
-        ctx.st = dict(hall=hall, gates=gates, toks=toks, z_in=z_in, prec=prec, T=T, B=B, H=H, I=I)
+        F_._chord_decoder_leave(ctx, F_.ChordDecoderState(T, B, H, I, prec, hall=hall, gates=gates, toks=toks, z_in=z_in), z, params)
         return root, chroma, bass
 
     @staticmethod
     def backward(ctx, droot, dchroma, dbass):
         # tokens are constants (ground truth or argmax one-hots): same BPTT as the teacher-forced path
-        g = F_.ChordDecoderTFFn.backward(ctx, droot, dchroma, dbass)
-        return (g[0], None, None, None, None) + tuple(g[3:])
+        z, *params = ctx.saved_tensors
+        state, ctx.saved_state = ctx.saved_state, None
+        dz, G = F_.chord_decoder_bwd(dict(zip(F_.CHD_PARAM_NAMES, params)), state, z, droot, dchroma, dbass)
+        return (dz, None, None, None, None) + tuple(G[n] for n in F_.CHD_PARAM_NAMES)
 
 
 # =============================================================================================
@@ -1302,12 +1303,8 @@ def chord_decode(z, P, prec, sampling=None, keep=None):
                C=_empty(B, T, 36, dev=dev), CHORD14=_empty(B, T, 14, dev=dev), STEP_LOGP=_empty(B, T, 3, dev=dev),
                STEP_LOGQ=_empty(B, T, 3, dev=dev), STEP_FORCED=torch.empty(B, T, 3, **i32), STEP_ERR=torch.empty(B, T, **i32),
                LOGP=_empty(B, 3, dev=dev), LOGQ=_empty(B, 3, dev=dev), FORCED=torch.empty(B, 3, **i32), ERR=torch.empty(B, **i32))
-    tens = {'Z': z, 'W_ZHID': P['z2dec_hid.weight'], 'B_ZHID': P['z2dec_hid.bias'], 'W_ZIN': P['z2dec_in.weight'],
-            'B_ZIN': P['z2dec_in.bias'], 'INIT_INPUT': P['init_input'], 'W_IH': w_ih, 'B_IH': P['gru.bias_ih_l0'],
-            'W_HH': P['gru.weight_hh_l0'], 'B_HH': P['gru.bias_hh_l0'], 'W_ROOT': P['root_out.weight'], 'B_ROOT': P['root_out.bias'],
-            'W_CHROMA': P['chroma_out.weight'], 'B_CHROMA': P['chroma_out.bias'], 'W_BASS': P['bass_out.weight'],
-            'B_BASS': P['bass_out.bias'], 'SAMPLE': sampling, 'KEEP_C': None if keep is None else keep.c,
-            'KEEP_STEPS': None if keep is None else keep.steps}
+    tens = dict(F_._chd_slots(P), Z=z, SAMPLE=sampling, KEEP_C=None if keep is None else keep.c,
+                KEEP_STEPS=None if keep is None else keep.steps)
     for k, v in tens.items():
         if v is not None and k not in ('SAMPLE', 'KEEP_STEPS') and (v.dtype != torch.float32 or not v.is_contiguous()):
             raise ValueError('ptv_chord_decode takes contiguous float32 tensors (%s is %s)' % (k, v.dtype))

@@ -429,6 +429,85 @@ def test_decoder_state_refuses_what_no_forward_leaves():
     assert len(want) == 14 + 5 + 1 + 10 and {id(x) for x in seen} == {id(x) for x in want}
 
 
+def test_chord_decoder_state_refuses_what_no_forward_leaves(monkeypatch):
+    """functional.ChordDecoderState (what either chord decoder forward leaves for chord_decoder_bwd): fp32 states of T + 1 steps, gates of the
+    storage dtype of (prec, H), the fed tokens, z_in, all contiguous and of the stated geometry; what it holds stays within reach of
+    _record_stream"""
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_
+    monkeypatch.setattr(F_, 'BF16_STORAGE', True)
+    T, B, H, I, Zi = 8, 3, 16, 36, 5
+    bf = torch.bfloat16
+    t = lambda *s, dt=torch.float32: torch.empty(*s, device='meta', dtype=dt)
+
+    def saved(gdt=torch.float32, h=H, **over):
+        kw = dict(hall=t(T + 1, B, h), gates=t(T, 4, B, h, dt=gdt), toks=t(T, B, I), z_in=t(B, Zi))
+        kw.update(over)
+        return kw
+    S = F_.ChordDecoderState
+    s = S(T, B, H, I, 0, **saved())
+    assert (s.T, s.B, s.H, s.I, s.prec) == (T, B, H, I, 0) and s.gates.dtype == torch.float32 and s.z_in.shape == (B, Zi)
+    assert S(T, B, H, I, 1, **saved(bf)).gates.dtype == bf
+    assert S(T, B, 12, I, 1, **saved(h=12)).gates.dtype == torch.float32                # (H no multiple of 8: fp32 storage in bf16 precision)
+    assert S(1, B, H, I, 1, hall=t(2, B, H), gates=t(1, 4, B, H, dt=bf), toks=t(1, B, I), z_in=t(B, Zi)).T == 1
+    for prec, gdt, h in ((0, bf, H), (1, torch.float32, H), (1, bf, 12)):
+        with pytest.raises(ValueError, match='gates'):
+            S(T, B, h, I, prec, **saved(gdt, h))
+    for name, over in (('hall', dict(hall=t(T, B, H))), ('hall', dict(hall=t(T + 1, B, H, dt=bf))), ('hall', dict(hall=t((T + 1) * B, H))),
+                       ('toks', dict(toks=t(T, B, I + 1))), ('toks', dict(toks=t(T, B + 1, I))), ('gates', dict(gates=t(T, 3, B, H))),
+                       ('z_in', dict(z_in=t(B + 1, Zi))), ('z_in', dict(z_in=t(B))),
+                       ('hall', dict(hall=t(T + 1, H, B).transpose(1, 2))), ('gates', dict(gates=t(T, 4, B, 2 * H)[..., ::2])),
+                       ('toks', dict(toks=t(B, T, I).transpose(0, 1))), ('z_in', dict(z_in=t(Zi, B).t()))):
+        with pytest.raises(ValueError, match='ChordDecoderState: ' + name):
+            S(T, B, H, I, 0, **saved(**over))
+    seen = []
+
+    class Probe(torch.Tensor):
+        is_cuda = True
+
+        def record_stream(self, stream):
+            seen.append(self)
+    kw = {k: torch.Tensor._make_subclass(Probe, torch.empty(v.shape, dtype=v.dtype)) for k, v in saved(bf).items()}
+    F_._record_stream(S(T, B, H, I, 1, **kw), None)
+    assert len(seen) == 4 and {id(x) for x in seen} == {id(x) for x in kw.values()}
+
+
+def test_chord_decoder_slot_helpers_name_only_slots_of_each_enum():
+    """functional._chd_slots, the one parameter-to-slot statement of the chord decoder's three tables: every name
+    it hands a table is an enumerator of that table's enum; CDF and CDS (whose C side refuses a NULL parameter) get all 15, CDB the seven
+    weight matrices and all 15 gradients"""
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_
+    from polyphonic_chord_texture_disentanglement_amd._lib import header_enum
+    P = {n: torch.empty(1) for n in F_.CHD_PARAM_NAMES}
+    enum = lambda tag: {k[len('PTV_%s_' % tag):] for k in header_enum('Ptv%sTensor' % tag.capitalize())}
+    every, weights, grads = F_._chd_slots(P), F_._chd_slots(P, biases=False), F_._chd_slots(P, 'G_')
+    assert len(every) == 15 and [every[F_._CHD_SLOTS[n]] is P[n] for n in P] == [True] * 15
+    params = lambda tag: {s for s in enum(tag) if s == 'INIT_INPUT' or s.split('_')[0] in ('W', 'B')}
+    assert set(every) == params('CDF') == params('CDS')
+    assert set(weights) == params('CDB') and len(weights) == 7 and all(weights[s] is every[s] for s in weights)
+    assert set(grads) == {s for s in enum('CDB') if s.startswith('G_')} and len(grads) == 15
+    assert [grads['G_' + F_._CHD_SLOTS[n]] is P[n] for n in P] == [True] * 15
+    for tag, maps in (('CDF', (every,)), ('CDS', (every,)), ('CDB', (weights, grads))):
+        F_.SlotTable(tag).pointers(*({s: None for s in m} for m in maps))               # (raises on a name the enum lacks)
+    with pytest.raises(KeyError, match='PtvCdb'):
+        F_.SlotTable('CDB').pointers({s: None for s in every})                           # CDB has no bias slot: nothing swallows that
+
+
+def test_loss_tensors_round_trip_in_saved_order():
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_
+    names = ['pitch', 'dur', 'mu_c', 'sd_c', 'mu_r', 'sd_r', 'root', 'chroma', 'bass', 'pitch_t', 'dur_t', 'counts', 'root_t', 'chroma_t',
+             'bass_t']
+    assert list(F_.LossTensors._fields) == names
+    ts = tuple(torch.full((1,), float(i)) for i in range(15))
+    L = F_.LossTensors(*ts)
+    assert tuple(L) == ts and all(getattr(L, n) is ts[i] for i, n in enumerate(names))
+    assert all(a is b for a, b in zip(F_.LossTensors(*tuple(L)), ts))                    # ctx.save_for_backward(*L) -> LossTensors(*saved_tensors)
+    assert F_._vl_slots(L) == {n.upper(): ts[i] for i, n in enumerate(names)}
+    assert F_.LossGrads._fields == ('dpitch', 'ddur', 'dmu_c', 'dsd_c', 'dmu_r', 'dsd_r', 'droot', 'dchroma', 'dbass')
+    assert F_.LossState._fields == ('scal', 'gcnt', 'sm_p', 'sm_c')
+    with pytest.raises(TypeError):
+        F_.LossTensors(*ts[:14])
+
+
 # ---- the free-running decode's host path: the kind of a block, the note loop's word, the coin masks, the decode request, the plan
 KIND_TABLE = {None: (0, 0, 0, 0, 0, 0, 'ptv_note_token', 'ptv_dur_gru_fwd', 'ptv_dur_out_token'),
               4: (4, 0x800000, 0, 0, 1, 32, 'ptv_note_token_sample', 'ptv_dur_gru_fwd_sample', 'ptv_dur_out_token_sample'),
