@@ -540,42 +540,243 @@ def gru_step(prec, hprev, gi, gi_ld, w_hh, b_hh, hout, *, gi2=None, gates=None, 
          ptr(lengths), t, ptr(gi_idx), F_._gru_flags(gates, gi, gi2, w=w_hh), stream_ptr())
 
 
-def _decoder_free_fwd_composite(plan, P, z, xs, tok0_src, tok0_lds, pk, wl, wr, io_of, ior, dims, tens, coins, w_hh_t, w_ih_t16, dev, M, R):
-    """DecoderStepFn.forward's persistent path through ptv_decoder_free_fwd (one C call); True when it ran"""
-    B, He, Ht, Hn, Hd, E = (dims[k] for k in ('B', 'He', 'Ht', 'Hn', 'Hd', 'E'))
-    w_ih_n, w_hh_n = P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0']
-    t = dict(tens)
-    t.update(Z=z, XS=xs, TOK0_SRC=tok0_src, W_ZHID=P['z2dec_hid_linear.weight'], B_ZHID=P['z2dec_hid_linear.bias'],
+# ---------------------------------------------------------------------------------------------
+# The host pointer arrays of ptv_free_note_loop and ptv_free_resummarize, slot by slot in the order of include/ptvae_hip.h (the header is
+# the authority; tests/test_gpu_freerun_kernels.py states the order a second time, by hand).
+# ---------------------------------------------------------------------------------------------
+NOTE_W = ('WG_H', 'WG_T', 'WP', 'WD_H', 'WD_P', 'WDUR', 'B_HH_N', 'B_P', 'B_DH', 'B_HH_D', 'TAB0', 'TAB', 'W_OUT_D', 'B_OUT_D', 'W_EMBT',
+          'B_EMB')
+NOTE_IO = ('GC', 'EMB', 'HN', 'GATES_N', 'PITCH', 'HD', 'GATES_D', 'DUR', 'IDX', 'TOK', 'PRED', 'XHAT', 'PLEN', 'FORCE_PITCH', 'FORCE_DUR',
+           'HN16', 'HD16', 'RESERVED17', 'H0GC', 'XCH', 'CNT', 'BLOCK')       # BLOCK: the sampling block, present only in a sampled decode
+RESUM_W = ('E_IH', 'E_HH', 'E_IH_R', 'E_HH_R', 'B_IH', 'B_HH', 'B_IH_R', 'B_HH_R')
+RESUM_IO = ('PRED', 'PLEN', 'XH0', 'XH1', 'XG0', 'XG1', 'TOK_OUT')
+
+
+def _slot_array(names, slots):
+    unknown = [n for n in slots if n not in names]
+    if unknown:
+        raise TypeError('no slot named %s; the slots are %s' % (', '.join(unknown), ', '.join(names)))
+    return F_._parr([slots.get(n) for n in names])
+
+
+def dur_tabs(P, dev):
+    """(tab0 [1, 3 Hd], tab [2, 3 Hd]): the duration GRU's input side for <sos> and for the two one-hot tokens, in fp32"""
+    w_ih_d, b_ih_d = P['dec_dur_gru.weight_ih_l0'], P['dec_dur_gru.bias_ih_l0']
+    return (gemm(P['dur_sos_token'].view(1, -1), w_ih_d, bias=b_ih_d, prec=0), gemm(_onehot2x5(dev), w_ih_d, bias=b_ih_d, prec=0))
+
+
+def note_loop_weights(P, pk, tab0, tab):
+    """ptv_free_note_loop's w (NOTE_W) from the parameters, the packs of _free_packs and dur_tabs"""
+    return _slot_array(NOTE_W, dict(
+        WG_H=pk['wg_h'], WG_T=pk['wg_t'], WP=pk['wp'], WD_H=pk['wd_h'], WD_P=pk['wd_p'], WDUR=pk['wdur'], B_HH_N=P['dec_notes_gru.bias_hh_l0'],
+        B_P=P['pitch_out_linear.bias'], B_DH=P['dur_hid_linear.bias'], B_HH_D=P['dec_dur_gru.bias_hh_l0'], TAB0=tab0, TAB=tab,
+        W_OUT_D=P['dur_out_linear.weight'], B_OUT_D=P['dur_out_linear.bias'], W_EMBT=pk['w_embT'], B_EMB=P['note_embedding.bias']))
+
+
+def resum_weights(P, pk):
+    """ptv_free_resummarize's w (RESUM_W) from dec_notes_emb_gru's biases and the packs of _free_packs"""
+    return _slot_array(RESUM_W, dict(
+        E_IH=pk['e_ih'], E_HH=pk['e_hh'], E_IH_R=pk['e_ih_r'], E_HH_R=pk['e_hh_r'], B_IH=P['dec_notes_emb_gru.bias_ih_l0'],
+        B_HH=P['dec_notes_emb_gru.bias_hh_l0'], B_IH_R=P['dec_notes_emb_gru.bias_ih_l0_reverse'],
+        B_HH_R=P['dec_notes_emb_gru.bias_hh_l0_reverse']))
+
+
+def note_loop_io(BLOCK=None, **slots):
+    """ptv_free_note_loop's io by slot name (NOTE_IO): 21 pointers, a slot not given is NULL; the sampling block is the 22nd when given"""
+    return _slot_array(NOTE_IO[:21] if BLOCK is None else NOTE_IO, slots if BLOCK is None else dict(slots, BLOCK=BLOCK))
+
+
+def resum_io(**slots):
+    """ptv_free_resummarize's io by slot name (RESUM_IO); a slot not given is NULL"""
+    return _slot_array(RESUM_IO, slots)
+
+
+class FreeBuffers:
+    """What one step-loop forward allocates, by its plan (fills and allocations only, nothing is launched through the library):
+    NS [33,B,Ht] / HN [16,R,Hn] / HD [6,M,Hd] states with their bf16 copies NS16 / HN16 / HD16 (or None), the time tokens TOKS, the gates
+    gates_t / gates_n / gates_d (training), the fed and predicted note tokens TOK / PRED, the outputs pitch, dur, idx and xhat (filled with
+    padding rows behind <sos>), plen (zero), the re-summarisation's XH / XG / XH16 per direction (XH None: no token is re-summarised), the
+    cluster mode's exchange words xch and counters xcnt (zero, or None), sos_emb (inference) and z_in / zg, which the prologue allocates
+    when the forward is not the composite.  dims: the plan's eight, then Zi"""
+
+    def __init__(self, plan, dims, prec, inference, dev):
+        B, R, E, He, Ht, Hn, Hd, NP, Zi = dims
+        M, bf16, train = 15 * R, torch.bfloat16, plan.train
+        self.dims = dims[:8]
+        self.NS = _empty(33, B, Ht, dev=dev)
+        self.TOKS = _empty(33, B, 2 * He, dev=dev)
+        self.z_in, self.zg = (_empty(B, Zi, dev=dev), _empty(B, 3 * Ht, dev=dev)) if plan.comp else (None, None)
+        self.gates_t = _empty(32, 4, B, Ht, dev=dev, dtype=F_._act_dtype(prec, Ht)) if train else None
+        self.HN = _empty(16, R, Hn, dev=dev)
+        self.gates_n = _empty(15, 4, R, Hn, dev=dev, dtype=F_._act_dtype(prec, Hn)) if train else None
+        self.TOK = _empty(15, R, E, dev=dev)
+        self.xhat = torch.full((B, 32, 16, 6), 2, device=dev, dtype=torch.long)
+        self.xhat[:, :, :, 0] = 130
+        self.xhat[:, :, 0, 0] = 128
+        self.plen = torch.zeros(R, device=dev, dtype=torch.int32)
+        # the persistent note loop writes every slot of PRED, and its heads read row-padded logits
+        self.PRED = _empty(16, R, E, dev=dev) if plan.fast else _zeros(16, R, E, dev=dev)
+        self.pitch = _empty(M, F_._pad8(NP), dev=dev)[:, :NP] if plan.fast else _empty(M, NP, dev=dev)
+        self.HD = _empty(6, M, Hd, dev=dev)
+        # (the batched recompute's duration GRU saves no gates: csrc/dur_bwd.hip rebuilds them)
+        self.gates_d = (_empty(5, 4, M, Hd, dev=dev, dtype=F_._act_dtype(prec, Hd))
+                        if train and not (plan.replay and F_.DUR_RECOMPUTE) else None)
+        self.idx = torch.empty(5, M, device=dev, dtype=torch.int32)
+        self.dur = _empty(M, 5, 2, dev=dev)
+        self.sos_emb = _empty(16, 32, 1, E, dev=dev) if inference else None
+        # bf16 state copies: MFMA operands of the batched backward, and of the time GRU / the per-step products in the loop
+        self.HN16 = _empty(16, R, Hn, dev=dev, dtype=bf16) if plan.state16 else None
+        self.HD16 = _empty(6, M, Hd, dev=dev, dtype=bf16) if plan.state16 else None
+        self.NS16 = _empty(33, B, Ht, dev=dev, dtype=bf16) if plan.ns16 else None
+        self._resum_buffers(plan, prec, dev)
+        self._cluster_buffers(plan, dev)
+
+    def _resum_buffers(self, plan, prec, dev):
+        R, He, bf16 = self.dims[1], self.dims[3], torch.bfloat16
+        self.XH = self.XG = None
+        self.XH16 = [None, None]
+        if plan.need_resum and plan.replay:                      # the batched recompute writes every row of every slot but slot 0
+            self.XH = [_empty(17, R, He, dev=dev) for _ in range(2)]
+            for d in range(2):
+                self.XH[d][0].zero_()
+            self.XG = [_empty(16, 4, R, He, dev=dev, dtype=bf16) for _ in range(2)]
+            self.XH16 = [_empty(17, R, He, dev=dev, dtype=bf16) for _ in range(2)]
+        elif plan.need_resum:
+            self.XH = [_zeros(17, R, He, dev=dev) for _ in range(2)]
+            self.XG = ([torch.zeros(16, 4, R, He, device=dev, dtype=F_._act_dtype(prec, He)) for _ in range(2)] if plan.train
+                       else [None, None])
+
+    def _cluster_buffers(self, plan, dev):
+        self.xch = self.xcnt = None
+        if plan.cluster:
+            global LAST_CLUSTER_COUNTERS
+            panels, Hn, bf16 = (self.dims[0] + 15) // 16, self.dims[5], torch.bfloat16
+            self.xch = torch.zeros(panels * 2 * 16 * Hn * 2, device=dev, dtype=bf16)   # 8-byte words {2 units, step tag}: tag 0 = nothing sent yet
+            self.xcnt = torch.zeros(panels + 1, device=dev, dtype=torch.int32)         # arrival counters of t = 0..31 + error word
+            LAST_CLUSTER_COUNTERS = self.xcnt        # (tests: every panel counts 32 * 15 * S arrivals, the error word stays 0)
+            F_._CLUSTER_SYNC.append(self.xcnt)
+            if len(F_._CLUSTER_SYNC) > 64:
+                del F_._CLUSTER_SYNC[:32]
+
+    def saved(self):
+        """the tensors of DecoderStepState, by its keyword names"""
+        return {n: getattr(self, n) for n in ('NS', 'NS16', 'z_in', 'TOKS', 'gates_t', 'HN', 'HN16', 'gates_n', 'pitch', 'HD', 'HD16', 'gates_d',
+                                              'idx', 'TOK', 'PRED', 'xhat', 'XH', 'XG', 'XH16', 'plen')}
+
+    def note_io(self, inp, **more):
+        """the note loop's io over these buffers; the caller adds GC or H0GC, and the BLOCK of a sampled decode"""
+        return note_loop_io(EMB=inp.emb3, HN=self.HN, GATES_N=self.gates_n, PITCH=self.pitch, HD=self.HD, GATES_D=self.gates_d, DUR=self.dur,
+                            IDX=self.idx, TOK=self.TOK, PRED=self.PRED, XHAT=self.xhat, PLEN=self.plen, FORCE_PITCH=inp.force_pitch,
+                            FORCE_DUR=inp.force_dur, HN16=self.HN16, HD16=self.HD16, XCH=self.xch, CNT=self.xcnt, **more)
+
+    def resum_io(self, tok_out=None):
+        """the re-summarisation's io over these buffers"""
+        return resum_io(PRED=self.PRED, PLEN=self.plen, XH0=self.XH[0], XH1=self.XH[1], XG0=self.XG[0], XG1=self.XG[1], TOK_OUT=tok_out)
+
+
+# what a step-loop forward was called with, beside the parameters: emb3 = the ground-truth embedding as [16, R, E] or None, coins as given,
+# masks / time_coins = coin_masks(coins), force_pitch [15, R] / force_dur [5, 15 R] int32 or None, sampling = the block or None
+FreeInputs = collections.namedtuple('FreeInputs', 'z emb3 xs coins masks time_coins force_pitch force_dur sampling inference prec')
+# the packs and tables of a step-loop forward: tok0 / tok0_lds = the first note token of every time step and its row stride (0: one <sos>
+# row), dur_tabs, the MFMA operands of the time GRU and of the per-step products (bf16 shadows on the persistent path), wE =
+# dec_notes_emb_gru's eight, and on the persistent path pk = _free_packs, wl / wr = note_loop_weights / resum_weights
+FreeTables = collections.namedtuple('FreeTables', 'tok0 tok0_lds tab0 tab w_hh_t w_ih_t16 w_tn16 w_ih_n16 wE pk wl wr')
+
+
+def _free_branches(plan, prec, dims, gates_d_dtype):
+    """(notes, heads, dur) of the DecoderStepState a forward by this plan leaves: the batched recompute ran the row kernel; the loop's own
+    heads and duration steps leave what csrc/heads.hip / csrc/dur_bwd.hip take back wherever the bf16 copies exist.  gates_d_dtype: None when
+    no duration gates are saved"""
+    Hn, Hd, NP = dims[5], dims[6], dims[7]
+    s16 = plan.state16 or None
+    dur_fused = F_.dur_bwd_fusable(prec, Hd, None) and gates_d_dtype in (None, torch.bfloat16)
+    return ('rows' if plan.replay else 'step', 'fused' if F_.heads_ok(prec, Hn, NP, Hd, s16, s16) else 'gemm',
+            'fused16' if plan.state16 else 'fused' if dur_fused else 'step')
+
+
+def _free_prologue(P, buf, z, prec):
+    """what does not depend on the loop: the first time state, the z part of the time GRU's input side, the first time token"""
+    w_ih_t = P['dec_time_gru.weight_ih_l0']
+    gemm(z, P['z2dec_hid_linear.weight'], buf.NS[0], bias=P['z2dec_hid_linear.bias'], prec=prec)
+    buf.z_in = gemm(z, P['z2dec_in_linear.weight'], bias=P['z2dec_in_linear.bias'], prec=prec)
+    buf.zg = gemm(buf.z_in, w_ih_t[:, 2 * buf.dims[3]:], bias=P['dec_time_gru.bias_ih_l0'], prec=prec)
+    copy2d(buf.TOKS[0], P['dec_init_input'].view(1, -1), lds=0)
+
+
+def _free_tables(plan, P, buf, inp):
+    """FreeTables of a forward; what it launches -- the <sos> embedding at inference, dur_tabs, the bf16 copy of the first time state
+    when the forward is not the composite, packs and shadows that are out of date -- reads no buffer but NS[0]"""
+    B, R, E, He, Ht, Hn, Hd, NP = buf.dims
+    prec, dev, st = inp.prec, inp.z.device, stream_ptr()
+    if inp.inference:
+        call('ptv_embed_fwd', ptr(_sos_grid(dev)), ptr(P['note_embedding.weight']), ptr(P['note_embedding.bias']), ptr(buf.sos_emb), None, 1,
+             E, st)
+        tok0, tok0_lds = buf.sos_emb.view(-1, E)[0:1], 0
+    else:
+        tok0, tok0_lds = inp.emb3[0], E
+    tab0, tab = dur_tabs(P, dev)
+    if plan.ns16 and not plan.comp:
+        call('ptv_cast_bf16', ptr(buf.NS[0]), ptr(buf.NS16[0]), B * Ht, st)
+    # per time step the loop runs four M = B products whose cost is reading the weights: their bf16 shadows halve it
+    w_ih_t, w_tn, w_ih_n = P['dec_time_gru.weight_ih_l0'], P['dec_time_to_notes_hid.weight'], P['dec_notes_gru.weight_ih_l0']
+    w_hh_t = F_._W(P['dec_time_gru.weight_hh_l0'], prec) if plan.ns16 else P['dec_time_gru.weight_hh_l0']
+    ops = (F_._W(w_ih_t, prec), F_._W(w_tn, prec), F_._W(w_ih_n, prec)) if plan.fast else (w_ih_t, w_tn, w_ih_n)
+    pk = _free_packs(P, Ht) if plan.fast else None
+    return FreeTables(tok0, tok0_lds, tab0, tab, w_hh_t, *ops, [P['dec_notes_emb_gru.' + n] for n in EMB_GRU], pk,
+                      note_loop_weights(P, pk, tab0, tab) if plan.fast else None, resum_weights(P, pk) if plan.fast else None)
+
+
+def _composite_tensors(plan, P, buf, tbl, inp):
+    """the DFF slots of ptv_decoder_free_fwd by name: buffers, inputs, parameters, packs, and the scratch of the call"""
+    B, R, E, He, Ht, Hn, Hd, NP = buf.dims
+    M, dev, pk = 15 * R, inp.z.device, tbl.pk
+    XH, XG = buf.XH or [None, None], buf.XG or [None, None]
+    t = dict(NS=buf.NS, NS16=buf.NS16, Z_IN=buf.z_in, ZG=buf.zg, TOKS=buf.TOKS, GATES_T=buf.gates_t, TOK=buf.TOK, PRED=buf.PRED,
+             PITCH=buf.pitch, HN=buf.HN, HN16=buf.HN16, GATES_N=buf.gates_n, HD=buf.HD, HD16=buf.HD16, GATES_D=buf.gates_d, IDX=buf.idx,
+             PLEN=buf.plen, XH0=XH[0], XH1=XH[1], XH16_0=buf.XH16[0], XH16_1=buf.XH16[1], XG0=XG[0], XG1=XG[1], TAB0=tbl.tab0, TAB=tbl.tab,
+             SAMPLE=inp.sampling,                    # (the composite appends the block to the note loop's io itself)
+             Z=inp.z, XS=inp.xs, TOK0_SRC=tbl.tok0, W_ZHID=P['z2dec_hid_linear.weight'], B_ZHID=P['z2dec_hid_linear.bias'],
              W_ZIN=P['z2dec_in_linear.weight'], B_ZIN=P['z2dec_in_linear.bias'], W_IH_T=P['dec_time_gru.weight_ih_l0'],
-             B_IH_T=P['dec_time_gru.bias_ih_l0'], INIT_INPUT=P['dec_init_input'], B_HH_T=P['dec_time_gru.bias_hh_l0'], W_IH_T_OP=w_ih_t16,
-             W_HH_T_OP=w_hh_t, W_CAT=pk['w_cat'], B_CAT=pk['b_cat'], GI=_empty(B, 3 * Ht, dev=dev), H0GC=_empty(B, 4 * Hn, dev=dev))
+             B_IH_T=P['dec_time_gru.bias_ih_l0'], INIT_INPUT=P['dec_init_input'], B_HH_T=P['dec_time_gru.bias_hh_l0'],
+             W_IH_T_OP=tbl.w_ih_t16, W_HH_T_OP=tbl.w_hh_t, W_CAT=pk['w_cat'], B_CAT=pk['b_cat'], GI=_empty(B, 3 * Ht, dev=dev),
+             H0GC=_empty(B, 4 * Hn, dev=dev))
     if plan.replay:
-        F_.zero_skip_sync()
-        pkn = F_.notes_packs(w_ih_n, w_hh_n, Ht)
+        w_ih_n = P['dec_notes_gru.weight_ih_l0']
+        pkn = F_.notes_packs(w_ih_n, P['dec_notes_gru.weight_hh_l0'], Ht)
         t.update(W_IH_N=w_ih_n, B_IH_N=P['dec_notes_gru.bias_ih_l0'], B_HH_N=P['dec_notes_gru.bias_hh_l0'], W_DH=P['dur_hid_linear.weight'],
                  B_DH=P['dur_hid_linear.bias'], W_HH_D=P['dec_dur_gru.weight_hh_l0'], B_HH_D=P['dec_dur_gru.bias_hh_l0'],
                  W_OUT_D=P['dur_out_linear.weight'], B_OUT_D=P['dur_out_linear.bias'], PK_NOTES_H=pkn['wg_h'], PK_NOTES_T=pkn['wg_t'],
                  GC16=_empty(R, 3 * Hn, dev=dev, dtype=torch.bfloat16), DUR_SCR=_empty(M, 10, dev=dev),
                  IDX_SCR=torch.empty(5, M, device=dev, dtype=torch.int32))
         if plan.need_resum:
-            wE = [P['dec_notes_emb_gru.' + n] for n in EMB_GRU]
             for d_ in range(2):
-                w_ih_e, w_hh_e, b_ih_e, b_hh_e = wE[4 * d_: 4 * d_ + 4]
+                w_ih_e, w_hh_e, b_ih_e, b_hh_e = tbl.wE[4 * d_: 4 * d_ + 4]
                 pke = F_.notes_packs(w_ih_e, w_hh_e, 0)
                 t.update({'PK_E_H%d' % d_: pke['wg_h'], 'PK_E_T%d' % d_: pke['wg_t'], 'B_HH_E%d' % d_: b_hh_e, 'B_IH_E%d' % d_: b_ih_e})
+    return t
+
+
+def _free_fwd_composite(plan, P, buf, tbl, inp):
+    """the persistent path through ptv_decoder_free_fwd (one C call: prologue, loop and batched recompute); True when it ran"""
+    B, R, E, He, Ht, Hn, Hd, NP = buf.dims
+    if plan.replay:
+        F_.zero_skip_sync()
+    t = _composite_tensors(plan, P, buf, tbl, inp)
     cluster = int(bool(plan.cluster) and not plan.capturing)
-    dvals = _DFF.dims({'B': B, 'ZS': dims['Zs'], 'ZI': dims['Zi'], 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'E': E, 'NP': dims['NP'],
-                       'LDP': dims['ldp'], 'TRAIN': int(plan.train), 'REPLAY': int(plan.replay), 'INFERENCE': dims['inference'],
+    dvals = _DFF.dims({'B': B, 'ZS': inp.z.shape[1], 'ZI': buf.z_in.shape[1], 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'E': E, 'NP': NP,
+                       'LDP': buf.pitch.stride(0), 'TRAIN': int(plan.train), 'REPLAY': int(plan.replay),
+                       'INFERENCE': int(bool(inp.inference)),
                        'LOOP_FLAGS': note_loop_word(plan.train, plan.replay, NOTE_LOOP_SPLIT, plan.cluster), 'CLUSTER': cluster,
-                       'RESUM_TRAIN': int(plan.train and not plan.replay), 'TOK0_LDS': tok0_lds,
-                       'W_IH_T_BF16': w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': w_hh_t.dtype == torch.bfloat16,
+                       'RESUM_TRAIN': int(plan.train and not plan.replay), 'TOK0_LDS': tbl.tok0_lds,
+                       'W_IH_T_BF16': tbl.w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': tbl.w_hh_t.dtype == torch.bfloat16,
                        'SAMPLE_TRUNC': plan.kind.trunc, 'SAMPLE_CONS': plan.kind.cons})
-    masks, tc = coins
+    masks, tc = inp.masks, inp.time_coins
     # the cluster-mode note loops take the persistent-launch turn (functional._PersistTurn): the library records again after the last one
     turn = F_._CompositeTurn(F_.cur_stream()) if cluster else None
     slots = _DFF.pointers(t, handles=turn.handles if turn else None)
     F_._chain_prio()
-    rc = lib().ptv_decoder_free_fwd(slots, dvals, wl, io_of(t['H0GC']), wr, ior, masks, tc, stream_ptr())
+    rc = lib().ptv_decoder_free_fwd(slots, dvals, tbl.wl, buf.note_io(inp, H0GC=t['H0GC']), tbl.wr,
+                                    buf.resum_io() if plan.need_resum else None, masks, tc, stream_ptr())
     if rc == -3:
         return False
     F_.check(rc, 'ptv_decoder_free_fwd')
@@ -584,6 +785,143 @@ def _decoder_free_fwd_composite(plan, P, z, xs, tok0_src, tok0_lds, pk, wl, wr, 
     _DFF.count()
     _DFF_KEEP[:] = (t, masks, tc)                           # (the scratch tensors stay referenced until the next call)
     return True
+
+
+def _first_tokens(buf, tbl):
+    """the first note token of every time step is the <sos> embedding (ptvae.py:388-392): one copy for all 32 steps"""
+    copy2d(buf.TOK[0], tbl.tok0, lds=tbl.tok0_lds)
+    copy2d(buf.PRED[0], buf.TOK[0])
+
+
+def _time_step(plan, P, buf, tbl, inp, t):
+    """the time GRU's cell t -> the new time state as the note level's operand (its bf16 copy where one exists)"""
+    B, He, Ht = buf.dims[0], buf.dims[3], buf.dims[4]
+    NS, NS16 = buf.NS, buf.NS16
+    gi = gemm(buf.TOKS[t], tbl.w_ih_t16[:, :2 * He], prec=inp.prec)
+    gru_step(inp.prec, NS[t], gi, 3 * Ht, tbl.w_hh_t, P['dec_time_gru.bias_hh_l0'], NS[t + 1], gi2=buf.zg,
+             gates=buf.gates_t[t] if plan.train else None, plane=B * Ht, hout16=NS16[t + 1] if NS16 is not None else None,
+             hprev16=NS16[t] if NS16 is not None else None)
+    return NS16[t + 1] if NS16 is not None else NS[t + 1]
+
+
+def _next_time_token(plan, P, buf, tbl, inp, t):
+    """TOKS[t + 1]: the ground-truth summary (time coin t), or the final states of dec_notes_emb_gru over the predicted notes of step t
+    (ptvae.py:480-486) -- one persistent launch, or cell by cell"""
+    B, R, E, He = buf.dims[:4]
+    prec, rows = inp.prec, slice(t * B, (t + 1) * B)
+    if inp.time_coins[t]:
+        copy2d(buf.TOKS[t + 1], inp.xs[rows])
+    elif plan.fast:
+        call('ptv_free_resummarize', tbl.wr, buf.resum_io(buf.TOKS[t + 1]), B, t, int(plan.train and not plan.replay), stream_ptr())
+    else:
+        wE, XH, XG = tbl.wE, buf.XH, buf.XG
+        PT = _empty(16, B * E, dev=inp.z.device)
+        copy2d(PT, buf.PRED.view(16, R * E)[:, t * B * E:(t + 1) * B * E])
+        for d in range(2):
+            gi_e = gemm(PT.view(16 * B, E), wE[4 * d], bias=wE[4 * d + 2], prec=prec).view(16, B, 3 * He)
+            for s_ in range(16):
+                tt = 15 - s_ if d else s_
+                gru_step(prec, XH[d][s_][rows], gi_e[tt], 3 * He, wE[4 * d + 1], wE[4 * d + 3], XH[d][s_ + 1][rows],
+                         gates=XG[d][s_][:, rows] if plan.train else None, plane=R * He, lengths=buf.plen[rows], t=tt)
+            copy2d(buf.TOKS[t + 1][:, d * He:(d + 1) * He], XH[d][16][rows])
+
+
+def _free_fwd_persistent(plan, P, buf, tbl, inp):
+    """the persistent kernels of csrc/freerun.hip sequenced from here: per time step the time GRU's cell, the initial notes-GRU state and
+    the hoisted input part in ONE product against the stacked weights ([512 | 1536] rows: 256 blocks, no split-K, no zero fill), all 15
+    note steps in ONE launch, and the next time token"""
+    B, pk, st = buf.dims[0], tbl.pk, stream_ptr()
+    word = note_loop_word(plan.train, plan.replay, NOTE_LOOP_SPLIT, plan.cluster, plan.kind)
+    _first_tokens(buf, tbl)
+    for t in range(32):
+        ns = _time_step(plan, P, buf, tbl, inp, t)
+        H0GC = gemm(ns, pk['w_cat'], bias=pk['b_cat'], prec=inp.prec)
+        io = buf.note_io(inp, H0GC=H0GC, BLOCK=inp.sampling)
+        # (cluster mode: the members of a panel spin on each other -- like every persistent launch it takes its turn, so that
+        # it is never half-resident next to another spinning grid, e.g. the chord decoder's on its sibling stream)
+        with (F_._PersistTurn() if plan.cluster and not plan.capturing else contextlib.nullcontext()):
+            call('ptv_free_note_loop', tbl.wl, io, buf.pitch.stride(0), B, t, inp.masks[t], word, st)
+        if t < 31:
+            _next_time_token(plan, P, buf, tbl, inp, t)
+
+
+def _free_fwd_steps(plan, P, buf, tbl, inp):
+    """the generic loop, one launch per cell and head: 32 time steps of 15 note steps of 5 duration steps"""
+    B, Ht = buf.dims[0], buf.dims[4]
+    _first_tokens(buf, tbl)
+    for t in range(32):
+        rows = slice(t * B, (t + 1) * B)
+        ns = _time_step(plan, P, buf, tbl, inp, t)
+        gemm(ns, tbl.w_tn16, buf.HN[0][rows], bias=P['dec_time_to_notes_hid.bias'], prec=inp.prec)
+        GCt = gemm(ns, tbl.w_ih_n16[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=inp.prec)
+        for n in range(15):
+            _note_step(plan, P, buf, tbl, inp, t, n, GCt)
+        if t < 31:
+            _next_time_token(plan, P, buf, tbl, inp, t)
+
+
+def _note_step(plan, P, buf, tbl, inp, t, n, GCt):
+    """note step n of time step t of the generic loop: the notes GRU's cell, the pitch head, the duration GRU (fused, or five cells and
+    heads), the predicted token, and the token fed next"""
+    B, R, E, He, Ht, Hn, Hd, NP = buf.dims
+    M, prec, kind, st, train = 15 * R, inp.prec, plan.kind, stream_ptr(), plan.train
+    HN, HD, TOK, PRED, pitch, idx, gates_d, force_dur = buf.HN, buf.HD, buf.TOK, buf.PRED, buf.pitch, buf.idx, buf.gates_d, inp.force_dur
+    w_dh, w_hh_d, b_hh_d = P['dur_hid_linear.weight'], P['dec_dur_gru.weight_hh_l0'], P['dec_dur_gru.bias_hh_l0']
+    w_out_d, b_out_d, dur2 = P['dur_out_linear.weight'], P['dur_out_linear.bias'], buf.dur.view(M, 10)
+    smp = () if inp.sampling is None else (ptr(inp.sampling),)      # sampled forms: the block, then (t, n) of the rows
+    rows, pr = slice(t * B, (t + 1) * B), slice(n * R + t * B, n * R + (t + 1) * B)
+    gi_tok = gemm(TOK[n][rows], P['dec_notes_gru.weight_ih_l0'][:, Ht:], prec=prec)
+    gru_step(prec, HN[n][rows], gi_tok, 3 * Hn, P['dec_notes_gru.weight_hh_l0'], P['dec_notes_gru.bias_hh_l0'], HN[n + 1][rows], gi2=GCt,
+             gates=buf.gates_n[n][:, rows] if train else None, plane=R * Hn)
+    h = HN[n + 1][rows]
+    gemm(h, P['pitch_out_linear.weight'], pitch[pr], bias=P['pitch_out_linear.bias'], prec=prec)
+    gemm(h, w_dh[:, :Hn], HD[0][pr], bias=P['dur_hid_linear.bias'], prec=prec)
+    gemm(pitch[pr], w_dh[:, Hn:], HD[0][pr], acc=True, prec=prec)
+    if prec == 1 and Hd == 64 and F_.FUSED_DUR:
+        call(kind.dur_gru, Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tbl.tab0), ptr(tbl.tab), ptr(w_out_d), ptr(b_out_d),
+             ptr(HD[1][pr]), M * Hd, None, ptr(gates_d[0][0][pr]) if train else None, M * Hd, 4 * M * Hd, F_._bf(gates_d), ptr(dur2[pr]), 10,
+             ptr(idx[0][pr]), M, ptr(force_dur[0][pr]) if force_dur is not None else None, M, *(smp and smp + (t, n)), st)
+    else:
+        for d in range(5):
+            g_, g_ld, g_idx = (tbl.tab0, 0, None) if d == 0 else (tbl.tab, 3 * Hd, idx[d - 1][pr])
+            gru_step(prec, HD[d][pr], g_, g_ld, w_hh_d, b_hh_d, HD[d + 1][pr], gates=gates_d[d][:, pr] if train else None, plane=M * Hd,
+                     gi_idx=g_idx)
+            call(kind.dur_token, ptr(HD[d + 1][pr]), Hd, ptr(w_out_d), ptr(b_out_d), ptr(dur2[pr][:, 2 * d:]), 10, ptr(idx[d][pr]),
+                 ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp and smp + (t, n, d)), st)
+    call(kind.note_token, ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(P['note_embedding.weight']), ptr(P['note_embedding.bias']), E,
+         ptr(PRED[n + 1][rows]), E, ptr(buf.xhat[0, t, n + 1]), 32 * 16 * 6, ptr(buf.plen[rows]), n + 1, int(n == 14),
+         ptr(inp.force_pitch[n][rows]) if inp.force_pitch is not None else None, B, *(smp and smp + (t,)), st)
+    if n < 14:
+        use_gt = (not inp.inference) and inp.coins[0][t][n]
+        copy2d(TOK[n + 1][rows], inp.emb3[n + 1][rows] if use_gt else PRED[n + 1][rows])
+
+
+def _free_recompute(plan, P, buf, tbl, prec):
+    """what the backward reads, recomputed batched over all rows by the teacher-forced kernels (the replayed loop stored decisions and
+    tokens only): notes-GRU states and gates, the duration GRU with the stored decisions forced, the re-summarisation bi-GRU"""
+    B, R, E, He, Ht, Hn, Hd, NP = buf.dims
+    M, st, dev, bf16 = 15 * R, stream_ptr(), buf.NS.device, torch.bfloat16
+    HD, HD16 = buf.HD, buf.HD16
+    w_ih_n, w_hh_n, w_dh = P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0'], P['dur_hid_linear.weight']
+    F_.zero_skip_sync()
+    GC16 = gemm(buf.NS16[1:].view(R, Ht), w_ih_n[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec, out_dtype=bf16,
+                out_blocked=16)      # (column-blocked by 16: the layout the row kernel reads)
+    pkn = F_.notes_packs(w_ih_n, w_hh_n, Ht)
+    call('ptv_notes_gru_persist_fwd', ptr(pkn['wg_h']), ptr(pkn['wg_t']), ptr(P['dec_notes_gru.bias_hh_l0']), ptr(GC16), ptr(buf.TOK),
+         ptr(buf.HN), ptr(buf.HN16), ptr(buf.gates_n), R, 15, st)
+    gemm(buf.HN16[1:].view(M, Hn), w_dh[:, :Hn], HD[0], bias=P['dur_hid_linear.bias'], prec=prec)
+    gemm(buf.pitch, w_dh[:, Hn:], HD[0], acc=True, prec=prec)
+    dur_scr, idx_scr = _empty(M, 10, dev=dev), torch.empty(5, M, device=dev, dtype=torch.int32)
+    call('ptv_dur_gru_fwd', Hd, M, ptr(HD[0]), Hd, ptr(P['dec_dur_gru.weight_hh_l0']), ptr(P['dec_dur_gru.bias_hh_l0']), ptr(tbl.tab0),
+         ptr(tbl.tab), ptr(P['dur_out_linear.weight']), ptr(P['dur_out_linear.bias']), None, M * Hd, ptr(HD16[1]), ptr(buf.gates_d), M * Hd,
+         4 * M * Hd, 1, ptr(dur_scr), 10, ptr(idx_scr), M, ptr(buf.idx), M, st)
+    call('ptv_cast_bf16', ptr(HD[0]), ptr(HD16[0]), M * Hd, st)
+    if plan.need_resum:
+        for d in range(2):
+            w_ih_e, w_hh_e, b_ih_e, b_hh_e = tbl.wE[4 * d: 4 * d + 4]
+            pke = F_.notes_packs(w_ih_e, w_hh_e, 0)
+            call('ptv_row_gru_persist_fwd', He, ptr(pke['wg_h']), ptr(pke['wg_t']), ptr(b_hh_e), ptr(b_ih_e), None, ptr(buf.PRED), R * E,
+                 ptr(buf.plen), ptr(buf.XH[d]), ptr(buf.XH16[d]), ptr(buf.XG[d]), None, 0, R, 16, d, st)
 
 
 def _decoder_free_bwd_call(items, dTOK, dTOKS, demb, dPRED, dxs, dxsp, mask_tok, mask_time, dx_pred, xhat, mh, gw, gb, B, E, He):
@@ -632,228 +970,38 @@ class DecoderStepFn(torch.autograd.Function):
                 raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
             _check_block(sampling, dev, z.shape[0])
         z = z.contiguous()
-        B = z.shape[0]
-        R = 32 * B
+        B, R = z.shape[0], 32 * z.shape[0]
         E, NP, Zi = (P[n + '.weight'].shape[0] for n in ('note_embedding', 'pitch_out_linear', 'z2dec_in_linear'))
         He, Ht, Hn, Hd = (P['dec_%s_gru.weight_hh_l0' % n].shape[1] for n in ('notes_emb', 'time', 'notes', 'dur'))
-        M = 15 * R
-        force_pitch = force.get('pitch') if force else None          # [15, R] int32
-        force_dur = force.get('dur') if force else None              # [5, 15R] int32
-        plan = _free_plan(prec, (B, R, E, He, Ht, Hn, Hd, NP), z.dtype, coins, inference, any(ctx.needs_input_grad),
+        dims = (B, R, E, He, Ht, Hn, Hd, NP)
+        force_pitch, force_dur = (force.get('pitch'), force.get('dur')) if force else (None, None)       # [15, R], [5, 15 R] int32
+        plan = _free_plan(prec, dims, z.dtype, coins, inference, any(ctx.needs_input_grad),
                           force_pitch is not None or force_dur is not None, block_kind(sampling), _num_cu(),
                           torch.cuda.is_current_stream_capturing())
-        train, fast, comp, replay, need_resum, cluster, capturing, kind = plan[:8]
-        masks, time_coins = coin_masks(coins, inference)
-        w_emb, b_emb = P['note_embedding.weight'], P['note_embedding.bias']
-        st = stream_ptr()
-        bf16 = torch.bfloat16
+        inp = FreeInputs(z, emb.view(16, R, E) if emb is not None else None, xs, coins, *coin_masks(coins, inference), force_pitch, force_dur,
+                         sampling, inference, prec)
 
-        # ---- allocate by the plan (the composite launches nothing from here before its call: it runs the prologue itself)
-        NS = _empty(33, B, Ht, dev=dev)
-        w_ih_t = P['dec_time_gru.weight_ih_l0']
-        TOKS = _empty(33, B, 2 * He, dev=dev)
-        if comp:
-            z_in, zg = _empty(B, Zi, dev=dev), _empty(B, 3 * Ht, dev=dev)
-        else:
-            gemm(z, P['z2dec_hid_linear.weight'], NS[0], bias=P['z2dec_hid_linear.bias'], prec=prec)
-            z_in = gemm(z, P['z2dec_in_linear.weight'], bias=P['z2dec_in_linear.bias'], prec=prec)
-            zg = gemm(z_in, w_ih_t[:, 2 * He:], bias=P['dec_time_gru.bias_ih_l0'], prec=prec)
-            copy2d(TOKS[0], P['dec_init_input'].view(1, -1), lds=0)
-        gates_t = _empty(32, 4, B, Ht, dev=dev, dtype=F_._act_dtype(prec, Ht)) if train else None
-        HN = _empty(16, R, Hn, dev=dev)
-        gates_n = _empty(15, 4, R, Hn, dev=dev, dtype=F_._act_dtype(prec, Hn)) if train else None
-        TOK = _empty(15, R, E, dev=dev)
-        xhat = torch.full((B, 32, 16, 6), 2, device=dev, dtype=torch.long)
-        xhat[:, :, :, 0] = 130
-        xhat[:, :, 0, 0] = 128
-        plen = torch.zeros(R, device=dev, dtype=torch.int32)
-        PRED = _empty(16, R, E, dev=dev) if fast else _zeros(16, R, E, dev=dev)      # the persistent note loop writes every slot
-        pitch = _empty(M, F_._pad8(NP), dev=dev)[:, :NP] if fast else _empty(M, NP, dev=dev)
-        HD = _empty(6, M, Hd, dev=dev)
-        # (the batched recompute's duration GRU saves no gates: csrc/dur_bwd.hip rebuilds them)
-        gates_d = _empty(5, 4, M, Hd, dev=dev, dtype=F_._act_dtype(prec, Hd)) if train and not (replay and F_.DUR_RECOMPUTE) else None
-        idx = torch.empty(5, M, device=dev, dtype=torch.int32)
-        dur = _empty(M, 5, 2, dev=dev)
-        dur2 = dur.view(M, 10)
-        if inference:
-            sos_emb = _empty(16, 32, 1, E, dev=dev)
-            call('ptv_embed_fwd', ptr(_sos_grid(dev)), ptr(w_emb), ptr(b_emb), ptr(sos_emb), None, 1, E, st)
-            sos_row = sos_emb.view(-1, E)[0:1]
-        w_ih_n, w_hh_n, b_hh_n = P['dec_notes_gru.weight_ih_l0'], P['dec_notes_gru.weight_hh_l0'], P['dec_notes_gru.bias_hh_l0']
-        w_dh = P['dur_hid_linear.weight']
-        w_ih_d, b_ih_d = P['dec_dur_gru.weight_ih_l0'], P['dec_dur_gru.bias_ih_l0']
-        w_hh_d, b_hh_d = P['dec_dur_gru.weight_hh_l0'], P['dec_dur_gru.bias_hh_l0']
-        tab0 = gemm(P['dur_sos_token'].view(1, -1), w_ih_d, bias=b_ih_d, prec=0)
-        tab = gemm(_onehot2x5(dev), w_ih_d, bias=b_ih_d, prec=0)
-        emb3 = emb.view(16, R, E) if emb is not None else None
-        wE = [P['dec_notes_emb_gru.' + n] for n in EMB_GRU]
-        # bf16 state copies: MFMA operands of the batched backward, and of the time GRU / the per-step products in the loop
-        HN16 = _empty(16, R, Hn, dev=dev, dtype=bf16) if plan.state16 else None
-        HD16 = _empty(6, M, Hd, dev=dev, dtype=bf16) if plan.state16 else None
-        NS16 = _empty(33, B, Ht, dev=dev, dtype=bf16) if plan.ns16 else None
-        if plan.ns16 and not comp:
-            call('ptv_cast_bf16', ptr(NS[0]), ptr(NS16[0]), B * Ht, st)
-        # per time step the loop runs four M = B products whose cost is reading the weights: their bf16 shadows halve it
-        w_hh_t = F_._W(P['dec_time_gru.weight_hh_l0'], prec) if plan.ns16 else P['dec_time_gru.weight_hh_l0']
-        w_ih_t16, w_tn16, w_ih_n16 = (F_._W(w_ih_t, prec), F_._W(P['dec_time_to_notes_hid.weight'], prec), F_._W(w_ih_n, prec)) if fast \
-            else (w_ih_t, P['dec_time_to_notes_hid.weight'], w_ih_n)
-        XH = XG = None
-        XH16 = [None, None]
-        if need_resum and replay:                                # the batched recompute writes every row of every slot but slot 0
-            XH = [_empty(17, R, He, dev=dev) for _ in range(2)]
-            for d in range(2):
-                XH[d][0].zero_()
-            XG = [_empty(16, 4, R, He, dev=dev, dtype=bf16) for _ in range(2)]
-            XH16 = [_empty(17, R, He, dev=dev, dtype=bf16) for _ in range(2)]
-        elif need_resum:
-            XH = [_zeros(17, R, He, dev=dev) for _ in range(2)]
-            XG = [torch.zeros(16, 4, R, He, device=dev, dtype=F_._act_dtype(prec, He)) for _ in range(2)] if train else [None, None]
-        xch = xcnt = None
-        if cluster:
-            global LAST_CLUSTER_COUNTERS
-            xch = torch.zeros((B + 15) // 16 * 2 * 16 * Hn * 2, device=dev, dtype=bf16)   # 8-byte words {2 units, step tag}: tag 0 = nothing sent yet
-            xcnt = torch.zeros((B + 15) // 16 + 1, device=dev, dtype=torch.int32)    # arrival counters of t = 0..31 + error word
-            LAST_CLUSTER_COUNTERS = xcnt             # (tests: every panel counts 32 * 15 * S arrivals, the error word stays 0)
-            F_._CLUSTER_SYNC.append(xcnt)
-            if len(F_._CLUSTER_SYNC) > 64:
-                del F_._CLUSTER_SYNC[:32]
-        if fast:
-            pk = _free_packs(P, Ht)
-            wl = F_._parr([pk['wg_h'], pk['wg_t'], pk['wp'], pk['wd_h'], pk['wd_p'], pk['wdur'], b_hh_n, P['pitch_out_linear.bias'],
-                           P['dur_hid_linear.bias'], b_hh_d, tab0, tab, P['dur_out_linear.weight'], P['dur_out_linear.bias'],
-                           pk['w_embT'], b_emb])
-            wr = F_._parr([pk['e_ih'], pk['e_hh'], pk['e_ih_r'], pk['e_hh_r'], wE[2], wE[3], wE[6], wE[7]])
-
-        # ---- the composite (one C call), or the same launches sequenced from here
-        if comp:
-            done = _decoder_free_fwd_composite(
-                plan, P, z, xs, sos_row if inference else emb3[0], 0 if inference else E, pk, wl, wr, io_of=lambda h0gc: F_._parr(
-                    [None, emb3, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16, None, h0gc,
-                     xch, xcnt]),
-                ior=F_._parr([PRED, plen, XH[0], XH[1], XG[0], XG[1], None]) if need_resum else None,
-                dims=dict(B=B, Zs=z.shape[1], Zi=Zi, He=He, Ht=Ht, Hn=Hn, Hd=Hd, E=E, NP=NP, ldp=pitch.stride(0), inference=int(bool(inference))),
-                tens=dict(NS=NS, NS16=NS16, Z_IN=z_in, ZG=zg, TOKS=TOKS, GATES_T=gates_t, TOK=TOK, PRED=PRED, PITCH=pitch, HN=HN, HN16=HN16,
-                          GATES_N=gates_n, HD=HD, HD16=HD16, GATES_D=gates_d, IDX=idx, PLEN=plen, XH0=XH[0] if XH else None,
-                          XH1=XH[1] if XH else None, XH16_0=XH16[0], XH16_1=XH16[1], XG0=XG[0] if XG else None, XG1=XG[1] if XG else None,
-                          TAB0=tab0, TAB=tab, SAMPLE=sampling),     # (the composite appends the block to the note loop's io itself)
-                coins=(masks, time_coins), w_hh_t=w_hh_t, w_ih_t16=w_ih_t16, dev=dev, M=M, R=R)
+        # ---- allocate by the plan, then launch (the composite runs the prologue itself)
+        buf = FreeBuffers(plan, dims + (Zi,), prec, inference, dev)
+        if not plan.comp:
+            _free_prologue(P, buf, z, prec)
+        tbl = _free_tables(plan, P, buf, inp)
+        if plan.comp:
+            done = _free_fwd_composite(plan, P, buf, tbl, inp)
             assert done, 'ptv_decoder_free_fwd declined a configuration free_persist_ok() accepted'
+        elif plan.fast:
+            _free_fwd_persistent(plan, P, buf, tbl, inp)
         else:
-            # the first note token of every time step is the <sos> embedding (ptvae.py:388-392): one copy for all 32 steps
-            if inference:
-                copy2d(TOK[0], sos_row, lds=0)
-            else:
-                copy2d(TOK[0], emb3[0])
-            copy2d(PRED[0], TOK[0])
-        smp = () if sampling is None else (ptr(sampling),)          # sampled forms of the non-persistent loop: the block, then (t, n) of the rows
-        for t in range(32 if comp else 0, 32):
-            rows = slice(t * B, (t + 1) * B)
-            gi = gemm(TOKS[t], w_ih_t16[:, :2 * He], prec=prec)
-            gru_step(prec, NS[t], gi, 3 * Ht, w_hh_t, P['dec_time_gru.bias_hh_l0'], NS[t + 1], gi2=zg,
-                     gates=gates_t[t] if train else None, plane=B * Ht, hout16=NS16[t + 1] if NS16 is not None else None,
-                     hprev16=NS16[t] if NS16 is not None else None)
-            ns = NS16[t + 1] if NS16 is not None else NS[t + 1]
-            if fast:
-                # initial notes-GRU state and the hoisted input part in ONE product against the stacked weights ([512 | 1536] rows):
-                # 256 blocks, no split-K, no zero fill; then all 15 note steps of this time step in ONE launch (csrc/freerun.hip)
-                H0GC = gemm(ns, pk['w_cat'], bias=pk['b_cat'], prec=prec)
-                io = F_._parr([None, emb3, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16,
-                               None, H0GC, xch, xcnt] + ([sampling] if sampling is not None else []))
-                # (cluster mode: the members of a panel spin on each other -- like every persistent launch it takes its turn, so that
-                # it is never half-resident next to another spinning grid, e.g. the chord decoder's on its sibling stream)
-                with (F_._PersistTurn() if cluster and not capturing else contextlib.nullcontext()):
-                    call('ptv_free_note_loop', wl, io, pitch.stride(0), B, t, masks[t],
-                         note_loop_word(train, replay, NOTE_LOOP_SPLIT, cluster, kind), st)
-                if t == 31:
-                    break
-                # ... and the next time-step token
-                if time_coins[t]:
-                    copy2d(TOKS[t + 1], xs[rows])
-                else:
-                    io = F_._parr([PRED, plen, XH[0], XH[1], XG[0], XG[1], TOKS[t + 1]])
-                    call('ptv_free_resummarize', wr, io, B, t, int(train and not replay), st)
-                continue
-            gemm(ns, w_tn16, HN[0][rows], bias=P['dec_time_to_notes_hid.bias'], prec=prec)
-            GCt = gemm(ns, w_ih_n16[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec)
-            for n in range(15):
-                gi_tok = gemm(TOK[n][rows], w_ih_n[:, Ht:], prec=prec)
-                gru_step(prec, HN[n][rows], gi_tok, 3 * Hn, w_hh_n, b_hh_n, HN[n + 1][rows], gi2=GCt,
-                         gates=gates_n[n][:, rows] if train else None, plane=R * Hn)
-                h = HN[n + 1][rows]
-                pr = slice(n * R + t * B, n * R + (t + 1) * B)
-                gemm(h, P['pitch_out_linear.weight'], pitch[pr], bias=P['pitch_out_linear.bias'], prec=prec)
-                gemm(h, w_dh[:, :Hn], HD[0][pr], bias=P['dur_hid_linear.bias'], prec=prec)
-                gemm(pitch[pr], w_dh[:, Hn:], HD[0][pr], acc=True, prec=prec)
-                if prec == 1 and Hd == 64 and F_.FUSED_DUR:
-                    call(kind.dur_gru, Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tab0), ptr(tab),
-                         ptr(P['dur_out_linear.weight']), ptr(P['dur_out_linear.bias']), ptr(HD[1][pr]), M * Hd, None,
-                         ptr(gates_d[0][0][pr]) if train else None, M * Hd, 4 * M * Hd, F_._bf(gates_d), ptr(dur2[pr]), 10,
-                         ptr(idx[0][pr]), M, ptr(force_dur[0][pr]) if force_dur is not None else None, M, *(smp and smp + (t, n)), st)
-                else:
-                    for d in range(5):
-                        g_, g_ld, g_idx = (tab0, 0, None) if d == 0 else (tab, 3 * Hd, idx[d - 1][pr])
-                        gru_step(prec, HD[d][pr], g_, g_ld, w_hh_d, b_hh_d, HD[d + 1][pr],
-                                 gates=gates_d[d][:, pr] if train else None, plane=M * Hd, gi_idx=g_idx)
-                        call(kind.dur_token, ptr(HD[d + 1][pr]), Hd, ptr(P['dur_out_linear.weight']),
-                             ptr(P['dur_out_linear.bias']), ptr(dur2[pr][:, 2 * d:]), 10, ptr(idx[d][pr]),
-                             ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp and smp + (t, n, d)), st)
-                call(kind.note_token, ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(w_emb), ptr(b_emb), E,
-                     ptr(PRED[n + 1][rows]), E, ptr(xhat[0, t, n + 1]), 32 * 16 * 6, ptr(plen[rows]), n + 1, int(n == 14),
-                     ptr(force_pitch[n][rows]) if force_pitch is not None else None, B, *(smp and smp + (t,)), st)
-                if n < 14:
-                    use_gt = (not inference) and coins[0][t][n]
-                    copy2d(TOK[n + 1][rows], emb3[n + 1][rows] if use_gt else PRED[n + 1][rows])
-            if t == 31:
-                break
-            if time_coins[t]:
-                copy2d(TOKS[t + 1], xs[rows])
-            else:
-                # token = final states of dec_notes_emb_gru over the predicted notes (ptvae.py:480-486)
-                PT = _empty(16, B * E, dev=dev)
-                copy2d(PT, PRED.view(16, R * E)[:, t * B * E:(t + 1) * B * E])
-                for d in range(2):
-                    gi_e = gemm(PT.view(16 * B, E), wE[4 * d], bias=wE[4 * d + 2], prec=prec).view(16, B, 3 * He)
-                    for s_ in range(16):
-                        tt = 15 - s_ if d else s_
-                        gru_step(prec, XH[d][s_][rows], gi_e[tt], 3 * He, wE[4 * d + 1], wE[4 * d + 3], XH[d][s_ + 1][rows],
-                                 gates=XG[d][s_][:, rows] if train else None, plane=R * He, lengths=plen[rows], t=tt)
-                    copy2d(TOKS[t + 1][:, d * He:(d + 1) * He], XH[d][16][rows])
-
-        if replay and not comp:
-            F_.zero_skip_sync()
-            # ---- recompute what the backward reads, batched over all rows (the step loop above stored decisions and tokens only)
-            GC16 = gemm(NS16[1:].view(R, Ht), w_ih_n[:, :Ht], bias=P['dec_notes_gru.bias_ih_l0'], prec=prec, out_dtype=bf16,
-                        out_blocked=16)      # (column-blocked by 16: the layout the row kernel reads)
-            pkn = F_.notes_packs(w_ih_n, w_hh_n, Ht)
-            call('ptv_notes_gru_persist_fwd', ptr(pkn['wg_h']), ptr(pkn['wg_t']), ptr(b_hh_n), ptr(GC16), ptr(TOK), ptr(HN), ptr(HN16),
-                 ptr(gates_n), R, 15, st)
-            NSUM_op = HN16[1:].view(M, Hn)
-            gemm(NSUM_op, w_dh[:, :Hn], HD[0], bias=P['dur_hid_linear.bias'], prec=prec)
-            gemm(pitch, w_dh[:, Hn:], HD[0], acc=True, prec=prec)
-            dur_scr, idx_scr = _empty(M, 10, dev=dev), torch.empty(5, M, device=dev, dtype=torch.int32)
-            call('ptv_dur_gru_fwd', Hd, M, ptr(HD[0]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tab0), ptr(tab), ptr(P['dur_out_linear.weight']),
-                 ptr(P['dur_out_linear.bias']), None, M * Hd, ptr(HD16[1]), ptr(gates_d), M * Hd, 4 * M * Hd, 1, ptr(dur_scr), 10,
-                 ptr(idx_scr), M, ptr(idx), M, st)
-            call('ptv_cast_bf16', ptr(HD[0]), ptr(HD16[0]), M * Hd, st)
-            if need_resum:
-                for d in range(2):
-                    w_ih_e, w_hh_e, b_ih_e, b_hh_e = wE[4 * d: 4 * d + 4]
-                    pke = F_.notes_packs(w_ih_e, w_hh_e, 0)
-                    call('ptv_row_gru_persist_fwd', He, ptr(pke['wg_h']), ptr(pke['wg_t']), ptr(b_hh_e), ptr(b_ih_e), None, ptr(PRED), R * E,
-                         ptr(plen), ptr(XH[d]), ptr(XH16[d]), ptr(XG[d]), None, 0, R, 16, d, st)
-        if train:
+            _free_fwd_steps(plan, P, buf, tbl, inp)
+        if plan.replay and not plan.comp:
+            _free_recompute(plan, P, buf, tbl, prec)
+        if plan.train:
             ctx.save_for_backward(z, emb, *params)
-            # (the names say which backward halves read the state: the batched recompute ran the row kernel; the loop's own heads and
-            # duration steps leave what csrc/heads.hip / csrc/dur_bwd.hip take back wherever the bf16 copies exist)
             ctx.saved_state = DecoderStepState(
-                (B, R, E, He, Ht, Hn, Hd, NP), prec, 'rows' if replay else 'step',
-                'fused' if F_.heads_ok(prec, Hn, NP, Hd, plan.state16 or None, plan.state16 or None) else 'gemm',
-                'fused16' if plan.state16 else 'fused' if F_.dur_bwd_fusable(prec, Hd, gates_d) else 'step', plan=plan,
-                NS=NS, NS16=NS16, z_in=z_in, TOKS=TOKS, gates_t=gates_t, HN=HN, HN16=HN16, gates_n=gates_n, pitch=pitch, HD=HD, HD16=HD16,
-                gates_d=gates_d, idx=idx, dur_tabs=(tab0, tab), TOK=TOK, PRED=PRED, xhat=xhat, XH=XH, XG=XG, XH16=XH16, plen=plen,
-                skipped=F_.ZERO_SKIP, coins=coins, has_xs=xs is not None)
-        ctx.mark_non_differentiable(xhat, idx)
-        return pitch.view(15, 32, B, NP), dur, xhat, idx
+                dims, prec, *_free_branches(plan, prec, dims, None if buf.gates_d is None else buf.gates_d.dtype), plan=plan,
+                dur_tabs=(tbl.tab0, tbl.tab), skipped=F_.ZERO_SKIP, coins=coins, has_xs=xs is not None, **buf.saved())
+        ctx.mark_non_differentiable(buf.xhat, buf.idx)
+        return buf.pitch.view(15, 32, B, NP), buf.dur, buf.xhat, buf.idx
 
     @staticmethod
     def backward(ctx, dpitch, ddur, _dx, _di):

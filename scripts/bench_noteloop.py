@@ -8,7 +8,6 @@ import sys
 import torch
 
 sys.path.insert(0, '.')
-from polyphonic_chord_texture_disentanglement_amd import functional as F_            # noqa: E402
 from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_      # noqa: E402
 from polyphonic_chord_texture_disentanglement_amd._lib import call, stream_ptr       # noqa: E402
 from polyphonic_chord_texture_disentanglement_amd.model import DisentangleVAE        # noqa: E402
@@ -21,15 +20,10 @@ def main():
     m = DisentangleVAE.init_model(dev).to(dev)
     P = dict(m.decoder.named_parameters())
     pk = FF_._free_packs(P, 1024)
-    w_ih_d, b_ih_d = P['dec_dur_gru.weight_ih_l0'], P['dec_dur_gru.bias_ih_l0']
-    tab0 = F_.gemm(P['dur_sos_token'].view(1, -1), w_ih_d, bias=b_ih_d, prec=0)
-    tab = F_.gemm(F_._onehot2x5(dev), w_ih_d, bias=b_ih_d, prec=0)
-    wl = F_._parr([pk['wg_h'], pk['wg_t'], pk['wp'], pk['wd_h'], pk['wd_p'], pk['wdur'], P['dec_notes_gru.bias_hh_l0'],
-                   P['pitch_out_linear.bias'], P['dur_hid_linear.bias'], P['dec_dur_gru.bias_hh_l0'], tab0, tab,
-                   P['dur_out_linear.weight'], P['dur_out_linear.bias'], pk['w_embT'], P['note_embedding.bias']])
+    tab0, tab = FF_.dur_tabs(P, dev)
+    wl = FF_.note_loop_weights(P, pk, tab0, tab)
     bf = torch.bfloat16
-    wE = [P['dec_notes_emb_gru.' + n] for n in FF_.EMB_GRU]
-    wr = F_._parr([pk['e_ih'], pk['e_hh'], pk['e_ih_r'], pk['e_hh_r'], wE[2], wE[3], wE[6], wE[7]])
+    wr = FF_.resum_weights(P, pk)
     for B in Bs:
         R, M = 32 * B, 15 * 32 * B
         panels = (B + 15) // 16
@@ -48,11 +42,9 @@ def main():
         plen = torch.zeros(R, device=dev, dtype=torch.int32)
         xch = torch.zeros(panels * 2 * 16 * 512 * 2, device=dev, dtype=bf)
         cnt = torch.zeros(panels + 1, device=dev, dtype=torch.int32)
-        io = F_._parr([GC[0], emb, HN, None, pitch, None, None, dur, idx, TOK, PRED, xhat, plen, None, None, None, None, None, None,
-                       xch if S > 1 else None, cnt if S > 1 else None])
-        ios = [F_._parr([GC[t], emb, HN, None, pitch, None, None, dur, idx, TOK, PRED, xhat, plen, None, None, None, None, None, None,
-                         xch if S > 1 else None, cnt if S > 1 else None]) for t in range(32)]
-        del io
+        slots = dict(EMB=emb, HN=HN, PITCH=pitch, DUR=dur, IDX=idx, TOK=TOK, PRED=PRED, XHAT=xhat, PLEN=plen, XCH=xch if S > 1 else None,
+                     CNT=cnt if S > 1 else None)
+        ios = [FF_.note_loop_io(GC=GC[t], **slots) for t in range(32)]
         print(f'B = {B}: {panels} panels x S = {S}')
         for name, extra in (('resident heads', 0), ('streamed heads (bit 21)', 0x200000),
                             ('resident, no gate MFMAs', 1 << 8), ('resident, no pitch head', 4 << 8), ('resident, no duration GRU', 8 << 8),
@@ -81,7 +73,7 @@ def main():
         # the re-summarisation of the predicted notes (ptv_free_resummarize): one launch per time step, 16 dependent bi-GRU steps each
         toks = torch.zeros(33, B, 256, device=dev)
         plen.fill_(9)
-        ior = [F_._parr([PRED, plen, None, None, None, None, toks[t + 1]]) for t in range(32)]
+        ior = [FF_.resum_io(PRED=PRED, PLEN=plen, TOK_OUT=toks[t + 1]) for t in range(32)]
         for name, fl in (('weights resident', 0), ('weights streamed (train bit 1)', 2)):
             best = 1e9
             toks.zero_()
@@ -98,8 +90,7 @@ def main():
         grid = (panels + 7) // 8 * 8 * S if S > 1 else panels
         dbg = torch.zeros(3 * grid + 8 * grid, device=dev, dtype=torch.long)
         for name, extra in (('resident', 0), ('streamed', 0x200000)):
-            iod = F_._parr([GC[5], emb, HN, None, pitch, None, None, dur, idx, TOK, PRED, xhat, plen, None, None, None, None, dbg, None,
-                            xch if S > 1 else None, cnt if S > 1 else None])
+            iod = FF_.note_loop_io(GC=GC[5], RESERVED17=dbg, **slots)
             cnt.zero_(); xch.zero_()
             for t in range(6):
                 call('ptv_free_note_loop', wl, iod if t == 5 else ios[t], 136, B, t, 0, 2 | 0x10000 | sbits | extra | ((64 << 8) if t == 5 else 0), stream_ptr())

@@ -73,3 +73,30 @@ def test_composite_python_sequencing_and_graph_replay_decode_the_same_bits(kind,
         m.decoder._graphs.clear()
     for a, b, c in zip(on, first, again):
         assert torch.equal(a, b) and torch.equal(a, c)
+
+
+def test_pointer_table_builders_put_every_tensor_in_its_named_slot():
+    """each builder's array holds data_ptr() of the tensor given for name i at entry i and NULL for an omitted name, 21 entries without a
+    block and 22 with one; the weight arrays over the model's parameters are the sequences include/ptvae_hip.h lists, written out here"""
+    one = lambda: torch.zeros(1, device=DEV)
+    for build, names in ((FF_.note_loop_io, FF_.NOTE_IO[:21]), (FF_.note_loop_io, FF_.NOTE_IO), (FF_.resum_io, FF_.RESUM_IO)):
+        ts = {n: one() for n in names}
+        assert len({t.data_ptr() for t in ts.values()}) == len(names)
+        arr = build(**ts)
+        assert len(arr) == len(names) and list(arr) == [ts[n].data_ptr() for n in names]
+        some = {n: ts[n] for n in names[1::2]}
+        arr = build(**some)
+        assert len(arr) == (21 if build is FF_.note_loop_io and 'BLOCK' not in some else len(names))
+        assert list(arr) == [some[n].data_ptr() if n in some else None for n in names[:len(arr)]]
+    P = dict(TT.model().decoder.named_parameters())
+    pk = FF_._free_packs(P, 1024)
+    with torch.no_grad():
+        tab0, tab = FF_.dur_tabs(P, torch.device(DEV))
+    assert tab0.shape == (1, 192) and tab.shape == (2, 192) and tab0.dtype == tab.dtype == torch.float32
+    want = [pk['wg_h'], pk['wg_t'], pk['wp'], pk['wd_h'], pk['wd_p'], pk['wdur'], P['dec_notes_gru.bias_hh_l0'], P['pitch_out_linear.bias'],
+            P['dur_hid_linear.bias'], P['dec_dur_gru.bias_hh_l0'], tab0, tab, P['dur_out_linear.weight'], P['dur_out_linear.bias'],
+            pk['w_embT'], P['note_embedding.bias']]
+    assert list(FF_.note_loop_weights(P, pk, tab0, tab)) == [t.data_ptr() for t in want]
+    want = [pk['e_ih'], pk['e_hh'], pk['e_ih_r'], pk['e_hh_r'], P['dec_notes_emb_gru.bias_ih_l0'], P['dec_notes_emb_gru.bias_hh_l0'],
+            P['dec_notes_emb_gru.bias_ih_l0_reverse'], P['dec_notes_emb_gru.bias_hh_l0_reverse']]
+    assert list(FF_.resum_weights(P, pk)) == [t.data_ptr() for t in want]

@@ -847,7 +847,6 @@ def test_row_segment_variants_of_step_sum_row_product_gather_and_scatter():
 def test_resummarize_with_resident_weights_is_bit_identical_to_the_streamed_kernel(B):
     """ptv_free_resummarize (round 6): a wave keeps its 48 weight fragments in registers for the 16 steps of a launch; train bit 1 selects the
     former path that streams them from L2 every step -- same products in the same k order: next tokens, saved states and gates bit-equal"""
-    from polyphonic_chord_texture_disentanglement_amd import functional as F_
     from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
     from polyphonic_chord_texture_disentanglement_amd._lib import call, stream_ptr
     from polyphonic_chord_texture_disentanglement_amd.model import DisentangleVAE
@@ -856,8 +855,7 @@ def test_resummarize_with_resident_weights_is_bit_identical_to_the_streamed_kern
     m = DisentangleVAE.init_model(dev).to(dev)
     P = dict(m.decoder.named_parameters())
     pk = FF_._free_packs(P, 1024)
-    wE = [P['dec_notes_emb_gru.' + n] for n in FF_.EMB_GRU]
-    wr = F_._parr([pk['e_ih'], pk['e_hh'], pk['e_ih_r'], pk['e_hh_r'], wE[2], wE[3], wE[6], wE[7]])
+    wr = FF_.resum_weights(P, pk)
     R = 32 * B
     g = torch.Generator(device=dev).manual_seed(9)
     PRED = torch.randn(16, R, 128, device=dev, generator=g) * 0.5
@@ -867,7 +865,7 @@ def test_resummarize_with_resident_weights_is_bit_identical_to_the_streamed_kern
         XH = [torch.zeros(17, R, 128, device=dev) for _ in range(2)]
         XG = [torch.zeros(16, 4, R, 128, device=dev, dtype=torch.bfloat16) for _ in range(2)]
         tok = torch.zeros(B, 256, device=dev)
-        io = F_._parr([PRED, plen, XH[0], XH[1], XG[0], XG[1], tok])
+        io = FF_.resum_io(PRED=PRED, PLEN=plen, XH0=XH[0], XH1=XH[1], XG0=XG[0], XG1=XG[1], TOK_OUT=tok)
         call('ptv_free_resummarize', wr, io, B, 3, fl, stream_ptr())
         torch.cuda.synchronize()
         outs.append([tok] + XH + XG)
@@ -1005,7 +1003,6 @@ def test_note_loop_cluster_mode_is_bit_identical_to_one_workgroup_per_panel(B):
     the arithmetic per unit is the same, so logits, decisions, tokens and states must equal the S = 1 launch BIT FOR BIT -- over
     two consecutive time steps (the arrival counters run on), inference and training mode; every panel counts 15 * S arrivals per
     launch and no member gave up waiting"""
-    from polyphonic_chord_texture_disentanglement_amd import functional as F_
     from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
     from polyphonic_chord_texture_disentanglement_amd._lib import call, stream_ptr
     from polyphonic_chord_texture_disentanglement_amd.model import DisentangleVAE
@@ -1016,12 +1013,8 @@ def test_note_loop_cluster_mode_is_bit_identical_to_one_workgroup_per_panel(B):
     R, M = 32 * B, 15 * 32 * B
     panels = (B + 15) // 16
     pk = FF_._free_packs(P, 1024)
-    w_ih_d, b_ih_d = P['dec_dur_gru.weight_ih_l0'], P['dec_dur_gru.bias_ih_l0']
-    tab0 = F_.gemm(P['dur_sos_token'].view(1, -1), w_ih_d, bias=b_ih_d, prec=0)
-    tab = F_.gemm(F_._onehot2x5(dev), w_ih_d, bias=b_ih_d, prec=0)
-    wl = F_._parr([pk['wg_h'], pk['wg_t'], pk['wp'], pk['wd_h'], pk['wd_p'], pk['wdur'], P['dec_notes_gru.bias_hh_l0'],
-                   P['pitch_out_linear.bias'], P['dur_hid_linear.bias'], P['dec_dur_gru.bias_hh_l0'], tab0, tab,
-                   P['dur_out_linear.weight'], P['dur_out_linear.bias'], pk['w_embT'], P['note_embedding.bias']])
+    tab0, tab = FF_.dur_tabs(P, dev)
+    wl = FF_.note_loop_weights(P, pk, tab0, tab)
     bf = torch.bfloat16
     g = torch.Generator(device=dev).manual_seed(5)
     GC = torch.randn(2, B, 1536, device=dev, generator=g) * 0.6
@@ -1049,8 +1042,8 @@ def test_note_loop_cluster_mode_is_bit_identical_to_one_workgroup_per_panel(B):
             xch = torch.zeros(panels * 2 * 16 * 512 * 2, device=dev, dtype=bf)
             cnt = torch.zeros(panels + 1, device=dev, dtype=torch.int32)
             for t in (0, 1):
-                io = F_._parr([GC[t], emb, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, None, None, None, None, None, None,
-                               xch if S > 1 else None, cnt if S > 1 else None])
+                io = FF_.note_loop_io(GC=GC[t], EMB=emb, HN=HN, GATES_N=gates_n, PITCH=pitch, HD=HD, GATES_D=gates_d, DUR=dur, IDX=idx, TOK=TOK,
+                                      PRED=PRED, XHAT=xhat, PLEN=plen, XCH=xch if S > 1 else None, CNT=cnt if S > 1 else None)
                 call('ptv_free_note_loop', wl, io, 136, B, t, 0x15a5 if train else 0,
                      train | 0x10000 | (0x400000 if S == 8 else ((S if S > 1 else 0) << 18)) | (0x200000 if S < 0 else 0), stream_ptr())
             torch.cuda.synchronize()

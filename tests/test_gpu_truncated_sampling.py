@@ -300,13 +300,9 @@ def test_4b_note_loop_kernels_agree_on_one_time_step():
     R, Mr = 32 * B, 15 * 32 * B
     panels = (B + 15) // 16
     pk = FF_._free_packs(P, 1024)
-    w_ih_d, b_ih_d = P['dec_dur_gru.weight_ih_l0'], P['dec_dur_gru.bias_ih_l0']
     with torch.no_grad():
-        tab0 = F_.gemm(P['dur_sos_token'].view(1, -1), w_ih_d, bias=b_ih_d, prec=0)
-        tab = F_.gemm(F_._onehot2x5(dev), w_ih_d, bias=b_ih_d, prec=0)
-    wl = F_._parr([pk['wg_h'], pk['wg_t'], pk['wp'], pk['wd_h'], pk['wd_p'], pk['wdur'], P['dec_notes_gru.bias_hh_l0'],
-                   P['pitch_out_linear.bias'], P['dur_hid_linear.bias'], P['dec_dur_gru.bias_hh_l0'], tab0, tab,
-                   P['dur_out_linear.weight'], P['dur_out_linear.bias'], pk['w_embT'], P['note_embedding.bias']])
+        tab0, tab = FF_.dur_tabs(P, dev)
+    wl = FF_.note_loop_weights(P, pk, tab0, tab)
     g = torch.Generator(device=dev).manual_seed(5)
     GC = torch.randn(B, 1536, device=dev, generator=g) * 0.6
     HN0 = torch.randn(R, 512, device=dev, generator=g) * 0.5
@@ -329,7 +325,7 @@ def test_4b_note_loop_kernels_agree_on_one_time_step():
         clustered = name in ('two', 'four', 'eight')
         xch = torch.zeros(panels * 2 * 16 * 512 * 2, device=dev, dtype=torch.bfloat16) if clustered else None
         cnt = torch.zeros(panels + 1, device=dev, dtype=torch.int32) if clustered else None
-        io = F_._parr([GC, None, HN, None, pitch, None, None, dur, idx, TOK, PRED, xhat, plen, None, None, None, None, None, None, xch, cnt, blk])
+        io = FF_.note_loop_io(GC=GC, HN=HN, PITCH=pitch, DUR=dur, IDX=idx, TOK=TOK, PRED=PRED, XHAT=xhat, PLEN=plen, XCH=xch, CNT=cnt, BLOCK=blk)
         call('ptv_free_note_loop', wl, io, 136, B, t, 0, bits | FF_.SAMPLE_BIT | FF_.TRUNC_BIT, stream_ptr())
         torch.cuda.synchronize()
         if clustered:

@@ -686,3 +686,70 @@ def test_free_plan_decides_the_step_loops_path_once(monkeypatch):
     assert plan(capturing=True) == p._replace(cluster=0, capturing=True)
     with torch.no_grad():
         assert plan(capturing=True, inference=True, needs_grad=False).cluster == 8
+
+
+def test_free_pointer_tables_are_named_in_the_headers_order():
+    from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
+    # include/ptvae_hip.h, ptv_free_note_loop / ptv_free_resummarize: w and io slot by slot
+    assert FF_.NOTE_W == ('WG_H', 'WG_T', 'WP', 'WD_H', 'WD_P', 'WDUR', 'B_HH_N', 'B_P', 'B_DH', 'B_HH_D', 'TAB0', 'TAB', 'W_OUT_D', 'B_OUT_D',
+                          'W_EMBT', 'B_EMB')
+    assert FF_.NOTE_IO == ('GC', 'EMB', 'HN', 'GATES_N', 'PITCH', 'HD', 'GATES_D', 'DUR', 'IDX', 'TOK', 'PRED', 'XHAT', 'PLEN', 'FORCE_PITCH',
+                           'FORCE_DUR', 'HN16', 'HD16', 'RESERVED17', 'H0GC', 'XCH', 'CNT', 'BLOCK')
+    assert FF_.RESUM_W == ('E_IH', 'E_HH', 'E_IH_R', 'E_HH_R', 'B_IH', 'B_HH', 'B_IH_R', 'B_HH_R')
+    assert FF_.RESUM_IO == ('PRED', 'PLEN', 'XH0', 'XH1', 'XG0', 'XG1', 'TOK_OUT')
+    assert [len(n) for n in (FF_.NOTE_W, FF_.NOTE_IO, FF_.RESUM_W, FF_.RESUM_IO)] == [16, 22, 8, 7]
+    assert [FF_.NOTE_IO.index(n) for n in ('H0GC', 'XCH', 'CNT', 'BLOCK')] == [18, 19, 20, 21]
+    for build in (FF_.note_loop_io, FF_.resum_io):
+        with pytest.raises(TypeError, match='NOPE'):
+            build(NOPE=torch.zeros(1))
+    # (host tensors have addresses too: omitted slots are NULL, the block is the 22nd pointer only when given)
+    a, b = torch.zeros(1), torch.zeros(1)
+    io = FF_.note_loop_io(PLEN=a)
+    assert len(io) == 21 and io[12] == a.data_ptr() and [io[i] for i in range(21) if i != 12] == [None] * 20
+    io = FF_.note_loop_io(PLEN=a, BLOCK=b)
+    assert len(io) == 22 and io[12] == a.data_ptr() and io[21] == b.data_ptr()
+    io = FF_.resum_io(TOK_OUT=a)
+    assert len(io) == 7 and io[6] == a.data_ptr() and list(io[:6]) == [None] * 6
+
+
+def test_free_branches_names_the_saved_states_kernels(monkeypatch):
+    from polyphonic_chord_texture_disentanglement_amd import functional as F_, functional_free as FF_
+    for mod, name, v in ((FF_, 'FREE_COMPOSITE', True), (FF_, 'FREE_PERSIST', True), (FF_, 'FREE_REPLAY', True), (FF_, 'NOTE_LOOP_SPLIT', None),
+                         (FF_, 'NOTE_LOOP_CLUSTER', None), (F_, 'BF16_STORAGE', True), (F_, 'NOTES_PERSIST', True), (F_, 'FUSED_DUR', True),
+                         (F_, 'HEADS_FUSED', True), (F_, 'DUR_RECOMPUTE', True)):
+        monkeypatch.setattr(mod, name, v)
+    B = 17
+    dims = (B, 32 * B, 128, 128, 1024, 512, 64, 130)                    # init_model()
+    small = (B, 32 * B, 20, 12, 40, 28, 8, 130)
+    none = ([[False] * 14] * 32, [False] * 31)
+
+    def case(prec=1, dims=dims):
+        """(the plan, gates_d as the forward allocates it) of a training forward"""
+        plan = FF_._free_plan(prec, dims, torch.float32, none, False, True, False, FF_.ARGMAX, 256, False)
+        saves = plan.train and not (plan.replay and F_.DUR_RECOMPUTE)
+        return plan, torch.empty(1, dtype=F_._act_dtype(prec, dims[6])) if saves else None
+
+    def rule(plan, prec, dims, gates_d):
+        """the three names as the forward chose them before the helper existed"""
+        Hn, Hd, NP = dims[5:8]
+        return ('rows' if plan.replay else 'step',
+                'fused' if F_.heads_ok(prec, Hn, NP, Hd, plan.state16 or None, plan.state16 or None) else 'gemm',
+                'fused16' if plan.state16 else 'fused' if F_.dur_bwd_fusable(prec, Hd, gates_d) else 'step')
+
+    def both(prec=1, dims=dims):
+        plan, gates_d = case(prec, dims)
+        got = FF_._free_branches(plan, prec, dims, None if gates_d is None else gates_d.dtype)
+        assert got == rule(plan, prec, dims, gates_d)
+        return plan, gates_d, got
+    plan, gates_d, names = both()                                     # the replayed training forward
+    assert plan.replay and gates_d is None and names == ('rows', 'fused', 'fused16')
+    assert both(prec=0)[2] == ('step', 'gemm', 'step')
+    assert both(dims=small)[2] == ('step', 'gemm', 'step')            # (Hd = 8: no fused duration backward)
+    monkeypatch.setattr(FF_, 'FREE_REPLAY', False)                    # the persistent loop's own states, with their bf16 copies
+    plan, gates_d, names = both()
+    assert plan.fast and plan.state16 and not plan.replay and gates_d.dtype == torch.bfloat16 and names == ('step', 'fused', 'fused16')
+    monkeypatch.setattr(FF_, 'FREE_PERSIST', False)                   # the per-step loop in bf16: saved bf16 gates, fp32 states
+    plan, gates_d, names = both()
+    assert not plan.fast and names == ('step', 'gemm', 'fused')
+    monkeypatch.setattr(F_, 'BF16_STORAGE', False)                    # ... and with fp32 gates
+    assert both()[2] == ('step', 'gemm', 'step')
