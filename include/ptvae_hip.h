@@ -1136,6 +1136,35 @@ int ptv_keep_voice_force_build(const long* x, const unsigned char* mode, int mod
                                int lowest_rows, int flags, long B, int* force_pitch, int* force_dur, int* kept_n, int* err, void* stream);
 int ptv_grid_split_voice(const long* x, const unsigned char* mode, int mode_rows, const int* below, int below_rows, const int* lowest,
                          int lowest_rows, long B, long* voice, long* rest, int* kept_n, int* err, void* stream);
+/* Kept rhythm: a decode that keeps the number of notes of a time step, its rests and its durations, and draws the pitches again
+ * (csrc/keep_rhythm.hip; INTEGRATION.md "Kept rhythm").
+ * PTV_FORCE_NOT_EOS (-2), a word of force_pitch: the decision is FREE, but <eos> (129) is not in its support unless nothing else is.  <eos>
+ *   leaves the allowed set of that decision iff at least one other class is allowed (after the mask, after `ascending`, never <sos> under
+ *   `ascending`, columns < 130).  If no other class is allowed <eos> stays: the allowed set is never empty, the step ends short, and nothing
+ *   reports it at decode time -- count the notes.  The removal is part of the allowed rule, so it precedes every truncation: top_k, the
+ *   nucleus mass, min_p's maximum and Z are those of the allowed classes without <eos>.  T_pitch = 0: the argmax over that set.  Every other
+ *   negative word, -1 included, is a plainly free decision as before.
+ *   ONLY the constrained kind (64-byte block: bit 25 of ptv_free_note_loop's train word, ptv_note_token_sample_cons, PTV_DFF_D_SAMPLE_CONS,
+ *   sample_bytes = 64 of ptv_decode_logprob) honours the word.  A -2 that reaches an argmax, sampled or truncated kernel is a free decision
+ *   like -1: send a decode with such words as the constrained kind (flags 0 and no mask constrain nothing).
+ *   ptv_decode_logprob: a -2 decision counts as free, its log q is taken over the same reduced support (a decided <eos> outside it sets
+ *   bit 0 of err); log p is untouched.
+ * ptv_keep_rhythm_force_build: the force arrays.  x as in "Kept steps"; mode: uint8 [mode_rows][32], mode_rows = 1 or B, per (b, t):
+ *   0  the step is free: every word -1.
+ *   1  the whole step is kept: ptv_keep_force_build's rule element for element.
+ *   3  the rhythm of the step is kept.  L = the first slot s in 1..15 with x[b][t][s][0] == 129, else 15 (the rule of "Kept steps");
+ *      K = L - 1 notes, or 15 where the step holds no <eos>.  For n < K force_pitch[n][t*B + b] = PTV_FORCE_NOT_EOS and
+ *      force_dur[d][n*R + t*B + b] = x[b][t][n+1][1+d] where that is 0 or 1 (else -1) -- unless bit 0 of flags ("pitches only") is set:
+ *      then every duration word of a rhythm step is -1.  For n = K < 15 force_pitch[n] = 129 (the step ends exactly there) with duration
+ *      words -1.  Every other word of the step is -1.  K = 0 keeps a rest.  A slot before L whose pitch lies outside 0..127 still counts
+ *      as a note position (-2) and sets bit 0 of err[b].
+ *   any other value: the step is free and bit 1 of err[b] is set.
+ * kept_n int32 [B][32]: K at a rhythm step, the number of forced pitch decisions at a whole step, 0 at a free step.  EVERY element of
+ * force_pitch [15][32B], force_dur [5][480B], kept_n and err [B] is written, by one thread each.  A NULL pointer, B < 1, mode_rows outside
+ * {1, B} or flags outside 0..1: PTV_ERR_ARG before any launch. */
+#define PTV_FORCE_NOT_EOS (-2)
+int ptv_keep_rhythm_force_build(const long* x, const unsigned char* mode, int mode_rows, int flags, long B, int* force_pitch, int* force_dur,
+                                int* kept_n, int* err, void* stream);
 int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
                              int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream);
 int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,

@@ -71,6 +71,11 @@ int ptv_debug_pitch_keep(const void* block48, const float* logits, long rows, in
  * Layouts as above.  keep_out [rows, 130] uint8 = allowed and logit >= threshold, thr_out [rows] fp32 = the threshold */
 int ptv_debug_pitch_constrain(const void* block64, const float* logits, const int* masks, const int* lo, long rows, int layout,
                               unsigned char* keep_out, float* thr_out, void* stream);
+/* ... with the force word of each row, words [rows] int32 (ptvae_hip.h "Kept rhythm"): a row whose word is PTV_FORCE_NOT_EOS loses <eos> from its
+ * allowed set unless nothing else is allowed, before the threshold is formed; every other word leaves the row what the entry above makes of
+ * it (all words -1: the same bytes).  A NULL words is PTV_ERR_ARG. */
+int ptv_debug_pitch_constrain_words(const void* block64, const float* logits, const int* masks, const int* lo, const int* words, long rows,
+                                    int layout, unsigned char* keep_out, float* thr_out, void* stream);
 
 /* test aid of the chord decode (ptvae_hip.h "Row-independent free-running chord decode"): the Gumbel values ptv_chord_decide uses for rows
  * [0, rows) -- samples sample_offset + row of the 32-byte block -- at chord step t, through the device function that kernel calls:

@@ -152,7 +152,9 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
   for (int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < M; r += gridDim.x * (blockDim.x >> 6)) {
     const float* lr = pitch + (long)r * ld_pitch;
     float best = -INFINITY; int bi = 0x7fffffff;
+    [[maybe_unused]] int fw3 = -1;                                 // SAMP = 3: the row's force word (negative: a free decision)
     if constexpr (SAMP == 3) {                                     // constrained: ... over the ALLOWED classes (pitch_constrain, philox.hpp)
+      if (force_pitch) fw3 = force_pitch[r];                       // (before the constrain: PTV_FORCE_NOT_EOS takes <eos> out of the allowed set)
       const SampleBlockC* q = reinterpret_cast<const SampleBlockC*>(samp);
       const SampleBlock sb = q->s.s;
       const Trunc tr = load_trunc(&q->s);
@@ -168,7 +170,7 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
       float pv[3], tv[3];
 #pragma unroll
       for (int i = 0; i < 3; i++) pv[i] = lane + 64 * i < 130 ? lr[lane + 64 * i] : -INFINITY;
-      const unsigned al = pitch_constrain<3, 64>(pv, mw, lo, cn.flags, lane, tv);
+      const unsigned al = pitch_constrain<3, 64>(pv, mw, lo, cn.flags, lane, tv, fw3 == PTV_FORCE_NOT_EOS);
       const float thr = pitch_keep_threshold<3, 64>(tr, sb.t_pitch, tv);      // (the whole wave is here: r is uniform over it)
 #pragma unroll
       for (int i = 0; i < 3; i++) {
@@ -206,7 +208,8 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
       float ov = __shfl_xor(best, o, 64); int oi = __shfl_xor(bi, o, 64);
       if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }       // first maximal index (torch.max)
     }
-    if (force_pitch) { const int fw = force_pitch[r]; if (fw >= 0) bi = fw; }   // (negative: a free decision)
+    if constexpr (SAMP == 3) { if (fw3 >= 0) bi = fw3; }
+    else if (force_pitch) { const int fw = force_pitch[r]; if (fw >= 0) bi = fw; }   // (negative: a free decision)
     int bits[5];
 #pragma unroll
     for (int d = 0; d < 5; d++) bits[d] = dur_idx[(long)d * dur_stride + r];

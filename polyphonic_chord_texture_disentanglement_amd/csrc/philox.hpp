@@ -215,6 +215,8 @@ __device__ __forceinline__ float pitch_keep_threshold(const Trunc tr, float T, c
 // <eos> (129) is always allowed: the allowed set is never empty.  A disallowed class enters pitch_keep_threshold() as -INFINITY (top_k counts
 // the k best ALLOWED classes, the nucleus mass, Z and min_p's maximum are those of the allowed classes; with fewer than k allowed the
 // select ends at the -INFINITY key: all of them are kept), and the draw tests the returned bitmap beside the threshold.
+// Kept rhythm: a decision whose force word is PTV_FORCE_NOT_EOS (-2) is free, but <eos> leaves its allowed set unless nothing
+// else is allowed -- inside the allowed rule, so before any truncation.  Only the kernels of this 64-byte kind honour the word.
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct SampleBlockC {
   SampleBlockT s;
@@ -256,8 +258,12 @@ __device__ __forceinline__ int pitch_lo_next(int lo, int decision) { return deci
 // own: pitch_mask_own() of the row's mask words; lo, flags as above (flags is uniform over the block: a scalar branch).
 // tv: v with the disallowed classes (and the columns >= 130) at -INFINITY -- the input of pitch_keep_threshold(); returns the bitmap of the
 // lane's allowed columns: the draw takes column i iff bit i is set and v[i] >= the threshold.
+// no_eos (a kept rhythm: the decision's force word is PTV_FORCE_NOT_EOS; uniform over the W lanes of the row, it may differ between the rows
+// of a wave): <eos> (129) leaves the allowed set iff another class is allowed -- one integer sum over the row, which every lane takes
+// whatever its flag, so nothing diverges around it; a caller that leaves the argument out compiles to what it did without it.
 template <int NV, int W>
-__device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], unsigned own, int lo, unsigned flags, int j, float (&tv)[NV]) {
+__device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], unsigned own, int lo, unsigned flags, int j, float (&tv)[NV],
+                                                    bool no_eos = false) {
   unsigned al = own;
   if (flags & CONS_ASCENDING) {
 #pragma unroll
@@ -266,14 +272,22 @@ __device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], unsign
       if (!(c == 129 || (c < 128 && c > lo))) al &= ~(1u << i);
     }
   }
+  {
+    constexpr int EI = 129 / W, EJ = 129 % W;                      // <eos> is column EJ + W * EI: bit EI of lane EJ
+    static_assert(EI < NV, "the row holds column 129");
+    const unsigned eos_bit = j == EJ ? 1u << EI : 0u;
+    const int others = row_sum<W>(__popc(al & ~eos_bit));
+    if (no_eos && others > 0) al &= ~eos_bit;
+  }
 #pragma unroll
   for (int i = 0; i < NV; i++) tv[i] = (al >> i) & 1u ? v[i] : -INFINITY;
   return al;
 }
 // ... from the row's four mask words (the step loop and the debug entry, which see a row once)
 template <int NV, int W>
-__device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], const unsigned (&m)[4], int lo, unsigned flags, int j, float (&tv)[NV]) {
-  return pitch_constrain<NV, W>(v, pitch_mask_own<NV, W>(m, j), lo, flags, j, tv);
+__device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], const unsigned (&m)[4], int lo, unsigned flags, int j, float (&tv)[NV],
+                                                    bool no_eos = false) {
+  return pitch_constrain<NV, W>(v, pitch_mask_own<NV, W>(m, j), lo, flags, j, tv, no_eos);
 }
 
 }  // namespace ptv

@@ -85,7 +85,8 @@ __global__ void pitch_keep_kernel(const SampleBlockT* __restrict__ blk, const fl
 // layouts; the block's flags are read, its mask address is not (the caller's rows are the masks)
 template <int LAYOUT>
 __global__ void pitch_constrain_kernel(const SampleBlockC* __restrict__ blk, const float* __restrict__ logits, const int* __restrict__ masks,
-                                       const int* __restrict__ lo, long rows, unsigned char* __restrict__ keep_out, float* __restrict__ thr_out) {
+                                       const int* __restrict__ lo, const int* __restrict__ words, long rows,
+                                       unsigned char* __restrict__ keep_out, float* __restrict__ thr_out) {
   constexpr int W = LAYOUT ? 64 : 16, NV = LAYOUT ? 3 : 9;
   const Trunc tr = load_trunc(&blk->s);
   const float T = blk->s.s.t_pitch;
@@ -101,7 +102,8 @@ __global__ void pitch_constrain_kernel(const SampleBlockC* __restrict__ blk, con
     unsigned mw[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) mw[i] = (unsigned)masks[r * 4 + i];
-    const unsigned al = pitch_constrain<NV, W>(v, mw, lo[r], flags, j, tv);
+    const bool no_eos = words && words[r] == PTV_FORCE_NOT_EOS;    // (words: the force word of each row, NULL = every decision plainly free)
+    const unsigned al = pitch_constrain<NV, W>(v, mw, lo[r], flags, j, tv, no_eos);
     const float thr = pitch_keep_threshold<NV, W>(tr, T, tv);
     if (ok) {
 #pragma unroll
@@ -113,18 +115,29 @@ __global__ void pitch_constrain_kernel(const SampleBlockC* __restrict__ blk, con
 
 }  // namespace ptv
 
-extern "C" int ptv_debug_pitch_constrain(const void* block64, const float* logits, const int* masks, const int* lo, long rows, int layout,
-                                         unsigned char* keep_out, float* thr_out, void* stream) {
+static int debug_pitch_constrain(const void* block64, const float* logits, const int* masks, const int* lo, const int* words, long rows,
+                                 int layout, unsigned char* keep_out, float* thr_out, void* stream) {
   if (!block64 || !logits || !masks || !lo || !keep_out || !thr_out || rows <= 0 || (layout != 0 && layout != 1)) return PTV_ERR_ARG;
   long nb = (rows + 3) / 4; if (nb > 4096) nb = 4096;
   if (layout == 0)
     hipLaunchKernelGGL(ptv::pitch_constrain_kernel<0>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (const ptv::SampleBlockC*)block64, logits,
-                       masks, lo, rows, keep_out, thr_out);
+                       masks, lo, words, rows, keep_out, thr_out);
   else
     hipLaunchKernelGGL(ptv::pitch_constrain_kernel<1>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (const ptv::SampleBlockC*)block64, logits,
-                       masks, lo, rows, keep_out, thr_out);
+                       masks, lo, words, rows, keep_out, thr_out);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
+}
+
+extern "C" int ptv_debug_pitch_constrain(const void* block64, const float* logits, const int* masks, const int* lo, long rows, int layout,
+                                         unsigned char* keep_out, float* thr_out, void* stream) {
+  return debug_pitch_constrain(block64, logits, masks, lo, nullptr, rows, layout, keep_out, thr_out, stream);
+}
+
+extern "C" int ptv_debug_pitch_constrain_words(const void* block64, const float* logits, const int* masks, const int* lo, const int* words,
+                                               long rows, int layout, unsigned char* keep_out, float* thr_out, void* stream) {
+  if (!words) return PTV_ERR_ARG;
+  return debug_pitch_constrain(block64, logits, masks, lo, words, rows, layout, keep_out, thr_out, stream);
 }
 
 extern "C" int ptv_debug_pitch_keep(const void* block48, const float* logits, long rows, int layout, unsigned char* keep_out, float* thr_out,

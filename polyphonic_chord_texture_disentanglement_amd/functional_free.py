@@ -247,6 +247,37 @@ def _check_grid(x):
         raise ValueError('x must be int64 [B, 32, 16, 6], got %s %s' % (x.dtype, tuple(x.shape)))
 
 
+def _check_step_selections(x, named):
+    """ValueError unless every selection of named = ((name, selection), ...) that is a tensor is a bool / uint8 tensor [B, 32] or [1, 32]
+    on the device of the (checked) grid x"""
+    B = x.shape[0]
+    for name, s in named:
+        if torch.is_tensor(s):
+            if s.device != x.device:
+                raise ValueError('%s must be on the device of x (or a host iterable of step indices / a slice)' % name)
+            if s.dtype not in (torch.bool, torch.uint8):
+                raise ValueError('%s must be bool or uint8, got %s' % (name, s.dtype))
+            if s.dim() != 2 or s.shape[1] != 32 or s.shape[0] not in (1, B):
+                raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(s.shape)))
+
+
+def _mode_bytes(x, first, whole, code):
+    """two validated selections (a device tensor or the 32 bytes of keep_steps_row; whole may be None) -> mode uint8 [rows, 32] on the
+    device of x: `code` at the steps of `first`, 1 at the steps of `whole` -- a step in both is a whole step.  Raises nothing."""
+    if not torch.is_tensor(first) and not torch.is_tensor(whole):
+        row = bytearray(code * v for v in first)
+        for t, w in enumerate(whole or b''):
+            if w:
+                row[t] = 1
+        return torch.frombuffer(row, dtype=torch.uint8).view(1, 32).to(x.device)
+    first, whole = (s if s is None or torch.is_tensor(s) else torch.frombuffer(bytearray(s), dtype=torch.uint8).view(1, 32).to(x.device)
+                    for s in (first, whole))
+    mode = (first != 0).to(torch.uint8) * code
+    if whole is not None:
+        mode = torch.where(whole != 0, torch.ones_like(mode[:1, :1]), mode)
+    return mode.contiguous()
+
+
 def _voice_selection(x, voice_steps, below, lowest, whole_steps):
     """the arguments both kept-voice entry points share, validated -- every ValueError before any launch -- and then put on the device:
     -> (x contiguous, mode uint8 [rows, 32] (2 = voice step, 1 = whole step: a step in both selections is a whole step), below, lowest:
@@ -262,14 +293,7 @@ def _voice_selection(x, voice_steps, below, lowest, whole_steps):
         raise ValueError('voice_steps must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice')
     _check_grid(x)
     B = x.shape[0]
-    for name, s in (('voice_steps', sels[0]), ('whole_steps', sels[1])):
-        if torch.is_tensor(s):
-            if s.device != x.device:
-                raise ValueError('%s must be on the device of x (or a host iterable of step indices / a slice)' % name)
-            if s.dtype not in (torch.bool, torch.uint8):
-                raise ValueError('%s must be bool or uint8, got %s' % (name, s.dtype))
-            if s.dim() != 2 or s.shape[1] != 32 or s.shape[0] not in (1, B):
-                raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(s.shape)))
+    _check_step_selections(x, (('voice_steps', sels[0]), ('whole_steps', sels[1])))
     for name, v in (('below', limits[0]), ('lowest', limits[1])):
         if torch.is_tensor(v):
             if v.device != x.device or v.dtype != torch.int32:
@@ -277,20 +301,7 @@ def _voice_selection(x, voice_steps, below, lowest, whole_steps):
             if v.dim() != 2 or v.shape[1] != 32 or v.shape[0] not in (1, B):
                 raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(v.shape)))
     # ---- nothing below raises
-    voice, whole = sels
-    if not torch.is_tensor(voice) and not torch.is_tensor(whole):
-        row = bytearray(2 * v for v in voice)
-        for t, w in enumerate(whole or b''):
-            if w:
-                row[t] = 1
-        mode = torch.frombuffer(row, dtype=torch.uint8).view(1, 32).to(x.device)
-    else:
-        voice, whole = (s if s is None or torch.is_tensor(s) else torch.frombuffer(bytearray(s), dtype=torch.uint8).view(1, 32).to(x.device)
-                        for s in (voice, whole))
-        mode = (voice != 0).to(torch.uint8) * 2
-        if whole is not None:
-            mode = torch.where(whole != 0, torch.ones_like(mode[:1, :1]), mode)
-        mode = mode.contiguous()
+    mode = _mode_bytes(x, sels[0], sels[1], 2)
     limits = [v.contiguous() if torch.is_tensor(v) else (None if v is None else torch.full((1, 32), v, dtype=torch.int32, device=x.device))
               for v in limits]
     return x.contiguous(), mode, limits[0], limits[1]
@@ -315,6 +326,48 @@ def build_keep_voice(x, voice_steps, below=None, lowest=None, durations=True, wh
     call('ptv_keep_voice_force_build', ptr(x), ptr(mode), mode.shape[0], ptr(below), 1 if below is None else below.shape[0], ptr(lowest),
          1 if lowest is None else lowest.shape[0], 0 if durations else 1, B, ptr(pitch), ptr(dur), ptr(kept_n), ptr(err), stream_ptr())
     keep = Keep(pitch, dur, err, B)
+    return (keep, kept_n) if return_counts else keep
+
+
+FORCE_NOT_EOS = -2          # PTV_FORCE_NOT_EOS: a pitch word that leaves the decision free but takes <eos> out of its support
+
+
+class RhythmKeep(Keep):
+    """a Keep whose pitch array holds FORCE_NOT_EOS words (ptv_keep_rhythm_force_build; INTEGRATION.md "Kept rhythm"): the same four
+    fields, so it goes wherever a Keep goes -- but only the constrained kernels honour the word, so a decode with one is always sent as
+    the constrained kind (DisentangleVAE._sampling_words), and PtvaeDecoder refuses it beside any other block"""
+    __slots__ = ()
+
+
+def _rhythm_selection(x, steps, whole_steps):
+    """the selections of build_keep_rhythm validated as _voice_selection's -- every ValueError before any launch -- and then put on the
+    device: -> (x contiguous, mode uint8 [rows, 32]: 3 = rhythm step, 1 = whole step; a step in both selections is a whole step)"""
+    sels = [s if s is None or torch.is_tensor(s) else keep_steps_row(s) for s in (steps, whole_steps)]
+    if sels[0] is None:
+        raise ValueError('steps must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice')
+    _check_grid(x)
+    _check_step_selections(x, (('steps', sels[0]), ('whole_steps', sels[1])))
+    return x.contiguous(), _mode_bytes(x, sels[0], sels[1], 3)      # (nothing after the checks raises)
+
+
+def build_keep_rhythm(x, steps, durations=True, whole_steps=None, return_counts=False):
+    """the kept RHYTHM of a free-running decode -> RhythmKeep (ptv_keep_rhythm_force_build; INTEGRATION.md "Kept rhythm"): at the steps of
+    `steps` the decode has exactly the notes of x's step -- K decisions that are free but may not be <eos>, then a forced <eos> -- with
+    x's duration bits (durations=False: pitches and durations are both drawn, only the count is kept); the steps of whole_steps are
+    kept whole as by build_keep (a step in both is a whole step).  Selections as build_keep's steps.  return_counts: -> (RhythmKeep,
+    kept_n int32 [B, 32]: K at a rhythm step, the forced pitch decisions at a whole step).  ValueError before any launch; nothing is
+    copied to the host."""
+    if not isinstance(durations, bool):
+        raise ValueError('durations must be a bool, got %r' % (durations,))
+    x, mode = _rhythm_selection(x, steps, whole_steps)
+    B = x.shape[0]
+    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=x.device)
+    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=x.device)
+    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
+    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    call('ptv_keep_rhythm_force_build', ptr(x), ptr(mode), mode.shape[0], 0 if durations else 1, B, ptr(pitch), ptr(dur), ptr(kept_n),
+         ptr(err), stream_ptr())
+    keep = RhythmKeep(pitch, dur, err, B)
     return (keep, kept_n) if return_counts else keep
 
 

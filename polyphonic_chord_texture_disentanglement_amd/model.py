@@ -13,8 +13,8 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import (Keep, build_chord_keep, build_keep, build_keep_voice, check_chord_keep, check_chord_sampling,
-                              check_constraints, check_keep, check_sampling, make_block, sampling_words, split_voice)
+from .functional_free import (Keep, RhythmKeep, build_chord_keep, build_keep, build_keep_rhythm, build_keep_voice, check_chord_keep,
+                              check_chord_sampling, check_constraints, check_keep, check_sampling, make_block, sampling_words, split_voice)
 from .optim import refresh_weight_shadows
 from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
@@ -50,8 +50,8 @@ class DecodeRequest(collections.namedtuple('DecodeRequest', 'sampled kw mask kee
         if mask is not None and mask.shape[0] == B and B > 1:
             mask = mask.repeat(n, 1, 1)
         if keep is not None:
-            keep = Keep(keep.pitch.view(15, 32, 1, B).expand(15, 32, n, B).reshape(15, 32 * n * B),
-                        keep.dur.view(5, 15, 32, 1, B).expand(5, 15, 32, n, B).reshape(5, 480 * n * B), keep.err.repeat(n), n * B)
+            keep = type(keep)(keep.pitch.view(15, 32, 1, B).expand(15, 32, n, B).reshape(15, 32 * n * B),
+                              keep.dur.view(5, 15, 32, 1, B).expand(5, 15, 32, n, B).reshape(5, 480 * n * B), keep.err.repeat(n), n * B)
         return self._replace(mask=mask, keep=keep, batch=n * B)
 
 
@@ -421,17 +421,21 @@ class DisentangleVAE(PytorchModel):
 
     def _sampling_words(self, req):
         """None (argmax decode) or the request's sampling block as host words (keep puts nothing into the block: it travels beside it);
-        a sampled decode that names no draw takes the model's counter and advances it"""
+        a sampled decode that names no draw takes the model's counter and advances it.  A rhythm keep promotes the decode to the constrained
+        kind, whose kernels alone honour its words: an `ascending` nobody gave becomes False, the vacuous constraint (flags 0, no mask)"""
         kw = req.kw
+        ascending = kw['ascending']
+        if ascending is None and isinstance(req.keep, RhythmKeep):
+            ascending = False
         if not req.sampled:
-            if req.mask is None and kw['ascending'] is None:
+            if req.mask is None and ascending is None:
                 return None
-            return sampling_words(0.0, 0.0, 0, 0, 0, pitch_mask=req.mask, ascending=kw['ascending'])   # the constrained argmax: no noise, no draw used
+            return sampling_words(0.0, 0.0, 0, 0, 0, pitch_mask=req.mask, ascending=ascending)   # the constrained argmax: no noise, no draw used
         ph = self._philox or (7, 0)
         seed, draw, offset = kw['seed'], kw['draw'], kw['sample_offset']
         words = sampling_words(kw['temperature'], kw['dur_temperature'], ph[0] if seed is None else seed,
                                self._sample_draws if draw is None else draw, ph[1] if offset is None else offset, top_k=kw['top_k'],
-                               min_p=kw['min_p'], top_p=kw['top_p'], pitch_mask=req.mask, ascending=kw['ascending'])
+                               min_p=kw['min_p'], top_p=kw['top_p'], pitch_mask=req.mask, ascending=ascending)
         if draw is None:
             self._sample_draws += 1
         return words
@@ -469,6 +473,19 @@ class DisentangleVAE(PytorchModel):
         is none of 0 / 1 / 2 (never from here).  return_counts=True: -> (Keep, kept_n int32 [B, 32], the forced pitch decisions per
         step).  Nothing is copied to the host."""
         return build_keep_voice(x, voice_steps, below, lowest, durations, whole_steps, return_counts)
+
+    def keep_rhythm(self, x, steps, durations=True, whole_steps=None, return_counts=False):
+        """The kept rhythm of a decode -> functional_free.RhythmKeep for keep= (ptv_keep_rhythm_force_build; INTEGRATION.md "Kept rhythm").
+        x: the grid as in keep(); steps / whole_steps: selections as keep()'s steps.  At a rhythm step the decode gets exactly the notes of
+        x's step: its K note decisions are free but cannot be <eos>, decision K is a forced <eos> (K = 0 keeps a rest, K = 15 forces no
+        <eos>), and the duration bits are x's (durations=False: only the note count is kept).  The pitches are drawn again under whatever
+        the decode is given -- temperature, top_k / min_p / top_p, pitch_mask, ascending.  Where a mask and ascending leave no pitch, <eos> is
+        the fallback and the step ends short: compare the note counts to see it.  A whole step is kept as by keep(); a step in both
+        selections is a whole step.  A decode with this keep always runs the constrained kernels (without a mask or ascending: with a
+        constraint that excludes nothing).  err[b] bit 0: a kept step of sample b held a pitch that is no note before its <eos> (a
+        rhythm step still counts the slot); bit 1: a mode byte that is none of 0 / 1 / 3 (never from here).  return_counts=True: ->
+        (RhythmKeep, kept_n int32 [B, 32]).  Nothing is copied to the host."""
+        return build_keep_rhythm(x, steps, durations, whole_steps, return_counts)
 
     def split_voice(self, x, voice_steps, below=None, lowest=None, whole_steps=None):
         """The selection of keep_voice as two grids -> (x_voice, x_rest, kept_n, err) (ptv_grid_split_voice): x_voice holds per step the

@@ -9,6 +9,9 @@ decode of the same process.
 The keep rows (kept time steps, keep=: six force words per row and note step, one select per decision) decode the same batch with the
 first bar of a synthetic grid kept under plain sampling, and with a per-row alternating pattern ((t + b) % 4 < 2) kept under mask +
 ascending + top_k + top_p; each is reported against the same setting without a keep.
+The rhythm rows (kept rhythm, DisentangleVAE.keep_rhythm: every step of the same grid keeps its note count and durations, the pitches are
+drawn again) run under plain sampling -- sent as the constrained kind with a block that constrains nothing, as the model sends it -- and
+under mask + ascending + top_k + top_p; each beside the same setting without a keep.
 The logprob rows (--logprob 1; PtvaeDecoder.decode_logprob, DisentangleVAE.decode_best_of) time the log-probability pass ALONE -- the two
 launches after a plain sampled decode, and after the mask + ascending + top_k + top_p decode, where every row also runs the allowed rule
 and both 32-round selects -- and decode_best_of(n=4) at a quarter of the batch (as many decoded rows as one plain decode of the batch).
@@ -78,6 +81,9 @@ def main():
         if a.constrained:
             alt = ((torch.arange(32, device=dev)[None, :] + rows[:, None]) % 4 < 2)
             keeps['keep alternating+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.keep(x, alt))
+        keeps['keep rhythm'] = ('sampled', m.keep_rhythm(x, range(32)))
+        if a.constrained:
+            keeps['keep rhythm+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.keep_rhythm(x, range(32)))
     kinds += list(keeps)
     blocks = {'argmax': [None] * (a.rounds + 1),
               'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
@@ -89,6 +95,8 @@ def main():
 
     for k, (base, _) in keeps.items():
         blocks[k] = blocks[base]
+    if 'keep rhythm' in keeps:                               # a rhythm keep needs the constrained kind: the vacuous constraint
+        blocks['keep rhythm'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=False) for d in range(a.rounds + 1)]
 
     def run(block, keep=None):
         with torch.no_grad():
