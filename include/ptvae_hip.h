@@ -1165,6 +1165,48 @@ int ptv_grid_split_voice(const long* x, const unsigned char* mode, int mode_rows
 #define PTV_FORCE_NOT_EOS (-2)
 int ptv_keep_rhythm_force_build(const long* x, const unsigned char* mode, int mode_rows, int flags, long B, int* force_pitch, int* force_dur,
                                 int* kept_n, int* err, void* stream);
+/* Kept top voice: a decode that keeps the HIGHEST notes of a time step -- a suffix of its note decisions -- and its note count, and draws
+ * the notes under them again (csrc/keep_top.hip; INTEGRATION.md "Kept top voice").
+ * PTV_FORCE_BELOW(u) = -256 - u, u in 1..128 (the words -257..-384 of force_pitch): the decision is FREE, is never <eos>, and its pitch is a
+ *   note strictly below the ceiling u.  The rule is part of the allowed rule: after the mask and `ascending`, before every truncation
+ *   (top_k, the nucleus mass, min_p's maximum and Z are those of the set below).  With lane = the notes c < 128 with c < u -- under the
+ *   `ascending` flag also c > lo -- the allowed set of the decision is
+ *     lane & mask   if that is not empty;
+ *     lane          if it is: the mask yields, so the step neither ends short nor loses the notes kept behind this decision;
+ *     {<eos>}       if lane itself is empty.  Only hand-made words get here: the builder emits no such ceiling on a grid that raises no err bit.
+ *   <sos> and <eos> are in no other case part of it.  T_pitch = 0: the argmax over that set.  Every other negative word keeps its meaning:
+ *   -2 is PTV_FORCE_NOT_EOS, -1 and any other value are plainly free.
+ *   ONLY the constrained kind honours the word, at the sites that honour PTV_FORCE_NOT_EOS (see "Kept rhythm"); anywhere else it is a free
+ *   decision like -1.  ptv_decode_logprob: such a decision counts as free, its log q is taken over the same set, relaxed or not (a decided
+ *   class outside it sets bit 0 of err); log p is untouched.
+ * ptv_keep_top_force_build: the force arrays.  x as in "Kept steps"; mode: uint8 [mode_rows][32], mode_rows = 1 or B, per (b, t):
+ *   0  the step is free: every word -1.
+ *   1  the whole step is kept: ptv_keep_force_build's rule element for element.
+ *   4  the top of the step is kept.  L = the first slot s in 1..15 with x[b][t][s][0] == 129, else 15 (the rule of "Kept steps"); K = L - 1
+ *      notes, or 15 where the step holds no <eos>.  The kept notes are the last h of them: from slot K downwards, stop at h == highest
+ *      (int32 [highest_rows][32], clamped to 0..15), at a pitch outside 0..127 and at the first pitch < above (int32 [above_rows][32],
+ *      clamped to 0..128).  A NULL limit does not limit; both NULL: h = min(1, K), the very top note.  J = K - h.
+ *      n < J:       force_pitch[n][t*B + b] = PTV_FORCE_BELOW(u_n), u_n clamped into 1..128.  Bit 1 of flags clear ("lanes"): u_n = the
+ *                   pitch of x's next note, x[b][t][n+2][0] (128 behind the last note): no re-drawn voice crosses its old upper neighbour.
+ *                   Bit 1 set ("room"): u_n = p_J - (J - 1 - n), p_J the lowest kept pitch, 128 where h = 0: a semitone for each decision
+ *                   still to come.  Under the `ascending` flag either leaves lane non-empty at every decision, whatever was drawn before
+ *                   it, if the step ascends strictly: the decode has K notes and the kept ones sit in their slots.
+ *      J <= n < K:  force_pitch = x's pitch.     n = K < 15: force_pitch = 129.     n > K: -1.
+ *      force_dur[d][n*R + t*B + b] = x[b][t][n+1][1+d] where that is 0 or 1 (else -1) for n < K; with bit 0 of flags set only for
+ *      J <= n < K (the durations under the kept notes are drawn).  Every other duration word of the step is -1.
+ *      Bit 0 of err[b]: a slot 1..K of a top step of the sample holds a pitch outside 0..127, or one not above the slot before it.
+ *   any other value: the step is free and bit 1 of err[b] is set.
+ * kept_n int32 [B][32]: h at a top step, the number of forced pitch decisions at a whole step, 0 at a free step.  EVERY element of
+ * force_pitch [15][32B], force_dur [5][480B], kept_n and err [B] is written, by one thread each.  A NULL pointer (but above / highest),
+ * B < 1, a row count outside {1, B} or flags outside 0..3: PTV_ERR_ARG before any launch.
+ * ptv_grid_split_top: the same selection as two model grids, voice and rest int64 [B][32][16][6], as ptv_grid_split_voice's.  A top step:
+ * voice = the h kept notes, <eos>, <pad>; rest = the J notes under them, <eos>, <pad> (rest's notes followed by voice's are x's).  A whole
+ * step: voice = the step, rest = the empty step; a free step the other way round.  kept_n and err as above. */
+#define PTV_FORCE_BELOW(u) (-256 - (u))
+int ptv_keep_top_force_build(const long* x, const unsigned char* mode, int mode_rows, const int* above, int above_rows, const int* highest,
+                             int highest_rows, int flags, long B, int* force_pitch, int* force_dur, int* kept_n, int* err, void* stream);
+int ptv_grid_split_top(const long* x, const unsigned char* mode, int mode_rows, const int* above, int above_rows, const int* highest,
+                       int highest_rows, long B, long* voice, long* rest, int* kept_n, int* err, void* stream);
 int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
                              int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream);
 int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,

@@ -72,7 +72,8 @@ int ptv_debug_pitch_keep(const void* block48, const float* logits, long rows, in
 int ptv_debug_pitch_constrain(const void* block64, const float* logits, const int* masks, const int* lo, long rows, int layout,
                               unsigned char* keep_out, float* thr_out, void* stream);
 /* ... with the force word of each row, words [rows] int32 (ptvae_hip.h "Kept rhythm"): a row whose word is PTV_FORCE_NOT_EOS loses <eos> from its
- * allowed set unless nothing else is allowed, before the threshold is formed; every other word leaves the row what the entry above makes of
+ * allowed set unless nothing else is allowed, before the threshold is formed; a row whose word is PTV_FORCE_BELOW(u) has the allowed set of
+ * "Kept top voice" (the notes under u, above lo under the ascending flag, within the mask unless that leaves none); every other word leaves the row what the entry above makes of
  * it (all words -1: the same bytes).  A NULL words is PTV_ERR_ARG. */
 int ptv_debug_pitch_constrain_words(const void* block64, const float* logits, const int* masks, const int* lo, const int* words, long rows,
                                     int layout, unsigned char* keep_out, float* thr_out, void* stream);

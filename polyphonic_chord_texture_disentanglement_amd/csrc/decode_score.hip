@@ -129,8 +129,8 @@ __global__ void __launch_bounds__(256) decode_logprob_kernel(const float* __rest
       bool outside = false;
       if (Tp > 0.f) {                                                      // (uniform: the block's word)
         float tv[9];
-        // (a kept rhythm: a PTV_FORCE_NOT_EOS decision is free, its support the decoder's -- without <eos>; only the 64-byte kind honours it)
-        const unsigned al = pitch_constrain<9, 16>(v, own, lo, cn.flags, j, tv, blk_bytes >= 64 && fp == PTV_FORCE_NOT_EOS);
+        // (a PTV_FORCE_NOT_EOS or PTV_FORCE_BELOW decision is free, its support the decoder's reduced one; only the 64-byte kind honours the word)
+        const unsigned al = pitch_constrain<9, 16>(v, own, lo, cn.flags, j, tv, blk_bytes >= 64 ? fp : -1);
         const float thr = pitch_keep_threshold<9, 16>(tr, Tp, tv);
         unsigned kept = 0u;
 #pragma unroll

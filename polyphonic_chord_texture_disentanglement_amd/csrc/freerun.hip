@@ -619,7 +619,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (SAMP == 3) {                                             // ... over the ALLOWED classes that reach the threshold of the allowed
           float tv[9];
-          const unsigned al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE && fpw == PTV_FORCE_NOT_EOS);
+          const unsigned al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE ? fpw : -1);
           const float thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
           float gum[9];
           pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
@@ -675,7 +675,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
         float pv[9], tv[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) pv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
-        al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE && fpw == PTV_FORCE_NOT_EOS);
+        al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE ? fpw : -1);
         thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
       } else if constexpr (SAMP == 2) {
         float tv[9];
@@ -1278,7 +1278,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         float pv[9], tv[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) pv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
-        al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE && fpw == PTV_FORCE_NOT_EOS);
+        al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE ? fpw : -1);
         thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
       } else if constexpr (SAMP == 2) {
         float tv[9];

@@ -154,7 +154,7 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
     float best = -INFINITY; int bi = 0x7fffffff;
     [[maybe_unused]] int fw3 = -1;                                 // SAMP = 3: the row's force word (negative: a free decision)
     if constexpr (SAMP == 3) {                                     // constrained: ... over the ALLOWED classes (pitch_constrain, philox.hpp)
-      if (force_pitch) fw3 = force_pitch[r];                       // (before the constrain: PTV_FORCE_NOT_EOS takes <eos> out of the allowed set)
+      if (force_pitch) fw3 = force_pitch[r];                       // (before the constrain: PTV_FORCE_NOT_EOS and PTV_FORCE_BELOW reduce the allowed set)
       const SampleBlockC* q = reinterpret_cast<const SampleBlockC*>(samp);
       const SampleBlock sb = q->s.s;
       const Trunc tr = load_trunc(&q->s);
@@ -170,7 +170,7 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
       float pv[3], tv[3];
 #pragma unroll
       for (int i = 0; i < 3; i++) pv[i] = lane + 64 * i < 130 ? lr[lane + 64 * i] : -INFINITY;
-      const unsigned al = pitch_constrain<3, 64>(pv, mw, lo, cn.flags, lane, tv, fw3 == PTV_FORCE_NOT_EOS);
+      const unsigned al = pitch_constrain<3, 64>(pv, mw, lo, cn.flags, lane, tv, fw3);
       const float thr = pitch_keep_threshold<3, 64>(tr, sb.t_pitch, tv);      // (the whole wave is here: r is uniform over it)
 #pragma unroll
       for (int i = 0; i < 3; i++) {

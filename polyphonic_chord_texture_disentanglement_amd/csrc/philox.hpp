@@ -217,6 +217,7 @@ __device__ __forceinline__ float pitch_keep_threshold(const Trunc tr, float T, c
 // select ends at the -INFINITY key: all of them are kept), and the draw tests the returned bitmap beside the threshold.
 // Kept rhythm: a decision whose force word is PTV_FORCE_NOT_EOS (-2) is free, but <eos> leaves its allowed set unless nothing
 // else is allowed -- inside the allowed rule, so before any truncation.  Only the kernels of this 64-byte kind honour the word.
+// Kept top voice: a word PTV_FORCE_BELOW(u) is free, never <eos>, and a note under the ceiling u -- same place, same kernels.
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct SampleBlockC {
   SampleBlockT s;
@@ -258,12 +259,16 @@ __device__ __forceinline__ int pitch_lo_next(int lo, int decision) { return deci
 // own: pitch_mask_own() of the row's mask words; lo, flags as above (flags is uniform over the block: a scalar branch).
 // tv: v with the disallowed classes (and the columns >= 130) at -INFINITY -- the input of pitch_keep_threshold(); returns the bitmap of the
 // lane's allowed columns: the draw takes column i iff bit i is set and v[i] >= the threshold.
-// no_eos (a kept rhythm: the decision's force word is PTV_FORCE_NOT_EOS; uniform over the W lanes of the row, it may differ between the rows
-// of a wave): <eos> (129) leaves the allowed set iff another class is allowed -- one integer sum over the row, which every lane takes
-// whatever its flag, so nothing diverges around it; a caller that leaves the argument out compiles to what it did without it.
+// word: the decision's force word (uniform over the W lanes of the row, it may differ between the rows of a wave); a caller that leaves it
+// out compiles to what it did without it.  Two families of it change the set, every other value (a forced class included) does not:
+//   PTV_FORCE_NOT_EOS (-2, a kept rhythm): <eos> (129) leaves the allowed set iff another class is allowed.
+//   PTV_FORCE_BELOW(u) = -256 - u, u in 1..128 (a kept top voice): lane = the notes c < u (under CONS_ASCENDING also c > lo);
+//     the allowed set is lane & mask; if that is empty it is lane (the mask yields); if lane is empty it is <eos> alone.
+// The three counts these need -- the allowed classes beside <eos>, lane & mask, lane: each <= 130 -- travel as three bytes of ONE integer
+// sum over the row, which every lane takes whatever its word, so nothing diverges around it.
 template <int NV, int W>
 __device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], unsigned own, int lo, unsigned flags, int j, float (&tv)[NV],
-                                                    bool no_eos = false) {
+                                                    int word = -1) {
   unsigned al = own;
   if (flags & CONS_ASCENDING) {
 #pragma unroll
@@ -276,8 +281,20 @@ __device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], unsign
     constexpr int EI = 129 / W, EJ = 129 % W;                      // <eos> is column EJ + W * EI: bit EI of lane EJ
     static_assert(EI < NV, "the row holds column 129");
     const unsigned eos_bit = j == EJ ? 1u << EI : 0u;
-    const int others = row_sum<W>(__popc(al & ~eos_bit));
-    if (no_eos && others > 0) al &= ~eos_bit;
+    const bool no_eos = word == -2;                                // PTV_FORCE_NOT_EOS
+    const int u = -256 - word;                                     // the ceiling of PTV_FORCE_BELOW(u)
+    const bool below = u >= 1 && u <= 128;
+    const int lo_u = (flags & CONS_ASCENDING) ? lo : -1;
+    unsigned lane = 0u;
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+      const int c = j + W * i;
+      if (below && c < u && c > lo_u) lane |= 1u << i;             // (u <= 128: a note)
+    }
+    const int sums = row_sum<W>(__popc(al & ~eos_bit) | (__popc(al & lane) << 8) | (__popc(lane) << 16));
+    const int others = sums & 0xff, in_mask = (sums >> 8) & 0xff, in_lane = sums >> 16;
+    if (below) al = in_mask > 0 ? (al & lane) : (in_lane > 0 ? lane : eos_bit);
+    else if (no_eos && others > 0) al &= ~eos_bit;
   }
 #pragma unroll
   for (int i = 0; i < NV; i++) tv[i] = (al >> i) & 1u ? v[i] : -INFINITY;
@@ -286,8 +303,8 @@ __device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], unsign
 // ... from the row's four mask words (the step loop and the debug entry, which see a row once)
 template <int NV, int W>
 __device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], const unsigned (&m)[4], int lo, unsigned flags, int j, float (&tv)[NV],
-                                                    bool no_eos = false) {
-  return pitch_constrain<NV, W>(v, pitch_mask_own<NV, W>(m, j), lo, flags, j, tv, no_eos);
+                                                    int word = -1) {
+  return pitch_constrain<NV, W>(v, pitch_mask_own<NV, W>(m, j), lo, flags, j, tv, word);
 }
 
 }  // namespace ptv

@@ -102,8 +102,8 @@ __global__ void pitch_constrain_kernel(const SampleBlockC* __restrict__ blk, con
     unsigned mw[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) mw[i] = (unsigned)masks[r * 4 + i];
-    const bool no_eos = words && words[r] == PTV_FORCE_NOT_EOS;    // (words: the force word of each row, NULL = every decision plainly free)
-    const unsigned al = pitch_constrain<NV, W>(v, mw, lo[r], flags, j, tv, no_eos);
+    const int word = words ? words[r] : -1;                        // (words: the force word of each row, NULL = every decision plainly free)
+    const unsigned al = pitch_constrain<NV, W>(v, mw, lo[r], flags, j, tv, word);
     const float thr = pitch_keep_threshold<NV, W>(tr, T, tv);
     if (ok) {
 #pragma unroll

@@ -371,6 +371,87 @@ def build_keep_rhythm(x, steps, durations=True, whole_steps=None, return_counts=
     return (keep, kept_n) if return_counts else keep
 
 
+FORCE_BELOW_BASE = -256     # PTV_FORCE_BELOW(u) = FORCE_BELOW_BASE - u, u in 1..128: a free pitch word, never <eos>, a note under the ceiling u
+
+
+class TopKeep(Keep):
+    """a Keep whose pitch array holds FORCE_BELOW words under the kept top notes (ptv_keep_top_force_build; INTEGRATION.md "Kept top
+    voice"): the same four fields, so it goes wherever a Keep goes -- but only the constrained kernels honour the words and the ceilings
+    leave room only for notes that ascend, so a decode with one is always sent as the constrained kind with ascending=True
+    (DisentangleVAE._sampling_words), and PtvaeDecoder refuses it beside any other block"""
+    __slots__ = ()
+
+
+def _top_selection(x, top_steps, above, highest, whole_steps):
+    """the arguments both kept-top entry points share, validated as _voice_selection's -- every ValueError before any launch -- and then
+    put on the device: -> (x contiguous, mode uint8 [rows, 32] (4 = top step, 1 = whole step: a step in both selections is a whole
+    step), above, highest: int32 [rows, 32] or None = no limit; both None: the very top note)"""
+    limits = [above, highest]
+    for name, v, top in (('above', above, 128), ('highest', highest, 15)):
+        if v is not None and not torch.is_tensor(v) and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top):
+            raise ValueError('%s must be an integer in 0..%d or an int32 device tensor [B, 32] / [1, 32], got %r' % (name, top, v))
+    sels = [s if s is None or torch.is_tensor(s) else keep_steps_row(s) for s in (top_steps, whole_steps)]
+    if sels[0] is None:
+        raise ValueError('top_steps must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice')
+    _check_grid(x)
+    B = x.shape[0]
+    _check_step_selections(x, (('top_steps', sels[0]), ('whole_steps', sels[1])))
+    for name, v in (('above', limits[0]), ('highest', limits[1])):
+        if torch.is_tensor(v):
+            if v.device != x.device or v.dtype != torch.int32:
+                raise ValueError('%s must be int32 on the device of x, got %s on %s' % (name, v.dtype, v.device))
+            if v.dim() != 2 or v.shape[1] != 32 or v.shape[0] not in (1, B):
+                raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(v.shape)))
+    # ---- nothing below raises
+    mode = _mode_bytes(x, sels[0], sels[1], 4)
+    limits = [v.contiguous() if torch.is_tensor(v) else (None if v is None else torch.full((1, 32), v, dtype=torch.int32, device=x.device))
+              for v in limits]
+    return x.contiguous(), mode, limits[0], limits[1]
+
+
+def build_keep_top(x, top_steps, above=None, highest=None, durations=True, lanes=True, whole_steps=None, return_counts=False):
+    """the kept TOP VOICE of a free-running decode -> TopKeep (ptv_keep_top_force_build; INTEGRATION.md "Kept top voice"): at the steps of
+    top_steps the highest notes of x's step -- those at or over pitch `above`, at most `highest` of them, a suffix of the step; neither
+    given: the very top note -- are forced in their slots, the step keeps its note count, and the notes under them are drawn again, each
+    under a ceiling: x's next note (lanes=True: no voice crosses its old neighbour) or the lowest kept pitch less a semitone per decision
+    still to come (lanes=False).  durations: True = x's bits for every note of the step, 'kept' = only for the kept notes, False = every
+    duration of a top step is drawn.  The steps of whole_steps are kept whole as by build_keep (a step in both is a whole step).
+    Selections as build_keep's steps; above / highest: a host int (0..128 / 0..15) or an int32 device tensor [B, 32] / [1, 32].
+    return_counts: -> (TopKeep, kept_n int32 [B, 32]: the kept notes of a top step, the forced pitch decisions of a whole step).
+    ValueError before any launch; nothing is copied to the host."""
+    if not (isinstance(durations, bool) or (isinstance(durations, str) and durations == 'kept')):
+        raise ValueError("durations must be True, 'kept' or False, got %r" % (durations,))
+    if not isinstance(lanes, bool):
+        raise ValueError('lanes must be a bool, got %r' % (lanes,))
+    x, mode, above, highest = _top_selection(x, top_steps, above, highest, whole_steps)
+    B = x.shape[0]
+    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=x.device)
+    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=x.device)
+    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
+    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    call('ptv_keep_top_force_build', ptr(x), ptr(mode), mode.shape[0], ptr(above), 1 if above is None else above.shape[0], ptr(highest),
+         1 if highest is None else highest.shape[0], (0 if durations is True else 1) | (0 if lanes else 2), B, ptr(pitch), ptr(dur),
+         ptr(kept_n), ptr(err), stream_ptr())
+    if durations is False:                                     # every duration word of a top step is free: the [t, b] rows of mode 4
+        top = (mode == 4).expand(B, 32).t().reshape(1, 1, 32 * B)
+        dur = dur.view(5, 15, 32 * B).masked_fill(top, -1).view(5, 480 * B)
+    keep = TopKeep(pitch, dur, err, B)
+    return (keep, kept_n) if return_counts else keep
+
+
+def split_top(x, top_steps, above=None, highest=None, whole_steps=None):
+    """the selection of build_keep_top as two model grids (ptv_grid_split_top) -> (x_top, x_rest int64 [B, 32, 16, 6], kept_n int32
+    [B, 32], err int32 [B]): per step the kept top notes and what the decoder would re-draw under them, each a valid step"""
+    x, mode, above, highest = _top_selection(x, top_steps, above, highest, whole_steps)
+    B = x.shape[0]
+    voice, rest = torch.empty_like(x), torch.empty_like(x)
+    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
+    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    call('ptv_grid_split_top', ptr(x), ptr(mode), mode.shape[0], ptr(above), 1 if above is None else above.shape[0], ptr(highest),
+         1 if highest is None else highest.shape[0], B, ptr(voice), ptr(rest), ptr(kept_n), ptr(err), stream_ptr())
+    return voice, rest, kept_n, err
+
+
 def split_voice(x, voice_steps, below=None, lowest=None, whole_steps=None):
     """the selection of build_keep_voice as two model grids (ptv_grid_split_voice) -> (x_voice, x_rest int64 [B, 32, 16, 6], kept_n int32
     [B, 32], err int32 [B]): per step the kept notes and what the decoder would re-draw, each a valid step"""
@@ -438,18 +519,21 @@ def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sa
 
 def make_block(words, pitch_mask, device):
     """validated host words (sampling_words) and the contiguous mask their last word points at -> the device block; the eight-word form
-    gets the mask as its attribute"""
+    gets the mask as its attribute, and its ascending flag as the host bool `ascending`"""
     blk = torch.tensor(words, dtype=torch.int64, device=device)
     if len(words) == CONSTRAINED.words:
         blk.pitch_mask = pitch_mask
+        blk.ascending = bool(words[6] & 1)
     return blk
 
 
 def clone_block(blk, pitch_mask=None):
-    """a copy of a block (clone() alone drops the attribute); an eight-word copy carries `pitch_mask`, or the original's when none is given"""
+    """a copy of a block (clone() alone drops the attributes); an eight-word copy carries `pitch_mask`, or the original's when none is
+    given, and `ascending`"""
     out = blk.clone()
     if hasattr(blk, 'pitch_mask'):
         out.pitch_mask = blk.pitch_mask if pitch_mask is None else pitch_mask
+        out.ascending = getattr(blk, 'ascending', False)
     return out
 
 

@@ -13,8 +13,9 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import (Keep, RhythmKeep, build_chord_keep, build_keep, build_keep_rhythm, build_keep_voice, check_chord_keep,
-                              check_chord_sampling, check_constraints, check_keep, check_sampling, make_block, sampling_words, split_voice)
+from .functional_free import (Keep, RhythmKeep, TopKeep, build_chord_keep, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice,
+                              check_chord_keep, check_chord_sampling, check_constraints, check_keep, check_sampling, make_block,
+                              sampling_words, split_top, split_voice)
 from .optim import refresh_weight_shadows
 from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
@@ -411,8 +412,11 @@ class DisentangleVAE(PytorchModel):
 
     def _request(self, batch, **sampling):
         """the keywords of a decode of `batch` rows, validated once -> DecodeRequest.  _check_sampling's ValueErrors, and what only this
-        model knows: kept steps and the decoder's replay mode exclude each other.  Before anything is encoded or launched, and before the
-        draw counter moves."""
+        model knows: kept steps and the decoder's replay mode exclude each other, and a kept top voice needs ascending notes.  Before
+        anything is encoded or launched, and before the draw counter moves."""
+        if isinstance(sampling.get('keep'), TopKeep) and sampling.get('ascending') is False:
+            raise ValueError('a TopKeep needs ascending notes: its ceilings leave room only for notes that ascend -- leave ascending out '
+                             '(it becomes True) or give ascending=True')
         sampled = self._check_sampling(**sampling, batch=batch)
         keep, mask = sampling.get('keep'), sampling.get('pitch_mask')
         if keep is not None and self.decoder.force_trace is not None:
@@ -422,11 +426,14 @@ class DisentangleVAE(PytorchModel):
     def _sampling_words(self, req):
         """None (argmax decode) or the request's sampling block as host words (keep puts nothing into the block: it travels beside it);
         a sampled decode that names no draw takes the model's counter and advances it.  A rhythm keep promotes the decode to the constrained
-        kind, whose kernels alone honour its words: an `ascending` nobody gave becomes False, the vacuous constraint (flags 0, no mask)"""
+        kind, whose kernels alone honour its words: an `ascending` nobody gave becomes False, the vacuous constraint (flags 0, no mask).  A
+        top keep does the same with True: its ceilings count on notes that ascend (_request has refused ascending=False)"""
         kw = req.kw
         ascending = kw['ascending']
         if ascending is None and isinstance(req.keep, RhythmKeep):
             ascending = False
+        if ascending is None and isinstance(req.keep, TopKeep):
+            ascending = True
         if not req.sampled:
             if req.mask is None and ascending is None:
                 return None
@@ -486,6 +493,29 @@ class DisentangleVAE(PytorchModel):
         rhythm step still counts the slot); bit 1: a mode byte that is none of 0 / 1 / 3 (never from here).  return_counts=True: ->
         (RhythmKeep, kept_n int32 [B, 32]).  Nothing is copied to the host."""
         return build_keep_rhythm(x, steps, durations, whole_steps, return_counts)
+
+    def keep_top(self, x, top_steps, above=None, highest=None, durations=True, lanes=True, whole_steps=None, return_counts=False):
+        """The kept top voice of a decode -> functional_free.TopKeep for keep= (ptv_keep_top_force_build; INTEGRATION.md "Kept top voice").
+        x: the grid as in keep(); top_steps / whole_steps: selections as keep()'s steps.  At a top step the HIGHEST notes of x's step are
+        forced in their slots -- the notes at or over pitch `above` (0..128), at most `highest` of them (0..15), a suffix of the step;
+        neither given: the very top note -- the step keeps its note count K (decision K is a forced <eos>), and the notes under the kept
+        ones are drawn again under whatever the decode is given.  Each of them is free, never <eos>, above the note before it and under a
+        ceiling: x's next note (lanes=True: every voice stays between its old neighbours) or the lowest kept pitch less one semitone per
+        decision still to come (lanes=False).  Where a pitch_mask leaves no note in that lane the mask yields for that decision; the count
+        and the kept notes never do.  durations: True = x's bits for every note, 'kept' = for the kept notes only, False = all drawn.
+        A whole step is kept as by keep(); a step in both selections is a whole step.  A decode with this keep always runs the
+        constrained kernels with ascending=True (ascending=False is a ValueError).  above / highest: a host int or an int32 device tensor
+        [B, 32] / [1, 32].  err[b] bit 0: a top step of sample b held a pitch that is no note before its <eos>, or notes that do not
+        ascend strictly (a lane may then be empty and the step end short); bit 1: a mode byte that is none of 0 / 1 / 4 (never from
+        here).  return_counts=True: -> (TopKeep, kept_n int32 [B, 32]).  Nothing is copied to the host."""
+        return build_keep_top(x, top_steps, above, highest, durations, lanes, whole_steps, return_counts)
+
+    def split_top(self, x, top_steps, above=None, highest=None, whole_steps=None):
+        """The selection of keep_top as two grids -> (x_top, x_rest, kept_n, err) (ptv_grid_split_top), the mirror of split_voice: x_top
+        holds per step the notes keep_top forces (a top step: the kept notes and an <eos>; a whole step: the step; a free step: the empty
+        step), x_rest the notes under them; x_rest's notes followed by x_top's are x's.  Split x and a decode that kept its top with the
+        same arguments to compare the re-drawn lower voices with the original ones.  Nothing is copied to the host."""
+        return split_top(x, top_steps, above, highest, whole_steps)
 
     def split_voice(self, x, voice_steps, below=None, lowest=None, whole_steps=None):
         """The selection of keep_voice as two grids -> (x_voice, x_rest, kept_n, err) (ptv_grid_split_voice): x_voice holds per step the

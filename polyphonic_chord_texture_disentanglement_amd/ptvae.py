@@ -437,6 +437,10 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             if isinstance(keep, FF_.RhythmKeep) and not (sampling is not None and torch.is_tensor(sampling) and FF_.block_kind(sampling).cons):
                 raise ValueError('a RhythmKeep needs a constrained block (functional_free.sampling_block(..., ascending=False) at least): '
                                  'only the constrained kernels honour its words')
+            if isinstance(keep, FF_.TopKeep) and not (sampling is not None and torch.is_tensor(sampling) and FF_.block_kind(sampling).cons
+                                                      and getattr(sampling, 'ascending', False)):
+                raise ValueError('a TopKeep needs a constrained block with the ascending flag (functional_free.sampling_block(..., '
+                                 'ascending=True)): only the constrained kernels honour its words, and its ceilings count on ascending notes')
             if self.force_trace is not None:
                 raise ValueError('keep cannot be combined with force_trace: both fill the force arrays')
         _require_cuda(z, 'PtvaeDecoder')

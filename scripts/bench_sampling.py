@@ -12,6 +12,9 @@ ascending + top_k + top_p; each is reported against the same setting without a k
 The rhythm rows (kept rhythm, DisentangleVAE.keep_rhythm: every step of the same grid keeps its note count and durations, the pitches are
 drawn again) run under plain sampling -- sent as the constrained kind with a block that constrains nothing, as the model sends it -- and
 under mask + ascending + top_k + top_p; each beside the same setting without a keep.
+The top rows (kept top voice, DisentangleVAE.keep_top: every step of the same grid keeps its top note and its note count, the notes under it
+are drawn again under their ceilings) run under plain sampling -- sent as the constrained kind with the ascending flag, as the model sends
+it, and reported beside `ascending` -- and under mask + ascending + top_k + top_p, beside the same setting without a keep.
 The logprob rows (--logprob 1; PtvaeDecoder.decode_logprob, DisentangleVAE.decode_best_of) time the log-probability pass ALONE -- the two
 launches after a plain sampled decode, and after the mask + ascending + top_k + top_p decode, where every row also runs the allowed rule
 and both 32-round selects -- and decode_best_of(n=4) at a quarter of the batch (as many decoded rows as one plain decode of the batch).
@@ -84,6 +87,9 @@ def main():
         keeps['keep rhythm'] = ('sampled', m.keep_rhythm(x, range(32)))
         if a.constrained:
             keeps['keep rhythm+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.keep_rhythm(x, range(32)))
+        keeps['keep top'] = ('ascending' if a.constrained else 'sampled', m.keep_top(x, range(32)))
+        if a.constrained:
+            keeps['keep top+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.keep_top(x, range(32)))
     kinds += list(keeps)
     blocks = {'argmax': [None] * (a.rounds + 1),
               'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
@@ -97,6 +103,8 @@ def main():
         blocks[k] = blocks[base]
     if 'keep rhythm' in keeps:                               # a rhythm keep needs the constrained kind: the vacuous constraint
         blocks['keep rhythm'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=False) for d in range(a.rounds + 1)]
+    if 'keep top' in keeps:                                  # a top keep needs the constrained kind with the ascending flag
+        blocks['keep top'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=True) for d in range(a.rounds + 1)]
 
     def run(block, keep=None):
         with torch.no_grad():
