@@ -1207,6 +1207,47 @@ int ptv_keep_top_force_build(const long* x, const unsigned char* mode, int mode_
                              int highest_rows, int flags, long B, int* force_pitch, int* force_dur, int* kept_n, int* err, void* stream);
 int ptv_grid_split_top(const long* x, const unsigned char* mode, int mode_rows, const int* above, int above_rows, const int* highest,
                        int highest_rows, long B, long* voice, long* rest, int* kept_n, int* err, void* stream);
+/* Duration limits: a decode whose notes have durations in a range per (sample, time step) -- "nothing longer than a beat", "nothing shorter
+ * than an eighth", "no note across the bar line" -- while the decoder still chooses inside the range and feeds its choice back
+ * (csrc/dur_limits.hip, csrc/philox.hpp; INTEGRATION.md "Duration limits").
+ * A note's duration is D = v + 1, v the 5-bit value of its duration bits, bit 0 the most significant.
+ * PTV_FORCE_DUR_RANGE(lo, hi) = -1024 - (lo | hi << 5), 0 <= lo <= hi <= 31 (the words -1024..-2047 of force_dur): the decision is FREE and
+ *   v ends in [lo, hi].  It is negative, so every "forced?" test answers as before; -1 and every other negative word stay plainly free.
+ *   ALL FIVE planes of one decision (n, row) hold the same word.  The rule of bit d, with p = the value of the bits 0..d-1 decided for the
+ *   note: value b is allowed iff [q << (4-d), (q << (4-d)) + (1 << (4-d)) - 1], q = 2p + b, meets [lo, hi].
+ *     one value allowed:  that is the decision; its noise words stay unused.
+ *     both allowed:       the decision is what it is without the word: the first maximum of logit + T_dur * g, same noise words.
+ *     neither allowed:    (forced bits mixed into the decision) the bit is plainly free.  A hand-made word with lo > hi is no range word.
+ *   A word >= 0 overrides everything.  The logits stored are the plain logits.  The draw is the model's own bit-by-bit chain with the
+ *   infeasible branches removed -- NOT the joint distribution of the 32 durations renormalised over the range.
+ *   ONLY the constrained kind honours the word, at the duration decisions of the SAMP = 3, FORCE = 1 note loops,
+ *   ptv_dur_gru_fwd_sample_cons / ptv_dur_out_token_sample_cons (the constrained step loop with force arrays) and ptv_decode_logprob;
+ *   anywhere else it is a free decision like -1.  ptv_decode_logprob (64-byte block): a bit the word determines adds its model
+ *   log-probability to log p, 0 to log q, and counts with the forced decisions (a decided value the range excludes sets bit 0 of err); a
+ *   bit with both values allowed is a free decision as ever.
+ * ptv_dur_range_force_build: the force arrays.  lo / hi: uint8 [rows][32] in DURATIONS 1..32 (rows = 1 or B, each its own), steps: uint8
+ *   [steps_rows][32], non-zero = the limits apply at that (b, t).  Per (b, t): H = hi clamped into 1..32, F = max(lo, 1), L = min(F, H) --
+ *   the ceiling wins -- and yielded[b][t] (int32 [B][32]) = 1 iff the step is selected and F > H, else 0.
+ *   src_pitch / src_dur: the arrays of an existing keep to build INTO, or both NULL (= every word -1); they may not be the outputs.
+ *   force_pitch [15][32B] = src_pitch.  For each of the 15 decisions (n, t*B + b) of a selected step whose five words of src_dur are ALL
+ *   negative, all five planes of force_dur [5][480B] get PTV_FORCE_DUR_RANGE(L - 1, H - 1) (a range word already there is replaced); every
+ *   other word is src_dur's, bit for bit.  EVERY element of the three outputs is written, by one thread each.  A NULL pointer (but the
+ *   src pair), one of the pair alone, an output that is its source, B < 1 or a row count outside {1, B}: PTV_ERR_ARG before any launch. */
+#define PTV_FORCE_DUR_RANGE(lo, hi) (-1024 - ((lo) | (hi) << 5))
+int ptv_dur_range_force_build(const unsigned char* lo, int lo_rows, const unsigned char* hi, int hi_rows, const unsigned char* steps,
+                              int steps_rows, const int* src_pitch, const int* src_dur, long B, int* force_pitch, int* force_dur, int* yielded,
+                              void* stream);
+/* the duration entries of the constrained step loop with force arrays: as the two below, and a word PTV_FORCE_DUR_RANGE of force / force_idx
+ * limits the note.  ptv_dur_out_token_sample_cons: idx is plane d of the decisions, the planes of the bits before it lie idx_stride words
+ * apart below it (idx - k * idx_stride, k = 1..d, written by the calls before).  idx and the force array must be given. */
+int ptv_dur_out_token_sample_cons(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
+                                  int* idx, long idx_stride, const int* force_idx, long rows, const void* sample, int t, int n, int d,
+                                  void* stream);
+int ptv_dur_gru_fwd_sample_cons(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,
+                                const float* tab0, const float* tab, const float* w_out, const float* b_out,
+                                float* hall, long plane_h, void* hall16, void* gates, long plane_g, long step_g, int gates_bf16,
+                                float* dur_out, long ld_out, int* idx, long idx_stride, const int* force, long force_stride,
+                                const void* sample, int t, int n, void* stream);
 int ptv_dur_out_token_sample(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
                              int* idx, const int* force_idx, long rows, const void* sample, int t, int n, int d, void* stream);
 int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,

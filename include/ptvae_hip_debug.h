@@ -78,6 +78,12 @@ int ptv_debug_pitch_constrain(const void* block64, const float* logits, const in
 int ptv_debug_pitch_constrain_words(const void* block64, const float* logits, const int* masks, const int* lo, const int* words, long rows,
                                     int layout, unsigned char* keep_out, float* thr_out, void* stream);
 
+/* test aid of the duration limits (ptvae_hip.h "Duration limits"): the decoder's own rule (csrc/philox.hpp dur_range_allowed /
+ * dur_range_bit) on caller-supplied triples, words / d / prefix int32 [rows]: out [rows] uint8 -- bit 0 / bit 1: value 0 / 1 of duration bit
+ * d is allowed after the prefix (a word that is no range word allows both), bit 2 / bit 3: the decision the rule makes of a decided 0 / a
+ * decided 1.  0xff for a d outside 0..4 or a prefix outside 0..2^d - 1. */
+int ptv_debug_dur_range(const int* words, const int* d, const int* prefix, long rows, unsigned char* out, void* stream);
+
 /* test aid of the chord decode (ptvae_hip.h "Row-independent free-running chord decode"): the Gumbel values ptv_chord_decide uses for rows
  * [0, rows) -- samples sample_offset + row of the 32-byte block -- at chord step t, through the device function that kernel calls:
  * out [rows, 12, 4], lane j's four values in word order (root class j, bass class j, class 0 and class 1 of chroma bit j) */

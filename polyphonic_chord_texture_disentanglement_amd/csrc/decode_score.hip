@@ -152,6 +152,11 @@ __global__ void __launch_bounds__(256) decode_logprob_kernel(const float* __rest
       // ---- duration bit j of the note: two classes
       const int dt = (note && j < 5) ? (int)xs[(n + 1) * 6 + 1 + j] : 2;
       const bool dlive = dt == 0 || dt == 1;
+      // (duration limits: the value of the note's bits before bit j, from the ones of the row's lanes 0..j-1 -- every lane takes the ballot)
+      const unsigned ones = (unsigned)(__ballot(dt == 1) >> (lane & 48)) & 31u;
+      int dpre = 0;
+#pragma unroll
+      for (int q = 0; q < 4; q++) if (q < j) dpre = 2 * dpre + (int)((ones >> q) & 1u);
       float lpd = 0.f, lqd = 0.f;
       bool dforced = false;
       if (dlive) {
@@ -159,7 +164,14 @@ __global__ void __launch_bounds__(256) decode_logprob_kernel(const float* __rest
         const float l0 = dr[0], l1 = dr[1];
         const float dm = fmaxf(l0, l1);
         lpd = (dt ? l1 : l0) - dm - logf(expf(l0 - dm) + expf(l1 - dm));
-        dforced = force_dur && force_dur[(long)j * M + fr] >= 0;
+        const int fdw = force_dur ? force_dur[(long)j * M + fr] : -1;
+        dforced = fdw >= 0;
+        // a PTV_FORCE_DUR_RANGE word (only the 64-byte kind honours it): a bit the range determines is no draw -- log p as ever, log q 0,
+        // counted with the forced decisions; a decided value the range excludes sets bit 0 of err.  Both values allowed: a free decision
+        if (!dforced && blk_bytes >= 64) {
+          const unsigned dal = dur_range_allowed(fdw, j, dpre);
+          if (dal == 1u || dal == 2u) { dforced = true; if (dal != (1u << dt)) outside = true; }
+        }
         if (!dforced && Td > 0.f) {
           const float a0_ = l0 / Td, a1_ = l1 / Td, am = fmaxf(a0_, a1_);
           lqd = (dt ? a1_ : a0_) - am - logf(expf(a0_ - am) + expf(a1_ - am));

@@ -50,10 +50,10 @@ struct DurArgs {
   const int* m_top; long m_unit;       // or null: only the rows below (*m_top + 1) * m_unit are wanted; the others stay unwritten
   const int* row_len;                  // or null (needs m_top): rows of a step sorted by descending length, [m_unit] live note steps per row -- a
                                        // tile inside a 128-row block whose first row has no target at its note step is passed over
-  const SampleBlock* samp; int t, n;   // SAMP = 1: row r is sample r at (t, n), the five decisions are draws (philox.hpp)
+  const SampleBlock* samp; int t, n;   // SAMP >= 1: row r is sample r at (t, n), the five decisions are draws (philox.hpp)
 };
 
-template <int SAMP>
+template <int SAMP>                    // SAMP = 2: the constrained kind's -- a negative force word may be a duration range word (philox.hpp)
 __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
   __builtin_amdgcn_s_setprio(3);                                         // a launch of the latency chain: wins instruction issue against sibling-stream products
   __shared__ __attribute__((aligned(16))) __bf16 Ws[3 * DH * DLD];       // W_hh as bf16
@@ -96,6 +96,7 @@ __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
       h[f][0] = v.x; h[f][1] = v.y; h[f][2] = v.z; h[f][3] = v.w;
     }
     int tok = 0;                                                        // table row: 0 = sos, 1 + idx afterwards
+    [[maybe_unused]] int pre = 0;                                       // SAMP = 2: the value of the row's bits so far
 #pragma unroll 1
     for (int d = 0; d < 5; d++) {
       // state -> LDS (bf16) as the MFMA operand
@@ -166,13 +167,18 @@ __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
         x0 = perturbed(o0, sb.t_dur, g0); x1 = perturbed(o1, sb.t_dur, g1);
       }
       int id = x1 > x0 ? 1 : 0;                                           // first max wins ties (torch.max)
-      if (a.force && ok) { const int fw = a.force[d * a.force_stride + row]; id = fw >= 0 ? fw : id; }   // (negative: a free decision)
+      if (a.force && ok) {
+        const int fw = a.force[d * a.force_stride + row];
+        if constexpr (SAMP == 2) id = dur_range_bit(fw, d, pre, id);
+        id = fw >= 0 ? fw : id;                                           // (negative: a free decision)
+      }
       if (ok && lane < 16) {
         a.dur_out[row * a.ld_out + 2 * d] = o0;
         a.dur_out[row * a.ld_out + 2 * d + 1] = o1;
         a.idx[d * a.idx_stride + row] = id;
       }
       tok = 1 + id;
+      if constexpr (SAMP == 2) pre = 2 * pre + id;
     }
   }
 }
@@ -243,6 +249,26 @@ extern "C" int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0
   const int cap = 3 * num_cus();
   long nb = ((M + 15) / 16 + 3) / 4; if (nb > cap) nb = cap; if (nb < 1) nb = 1;
   hipLaunchKernelGGL(dur_gru_fwd_kernel<1>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// ... of the CONSTRAINED step loop with force words: a word PTV_FORCE_DUR_RANGE(lo, hi) of `force` limits the note's duration
+// (dur_range_bit, philox.hpp); everything else as above.  force must be given.
+extern "C" int ptv_dur_gru_fwd_sample_cons(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,
+                                           const float* tab0, const float* tab, const float* w_out, const float* b_out,
+                                           float* hall, long plane_h, void* hall16, void* gates, long plane_g, long step_g, int gates_bf16,
+                                           float* dur_out, long ld_out, int* idx, long idx_stride, const int* force, long force_stride,
+                                           const void* sample, int t, int n, void* stream) {
+  if (H != DH) return PTV_ERR_ARG;
+  if (M <= 0 || !h0 || !w_hh || !b_hh || !tab0 || !tab || !w_out || !b_out || !dur_out || !idx || !force) return PTV_ERR_ARG;
+  if ((ld_h0 & 3) || (plane_h & 7) || (plane_g & 7) || (step_g & 7)) return PTV_ERR_ARG;
+  if (!sample || t < 0 || t >= 32 || n < 0 || n >= 15) return PTV_ERR_ARG;
+  DurArgs a{h0, ld_h0, w_hh, b_hh, tab0, tab, w_out, b_out, hall, plane_h, (__bf16*)hall16, gates, plane_g, step_g, gates_bf16,
+            dur_out, ld_out, idx, idx_stride, force, force_stride, M, nullptr, 0, nullptr, (const SampleBlock*)sample, t, n};
+  const int cap = 3 * num_cus();
+  long nb = ((M + 15) / 16 + 3) / 4; if (nb > cap) nb = cap; if (nb < 1) nb = 1;
+  hipLaunchKernelGGL(dur_gru_fwd_kernel<2>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

@@ -785,15 +785,18 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           for (int i = 0; i < 10; i++) dn[i] = sb.t_dur * gum[i];
         }
         int dtk = 0;                                                           // this lane's row: 0 = <sos>, 1 + previous decision
+        [[maybe_unused]] int dpx = 0;                                          // ... and the value of its bits so far (duration range words)
         auto decide = [&](int d) {                                             // logits and decision of duration step d from the four waves' partial sums
           const float e0 = q[0].x + q[1].x + q[2].x + q[3].x + wb0;
           const float e1 = q[0].y + q[1].y + q[2].y + q[3].y + wb1;
           float x0 = e0, x1 = e1;
           if constexpr (SAMP) { x0 = e0 + dn[2 * d]; x1 = e1 + dn[2 * d + 1]; }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
+          if constexpr (SAMP == 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
           if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
           else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
+          if constexpr (SAMP == 3 && FORCE) dpx = 2 * dpx + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
               a.dur[prC * 10 + 2 * d] = e0; a.dur[prC * 10 + 2 * d + 1] = e1;
@@ -863,6 +866,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
       const long prC = (long)n * R + wrowC;
       const int u = wave * 16 + ckq * 4;
       int dtk = 0;                                                             // this lane's row: 0 = <sos>, 1 + previous decision
+      [[maybe_unused]] int dpx = 0;                                            // ... and the value of its bits so far (duration range words)
 #pragma unroll 1
       for (int d = 0; d < ((a.dbg & 8) ? 0 : 5); d++) {
         const int dc = d & 1, dn = dc ^ 1;
@@ -930,9 +934,11 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
             x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
           }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
+          if constexpr (SAMP == 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
           if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
           else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
+          if constexpr (SAMP == 3 && FORCE) dpx = 2 * dpx + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
               a.dur[prC * 10 + 2 * d] = e0; a.dur[prC * 10 + 2 * d + 1] = e1;
@@ -1215,6 +1221,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
     }
   } else {
     // the decision of duration step d for `row` from the four waves' partial sums (complete after that step's barrier)
+    // (SAMP = 3, FORCE: a duration range word needs the value of the row's bits 0..d-1 -- formed here from bits[], which holds them)
     auto dur_decision = [&](int n, int d, int row, long pr, int fw) {   // fw: the force word of (d, row), prefetched (FORCE)
       const int dc = d & 1;
       const float e0 = part[dc][0][row][0] + part[dc][1][row][0] + part[dc][2][row][0] + part[dc][3][row][0] + wo[2 * FHD];
@@ -1226,6 +1233,11 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
       }
       int id = x1 > x0 ? 1 : 0;
+      if constexpr (SAMP == 3 && FORCE) {
+        int p = 0;
+        for (int k = 0; k < d; k++) p = 2 * p + bits[row][k];
+        id = dur_range_bit(fw, d, p, id);
+      }
       if constexpr (FORCE) id = forced(fw, id);
       else if (a.force_dur) id = forced(a.force_dur[(long)d * M + pr], id);
       return id;
@@ -1331,6 +1343,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       const long prC = (long)n * R + wrowC;
       const int u = wave * 16 + ckq * 4;
       int dtk = 0;                                                             // this lane's row: 0 = <sos>, 1 + previous decision
+      [[maybe_unused]] int dpx = 0;                                            // ... and the value of its bits so far (duration range words)
 #pragma unroll 1
       for (int d = 0; d < 5; d++) {
         const int dc = d & 1, dn = dc ^ 1;
@@ -1385,9 +1398,11 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
             x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
           }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
+          if constexpr (SAMP == 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
           if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
           else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
+          if constexpr (SAMP == 3 && FORCE) dpx = 2 * dpx + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
               a.dur[prC * 10 + 2 * d] = e0; a.dur[prC * 10 + 2 * d + 1] = e1;

@@ -40,6 +40,33 @@ __global__ void dur_out_token_kernel(const float* __restrict__ h, int H, const f
     }
   }
 }
+// ... of the constrained kind with force words: the sampled form above, and a negative force word may be a duration range word
+// (dur_range_bit, philox.hpp).  The row's earlier bits are the planes idx - k * idx_stride, k = 1..d, written by the launches of the steps
+// before.  A kernel of its own, so that the two above stay the instructions they were.
+__global__ void dur_out_token_cons_kernel(const float* __restrict__ h, int H, const float* __restrict__ w_out, const float* __restrict__ b_out,
+                                          float* __restrict__ dur_out, long ld_out, int* __restrict__ idx, long idx_stride,
+                                          const int* __restrict__ force_idx, long rows, const SampleBlock* __restrict__ samp, int t, int n, int d) {
+  const int sub = threadIdx.x & 15;
+  const long rpb = blockDim.x / 16;
+  for (long r = (long)blockIdx.x * rpb + threadIdx.x / 16; r < rows; r += (long)gridDim.x * rpb) {
+    float s0 = 0.f, s1 = 0.f;
+    for (int j = sub; j < H; j += 16) { float v = h[r * H + j]; s0 += v * w_out[j]; s1 += v * w_out[H + j]; }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o, 16); s1 += __shfl_xor(s1, o, 16); }
+    if (sub == 0) {
+      s0 += b_out[0]; s1 += b_out[1];
+      dur_out[r * ld_out + 0] = s0; dur_out[r * ld_out + 1] = s1;
+      const SampleBlock sb = *samp;
+      float g0, g1;
+      dur_gumbel2(sb, sb.sample_offset + r, t, n, d, g0, g1);
+      const float x0 = perturbed(s0, sb.t_dur, g0), x1 = perturbed(s1, sb.t_dur, g1);
+      const int fw = force_idx[r];
+      int p = 0;
+      for (int k = d; k > 0; k--) p = 2 * p + idx[r - k * idx_stride];
+      idx[r] = fw >= 0 ? fw : dur_range_bit(fw, d, p, x1 > x0 ? 1 : 0);       // first max wins ties (torch.max)
+    }
+  }
+}
 
 // ---------------------------------------------------------------------------------------------
 // gradient global norm + clip_grad_norm_(.,clip) + Adam (module.py:142-144, train.py:50) over the
@@ -284,6 +311,20 @@ extern "C" int ptv_dur_out_token_sample(const float* h, int H, const float* w_ou
   long nb = (rows + 15) / 16; if (nb > 8192) nb = 8192;
   hipLaunchKernelGGL(dur_out_token_kernel<1>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, h, H, w_out, b_out, dur_out, ld_out, idx, force_idx, rows,
                      (const SampleBlock*)sample, t, n, d);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// ... of the CONSTRAINED step loop with force words: a word PTV_FORCE_DUR_RANGE(lo, hi) limits the note's duration.  idx is plane d of
+// the decisions; the planes of the bits before it lie idx_stride words apart below it.  idx and force_idx must be given.
+extern "C" int ptv_dur_out_token_sample_cons(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
+                                             int* idx, long idx_stride, const int* force_idx, long rows, const void* sample, int t, int n, int d,
+                                             void* stream) {
+  if (!h || !w_out || !b_out || !dur_out || !idx || !force_idx || rows <= 0 || H <= 0 || idx_stride < rows) return PTV_ERR_ARG;
+  if (!sample || t < 0 || t >= 32 || n < 0 || n >= 15 || d < 0 || d >= 5) return PTV_ERR_ARG;
+  long nb = (rows + 15) / 16; if (nb > 8192) nb = 8192;
+  hipLaunchKernelGGL(dur_out_token_cons_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, h, H, w_out, b_out, dur_out, ld_out, idx, idx_stride,
+                     force_idx, rows, (const SampleBlock*)sample, t, n, d);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

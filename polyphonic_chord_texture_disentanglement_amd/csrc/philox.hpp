@@ -307,4 +307,29 @@ __device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], const 
   return pitch_constrain<NV, W>(v, pitch_mask_own<NV, W>(m, j), lo, flags, j, tv, word);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Duration limits: THE rule of a duration range word, shared by every duration site that honours it (and
+// ptv_debug_dur_range).  A note's duration is D = v + 1, v the 5-bit value of its duration bits, bit 0 the most significant.
+// word = PTV_FORCE_DUR_RANGE(lo, hi) = -1024 - (lo | hi << 5), 0 <= lo <= hi <= 31 (the words -1024..-2047 of force_dur; all five planes of
+// a decision hold the same one): the decision of bit d is free, but v ends in [lo, hi].  With p = the value of the bits 0..d-1 already
+// decided, bit value b is ALLOWED iff some completion can still end in the range: the interval [q << (4-d), (q << (4-d)) + (1 << (4-d)) - 1],
+// q = 2p + b, meets [lo, hi].  Returns bit b set = value b allowed; a word that is no range word allows both.
+// One value allowed: that is the decision (its noise words stay unused); both: the caller's own decision, the first maximum of
+// logit + T g; neither (forced bits mixed into a range decision): the bit is free.  A word in -1024..-2047 with lo > hi is no range word.  A word >= 0 still overrides everything:
+// forced() comes after.  The draw is the model's own bit-by-bit chain with the infeasible branches cut, NOT the joint renormalised over
+// the range.  Only the kernels of the 64-byte kind honour the word; nothing is loaded for it and no state but p is carried.
+// ---------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned dur_range_allowed(int word, int d, int p) {
+  const int r = -1024 - word;
+  const int lo = r & 31, hi = r >> 5, s = 4 - d;
+  if (r < 0 || r > 1023 || lo > hi) return 3u;
+  const int a0 = (2 * p) << s, a1 = (2 * p + 1) << s, w = (1 << s) - 1;
+  return (a0 <= hi && a0 + w >= lo ? 1u : 0u) | (a1 <= hi && a1 + w >= lo ? 2u : 0u);
+}
+// ... applied to a decision: `decided` where both values or neither are allowed, else the allowed one
+__device__ __forceinline__ int dur_range_bit(int word, int d, int p, int decided) {
+  const unsigned al = dur_range_allowed(word, d, p);
+  return al == 1u ? 0 : al == 2u ? 1 : decided;
+}
+
 }  // namespace ptv

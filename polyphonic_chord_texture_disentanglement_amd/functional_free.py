@@ -452,6 +452,119 @@ def split_top(x, top_steps, above=None, highest=None, whole_steps=None):
     return voice, rest, kept_n, err
 
 
+FORCE_DUR_RANGE_BASE = -1024    # PTV_FORCE_DUR_RANGE(lo, hi) = FORCE_DUR_RANGE_BASE - (lo | hi << 5), 0 <= lo <= hi <= 31: a free duration word
+DUR_FITS = ('segment', 'bar', 'beat')
+
+
+class DurKeep(Keep):
+    """a Keep whose duration array holds FORCE_DUR_RANGE words (ptv_dur_range_force_build; INTEGRATION.md "Duration limits"): the same
+    four fields, so it goes wherever a Keep goes -- but only the constrained kernels honour the words, so a decode with one is always
+    sent as the constrained kind (DisentangleVAE._sampling_words), and PtvaeDecoder refuses it beside any other block"""
+    __slots__ = ()
+
+
+class RhythmDurKeep(RhythmKeep, DurKeep):
+    """duration limits built into a RhythmKeep: it stays one"""
+    __slots__ = ()
+
+
+class TopDurKeep(TopKeep, DurKeep):
+    """duration limits built into a TopKeep: it stays one, `ascending` rule included"""
+    __slots__ = ()
+
+
+def _dur_keep_type(keep):
+    if isinstance(keep, DurKeep):
+        return type(keep)
+    return TopDurKeep if isinstance(keep, TopKeep) else RhythmDurKeep if isinstance(keep, RhythmKeep) else DurKeep
+
+
+def dur_fit_row(fit):
+    """the ceiling of a fit per time step, 32 host ints in durations: 'segment' 32 - t, 'bar' 16 - t % 16, 'beat' 4 - t % 4"""
+    if not isinstance(fit, str) or fit not in DUR_FITS:
+        raise ValueError("fit must be 'segment', 'bar' or 'beat', got %r" % (fit,))
+    return [{'segment': 32 - t, 'bar': 16 - t % 16, 'beat': 4 - t % 4}[fit] for t in range(32)]
+
+
+def build_dur_limits(device, min_dur=None, max_dur=None, fit=None, steps=None, batch=None, keep=None, return_counts=False):
+    """duration limits of a free-running decode -> DurKeep (ptv_dur_range_force_build; INTEGRATION.md "Duration limits"): at the selected
+    steps every note decision whose duration bits are free gets the range [floor, ceiling] in durations 1..32.  min_dur / max_dur: a host
+    int 1..32 or an integer device tensor [32] / [B, 32]; fit: 'segment' / 'bar' / 'beat' (dur_fit_row).  Whatever is given is combined:
+    the ceiling is the smallest of max_dur and the fit's, then the floor, which yields to it.  steps: as build_keep's, None = all 32.
+    keep: an existing keep to build into -- its forced and foreign words survive bit for bit, and the result stays what it is (a
+    RhythmKeep / TopKeep keeps its promotion).  batch: B, needed when neither keep nor a [B, 32] tensor tells it.  return_counts: ->
+    (keep, yielded int32 [B, 32]: 1 where a selected step's floor lay over its ceiling).  ValueError before any launch; nothing is
+    copied to the host."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise ValueError('duration limits are built on the device, got %s' % (dev,))
+    if keep is not None:
+        check_keep(keep)
+        dev = keep.pitch.device
+    if batch is not None and (isinstance(batch, bool) or not isinstance(batch, int) or batch < 1):
+        raise ValueError('batch must be an integer >= 1, got %r' % (batch,))
+    sizes = set() if batch is None else {batch}
+    if keep is not None:
+        sizes.add(keep.batch)
+    for name, v in (('min_dur', min_dur), ('max_dur', max_dur)):
+        if v is None:
+            continue
+        if torch.is_tensor(v):
+            if v.device.type != 'cuda' or (keep is not None and v.device != dev):
+                raise ValueError('%s must be a device tensor (on the device of keep), got one on %s' % (name, v.device))
+            if v.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError('%s must be an integer tensor, got %s' % (name, v.dtype))
+            if not ((v.dim() == 1 and v.shape[0] == 32) or (v.dim() == 2 and v.shape[1] == 32 and v.shape[0] >= 1)):
+                raise ValueError('%s must have shape [32] or [B, 32], got %s' % (name, tuple(v.shape)))
+            if v.dim() == 2 and v.shape[0] > 1:
+                sizes.add(v.shape[0])
+        elif isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 32:
+            raise ValueError('%s must be an integer in 1..32 or an integer device tensor [32] / [B, 32], got %r' % (name, v))
+    fit_row = None if fit is None else dur_fit_row(fit)
+    sel = steps if steps is None or torch.is_tensor(steps) else keep_steps_row(steps)
+    if torch.is_tensor(sel):
+        if sel.device.type != 'cuda' or (keep is not None and sel.device != dev):
+            raise ValueError('steps must be on the device (or a host iterable of step indices / a slice)')
+        if sel.dtype not in (torch.bool, torch.uint8):
+            raise ValueError('steps must be bool or uint8, got %s' % (sel.dtype,))
+        if sel.dim() != 2 or sel.shape[1] != 32 or sel.shape[0] < 1:
+            raise ValueError('steps must have shape [B, 32] or [1, 32], got %s' % (tuple(sel.shape),))
+        if sel.shape[0] > 1:
+            sizes.add(sel.shape[0])
+    if len(sizes) > 1:
+        raise ValueError('the batch sizes of keep, batch, min_dur, max_dur and steps disagree: %s' % (sorted(sizes),))
+    if not sizes:
+        raise ValueError('batch is needed: neither a keep nor a [B, 32] tensor tells the number of samples')
+    B = sizes.pop()
+    # ---- nothing below raises
+    def rows(v, fill):
+        if v is None:
+            return torch.full((1, 32), fill, dtype=torch.uint8, device=dev)
+        if torch.is_tensor(v):
+            return v.to(dev).view(-1, 32).clamp(0, 255).to(torch.uint8)
+        return torch.full((1, 32), v, dtype=torch.uint8, device=dev)
+    lo, hi = rows(min_dur, 1).contiguous(), rows(max_dur, 32)
+    if fit_row is not None:
+        hi = torch.minimum(hi, torch.tensor(fit_row, dtype=torch.uint8, device=dev).view(1, 32))
+    hi = hi.contiguous()
+    if sel is None:
+        sel = torch.ones(1, 32, dtype=torch.uint8, device=dev)
+    elif torch.is_tensor(sel):
+        sel = sel.to(dev).contiguous()
+        sel = sel.view(torch.uint8) if sel.dtype == torch.bool else sel
+    else:
+        sel = torch.frombuffer(bytearray(sel), dtype=torch.uint8).view(1, 32).to(dev)
+    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=dev)
+    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=dev)
+    yielded = torch.empty(B, 32, dtype=torch.int32, device=dev)
+    src = (None, None) if keep is None else (keep.pitch.contiguous(), keep.dur.contiguous())
+    call('ptv_dur_range_force_build', ptr(lo), lo.shape[0], ptr(hi), hi.shape[0], ptr(sel), sel.shape[0], ptr(src[0]), ptr(src[1]), B,
+         ptr(pitch), ptr(dur), ptr(yielded), stream_ptr())
+    err = torch.zeros(B, dtype=torch.int32, device=dev) if keep is None else keep.err
+    out = _dur_keep_type(keep)(pitch, dur, err, B)
+    return (out, yielded) if return_counts else out
+
+
 def split_voice(x, voice_steps, below=None, lowest=None, whole_steps=None):
     """the selection of build_keep_voice as two model grids (ptv_grid_split_voice) -> (x_voice, x_rest int64 [B, 32, 16, 6], kept_n int32
     [B, 32], err int32 [B]): per step the kept notes and what the decoder would re-draw, each a valid step"""
@@ -1014,8 +1127,10 @@ def _note_step(plan, P, buf, tbl, inp, t, n, GCt):
     gemm(h, P['pitch_out_linear.weight'], pitch[pr], bias=P['pitch_out_linear.bias'], prec=prec)
     gemm(h, w_dh[:, :Hn], HD[0][pr], bias=P['dur_hid_linear.bias'], prec=prec)
     gemm(pitch[pr], w_dh[:, Hn:], HD[0][pr], acc=True, prec=prec)
+    # (the constrained kind with force arrays: the entries that honour a duration range word -- INTEGRATION.md "Duration limits")
+    cons_dur = bool(kind.cons) and force_dur is not None
     if prec == 1 and Hd == 64 and F_.FUSED_DUR:
-        call(kind.dur_gru, Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tbl.tab0), ptr(tbl.tab), ptr(w_out_d), ptr(b_out_d),
+        call(kind.dur_gru + ('_cons' if cons_dur else ''), Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tbl.tab0), ptr(tbl.tab), ptr(w_out_d), ptr(b_out_d),
              ptr(HD[1][pr]), M * Hd, None, ptr(gates_d[0][0][pr]) if train else None, M * Hd, 4 * M * Hd, F_._bf(gates_d), ptr(dur2[pr]), 10,
              ptr(idx[0][pr]), M, ptr(force_dur[0][pr]) if force_dur is not None else None, M, *(smp and smp + (t, n)), st)
     else:
@@ -1023,6 +1138,10 @@ def _note_step(plan, P, buf, tbl, inp, t, n, GCt):
             g_, g_ld, g_idx = (tbl.tab0, 0, None) if d == 0 else (tbl.tab, 3 * Hd, idx[d - 1][pr])
             gru_step(prec, HD[d][pr], g_, g_ld, w_hh_d, b_hh_d, HD[d + 1][pr], gates=gates_d[d][:, pr] if train else None, plane=M * Hd,
                      gi_idx=g_idx)
+            if cons_dur:
+                call(kind.dur_token + '_cons', ptr(HD[d + 1][pr]), Hd, ptr(w_out_d), ptr(b_out_d), ptr(dur2[pr][:, 2 * d:]), 10,
+                     ptr(idx[d][pr]), M, ptr(force_dur[d][pr]), B, *smp, t, n, d, st)
+                continue
             call(kind.dur_token, ptr(HD[d + 1][pr]), Hd, ptr(w_out_d), ptr(b_out_d), ptr(dur2[pr][:, 2 * d:]), 10, ptr(idx[d][pr]),
                  ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp and smp + (t, n, d)), st)
     call(kind.note_token, ptr(pitch[pr]), NP, ptr(idx[0][pr]), M, ptr(P['note_embedding.weight']), ptr(P['note_embedding.bias']), E,

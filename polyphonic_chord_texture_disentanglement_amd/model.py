@@ -13,9 +13,9 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import (Keep, RhythmKeep, TopKeep, build_chord_keep, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice,
-                              check_chord_keep, check_chord_sampling, check_constraints, check_keep, check_sampling, make_block,
-                              sampling_words, split_top, split_voice)
+from .functional_free import (DurKeep, Keep, RhythmKeep, TopKeep, build_chord_keep, build_dur_limits, build_keep, build_keep_rhythm,
+                              build_keep_top, build_keep_voice, check_chord_keep, check_chord_sampling, check_constraints, check_keep,
+                              check_sampling, make_block, sampling_words, split_top, split_voice)
 from .optim import refresh_weight_shadows
 from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
@@ -427,13 +427,14 @@ class DisentangleVAE(PytorchModel):
         """None (argmax decode) or the request's sampling block as host words (keep puts nothing into the block: it travels beside it);
         a sampled decode that names no draw takes the model's counter and advances it.  A rhythm keep promotes the decode to the constrained
         kind, whose kernels alone honour its words: an `ascending` nobody gave becomes False, the vacuous constraint (flags 0, no mask).  A
-        top keep does the same with True: its ceilings count on notes that ascend (_request has refused ascending=False)"""
+        top keep does the same with True: its ceilings count on notes that ascend (_request has refused ascending=False).  A keep with
+        duration limits (DurKeep) is promoted like a rhythm keep; built into a top keep it stays a top keep"""
         kw = req.kw
         ascending = kw['ascending']
-        if ascending is None and isinstance(req.keep, RhythmKeep):
-            ascending = False
         if ascending is None and isinstance(req.keep, TopKeep):
             ascending = True
+        if ascending is None and isinstance(req.keep, (RhythmKeep, DurKeep)):
+            ascending = False
         if not req.sampled:
             if req.mask is None and ascending is None:
                 return None
@@ -509,6 +510,20 @@ class DisentangleVAE(PytorchModel):
         ascend strictly (a lane may then be empty and the step end short); bit 1: a mode byte that is none of 0 / 1 / 4 (never from
         here).  return_counts=True: -> (TopKeep, kept_n int32 [B, 32]).  Nothing is copied to the host."""
         return build_keep_top(x, top_steps, above, highest, durations, lanes, whole_steps, return_counts)
+
+    def dur_limits(self, min_dur=None, max_dur=None, fit=None, steps=None, batch=None, keep=None, return_counts=False):
+        """Duration limits of a decode -> functional_free.DurKeep for keep= (ptv_dur_range_force_build; INTEGRATION.md "Duration limits").
+        At the selected steps every note whose duration bits are not forced gets a duration (1..32 sixteenths) in [floor, ceiling], and
+        the decoder still chooses inside that range and feeds its choice back.  min_dur / max_dur: an int 1..32 or an integer device
+        tensor [32] / [B, 32]; fit: 'segment' (ceiling 32 - t: nothing hangs over the end), 'bar' (16 - t % 16: nothing crosses the bar
+        line) or 'beat' (4 - t % 4).  Whatever is given is combined: the ceiling is the smallest, then the floor, which yields where
+        it lies above the ceiling.  steps: as keep()'s, default all 32.  batch: the number of samples, needed when neither `keep` nor a
+        [B, 32] tensor tells it.  keep: an existing keep to build into; its forced words survive bit for bit and it stays what it is (a
+        RhythmKeep / TopKeep keeps its promotion and its `ascending` rule).  The decision of each duration bit is the model's own,
+        with the values that cannot end in the range removed: the bit-by-bit chain cut to the range, not the joint distribution over
+        the 32 durations renormalised.  A decode with such a keep always runs the constrained kernels.  return_counts=True: -> (keep,
+        yielded int32 [B, 32]: 1 where a selected step's floor yielded).  ValueError before any launch; nothing is copied to the host."""
+        return build_dur_limits(self.device, min_dur, max_dur, fit, steps, batch, keep, return_counts)
 
     def split_top(self, x, top_steps, above=None, highest=None, whole_steps=None):
         """The selection of keep_top as two grids -> (x_top, x_rest, kept_n, err) (ptv_grid_split_top), the mirror of split_voice: x_top

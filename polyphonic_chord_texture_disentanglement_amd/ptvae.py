@@ -434,9 +434,10 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             if not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None:
                 raise ValueError('keep is inference only: it cannot be combined with training or teacher forcing')
             FF_.check_keep(keep, z.size(0))
-            if isinstance(keep, FF_.RhythmKeep) and not (sampling is not None and torch.is_tensor(sampling) and FF_.block_kind(sampling).cons):
-                raise ValueError('a RhythmKeep needs a constrained block (functional_free.sampling_block(..., ascending=False) at least): '
-                                 'only the constrained kernels honour its words')
+            if isinstance(keep, (FF_.RhythmKeep, FF_.DurKeep)) and not (sampling is not None and torch.is_tensor(sampling)
+                                                                       and FF_.block_kind(sampling).cons):
+                raise ValueError('a %s needs a constrained block (functional_free.sampling_block(..., ascending=False) at least): '
+                                 'only the constrained kernels honour its words' % ('DurKeep' if isinstance(keep, FF_.DurKeep) else 'RhythmKeep'))
             if isinstance(keep, FF_.TopKeep) and not (sampling is not None and torch.is_tensor(sampling) and FF_.block_kind(sampling).cons
                                                       and getattr(sampling, 'ascending', False)):
                 raise ValueError('a TopKeep needs a constrained block with the ascending flag (functional_free.sampling_block(..., '

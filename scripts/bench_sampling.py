@@ -15,6 +15,9 @@ under mask + ascending + top_k + top_p; each beside the same setting without a k
 The top rows (kept top voice, DisentangleVAE.keep_top: every step of the same grid keeps its top note and its note count, the notes under it
 are drawn again under their ceilings) run under plain sampling -- sent as the constrained kind with the ascending flag, as the model sends
 it, and reported beside `ascending` -- and under mask + ascending + top_k + top_p, beside the same setting without a keep.
+The limits rows (duration limits, DisentangleVAE.dur_limits: every step fit to the bar with a floor of two sixteenths, every decision
+free inside its range) run under plain sampling -- sent as the constrained kind with the vacuous constraint, like the rhythm row, and to
+be read beside it -- and under mask + ascending + top_k + top_p, beside the same setting without a keep and beside the rhythm row.
 The logprob rows (--logprob 1; PtvaeDecoder.decode_logprob, DisentangleVAE.decode_best_of) time the log-probability pass ALONE -- the two
 launches after a plain sampled decode, and after the mask + ascending + top_k + top_p decode, where every row also runs the allowed rule
 and both 32-round selects -- and decode_best_of(n=4) at a quarter of the batch (as many decoded rows as one plain decode of the batch).
@@ -90,6 +93,9 @@ def main():
         keeps['keep top'] = ('ascending' if a.constrained else 'sampled', m.keep_top(x, range(32)))
         if a.constrained:
             keeps['keep top+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.keep_top(x, range(32)))
+        keeps['dur limits'] = ('sampled', m.dur_limits(min_dur=2, fit='bar', batch=a.batch))
+        if a.constrained:
+            keeps['dur limits+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.dur_limits(min_dur=2, fit='bar', batch=a.batch))
     kinds += list(keeps)
     blocks = {'argmax': [None] * (a.rounds + 1),
               'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
@@ -103,6 +109,8 @@ def main():
         blocks[k] = blocks[base]
     if 'keep rhythm' in keeps:                               # a rhythm keep needs the constrained kind: the vacuous constraint
         blocks['keep rhythm'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=False) for d in range(a.rounds + 1)]
+    if 'dur limits' in keeps:                                # ... and so do duration limits
+        blocks['dur limits'] = blocks['keep rhythm']
     if 'keep top' in keeps:                                  # a top keep needs the constrained kind with the ascending flag
         blocks['keep top'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=True) for d in range(a.rounds + 1)]
 
