@@ -1105,7 +1105,7 @@ int ptv_pitch_mask_build(int* mask, long B, int lo, int hi, int pitch_classes, c
  * B < 1, steps_rows not in {1, B} or a NULL pointer: PTV_ERR_ARG before any launch. */
 int ptv_keep_force_build(const long* x, const unsigned char* steps, int steps_rows, long B, int* force_pitch, int* force_dur, int* err,
                          void* stream);
-/* Kept voices: the force arrays of a decode that keeps the LOWEST notes of a time step and decides the rest of it (csrc/keep_voice.hip;
+/* Kept voices: the force arrays of a decode that keeps the LOWEST notes of a time step and decides the rest of it (csrc/keep.hip;
  * INTEGRATION.md "Kept voices").  The grammar orders the notes of a step by ascending pitch, so the lowest voice is a PREFIX of
  * the step's note decisions: the note loop is forced through it and goes on freely.  x as in "Kept steps".  mode: uint8 [mode_rows][32],
  * mode_rows = 1 (one row serves every sample) or B, per (b, t):
@@ -1137,7 +1137,7 @@ int ptv_keep_voice_force_build(const long* x, const unsigned char* mode, int mod
 int ptv_grid_split_voice(const long* x, const unsigned char* mode, int mode_rows, const int* below, int below_rows, const int* lowest,
                          int lowest_rows, long B, long* voice, long* rest, int* kept_n, int* err, void* stream);
 /* Kept rhythm: a decode that keeps the number of notes of a time step, its rests and its durations, and draws the pitches again
- * (csrc/keep_rhythm.hip; INTEGRATION.md "Kept rhythm").
+ * (csrc/keep.hip; INTEGRATION.md "Kept rhythm").
  * PTV_FORCE_NOT_EOS (-2), a word of force_pitch: the decision is FREE, but <eos> (129) is not in its support unless nothing else is.  <eos>
  *   leaves the allowed set of that decision iff at least one other class is allowed (after the mask, after `ascending`, never <sos> under
  *   `ascending`, columns < 130).  If no other class is allowed <eos> stays: the allowed set is never empty, the step ends short, and nothing
@@ -1166,7 +1166,7 @@ int ptv_grid_split_voice(const long* x, const unsigned char* mode, int mode_rows
 int ptv_keep_rhythm_force_build(const long* x, const unsigned char* mode, int mode_rows, int flags, long B, int* force_pitch, int* force_dur,
                                 int* kept_n, int* err, void* stream);
 /* Kept top voice: a decode that keeps the HIGHEST notes of a time step -- a suffix of its note decisions -- and its note count, and draws
- * the notes under them again (csrc/keep_top.hip; INTEGRATION.md "Kept top voice").
+ * the notes under them again (csrc/keep.hip; INTEGRATION.md "Kept top voice").
  * PTV_FORCE_BELOW(u) = -256 - u, u in 1..128 (the words -257..-384 of force_pitch): the decision is FREE, is never <eos>, and its pitch is a
  *   note strictly below the ceiling u.  The rule is part of the allowed rule: after the mask and `ascending`, before every truncation
  *   (top_k, the nucleus mass, min_p's maximum and Z are those of the set below).  With lane = the notes c < 128 with c < u -- under the
@@ -1209,7 +1209,7 @@ int ptv_grid_split_top(const long* x, const unsigned char* mode, int mode_rows, 
                        int highest_rows, long B, long* voice, long* rest, int* kept_n, int* err, void* stream);
 /* Duration limits: a decode whose notes have durations in a range per (sample, time step) -- "nothing longer than a beat", "nothing shorter
  * than an eighth", "no note across the bar line" -- while the decoder still chooses inside the range and feeds its choice back
- * (csrc/dur_limits.hip, csrc/philox.hpp; INTEGRATION.md "Duration limits").
+ * (csrc/keep.hip, csrc/philox.hpp; INTEGRATION.md "Duration limits").
  * A note's duration is D = v + 1, v the 5-bit value of its duration bits, bit 0 the most significant.
  * PTV_FORCE_DUR_RANGE(lo, hi) = -1024 - (lo | hi << 5), 0 <= lo <= hi <= 31 (the words -1024..-2047 of force_dur): the decision is FREE and
  *   v ends in [lo, hi].  It is negative, so every "forced?" test answers as before; -1 and every other negative word stay plainly free.

@@ -493,55 +493,6 @@ extern "C" int ptv_pitch_mask_build(int* mask, long B, int lo, int hi, int pitch
   return PTV_OK;
 }
 
-// force arrays of a decode with kept time steps (include/ptvae_hip.h "Kept steps"): one thread per (time step, sample) row r = t * B + b
-// of the step-major arrays -- a wave's stores are 64 consecutive words of every one of the 15 + 75 planes, while it reads its own 768
-// contiguous bytes of the sample-major grid.  Every element is written (-1 = free).  err[b] has ONE writer, the thread of (t = 0, b),
-// which looks at the pitch column of the sample's 32 steps again (L2 hits).
-__device__ __forceinline__ int keep_step_len(const long* __restrict__ xs) {      // first slot 1..15 holding <eos>, else 15
-  int L = 15;
-  for (int s = 15; s >= 1; s--) if (xs[s * 6] == 129) L = s;
-  return L;
-}
-__global__ void keep_force_build_kernel(const long* __restrict__ x, const unsigned char* __restrict__ steps, int one_row, long B,
-                                        int* __restrict__ force_pitch, int* __restrict__ force_dur, int* __restrict__ err) {
-  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long R = 32 * B, M = 15 * R;
-  if (r >= R) return;
-  const long t = r / B, b = r % B;
-  const long* xs = x + (b * 32 + t) * 96;
-  const bool kept = steps[(one_row ? 0 : b * 32) + t] != 0;
-  const int L = kept ? keep_step_len(xs) : 0;
-  for (int n = 0; n < 15; n++) {
-    const long p = xs[(n + 1) * 6];
-    force_pitch[n * R + r] = (n < L && p >= 0 && p <= 129) ? (int)p : -1;
-#pragma unroll
-    for (int d = 0; d < 5; d++) {
-      const long v = xs[(n + 1) * 6 + 1 + d];
-      force_dur[d * M + n * R + r] = (n < L && (v == 0 || v == 1)) ? (int)v : -1;
-    }
-  }
-  if (t == 0) {
-    int e = 0;
-    for (int tt = 0; tt < 32; tt++) {
-      if (!steps[(one_row ? 0 : b * 32) + tt]) continue;
-      const long* xt = x + (b * 32 + tt) * 96;
-      const int Lt = keep_step_len(xt);
-      for (int s = 1; s <= Lt; s++) { const long p = xt[s * 6]; if (p < 0 || p > 129) e |= 1; }
-    }
-    err[b] = e;
-  }
-}
-
-extern "C" int ptv_keep_force_build(const long* x, const unsigned char* steps, int steps_rows, long B, int* force_pitch, int* force_dur,
-                                    int* err, void* stream) {
-  if (!x || !steps || !force_pitch || !force_dur || !err || B < 1 || (steps_rows != 1 && steps_rows != B)) return PTV_ERR_ARG;
-  const long R = 32 * B;
-  hipLaunchKernelGGL(keep_force_build_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, steps,
-                     (steps_rows == 1 && B != 1) ? 1 : 0, B, force_pitch, force_dur, err);
-  PTV_CHECK_LAUNCH();
-  return PTV_OK;
-}
-
 extern "C" int ptv_chord_token(const float* root, const float* chroma, const float* bass, unsigned* masks2, float* token, int B, void* stream) {
   if (!root || !chroma || !bass || !masks2 || !token || B <= 0) return PTV_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;

@@ -192,8 +192,14 @@ def check_constraints(pitch_mask=None, ascending=None, batch=None):
 class Keep(collections.namedtuple('Keep', 'pitch dur err batch')):
     """the kept time steps of a free-running decode as its force arrays on the device (ptv_keep_force_build; INTEGRATION.md "Kept steps"):
     pitch int32 [15, 32 B], dur int32 [5, 480 B] (>= 0: the decision is forced to that value, negative: free), err int32 [B] (bit 0: a kept
-    step held a pitch outside 0..129 before its <eos> -- that decision stays free), batch = B"""
+    step held a pitch outside 0..129 before its <eos> -- that decision stays free), batch = B.
+    What a keep demands of the decode is stated here, by class (attributes, not fields), and read by DisentangleVAE._request /
+    _sampling_words and PtvaeDecoder.decoder: needs_constrained -- its arrays hold words only the constrained kernels honour, so a decode
+    with it is always sent as the constrained kind and refused beside any other block; needs_ascending -- that block must carry the
+    `ascending` flag too"""
     __slots__ = ()
+    needs_constrained = False
+    needs_ascending = False
 
 
 def keep_steps_row(steps):
@@ -216,26 +222,16 @@ def keep_steps_row(steps):
 def build_keep(x, steps):
     """(x int64 device [B, 32, 16, 6] in the model's grid layout, steps) -> Keep; steps: a device bool / uint8 tensor [B, 32] or [1, 32], or
     a host selection (keep_steps_row) that becomes one [1, 32] row.  ValueError before any launch; nothing is copied to the host."""
-    if not torch.is_tensor(x) or x.device.type != 'cuda':
-        raise ValueError('x must be a device tensor: the grid int64 [B, 32, 16, 6]')
-    if x.dtype != torch.int64 or x.dim() != 4 or tuple(x.shape[1:]) != (32, 16, 6) or x.shape[0] < 1:
-        raise ValueError('x must be int64 [B, 32, 16, 6], got %s %s' % (x.dtype, tuple(x.shape)))
+    _check_grid(x)
     B = x.shape[0]
     if torch.is_tensor(steps):
-        if steps.device.type != 'cuda':
-            raise ValueError('steps must be a device tensor (or a host iterable of step indices / a slice)')
-        if steps.dtype not in (torch.bool, torch.uint8):
-            raise ValueError('steps must be bool or uint8, got %s' % (steps.dtype,))
-        if steps.dim() != 2 or steps.shape[1] != 32 or steps.shape[0] not in (1, B):
-            raise ValueError('steps must have shape [B, 32] or [1, 32] with B = %d, got %s' % (B, tuple(steps.shape)))
+        _check_step_selections(x, (('steps', steps),))
         steps = steps.contiguous()
-        steps = steps.view(torch.uint8) if steps.dtype == torch.bool else steps
+        steps = steps.view(torch.uint8) if steps.dtype == torch.bool else steps     # (uint8 bytes go as they are: non-zero = kept)
     else:
         steps = torch.frombuffer(bytearray(keep_steps_row(steps)), dtype=torch.uint8).view(1, 32).to(x.device)
     x = x.contiguous()
-    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=x.device)
-    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=x.device)
-    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    pitch, dur, err, _ = _force_outputs(B, x.device, counts=False)
     call('ptv_keep_force_build', ptr(x), ptr(steps), steps.shape[0], B, ptr(pitch), ptr(dur), ptr(err), stream_ptr())
     return Keep(pitch, dur, err, B)
 
@@ -261,6 +257,19 @@ def _check_step_selections(x, named):
                 raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(s.shape)))
 
 
+def _force_outputs(B, device, counts=True):
+    """the outputs of a builder, every element of which its kernel writes: -> (pitch int32 [15, 32 B], dur int32 [5, 480 B], err int32
+    [B], counts int32 [B, 32] -- kept_n / yielded -- or None)"""
+    def i32(*shape):
+        return torch.empty(*shape, dtype=torch.int32, device=device)
+    return i32(15, 32 * B), i32(5, 480 * B), i32(B), i32(B, 32) if counts else None
+
+
+def _ptr_rows(t):
+    """an optional per-step operand [rows, 32] as the entry points take it: its address and row count (NULL still names one: 1)"""
+    return ptr(t), 1 if t is None else t.shape[0]
+
+
 def _mode_bytes(x, first, whole, code):
     """two validated selections (a device tensor or the 32 bytes of keep_steps_row; whole may be None) -> mode uint8 [rows, 32] on the
     device of x: `code` at the steps of `first`, 1 at the steps of `whole` -- a step in both is a whole step.  Raises nothing."""
@@ -278,33 +287,55 @@ def _mode_bytes(x, first, whole, code):
     return mode.contiguous()
 
 
-def _voice_selection(x, voice_steps, below, lowest, whole_steps):
-    """the arguments both kept-voice entry points share, validated -- every ValueError before any launch -- and then put on the device:
-    -> (x contiguous, mode uint8 [rows, 32] (2 = voice step, 1 = whole step: a step in both selections is a whole step), below, lowest:
-    int32 [rows, 32] or None = no limit)"""
-    limits = [below, lowest]
-    for name, v, top in (('below', below, 128), ('lowest', lowest, 15)):
+def _selection(x, name, steps, code, whole_steps, limits=(), need_one=None):
+    """the arguments the grid-reading builders and splits share, validated -- every ValueError before any launch, in this order: the
+    host limits, need_one, the selections, the grid, the device limits -- and then put on the device: -> (x contiguous, mode uint8
+    [rows, 32]: `code` at the steps of `steps`, 1 at those of whole_steps, a step in both is a whole step; then one int32 [rows, 32] or
+    None = no limit per entry of limits).  name: the argument name of `steps`; limits: ((name, value, top), ...), value None, a host int
+    0..top or an int32 device tensor [B, 32] / [1, 32]; need_one: the message for a call that gives none of them, if that is an error"""
+    for lname, v, top in limits:
         if v is not None and not torch.is_tensor(v) and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top):
-            raise ValueError('%s must be an integer in 0..%d or an int32 device tensor [B, 32] / [1, 32], got %r' % (name, top, v))
-    if below is None and lowest is None:
-        raise ValueError('a kept voice needs below (keep the notes under that pitch) or lowest (keep that many notes), or both')
-    sels = [s if s is None or torch.is_tensor(s) else keep_steps_row(s) for s in (voice_steps, whole_steps)]
+            raise ValueError('%s must be an integer in 0..%d or an int32 device tensor [B, 32] / [1, 32], got %r' % (lname, top, v))
+    if need_one and all(v is None for _, v, _ in limits):
+        raise ValueError(need_one)
+    sels = [s if s is None or torch.is_tensor(s) else keep_steps_row(s) for s in (steps, whole_steps)]
     if sels[0] is None:
-        raise ValueError('voice_steps must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice')
+        raise ValueError('%s must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice' % name)
     _check_grid(x)
     B = x.shape[0]
-    _check_step_selections(x, (('voice_steps', sels[0]), ('whole_steps', sels[1])))
-    for name, v in (('below', limits[0]), ('lowest', limits[1])):
+    _check_step_selections(x, ((name, sels[0]), ('whole_steps', sels[1])))
+    for lname, v, _ in limits:
         if torch.is_tensor(v):
             if v.device != x.device or v.dtype != torch.int32:
-                raise ValueError('%s must be int32 on the device of x, got %s on %s' % (name, v.dtype, v.device))
+                raise ValueError('%s must be int32 on the device of x, got %s on %s' % (lname, v.dtype, v.device))
             if v.dim() != 2 or v.shape[1] != 32 or v.shape[0] not in (1, B):
-                raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(v.shape)))
+                raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (lname, B, tuple(v.shape)))
     # ---- nothing below raises
-    mode = _mode_bytes(x, sels[0], sels[1], 2)
-    limits = [v.contiguous() if torch.is_tensor(v) else (None if v is None else torch.full((1, 32), v, dtype=torch.int32, device=x.device))
-              for v in limits]
-    return x.contiguous(), mode, limits[0], limits[1]
+    on_device = tuple(None if v is None else v.contiguous() if torch.is_tensor(v)
+                      else torch.full((1, 32), v, dtype=torch.int32, device=x.device) for _, v, _ in limits)
+    return (x.contiguous(), _mode_bytes(x, sels[0], sels[1], code)) + on_device
+
+
+def _voice_selection(x, voice_steps, below, lowest, whole_steps):
+    """build_keep_voice's and split_voice's: mode 2 = voice step; below / lowest, at least one of the two"""
+    return _selection(x, 'voice_steps', voice_steps, 2, whole_steps, (('below', below, 128), ('lowest', lowest, 15)),
+                      'a kept voice needs below (keep the notes under that pitch) or lowest (keep that many notes), or both')
+
+
+def _top_selection(x, top_steps, above, highest, whole_steps):
+    """build_keep_top's and split_top's: mode 4 = top step; above / highest, neither given: the very top note"""
+    return _selection(x, 'top_steps', top_steps, 4, whole_steps, (('above', above, 128), ('highest', highest, 15)))
+
+
+def _split(entry, x, mode, pitch_lim, count_lim):
+    """a selection as two model grids, by ptv_grid_split_voice / ptv_grid_split_top -> (voice, rest, kept_n, err)"""
+    B = x.shape[0]
+    voice, rest = torch.empty_like(x), torch.empty_like(x)
+    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
+    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    call(entry, ptr(x), ptr(mode), mode.shape[0], *_ptr_rows(pitch_lim), *_ptr_rows(count_lim), B, ptr(voice), ptr(rest), ptr(kept_n),
+         ptr(err), stream_ptr())
+    return voice, rest, kept_n, err
 
 
 def build_keep_voice(x, voice_steps, below=None, lowest=None, durations=True, whole_steps=None, return_counts=False):
@@ -319,12 +350,9 @@ def build_keep_voice(x, voice_steps, below=None, lowest=None, durations=True, wh
         raise ValueError('durations must be a bool, got %r' % (durations,))
     x, mode, below, lowest = _voice_selection(x, voice_steps, below, lowest, whole_steps)
     B = x.shape[0]
-    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=x.device)
-    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=x.device)
-    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
-    err = torch.empty(B, dtype=torch.int32, device=x.device)
-    call('ptv_keep_voice_force_build', ptr(x), ptr(mode), mode.shape[0], ptr(below), 1 if below is None else below.shape[0], ptr(lowest),
-         1 if lowest is None else lowest.shape[0], 0 if durations else 1, B, ptr(pitch), ptr(dur), ptr(kept_n), ptr(err), stream_ptr())
+    pitch, dur, err, kept_n = _force_outputs(B, x.device)
+    call('ptv_keep_voice_force_build', ptr(x), ptr(mode), mode.shape[0], *_ptr_rows(below), *_ptr_rows(lowest), 0 if durations else 1, B,
+         ptr(pitch), ptr(dur), ptr(kept_n), ptr(err), stream_ptr())
     keep = Keep(pitch, dur, err, B)
     return (keep, kept_n) if return_counts else keep
 
@@ -337,17 +365,7 @@ class RhythmKeep(Keep):
     fields, so it goes wherever a Keep goes -- but only the constrained kernels honour the word, so a decode with one is always sent as
     the constrained kind (DisentangleVAE._sampling_words), and PtvaeDecoder refuses it beside any other block"""
     __slots__ = ()
-
-
-def _rhythm_selection(x, steps, whole_steps):
-    """the selections of build_keep_rhythm validated as _voice_selection's -- every ValueError before any launch -- and then put on the
-    device: -> (x contiguous, mode uint8 [rows, 32]: 3 = rhythm step, 1 = whole step; a step in both selections is a whole step)"""
-    sels = [s if s is None or torch.is_tensor(s) else keep_steps_row(s) for s in (steps, whole_steps)]
-    if sels[0] is None:
-        raise ValueError('steps must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice')
-    _check_grid(x)
-    _check_step_selections(x, (('steps', sels[0]), ('whole_steps', sels[1])))
-    return x.contiguous(), _mode_bytes(x, sels[0], sels[1], 3)      # (nothing after the checks raises)
+    needs_constrained = True
 
 
 def build_keep_rhythm(x, steps, durations=True, whole_steps=None, return_counts=False):
@@ -359,12 +377,9 @@ def build_keep_rhythm(x, steps, durations=True, whole_steps=None, return_counts=
     copied to the host."""
     if not isinstance(durations, bool):
         raise ValueError('durations must be a bool, got %r' % (durations,))
-    x, mode = _rhythm_selection(x, steps, whole_steps)
+    x, mode = _selection(x, 'steps', steps, 3, whole_steps)            # (3 = rhythm step; no limits)
     B = x.shape[0]
-    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=x.device)
-    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=x.device)
-    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
-    err = torch.empty(B, dtype=torch.int32, device=x.device)
+    pitch, dur, err, kept_n = _force_outputs(B, x.device)
     call('ptv_keep_rhythm_force_build', ptr(x), ptr(mode), mode.shape[0], 0 if durations else 1, B, ptr(pitch), ptr(dur), ptr(kept_n),
          ptr(err), stream_ptr())
     keep = RhythmKeep(pitch, dur, err, B)
@@ -380,33 +395,8 @@ class TopKeep(Keep):
     leave room only for notes that ascend, so a decode with one is always sent as the constrained kind with ascending=True
     (DisentangleVAE._sampling_words), and PtvaeDecoder refuses it beside any other block"""
     __slots__ = ()
-
-
-def _top_selection(x, top_steps, above, highest, whole_steps):
-    """the arguments both kept-top entry points share, validated as _voice_selection's -- every ValueError before any launch -- and then
-    put on the device: -> (x contiguous, mode uint8 [rows, 32] (4 = top step, 1 = whole step: a step in both selections is a whole
-    step), above, highest: int32 [rows, 32] or None = no limit; both None: the very top note)"""
-    limits = [above, highest]
-    for name, v, top in (('above', above, 128), ('highest', highest, 15)):
-        if v is not None and not torch.is_tensor(v) and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top):
-            raise ValueError('%s must be an integer in 0..%d or an int32 device tensor [B, 32] / [1, 32], got %r' % (name, top, v))
-    sels = [s if s is None or torch.is_tensor(s) else keep_steps_row(s) for s in (top_steps, whole_steps)]
-    if sels[0] is None:
-        raise ValueError('top_steps must be a device bool / uint8 tensor [B, 32] or [1, 32], an iterable of step indices or a slice')
-    _check_grid(x)
-    B = x.shape[0]
-    _check_step_selections(x, (('top_steps', sels[0]), ('whole_steps', sels[1])))
-    for name, v in (('above', limits[0]), ('highest', limits[1])):
-        if torch.is_tensor(v):
-            if v.device != x.device or v.dtype != torch.int32:
-                raise ValueError('%s must be int32 on the device of x, got %s on %s' % (name, v.dtype, v.device))
-            if v.dim() != 2 or v.shape[1] != 32 or v.shape[0] not in (1, B):
-                raise ValueError('%s must have shape [B, 32] or [1, 32] with B = %d, got %s' % (name, B, tuple(v.shape)))
-    # ---- nothing below raises
-    mode = _mode_bytes(x, sels[0], sels[1], 4)
-    limits = [v.contiguous() if torch.is_tensor(v) else (None if v is None else torch.full((1, 32), v, dtype=torch.int32, device=x.device))
-              for v in limits]
-    return x.contiguous(), mode, limits[0], limits[1]
+    needs_constrained = True
+    needs_ascending = True
 
 
 def build_keep_top(x, top_steps, above=None, highest=None, durations=True, lanes=True, whole_steps=None, return_counts=False):
@@ -425,13 +415,9 @@ def build_keep_top(x, top_steps, above=None, highest=None, durations=True, lanes
         raise ValueError('lanes must be a bool, got %r' % (lanes,))
     x, mode, above, highest = _top_selection(x, top_steps, above, highest, whole_steps)
     B = x.shape[0]
-    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=x.device)
-    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=x.device)
-    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
-    err = torch.empty(B, dtype=torch.int32, device=x.device)
-    call('ptv_keep_top_force_build', ptr(x), ptr(mode), mode.shape[0], ptr(above), 1 if above is None else above.shape[0], ptr(highest),
-         1 if highest is None else highest.shape[0], (0 if durations is True else 1) | (0 if lanes else 2), B, ptr(pitch), ptr(dur),
-         ptr(kept_n), ptr(err), stream_ptr())
+    pitch, dur, err, kept_n = _force_outputs(B, x.device)
+    call('ptv_keep_top_force_build', ptr(x), ptr(mode), mode.shape[0], *_ptr_rows(above), *_ptr_rows(highest),
+         (0 if durations is True else 1) | (0 if lanes else 2), B, ptr(pitch), ptr(dur), ptr(kept_n), ptr(err), stream_ptr())
     if durations is False:                                     # every duration word of a top step is free: the [t, b] rows of mode 4
         top = (mode == 4).expand(B, 32).t().reshape(1, 1, 32 * B)
         dur = dur.view(5, 15, 32 * B).masked_fill(top, -1).view(5, 480 * B)
@@ -442,14 +428,7 @@ def build_keep_top(x, top_steps, above=None, highest=None, durations=True, lanes
 def split_top(x, top_steps, above=None, highest=None, whole_steps=None):
     """the selection of build_keep_top as two model grids (ptv_grid_split_top) -> (x_top, x_rest int64 [B, 32, 16, 6], kept_n int32
     [B, 32], err int32 [B]): per step the kept top notes and what the decoder would re-draw under them, each a valid step"""
-    x, mode, above, highest = _top_selection(x, top_steps, above, highest, whole_steps)
-    B = x.shape[0]
-    voice, rest = torch.empty_like(x), torch.empty_like(x)
-    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
-    err = torch.empty(B, dtype=torch.int32, device=x.device)
-    call('ptv_grid_split_top', ptr(x), ptr(mode), mode.shape[0], ptr(above), 1 if above is None else above.shape[0], ptr(highest),
-         1 if highest is None else highest.shape[0], B, ptr(voice), ptr(rest), ptr(kept_n), ptr(err), stream_ptr())
-    return voice, rest, kept_n, err
+    return _split('ptv_grid_split_top', *_top_selection(x, top_steps, above, highest, whole_steps))
 
 
 FORCE_DUR_RANGE_BASE = -1024    # PTV_FORCE_DUR_RANGE(lo, hi) = FORCE_DUR_RANGE_BASE - (lo | hi << 5), 0 <= lo <= hi <= 31: a free duration word
@@ -461,6 +440,7 @@ class DurKeep(Keep):
     four fields, so it goes wherever a Keep goes -- but only the constrained kernels honour the words, so a decode with one is always
     sent as the constrained kind (DisentangleVAE._sampling_words), and PtvaeDecoder refuses it beside any other block"""
     __slots__ = ()
+    needs_constrained = True
 
 
 class RhythmDurKeep(RhythmKeep, DurKeep):
@@ -554,13 +534,11 @@ def build_dur_limits(device, min_dur=None, max_dur=None, fit=None, steps=None, b
         sel = sel.view(torch.uint8) if sel.dtype == torch.bool else sel
     else:
         sel = torch.frombuffer(bytearray(sel), dtype=torch.uint8).view(1, 32).to(dev)
-    pitch = torch.empty(15, 32 * B, dtype=torch.int32, device=dev)
-    dur = torch.empty(5, 480 * B, dtype=torch.int32, device=dev)
-    yielded = torch.empty(B, 32, dtype=torch.int32, device=dev)
+    pitch, dur, err, yielded = _force_outputs(B, dev)
     src = (None, None) if keep is None else (keep.pitch.contiguous(), keep.dur.contiguous())
     call('ptv_dur_range_force_build', ptr(lo), lo.shape[0], ptr(hi), hi.shape[0], ptr(sel), sel.shape[0], ptr(src[0]), ptr(src[1]), B,
          ptr(pitch), ptr(dur), ptr(yielded), stream_ptr())
-    err = torch.zeros(B, dtype=torch.int32, device=dev) if keep is None else keep.err
+    err = err.zero_() if keep is None else keep.err          # (this builder reports nothing: the err of the keep it built into)
     out = _dur_keep_type(keep)(pitch, dur, err, B)
     return (out, yielded) if return_counts else out
 
@@ -568,14 +546,7 @@ def build_dur_limits(device, min_dur=None, max_dur=None, fit=None, steps=None, b
 def split_voice(x, voice_steps, below=None, lowest=None, whole_steps=None):
     """the selection of build_keep_voice as two model grids (ptv_grid_split_voice) -> (x_voice, x_rest int64 [B, 32, 16, 6], kept_n int32
     [B, 32], err int32 [B]): per step the kept notes and what the decoder would re-draw, each a valid step"""
-    x, mode, below, lowest = _voice_selection(x, voice_steps, below, lowest, whole_steps)
-    B = x.shape[0]
-    voice, rest = torch.empty_like(x), torch.empty_like(x)
-    kept_n = torch.empty(B, 32, dtype=torch.int32, device=x.device)
-    err = torch.empty(B, dtype=torch.int32, device=x.device)
-    call('ptv_grid_split_voice', ptr(x), ptr(mode), mode.shape[0], ptr(below), 1 if below is None else below.shape[0], ptr(lowest),
-         1 if lowest is None else lowest.shape[0], B, ptr(voice), ptr(rest), ptr(kept_n), ptr(err), stream_ptr())
-    return voice, rest, kept_n, err
+    return _split('ptv_grid_split_voice', *_voice_selection(x, voice_steps, below, lowest, whole_steps))
 
 
 def check_keep(keep, batch=None):

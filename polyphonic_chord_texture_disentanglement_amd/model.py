@@ -13,9 +13,9 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import (DurKeep, Keep, RhythmKeep, TopKeep, build_chord_keep, build_dur_limits, build_keep, build_keep_rhythm,
-                              build_keep_top, build_keep_voice, check_chord_keep, check_chord_sampling, check_constraints, check_keep,
-                              check_sampling, make_block, sampling_words, split_top, split_voice)
+from .functional_free import (build_chord_keep, build_dur_limits, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice,
+                              check_chord_keep, check_chord_sampling, check_constraints, check_keep, check_sampling, make_block,
+                              sampling_words, split_top, split_voice)
 from .optim import refresh_weight_shadows
 from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
@@ -414,9 +414,9 @@ class DisentangleVAE(PytorchModel):
         """the keywords of a decode of `batch` rows, validated once -> DecodeRequest.  _check_sampling's ValueErrors, and what only this
         model knows: kept steps and the decoder's replay mode exclude each other, and a kept top voice needs ascending notes.  Before
         anything is encoded or launched, and before the draw counter moves."""
-        if isinstance(sampling.get('keep'), TopKeep) and sampling.get('ascending') is False:
-            raise ValueError('a TopKeep needs ascending notes: its ceilings leave room only for notes that ascend -- leave ascending out '
-                             '(it becomes True) or give ascending=True')
+        if getattr(sampling.get('keep'), 'needs_ascending', False) and sampling.get('ascending') is False:
+            raise ValueError('a %s needs ascending notes: its ceilings leave room only for notes that ascend -- leave ascending out '
+                             '(it becomes True) or give ascending=True' % (type(sampling['keep']).__name__,))
         sampled = self._check_sampling(**sampling, batch=batch)
         keep, mask = sampling.get('keep'), sampling.get('pitch_mask')
         if keep is not None and self.decoder.force_trace is not None:
@@ -431,10 +431,8 @@ class DisentangleVAE(PytorchModel):
         duration limits (DurKeep) is promoted like a rhythm keep; built into a top keep it stays a top keep"""
         kw = req.kw
         ascending = kw['ascending']
-        if ascending is None and isinstance(req.keep, TopKeep):
-            ascending = True
-        if ascending is None and isinstance(req.keep, (RhythmKeep, DurKeep)):
-            ascending = False
+        if ascending is None and req.keep is not None and req.keep.needs_constrained:
+            ascending = req.keep.needs_ascending
         if not req.sampled:
             if req.mask is None and ascending is None:
                 return None

@@ -434,14 +434,14 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             if not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None:
                 raise ValueError('keep is inference only: it cannot be combined with training or teacher forcing')
             FF_.check_keep(keep, z.size(0))
-            if isinstance(keep, (FF_.RhythmKeep, FF_.DurKeep)) and not (sampling is not None and torch.is_tensor(sampling)
-                                                                       and FF_.block_kind(sampling).cons):
-                raise ValueError('a %s needs a constrained block (functional_free.sampling_block(..., ascending=False) at least): '
-                                 'only the constrained kernels honour its words' % ('DurKeep' if isinstance(keep, FF_.DurKeep) else 'RhythmKeep'))
-            if isinstance(keep, FF_.TopKeep) and not (sampling is not None and torch.is_tensor(sampling) and FF_.block_kind(sampling).cons
-                                                      and getattr(sampling, 'ascending', False)):
-                raise ValueError('a TopKeep needs a constrained block with the ascending flag (functional_free.sampling_block(..., '
-                                 'ascending=True)): only the constrained kernels honour its words, and its ceilings count on ascending notes')
+            cons = sampling is not None and torch.is_tensor(sampling) and FF_.block_kind(sampling).cons
+            if keep.needs_constrained and not cons:
+                raise ValueError('a %s needs a constrained block (functional_free.sampling_block(..., ascending=%s)%s): only the '
+                                 'constrained kernels honour its words'
+                                 % (type(keep).__name__, keep.needs_ascending, '' if keep.needs_ascending else ' at least'))
+            if keep.needs_ascending and not getattr(sampling, 'ascending', False):
+                raise ValueError('a %s needs a constrained block with the ascending flag (functional_free.sampling_block(..., '
+                                 'ascending=True)): its ceilings count on ascending notes' % (type(keep).__name__,))
             if self.force_trace is not None:
                 raise ValueError('keep cannot be combined with force_trace: both fill the force arrays')
         _require_cuda(z, 'PtvaeDecoder')

@@ -149,11 +149,14 @@ def explained_free(po, do, xh, pn, dn, kw, mask_np, ref, what):
 # ---------------------------------------------------------------------------------------------------------------------------------
 def test_1_builder_matches_keep_ref():
     """ptv_keep_force_build on B = 3 rows of the crafted grid (everything kept with all six hand-made steps; the (t + b) % 4 pattern with
-    pitch 131; only t = 0), [B, 32] and [1, 32] steps: pitch, dur and err equal keep_ref in every element; bad arguments are PTV_ERR_ARG"""
+    pitch 131; only t = 0), [B, 32] and [1, 32] steps and a [B, 32] array of the bytes 0, 1, 2, 3, 4, 7 and 255: pitch, dur and err equal keep_ref in every element; bad arguments are PTV_ERR_ARG"""
     x, steps, _ = crafted()
     x3, s3 = np.ascontiguousarray(x[[1, 5, 2]]), np.ascontiguousarray(steps[[1, 5, 2]])
-    for st in (s3, np.ascontiguousarray(steps[5:6])):
+    other = np.array([0, 1, 2, 3, 4, 7, 255], dtype=np.uint8)     # any non-zero byte is a kept step here: err never gets bit 1
+    other = other[(np.arange(32)[None, :] + np.arange(3)[:, None]) % 7]
+    for st in (s3, np.ascontiguousarray(steps[5:6]), other):
         want = K.build(x3, st)
+        assert not (want['err'] & 2).any()
         xd, sd = dev(x3), dev(st)
         pitch = torch.full((15, 96), 77, dtype=torch.int32, device=DEV)
         dur = torch.full((5, 1440), 77, dtype=torch.int32, device=DEV)

@@ -17,6 +17,7 @@ import sample_ref as S
 import test_gpu_constrained_decode as CD
 import test_gpu_decode_logprob_kernels as LK
 import test_gpu_keep_decode as KD
+import test_gpu_keep_voice_kernels as VK
 import test_gpu_truncated_sampling as TT
 import trunc_ref as TR
 from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
@@ -83,6 +84,16 @@ def test_1_builder_matches_the_reference(B):
         seen += [(want['K'] == 0).sum(), (want['K'] == 15).sum(), (want['err'] & 1).sum(), (want['err'] & 2).sum(), (m == 1).sum(),
                  (want['pitch'] == -2).sum()]
     assert seen.all(), seen
+    if B == 3:                                                     # the same grid under every byte: 2 and 4 are the siblings' legal ones
+        every = VK.sibling_bytes(B)
+        for m in (every, np.ascontiguousarray(every[:1])):
+            for flags in (0, 1):
+                want = RR.build(x, m, durations=not flags)
+                got = gpu_build(x, m, flags)
+                for k in ('pitch', 'dur', 'kept_n', 'err'):
+                    assert np.array_equal(got[k], want[k]), (m.shape[0], flags, k, np.argwhere(got[k] != want[k])[:4])
+                VK.assert_foreign_free(got, m, (2, 4), B)
+            assert (want['err'] & 2).all() and (want['pitch'] == -2).any()
     if B > 1:
         first = RR.build(x, mode)
         assert first['err'][0] == 3

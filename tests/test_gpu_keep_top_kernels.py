@@ -12,6 +12,7 @@ import nucleus_ref as NR
 import test_gpu_constrained_decode as CD
 import test_gpu_keep_decode as KD
 import test_gpu_keep_rhythm_kernels as RK
+import test_gpu_keep_voice_kernels as VK
 import top_ref as TP
 import trunc_ref as TR
 from polyphonic_chord_texture_disentanglement_amd import functional_free as FF_
@@ -83,6 +84,16 @@ def test_1_builder_matches_the_reference(B):
             seen += [(want['K'] == 0).sum(), (want['K'] == 15).sum(), (want['err'] & 1).sum(), (want['err'] & 2).sum(), (m == 1).sum(),
                      (want['pitch'] <= -257).sum(), (want['h'] == 0).sum(), (want['h'] == 1).sum(), (want['h'] > 1).sum()]
     assert seen.all(), seen
+    if B == 3:                                                     # the same grid under every byte: 2 and 3 are the siblings' legal ones
+        every = VK.sibling_bytes(B)
+        for m in (every, np.ascontiguousarray(every[:1])):
+            for flags in range(4):
+                want = TP.build(x, m, above, highest, durations='kept' if flags & 1 else True, lanes=not flags & 2)
+                got = gpu_build(x, m, above, highest, flags)
+                for k in ('pitch', 'dur', 'kept_n', 'err'):
+                    assert np.array_equal(got[k], want[k]), (m.shape[0], flags, k, np.argwhere(got[k] != want[k])[:4])
+                VK.assert_foreign_free(got, m, (2, 3), B)
+            assert (want['err'] & 2).all() and (want['pitch'] <= -257).any() and (want['h'] > 0).any()
     lanes, room = (TP.build(x, mode, above, highest, lanes=l)['pitch'] for l in (True, False))
     assert (lanes != room).any() and np.array_equal(lanes >= -1, room >= -1)
     first = TP.build(x, mode)
@@ -159,7 +170,8 @@ def test_4_split(B):
     the builder's"""
     x, mode, above, highest = inputs(B)
     xd = dev(x)
-    for m in (mode, np.ascontiguousarray(mode[:1])):
+    every = VK.sibling_bytes(B)                                    # first, under every byte: 2 and 3 are the siblings' legal ones  
+    for m in (every, np.ascontiguousarray(every[:1])) * (B == 3) + (mode, np.ascontiguousarray(mode[:1])):
         for ab, hi in limit_forms(above, highest):
             voice = torch.full((B, 32, 16, 6), SENT, dtype=torch.int64, device=DEV)
             rest = torch.full((B, 32, 16, 6), SENT, dtype=torch.int64, device=DEV)
@@ -174,6 +186,9 @@ def test_4_split(B):
             v, r = voice.cpu().numpy(), rest.cpu().numpy()
             assert np.array_equal(v, wv) and np.array_equal(r, wr), (m.shape[0], rows_of(ab), rows_of(hi))
             assert np.array_equal(kept_n.cpu().numpy(), wk) and np.array_equal(err.cpu().numpy(), ref['err'])
+            foreign = np.isin(np.broadcast_to(m, (B, 32)), (2, 3))         # a free step: all of it in rest, none kept, bit 1 of err
+            assert np.array_equal(r[foreign], x[foreign]) and (v[foreign][:, 1, 0] == EOS).all() and (wk[foreign] == 0).all()
+            assert (ref['err'][foreign.any(1)] & 2).all()
     mm = np.broadcast_to(m, (B, 32))
     n_top = 0
     for b in range(min(B, 8)):

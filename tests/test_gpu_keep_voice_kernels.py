@@ -1,4 +1,4 @@
-"""GPU: ptv_keep_voice_force_build and ptv_grid_split_voice (csrc/keep_voice.hip; include/ptvae_hip.h "Kept voices") element for element
+"""GPU: ptv_keep_voice_force_build and ptv_grid_split_voice (csrc/keep.hip; include/ptvae_hip.h "Kept voices") element for element
 against tests/keep_voice_ref.py, at B = 1, 3 and 67 (R = 2144: a partial last block and a partial last wave), for every combination of one
 row / B rows / NULL of mode, below and lowest and both flag values; the whole-step mode against ptv_keep_force_build bit for bit; the
 argument checks; what the two split grids are to each other and to x; functional_free.build_keep_voice / split_voice on top."""
@@ -44,6 +44,24 @@ def inputs(B):
     for a in (x, mode, below, lowest):
         a.setflags(write=False)
     return x, mode, below, lowest
+
+
+def sibling_bytes(B):
+    """mode uint8 [B, 32] that cycles through every byte 0..7 and 255 -- the legal bytes of the sibling entry points among them -- each
+    row from another start, so that a row and a column meet every byte"""
+    cycle = np.array(list(range(8)) + [255], dtype=np.uint8)
+    return cycle[(np.arange(32)[None, :] + 3 * np.arange(B)[:, None]) % 9]
+
+
+def assert_foreign_free(got, mode, foreign, B):
+    """every step whose byte is one of `foreign` -- a sibling's legal byte -- came out free (all 15 + 75 words -1, kept_n 0), with bit 1
+    of its sample's err"""
+    mm = np.broadcast_to(mode, (B, 32))
+    hit = np.isin(mm, foreign)
+    assert all((mm == f).any() for f in foreign)
+    cols = hit.T.reshape(-1)                                       # r = t * B + b
+    assert (got['pitch'][:, cols] == -1).all() and (got['dur'].reshape(5, 15, 32 * B)[:, :, cols] == -1).all()
+    assert (got['kept_n'][hit] == 0).all() and (got['err'][hit.any(1)] & 2).all()
 
 
 def variants(a, with_null=True):
@@ -99,6 +117,19 @@ def test_1_builder_and_split_match_the_reference(B):
                 assert np.array_equal(sp['kept_n'], want['kept_n']) and np.array_equal(sp['err'], want['err']), what
         seen += [(want['K'] > 0).sum(), (want['err'] & 1).sum(), (want['err'] & 2).sum() // 2, (m == 1).sum()]
     assert seen.all()                                              # kept notes, both err bits and whole steps took part
+    if B == 3:                                                     # the same grid under every byte: 3 and 4 are the siblings' legal ones
+        for m in variants(sibling_bytes(B), False):
+            sp = gpu_split(x, m, below, lowest)
+            voice, rest = V.split(x, m, below, lowest)
+            assert np.array_equal(sp['voice'], voice) and np.array_equal(sp['rest'], rest), rows_of(m)
+            for flags in (0, 1):
+                want = V.build(x, m, below, lowest, durations=not flags)
+                got = gpu_build(x, m, below, lowest, flags)
+                for k in ('pitch', 'dur', 'kept_n', 'err'):
+                    assert np.array_equal(got[k], want[k]), (rows_of(m), flags, k)
+                assert_foreign_free(got, m, (3, 4), B)
+            assert np.array_equal(sp['kept_n'], want['kept_n']) and np.array_equal(sp['err'], want['err']), rows_of(m)
+            assert (want['err'] & 2).all() and (want['K'][np.broadcast_to(m, (B, 32)) == 2] > 0).any()
 
 
 def test_2_whole_and_free_steps_are_ptv_keep_force_build():
