@@ -306,6 +306,7 @@ int ptv_txt_conv_relu_pool_bwd_rows(const float* pr_mat, const float* w, const f
 /* ------------------------------------------------------------------------------------------------
  * reparameterize(): get_zs_from_dists / Normal.rsample (amc_dl/torch_plus/train_utils.py:33-34)
  *   z[b*ldz + j] = mu + sd*eps (eps NULL -> z = mu); kl_sum += sum(-log sd + (sd^2+mu^2)/2 - 1/2)
+ *   kl_sum NULL: z alone, from a kernel that computes no KL and reduces nothing (the same z bits)
  * bwd: dmu = dz + klw*mu + dmu_ext ; dsd = dz*eps + klw*(sd - 1/sd) + dsd_ext ; dlv = dsd*sd
  *      (lv = log sd is the linear_var output, ptvae.py:27,120); any of dz/eps/ext may be NULL;
  *      mul_sd = 0 returns dsd itself in `dlv`.
@@ -720,9 +721,18 @@ enum PtvBrbDim { PTV_BRB_D_M = 0, PTV_BRB_D_T, PTV_BRB_D_H, PTV_BRB_D_I, PTV_BRB
 int ptv_bigru_rows_bwd(const void* const* tensors, const long* dims, void* stream);
 
 /* ptv_vae_loss_fwd / ptv_vae_loss_bwd: DisentangleVAE.loss_function (model.py:57-68: PianoTree reconstruction CE x2 with ignore_index, the
- * two KL terms, the three chord CEs, the 11 output scalars) and its backward, one call each -- what functional.VaeLossFn sequences (12 / 9
- * launches).  scal = {beta, w0, w1, B * Z, 8 B, 96 B} as doubles.  PITCH_T / DUR_T / COUNTS: the targets of ptv_pianotree_targets; with
- * d[PTV_VL_D_HAVE_TARGETS] they were computed by the caller already (DisentangleVAE.loss() does, before the decoder). */
+ * two KL terms, the three chord CEs, the 11 output scalars) and its backward, one call each -- what functional.VaeLossFn sequences.
+ * scal = {beta, w0, w1, B * Z, 8 B, 96 B} as doubles.  PITCH_T / DUR_T / COUNTS: the targets of ptv_pianotree_targets; with
+ * d[PTV_VL_D_HAVE_TARGETS] they were computed by the caller already (DisentangleVAE.loss() does, before the decoder).
+ * One launch per direction (csrc/loss.hip: vae_loss_fwd_kernel / vae_loss_bwd_kernel; ptv_pianotree_targets in front when the forward
+ * computes the targets), bit for bit what the launch sequence gives (9 / 8 launches: what runs without an ordered-reduction workspace,
+ * and the backward without REC).
+ * Forward with the nine D* slots and REC: the same launch also writes the gradients for the upstream (1, 0, ..., 0) -- losses[0].backward()
+ * -- and REC, the record of that (upstream vector and beta, as bits, and a valid word; all nine or none; REC is cleared when the launch
+ * sequence ran).  Backward with REC and EARLY: every block compares GOUT and beta with REC; equal bit for bit, the gradients stand in the
+ * D* buffers of that forward already, the launch returns and adds one to EARLY; otherwise it computes the scales and writes every row.
+ * A caller that hands other buffers than the forward's to the backward passes a cleared REC.
+ * On a stream that is being captured both directions are the launch sequence; a forward with REC is PTV_ERR_ARG there. */
 enum PtvVlTensor {
   PTV_VL_X = 0, PTV_VL_C,                                    /* int64 [B,32,16,6], fp32 [B,8,36] */
   PTV_VL_PITCH, PTV_VL_DUR,                                  /* logits in memory order: [480 B, ldp], [2400 B, 2] */
@@ -732,8 +742,10 @@ enum PtvVlTensor {
   PTV_VL_SUMS,            /* fwd: [8] fp32 ZEROED */
   PTV_VL_OUT,             /* fwd out: [11] */
   PTV_VL_GOUT,            /* bwd in: [11] */
-  PTV_VL_GS,              /* bwd scratch: [8] */
-  PTV_VL_DPITCH, PTV_VL_DDUR, PTV_VL_DMU_C, PTV_VL_DSD_C, PTV_VL_DMU_R, PTV_VL_DSD_R, PTV_VL_DROOT, PTV_VL_DCHROMA, PTV_VL_DBASS,   /* bwd out */
+  PTV_VL_GS,              /* bwd scratch: [8]; only the launch sequence (no REC) needs it */
+  PTV_VL_DPITCH, PTV_VL_DDUR, PTV_VL_DMU_C, PTV_VL_DSD_C, PTV_VL_DMU_R, PTV_VL_DSD_R, PTV_VL_DROOT, PTV_VL_DCHROMA, PTV_VL_DBASS,   /* bwd out; fwd out with REC */
+  PTV_VL_REC,             /* [16] 32-bit words: the record of a forward that wrote the gradients, or NULL */
+  PTV_VL_EARLY,           /* bwd with REC: uint32 [1], counts the launches that returned on a matching record */
   PTV_VL_COUNT
 };
 enum PtvVlDim { PTV_VL_D_B = 0, PTV_VL_D_Z, PTV_VL_D_NP, PTV_VL_D_LDP, PTV_VL_D_SM_P, PTV_VL_D_SM_C, PTV_VL_D_HAVE_TARGETS, PTV_VL_D_COUNT };

@@ -90,10 +90,16 @@ OrdScratch ord_scratch(hipStream_t s, long need_floats, int need_counters);     
 
 // Every thread of the block calls it after the block's partial vector part[0..L) (LDS) is complete and visible (caller synced).
 // group = which output vector / counter, idx = this block's position among the n blocks that contribute to it.
-__device__ __forceinline__ void ordered_commit(float* out, const float* part, int L, const OrdScratch& sc, int group, int idx, int n) {
+// -> true (in every thread) in the block that arrived last and added the partials; always false on the atomics.
+// sub, fan > 1: the arrivals are counted in two levels -- block idx bumps sub[(idx % fan) * ORD_SUB_STRIDE], the last arrival there bumps the
+// group's counter -- so thousands of blocks that finish together queue on fan addresses instead of one.  Who adds is still the last
+// block to arrive, and what it adds, in which order, does not depend on who it is.  sub: fan * ORD_SUB_STRIDE zeroed words, left zeroed.
+constexpr int ORD_SUB_STRIDE = 16;
+__device__ __forceinline__ bool ordered_commit(float* out, const float* part, int L, const OrdScratch& sc, int group, int idx, int n,
+                                               unsigned* sub = nullptr, int fan = 0) {
   if (!sc.slots) {
     for (int i = threadIdx.x; i < L; i += blockDim.x) { const float v = part[i]; if (v != 0.f) atomicAdd(out + i, v); }
-    return;
+    return false;
   }
   __shared__ int s_last;
   __shared__ float s_red[16];
@@ -101,9 +107,21 @@ __device__ __forceinline__ void ordered_commit(float* out, const float* part, in
   for (int i = threadIdx.x; i < L; i += blockDim.x) __hip_atomic_store(base + (long)idx * L + i, part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the write-through (sc1) stores above are acknowledged ...
   __syncthreads();
-  if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(sc.counters + group, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(n - 1);
+  if (threadIdx.x == 0) {
+    if (fan > 1 && n > fan) {
+      unsigned* mine = sub + (idx % fan) * ORD_SUB_STRIDE;
+      const unsigned members = (unsigned)((n - idx % fan + fan - 1) / fan);          // blocks that share this word
+      s_last = 0;
+      if (__hip_atomic_fetch_add(mine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1) {
+        __hip_atomic_store(mine, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = __hip_atomic_fetch_add(sc.counters + group, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(fan - 1);
+      }
+    } else {
+      s_last = __hip_atomic_fetch_add(sc.counters + group, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(n - 1);
+    }
+  }
   __syncthreads();
-  if (!s_last) return;
+  if (!s_last) return false;
   if (L == 1) {                                                   // a scalar: the whole block adds (fixed strides + fixed tree = fixed order)
     float s = 0.f;
     for (int b = threadIdx.x; b < n; b += blockDim.x) s += __hip_atomic_load(base + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -131,6 +149,7 @@ __device__ __forceinline__ void ordered_commit(float* out, const float* part, in
     }
   }
   if (threadIdx.x == 0) __hip_atomic_store(sc.counters + group, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
 }
 
 }  // namespace ptv

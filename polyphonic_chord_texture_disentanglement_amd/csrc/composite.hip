@@ -7,6 +7,7 @@
 // bf16 precision at the init_model() sizes (the configuration every persistent / fused kernel below is specialised for); anything
 // else returns PTV_ERR_UNSUPPORTED BEFORE the first launch and the caller sequences the generic entry points itself.
 #include "common.hpp"
+#include "loss_fused.hpp"
 #include "../../include/ptvae_hip.h"
 
 namespace {
@@ -802,8 +803,41 @@ extern "C" int ptv_decoder_free_bwd(const void* const* t_tf, const long* d_tf, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// ptv_vae_loss_fwd / ptv_vae_loss_bwd: functional.VaeLossFn's two launch sequences
+// ptv_vae_loss_fwd / ptv_vae_loss_bwd: functional.VaeLossFn's two directions, one launch each (loss.hip: vae_loss_fused_fwd / _bwd);
+// the launch sequences they replace stay below them as the path without an ordered-reduction workspace and as the reference
 // ---------------------------------------------------------------------------------------------
+static const int VL_GRAD_SLOTS[] = {PTV_VL_DPITCH, PTV_VL_DDUR, PTV_VL_DMU_C, PTV_VL_DSD_C, PTV_VL_DMU_R, PTV_VL_DSD_R, PTV_VL_DROOT, PTV_VL_DCHROMA, PTV_VL_DBASS};
+
+static ptv::VlArgs vl_args(const void* const* t, const long* d, const double* sc, bool grads) {
+  ptv::VlArgs a{};
+  a.pitch = (const float*)T_(t, PTV_VL_PITCH); a.dur = (const float*)T_(t, PTV_VL_DUR);
+  a.mu_c = (const float*)T_(t, PTV_VL_MU_C); a.sd_c = (const float*)T_(t, PTV_VL_SD_C);
+  a.mu_r = (const float*)T_(t, PTV_VL_MU_R); a.sd_r = (const float*)T_(t, PTV_VL_SD_R);
+  a.root = (const float*)T_(t, PTV_VL_ROOT); a.chroma = (const float*)T_(t, PTV_VL_CHROMA); a.bass = (const float*)T_(t, PTV_VL_BASS);
+  a.c = (const float*)T_(t, PTV_VL_C);
+  a.pitch_t = (const int*)T_(t, PTV_VL_PITCH_T); a.dur_t = (const int*)T_(t, PTV_VL_DUR_T); a.counts = (const int*)T_(t, PTV_VL_COUNTS);
+  a.root_t = M_<int>(t, PTV_VL_ROOT_T); a.chroma_t = M_<int>(t, PTV_VL_CHROMA_T); a.bass_t = M_<int>(t, PTV_VL_BASS_T);
+  a.sums = M_<float>(t, PTV_VL_SUMS); a.out = M_<float>(t, PTV_VL_OUT); a.gout = (const float*)T_(t, PTV_VL_GOUT);
+  if (grads) {
+    a.dpitch = M_<float>(t, PTV_VL_DPITCH); a.ddur = M_<float>(t, PTV_VL_DDUR);
+    a.dmu_c = M_<float>(t, PTV_VL_DMU_C); a.dsd_c = M_<float>(t, PTV_VL_DSD_C); a.dmu_r = M_<float>(t, PTV_VL_DMU_R); a.dsd_r = M_<float>(t, PTV_VL_DSD_R);
+    a.droot = M_<float>(t, PTV_VL_DROOT); a.dchroma = M_<float>(t, PTV_VL_DCHROMA); a.dbass = M_<float>(t, PTV_VL_DBASS);
+    a.rec = M_<unsigned>(t, PTV_VL_REC);
+  }
+  a.early = M_<unsigned>(t, PTV_VL_EARLY);
+  a.B = (int)d[PTV_VL_D_B]; a.NP = (int)d[PTV_VL_D_NP]; a.sm_c = (int)d[PTV_VL_D_SM_C];
+  a.rows = (long)a.B * 480; a.ldp = d[PTV_VL_D_LDP]; a.nz = (long)a.B * d[PTV_VL_D_Z];
+  a.beta = (float)sc[0]; a.w0 = (float)sc[1]; a.w1 = (float)sc[2]; a.n_kl = (float)sc[3]; a.n_root = (float)sc[4]; a.n_chroma = (float)sc[5];
+  return a;
+}
+
+// A loss node on a stream that is being captured is the launch sequence in both directions, and its forward writes no gradients: the
+// one-launch kernels are not part of any graph.
+static bool vl_capturing(void* stream) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone;
+}
+
 extern "C" int ptv_vae_loss_fwd(const void* const* t, const long* d, const double* sc, void* stream) {
   if (!t || !d || !sc) return PTV_ERR_ARG;
   const int B = (int)d[PTV_VL_D_B], Z = (int)d[PTV_VL_D_Z], NP = (int)d[PTV_VL_D_NP], sm_p = (int)d[PTV_VL_D_SM_P], sm_c = (int)d[PTV_VL_D_SM_C];
@@ -811,11 +845,21 @@ extern "C" int ptv_vae_loss_fwd(const void* const* t, const long* d, const doubl
   const int need[] = {PTV_VL_X, PTV_VL_C, PTV_VL_PITCH, PTV_VL_DUR, PTV_VL_MU_C, PTV_VL_SD_C, PTV_VL_MU_R, PTV_VL_SD_R, PTV_VL_ROOT, PTV_VL_CHROMA,
                       PTV_VL_BASS, PTV_VL_PITCH_T, PTV_VL_DUR_T, PTV_VL_COUNTS, PTV_VL_ROOT_T, PTV_VL_CHROMA_T, PTV_VL_BASS_T, PTV_VL_SUMS, PTV_VL_OUT};
   for (int i : need) if (!t[i]) return PTV_ERR_ARG;
+  int n_grads = 0;
+  for (int i : VL_GRAD_SLOTS) n_grads += t[i] != nullptr;
+  const bool grads = t[PTV_VL_REC] != nullptr;
+  if (n_grads != (grads ? 9 : 0)) return PTV_ERR_ARG;                     // the gradients and their record: all or none
+  const bool capturing = vl_capturing(stream);
+  if (capturing && grads) return PTV_ERR_ARG;
   if (B <= 0 || Z <= 0 || NP <= 0 || ldp < NP) return PTV_ERR_ARG;
   const long rows = (long)B * 480;
   float* sums = M_<float>(t, PTV_VL_SUMS);
   int* pitch_t = M_<int>(t, PTV_VL_PITCH_T); int* dur_t = M_<int>(t, PTV_VL_DUR_T); int* counts = M_<int>(t, PTV_VL_COUNTS);
   if (!d[PTV_VL_D_HAVE_TARGETS]) PTV_TRY(ptv_pianotree_targets((const long*)T_(t, PTV_VL_X), B, sm_p, pitch_t, dur_t, counts, stream));
+  const int rc = capturing ? PTV_ERR_UNSUPPORTED : ptv::vae_loss_fused_fwd(vl_args(t, d, sc, grads), (hipStream_t)stream);
+  if (rc != PTV_ERR_UNSUPPORTED) return rc;
+  // ---- the launch sequence: no gradients from this forward, and the record says so
+  if (grads && hipMemsetAsync(M_<unsigned>(t, PTV_VL_REC), 0, sizeof(unsigned) * ptv::VL_REC_WORDS, (hipStream_t)stream) != hipSuccess) return PTV_ERR_LAUNCH;
   PTV_TRY(ptv_ce_fwd((const float*)T_(t, PTV_VL_PITCH), ldp, pitch_t, rows, NP, 130, sums + 0, stream));
   PTV_TRY(ptv_ce_fwd((const float*)T_(t, PTV_VL_DUR), 2, dur_t, rows * 5, 2, 2, sums + 1, stream));
   int* root_t = M_<int>(t, PTV_VL_ROOT_T); int* chroma_t = M_<int>(t, PTV_VL_CHROMA_T); int* bass_t = M_<int>(t, PTV_VL_BASS_T);
@@ -834,10 +878,16 @@ extern "C" int ptv_vae_loss_bwd(const void* const* t, const long* d, const doubl
   const int B = (int)d[PTV_VL_D_B], Z = (int)d[PTV_VL_D_Z], NP = (int)d[PTV_VL_D_NP];
   const long ldp = d[PTV_VL_D_LDP];
   const int need[] = {PTV_VL_PITCH, PTV_VL_DUR, PTV_VL_MU_C, PTV_VL_SD_C, PTV_VL_MU_R, PTV_VL_SD_R, PTV_VL_ROOT, PTV_VL_CHROMA, PTV_VL_BASS, PTV_VL_PITCH_T,
-                      PTV_VL_DUR_T, PTV_VL_COUNTS, PTV_VL_ROOT_T, PTV_VL_CHROMA_T, PTV_VL_BASS_T, PTV_VL_GOUT, PTV_VL_GS, PTV_VL_DPITCH, PTV_VL_DDUR,
+                      PTV_VL_DUR_T, PTV_VL_COUNTS, PTV_VL_ROOT_T, PTV_VL_CHROMA_T, PTV_VL_BASS_T, PTV_VL_GOUT, PTV_VL_DPITCH, PTV_VL_DDUR,
                       PTV_VL_DMU_C, PTV_VL_DSD_C, PTV_VL_DMU_R, PTV_VL_DSD_R, PTV_VL_DROOT, PTV_VL_DCHROMA, PTV_VL_DBASS};
   for (int i : need) if (!t[i]) return PTV_ERR_ARG;
   if (B <= 0 || Z <= 0 || NP <= 0 || ldp < NP) return PTV_ERR_ARG;
+  if (t[PTV_VL_REC] && !vl_capturing(stream)) {
+    if (!t[PTV_VL_EARLY]) return PTV_ERR_ARG;
+    const int rc = ptv::vae_loss_fused_bwd(vl_args(t, d, sc, true), (hipStream_t)stream);
+    if (rc != PTV_ERR_UNSUPPORTED) return rc;
+  }
+  if (!t[PTV_VL_GS]) return PTV_ERR_ARG;
   const long rows = (long)B * 480;
   float* gs = M_<float>(t, PTV_VL_GS);
   PTV_TRY(ptv_loss_bwd_scales((const float*)T_(t, PTV_VL_GOUT), (const int*)T_(t, PTV_VL_COUNTS), (float)sc[0], (float)sc[1], (float)sc[2], (float)sc[3],

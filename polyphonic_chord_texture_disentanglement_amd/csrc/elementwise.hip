@@ -390,6 +390,8 @@ __global__ void multihot_bytes_rows_kernel(const unsigned char* __restrict__ mh,
 // ---------------------------------------------------------------------------------------------
 // reparameterisation + KL (train_utils.py:33-34,45-49):  z = mu + std*eps ; kl = mean(-log std + (std^2+mu^2)/2 - 1/2)
 // ---------------------------------------------------------------------------------------------
+// KL false: z alone -- no KL term, no reduction, no workspace (ReparamFn: the loss node computes the KL terms itself)
+template <bool KL>
 __global__ void reparam_kl_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ sd, const float* __restrict__ eps,
                                       float* __restrict__ z, long ldz, float* __restrict__ kl_sum, int B, int Z, OrdScratch sc) {
   __shared__ float red[4];
@@ -399,8 +401,9 @@ __global__ void reparam_kl_fwd_kernel(const float* __restrict__ mu, const float*
     int b = (int)(i / Z), j = (int)(i % Z);
     float m = mu[i], d = sd[i];
     z[(long)b * ldz + j] = m + d * (eps ? eps[i] : 0.f);
-    s += -logf(d) + (d * d + m * m) * 0.5f - 0.5f;
+    if (KL) s += -logf(d) + (d * d + m * m) * 0.5f - 0.5f;
   }
+  if (!KL) return;
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -612,8 +615,10 @@ extern "C" int ptv_multihot_bytes_rows(const unsigned char* mh, void* out, long 
 }
 
 extern "C" int ptv_reparam_kl_fwd(const float* mu, const float* sd, const float* eps, float* z, long ldz, float* kl_sum, int B, int Z, void* stream) {
-  if (!mu || !sd || !z || !kl_sum || B <= 0 || Z <= 0) return PTV_ERR_ARG;
-  hipLaunchKernelGGL(reparam_kl_fwd_kernel, dim3(grid_for((long)B * Z, 256, 256)), dim3(256), 0, (hipStream_t)stream, mu, sd, eps, z, ldz, kl_sum, B, Z, kl_sum ? ord_scratch((hipStream_t)stream, 256, 1) : OrdScratch{nullptr, nullptr});
+  if (!mu || !sd || !z || B <= 0 || Z <= 0) return PTV_ERR_ARG;
+  const dim3 grid(grid_for((long)B * Z, 256, 256));
+  if (kl_sum) hipLaunchKernelGGL((reparam_kl_fwd_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, mu, sd, eps, z, ldz, kl_sum, B, Z, ord_scratch((hipStream_t)stream, 256, 1));
+  else hipLaunchKernelGGL((reparam_kl_fwd_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, mu, sd, eps, z, ldz, kl_sum, B, Z, OrdScratch{nullptr, nullptr});
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

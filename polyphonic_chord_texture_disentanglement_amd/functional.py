@@ -1547,9 +1547,8 @@ class ReparamFn(torch.autograd.Function):
     def forward(ctx, mu, sd, eps):
         B, Z = mu.shape
         z = _empty(B, Z, dev=mu.device)
-        scratch = _zeros(1, dev=mu.device)
-        call('ptv_reparam_kl_fwd', ptr(mu.contiguous()), ptr(sd.contiguous()), ptr(eps), ptr(z), Z, ptr(scratch), B, Z,
-             stream_ptr())
+        # (no KL sum asked for: the loss node computes both KL terms; the kernel then reduces nothing)
+        call('ptv_reparam_kl_fwd', ptr(mu.contiguous()), ptr(sd.contiguous()), ptr(eps), ptr(z), Z, None, B, Z, stream_ptr())
         ctx.save_for_backward(mu, sd, eps)
         return z
 
@@ -2903,39 +2902,81 @@ def _vl_slots(rec):
     return {k.upper(): v for k, v in zip(rec._fields, rec)}
 
 
-def _vae_loss_fwd_composite(L, x, c, sm_p, sm_c, have_targets, sums, out, scal, st):
-    """-> True when ptv_vae_loss_fwd ran on the LossTensors L (have_targets False: it computed pitch_t, dur_t and counts too)"""
+# The forward that writes the gradients too: D (LossGrads in the logits' memory layout) and rec, the 16-word record the kernel leaves of
+# the upstream vector and beta it assumed (enum PtvVlTensor: REC).  The backward's kernel returns at once when its upstream equals the
+# record bit for bit, and counts that in the device word _vl_early(dev) (tests read it: "the shortcut really ran").
+# Not while a stream is being captured: a captured loss node is the launch sequence in both directions, as before the one-launch
+# kernels (ptv_vae_loss_fwd / _bwd decide the same way), without gradient buffers, record or early word.
+VL_REC_WORDS = 16
+_VL_EARLY = {}
+# Grad mode at VaeLossFn.apply.  ctx.needs_input_grad alone does not say whether a gradient will be wanted: it reports requires_grad of
+# the inputs whatever the grad mode is, and inside forward() grad mode is always off.  forward() runs synchronously inside apply() on the
+# calling thread, which is the only reader; a process that calls the node from several threads at once must not rely on it.
+_LOSS_GRAD_MODE = [False]
+
+
+def _vl_early(dev):
+    key = torch.device(dev).index or 0
+    w = _VL_EARLY.get(key)
+    if w is None:
+        w = _VL_EARLY[key] = torch.zeros(1, device=dev, dtype=torch.int32)
+    return w
+
+
+def _loss_grad_buffers(L, sm_p):
+    """-> LossGrads of the LossTensors L as the kernels write them (memory layout of the logits)"""
+    mem, _ = _pianotree_grad_buffers(L.pitch, L.dur, sm_p)
+    return LossGrads(*mem, *(torch.empty_like(t) for t in (L.mu_c, L.sd_c, L.mu_r, L.sd_r, L.root, L.chroma, L.bass)))
+
+
+def _vae_loss_fwd_applies(L, x, c):
+    """ptv_vae_loss_fwd takes these LossTensors (asked before anything is allocated for it)"""
     B = x.shape[0]
     NP = L.pitch.shape[-1]
-    if (x.dtype != torch.int64 or not _vl_ok(c, L.mu_c, L.sd_c, L.mu_r, L.sd_r, L.root, L.chroma, L.bass) or L.pitch.dtype != F32
-            or L.dur.dtype != F32 or not L.dur.is_contiguous() or not _row_dense(L.pitch) or L.pitch.numel() != B * 480 * NP
-            or L.dur.numel() != B * 4800):
-        return False
+    return not (x.dtype != torch.int64 or not _vl_ok(c, L.mu_c, L.sd_c, L.mu_r, L.sd_r, L.root, L.chroma, L.bass) or L.pitch.dtype != F32
+                or L.dur.dtype != F32 or not L.dur.is_contiguous() or not _row_dense(L.pitch) or L.pitch.numel() != B * 480 * NP
+                or L.dur.numel() != B * 4800)
+
+
+def _vae_loss_bwd_applies(gout, L):
+    return gout.dtype == F32 and _row_dense(L.pitch) and L.dur.is_contiguous()
+
+
+def _vae_loss_fwd_composite(L, x, c, sm_p, sm_c, have_targets, sums, out, scal, st, D=None, rec=None):
+    """ptv_vae_loss_fwd on the LossTensors L, which _vae_loss_fwd_applies accepted (have_targets False: it computes pitch_t, dur_t and
+    counts too); with the LossGrads D and rec it also writes the gradients for the upstream (1, 0, ..., 0), or clears rec where it cannot"""
+    B = x.shape[0]
+    NP = L.pitch.shape[-1]
     dims = _VL.dims({'B': B, 'Z': L.mu_c.shape[1], 'NP': NP, 'LDP': L.pitch.stride(-2), 'SM_P': sm_p, 'SM_C': sm_c,
                      'HAVE_TARGETS': have_targets})
-    slots = _VL.pointers(_vl_slots(L), {'X': x, 'C': c, 'SUMS': sums, 'OUT': out})
+    slots = _VL.pointers(_vl_slots(L), {'X': x, 'C': c, 'SUMS': sums, 'OUT': out}, _vl_slots(D) if D is not None else {}, {'REC': rec})
     rc = lib().ptv_vae_loss_fwd(slots, dims, (ctypes.c_double * 6)(*scal), st)
     check(rc, 'ptv_vae_loss_fwd')
     _VL.count()
-    return True
 
 
-def _vae_loss_bwd_composite(gout, gs, L, D, scal, st):
-    """-> True when ptv_vae_loss_bwd wrote the LossGrads D of the LossTensors L"""
-    if gout.dtype != F32 or not _row_dense(L.pitch) or not L.dur.is_contiguous():
-        return False
+def _vae_loss_bwd_composite(gout, gs, L, D, rec, scal, st):
+    """ptv_vae_loss_bwd (_vae_loss_bwd_applies accepted gout and L) leaves the LossGrads D of the LossTensors L: written now, or -- rec
+    matching gout and beta -- by the forward.  rec None: the launch sequence in C (a captured backward)"""
     dims = _VL.dims({'B': L.root_t.numel() // 8, 'Z': L.mu_c.shape[1], 'NP': L.pitch.shape[-1], 'LDP': L.pitch.stride(-2)})
-    slots = _VL.pointers(_vl_slots(L), _vl_slots(D), {'GOUT': gout, 'GS': gs})
+    slots = _VL.pointers(_vl_slots(L), _vl_slots(D), {'GOUT': gout, 'GS': gs, 'REC': rec, 'EARLY': _vl_early(gout.device) if rec is not None else None})
     rc = lib().ptv_vae_loss_bwd(slots, dims, (ctypes.c_double * 6)(*scal), st)
     check(rc, 'ptv_vae_loss_bwd')
     _VL.count('bwd_calls')
-    return True
 
 
 class VaeLossFn(torch.autograd.Function):
     """(pitch [B,32,15,130], dur [B,32,15,5,2], mu_c, sd_c, mu_r, sd_r, root [B,8,12], chroma [B,8,12,2],
     bass [B,8,12], x, c, beta, w0, w1, weighted_dur, live (loss()'s LiveRows plan: the targets of x in the logits' row order) or None)
-    -> the 11 scalars of model.py:67-68 as one [11] tensor."""
+    -> the 11 scalars of model.py:67-68 as one [11] tensor.
+    When a gradient will be wanted (grad mode on, some input requires one) the composite forward writes the nine gradients for
+    losses[0].backward() in the same launch; they live on the node (ctx.fused = [LossGrads, record]) until its first backward, whose one
+    launch returns at once if the upstream is what the forward assumed and recomputes them otherwise."""
+
+    @classmethod
+    def apply(cls, *args):
+        _LOSS_GRAD_MODE[0] = torch.is_grad_enabled()
+        return super(VaeLossFn, cls).apply(*args)
 
     @staticmethod
     def forward(ctx, pitch, dur, mu_c, sd_c, mu_r, sd_r, root, chroma, bass, x, c, beta, w0, w1, weighted_dur=False, live=None):
@@ -2964,7 +3005,16 @@ class VaeLossFn(torch.autograd.Function):
         out = _empty(11, dev=dev)
         scal = (float(beta), float(w0), float(w1), float(B * mu_c.shape[1]), float(B * 8), float(B * 96))
         gcnt = None
-        if not (LOSS_COMPOSITE and not weighted_dur and _vae_loss_fwd_composite(L, x, c, sm_p, sm_c, have, sums, out, scal, st)):
+        composite = LOSS_COMPOSITE and not weighted_dur and _vae_loss_fwd_applies(L, x, c)
+        ctx.fused = None
+        if composite:
+            D = rec = None
+            if _LOSS_GRAD_MODE[0] and any(ctx.needs_input_grad[:9]) and not torch.cuda.is_current_stream_capturing():
+                D, rec = _loss_grad_buffers(L, sm_p), _empty(VL_REC_WORDS, dev=dev)
+                _VL.count('fwd_grads')
+                ctx.fused = [D, rec]
+            _vae_loss_fwd_composite(L, x, c, sm_p, sm_c, have, sums, out, scal, st, D, rec)
+        else:
             gcnt = _pianotree_ce_fwd(pitch_m, dur_m, sm_p, x, sums, st, weighted_dur, (L.pitch_t, L.dur_t, L.counts), not have)
             small()                               # (on a sibling stream beside the PianoTree cross-entropy: 8.298 against 8.302 ms -- in line)
             call('ptv_loss_finalize', ptr(sums), ptr(L.counts), *scal, ptr(out), st)
@@ -2978,16 +3028,27 @@ class VaeLossFn(torch.autograd.Function):
         st = stream_ptr()
         reset_deferred()                        # first node of the backward pass: nothing may be left from an aborted one
         gs = _empty(8, dev=L.pitch.device)
-        mem, (dpitch, ddur) = _pianotree_grad_buffers(L.pitch, L.dur, S.sm_p)
-        D = LossGrads(*mem, *(torch.empty_like(t) for t in (L.mu_c, L.sd_c, L.mu_r, L.sd_r, L.root, L.chroma, L.bass)))
+        # the first backward takes the buffers the forward wrote; a later one (retained graph) fresh ones and a cleared record: the decoder's
+        # backward has updated dpitch in place by then
         gout = gout.contiguous()
+        composite = LOSS_COMPOSITE and S.gcnt is None and _vae_loss_bwd_applies(gout, L)
+        fused, ctx.fused = getattr(ctx, 'fused', None), None
+        D, rec = fused if fused is not None else (_loss_grad_buffers(L, S.sm_p), None)
+        if not composite or torch.cuda.is_current_stream_capturing():
+            rec = None                                               # (the launch sequence writes every row of D whatever the forward left)
+        elif rec is None:
+            rec = _zeros(VL_REC_WORDS, dev=L.pitch.device)
+        dpitch, ddur = (D.dpitch.permute(*_PERM[4]), D.ddur.permute(*_PERM[5])) if S.sm_p else (D.dpitch, D.ddur)
+        mem = (D.dpitch, D.ddur)
 
         def small():
             st2 = stream_ptr()
             call('ptv_kl_bwd', ptr(L.mu_c), ptr(L.sd_c), L.mu_c.numel(), ptr(gs[2:]), ptr(D.dmu_c), ptr(D.dsd_c), st2)
             call('ptv_kl_bwd', ptr(L.mu_r), ptr(L.sd_r), L.mu_r.numel(), ptr(gs[3:]), ptr(D.dmu_r), ptr(D.dsd_r), st2)
             _chord_ce_bwd(L.root, L.chroma, L.bass, (L.root_t, L.chroma_t, L.bass_t), gs, (D.droot, D.dchroma, D.dbass), st2)
-        if not (LOSS_COMPOSITE and S.gcnt is None and _vae_loss_bwd_composite(gout, gs, L, D, S.scal, st)):
+        if composite:
+            _vae_loss_bwd_composite(gout, gs, L, D, rec, S.scal, st)
+        else:
             call('ptv_loss_bwd_scales', ptr(gout), ptr(L.counts), *S.scal, ptr(gs), st)
             _pianotree_ce_bwd(L.pitch, L.dur, L.pitch_t, L.dur_t, gs, st, S.gcnt, *mem)
             small()

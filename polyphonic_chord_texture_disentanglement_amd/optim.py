@@ -188,6 +188,8 @@ def reserve_step_memory(batch, device=None, gb_per_512=(12.0, 3.0)):
     the allocator grows by hipMalloc (a device-wide synchronisation, ~70 ms) for as long as the step's working set keeps changing: measured
     at B = 512 a step around the seventh takes 77 ms instead of 7 (the first full garbage collection frees reference cycles that held
     blocks until then).  Sizes: the steady state at B = 512 holds 5.6 GB on the step's stream and <= 1.7 GB per pool stream; HBM is 288 GB.
+    (The loss node's forward writes its gradients: about 144 MB at B = 512, dpitch and ddur, are allocated in the loss forward and live
+    until its backward instead of being allocated there -- the same blocks of the same stream, held a little longer.  Reasoned, not measured: the step's peak lies in the decoder's backward, where these buffers were live before too.)
     Returns the bytes reserved."""
     from . import functional as F_
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
