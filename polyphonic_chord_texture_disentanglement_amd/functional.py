@@ -332,28 +332,32 @@ def _gru_flags(gates=None, gi=None, gi2=None, dg=None, w=None, ext=None):
 # the same time: every launch waits for the event of the previous one, whatever stream that ran on.
 # ---------------------------------------------------------------------------------------------
 _PERSIST_LAST = {}          # device index -> event recorded after the last persistent launch
-# A backward node that is itself one C entry point made of other composites (functional_free.DecoderStepFn.backward ->
-# ptv_decoder_free_bwd) COLLECTS its stages instead of launching them: while _DEFER is a list, every stage appends (kind, payload, thunk)
-# -- payload = the C tables (and the tensors they point to, kept alive), thunk = the launch as it would have run here.  A stage that cannot
-# go behind the C ABI flushes first (the thunks run, in order, and collecting stops): nothing is ever reordered.
-_DEFER = None
 
 
-def _defer_or_run(kind, payload, thunk):
-    if _DEFER is not None:
-        _DEFER.append((kind, payload, thunk))
-        return 0
-    return thunk()
+class PreparedCall:
+    """A backward composite with its tables built and nothing launched.  launch() runs the entry point; ran_inside() is for a caller that
+    handed `ptrs` / `dims` to an enclosing C call which ran it (only functional_free.DecoderStepFn.backward -> ptv_decoder_free_bwd prepares
+    without launching).  Either way `booked` -- the host's record of launches that went out: the persistent turn, the call counter, the
+    side stream's state -- runs after them, never before.  Lifetime: the tables hold raw pointers and hipEvent_t handles, so `keep`
+    references what they point to (the tensors, the turn's previous and own event, the fork events) and the record lives until one of the
+    two has returned: a destroyed hipEvent_t in a table was a segfault.  The tables take the persistent turn as it stood (_CompositeTurn
+    reads _PERSIST_LAST): no persistent launch may go out between preparing and launching."""
+    def __init__(self, fn, ptrs, dims, keep, booked):
+        self.fn, self.ptrs, self.dims, self.stream, self.keep, self.booked = fn, ptrs, dims, stream_ptr(), keep, booked
 
+    def launch(self):
+        self.after(self.fn(self.ptrs, self.dims, self.stream))
 
-def _defer_flush():
-    """run what was collected so far, in order, and stop collecting"""
-    global _DEFER
-    items, _DEFER = _DEFER, None
-    for kind, payload, thunk in items or ():
-        rc = thunk()
-        if isinstance(rc, int):
-            check(rc, 'deferred ' + kind)
+    def ran_inside(self, rc, inside):
+        self.after(rc, inside)
+
+    def after(self, rc, what=None):
+        what = what or self.fn.__name__
+        _SIDE_DEPTH[1] = 1                # (the library's priority state as the call leaves it)
+        if rc == -3:                      # (the Python-side checks mirror the entry point's: a late refusal would leave taken arena views behind)
+            raise RuntimeError('%s refused a configuration its Python-side checks accepted' % what)
+        check(rc, what)
+        self.booked()
 
 
 _PERSIST_SYNC = []          # (sync words, error index) of recent launches, for persist_check()
@@ -1161,11 +1165,16 @@ def _bigru_rows_fwd_composite(x3, lengths, skip_by, perm, seg, w, out, side, T, 
     return BiGruState('rows', dirs, skip_by, perm, seg)
 
 
-def _bigru_rows_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, side, T, M, I, H):
-    """-> _bigru_backward's result when ptv_bigru_rows_bwd took the 'rows' BiGruState `state` back through the row kernels (launched, or
-    collected while _DEFER is a list), else None (the caller flushes)"""
+def bigru_rows_bwd_prepare(prec, x3, w, state, dout, need_dx, dx_acc=None, side=None):
+    """-> (PreparedCall of ptv_bigru_rows_bwd, _bigru_backward's result once it has run) when that entry point can take the 'rows' BiGruState
+    `state` back, else None: nothing was allocated, _bigru_backward launches kernel by kernel.  side: its sibling-stream handle (None: its default)"""
+    T, M, I = x3.shape
+    H = w[1].shape[1]
     dev = x3.device
-    if (prec != 1 or not OVERLAP or side.s == side.main or torch.cuda.is_current_stream_capturing() or H != 128 or I != 128 or T * M < 512
+    xf = x3.reshape(T * M, I)
+    side = Side(BIGRU_SLOT_BWD) if side is None else side
+    if (not BIGRU_BWD_COMPOSITE or state.branch != 'rows' or not (NOTES_PERSIST and BF16_STORAGE)
+            or prec != 1 or not OVERLAP or side.s == side.main or torch.cuda.is_current_stream_capturing() or H != 128 or I != 128 or T * M < 512
             or xf.dtype != F32 or xf.stride(1) != 1 or xf.stride(0) != I or dout.dtype != F32 or dout.stride(1) != 1):
         return None
     wt_ih = [_WT(w[0], prec), _WT(w[4], prec)] if need_dx else [None, None]
@@ -1185,14 +1194,9 @@ def _bigru_rows_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, sid
     arr_ = _BRB.pointers(tens, dict(zip(_BIGRU_G, G)),
                          handles={'FORK_EVENT': evs[0].cuda_event, 'JOIN_EVENT': evs[1].cuda_event, 'SIDE_STREAM': side.s.cuda_stream})
     darr_ = _BRB.dims({'M': M, 'T': T, 'H': H, 'I': I, 'DX_ACC': dx_acc is not None, 'DOUT_LD': dout.stride(0)})
-    sp_ = stream_ptr()
-    rc = _defer_or_run('rows_bwd', (arr_, darr_, (tens, G, state, dout, xf)), lambda: lib().ptv_bigru_rows_bwd(arr_, darr_, sp_))
-    _SIDE_DEPTH[1] = 1
-    if rc == -3:                          # (H = I = 128 was checked above: ptv_bigru_rows_bwd's only refusal)
-        raise RuntimeError('ptv_bigru_rows_bwd refused a configuration its Python-side checks accepted')
-    check(rc, 'ptv_bigru_rows_bwd')
-    _BRB.count()
-    return G[0:4] + G[4:8], (dx.view(T, M, I) if need_dx else None)
+    # (H = I = 128 was checked above: ptv_bigru_rows_bwd's only refusal)
+    return (PreparedCall(lib().ptv_bigru_rows_bwd, arr_, darr_, (tens, G, state, dout, xf, evs), _BRB.count),
+            (G[0:4] + G[4:8], (dx.view(T, M, I) if need_dx else None)))
 
 
 def _bigru_fwd_composite(prec, xf, lengths, w, w16, out, T, M, I, H, dev):
@@ -1377,15 +1381,15 @@ def _bigru_backward(prec, x3, w, state, dout, need_dx, dx_acc=None, rev_slot=Non
         return [dw_ih, dw_hh, db_ih, db_hh], (dx_of(0, dgi2, top, True) if d == 0 else None)
 
     side = Side(BIGRU_SLOT_BWD if rev_slot is None else rev_slot)
-    res = None
     if BIGRU_BWD_COMPOSITE and branch == 'rows':
-        res = _bigru_rows_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, side, T, M, I, H)
-    if res is None:
-        _defer_flush()                    # (only the row-kernel composite can be collected: whatever else runs launches at once)
-        if BIGRU_BWD_COMPOSITE and branch == 'persist':
-            res = _bigru_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, wts, side, T, M, I, H)
-    if res is not None:
-        return res
+        prepared = bigru_rows_bwd_prepare(prec, x3, w, state, dout, need_dx, dx_acc, side)
+        if prepared is not None:
+            prepared[0].launch()
+            return prepared[1]
+    if BIGRU_BWD_COMPOSITE and branch == 'persist':
+        res = _bigru_bwd_composite(prec, x3, xf, w, state, dout, need_dx, dx_acc, wts, side, T, M, I, H)
+        if res is not None:
+            return res
     if branch == 'persist':
         # BPTT of both directions in ONE persistent launch, then the weight-gradient products of the two on sibling streams
         chains = []
@@ -2112,11 +2116,11 @@ def decoder_bwd_composite_static_ok(prec, B, Ht, Hn, NP, Hd, E, P=None):
                 'z2dec_hid_linear.weight', 'z2dec_in_linear.weight'))))
 
 
-DecoderGrads = collections.namedtuple('DecoderGrads', 'dz dtok dTOKS G side ev_dtoks')       # decoder_bwd_core's result
+DecoderGrads = collections.namedtuple('DecoderGrads', 'dz dtok dTOKS G side ev_dtoks call', defaults=(None,))    # decoder_bwd_core's result
 
 
-def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
-    """-> decoder_bwd_core's result when ptv_decoder_tf_bwd ran the whole sequence, else None (the caller sequences it: same bits)"""
+def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G, launch):
+    """-> decoder_bwd_core's result when ptv_decoder_tf_bwd takes the whole sequence (launch False: left in `call`), else None (the caller sequences it)"""
     B, R, E, He, Ht, Hn, Hd, NP, prec = st.B, st.R, st.E, st.He, st.Ht, st.Hn, st.Hd, st.NP, st.prec
     dev = z.device
     M = 15 * R
@@ -2126,7 +2130,6 @@ def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
             or (st.notes, st.heads, st.dur) != ('rows', 'fused', 'fused16') or st.gates_d is not None or st.NS16 is None
             or dP.stride(0) != _pad8(NP) or dP.data_ptr() % 16 or not ddur.is_contiguous() or ddur.dtype != F32
             or tok_op.dtype != F32 or not tok_op.is_contiguous() or z.dtype != F32 or not z.is_contiguous() or side.s == side.main):
-        _defer_flush()
         return None
     wts = [_WT(P[n], prec) for n in ('dec_notes_gru.weight_ih_l0', 'dec_time_to_notes_hid.weight', 'dec_time_gru.weight_ih_l0',
                                       'dec_time_gru.weight_hh_l0', 'z2dec_hid_linear.weight', 'z2dec_in_linear.weight')]
@@ -2170,25 +2173,21 @@ def _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G):
                          handles={'FORK_EVENT0': evs[0].cuda_event, 'FORK_EVENT1': evs[1].cuda_event, 'FORK_EVENT2': evs[2].cuda_event,
                                   'FORK_EVENT3': evs[3].cuda_event, 'SIDE_STREAM': side.s.cuda_stream, **turn.handles})
     mark('dec_bwd:composite')
-    darr_, sp_ = _DTB.dims(dims), stream_ptr()
-    # (payload: the tables AND everything they point to that nothing else keeps alive until a collected call runs -- the tensors, and the
-    # previous persistent launch's event, which turn.taken() drops from _PERSIST_LAST below: a destroyed hipEvent_t in the table was a
-    # segfault)
-    rc = _defer_or_run('tf_bwd', (arr_, darr_, tens, turn.prev, turn.done, evs), lambda: lib().ptv_decoder_tf_bwd(arr_, darr_, sp_))
-    _SIDE_DEPTH[1] = 1                    # (the library's priority state as the call leaves it)
-    if rc == -3:                          # (the checks above mirror ptv_decoder_tf_bwd's: a late refusal would leave taken arena views behind)
-        raise RuntimeError('ptv_decoder_tf_bwd refused a configuration its Python-side checks accepted')
-    check(rc, 'ptv_decoder_tf_bwd')
-    turn.taken()
-    _DTB.count()
-    # the sibling stream's products are queued, not run: everything they read or write stays referenced until the join (the caller defers
-    # it to the end of the backward pass) -- EXCEPT the gradient buffers (a second reference makes AccumulateGrad clone them)
-    side.used = True
-    side.keep.extend([v for k, v in tens.items() if v is not None] + [st, z, tok_op])
-    return DecoderGrads(dz, dtok, dTOKS, G, side, None)
+
+    def booked():
+        turn.taken()
+        _DTB.count()
+        # the sibling stream's products are queued, not run: everything they read or write stays referenced until the join (the caller
+        # defers it to the end of the backward pass) -- EXCEPT the gradient buffers (a second reference makes AccumulateGrad clone them)
+        side.used = True
+        side.keep.extend([v for k, v in tens.items() if v is not None] + [st, z, tok_op])
+    prepared = PreparedCall(lib().ptv_decoder_tf_bwd, arr_, _DTB.dims(dims), (tens, turn.prev, turn.done, evs), booked)
+    if launch:
+        prepared.launch()
+    return DecoderGrads(dz, dtok, dTOKS, G, side, None, None if launch else prepared)
 
 
-def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
+def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur, launch=True):
     """BPTT of the PianoTree decoder given the forward's DecoderState `st`, whose branch names select the code below -- shared by the teacher-forced node (DecoderTFFn) and
     the step-loop node (functional_free.DecoderStepFn: argmax is not differentiable, so with the fed tokens recorded every
     chain is the same batched BPTT).  Chain (duration GRU -> heads -> notes GRU -> time GRU -> z) on the caller's stream; every
@@ -2197,7 +2196,8 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
       tok_op [15*R, E]: the note tokens that were FED to the notes GRU (ground-truth embedding rows, or the recorded mix)
     -> DecoderGrads(dz, dtok [16,R,E] gradient w.r.t. the fed note tokens (slot 15 zero), dTOKS [33,B,2He] gradient w.r.t. the time-step
         tokens, G parameter gradients by name, side stream handle -- the caller joins or defers it, ev_dtoks: the event after which dTOKS
-        is final when the note-summary family waits for one, else None)"""
+        is final when the note-summary family waits for one, else None, call: None, or with launch=False (functional_free.DecoderStepFn.backward) the
+        PreparedCall of a pass the composite took and the caller has yet to send out; a pass it declined was launched kernel by kernel here)"""
     B, R, E, He, Ht, Hn, Hd, NP, prec = st.B, st.R, st.E, st.He, st.Ht, st.Hn, st.Hd, st.NP, st.prec
     if st.notes == 'rows' and not notes_persist_ok(prec, Hn, E):
         raise RuntimeError("decoder backward: the forward ran on the row kernel (DecoderState.notes == 'rows') and it cannot run now "
@@ -2264,13 +2264,12 @@ def decoder_bwd_core(P, st, z, tok_op, dpitch, ddur):
             call('ptv_last_nonzero_unit', ptr(dP), M, NP, dP.stride(0), R, ptr(top_h), stream_ptr())
             call('ptv_last_nonzero_unit', ptr(ddur), M, 10, 10, R, ptr(top_h), stream_ptr())
 
-    res = _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G)
+    res = _decoder_bwd_composite(P, st, z, tok_op, dP, ddur, top_h, side, G, launch)
     if res is not None:
         return res
     if st.sorted is not None:
         raise RuntimeError('the decoder forward ran on length-sorted rows (PTV_SORT_DEC_ROWS) but ptv_decoder_tf_bwd, the only place that '
                            'restores the row order, declined this backward pass')
-    _defer_flush()                        # (the launch-by-launch sequencing below runs at once)
 
     # ---- duration GRU (5 steps) ----
     w_out = P['dur_out_linear.weight']

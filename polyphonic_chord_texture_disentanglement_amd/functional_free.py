@@ -71,7 +71,7 @@ FREE_PERSIST = True
 FREE_COMPOSITE = os.environ.get('PTV_FREE_COMPOSITE', '1') != '0'
 _DFF, _DFB = SlotTable('DFF'), SlotTable('DFB')
 _DFF_KEEP = []              # what the last ptv_decoder_free_fwd call points to: its launches are queued, not run, when the call returns
-_DFB_FLUSHED = []           # (diagnostic) why the last DecoderStepFn.backward did not go through ptv_decoder_free_bwd as one call
+_DFB_PATH = ''              # (diagnostic) the last DecoderStepFn.backward: 'one call' (ptv_decoder_free_bwd), else the first reason against it
 # training forward of the step loop: the panels store only decisions, logits and fed tokens; states and gates the backward needs are
 # recomputed afterwards for all 480*B rows at once by the teacher-forced kernels (same tokens, same decisions forced)
 FREE_REPLAY = True
@@ -1151,20 +1151,46 @@ def _free_recompute(plan, P, buf, tbl, prec):
                  ptr(buf.plen), ptr(buf.XH[d]), ptr(buf.XH16[d]), ptr(buf.XG[d]), None, 0, R, 16, d, st)
 
 
-def _decoder_free_bwd_call(items, dTOK, dTOKS, demb, dPRED, dxs, dxsp, mask_tok, mask_time, dx_pred, xhat, mh, gw, gb, B, E, He):
-    """the collected stages of DecoderStepFn.backward through ptv_decoder_free_bwd (one C call); True when it ran"""
-    tf = [p for k, p, _ in items if k == 'tf_bwd'][0]
-    rows = [p for k, p, _ in items if k == 'rows_bwd']
-    if dx_pred is not None and not dx_pred.is_contiguous():
-        return False
-    slots = _DFB.pointers({'DTOK': dTOK, 'DTOKS': dTOKS, 'DEMB': demb, 'DPRED': dPRED, 'DXS': dxs, 'DXSP': dxsp, 'MASK_TOK': mask_tok,
-                           'MASK_TIME': mask_time, 'DX_PRED': dx_pred, 'XHAT': xhat, 'MH': mh, 'G_W_EMB': gw, 'G_B_EMB': gb})
-    F_._chain_prio()
-    rc = lib().ptv_decoder_free_bwd(tf[0], tf[1], rows[0][0] if rows else None, rows[0][1] if rows else None, slots,
-                                    _DFB.dims({'B': B, 'E': E, 'HE': He}), stream_ptr())
-    F_.check(rc, 'ptv_decoder_free_bwd')
-    _DFF.count('bcalls')                # (counted beside the forward's)
-    return True
+def _free_bwd_switch_off(prec):
+    """the first switch that keeps DecoderStepFn.backward from asking for its one-call form (ptv_decoder_free_bwd), or None"""
+    for on, word in ((FREE_COMPOSITE, 'FREE_COMPOSITE off'), (prec == 1, 'not bf16'), (F_.DEC_BWD_COMPOSITE, 'DEC_BWD_COMPOSITE off'),
+                     (F_.BIGRU_BWD_COMPOSITE, 'BIGRU_BWD_COMPOSITE off'), (F_.WGRAD_FUSE_BIAS, 'WGRAD_FUSE_BIAS off')):
+        if not on:
+            return word
+    return 'capturing' if torch.cuda.is_current_stream_capturing() else None
+
+
+class FreeRoutes:
+    """where DecoderStepFn.backward routes the token gradients: demb / dPRED [16,R,E] the note tokens' -- ground-truth embedding (coin true / slot 0)
+    vs predicted tokens -- and dxs / dxsp [32,B,2He] the time tokens' -- ground-truth summaries (coin true) vs re-summarised predictions"""
+
+    def __init__(self, st, dev):
+        coin_notes, coin_time = st.coins
+        self.demb, self.dPRED = _zeros(16, st.R, st.E, dev=dev), _zeros(16, st.R, st.E, dev=dev)
+        self.mask_tok = _route_mask(('tok', tuple(tuple(bool(v) for v in row) for row in coin_notes)), dev)
+        self.dxs, self.dxsp = _zeros(32, st.B, 2 * st.He, dev=dev), _zeros(32, st.B, 2 * st.He, dev=dev)
+        self.mask_time = _route_mask(('time', tuple(bool(v) for v in coin_time)), dev)
+
+
+def _free_bwd_route(st, tf, rt):
+    sp = stream_ptr()
+    call('ptv_route_slices', ptr(tf.dtok), ptr(rt.demb), ptr(rt.dPRED), ptr(rt.mask_tok), st.B * st.E, 15 * 32, 0, sp)
+    call('ptv_route_slices', ptr(tf.dTOKS[1:]), ptr(rt.dxs), ptr(rt.dxsp), ptr(rt.mask_time), st.B * 2 * st.He, 32, 0, sp)
+
+
+def _free_resum_operands(P, st):
+    """-> the re-summarisation bi-GRU's weights and the BiGruState its backward reads"""
+    wE = [P['dec_notes_emb_gru.' + n] for n in EMB_GRU]
+    # (the batched recompute ran the row kernels -- they left bf16 states -- and skipped dead panel steps by plen)
+    return wE, BiGruState('rows' if st.XH16[0] is not None else 'step', zip(st.XH, st.XG, st.XH16), lengths=st.plen if st.skipped else None)
+
+
+def _free_bwd_tail(st, rt, mh, gw, gb):
+    """predicted tokens -> note_embedding (slot 0 is the ground-truth <sos> embedding); weight and bias gradient in ONE pass (ptv_wgrad's colsum_a)"""
+    copy2d(rt.demb[0], rt.dPRED[0], acc=True)
+    rt.dPRED[0].zero_()
+    call('ptv_multihot', ptr(st.xhat), ptr(mh), 136, st.B, stream_ptr())
+    F_.wgrad_bias(rt.dPRED.view(16 * st.R, st.E), mh[:, :135], gw, gb, st.prec)
 
 
 class DecoderStepState(F_.DecoderState):
@@ -1237,83 +1263,57 @@ class DecoderStepFn(torch.autograd.Function):
         st = ctx.saved_state
         if not getattr(ctx, 'keep_state', False):        # a captured forward (GraphedDecoderStepFn) reuses its buffers
             ctx.saved_state = None
-        B, R, E, He, prec = st.B, st.R, st.E, st.He, st.prec
-        dev = z.device
-        M = 15 * R
-        PRED = st.PRED
-        coin_notes, coin_time = st.coins
-        sp = stream_ptr()
-        # ---- the node behind ONE C entry point (ptv_decoder_free_bwd): its stages are COLLECTED (functional._DEFER) instead of launched -- the
-        # decoder's composite backward, the two routings, the re-summarisation bi-GRU's composite backward, the note_embedding gradients --
-        # and go out as one call; a stage that cannot go behind the C ABI flushes what was collected and the rest launches at once (same
-        # order, same bits either way)
-        collect = (FREE_COMPOSITE and prec == 1 and F_.DEC_BWD_COMPOSITE and F_.BIGRU_BWD_COMPOSITE and F_.WGRAD_FUSE_BIAS
-                   and not torch.cuda.is_current_stream_capturing() and F_._DEFER is None)
-        if collect:
-            F_._DEFER = []
-        try:
-            # ---- duration GRU, heads, notes GRU, time GRU: the batched BPTT of the teacher-forced path on the recorded fed tokens
-            dz, dTOK, dTOKS, G0, side, _ = F_.decoder_bwd_core(P, st, z, st.TOK.view(M, E), dpitch, ddur)
-            G = {n: None for n in FREE_PARAM_NAMES}
-            G.update(G0)
-
-            # ---- route token gradients: ground-truth embedding (coin true / slot 0) vs predicted tokens
-            demb = _zeros(16, R, E, dev=dev)
-            dPRED = _zeros(16, R, E, dev=dev)
-            mask_tok = _route_mask(('tok', tuple(tuple(bool(v) for v in row) for row in coin_notes)), dev)
-            F_._defer_or_run('route', None, lambda: call('ptv_route_slices', ptr(dTOK), ptr(demb), ptr(dPRED), ptr(mask_tok), B * E, 15 * 32, 0, sp))
-
-            # ---- time tokens: ground-truth summaries (coin true) vs re-summarised predictions
-            dxs = _zeros(32, B, 2 * He, dev=dev)
-            dxsp = _zeros(32, B, 2 * He, dev=dev)
-            mask_time = _route_mask(('time', tuple(bool(v) for v in coin_time)), dev)
-            F_._defer_or_run('route', None, lambda: call('ptv_route_slices', ptr(dTOKS[1:]), ptr(dxs), ptr(dxsp), ptr(mask_time), B * 2 * He, 32, 0, sp))
-            dx_pred = None
+        global _DFB_PATH
+        B, R, E, He, prec, dev = st.B, st.R, st.E, st.He, st.prec, z.device
+        # ---- the stages, in order: the decoder's batched BPTT (duration GRU, heads, notes GRU, time GRU: the teacher-forced path's, on the
+        # recorded fed tokens), the two routings, the re-summarisation bi-GRU's backward and its accumulate, the note_embedding gradients.
+        # They go out as ONE C call (ptv_decoder_free_bwd) when no switch is off and both composite stages come back prepared, else stage
+        # by stage: same launches, same order, same bits.  `why`: the first reason against the one call
+        why = _free_bwd_switch_off(prec)
+        tf = F_.decoder_bwd_core(P, st, z, st.TOK.view(15 * R, E), dpitch, ddur, launch=why is not None)
+        if why is None and tf.call is None:
+            why = 'decoder stage declined'
+        G = {**dict.fromkeys(FREE_PARAM_NAMES), **tf.G}
+        rt = FreeRoutes(st, dev)
+        rows, dout = None, rt.dxsp.view(R, 2 * He)
+        if st.XH is not None:
+            wE, state = _free_resum_operands(P, st)
+            if why is None:                # (prepared before anything is launched: it reads dxsp, which the second route writes)
+                rows = F_.bigru_rows_bwd_prepare(prec, st.PRED, wE, state, dout, True)
+                if rows is None or not rows[1][1].is_contiguous():
+                    why = 'rows stage declined' if rows is None else 'dx_pred not contiguous'
+        mh = _empty(B * 512, 136, dev=dev)
+        for n in ('note_embedding.weight', 'note_embedding.bias'):
+            if G[n] is None:
+                G[n] = _gbuf(P[n])
+        gw, gb = G['note_embedding.weight'], G['note_embedding.bias']
+        _DFB_PATH = why or 'one call'
+        ge, dx_pred = rows[1] if rows else ((), None)
+        if why is None:
+            slots = _DFB.pointers({'DTOK': tf.dtok, 'DTOKS': tf.dTOKS, 'DEMB': rt.demb, 'DPRED': rt.dPRED, 'DXS': rt.dxs, 'DXSP': rt.dxsp,
+                                   'MASK_TOK': rt.mask_tok, 'MASK_TIME': rt.mask_time, 'DX_PRED': dx_pred, 'XHAT': st.xhat, 'MH': mh,
+                                   'G_W_EMB': gw, 'G_B_EMB': gb})
+            F_._chain_prio()
+            rc = lib().ptv_decoder_free_bwd(tf.call.ptrs, tf.call.dims, rows[0].ptrs if rows else None, rows[0].dims if rows else None, slots,
+                                            _DFB.dims({'B': B, 'E': E, 'HE': He}), stream_ptr())
+            for c in (tf.call,) + ((rows[0],) if rows else ()):
+                c.ran_inside(rc, 'ptv_decoder_free_bwd')
+            _DFF.count('bcalls')                # (counted beside the forward's)
+        else:
+            if tf.call is not None:
+                tf.call.launch()
+            _free_bwd_route(st, tf, rt)
             if st.XH is not None:
-                wE = [P['dec_notes_emb_gru.' + n] for n in EMB_GRU]
-                # (the batched recompute ran the row kernels -- they left bf16 states -- and skipped dead panel steps by plen)
-                state = BiGruState('rows' if st.XH16[0] is not None else 'step', zip(st.XH, st.XG, st.XH16),
-                                   lengths=st.plen if st.skipped else None)
-                ge, dx_pred = _bigru_backward(prec, PRED, wE, state, dxsp.view(R, 2 * He), True)
-                for n, gg in zip(EMB_GRU, ge):
-                    G['dec_notes_emb_gru.' + n] = gg
-                F_._defer_or_run('copy', None, lambda: copy2d(dPRED.view(16 * R, E), dx_pred.view(16 * R, E), acc=True))
-
-            # ---- predicted tokens -> note_embedding (slot 0 is the ground-truth <sos> embedding); weight and bias gradient in ONE pass
-            # over the gradient matrix (ptv_wgrad's colsum_a)
-            mh = _empty(B * 512, 136, dev=dev)
-            for n in ('note_embedding.weight', 'note_embedding.bias'):
-                if G[n] is None:
-                    G[n] = _gbuf(P[n])
-
-            def tail():
-                copy2d(demb[0], dPRED[0], acc=True)
-                dPRED[0].zero_()
-                call('ptv_multihot', ptr(st.xhat), ptr(mh), 136, B, sp)
-                F_.wgrad_bias(dPRED.view(16 * R, E), mh[:, :135], G['note_embedding.weight'], G['note_embedding.bias'], prec)
-            F_._defer_or_run('tail', None, tail)
-            items = F_._DEFER
-            if items is None and collect:
-                _DFB_FLUSHED[:] = ['a stage flushed']
-            if items is not None:
-                F_._DEFER = None
-                kinds = [k for k, _, _ in items]
-                want = ['tf_bwd', 'route', 'route'] + (['rows_bwd', 'copy'] if dx_pred is not None else []) + ['tail']
-                if kinds == want and _decoder_free_bwd_call(items, dTOK, dTOKS, demb, dPRED, dxs, dxsp, mask_tok, mask_time, dx_pred, st.xhat, mh,
-                                                            G['note_embedding.weight'], G['note_embedding.bias'], B, E, He):
-                    pass
-                else:                                       # (not the whole pattern: the collected stages run as they are, in order)
-                    _DFB_FLUSHED[:] = kinds
-                    F_._DEFER = items
-                    F_._defer_flush()
-        finally:
-            F_._DEFER = None
-
-        side.join()
-        for s2 in getattr(side, 'extra', []):
-            s2.join()
+                if rows is not None:
+                    rows[0].launch()
+                else:
+                    ge, dx_pred = _bigru_backward(prec, st.PRED, wE, state, dout, True)
+                copy2d(rt.dPRED.view(16 * R, E), dx_pred.view(16 * R, E), acc=True)
+            _free_bwd_tail(st, rt, mh, gw, gb)
+        G.update(('dec_notes_emb_gru.' + n, gg) for n, gg in zip(EMB_GRU, ge))
+        tf.side.join()
         grads = tuple(G[n] for n in FREE_PARAM_NAMES)
-        return (dz, demb.view(16, 32, B, E), dxs.view(R, 2 * He) if st.has_xs else None, None, None, None, None) + grads
+        return (tf.dz, rt.demb.view(16, 32, B, E), rt.dxs.view(R, 2 * He) if st.has_xs else None, None, None, None, None) + grads
 
 
 # =============================================================================================

@@ -857,7 +857,7 @@ def test_decoder_free_composite_entry_point_equals_python_sequencing(B, tfr, bwd
         assert bool(FF_._DFF.get('calls')) == comp                 # the composites ran exactly when asked to: forward ...
         if bwd_call:                                               # ... and backward (ptv_decoder_free_bwd: when every stage of the node has its
             assert bool(FF_._DFF.get('bcalls')) == comp            # composite -- at small batches the re-summarisation BPTT runs on the persistent
-                                                                   # kernels, launched from Python: the collected stages then run as they are)
+                                                                   # kernels, launched from Python: the node then goes out stage by stage)
         with torch.no_grad():
             z = torch.cat([outs[2].mean, outs[3].mean], -1).detach()
             est = m.inference_decode(z[:, :256], z[:, 256:])
