@@ -851,7 +851,7 @@ int ptv_roll_match(const float* est_pr, const float* ref_pr, int B, int* counts,
  *   pitch / ld_pitch / step_major / dur: the plain logits a decode wrote, rows and load rule as ptv_recon_step_scores (row of (b, t, n) =
  *     (n*32 + t)*B + b if step_major else (b*32 + t)*15 + n; 16-byte loads iff ld_pitch % 4 == 0, ld_pitch >= 132 and the base is 16-byte
  *     aligned, else 4-byte loads of the same classes); xhat: the decided grid int64 [B][32][16][6].
- *   sample / sample_bytes: NULL / 0 (an argmax decode) or the decode's sampling block of 32, 48 or 64 bytes ("Sampled decode" above);
+ *   sample / sample_bytes: NULL / 0 (an argmax decode) or the decode's sampling block of 32, 48, 64 or 80 bytes ("Sampled decode" / "Per-row sampling" below);
  *     anything else is PTV_ERR_ARG.  force_pitch [15][32B] / force_dur [5][480B] (ptv_keep_force_build's layout), or NULL, each on its own.
  *   What counts: for (b, t) L = the first slot s in 1..15 with xhat[b][t][s][0] == 129, else 15 (ptv_keep_force_build's rule).  The pitch
  *     decisions of the note steps n = 0..L-1 count (the <eos> among them); the five duration bits of those notes whose pitch is < 128
@@ -1267,6 +1267,44 @@ int ptv_dur_gru_fwd_sample(int H, long M, const float* h0, long ld_h0, const flo
                            float* hall, long plane_h, void* hall16, void* gates, long plane_g, long step_g, int gates_bf16,
                            float* dur_out, long ld_out, int* idx, long idx_stride, const int* force, long force_stride,
                            const void* sample, int t, int n, void* stream);
+/* Per-row sampling: a decode whose rows each have their own sampling rule -- a batch of requests that differ in temperature, top_k,
+ * min_p or top_p, or a sweep of one z over several settings, decoded as ONE batch (csrc/philox.hpp SampleBlockR; INTEGRATION.md "Per-row
+ * sampling").  The ROW-WISE kind is the constrained kind with the six scalars of its block replaced by one record per row;
+ * everything the constrained kind honours stays: the pitch mask and the ascending flag, every force word (forced classes,
+ * PTV_FORCE_NOT_EOS, PTV_FORCE_BELOW(u), PTV_FORCE_DUR_RANGE(lo, hi)), <eos> always allowed, constraints before truncation.
+ * Block: 80 bytes, ten int64 words.  The first 64 are laid out as the constrained block; then { uint64 device address of the row table,
+ *   uint32 reserved (zero), uint32 reserved (zero) }.  Of the first 64 bytes the row-wise kernels read only seed, draw, flags and mask;
+ *   the host writes T_pitch = T_dur = 0, top_k = 0, ln_min_p = 1.0f (off), top_p_q24 = 0 and sample_offset = 0 there.
+ * Row table: int32 [B, 8] on the device, contiguous, 16-byte aligned, 32 bytes per row (two 16-byte loads), row b of the decoded batch:
+ *   words 0..4 = { float T_pitch, float T_dur, int32 top_k (0 = off), float ln_min_p (1.0f = off), uint32 top_p_q24 (0 = off) } -- the
+ *   encodings of the scalar block, bit for bit; word 5 = reserved (zero); words 6..7 = int64 sample_id, the global sample index g of the
+ *   Philox counter in place of sample_offset + b, range [0, 2^47).  seed and draw stay shared: sample_id already gives every row its own
+ *   stream.  Row b decides exactly as row b of a constrained decode whose block holds b's five words and sample_offset = sample_id[b] - b:
+ *   the same logits, the same noise words, the same decisions, bit for bit.
+ * A row's record is loaded once per launch by the lanes that decide for the row; rows past B are clamped like every other per-row load.
+ * Where 16 lanes hold a row (the note loops) the four rows of a wave take their own branches of the keep rule; the rule's cross-lane
+ * steps stay inside the row.
+ *   ptv_free_note_loop: bit 26 of train, together with bit 23, says io[21] is the 80-byte block (bits 24 / 25 then add nothing); the
+ *     guards of bit 25 apply: bit 26 without bit 23, with train & 3 != 0, a coin mask or a NULL block is PTV_ERR_ARG before any launch.
+ *     (Bits 0-1, 8-15, 16-25 of the word are taken; 26 was free.)
+ *   ptv_note_token_sample_rows: ptv_note_token_sample_cons with the 80-byte block; row r takes mask row r and record r.
+ *   ptv_dur_gru_fwd_sample_rows / ptv_dur_out_token_sample_rows: the duration entries of the row-wise step loop -- row r draws with T_dur and
+ *     sample_id of record r; a word PTV_FORCE_DUR_RANGE of force / force_idx limits the note as in the _cons forms, and the force array may
+ *     be NULL (every decision free).  ptv_dur_out_token_sample_rows reads the planes idx - k * idx_stride, k = 1..d, like its _cons form.
+ *   ptv_decoder_free_fwd: PTV_DFF_D_SAMPLE_ROWS != 0 says PTV_DFF_SAMPLE is the 80-byte block.
+ *   ptv_decode_logprob: sample_bytes = 80 takes T_pitch, T_dur and the truncation words from record b (one workgroup is one sample); log q
+ *     of a row-wise decode is the log-probability under that row's own proposal. */
+int ptv_note_token_sample_rows(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
+                               float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
+                               const int* force_pitch, int M, const void* sample80, int t, void* stream);
+int ptv_dur_out_token_sample_rows(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
+                                  int* idx, long idx_stride, const int* force_idx, long rows, const void* sample80, int t, int n, int d,
+                                  void* stream);
+int ptv_dur_gru_fwd_sample_rows(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,
+                                const float* tab0, const float* tab, const float* w_out, const float* b_out,
+                                float* hall, long plane_h, void* hall16, void* gates, long plane_g, long step_g, int gates_bf16,
+                                float* dur_out, long ld_out, int* idx, long idx_stride, const int* force, long force_stride,
+                                const void* sample80, int t, int n, void* stream);
 int ptv_free_resummarize(const void* const* w, const void* const* io, int B, int t, int train, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -1310,7 +1348,7 @@ enum PtvDffTensor {
   PTV_DFF_IDX, PTV_DFF_PLEN, PTV_DFF_GC16, PTV_DFF_DUR_SCR, PTV_DFF_IDX_SCR,
   PTV_DFF_XH0, PTV_DFF_XH1, PTV_DFF_XH16_0, PTV_DFF_XH16_1, PTV_DFF_XG0, PTV_DFF_XG1,
   PTV_DFF_WAIT_EVENT, PTV_DFF_RECORD_EVENT,   /* hipEvent_t or NULL: the persistent-launch turn around the cluster-mode note loops */
-  PTV_DFF_SAMPLE,           /* NULL, or the sampling block of a sampled decode (32 bytes on the device, 48 with D_SAMPLE_TRUNC, 64 with D_SAMPLE_CONS; "Sampled decode" above): D_INFERENCE only,
+  PTV_DFF_SAMPLE,           /* NULL, or the sampling block of a sampled decode (32 bytes on the device, 48 with D_SAMPLE_TRUNC, 64 with D_SAMPLE_CONS, 80 with D_SAMPLE_ROWS; "Sampled decode" above): D_INFERENCE only,
                              * anything else is PTV_ERR_ARG before the first launch */
   PTV_DFF_COUNT
 };
@@ -1325,6 +1363,7 @@ enum PtvDffDim {
   PTV_DFF_D_W_IH_T_BF16, PTV_DFF_D_W_HH_T_BF16,
   PTV_DFF_D_SAMPLE_TRUNC,   /* != 0: PTV_DFF_SAMPLE is the 48-byte block of a truncated sampled decode (top_k / min_p / top_p); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
   PTV_DFF_D_SAMPLE_CONS,    /* != 0: PTV_DFF_SAMPLE is the 64-byte block of a constrained decode (pitch mask / ascending notes); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
+  PTV_DFF_D_SAMPLE_ROWS,    /* != 0: PTV_DFF_SAMPLE is the 80-byte block of a row-wise decode ("Per-row sampling"); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
   PTV_DFF_D_COUNT
 };
 int ptv_decoder_free_fwd(const void* const* t, const long* d, const void* const* wl, const void* const* io, const void* const* wr,

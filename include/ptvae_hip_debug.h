@@ -77,6 +77,12 @@ int ptv_debug_pitch_constrain(const void* block64, const float* logits, const in
  * it (all words -1: the same bytes).  A NULL words is PTV_ERR_ARG. */
 int ptv_debug_pitch_constrain_words(const void* block64, const float* logits, const int* masks, const int* lo, const int* words, long rows,
                                     int layout, unsigned char* keep_out, float* thr_out, void* stream);
+/* ... with a row table in place of the block's scalars (ptvae_hip.h "Per-row sampling"): table int32 [rows, 8], 16-byte aligned -- row r is
+ * judged with T_pitch, top_k, ln_min_p and top_p_q24 of record r; of the block only the flags are read.  In layout 0 a wave holds four rows,
+ * so four records: the branches of the keep rule diverge between them.  words may be NULL (every decision plainly free).  A row whose record
+ * holds the block's scalars gets the bytes the entry above writes for it. */
+int ptv_debug_pitch_constrain_rows(const void* block64, const int* table, const float* logits, const int* masks, const int* lo,
+                                   const int* words, long rows, int layout, unsigned char* keep_out, float* thr_out, void* stream);
 
 /* test aid of the duration limits (ptvae_hip.h "Duration limits"): the decoder's own rule (csrc/philox.hpp dur_range_allowed /
  * dur_range_bit) on caller-supplied triples, words / d / prefix int32 [rows]: out [rows] uint8 -- bit 0 / bit 1: value 0 / 1 of duration bit

@@ -644,6 +644,8 @@ extern "C" int ptv_decoder_free_fwd(const void* const* t, const long* d, const v
   if (trunc && !t[PTV_DFF_SAMPLE]) return PTV_ERR_ARG;
   const bool cons = d[PTV_DFF_D_SAMPLE_CONS] != 0;                              // ... and so do constraints (the 64-byte block)
   if (cons && !t[PTV_DFF_SAMPLE]) return PTV_ERR_ARG;
+  const bool rowwise = d[PTV_DFF_D_SAMPLE_ROWS] != 0;                           // ... and per-row parameters (the 80-byte block)
+  if (rowwise && !t[PTV_DFF_SAMPLE]) return PTV_ERR_ARG;
   bool need_resum = inference;
   for (int i = 0; i < 31 && !need_resum; i++) need_resum = !time_coin[i];
   {
@@ -696,14 +698,14 @@ extern "C" int ptv_decoder_free_fwd(const void* const* t, const long* d, const v
   int loop_flags = (int)d[PTV_DFF_D_LOOP_FLAGS];
   const int cluster = (int)d[PTV_DFF_D_CLUSTER];
   // sampled decode: the note loop's io table with the sampling block as its 22nd entry, announced by bit 23 of the `train` word (+ bit 24: the 48-byte
-  // block of a truncated decode, bit 25: the 64-byte block of a constrained one)
+  // block of a truncated decode, bit 25: the 64-byte block of a constrained one, bit 26: the 80-byte block of a row-wise one)
   const void* io_s[22];
   if (t[PTV_DFF_SAMPLE]) {
     for (int i = 0; i < 21; i++) io_s[i] = io[i];
     io_s[21] = t[PTV_DFF_SAMPLE];
     io = io_s;
-    loop_flags |= 0x800000 | (trunc ? 0x1000000 : 0) | (cons ? 0x2000000 : 0);
-  } else if (loop_flags & 0x3800000) return PTV_ERR_ARG;
+    loop_flags |= 0x800000 | (trunc ? 0x1000000 : 0) | (cons ? 0x2000000 : 0) | (rowwise ? 0x4000000 : 0);
+  } else if (loop_flags & 0x7800000) return PTV_ERR_ARG;
   const void* ior_[7];
   if (need_resum) for (int i = 0; i < 7; i++) ior_[i] = ior[i];
   if (cluster && t[PTV_DFF_WAIT_EVENT] && hipStreamWaitEvent(s, (hipEvent_t)const_cast<void*>(t[PTV_DFF_WAIT_EVENT]), 0) != hipSuccess) return PTV_ERR_LAUNCH;

@@ -49,6 +49,10 @@ __global__ void __launch_bounds__(256) decode_logprob_kernel(const float* __rest
     Tp = s->t_pitch; Td = s->t_dur;
     if (blk_bytes >= 48) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(blk));
     if (blk_bytes >= 64) cn = load_cons(reinterpret_cast<const SampleBlockC*>(blk));
+    if (blk_bytes >= 80) {                                                 // row-wise: sample b's own record (one workgroup, one sample: still uniform)
+      const RowRule rw = load_row_rule(load_row_table(blk), b);
+      Tp = rw.t_pitch; Td = rw.t_dur; tr = rw.tr;
+    }
   }
   int e = 0;
   for (int t = wv; t < 32; t += 4) {
@@ -127,7 +131,7 @@ __global__ void __launch_bounds__(256) decode_logprob_kernel(const float* __rest
       // ---- log q: the decoder's own allowed and kept set, softmax of (v - m) / T over it
       float lqp = 0.f;
       bool outside = false;
-      if (Tp > 0.f) {                                                      // (uniform: the block's word)
+      if (Tp > 0.f) {                                                      // (uniform: the block's word, or the sample's)
         float tv[9];
         // (a PTV_FORCE_NOT_EOS or PTV_FORCE_BELOW decision is free, its support the decoder's reduced one; only the 64-byte kind honours the word)
         const unsigned al = pitch_constrain<9, 16>(v, own, lo, cn.flags, j, tv, blk_bytes >= 64 ? fp : -1);
@@ -256,7 +260,7 @@ extern "C" int ptv_decode_logprob(const float* pitch, long ld_pitch, const float
                                   const void* sample, int sample_bytes, const int* force_pitch, const int* force_dur, float* step_logp,
                                   int* step_counts, int* err, void* stream) {
   if (!pitch || !dur || !xhat || !step_logp || !step_counts || !err || B < 1 || ld_pitch < DS_NP) return PTV_ERR_ARG;
-  if (sample ? (sample_bytes != 32 && sample_bytes != 48 && sample_bytes != 64) : sample_bytes != 0) return PTV_ERR_ARG;
+  if (sample ? (sample_bytes != 32 && sample_bytes != 48 && sample_bytes != 64 && sample_bytes != 80) : sample_bytes != 0) return PTV_ERR_ARG;
   const dim3 grid(B), block(256);
   if (ds_vec_ok(pitch, ld_pitch))
     hipLaunchKernelGGL((decode_logprob_kernel<true>), grid, block, 0, (hipStream_t)stream, pitch, ld_pitch, dur, xhat, B, step_major, sample,

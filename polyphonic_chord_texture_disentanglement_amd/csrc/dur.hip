@@ -54,6 +54,7 @@ struct DurArgs {
 };
 
 template <int SAMP>                    // SAMP = 2: the constrained kind's -- a negative force word may be a duration range word (philox.hpp)
+                                       // SAMP = 3: the row-wise kind's -- SAMP = 2 with the temperature and noise stream of the row's own record (SampleBlockR)
 __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
   __builtin_amdgcn_s_setprio(3);                                         // a launch of the latency chain: wins instruction issue against sibling-stream products
   __shared__ __attribute__((aligned(16))) __bf16 Ws[3 * DH * DLD];       // W_hh as bf16
@@ -96,7 +97,10 @@ __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
       h[f][0] = v.x; h[f][1] = v.y; h[f][2] = v.z; h[f][3] = v.w;
     }
     int tok = 0;                                                        // table row: 0 = sos, 1 + idx afterwards
-    [[maybe_unused]] int pre = 0;                                       // SAMP = 2: the value of the row's bits so far
+    [[maybe_unused]] int pre = 0;                                       // SAMP >= 2: the value of the row's bits so far
+    [[maybe_unused]] float rtd = 0.f;                                   // SAMP = 3: T_dur and sample id of the row's record (a row past M: the last row's)
+    [[maybe_unused]] long long rid = 0;
+    if constexpr (SAMP == 3) { const RowRule rw = load_row_rule(load_row_table(a.samp), min(row, a.M - 1)); rtd = rw.t_dur; rid = rw.id; }
 #pragma unroll 1
     for (int d = 0; d < 5; d++) {
       // state -> LDS (bf16) as the MFMA operand
@@ -160,7 +164,12 @@ __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
       o0 += __shfl_xor(o0, 32, 64); o1 += __shfl_xor(o1, 32, 64);
       o0 += wo[2 * DH]; o1 += wo[2 * DH + 1];
       float x0 = o0, x1 = o1;
-      if constexpr (SAMP) {
+      if constexpr (SAMP == 3) {
+        const SampleBlock sb = *a.samp;
+        float g0, g1;
+        dur_gumbel2(sb, rid, a.t, a.n, d, g0, g1);
+        x0 = perturbed(o0, rtd, g0); x1 = perturbed(o1, rtd, g1);
+      } else if constexpr (SAMP) {
         const SampleBlock sb = *a.samp;
         float g0, g1;
         dur_gumbel2(sb, sb.sample_offset + row, a.t, a.n, d, g0, g1);
@@ -169,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
       int id = x1 > x0 ? 1 : 0;                                           // first max wins ties (torch.max)
       if (a.force && ok) {
         const int fw = a.force[d * a.force_stride + row];
-        if constexpr (SAMP == 2) id = dur_range_bit(fw, d, pre, id);
+        if constexpr (SAMP >= 2) id = dur_range_bit(fw, d, pre, id);
         id = fw >= 0 ? fw : id;                                           // (negative: a free decision)
       }
       if (ok && lane < 16) {
@@ -178,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void dur_gru_fwd_kernel(DurArgs a) {
         a.idx[d * a.idx_stride + row] = id;
       }
       tok = 1 + id;
-      if constexpr (SAMP == 2) pre = 2 * pre + id;
+      if constexpr (SAMP >= 2) pre = 2 * pre + id;
     }
   }
 }
@@ -269,6 +278,26 @@ extern "C" int ptv_dur_gru_fwd_sample_cons(int H, long M, const float* h0, long 
   const int cap = 3 * num_cus();
   long nb = ((M + 15) / 16 + 3) / 4; if (nb > cap) nb = cap; if (nb < 1) nb = 1;
   hipLaunchKernelGGL(dur_gru_fwd_kernel<2>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// ... of the ROW-WISE step loop (80-byte block): row r draws with T_dur and sample_id of record r of the block's table; force may be NULL,
+// a word PTV_FORCE_DUR_RANGE of it limits the note as in the constrained form
+extern "C" int ptv_dur_gru_fwd_sample_rows(int H, long M, const float* h0, long ld_h0, const float* w_hh, const float* b_hh,
+                                           const float* tab0, const float* tab, const float* w_out, const float* b_out,
+                                           float* hall, long plane_h, void* hall16, void* gates, long plane_g, long step_g, int gates_bf16,
+                                           float* dur_out, long ld_out, int* idx, long idx_stride, const int* force, long force_stride,
+                                           const void* sample80, int t, int n, void* stream) {
+  if (H != DH) return PTV_ERR_ARG;
+  if (M <= 0 || !h0 || !w_hh || !b_hh || !tab0 || !tab || !w_out || !b_out || !dur_out || !idx) return PTV_ERR_ARG;
+  if ((ld_h0 & 3) || (plane_h & 7) || (plane_g & 7) || (step_g & 7)) return PTV_ERR_ARG;
+  if (!sample80 || t < 0 || t >= 32 || n < 0 || n >= 15) return PTV_ERR_ARG;
+  DurArgs a{h0, ld_h0, w_hh, b_hh, tab0, tab, w_out, b_out, hall, plane_h, (__bf16*)hall16, gates, plane_g, step_g, gates_bf16,
+            dur_out, ld_out, idx, idx_stride, force, force_stride, M, nullptr, 0, nullptr, (const SampleBlock*)sample80, t, n};
+  const int cap = 3 * num_cus();
+  long nb = ((M + 15) / 16 + 3) / 4; if (nb > cap) nb = cap; if (nb < 1) nb = 1;
+  hipLaunchKernelGGL(dur_gru_fwd_kernel<3>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

@@ -253,6 +253,7 @@ __device__ __forceinline__ int force_word5(const int (&w)[5], int d) {   // (sel
 // SAMP = 2: truncated sampling (top_k / min_p) -- the draw runs over the classes whose logit reaches pitch_keep_threshold() of the row
 // (philox.hpp: ONE function for every decision site).  SAMP = 3: ... and that are ALLOWED (pitch mask / ascending notes: pitch_constrain(),
 // philox.hpp) -- the mask bitmap and the running `lo` are integer registers every member forms from the same decisions.
+// SAMP = 4: SAMP = 3 with temperatures, truncation words and noise stream taken per row from the block's table (philox.hpp SampleBlockR).
 // Cluster mode: every member runs those functions on the same logits (each computed the whole head redundantly, same products, same
 // order) with the same block, so all members reach the same decision; nobody is told it.
 // FORCE = 1: the launch has force arrays (replay mode / kept steps) and requests the six force words of a note step ahead of the decisions.
@@ -360,18 +361,28 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
   Trunc tr{};                                                   // SAMP >= 2: a.samp is the 48-byte block, these its last words
   if constexpr (SAMP >= 2) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(a.samp));
   (void)tr;
-  // SAMP = 3: the 64-byte block.  The row's mask is fixed over the 15 note steps: its 16 bytes are loaded here, once, and reduced to the
+  // SAMP >= 3: the 64-byte block.  The row's mask is fixed over the 15 note steps: its 16 bytes are loaded here, once, and reduced to the
   // bitmap of the nine columns this lane owns in P3; `lo` runs with the decisions
   Cons cn{};
   unsigned own = 0u;
   int lo = -1;
-  if constexpr (SAMP == 3) {
+  if constexpr (SAMP >= 3) {
     cn = load_cons(reinterpret_cast<const SampleBlockC*>(a.samp));
     unsigned mw[4];
     pitch_mask_words(cn, min(r0 + (tid >> 4), B - 1), t, mw);
     own = pitch_mask_own<9, 16>(mw, tid & 15);
   }
   (void)cn; (void)own; (void)lo;
+  // SAMP = 4: the 80-byte block of a row-wise decode (philox.hpp SampleBlockR).  Temperatures, truncation words and the noise stream are a
+  // row's own: its record is loaded here, once, by the lanes that decide for it -- rwp for the row this thread decides in P3 (tid >> 4),
+  // rwc for its row in P5 (rC).  The values are uniform over a row's 16 lanes and differ between the rows of a wave; of the block itself
+  // only seed and draw (sb), flags and mask (cn) are used.  The sites below choose by `SAMP == 4 ? the record's : the block's`
+  [[maybe_unused]] RowRule rwp{}, rwc{};
+  if constexpr (SAMP == 4) {
+    const int* rtab = load_row_table(a.samp);
+    rwp = load_row_rule(rtab, min(r0 + (tid >> 4), B - 1));
+    rwc = load_row_rule(rtab, rC);
+  }
   // timing experiments (dbg_out): 100-MHz ticks wave 0 spends per phase, summed over the 15 note steps -> dbg_out[3 * grid + 8 * block + i],
   // i = 0 cell (products + epilogue), 1 barrier + state exchange, 2 pitch head, 3 argmax + dur_hid, 4 duration GRU, 5 token embedding
   long tph[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;
@@ -617,16 +628,16 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
 #pragma unroll
         for (int k = 0; k < 9; k++) pv[k] = pit[row][j + 16 * k];              // (columns 130..143 of the row exist and hold zeros)
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (SAMP == 3) {                                             // ... over the ALLOWED classes that reach the threshold of the allowed
+        if constexpr (SAMP >= 3) {                                             // ... over the ALLOWED classes that reach the threshold of the allowed
           float tv[9];
           const unsigned al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE ? fpw : -1);
-          const float thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
+          const float thr = pitch_keep_threshold<9, 16>((SAMP == 4 ? rwp.tr : tr), (SAMP == 4 ? rwp.t_pitch : sb.t_pitch), tv);   // (SAMP = 4: the branches inside diverge between the wave's rows)
           float gum[9];
-          pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
+          pitch_gumbel9(sb, (SAMP == 4 ? rwp.id : sb.sample_offset + min(r0 + row, B - 1)), t, n, j, gum);
 #pragma unroll
           for (int k = 0; k < 9; k++) {
             const int c = j + 16 * k;
-            const float x = perturbed(pv[k], sb.t_pitch, gum[k]);
+            const float x = perturbed(pv[k], (SAMP == 4 ? rwp.t_pitch : sb.t_pitch), gum[k]);
             const bool take = ((al >> k) & 1u) && pv[k] >= thr && x > best;
             best = take ? x : best; bi = take ? c : bi;
           }
@@ -671,12 +682,12 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
       float thr = -INFINITY;
       unsigned al = 0u;
       (void)al;
-      if constexpr (SAMP == 3) {
+      if constexpr (SAMP >= 3) {
         float pv[9], tv[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) pv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
         al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE ? fpw : -1);
-        thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
+        thr = pitch_keep_threshold<9, 16>((SAMP == 4 ? rwp.tr : tr), (SAMP == 4 ? rwp.t_pitch : sb.t_pitch), tv);
       } else if constexpr (SAMP == 2) {
         float tv[9];
 #pragma unroll
@@ -684,7 +695,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
         thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
       }
       float gum[SAMP ? 9 : 1];
-      if constexpr (SAMP) pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
+      if constexpr (SAMP) pitch_gumbel9(sb, (SAMP == 4 ? rwp.id : sb.sample_offset + min(r0 + row, B - 1)), t, n, j, gum);
 #pragma unroll
       for (int k = 0; k < 9; k++) {
         const int c = j + 16 * k;
@@ -692,8 +703,8 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           const float v = pit[row][c];
           if (ok) a.pitch[pr * a.ld_pitch + c] = v;
           float x = v;
-          if constexpr (SAMP) x = perturbed(v, sb.t_pitch, gum[k]);
-          if constexpr (SAMP == 3) { if (((al >> k) & 1u) && v >= thr && x > best) { best = x; bi = c; } }
+          if constexpr (SAMP) x = perturbed(v, (SAMP == 4 ? rwp.t_pitch : sb.t_pitch), gum[k]);
+          if constexpr (SAMP >= 3) { if (((al >> k) & 1u) && v >= thr && x > best) { best = x; bi = c; } }
           else if constexpr (SAMP == 2) { if (v >= thr && x > best) { best = x; bi = c; } }
           else if (x > best) { best = x; bi = c; }
         }
@@ -706,7 +717,7 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
       }
       if constexpr (FORCE) bi = forced(fpw, bi);
       else if (a.force_pitch) bi = forced(a.force_pitch[(long)n * R + (long)t * B + min(r0 + row, B - 1)], bi);
-      if constexpr (SAMP == 3) lo = pitch_lo_next(lo, bi);       // (every lane of the row holds the decision)
+      if constexpr (SAMP >= 3) lo = pitch_lo_next(lo, bi);       // (every lane of the row holds the decision)
       if (j == 0) pidx[row] = bi;
       if constexpr (RES) {                                        // (every lane of the row holds the decision; P6 maps threads the same way)
         const float* wr_ = a.w_embT + (long)bi * FE + j * 8;
@@ -780,9 +791,9 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
         float dn[SAMP ? 10 : 1];                                               // SAMP: T * gumbel of this lane's row, [2 d + class]
         if constexpr (SAMP) {
           float gum[10];
-          dur_gumbel10(sb, sb.sample_offset + rC, t, n, gum);
+          dur_gumbel10(sb, (SAMP == 4 ? rwc.id : sb.sample_offset + rC), t, n, gum);
 #pragma unroll
-          for (int i = 0; i < 10; i++) dn[i] = sb.t_dur * gum[i];
+          for (int i = 0; i < 10; i++) dn[i] = (SAMP == 4 ? rwc.t_dur : sb.t_dur) * gum[i];
         }
         int dtk = 0;                                                           // this lane's row: 0 = <sos>, 1 + previous decision
         [[maybe_unused]] int dpx = 0;                                          // ... and the value of its bits so far (duration range words)
@@ -792,11 +803,11 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           float x0 = e0, x1 = e1;
           if constexpr (SAMP) { x0 = e0 + dn[2 * d]; x1 = e1 + dn[2 * d + 1]; }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
-          if constexpr (SAMP == 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
+          if constexpr (SAMP >= 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
           if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
           else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
-          if constexpr (SAMP == 3 && FORCE) dpx = 2 * dpx + id;
+          if constexpr (SAMP >= 3 && FORCE) dpx = 2 * dpx + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
               a.dur[prC * 10 + 2 * d] = e0; a.dur[prC * 10 + 2 * d + 1] = e1;
@@ -930,15 +941,15 @@ __global__ __launch_bounds__(256, 1) void note_loop_kernel(NoteLoopArgs a) {
           float x0 = e0, x1 = e1;
           if constexpr (SAMP) {                                                 // (a runtime d: one call per step instead of an indexed register array)
             float g0, g1;
-            dur_gumbel2(sb, sb.sample_offset + rC, t, n, d, g0, g1);
-            x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
+            dur_gumbel2(sb, (SAMP == 4 ? rwc.id : sb.sample_offset + rC), t, n, d, g0, g1);
+            x0 = perturbed(e0, (SAMP == 4 ? rwc.t_dur : sb.t_dur), g0); x1 = perturbed(e1, (SAMP == 4 ? rwc.t_dur : sb.t_dur), g1);
           }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
-          if constexpr (SAMP == 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
+          if constexpr (SAMP >= 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
           if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
           else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
-          if constexpr (SAMP == 3 && FORCE) dpx = 2 * dpx + id;
+          if constexpr (SAMP >= 3 && FORCE) dpx = 2 * dpx + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
               a.dur[prC * 10 + 2 * d] = e0; a.dur[prC * 10 + 2 * d + 1] = e1;
@@ -1066,18 +1077,28 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
   Trunc tr{};                                                   // SAMP >= 2: a.samp is the 48-byte block, these its last words
   if constexpr (SAMP >= 2) tr = load_trunc(reinterpret_cast<const SampleBlockT*>(a.samp));
   (void)tr;
-  // SAMP = 3: the 64-byte block.  The row's mask is fixed over the 15 note steps: its 16 bytes are loaded here, once, and reduced to the
+  // SAMP >= 3: the 64-byte block.  The row's mask is fixed over the 15 note steps: its 16 bytes are loaded here, once, and reduced to the
   // bitmap of the nine columns this lane owns in P3; `lo` runs with the decisions
   Cons cn{};
   unsigned own = 0u;
   int lo = -1;
-  if constexpr (SAMP == 3) {
+  if constexpr (SAMP >= 3) {
     cn = load_cons(reinterpret_cast<const SampleBlockC*>(a.samp));
     unsigned mw[4];
     pitch_mask_words(cn, min(r0 + (tid >> 4), B - 1), t, mw);
     own = pitch_mask_own<9, 16>(mw, tid & 15);
   }
   (void)cn; (void)own; (void)lo;
+  // SAMP = 4: the 80-byte block of a row-wise decode (philox.hpp SampleBlockR).  Temperatures, truncation words and the noise stream are a
+  // row's own: its record is loaded here, once, by the lanes that decide for it -- rwp for the row this thread decides in P3 (tid >> 4),
+  // rwc for its row in P5 (rC).  The values are uniform over a row's 16 lanes and differ between the rows of a wave; of the block itself
+  // only seed and draw (sb), flags and mask (cn) are used.  The sites below choose by `SAMP == 4 ? the record's : the block's`
+  [[maybe_unused]] RowRule rwp{}, rwc{};
+  if constexpr (SAMP == 4) {
+    const int* rtab = load_row_table(a.samp);
+    rwp = load_row_rule(rtab, min(r0 + (tid >> 4), B - 1));
+    rwc = load_row_rule(rtab, rC);
+  }
 
   // ---- one-time loads: duration GRU weights / tables -> LDS, initial state and first token -> LDS
   for (int i = tid0; i < 12 * 2 * 64; i += 512) wdl[i] = a.wdur[i];
@@ -1229,11 +1250,17 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       float x0 = e0, x1 = e1;
       if constexpr (SAMP) {
         float g0, g1;
+        if constexpr (SAMP == 4) {                               // (its two callers: the thread's P3 row, or with tid < FP its P5 row)
+          const bool p3 = row == (tid >> 4);
+          dur_gumbel2(sb, p3 ? rwp.id : rwc.id, t, n, d, g0, g1);
+          x0 = perturbed(e0, p3 ? rwp.t_dur : rwc.t_dur, g0); x1 = perturbed(e1, p3 ? rwp.t_dur : rwc.t_dur, g1);
+        } else {
         dur_gumbel2(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, d, g0, g1);
         x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
+        }
       }
       int id = x1 > x0 ? 1 : 0;
-      if constexpr (SAMP == 3 && FORCE) {
+      if constexpr (SAMP >= 3 && FORCE) {
         int p = 0;
         for (int k = 0; k < d; k++) p = 2 * p + bits[row][k];
         id = dur_range_bit(fw, d, p, id);
@@ -1286,12 +1313,12 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       float thr = -INFINITY;
       unsigned al = 0u;
       (void)al;
-      if constexpr (SAMP == 3) {                                        // (all 256 head threads are here: whole DPP rows)
+      if constexpr (SAMP >= 3) {                                        // (all 256 head threads are here: whole DPP rows)
         float pv[9], tv[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) pv[k] = j + 16 * k < FNP ? pit[row][j + 16 * k] : -INFINITY;
         al = pitch_constrain<9, 16>(pv, own, lo, cn.flags, j, tv, FORCE ? fpw : -1);
-        thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
+        thr = pitch_keep_threshold<9, 16>((SAMP == 4 ? rwp.tr : tr), (SAMP == 4 ? rwp.t_pitch : sb.t_pitch), tv);
       } else if constexpr (SAMP == 2) {
         float tv[9];
 #pragma unroll
@@ -1299,7 +1326,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
         thr = pitch_keep_threshold<9, 16>(tr, sb.t_pitch, tv);
       }
       float gum[SAMP ? 9 : 1];
-      if constexpr (SAMP) pitch_gumbel9(sb, sb.sample_offset + min(r0 + row, B - 1), t, n, j, gum);
+      if constexpr (SAMP) pitch_gumbel9(sb, (SAMP == 4 ? rwp.id : sb.sample_offset + min(r0 + row, B - 1)), t, n, j, gum);
 #pragma unroll
       for (int k = 0; k < 9; k++) {
         const int c = j + 16 * k;
@@ -1307,8 +1334,8 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
           const float v = pit[row][c];
           if (ok) a.pitch[pr * a.ld_pitch + c] = v;
           float x = v;
-          if constexpr (SAMP) x = perturbed(v, sb.t_pitch, gum[k]);
-          if constexpr (SAMP == 3) { if (((al >> k) & 1u) && v >= thr && x > best) { best = x; bi = c; } }
+          if constexpr (SAMP) x = perturbed(v, (SAMP == 4 ? rwp.t_pitch : sb.t_pitch), gum[k]);
+          if constexpr (SAMP >= 3) { if (((al >> k) & 1u) && v >= thr && x > best) { best = x; bi = c; } }
           else if constexpr (SAMP == 2) { if (v >= thr && x > best) { best = x; bi = c; } }
           else if (x > best) { best = x; bi = c; }
         }
@@ -1320,7 +1347,7 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
       }
       if constexpr (FORCE) bi = forced(fpw, bi);
       else if (a.force_pitch) bi = forced(a.force_pitch[(long)n * R + (long)t * B + min(r0 + row, B - 1)], bi);
-      if constexpr (SAMP == 3) lo = pitch_lo_next(lo, bi);       // (every lane of the row holds the decision)
+      if constexpr (SAMP >= 3) lo = pitch_lo_next(lo, bi);       // (every lane of the row holds the decision)
       if (j == 0) pidx[row] = bi;
     }
     // ================= P4: dur_hid_linear([h | logits]) -> initial duration state (wave w = units w*16..) =================
@@ -1394,15 +1421,15 @@ __global__ __launch_bounds__(512, 1) void note_loop2_kernel(NoteLoopArgs a) {
           float x0 = e0, x1 = e1;
           if constexpr (SAMP) {
             float g0, g1;
-            dur_gumbel2(sb, sb.sample_offset + rC, t, n, d, g0, g1);
-            x0 = perturbed(e0, sb.t_dur, g0); x1 = perturbed(e1, sb.t_dur, g1);
+            dur_gumbel2(sb, (SAMP == 4 ? rwc.id : sb.sample_offset + rC), t, n, d, g0, g1);
+            x0 = perturbed(e0, (SAMP == 4 ? rwc.t_dur : sb.t_dur), g0); x1 = perturbed(e1, (SAMP == 4 ? rwc.t_dur : sb.t_dur), g1);
           }
           int id = x1 > x0 ? 1 : 0;                                             // first max wins ties (torch.max)
-          if constexpr (SAMP == 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
+          if constexpr (SAMP >= 3 && FORCE) id = dur_range_bit(force_word5(fdw, d), d, dpx, id);   // (a range word: philox.hpp)
           if constexpr (FORCE) id = forced(force_word5(fdw, d), id);
           else if (a.force_dur) id = forced(a.force_dur[(long)d * M + prC], id);
           dtk = 1 + id;
-          if constexpr (SAMP == 3 && FORCE) dpx = 2 * dpx + id;
+          if constexpr (SAMP >= 3 && FORCE) dpx = 2 * dpx + id;
           if (tid < FP) {                                                      // wave 0, lanes 0..15: crow == tid
             if (okC) {
               a.dur[prC * 10 + 2 * d] = e0; a.dur[prC * 10 + 2 * d + 1] = e1;
@@ -1699,6 +1726,7 @@ static void launch_note_loop(const NoteLoopArgs& a, bool split, bool force, bool
 // train bit 23: io has a 22nd entry, the sampling block (inference only); without the bit io[21] is never read
 // train bit 24 (with bit 23): io[21] is the 48-byte block of a truncated sampled decode (top_k / min_p; philox.hpp SampleBlockT)
 // train bit 25 (with bit 23): io[21] is the 64-byte block of a constrained decode (pitch mask / ascending notes + truncation; SampleBlockC)
+// train bit 26 (with bit 23): io[21] is the 80-byte block of a row-wise decode (the constrained kind with one record per row; SampleBlockR)
 // io[21]: gc, emb, HN, gates_n, pitch, HD, gates_d, dur, idx, TOK, PRED, xhat, plen, force_pitch, force_dur, HN16, HD16, dbg words, h0gc,
 //         xch, cnt (cluster mode, train bits 18-20 = S in {2, 4}: S workgroups per 16-sample panel, ptvae_hip.h)
 extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, long ld_pitch, int B, int t, unsigned coin_mask, int train,
@@ -1713,6 +1741,8 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   if (trunc && (!samp || (train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG;   // truncation belongs to a sampled decode (io[21]: the 48-byte block)
   const bool cons = (train & 0x2000000) != 0;
   if (cons && (!samp || (train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG;    // ... and so do constraints (io[21]: the 64-byte block)
+  const bool rowwise = (train & 0x4000000) != 0;
+  if (rowwise && (!samp || (train & 3) != 0 || coin_mask || !io[21])) return PTV_ERR_ARG; // ... and per-row parameters (io[21]: the 80-byte block)
   NoteLoopArgs a{};
   a.samp = samp ? (const SampleBlock*)io[21] : nullptr;
   a.wg_h = (const bf16x8*)w[0]; a.wg_t = (const bf16x8*)w[1]; a.wp = (const bf16x8*)w[2]; a.wd_h = (const bf16x8*)w[3];
@@ -1754,7 +1784,8 @@ extern "C" int ptv_free_note_loop(const void* const* w, const void* const* io, l
   const int pi = prof::want(7, B, FHN) ? prof::begin((hipStream_t)stream) : -1;
   const dim3 grid(split ? panels : a.S > 1 ? (panels + 7) / 8 * 8 * a.S : panels);
   const bool force = a.force_pitch || a.force_dur;               // the FORCE instantiations: replay mode / kept steps
-  if (cons) launch_note_loop<3>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
+  if (rowwise) launch_note_loop<4>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
+  else if (cons) launch_note_loop<3>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
   else if (trunc) launch_note_loop<2>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
   else if (samp) launch_note_loop<1>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);
   else launch_note_loop<0>(a, split, force, (train & 0x200000) != 0, grid, (hipStream_t)stream);

@@ -68,6 +68,34 @@ __global__ void dur_out_token_cons_kernel(const float* __restrict__ h, int H, co
   }
 }
 
+// ... of the row-wise kind (philox.hpp SampleBlockR): the temperature and the noise stream are row r's own record; a range word is honoured
+// where force_idx is given, as above (force_idx may be NULL: every decision free)
+__global__ void dur_out_token_rows_kernel(const float* __restrict__ h, int H, const float* __restrict__ w_out, const float* __restrict__ b_out,
+                                          float* __restrict__ dur_out, long ld_out, int* __restrict__ idx, long idx_stride,
+                                          const int* __restrict__ force_idx, long rows, const SampleBlock* __restrict__ samp, int t, int n, int d) {
+  const int sub = threadIdx.x & 15;
+  const long rpb = blockDim.x / 16;
+  for (long r = (long)blockIdx.x * rpb + threadIdx.x / 16; r < rows; r += (long)gridDim.x * rpb) {
+    float s0 = 0.f, s1 = 0.f;
+    for (int j = sub; j < H; j += 16) { float v = h[r * H + j]; s0 += v * w_out[j]; s1 += v * w_out[H + j]; }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o, 16); s1 += __shfl_xor(s1, o, 16); }
+    if (sub == 0) {
+      s0 += b_out[0]; s1 += b_out[1];
+      dur_out[r * ld_out + 0] = s0; dur_out[r * ld_out + 1] = s1;
+      const SampleBlock sb = *samp;
+      const RowRule rw = load_row_rule(load_row_table(samp), r);
+      float g0, g1;
+      dur_gumbel2(sb, rw.id, t, n, d, g0, g1);
+      const float x0 = perturbed(s0, rw.t_dur, g0), x1 = perturbed(s1, rw.t_dur, g1);
+      const int fw = force_idx ? force_idx[r] : -1;
+      int p = 0;
+      for (int k = d; k > 0; k--) p = 2 * p + idx[r - k * idx_stride];
+      idx[r] = fw >= 0 ? fw : dur_range_bit(fw, d, p, x1 > x0 ? 1 : 0);       // first max wins ties (torch.max)
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // gradient global norm + clip_grad_norm_(.,clip) + Adam (module.py:142-144, train.py:50) over the
 // flat parameter / gradient buffers.  Two launches, no host sync: the norm stays on the device.
@@ -170,6 +198,7 @@ __global__ void clip_adam_kernel(float* __restrict__ p, const float* __restrict_
 template <int SAMP>                    // SAMP = 1: row r is sample r at (t, note step n - 1), the pitch decision a draw (philox.hpp)
                                        // SAMP = 2: ... over the classes pitch_keep_threshold() keeps; `samp` is then the 48-byte block
                                        // SAMP = 3: ... that pitch_constrain() allows; `samp` is then the 64-byte block
+                                       // SAMP = 4: ... with row r's own record for temperature, truncation and noise stream; the 80-byte block
 __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch, const int* __restrict__ dur_idx, long dur_stride,
                                   const float* __restrict__ W, const float* __restrict__ bias, int E,
                                   float* __restrict__ pred, long ld_pred, long* __restrict__ xhat, long xhat_stride,
@@ -180,7 +209,33 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
     const float* lr = pitch + (long)r * ld_pitch;
     float best = -INFINITY; int bi = 0x7fffffff;
     [[maybe_unused]] int fw3 = -1;                                 // SAMP = 3: the row's force word (negative: a free decision)
-    if constexpr (SAMP == 3) {                                     // constrained: ... over the ALLOWED classes (pitch_constrain, philox.hpp)
+    if constexpr (SAMP == 4) {                                     // row-wise: the constrained branch below with the row's record (r is uniform over the wave)
+      if (force_pitch) fw3 = force_pitch[r];
+      const SampleBlockC* q = reinterpret_cast<const SampleBlockC*>(samp);
+      const SampleBlock sb = q->s.s;
+      const RowRule rw = load_row_rule(load_row_table(samp), r);
+      const Cons cn = load_cons(q);
+      const long* xr = xhat + (long)r * xhat_stride;
+      int lo = -1;
+      if (lane + 1 < n) { const long p = xr[(long)(lane + 1 - n) * 6]; if (p < 128) lo = (int)p; }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lo = max(lo, __shfl_xor(lo, o, 64));
+      unsigned mw[4];
+      pitch_mask_words(cn, r, t, mw);
+      float pv[3], tv[3];
+#pragma unroll
+      for (int i = 0; i < 3; i++) pv[i] = lane + 64 * i < 130 ? lr[lane + 64 * i] : -INFINITY;
+      const unsigned al = pitch_constrain<3, 64>(pv, mw, lo, cn.flags, lane, tv, fw3);
+      const float thr = pitch_keep_threshold<3, 64>(rw.tr, rw.t_pitch, tv);
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const int c = lane + 64 * i;
+        if (((al >> i) & 1u) && pv[i] >= thr) {
+          const float x = perturbed(pv[i], rw.t_pitch, pitch_gumbel1(sb, rw.id, t, n - 1, c));
+          if (x > best) { best = x; bi = c; }
+        }
+      }
+    } else if constexpr (SAMP == 3) {                                     // constrained: ... over the ALLOWED classes (pitch_constrain, philox.hpp)
       if (force_pitch) fw3 = force_pitch[r];                       // (before the constrain: PTV_FORCE_NOT_EOS and PTV_FORCE_BELOW reduce the allowed set)
       const SampleBlockC* q = reinterpret_cast<const SampleBlockC*>(samp);
       const SampleBlock sb = q->s.s;
@@ -235,7 +290,7 @@ __global__ void note_token_kernel(const float* __restrict__ pitch, long ld_pitch
       float ov = __shfl_xor(best, o, 64); int oi = __shfl_xor(bi, o, 64);
       if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }       // first maximal index (torch.max)
     }
-    if constexpr (SAMP == 3) { if (fw3 >= 0) bi = fw3; }
+    if constexpr (SAMP >= 3) { if (fw3 >= 0) bi = fw3; }
     else if (force_pitch) { const int fw = force_pitch[r]; if (fw >= 0) bi = fw; }   // (negative: a free decision)
     int bits[5];
 #pragma unroll
@@ -325,6 +380,19 @@ extern "C" int ptv_dur_out_token_sample_cons(const float* h, int H, const float*
   long nb = (rows + 15) / 16; if (nb > 8192) nb = 8192;
   hipLaunchKernelGGL(dur_out_token_cons_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, h, H, w_out, b_out, dur_out, ld_out, idx, idx_stride,
                      force_idx, rows, (const SampleBlock*)sample, t, n, d);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// ... of the ROW-WISE step loop (80-byte block): row r draws with its own record; force_idx may be NULL, a range word is honoured as above
+extern "C" int ptv_dur_out_token_sample_rows(const float* h, int H, const float* w_out, const float* b_out, float* dur_out, long ld_out,
+                                             int* idx, long idx_stride, const int* force_idx, long rows, const void* sample80, int t, int n, int d,
+                                             void* stream) {
+  if (!h || !w_out || !b_out || !dur_out || !idx || rows <= 0 || H <= 0 || idx_stride < rows) return PTV_ERR_ARG;
+  if (!sample80 || t < 0 || t >= 32 || n < 0 || n >= 15 || d < 0 || d >= 5) return PTV_ERR_ARG;
+  long nb = (rows + 15) / 16; if (nb > 8192) nb = 8192;
+  hipLaunchKernelGGL(dur_out_token_rows_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, h, H, w_out, b_out, dur_out, ld_out, idx, idx_stride,
+                     force_idx, rows, (const SampleBlock*)sample80, t, n, d);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }
@@ -462,6 +530,19 @@ extern "C" int ptv_note_token_sample_cons(const float* pitch, long ld_pitch, con
   int nb = (M + 3) / 4; if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(note_token_kernel<3>, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
                      pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M, (const SampleBlock*)sample64, t);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+// ... with the 80-byte block of a row-wise decode: the 64-byte form with row r's record of the block's table (M is the batch)
+extern "C" int ptv_note_token_sample_rows(const float* pitch, long ld_pitch, const int* dur_idx, long dur_stride, const float* W, const float* bias, int E,
+                                          float* pred, long ld_pred, long* xhat, long xhat_stride, int* plen, int n, int last,
+                                          const int* force_pitch, int M, const void* sample80, int t, void* stream) {
+  if (!pitch || !dur_idx || !W || !bias || !pred || !xhat || !plen || M <= 0 || E <= 0) return PTV_ERR_ARG;
+  if (!sample80 || t < 0 || t >= 32 || n < 1 || n > 15) return PTV_ERR_ARG;
+  int nb = (M + 3) / 4; if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(note_token_kernel<4>, dim3(nb), dim3(256), 0, (hipStream_t)stream, pitch, ld_pitch, dur_idx, dur_stride, W, bias, E,
+                     pred, ld_pred, xhat, xhat_stride, plen, n, last, force_pitch, M, (const SampleBlock*)sample80, t);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

@@ -144,8 +144,12 @@ template <int W> __device__ __forceinline__ float row_max(float x) {
 }
 
 // THE keep rule, shared by every decision site (and ptv_debug_pitch_keep): class c of the row is kept iff logit[c] >= the value returned.
-// v: the NV logits this lane owns, -INFINITY where the column does not exist; all W lanes of the row call it together (tr and T are
-// uniform over the block: both tests below are scalar branches).
+// v: the NV logits this lane owns, -INFINITY where the column does not exist; all W lanes of the row call it together.  tr and T are
+// uniform over the W lanes of a row.  The block kinds pass the block's own words, uniform over the wave: the tests below are scalar
+// branches.  The row-wise kind (SampleBlockR below) passes each row's record, so with W = 16 the four rows of a wave may take different
+// branches: the rule holds all the same, because every cross-lane step inside a branch -- the rotations of row_sum<16> / row_max<16> --
+// stays inside one DPP row, whose 16 lanes are active or inactive together (a rotation never reads an inactive lane), and the select
+// loops run a fixed 32 rounds.  W = 64 also crosses DPP rows (__shfl_xor), and there the row is the wave: uniform again.
 // top_k: a 32-round bitwise select of the k-th largest order key -- a round counts the row's keys >= the candidate (NV compares per
 // lane, one W-lane sum) and keeps the bit if there are at least k; fixed cost, no LDS, independent of the lane layout.  The padding
 // keys are below every real one and k < 130 real values exist, so the selected key is a real logit's.
@@ -306,6 +310,34 @@ __device__ __forceinline__ unsigned pitch_constrain(const float (&v)[NV], const 
                                                     int word = -1) {
   return pitch_constrain<NV, W>(v, pitch_mask_own<NV, W>(m, j), lo, flags, j, tv, word);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Row-wise decode: the constrained kind with the six scalars of the block -- t_pitch, t_dur, top_k, ln_min_p, top_p_q24 and
+// the noise stream sample_offset + row -- replaced by one 32-byte record per row.  The block is the 64 bytes above followed by 16 more: 80
+// bytes, ten int64 words.  Of the first 64 the row-wise kernels read only seed, draw, flags and mask (the host writes t_pitch = t_dur = 0,
+// top_k = 0, LN_MIN_P_OFF, top_p_q24 = 0, sample_offset = 0); mask, ascending and every force word are honoured as by the 64-byte kind.
+//   rows:     the device address of int32 [B, 8], contiguous and 16-byte aligned -- row b:
+//             {float t_pitch, float t_dur, int top_k (0 = off), float ln_min_p (LN_MIN_P_OFF = off), uint32 top_p_q24 (0 = off),
+//              uint32 reserved = 0, int64 sample_id}
+//             the encodings of the scalar block, word for word; sample_id is the g of the Philox counter (sample_words), in place of
+//             sample_offset + row, range [0, 2^47).  seed and draw stay shared: sample_id already gives every row its own stream, and a
+//             row reproduces alone in a scalar decode that passes its id as sample_offset.
+// A row's record is two 16-byte loads, made once per launch by the lanes that decide for the row (rows past B clamped by the caller).
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct SampleBlockR {
+  SampleBlockC s;
+  const int* rows;
+  unsigned reserved0, reserved1;
+};
+static_assert(sizeof(SampleBlockR) == 80, "row-wise sampling block: 80 bytes (include/ptvae_hip.h)");
+struct RowRule { float t_pitch, t_dur; Trunc tr; long long id; };   // what a kernel keeps of a row's record
+__device__ __forceinline__ RowRule load_row_rule(const int* table, long r) {
+  const int4 a = *reinterpret_cast<const int4*>(table + r * 8), b = *reinterpret_cast<const int4*>(table + r * 8 + 4);
+  return RowRule{__builtin_bit_cast(float, a.x), __builtin_bit_cast(float, a.y),
+                 Trunc{a.z, __builtin_bit_cast(float, a.w), (unsigned)b.x},
+                 (long long)(((unsigned long long)(unsigned)b.w << 32) | (unsigned)b.z)};
+}
+__device__ __forceinline__ const int* load_row_table(const void* blk) { return reinterpret_cast<const SampleBlockR*>(blk)->rows; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Duration limits: THE rule of a duration range word, shared by every duration site that honours it (and

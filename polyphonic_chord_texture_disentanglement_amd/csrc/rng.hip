@@ -113,7 +113,54 @@ __global__ void pitch_constrain_kernel(const SampleBlockC* __restrict__ blk, con
   }
 }
 
+// test aid: the kernel above with a row table (philox.hpp SampleBlockR) in place of the block's scalars -- row r is judged by record r.  In
+// LAYOUT 0 the four rows of a wave hold four records: pitch_keep_threshold()'s branches diverge between them.  Of the block only the
+// flags are read; a clamped row takes the last row's record
+template <int LAYOUT>
+__global__ void pitch_constrain_rows_kernel(const SampleBlockC* __restrict__ blk, const int* __restrict__ table, const float* __restrict__ logits,
+                                            const int* __restrict__ masks, const int* __restrict__ lo, const int* __restrict__ words, long rows,
+                                            unsigned char* __restrict__ keep_out, float* __restrict__ thr_out) {
+  constexpr int W = LAYOUT ? 64 : 16, NV = LAYOUT ? 3 : 9;
+  const unsigned flags = blk->flags;
+  const long per = blockDim.x / W, total = (rows + per - 1) / per * per;
+  for (long r_ = (long)blockIdx.x * per + threadIdx.x / W; r_ < total; r_ += (long)gridDim.x * per) {
+    const bool ok = r_ < rows;
+    const long r = ok ? r_ : rows - 1;
+    const int j = threadIdx.x % W;
+    const RowRule rw = load_row_rule(table, r);
+    float v[NV], tv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) v[i] = j + W * i < 130 ? logits[r * 130 + j + W * i] : -INFINITY;
+    unsigned mw[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) mw[i] = (unsigned)masks[r * 4 + i];
+    const int word = words ? words[r] : -1;
+    const unsigned al = pitch_constrain<NV, W>(v, mw, lo[r], flags, j, tv, word);
+    const float thr = pitch_keep_threshold<NV, W>(rw.tr, rw.t_pitch, tv);
+    if (ok) {
+#pragma unroll
+      for (int i = 0; i < NV; i++) if (j + W * i < 130) keep_out[r * 130 + j + W * i] = ((al >> i) & 1u) && v[i] >= thr ? 1 : 0;
+      if (j == 0) thr_out[r] = thr;
+    }
+  }
+}
+
 }  // namespace ptv
+
+extern "C" int ptv_debug_pitch_constrain_rows(const void* block64, const int* table, const float* logits, const int* masks, const int* lo,
+                                              const int* words, long rows, int layout, unsigned char* keep_out, float* thr_out, void* stream) {
+  if (!block64 || !table || !logits || !masks || !lo || !keep_out || !thr_out || rows <= 0 || (layout != 0 && layout != 1)) return PTV_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(table) & 15) return PTV_ERR_ARG;
+  long nb = (rows + 3) / 4; if (nb > 4096) nb = 4096;
+  if (layout == 0)
+    hipLaunchKernelGGL(ptv::pitch_constrain_rows_kernel<0>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (const ptv::SampleBlockC*)block64, table,
+                       logits, masks, lo, words, rows, keep_out, thr_out);
+  else
+    hipLaunchKernelGGL(ptv::pitch_constrain_rows_kernel<1>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (const ptv::SampleBlockC*)block64, table,
+                       logits, masks, lo, words, rows, keep_out, thr_out);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
 
 static int debug_pitch_constrain(const void* block64, const float* logits, const int* masks, const int* lo, const int* words, long rows,
                                  int layout, unsigned char* keep_out, float* thr_out, void* stream) {

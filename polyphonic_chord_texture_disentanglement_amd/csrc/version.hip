@@ -19,6 +19,9 @@ extern "C" const char* ptv_arch(void) { return "gfx950"; }
 // stays because the host tests of the two round-7 families pin it; ptv_header_hash below is what refuses a library built from other headers
 // still 7: the per-sample scores (csrc/score.hip: ptv_recon_step_scores, ptv_score_fold, ptv_kl_rows, ptv_chord_step_scores, ptv_roll_match)
 // added; no existing entry point changed, and the same host tests pin the number
+// still 7: the row-wise decode kind (ptv_note_token_sample_rows, ptv_dur_gru_fwd_sample_rows, ptv_dur_out_token_sample_rows, bit 26 of
+// ptv_free_note_loop's train word, PTV_DFF_D_SAMPLE_ROWS appended, the 80-byte block of ptv_decode_logprob) added; no existing entry
+// point changed its arguments, and the same host tests pin the number
 extern "C" int ptv_abi_version(void) { return 7; }
 #ifndef PTV_HEADER_HASH
 #define PTV_HEADER_HASH "unknown"

@@ -19,6 +19,7 @@ import os
 import struct
 import weakref
 
+import numpy as np
 import torch
 
 from . import functional as F_
@@ -101,23 +102,41 @@ TOP_P_ONE = 1 << 24             # nucleus: the block holds top_p as round(top_p 
 CONS_BIT = 0x2000000            # ... io[21] is the 64-byte block (only together with SAMPLE_BIT)
 CONS_ASCENDING = 1              # flags bit 0: a pitch < 128 must exceed the largest pitch < 128 already decided in the time step; never <sos>
 CONS_MASK_ROW1 = 2              # flags bit 1: the mask has one row [32, 4] for the whole batch
+# row-wise decode (per-row sampling parameters: the constrained kind with its six scalars -- both temperatures, top_k, ln_min_p, top_p and
+# the noise stream -- replaced by one 32-byte record per row): the block grows to 80 bytes -- the 64 above (temperatures 0, no rule, sample
+# offset 0: the kernels read only seed, draw, flags and mask of them), then {uint64 device address of the row table int32 [B, 8], 8 reserved
+# bytes} -- ten words.  Row b of the table: {float T_pitch, float T_dur, int32 top_k, float ln_min_p, uint32 top_p_q24, 0, int64 sample_id}
+ROWS_BIT = 0x4000000            # ... io[21] is the 80-byte block (only together with SAMPLE_BIT)
+SAMPLE_ID_TOP = 1 << 47         # a sample id, like sample_offset + row, lies in [0, 2^47)
 
-# the four variants of a decode, each stated once: words of the block, its bits in ptv_free_note_loop's `train` word, the composite's
-# SAMPLE_TRUNC / SAMPLE_CONS dims, the kind number of PtvaeDecoder's graph keys, the bytes ptv_decode_logprob reads, and the entry points
-# of the non-persistent loop (note token, fused duration GRU, per-step duration token)
-BlockKind = collections.namedtuple('BlockKind', 'words bits trunc cons kind nbytes note_token dur_gru dur_token')
+# the five variants of a decode, each stated once: words of the block, its bits in ptv_free_note_loop's `train` word, the composite's
+# SAMPLE_TRUNC / SAMPLE_CONS / SAMPLE_ROWS dims, the kind number of PtvaeDecoder's graph keys, the bytes ptv_decode_logprob reads, and the
+# entry points of the non-persistent loop (note token, fused duration GRU, per-step duration token).  The row-wise kind is a constrained
+# kind (cons = 1: mask, flags and force words as there) whose duration entries take the force array or NULL under one name
+class BlockKind(collections.namedtuple('BlockKind', 'words bits trunc cons kind nbytes note_token dur_gru dur_token')):
+    __slots__ = ()
+
+    @property
+    def rows(self):
+        """1 for the row-wise kind (the composite's SAMPLE_ROWS dim), else 0"""
+        return int(self.kind == 4)
+
+
 ARGMAX = BlockKind(0, 0, 0, 0, 0, 0, 'ptv_note_token', 'ptv_dur_gru_fwd', 'ptv_dur_out_token')
 SAMPLED = BlockKind(4, SAMPLE_BIT, 0, 0, 1, 32, 'ptv_note_token_sample', 'ptv_dur_gru_fwd_sample', 'ptv_dur_out_token_sample')
 TRUNCATED = SAMPLED._replace(words=6, bits=SAMPLE_BIT | TRUNC_BIT, trunc=1, kind=2, nbytes=48, note_token='ptv_note_token_sample_trunc')
 CONSTRAINED = TRUNCATED._replace(words=8, bits=SAMPLE_BIT | TRUNC_BIT | CONS_BIT, cons=1, kind=3, nbytes=64,
                                  note_token='ptv_note_token_sample_cons')
+ROWWISE = CONSTRAINED._replace(words=10, bits=SAMPLE_BIT | TRUNC_BIT | CONS_BIT | ROWS_BIT, kind=4, nbytes=80,
+                               note_token='ptv_note_token_sample_rows', dur_gru='ptv_dur_gru_fwd_sample_rows',
+                               dur_token='ptv_dur_out_token_sample_rows')
 
 
 def block_kind(sampling):
     """the BlockKind of a sampling block by its word count; None is the argmax decode"""
     if sampling is None:
         return ARGMAX
-    for k in (SAMPLED, TRUNCATED, CONSTRAINED):
+    for k in (SAMPLED, TRUNCATED, CONSTRAINED, ROWWISE):
         if sampling.numel() == k.words:
             return k
     raise ValueError('sampling must be a block made by functional_free.sampling_block() on the device of z')
@@ -564,14 +583,117 @@ def check_keep(keep, batch=None):
         raise ValueError('keep was built for a batch of %d, the decoded batch has %d rows' % (B, batch))
 
 
+def _row_values(name, v, batch):
+    """one rule argument of row_sampling_words as a list of `batch` host values: a scalar (or None) broadcast, a host sequence or numpy
+    array of length batch taken element by element (numpy scalars become Python ones: the validators take those)"""
+    if v is None or isinstance(v, (bool, int, float, np.generic)):
+        v = [v] * batch
+    elif isinstance(v, np.ndarray):
+        v = v.tolist() if v.ndim == 1 else None
+    elif torch.is_tensor(v) or isinstance(v, (str, bytes)) or not hasattr(v, '__len__'):
+        v = None
+    if v is None or len(v) != batch:
+        raise ValueError('%s must be a scalar or a host sequence of %d values (one per row)' % (name, batch))
+    return [x.item() if isinstance(x, np.generic) else x for x in v]
+
+
+def row_sampling_words(batch, temperature, dur_temperature=None, top_k=None, min_p=None, top_p=None, sample_id=None, sample_offset=0):
+    """the row table of a row-wise decode as a host numpy int32 [batch, 8] (INTEGRATION.md "Per-row sampling"); touches no GPU.  Each of
+    the five rule arguments is a scalar (every row alike) or a host sequence / numpy array of `batch` values; None, or a None element,
+    is what it is for the scalar block (no temperature: 0; no rule).  Row b holds {T_pitch, T_dur, top_k, ln_min_p, top_p_q24} exactly as
+    check_sampling / check_truncation make them for b's values -- each distinct combination is validated once, and a ValueError is the
+    scalar one prefixed with the row --, then 0 and the int64 sample_id.  sample_id: None (sample_offset + b, the scalar block's rule) or
+    `batch` integers in [0, 2^47), the row's index in the Philox counter: a row reproduces alone in a scalar decode with that
+    sample_offset"""
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+        raise ValueError('batch must be an integer >= 1, got %r' % (batch,))
+    cols = [_row_values(name, v, batch) for name, v in (('temperature', temperature), ('dur_temperature', dur_temperature),
+                                                         ('top_k', top_k), ('min_p', min_p), ('top_p', top_p))]
+    if sample_id is None:
+        check_sampling(0.0, None, sample_offset)
+        ids = [sample_offset + b for b in range(batch)]
+    else:
+        ids = _row_values('sample_id', sample_id, batch)
+    out = np.zeros((batch, 8), dtype=np.int32)
+    f32, i64, seen = out.view(np.float32), out.view(np.int64), {}
+    for b, key in enumerate(zip(*cols)):
+        try:
+            tkey = tuple((type(x), x) for x in key)                # (2, 2.0 and True are equal as keys and not as values)
+            rec = seen.get(tkey) if all(isinstance(x, (int, float, type(None))) for x in key) else None
+            if rec is None:
+                t, td, k, mp, pp = key
+                tp_, td_ = check_sampling(t, td, top_k=k, min_p=mp, top_p=pp)[:2]
+                rec = (tp_, td_) + (check_truncation(k, mp, pp) or (0, LN_MIN_P_OFF, 0))
+                seen[tkey] = rec
+            v = ids[b]
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0 or v >= SAMPLE_ID_TOP:
+                raise ValueError('sample_id must be an integer in [0, 2^47), got %r' % (v,))
+        except ValueError as e:
+            raise ValueError('row %d: %s' % (b, e)) from None
+        f32[b, 0], f32[b, 1], out[b, 2], f32[b, 3], out[b, 4], i64[b, 3] = rec[0], rec[1], rec[2], rec[3], rec[4], v
+    return out
+
+
+class RowSampling:
+    """the row table of a row-wise decode on the device, for rows= (DisentangleVAE.row_sampling; INTEGRATION.md "Per-row sampling"):
+    table (int32 device tensor [batch, 8], row_sampling_words' layout), batch, and sample_offset, the default of update()"""
+
+    def __init__(self, table, batch, sample_offset=0):
+        self.table, self.batch, self.sample_offset = table, batch, sample_offset
+
+    def __iter__(self):
+        return iter((self.table, self.batch))
+
+    def update(self, temperature, dur_temperature=None, top_k=None, min_p=None, top_p=None, sample_id=None, sample_offset=None):
+        """new parameters into the SAME device tensor (one host-to-device copy): a captured graph, or a block made before, sees them.
+        A bad value is a ValueError that leaves the table as it was"""
+        words = row_sampling_words(self.batch, temperature, dur_temperature, top_k, min_p, top_p, sample_id,
+                                   self.sample_offset if sample_offset is None else sample_offset)
+        self.table.copy_(torch.from_numpy(words))
+        return self
+
+    def tiled(self, n):
+        """the table of the batch repeated n times (decode_best_of): candidate k of row b is row k * batch + b and draws as sample
+        sample_id[b] + k * batch -- with default ids the scalar block's rule; ids past 2^47 are the caller's to avoid"""
+        t = self.table.repeat(n, 1)
+        t.view(torch.int64)[:, 3] += (torch.arange(n, device=t.device) * self.batch).repeat_interleave(self.batch)
+        return RowSampling(t, n * self.batch, self.sample_offset)
+
+
+def check_rows(rows, batch=None, device=None):
+    """ValueError unless rows is None or a RowSampling whose table fits its batch (and `batch` / `device`, where the caller knows them)"""
+    if rows is None:
+        return
+    if not isinstance(rows, RowSampling):
+        raise ValueError('rows must be what DisentangleVAE.row_sampling(batch, ...) returns, got %r' % (type(rows).__name__,))
+    t_ = rows.table
+    if (not torch.is_tensor(t_) or t_.device.type != 'cuda' or t_.dtype != torch.int32 or tuple(t_.shape) != (rows.batch, 8)
+            or not t_.is_contiguous() or t_.data_ptr() % 16):
+        raise ValueError('rows.table must be a contiguous, 16-byte aligned int32 device tensor [%d, 8]' % (rows.batch,))
+    if batch is not None and rows.batch != batch:
+        raise ValueError('rows was built for a batch of %d, the decoded batch has %d rows' % (rows.batch, batch))
+    if device is not None and t_.device != device:
+        raise ValueError('rows.table is on %s, the decode on %s' % (t_.device, device))
+
+
 def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None,
-                   pitch_mask=None, ascending=None):
+                   pitch_mask=None, ascending=None, rows=None):
     """the block as four int64 words (host list); six with top_k / min_p / top_p; eight with pitch_mask / ascending (the last word is
-    the address of pitch_mask as given: the caller keeps that tensor alive and contiguous -- sampling_block does)"""
+    the address of pitch_mask as given: the caller keeps that tensor alive and contiguous -- sampling_block does); ten with rows (a
+    RowSampling: the ninth word is the address of its table, and the scalars it replaces must be left out -- the block then holds
+    temperatures 0, no rule and sample offset 0)"""
+    if rows is not None:
+        check_rows(rows)
+        if any(v is not None for v in (temperature, dur_temperature, top_k, min_p, top_p)) or sample_offset:
+            raise ValueError('rows carries temperature, dur_temperature, top_k, min_p, top_p and the sample ids of every row: '
+                             'leave the scalar keywords out')
+        temperature = 0.0
     tp, td, off, seed, draw = check_sampling(temperature, dur_temperature, sample_offset, seed, draw)
     words = [seed - (1 << 64) if seed >= (1 << 63) else seed, draw, off, struct.unpack('<q', struct.pack('<ff', tp, td))[0]]
     tr = check_truncation(top_k, min_p, top_p)
     flags = check_constraints(pitch_mask, ascending)
+    if rows is not None and flags is None:
+        flags = 0
     if flags is not None and tr is None:
         tr = (0, LN_MIN_P_OFF, 0)
     if tr is not None:
@@ -580,44 +702,53 @@ def sampling_words(temperature, dur_temperature=None, seed=7, draw=0, sample_off
         if pitch_mask is not None and not pitch_mask.is_contiguous():
             raise ValueError('pitch_mask must be contiguous')
         words += [flags, 0 if pitch_mask is None else pitch_mask.data_ptr()]
+    if rows is not None:
+        words += [rows.table.data_ptr(), 0]
     return words
 
 
-def sampling_block(device, temperature, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None,
-                   pitch_mask=None, ascending=None):
+def sampling_block(device, temperature=None, dur_temperature=None, seed=7, draw=0, sample_offset=0, *, top_k=None, min_p=None, top_p=None,
+                   pitch_mask=None, ascending=None, rows=None):
     """the device block of a sampled decode: PtvaeDecoder.decoder(..., sampling=block).  Four int64 words; six with top_k / min_p /
     top_p (truncated sampling, INTEGRATION.md "Sampled decode"); eight with pitch_mask / ascending (INTEGRATION.md "Constrained
     decode"; temperature 0 is then the constrained argmax).  The word count selects the kernels.  An eight-word block carries the mask
-    it points at as its attribute `pitch_mask` (None without one): that keeps the mask alive, and tells the decoder its row count"""
+    it points at as its attribute `pitch_mask` (None without one): that keeps the mask alive, and tells the decoder its row count; ten
+    with rows (a RowSampling; INTEGRATION.md "Per-row sampling"), which the block carries as its attribute `rows`"""
     if pitch_mask is not None and torch.is_tensor(pitch_mask):
         pitch_mask = pitch_mask.contiguous()
     words = sampling_words(temperature, dur_temperature, seed, draw, sample_offset, top_k=top_k, min_p=min_p, top_p=top_p,
-                           pitch_mask=pitch_mask, ascending=ascending)
+                           pitch_mask=pitch_mask, ascending=ascending, rows=rows)
     if torch.device(device).type != 'cuda':
         raise RuntimeError('a sampled decode runs on the GPU: the sampling block lives in device memory (got device %s)' % (device,))
-    blk = make_block(words, pitch_mask, device)
+    blk = make_block(words, pitch_mask, device, rows)
     if pitch_mask is not None and pitch_mask.device != blk.device:
         raise ValueError('pitch_mask is on %s, the block on %s' % (pitch_mask.device, blk.device))
+    check_rows(rows, device=blk.device)
     return blk
 
 
-def make_block(words, pitch_mask, device):
-    """validated host words (sampling_words) and the contiguous mask their last word points at -> the device block; the eight-word form
-    gets the mask as its attribute, and its ascending flag as the host bool `ascending`"""
+def make_block(words, pitch_mask, device, rows=None):
+    """validated host words (sampling_words) and the contiguous mask their eighth word points at -> the device block; the eight-word form
+    gets the mask as its attribute, and its ascending flag as the host bool `ascending`; the ten-word form also the RowSampling whose
+    table its ninth word points at, as `rows`"""
     blk = torch.tensor(words, dtype=torch.int64, device=device)
-    if len(words) == CONSTRAINED.words:
+    if len(words) >= CONSTRAINED.words:
         blk.pitch_mask = pitch_mask
         blk.ascending = bool(words[6] & 1)
+    if len(words) == ROWWISE.words:
+        blk.rows = rows
     return blk
 
 
 def clone_block(blk, pitch_mask=None):
     """a copy of a block (clone() alone drops the attributes); an eight-word copy carries `pitch_mask`, or the original's when none is
-    given, and `ascending`"""
+    given, and `ascending`; a ten-word copy also `rows`"""
     out = blk.clone()
     if hasattr(blk, 'pitch_mask'):
         out.pitch_mask = blk.pitch_mask if pitch_mask is None else pitch_mask
         out.ascending = getattr(blk, 'ascending', False)
+    if hasattr(blk, 'rows'):
+        out.rows = blk.rows
     return out
 
 
@@ -630,6 +761,10 @@ def _check_block(sampling, dev, B=None):
         mask = sampling.pitch_mask
         if mask is not None and (mask.device != dev or (B is not None and mask.shape[0] not in (1, B))):
             raise ValueError('pitch_mask has %d rows on %s, the decoded batch has %s rows on %s' % (mask.shape[0], mask.device, B, dev))
+    if block_kind(sampling).rows:
+        if getattr(sampling, 'rows', None) is None:
+            raise ValueError('a row-wise block must come from functional_free.sampling_block(rows=...): it carries the table it points at')
+        check_rows(sampling.rows, B, dev)
     return sampling
 
 
@@ -990,7 +1125,7 @@ def _free_fwd_composite(plan, P, buf, tbl, inp):
                        'LOOP_FLAGS': note_loop_word(plan.train, plan.replay, NOTE_LOOP_SPLIT, plan.cluster), 'CLUSTER': cluster,
                        'RESUM_TRAIN': int(plan.train and not plan.replay), 'TOK0_LDS': tbl.tok0_lds,
                        'W_IH_T_BF16': tbl.w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': tbl.w_hh_t.dtype == torch.bfloat16,
-                       'SAMPLE_TRUNC': plan.kind.trunc, 'SAMPLE_CONS': plan.kind.cons})
+                       'SAMPLE_TRUNC': plan.kind.trunc, 'SAMPLE_CONS': plan.kind.cons, 'SAMPLE_ROWS': plan.kind.rows})
     masks, tc = inp.masks, inp.time_coins
     # the cluster-mode note loops take the persistent-launch turn (functional._PersistTurn): the library records again after the last one
     turn = F_._CompositeTurn(F_.cur_stream()) if cluster else None
@@ -1099,9 +1234,11 @@ def _note_step(plan, P, buf, tbl, inp, t, n, GCt):
     gemm(h, w_dh[:, :Hn], HD[0][pr], bias=P['dur_hid_linear.bias'], prec=prec)
     gemm(pitch[pr], w_dh[:, Hn:], HD[0][pr], acc=True, prec=prec)
     # (the constrained kind with force arrays: the entries that honour a duration range word -- INTEGRATION.md "Duration limits")
+    # (the row-wise kind: one entry each, with the force array or NULL)
     cons_dur = bool(kind.cons) and force_dur is not None
+    sfx = '' if kind.rows else '_cons'
     if prec == 1 and Hd == 64 and F_.FUSED_DUR:
-        call(kind.dur_gru + ('_cons' if cons_dur else ''), Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tbl.tab0), ptr(tbl.tab), ptr(w_out_d), ptr(b_out_d),
+        call(kind.dur_gru + (sfx if cons_dur else ''), Hd, B, ptr(HD[0][pr]), Hd, ptr(w_hh_d), ptr(b_hh_d), ptr(tbl.tab0), ptr(tbl.tab), ptr(w_out_d), ptr(b_out_d),
              ptr(HD[1][pr]), M * Hd, None, ptr(gates_d[0][0][pr]) if train else None, M * Hd, 4 * M * Hd, F_._bf(gates_d), ptr(dur2[pr]), 10,
              ptr(idx[0][pr]), M, ptr(force_dur[0][pr]) if force_dur is not None else None, M, *(smp and smp + (t, n)), st)
     else:
@@ -1109,9 +1246,9 @@ def _note_step(plan, P, buf, tbl, inp, t, n, GCt):
             g_, g_ld, g_idx = (tbl.tab0, 0, None) if d == 0 else (tbl.tab, 3 * Hd, idx[d - 1][pr])
             gru_step(prec, HD[d][pr], g_, g_ld, w_hh_d, b_hh_d, HD[d + 1][pr], gates=gates_d[d][:, pr] if train else None, plane=M * Hd,
                      gi_idx=g_idx)
-            if cons_dur:
-                call(kind.dur_token + '_cons', ptr(HD[d + 1][pr]), Hd, ptr(w_out_d), ptr(b_out_d), ptr(dur2[pr][:, 2 * d:]), 10,
-                     ptr(idx[d][pr]), M, ptr(force_dur[d][pr]), B, *smp, t, n, d, st)
+            if cons_dur or kind.rows:
+                call(kind.dur_token + sfx, ptr(HD[d + 1][pr]), Hd, ptr(w_out_d), ptr(b_out_d), ptr(dur2[pr][:, 2 * d:]), 10,
+                     ptr(idx[d][pr]), M, ptr(force_dur[d][pr]) if force_dur is not None else None, B, *smp, t, n, d, st)
                 continue
             call(kind.dur_token, ptr(HD[d + 1][pr]), Hd, ptr(w_out_d), ptr(b_out_d), ptr(dur2[pr][:, 2 * d:]), 10, ptr(idx[d][pr]),
                  ptr(force_dur[d][pr]) if force_dur is not None else None, B, *(smp and smp + (t, n, d)), st)

@@ -13,9 +13,9 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import (build_chord_keep, build_dur_limits, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice,
-                              check_chord_keep, check_chord_sampling, check_constraints, check_keep, check_sampling, make_block,
-                              sampling_words, split_top, split_voice)
+from .functional_free import (RowSampling, build_chord_keep, build_dur_limits, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice,
+                              check_chord_keep, check_chord_sampling, check_constraints, check_keep, check_rows, check_sampling, make_block,
+                              row_sampling_words, sampling_words, split_top, split_voice)
 from .optim import refresh_weight_shadows
 from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
@@ -37,8 +37,10 @@ CHD_DEC_SLOT = 4        # the chord decoder beside the PianoTree decoder
 ENC_CHAIN = True
 DT_PAD_COL = 3          # column of dt_x that is set for a <pad> row (is_note class 3, dataset.py:194-195): its zeros count the live rows
 DT_SHAPE = (32, 16, 39)
-# the keywords of a free-running decode (inference_decode); the last two are device objects, the rest host values
-DECODE_KEYS = ('temperature', 'dur_temperature', 'seed', 'draw', 'sample_offset', 'top_k', 'min_p', 'top_p', 'ascending', 'pitch_mask', 'keep')
+# the keywords of a free-running decode (inference_decode); rows (a functional_free.RowSampling) and the last two are device objects, the
+# rest host values
+DECODE_KEYS = ('temperature', 'dur_temperature', 'seed', 'draw', 'sample_offset', 'top_k', 'min_p', 'top_p', 'rows', 'ascending', 'pitch_mask',
+               'keep')
 
 
 class DecodeRequest(collections.namedtuple('DecodeRequest', 'sampled kw mask keep batch')):
@@ -46,8 +48,11 @@ class DecodeRequest(collections.namedtuple('DecodeRequest', 'sampled kw mask kee
     (pitch_mask made contiguous -- the block holds its address -- or None), keep (functional_free.Keep or None), batch (the decoded rows)"""
 
     def tiled(self, n):
-        """the request of the batch repeated n times (decode_best_of): a mask or keep with one row per sample is tiled alike"""
+        """the request of the batch repeated n times (decode_best_of): a mask or keep with one row per sample is tiled alike, and so is
+        the table of rows= -- candidate k of row b draws as sample sample_id[b] + k * B"""
         mask, keep, B = self.mask, self.keep, self.batch
+        if self.kw.get('rows') is not None:
+            self = self._replace(kw=dict(self.kw, rows=self.kw['rows'].tiled(n)))
         if mask is not None and mask.shape[0] == B and B > 1:
             mask = mask.repeat(n, 1, 1)
         if keep is not None:
@@ -392,14 +397,25 @@ class DisentangleVAE(PytorchModel):
     # use, ascending=True makes the notes of a time step strictly increasing and never <sos> -- the PianoTree grammar.  <eos> is always
     # allowed.  The mask's rows are the rows of the decoded batch (sample_offset moves only the noise).  With temperature=None the decode
     # is the constrained ARGMAX (the draw counter does not advance; seed / draw / sample_offset stay a ValueError).
+    # Per-row sampling (INTEGRATION.md "Per-row sampling"): rows= (row_sampling() below builds one) gives every row of the batch its own
+    # temperature, dur_temperature, top_k, min_p, top_p and sample id -- a batch of different requests, or a sweep of one z, as ONE decode.
+    # It makes the decode a sampled one (the draw counter advances as with temperature=), excludes those five keywords and sample_offset,
+    # and combines with seed, draw, pitch_mask, ascending and keep like a constrained decode.
     @staticmethod
     def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
-                        top_p=None, pitch_mask=None, ascending=None, keep=None, batch=None):
+                        top_p=None, rows=None, pitch_mask=None, ascending=None, keep=None, batch=None):
         """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode (constrained or not).  No side
         effect, no launch.  batch: the rows of the decoded batch where the caller knows them (pitch_mask's row count and keep's batch are
         held to it)"""
         check_constraints(pitch_mask, ascending, batch)
         check_keep(keep, batch)
+        if rows is not None:                                   # per-row sampling: a sampled decode whose rule is the table's
+            if any(v is not None for v in (temperature, dur_temperature, top_k, min_p, top_p, sample_offset)):
+                raise ValueError('rows carries temperature, dur_temperature, top_k, min_p, top_p and the sample ids of every row: it cannot '
+                                 'be combined with those keywords or with sample_offset')
+            check_rows(rows, batch)
+            check_sampling(0.0, None, 0, 0 if seed is None else seed, 0 if draw is None else draw)
+            return True
         if temperature is None and dur_temperature is None:
             if seed is not None or draw is not None or sample_offset is not None:
                 raise ValueError('seed / draw / sample_offset belong to a sampled decode: give a temperature')
@@ -439,9 +455,13 @@ class DisentangleVAE(PytorchModel):
             return sampling_words(0.0, 0.0, 0, 0, 0, pitch_mask=req.mask, ascending=ascending)   # the constrained argmax: no noise, no draw used
         ph = self._philox or (7, 0)
         seed, draw, offset = kw['seed'], kw['draw'], kw['sample_offset']
-        words = sampling_words(kw['temperature'], kw['dur_temperature'], ph[0] if seed is None else seed,
-                               self._sample_draws if draw is None else draw, ph[1] if offset is None else offset, top_k=kw['top_k'],
-                               min_p=kw['min_p'], top_p=kw['top_p'], pitch_mask=req.mask, ascending=ascending)
+        if kw['rows'] is not None:                             # (the table holds every row's rule and sample id; seed and draw stay shared)
+            words = sampling_words(None, None, ph[0] if seed is None else seed, self._sample_draws if draw is None else draw, 0,
+                                   pitch_mask=req.mask, ascending=ascending, rows=kw['rows'])
+        else:
+            words = sampling_words(kw['temperature'], kw['dur_temperature'], ph[0] if seed is None else seed,
+                                   self._sample_draws if draw is None else draw, ph[1] if offset is None else offset, top_k=kw['top_k'],
+                                   min_p=kw['min_p'], top_p=kw['top_p'], pitch_mask=req.mask, ascending=ascending)
         if draw is None:
             self._sample_draws += 1
         return words
@@ -453,10 +473,24 @@ class DisentangleVAE(PytorchModel):
             _require_cuda(z_chd, 'DisentangleVAE sampled decode')
             _require_cuda(z_rhy, 'DisentangleVAE sampled decode')
         dec_z = torch.cat([z_chd, z_rhy], dim=-1)
-        block = None if words is None else make_block(words, req.mask, dec_z.device)
+        block = None if words is None else make_block(words, req.mask, dec_z.device, req.kw['rows'])
         if req.keep is not None:
             _require_cuda(dec_z, 'DisentangleVAE decode with kept steps')
         return self.decoder(dec_z, True, None, None, 0., 0., sampling=block, keep=req.keep)
+
+    def row_sampling(self, batch, temperature, dur_temperature=None, top_k=None, min_p=None, top_p=None, sample_id=None, sample_offset=None):
+        """The sampling rule of every row of a decode -> functional_free.RowSampling(table, batch) for rows= (INTEGRATION.md "Per-row
+        sampling").  Each of temperature, dur_temperature, top_k, min_p, top_p is a scalar (every row alike) or a host sequence / numpy
+        array of `batch` values with the meaning of the scalar keyword; sample_id: None (sample_offset + row; sample_offset defaults to
+        use_philox()'s, else 0) or `batch` integers in [0, 2^47), the row's own index in the noise stream.  table is an int32 device
+        tensor [batch, 8] on the decoder's device; RowSampling.update(...) rewrites it in place.  A bad value is a ValueError naming its
+        row, before anything touches the GPU."""
+        offset = (self._philox or (7, 0))[1] if sample_offset is None else sample_offset
+        words = row_sampling_words(batch, temperature, dur_temperature, top_k, min_p, top_p, sample_id, offset)
+        dev = next(self.decoder.parameters()).device
+        if dev.type != 'cuda':
+            raise RuntimeError('a sampled decode runs on the GPU: the row table lives in device memory (the model is on %s)' % (dev,))
+        return RowSampling(torch.from_numpy(words).to(dev), batch, offset)
 
     def keep(self, x, steps):
         """The kept time steps of a decode -> functional_free.Keep(pitch, dur, err, batch) for keep= (ptv_keep_force_build; INTEGRATION.md
@@ -577,7 +611,7 @@ class DisentangleVAE(PytorchModel):
         return out
 
     def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None,
-                         top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None, keep=None):
+                         top_k=None, min_p=None, top_p=None, rows=None, pitch_mask=None, ascending=None, keep=None):
         kw = locals()
         return self._inference_decode(z_chd, z_rhy, self._request(z_chd.shape[0], **{k: kw[k] for k in DECODE_KEYS}))
 
@@ -643,7 +677,7 @@ class DisentangleVAE(PytorchModel):
     # ---- the output path on the device: decoded grid and chord logits -> the three tensors the model consumes plus a note list
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
-                         sample_offset=None, top_k=None, min_p=None, top_p=None, pitch_mask=None, ascending=None, keep=None,
+                         sample_offset=None, top_k=None, min_p=None, top_p=None, rows=None, pitch_mask=None, ascending=None, keep=None,
                          return_logprob=False, chord_temperature=None, chroma_temperature=None, keep_chords=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
@@ -656,7 +690,7 @@ class DisentangleVAE(PytorchModel):
         once.  With none of the three the call is what it was: the same launches, the same bits."""
         kw = locals()
         B = z_chd.shape[0]
-        note_sampled = temperature is not None or dur_temperature is not None
+        note_sampled = temperature is not None or dur_temperature is not None or rows is not None
         creq = self._chord_request(B, chord_temperature, chroma_temperature, keep_chords, seed, draw, sample_offset, note_sampled)
         note_kw = {k: kw[k] for k in DECODE_KEYS}
         if creq is not None and creq.sampled and not note_sampled:
@@ -691,7 +725,7 @@ class DisentangleVAE(PytorchModel):
         return self.decode_to_inputs(z_chd, z_rhy, max_notes, return_logprob=True, **sampling)
 
     @staticmethod
-    def _check_best_of(n, rank_by='logp', length_normalize=False, temperature=None, dur_temperature=None, **_):
+    def _check_best_of(n, rank_by='logp', length_normalize=False, temperature=None, dur_temperature=None, rows=None, **_):
         """ValueError for a bad decode_best_of argument; no side effect, no launch"""
         if isinstance(n, bool) or not isinstance(n, int) or n < 1:
             raise ValueError('n must be an integer >= 1, got %r' % (n,))
@@ -699,7 +733,7 @@ class DisentangleVAE(PytorchModel):
             raise ValueError("rank_by must be 'logp' or 'logq', got %r" % (rank_by,))
         if not isinstance(length_normalize, bool):
             raise ValueError('length_normalize must be a bool, got %r' % (length_normalize,))
-        if temperature is None and dur_temperature is None:
+        if temperature is None and dur_temperature is None and rows is None:
             raise ValueError('decode_best_of ranks draws of a sampled decode: give a temperature (an argmax decode has one candidate)')
 
     def decode_best_of(self, z_chd, z_rhy, n, *, rank_by='logp', length_normalize=False, max_notes=10, **sampling):

@@ -263,10 +263,11 @@ DecodeLogprob = collections.namedtuple('DecodeLogprob', 'logp logq counts err st
 LastDecode = collections.namedtuple('LastDecode', 'pitch dur xhat sampling force')      # what an inference decode leaves for decode_logprob()
 
 
-class _DecodeGraph(collections.namedtuple('_DecodeGraph', 'graph z outs block mask mask_addr force')):
+class _DecodeGraph(collections.namedtuple('_DecodeGraph', 'graph z outs block mask mask_addr force rows rows_addr', defaults=(None, None))):
     """one captured inference decode: graph, z (static input), outs (static outputs), block / mask / mask_addr (static sampling block, the
     static pitch mask of a constrained one and the one-word tensor holding that mask's address; None where the kind has none), force (the
-    static force arrays of a decode with kept steps, or None)"""
+    static force arrays of a decode with kept steps, or None), rows / rows_addr (the static row table of a row-wise decode and the
+    one-word tensor holding its address, or None)"""
 
     def refresh(self, z, sampling, keep):
         """the caller's inputs into the static tensors, before every replay"""
@@ -279,6 +280,9 @@ class _DecodeGraph(collections.namedtuple('_DecodeGraph', 'graph z outs block ma
             if self.mask is not None and sampling.pitch_mask is not None:
                 self.mask[:sampling.pitch_mask.shape[0]].copy_(sampling.pitch_mask)   # (a one-row mask: row 0, the block's flag says so)
                 self.block[7:8].copy_(self.mask_addr)
+            if self.rows is not None:
+                self.rows.copy_(sampling.rows.table)
+                self.block[8:9].copy_(self.rows_addr)
 
 
 class PtvaeDecoder(nn.Module, _PrecMixin):
@@ -337,16 +341,16 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         """Free-running decode replayed from a captured hipGraph: the step loop is ~9,000 tiny launches whose order and arguments depend
         only on (B, precision) -- capture once, then one graph launch per call.  The graph holds raw parameter pointers, so it is
         re-captured if the parameter storage moves.  Each kind of decode (functional_free.BlockKind: argmax, sampled, truncated,
-        constrained) is a graph of its own (other kernels), and kept steps (keep: functional_free.Keep) double the kinds: the key holds
+        constrained, row-wise) is a graph of its own (other kernels), and kept steps (keep: functional_free.Keep) double the kinds: the key holds
         the kind number and, only with a keep, one more element.  What a caller may vary -- z, seed / draw / temperatures / top_k / min_p
-        / top_p / flags in the block, the pitch mask, the force arrays of a keep -- lives in static tensors that _DecodeGraph.refresh
+        / top_p / flags in the block, the pitch mask, the row table, the force arrays of a keep -- lives in static tensors that _DecodeGraph.refresh
         fills before every replay, so one capture per key serves them all."""
         ps = self._params_free()
         kind = FF_.block_kind(sampling)
         key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind.kind) + ((True,) if keep is not None else ())
         ent = self._graphs.get(key)
         if ent is None:
-            block = mask = mask_addr = None
+            block = mask = mask_addr = rows = rows_addr = None
             if kind.cons:                                      # (captured with every pitch allowed; the flags are the first caller's)
                 mask = torch.full((z.shape[0], 32, 4), -1, dtype=torch.int32, device=z.device)
                 mask_addr = torch.tensor([mask.data_ptr()], dtype=torch.int64, device=z.device)
@@ -355,6 +359,11 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
                 ps = ps + [block]
             if kind.cons:
                 block[7:8].copy_(mask_addr if sampling.pitch_mask is not None else torch.zeros_like(mask_addr))
+            if kind.rows:                                      # (a static table: any caller's table is copied into it before a replay)
+                rows = sampling.rows.table.clone()
+                rows_addr = torch.tensor([rows.data_ptr()], dtype=torch.int64, device=z.device)
+                block.rows = FF_.RowSampling(rows, z.shape[0])
+                block[8:9].copy_(rows_addr)
             static_z = z.detach().clone()
             force = None if keep is None else {'pitch': keep.pitch.clone(), 'dur': keep.dur.clone()}
             cur = torch.cuda.current_stream()
@@ -373,7 +382,7 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             for k in [k for k in self._graphs if k[4:] == key[4:]]:         # one graph per kind (argmax, sampled, truncated, constrained; each
                 del self._graphs[k]                                         # with and without kept steps) is kept
             self.graph_captures += 1
-            ent = self._graphs[key] = _DecodeGraph(g, static_z, outs, block, mask, mask_addr, force)
+            ent = self._graphs[key] = _DecodeGraph(g, static_z, outs, block, mask, mask_addr, force, rows, rows_addr)
         ent.refresh(z, sampling, keep)
         ent.graph.replay()
         return ent.outs

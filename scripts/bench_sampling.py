@@ -21,9 +21,15 @@ be read beside it -- and under mask + ascending + top_k + top_p, beside the same
 The logprob rows (--logprob 1; PtvaeDecoder.decode_logprob, DisentangleVAE.decode_best_of) time the log-probability pass ALONE -- the two
 launches after a plain sampled decode, and after the mask + ascending + top_k + top_p decode, where every row also runs the allowed rule
 and both 32-round selects -- and decode_best_of(n=4) at a quarter of the batch (as many decoded rows as one plain decode of the batch).
+The rows rows (--rows 1; per-row sampling, DisentangleVAE.row_sampling: the row-wise kind, whose kernels read temperature, top_k, min_p,
+top_p and the sample id of every row from a table) run (a) a uniform table holding the plain sampled values, beside the plain sampled
+decode and beside the constrained scalar kind with the same values ('constrained plain': the kernels the row-wise kind is made from), and
+(b) the six-group table of the tests -- no rule, T = 0, top_k = 4, top_p = 0.85, min_p = 0.2, top_k = 8 + top_p = 0.9 + min_p = 0.05 by
+row % 6, so that every wave holds four rules and both selects diverge between its rows -- beside 'constrained top_k+top_p', the scalar
+decode of its most expensive member.
 
     python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--top-k 8] [--min-p 0.9] [--top-p 0.9]
-                                     [--constrained 1] [--keep 1] [--logprob 1] [--eager]
+                                     [--constrained 1] [--keep 1] [--logprob 1] [--rows 1] [--eager]
 
 --top-k 0, --min-p 0 and --top-p 0 switch the rule off; with top_k and min_p both off the 'truncated' decode is not timed, with top_p
 off the two nucleus rows are not; --constrained 0 leaves the constrained rows out.
@@ -52,6 +58,7 @@ def main():
     ap.add_argument('--constrained', type=int, default=1, help='0 = no constrained rows')
     ap.add_argument('--keep', type=int, default=1, help='0 = no keep rows')
     ap.add_argument('--logprob', type=int, default=1, help='0 = no logprob / best-of rows')
+    ap.add_argument('--rows', type=int, default=1, help='0 = no per-row sampling rows')
     ap.add_argument('--eager', action='store_true', help='no graph replay')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the MI355X'
@@ -97,6 +104,14 @@ def main():
         if a.constrained:
             keeps['dur limits+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.dur_limits(min_dur=2, fit='bar', batch=a.batch))
     kinds += list(keeps)
+    rowwise = {}                                             # kind -> (the kinds it is compared with, its RowSampling)
+    if a.rows:
+        six = (dict(), dict(t=0.0), dict(top_k=4), dict(top_p=0.85), dict(min_p=0.2), dict(top_k=8, top_p=0.9, min_p=0.05))
+        col = lambda key, default=None: [six[b % 6].get(key, default) for b in range(a.batch)]           # noqa: E731
+        rowwise['rows uniform'] = (('sampled', 'constrained plain'), m.row_sampling(a.batch, a.temperature))
+        rowwise['rows mixed'] = (('constrained top_k+top_p',), m.row_sampling(a.batch, col('t', a.temperature), top_k=col('top_k'),
+                                                                           min_p=col('min_p'), top_p=col('top_p')))
+        kinds += ['constrained plain', 'constrained top_k+top_p'] + list(rowwise)
     blocks = {'argmax': [None] * (a.rounds + 1),
               'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
               'truncated': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **trunc) for d in range(a.rounds + 1)]}
@@ -105,6 +120,12 @@ def main():
     for k, kw in constrained.items():
         blocks[k] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **kw) for d in range(a.rounds + 1)]
 
+    if a.rows:
+        blocks['constrained plain'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=False) for d in range(a.rounds + 1)]
+        blocks['constrained top_k+top_p'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=False, top_k=8, top_p=0.9)
+                                             for d in range(a.rounds + 1)]
+    for k, (_, rs) in rowwise.items():
+        blocks[k] = [FF_.sampling_block(dev, seed=7, draw=d, rows=rs) for d in range(a.rounds + 1)]
     for k, (base, _) in keeps.items():
         blocks[k] = blocks[base]
     if 'keep rhythm' in keeps:                               # a rhythm keep needs the constrained kind: the vacuous constraint
@@ -139,7 +160,7 @@ def main():
     assert m.decoder.graph_captures == captures              # a new draw is not a new capture
     rate = {k: [round(a.batch / (v * 1e-3), 1) for v in vs] for k, vs in ms.items()}
     best = {k: max(v) for k, v in rate.items()}
-    out = {'what': 'free-running decode: argmax, sampled, truncated-sampled, nucleus-sampled and constrained decisions, kept steps', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
+    out = {'what': 'free-running decode: argmax, sampled, truncated-sampled, nucleus-sampled and constrained decisions, kept steps, per-row sampling', 'batch': a.batch, 'graph': not a.eager, 'reps': a.reps,
            'temperature': a.temperature, 'top_k': a.top_k, 'min_p': a.min_p, 'top_p': a.top_p, 'ms_per_decode': {k: [round(x, 3) for x in v] for k, v in ms.items()},
            'samples_per_s': rate, 'sampled_over_argmax_best': round(best['sampled'] / best['argmax'], 4)}
     if 'truncated' in kinds:
@@ -150,6 +171,10 @@ def main():
     for k, (base, _) in keeps.items():
         out[k + '_over_' + base + '_best'] = round(best[k] / best[base], 4)
         out[k + '_over_' + base + '_by_round'] = [round(x / y, 4) for x, y in zip(rate[k], rate[base])]
+    for k, (bases, _) in rowwise.items():
+        for base in bases:
+            out[k + '_over_' + base + '_best'] = round(best[k] / best[base], 4)
+            out[k + '_over_' + base + '_by_round'] = [round(x / y, 4) for x, y in zip(rate[k], rate[base])]
     if a.logprob:
         def timed_pass():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
