@@ -23,14 +23,18 @@ NOISE_DELTA = 9.537e-07
 NOISE_TOL = 4e-06
 
 
-def words(seed, draw, g, t, n, kind, sub):
-    """broadcastable integer arrays -> uint32 [..., 4]"""
+def counter(draw, g, t, n, kind, sub):
+    """the four counter words of a call before Philox: broadcastable integer arrays -> uint64 [..., 4], every word < 2^32"""
     g, t, n, sub = np.broadcast_arrays(*(np.asarray(a, dtype=np.uint64) for a in (g, t, n, sub)))
     c1 = ((g >> np.uint64(32)) << np.uint64(16)) | (t << np.uint64(11)) | (n << np.uint64(7)) | np.uint64(kind << 6) | sub
-    ctr = np.stack([g & np.uint64(0xFFFFFFFF), c1 & np.uint64(0xFFFFFFFF), np.full(g.shape, draw & 0xFFFFFFFF, dtype=np.uint64),
-                    np.full(g.shape, 0x80000000 | (draw >> 32), dtype=np.uint64)], -1)
+    return np.stack([g & np.uint64(0xFFFFFFFF), c1 & np.uint64(0xFFFFFFFF), np.full(g.shape, draw & 0xFFFFFFFF, dtype=np.uint64),
+                     np.full(g.shape, 0x80000000 | (draw >> 32), dtype=np.uint64)], -1)
+
+
+def words(seed, draw, g, t, n, kind, sub):
+    """broadcastable integer arrays -> uint32 [..., 4]"""
     key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
-    return philox4x32_10(ctr, key)
+    return philox4x32_10(counter(draw, g, t, n, kind, sub), key)
 
 
 def uniform_from_word(w):
