@@ -1249,6 +1249,38 @@ int ptv_grid_split_top(const long* x, const unsigned char* mode, int mode_rows, 
 int ptv_dur_range_force_build(const unsigned char* lo, int lo_rows, const unsigned char* hi, int hi_rows, const unsigned char* steps,
                               int steps_rows, const int* src_pitch, const int* src_dur, long B, int* force_pitch, int* force_dur, int* yielded,
                               void* stream);
+/* Note-count limits: a decode whose time steps have a number of notes in a range per (sample, time step) -- "at most four notes per step",
+ * "at least a dyad on every beat", "rests on the off-beats", "notes exactly on this onset pattern" -- with no grid to copy the count from
+ * (csrc/keep.hip; INTEGRATION.md "Note-count limits").  The count-side twin of "Duration limits": no new word, the builder
+ * writes a forced <eos> (129), PTV_FORCE_NOT_EOS and PTV_FORCE_BELOW(u) from limits instead of from a grid.
+ * ptv_note_count_force_build: the force arrays.  lo / hi: uint8 [rows][32] in NOTE COUNTS (rows = 1 or B, each its own), steps: uint8
+ *   [steps_rows][32], non-zero = the step is SELECTED.  src_pitch / src_dur: the arrays of an existing keep to build INTO, or both NULL
+ *   (= every word -1); they may not be the outputs.  flags: bit 0 = "room" (below).  Per (b, t) of a selected step:
+ *   F = lo and H = hi, each clamped into 0..15; the ceiling wins: L = min(F, H).  w[n], n = 0..14: the step's words of src_pitch.
+ *   Owned step: some w[n] is 129, or is a negative word other than -1 (the keep already fixes this step's count: whole, rhythm and top
+ *     steps).  The step is copied bit for bit and bit 1 (value 2) of yielded[b][t] is set.
+ *   Otherwise: J = 1 + the index of the last w[n] >= 0, or 0 with none (the forced prefix of a kept voice); E = max(H, J).  Only words
+ *     equal to -1 are ever replaced.
+ *     Floor:   for n < L with w[n] == -1 the word is PTV_FORCE_NOT_EOS, or with the room flag PTV_FORCE_BELOW(128 - (L - 1 - n)).
+ *              Under `ascending` the room ceilings guarantee the floor: decision n lies at or below 128 - L + n, so decision n + 1 always
+ *              has a note left; with a mask the BELOW rule lets the mask yield, never the count.
+ *              WITHOUT the room flag a floor is "not <eos> while anything else is allowed", the meaning PTV_FORCE_NOT_EOS already has:
+ *              under a narrow mask or `ascending` the allowed set can shrink to <eos> alone and the count FALLS SHORT of L; nothing
+ *              reports it at decode time -- count the notes.
+ *     Ceiling: if E <= 14 and w[E] == -1, w[E] = 129.  H = 0 makes the step a rest; H = 15 is no ceiling.  A forced <eos> behind a step
+ *              that already ended is inert: the note loop decides nothing behind the first <eos> of a step.
+ *     yielded[b][t] (int32 [B][32]) bits: bit 0 (1): F > H.  bit 2 (4): J > H, the prefix is longer than the ceiling and the <eos>
+ *              follows the prefix.  bit 3 (8): room flag set, 0 < J < L and the prefix's last forced pitch p (0..127) has
+ *              p + 1 >= 128 - (L - 1 - J): the floor may fall short above that voice.
+ *   Unselected step: copied, yielded = 0.  Duration words are src_dur's (or -1) everywhere.
+ *   Without a floor (L = 0 everywhere) only plain forced <eos> words are written, which every decode kind honours; PTV_FORCE_NOT_EOS and
+ *   PTV_FORCE_BELOW are honoured ONLY by the constrained kind, and the room ceilings leave room only for notes that ascend.
+ *   EVERY element of force_pitch [15][32B], force_dur [5][480B] and yielded is written, by one thread each.  A NULL pointer (but the src
+ *   pair), one of the pair alone, an output that is its source, flags outside 0..1, B < 1 or a row count outside {1, B}: PTV_ERR_ARG
+ *   before any launch. */
+int ptv_note_count_force_build(const unsigned char* lo, int lo_rows, const unsigned char* hi, int hi_rows, const unsigned char* steps,
+                               int steps_rows, const int* src_pitch, const int* src_dur, int flags, long B, int* force_pitch, int* force_dur,
+                               int* yielded, void* stream);
 /* the duration entries of the constrained step loop with force arrays: as the two below, and a word PTV_FORCE_DUR_RANGE of force / force_idx
  * limits the note.  ptv_dur_out_token_sample_cons: idx is plane d of the decisions, the planes of the bits before it lie idx_stride words
  * apart below it (idx - k * idx_stride, k = 1..d, written by the calls before).  idx and the force array must be given. */

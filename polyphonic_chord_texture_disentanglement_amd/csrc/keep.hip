@@ -4,8 +4,8 @@
 // -- (2), keeps its note count and durations (3: K decisions that are free but may not be <eos>, then a forced <eos>), or keeps its
 // highest notes -- a suffix -- (4: J decisions that are free, never <eos> and under a ceiling that leaves room for what follows, then the
 // kept pitches and a forced <eos>).  Every entry point accepts its own set of these bytes; ONE plan function states what each does to the
-// 15 decisions of a step, and the builder kernel, the split kernel and the err scan all read that plan.  The duration-range builder
-// reads the arrays of a keep, not a grid, and is a kernel of its own.  No atomics, no LDS, no workspace: every output element has one writer.
+// 15 decisions of a step, and the builder kernel, the split kernel and the err scan all read that plan.  The duration-range builder and
+// the note-count builder ("Note-count limits") read the arrays of a keep, not a grid, and are kernels of their own.  No atomics, no LDS, no workspace: every output element has one writer.
 #include "common.hpp"
 #include "philox.hpp"
 #include "../../include/ptvae_hip.h"
@@ -265,6 +265,54 @@ __global__ void dur_range_force_build_kernel(PerStep<unsigned char> lo, PerStep<
   yielded[b * 32 + t] = (sel && f > h) ? 1 : 0;
 }
 
+// ---- note-count limits: the pitch words of a step written from a floor and a ceiling in note counts instead of from a grid -- a forced
+// <eos> at the ceiling, PTV_FORCE_NOT_EOS (room, flags bit 0: PTV_FORCE_BELOW ceilings) under the floor -- alone or built INTO the arrays
+// of an existing keep (include/ptvae_hip.h "Note-count limits": the rule).  One thread per row r = t * B + b as above; the 15 source words
+// of the step are loaded once, and J, the owned test and E come from that one pass over registers
+__global__ void note_count_force_build_kernel(PerStep<unsigned char> lo, PerStep<unsigned char> hi, PerStep<unsigned char> steps,
+                                              const int* __restrict__ src_pitch, const int* __restrict__ src_dur, int flags, long B,
+                                              int* __restrict__ force_pitch, int* __restrict__ force_dur, int* __restrict__ yielded) {
+  const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long R = 32 * B, M = 15 * R;
+  if (r >= R) return;
+  const long t = r / B, b = r % B;
+  const bool sel = steps.at(b, t) != 0;
+  const int H = min((int)hi.at(b, t), 15), F = min((int)lo.at(b, t), 15);      // (bytes: never below 0)
+  const int L = min(F, H);                                                      // the ceiling wins
+  int w[15];
+#pragma unroll
+  for (int n = 0; n < 15; n++) w[n] = src_pitch ? src_pitch[n * R + r] : -1;
+  int J = 0;
+  long last = -1;                                  // the prefix's last forced pitch
+  bool owned = false;
+#pragma unroll
+  for (int n = 0; n < 15; n++) {
+    owned = owned || w[n] == 129 || w[n] < -1;
+    if (w[n] >= 0) { J = n + 1; last = w[n]; }
+  }
+  const int E = max(H, J);
+  const bool act = sel && !owned;
+#pragma unroll
+  for (int n = 0; n < 15; n++) {
+    int v = w[n];
+    if (act && v == -1) {
+      if (n < L) v = (flags & 1) ? PTV_FORCE_BELOW(128 - (L - 1 - n)) : PTV_FORCE_NOT_EOS;
+      else if (n == E) v = 129;
+    }
+    force_pitch[n * R + r] = v;
+#pragma unroll
+    for (int d = 0; d < 5; d++) force_dur[d * M + n * R + r] = src_dur ? src_dur[d * M + n * R + r] : -1;
+  }
+  int y = 0;
+  if (sel && owned) y = 2;
+  else if (sel) {
+    if (F > H) y |= 1;
+    if (J > H) y |= 4;
+    if ((flags & 1) && J > 0 && J < L && last <= 127 && last + 1 >= 128 - (L - 1 - J)) y |= 8;
+  }
+  yielded[b * 32 + t] = y;
+}
+
 // test aid: the rule of a range word itself (dur_range_allowed / dur_range_bit, philox.hpp: the only statement of it) on caller-supplied triples
 __global__ void dur_range_debug_kernel(const int* __restrict__ words, const int* __restrict__ d, const int* __restrict__ prefix, long rows,
                                        unsigned char* __restrict__ out) {
@@ -352,6 +400,19 @@ extern "C" int ptv_dur_range_force_build(const unsigned char* lo, int lo_rows, c
   if ((src_pitch == nullptr) != (src_dur == nullptr) || src_pitch == force_pitch || src_dur == force_dur) return PTV_ERR_ARG;
   hipLaunchKernelGGL(dur_range_force_build_kernel, dim3(row_blocks(B)), dim3(256), 0, (hipStream_t)stream, l, h, s, src_pitch, src_dur, B,
                      force_pitch, force_dur, yielded);
+  PTV_CHECK_LAUNCH();
+  return PTV_OK;
+}
+
+extern "C" int ptv_note_count_force_build(const unsigned char* lo, int lo_rows, const unsigned char* hi, int hi_rows, const unsigned char* steps,
+                                          int steps_rows, const int* src_pitch, const int* src_dur, int flags, long B, int* force_pitch,
+                                          int* force_dur, int* yielded, void* stream) {
+  PerStep<unsigned char> l, h, s;
+  if (!lo || !hi || !steps || !force_pitch || !force_dur || !yielded || B < 1 || flags < 0 || flags > 1) return PTV_ERR_ARG;
+  if (!per_step(l, lo, lo_rows, B) || !per_step(h, hi, hi_rows, B) || !per_step(s, steps, steps_rows, B)) return PTV_ERR_ARG;
+  if ((src_pitch == nullptr) != (src_dur == nullptr) || src_pitch == force_pitch || src_dur == force_dur) return PTV_ERR_ARG;
+  hipLaunchKernelGGL(note_count_force_build_kernel, dim3(row_blocks(B)), dim3(256), 0, (hipStream_t)stream, l, h, s, src_pitch, src_dur,
+                     flags, B, force_pitch, force_dur, yielded);
   PTV_CHECK_LAUNCH();
   return PTV_OK;
 }

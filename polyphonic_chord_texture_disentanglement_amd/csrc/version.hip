@@ -22,6 +22,8 @@ extern "C" const char* ptv_arch(void) { return "gfx950"; }
 // still 7: the row-wise decode kind (ptv_note_token_sample_rows, ptv_dur_gru_fwd_sample_rows, ptv_dur_out_token_sample_rows, bit 26 of
 // ptv_free_note_loop's train word, PTV_DFF_D_SAMPLE_ROWS appended, the 80-byte block of ptv_decode_logprob) added; no existing entry
 // point changed its arguments, and the same host tests pin the number
+// still 7: ptv_note_count_force_build (csrc/keep.hip, "Note-count limits") added as the builders before it were -- a new entry point, no
+// existing one changed, the same host tests pin the number; the header hash moves with the declaration
 extern "C" int ptv_abi_version(void) { return 7; }
 #ifndef PTV_HEADER_HASH
 #define PTV_HEADER_HASH "unknown"

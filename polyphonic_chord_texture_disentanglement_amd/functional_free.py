@@ -472,10 +472,43 @@ class TopDurKeep(TopKeep, DurKeep):
     __slots__ = ()
 
 
-def _dur_keep_type(keep):
-    if isinstance(keep, DurKeep):
-        return type(keep)
-    return TopDurKeep if isinstance(keep, TopKeep) else RhythmDurKeep if isinstance(keep, RhythmKeep) else DurKeep
+class CountKeep(Keep):
+    """a Keep whose pitch array holds the floor words of note-count limits (ptv_note_count_force_build; INTEGRATION.md "Note-count
+    limits"): FORCE_NOT_EOS, or with room=True FORCE_BELOW ceilings -- then the class it comes back as also has needs_ascending.  The
+    same four fields, so it goes wherever a Keep goes; only the constrained kernels honour the words.  (Limits without a floor write
+    plain forced <eos> words and need no class of their own.)"""
+    __slots__ = ()
+    needs_constrained = True
+
+
+_COMPOSED_KEEPS = {}
+
+
+def _limits_keep_type(keep, added, ascending=False):
+    """the class of the keep that results from building limits into `keep` (None: into nothing).  added: DurKeep, CountKeep, or None for
+    limits that write no word of their own kind (a ceiling-only count limit); ascending: the limits' words count on ascending notes.
+    The result demands the union of what both demand (needs_constrained / needs_ascending).  A keep that already is of the added kind
+    stays what it is, the pairs that have a name keep it (RhythmDurKeep, TopDurKeep), and every other pair is ONE composed class made
+    here on first use -- there is no class per combination to maintain."""
+    have = Keep if keep is None else type(keep)
+    if added is None or issubclass(have, added):
+        cls = have
+    elif have is Keep:
+        cls = added
+    elif added is DurKeep and have in (TopKeep, RhythmKeep):
+        cls = TopDurKeep if have is TopKeep else RhythmDurKeep
+    else:
+        cls = (have, added)
+    if isinstance(cls, tuple) or (ascending and not cls.needs_ascending):
+        bases = cls if isinstance(cls, tuple) else (cls,)
+        key = bases + (bool(ascending),)
+        if key not in _COMPOSED_KEEPS:
+            name = ''.join(b.__name__[:-4] for b in bases) + ('Ascending' if ascending and not any(b.needs_ascending for b in bases) else '')
+            _COMPOSED_KEEPS[key] = type(name + 'Keep', bases, {
+                '__slots__': (), '__doc__': 'limits built into a keep: the demands of %s' % ' and '.join(b.__name__ for b in bases),
+                'needs_constrained': True, 'needs_ascending': bool(ascending) or any(b.needs_ascending for b in bases)})
+        cls = _COMPOSED_KEEPS[key]
+    return cls
 
 
 def dur_fit_row(fit):
@@ -558,7 +591,100 @@ def build_dur_limits(device, min_dur=None, max_dur=None, fit=None, steps=None, b
     call('ptv_dur_range_force_build', ptr(lo), lo.shape[0], ptr(hi), hi.shape[0], ptr(sel), sel.shape[0], ptr(src[0]), ptr(src[1]), B,
          ptr(pitch), ptr(dur), ptr(yielded), stream_ptr())
     err = err.zero_() if keep is None else keep.err          # (this builder reports nothing: the err of the keep it built into)
-    out = _dur_keep_type(keep)(pitch, dur, err, B)
+    out = _limits_keep_type(keep, DurKeep)(pitch, dur, err, B)
+    return (out, yielded) if return_counts else out
+
+
+def build_count_limits(device, min_count=None, max_count=None, onsets=None, rests=None, steps=None, room=False, batch=None, keep=None,
+                       return_counts=False):
+    """note-count limits of a free-running decode -> keep (ptv_note_count_force_build; INTEGRATION.md "Note-count limits"): a selected
+    step gets at least `min_count` and at most `max_count` notes (the ceiling wins).  min_count / max_count: a host int 0..15 or an
+    integer device tensor [32] / [B, 32] (clamped into 0..15).  steps: as build_keep's, None = all 32.  onsets / rests: selections too,
+    selected whatever `steps` says -- onsets: a floor of at least 1, rests: the ceiling 0; a step in both is a rest.  At least one of
+    the four is needed.  room=True: the floor words are FORCE_BELOW ceilings that leave a semitone for each note still owed, which
+    under `ascending` guarantees the floor (without it a floor is "not <eos> while anything else is allowed" and can fall short under
+    a narrow mask or `ascending`).  keep: an existing keep to build into -- its words survive bit for bit, a step whose count it
+    already fixes is left alone.  The result: without a floor (min_count and onsets both None) only forced <eos> words are written
+    and the type of `keep` stays (a plain Keep without one); with a floor a CountKeep (needs_constrained), with room=True one that
+    needs_ascending too; built into another keep, the union of both keeps' demands (_limits_keep_type).  batch: B, needed when neither
+    keep nor a [B, 32] tensor tells it.  return_counts: -> (keep, yielded int32 [B, 32]: bit 0 the floor lay over the ceiling, bit 1
+    the keep owns the step's count, bit 2 a kept prefix is longer than the ceiling, bit 3 the room above a kept prefix may not hold the
+    floor).  ValueError before any launch; nothing is copied to the host."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise ValueError('note-count limits are built on the device, got %s' % (dev,))
+    if keep is not None:
+        check_keep(keep)
+        dev = keep.pitch.device
+    if batch is not None and (isinstance(batch, bool) or not isinstance(batch, int) or batch < 1):
+        raise ValueError('batch must be an integer >= 1, got %r' % (batch,))
+    if not isinstance(room, bool):
+        raise ValueError('room must be a bool, got %r' % (room,))
+    sizes = set() if batch is None else {batch}
+    if keep is not None:
+        sizes.add(keep.batch)
+    for name, v in (('min_count', min_count), ('max_count', max_count)):
+        if v is None:
+            continue
+        if torch.is_tensor(v):
+            if v.device.type != 'cuda' or (keep is not None and v.device != dev):
+                raise ValueError('%s must be a device tensor (on the device of keep), got one on %s' % (name, v.device))
+            if v.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError('%s must be an integer tensor, got %s' % (name, v.dtype))
+            if not ((v.dim() == 1 and v.shape[0] == 32) or (v.dim() == 2 and v.shape[1] == 32 and v.shape[0] >= 1)):
+                raise ValueError('%s must have shape [32] or [B, 32], got %s' % (name, tuple(v.shape)))
+            if v.dim() == 2 and v.shape[0] > 1:
+                sizes.add(v.shape[0])
+        elif isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 15:
+            raise ValueError('%s must be an integer in 0..15 or an integer device tensor [32] / [B, 32], got %r' % (name, v))
+    sels = {}
+    for name, s in (('steps', steps), ('onsets', onsets), ('rests', rests)):
+        s = s if s is None or torch.is_tensor(s) else keep_steps_row(s)
+        if torch.is_tensor(s):
+            if s.device.type != 'cuda' or (keep is not None and s.device != dev):
+                raise ValueError('%s must be on the device (or a host iterable of step indices / a slice)' % name)
+            if s.dtype not in (torch.bool, torch.uint8):
+                raise ValueError('%s must be bool or uint8, got %s' % (name, s.dtype))
+            if s.dim() != 2 or s.shape[1] != 32 or s.shape[0] < 1:
+                raise ValueError('%s must have shape [B, 32] or [1, 32], got %s' % (name, tuple(s.shape)))
+            if s.shape[0] > 1:
+                sizes.add(s.shape[0])
+        sels[name] = s
+    if min_count is None and max_count is None and onsets is None and rests is None:
+        raise ValueError('note-count limits need min_count, max_count, onsets or rests')
+    if len(sizes) > 1:
+        raise ValueError('the batch sizes of keep, batch, min_count, max_count, steps, onsets and rests disagree: %s' % (sorted(sizes),))
+    if not sizes:
+        raise ValueError('batch is needed: neither a keep nor a [B, 32] tensor tells the number of samples')
+    B = sizes.pop()
+    # ---- nothing below raises
+    def rows(v, fill):
+        if torch.is_tensor(v):
+            return v.to(dev).reshape(-1, 32).clamp(0, 255).to(torch.uint8)
+        return torch.full((1, 32), fill if v is None else v, dtype=torch.uint8, device=dev)
+
+    def selection(s):                                          # -> bool [rows, 32]
+        if torch.is_tensor(s):
+            return s.to(dev) != 0
+        return torch.frombuffer(bytearray(s), dtype=torch.uint8).view(1, 32).to(dev) != 0
+    lo, hi = rows(min_count, 0), rows(max_count, 15)
+    sel = torch.ones(1, 32, dtype=torch.bool, device=dev) if sels['steps'] is None else selection(sels['steps'])
+    rest = None if sels['rests'] is None else selection(sels['rests'])
+    if sels['onsets'] is not None:                             # a floor of at least 1 -- but at a step that is a rest as well
+        on = selection(sels['onsets'])
+        sel = sel | on
+        lo = torch.where(on if rest is None else on & ~rest, lo.clamp(min=1), lo)
+    if rest is not None:
+        sel = sel | rest
+        hi = torch.where(rest, torch.zeros_like(hi[:1, :1]), hi)
+    lo, hi, sel = lo.contiguous(), hi.contiguous(), sel.to(torch.uint8).contiguous()
+    pitch, dur, err, yielded = _force_outputs(B, dev)
+    src = (None, None) if keep is None else (keep.pitch.contiguous(), keep.dur.contiguous())
+    call('ptv_note_count_force_build', ptr(lo), lo.shape[0], ptr(hi), hi.shape[0], ptr(sel), sel.shape[0], ptr(src[0]), ptr(src[1]),
+         1 if room else 0, B, ptr(pitch), ptr(dur), ptr(yielded), stream_ptr())
+    err = err.zero_() if keep is None else keep.err          # (this builder reports nothing: the err of the keep it built into)
+    floor = min_count is not None or onsets is not None
+    out = _limits_keep_type(keep, CountKeep if floor else None, floor and room)(pitch, dur, err, B)
     return (out, yielded) if return_counts else out
 
 

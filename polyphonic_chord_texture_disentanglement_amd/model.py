@@ -13,7 +13,7 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import (RowSampling, build_chord_keep, build_dur_limits, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice,
+from .functional_free import (RowSampling, build_chord_keep, build_count_limits, build_dur_limits, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice,
                               check_chord_keep, check_chord_sampling, check_constraints, check_keep, check_rows, check_sampling, make_block,
                               row_sampling_words, sampling_words, split_top, split_voice)
 from .optim import refresh_weight_shadows
@@ -444,7 +444,8 @@ class DisentangleVAE(PytorchModel):
         a sampled decode that names no draw takes the model's counter and advances it.  A rhythm keep promotes the decode to the constrained
         kind, whose kernels alone honour its words: an `ascending` nobody gave becomes False, the vacuous constraint (flags 0, no mask).  A
         top keep does the same with True: its ceilings count on notes that ascend (_request has refused ascending=False).  A keep with
-        duration limits (DurKeep) is promoted like a rhythm keep; built into a top keep it stays a top keep"""
+        duration limits (DurKeep) is promoted like a rhythm keep; built into a top keep it stays a top keep.  Note-count limits with a
+        floor (CountKeep) are promoted like a rhythm keep, with room=True like a top keep; without a floor they promote nothing"""
         kw = req.kw
         ascending = kw['ascending']
         if ascending is None and req.keep is not None and req.keep.needs_constrained:
@@ -556,6 +557,26 @@ class DisentangleVAE(PytorchModel):
         the 32 durations renormalised.  A decode with such a keep always runs the constrained kernels.  return_counts=True: -> (keep,
         yielded int32 [B, 32]: 1 where a selected step's floor yielded).  ValueError before any launch; nothing is copied to the host."""
         return build_dur_limits(self.device, min_dur, max_dur, fit, steps, batch, keep, return_counts)
+
+    def count_limits(self, min_count=None, max_count=None, onsets=None, rests=None, steps=None, room=False, batch=None, keep=None,
+                     return_counts=False):
+        """Note-count limits of a decode -> a keep for keep= (ptv_note_count_force_build; INTEGRATION.md "Note-count limits"): how many
+        notes sound at a time step, with no grid to copy the count from.  At the selected steps (steps: as keep()'s, default all 32) a
+        step gets at least min_count and at most max_count notes; each an int 0..15 or an integer device tensor [32] / [B, 32].  The
+        ceiling wins where the floor lies above it; max_count=0 is a rest, 15 no ceiling.  onsets / rests: selections that are selected
+        whatever `steps` says -- a floor of at least 1 / the ceiling 0; a step in both is a rest, so count_limits(onsets=pattern,
+        rests=~pattern) is "notes exactly on this pattern".  At least one of the four is needed.  A floor is "not <eos> while anything
+        else is allowed": under a narrow pitch_mask or `ascending` the step can run out of pitches and fall short -- count the notes.
+        room=True writes ceilings that leave a semitone for every note still owed instead: the decode then runs with ascending=True
+        (ascending=False is a ValueError) and always reaches the floor; a mask yields before the count does.  keep: an existing keep to
+        build into; its words survive bit for bit, a step whose count it fixes already (whole, rhythm, top steps) is left alone, and the
+        result demands what both demand.  Without a floor the result is a plain Keep (or stays what `keep` is) and every decode kind
+        takes it unchanged; with one it is a functional_free.CountKeep and the decode always runs the constrained kernels.  batch: the
+        number of samples, needed when neither `keep` nor a [B, 32] tensor tells it.  return_counts=True: -> (keep, yielded int32
+        [B, 32]: bit 0 the floor yielded to the ceiling, bit 1 the keep owns the step, bit 2 a kept voice is longer than the ceiling,
+        bit 3 the room over a kept voice may not hold the floor).  decode_to_inputs(max_notes=) is the capacity of the note list the
+        output path writes, not a limit on the decode: this is.  ValueError before any launch; nothing is copied to the host."""
+        return build_count_limits(self.device, min_count, max_count, onsets, rests, steps, room, batch, keep, return_counts)
 
     def split_top(self, x, top_steps, above=None, highest=None, whole_steps=None):
         """The selection of keep_top as two grids -> (x_top, x_rest, kept_n, err) (ptv_grid_split_top), the mirror of split_voice: x_top

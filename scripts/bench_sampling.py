@@ -18,6 +18,9 @@ it, and reported beside `ascending` -- and under mask + ascending + top_k + top_
 The limits rows (duration limits, DisentangleVAE.dur_limits: every step fit to the bar with a floor of two sixteenths, every decision
 free inside its range) run under plain sampling -- sent as the constrained kind with the vacuous constraint, like the rhythm row, and to
 be read beside it -- and under mask + ascending + top_k + top_p, beside the same setting without a keep and beside the rhythm row.
+The count rows (note-count limits, DisentangleVAE.count_limits: every step gets at least two and at most four notes -- two floor words
+and one forced <eos> per step) run under plain sampling, sent as the constrained kind with the vacuous constraint like the rhythm row and
+to be read beside it, and under mask + ascending + top_k + top_p, beside the same setting without a keep and beside the rhythm row.
 The logprob rows (--logprob 1; PtvaeDecoder.decode_logprob, DisentangleVAE.decode_best_of) time the log-probability pass ALONE -- the two
 launches after a plain sampled decode, and after the mask + ascending + top_k + top_p decode, where every row also runs the allowed rule
 and both 32-round selects -- and decode_best_of(n=4) at a quarter of the batch (as many decoded rows as one plain decode of the batch).
@@ -103,6 +106,9 @@ def main():
         keeps['dur limits'] = ('sampled', m.dur_limits(min_dur=2, fit='bar', batch=a.batch))
         if a.constrained:
             keeps['dur limits+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.dur_limits(min_dur=2, fit='bar', batch=a.batch))
+        keeps['count limits'] = ('sampled', m.count_limits(min_count=2, max_count=4, batch=a.batch))
+        if a.constrained:
+            keeps['count limits+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p', m.count_limits(min_count=2, max_count=4, batch=a.batch))
     kinds += list(keeps)
     rowwise = {}                                             # kind -> (the kinds it is compared with, its RowSampling)
     if a.rows:
@@ -132,6 +138,8 @@ def main():
         blocks['keep rhythm'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=False) for d in range(a.rounds + 1)]
     if 'dur limits' in keeps:                                # ... and so do duration limits
         blocks['dur limits'] = blocks['keep rhythm']
+    if 'count limits' in keeps:                              # ... and a floor of note-count limits
+        blocks['count limits'] = blocks['keep rhythm']
     if 'keep top' in keeps:                                  # a top keep needs the constrained kind with the ascending flag
         blocks['keep top'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=True) for d in range(a.rounds + 1)]
 
@@ -171,6 +179,9 @@ def main():
     for k, (base, _) in keeps.items():
         out[k + '_over_' + base + '_best'] = round(best[k] / best[base], 4)
         out[k + '_over_' + base + '_by_round'] = [round(x / y, 4) for x, y in zip(rate[k], rate[base])]
+    for k, other in (('count limits', 'keep rhythm'), ('count limits+mask+ascending+top_k+top_p', 'keep rhythm+mask+ascending+top_k+top_p')):
+        if k in keeps and other in keeps:                    # the count limits beside the keep they are made like, round by round
+            out[k + '_over_' + other + '_by_round'] = [round(x / y, 4) for x, y in zip(rate[k], rate[other])]
     for k, (bases, _) in rowwise.items():
         for base in bases:
             out[k + '_over_' + base + '_best'] = round(best[k] / best[base], 4)
