@@ -949,6 +949,83 @@ enum PtvCdsDim { PTV_CDS_D_B = 0, PTV_CDS_D_H, PTV_CDS_D_Z, PTV_CDS_D_ZI, PTV_CD
 int ptv_chord_decode(const void* const* tensors, const long* dims, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Chord grammar (csrc/chord_decode.hip; DESIGN.md 7f, INTEGRATION.md "Chord grammar"): the chord step above under a rule -- which roots and
+ * pitch classes are allowed, a vocabulary of chord qualities in place of twelve independent bits, a chord-tone bass.
+ * rule int32 [rule_rows][8], rule_rows = B or 1 (one row serves every sample); the word of (row b, step t):
+ *   bits 0..11   root mask: bit r set = root r allowed
+ *   bits 12..23  chroma mask: bit 12 + p set = absolute pitch class p may be set in the chroma
+ *   bit 24       PTV_CHORD_RULE_VOCAB: the chroma is ONE draw from the vocabulary instead of twelve bit draws (ignored when n_vocab = 0)
+ *   bit 25       PTV_CHORD_RULE_ROOT_IN_CHORD: the chroma bit of the decided root is 1 (a vocabulary implies it: every template holds 0)
+ *   bit 26       PTV_CHORD_RULE_BASS_IN_CHORD: bass interval i is allowed iff the decided chroma holds pitch class (root + i) % 12
+ *   bits 27..31  0 (the kernel ignores them)
+ *   PTV_CHORD_RULE_IDENTITY = 0x00ffffff with n_vocab = 0: every output of ptv_chord_decide, bit for bit.
+ * vocab int32 [n_vocab], 0 <= n_vocab <= 64: root-relative 12-bit templates, bit i = interval i above the root is in the chord (the
+ *   caller keeps bit 0 set, the value inside 12 bits and the templates distinct).
+ * The decisions of (b, t), every set judged on the plain logits:
+ *   a kept step (keep_c / keep_steps) is ptv_chord_decide's: the rule is not consulted, error bit 0 as there.
+ *   root: the first maximal index over the allowed roots of logit + T_chord * gumbel (word 0 of sub = j, as ptv_chord_decide).  No root
+ *     allowed: all twelve are, and PTV_CHORD_ERR_ROOT_MASK is set.  logq = log softmax(logits / T_chord) over the allowed roots (one
+ *     allowed root: exactly 0); logp stays the model's log softmax over all twelve, here and below.
+ *   chroma without a vocabulary: bit p is free iff mask bit p is set, else 0; under ROOT_IN_CHORD bit r is 1 whatever the mask says.
+ *     Free bits are decided as by ptv_chord_decide (words 2 / 3 of sub = p); logq adds the free bits in ascending order, forced bits 0.
+ *   chroma with a vocabulary: template v stands for A_v = its bits rotated up by r (mod 12); it is allowed iff A_v lies inside the chroma
+ *     mask united with {r}.  None allowed: all n_vocab are (the vocabulary wins, the mask yields) and PTV_CHORD_ERR_NO_TEMPLATE is set.
+ *     Score s_v = the sum over p = 0..11 ascending of (p in A_v ? e1[p] : e0[p]), fp32 from 0: softmax(s / T_chroma) over the allowed
+ *     templates is the model's bit-product distribution conditioned on them.  The decision is the first maximal allowed v of
+ *     s_v + T_chroma * gumbel(word v >> 4 of the Philox call at n = 15, kind 0, sub = 16 + (v & 15)); the step's bits are A_v.
+ *     logq = s_v / T - log sum over the allowed u of exp(s_u / T) (0 at T_chroma = 0): a lane adds its templates j, j + 16, j + 32,
+ *     j + 48 in that order, a disallowed one as 0, then the 16-lane rotation tree.
+ *   bass under BASS_IN_CHORD: over the intervals i whose pitch class (r + i) % 12 is a decided bit, decision and logq as the root's with
+ *     word 1.  All twelve bits 0: all twelve intervals, and PTV_CHORD_ERR_NO_BASS is set.
+ * step_forced counts the decisions a keep forced, as before; the error bits are ORed into step_err / err.
+ * ptv_chord_decide_grammar: PTV_ERR_ARG (nothing launched) in the cases of ptv_chord_decide and for rule = NULL, rule_rows other than 1
+ *   or B, n_vocab outside 0..64, n_vocab > 0 with vocab = NULL.
+ * ptv_chord_decode_grammar: ptv_chord_decode with the decide launch replaced -- the same launches in the same order.  Its tables repeat
+ *   PTV_CDS_* slot for slot and add RULE (required), VOCAB (NULL with N_VOCAB = 0) and the dimensions RULE_ROWS, N_VOCAB.
+ */
+#define PTV_CHORD_RULE_VOCAB (1 << 24)
+#define PTV_CHORD_RULE_ROOT_IN_CHORD (1 << 25)
+#define PTV_CHORD_RULE_BASS_IN_CHORD (1 << 26)
+#define PTV_CHORD_RULE_IDENTITY 0x00ffffff
+#define PTV_CHORD_ERR_KEEP 1        /* a kept root / bass block without exactly one non-zero entry (ptv_chord_decide's bit) */
+#define PTV_CHORD_ERR_ROOT_MASK 2   /* no root allowed: all twelve were */
+#define PTV_CHORD_ERR_NO_TEMPLATE 4 /* no template inside the chroma mask: all of them were allowed */
+#define PTV_CHORD_ERR_NO_BASS 8     /* no chroma bit under BASS_IN_CHORD: all twelve intervals were allowed */
+int ptv_chord_decide_grammar(const float* root, const float* chroma, const float* bass, int B, int t, const void* sample,
+                             const float* keep_c, const unsigned char* keep_steps, int keep_rows, const int* rule, int rule_rows,
+                             const int* vocab, int n_vocab, float* tok, float* c, float* chord14, float* step_logp, float* step_logq,
+                             int* step_forced, int* step_err, void* stream);
+enum PtvCdgTensor {
+  PTV_CDG_Z = 0,
+  PTV_CDG_W_ZHID, PTV_CDG_B_ZHID, PTV_CDG_W_ZIN, PTV_CDG_B_ZIN, PTV_CDG_INIT_INPUT,
+  PTV_CDG_W_IH,
+  PTV_CDG_B_IH, PTV_CDG_W_HH, PTV_CDG_B_HH, PTV_CDG_W_ROOT, PTV_CDG_B_ROOT, PTV_CDG_W_CHROMA, PTV_CDG_B_CHROMA, PTV_CDG_W_BASS, PTV_CDG_B_BASS,
+  PTV_CDG_SAMPLE,
+  PTV_CDG_KEEP_C,
+  PTV_CDG_KEEP_STEPS,
+  PTV_CDG_HALL,
+  PTV_CDG_Z_IN,
+  PTV_CDG_ZG,
+  PTV_CDG_GI,
+  PTV_CDG_TOK,
+  PTV_CDG_ROOT, PTV_CDG_CHROMA, PTV_CDG_BASS,
+  PTV_CDG_C,
+  PTV_CDG_CHORD14,
+  PTV_CDG_STEP_LOGP, PTV_CDG_STEP_LOGQ,
+  PTV_CDG_STEP_FORCED,
+  PTV_CDG_STEP_ERR,
+  PTV_CDG_LOGP, PTV_CDG_LOGQ,
+  PTV_CDG_FORCED,
+  PTV_CDG_ERR,            /* ... every slot above as its PTV_CDS_ namesake */
+  PTV_CDG_RULE,           /* int32 [RULE_ROWS, 8] */
+  PTV_CDG_VOCAB,          /* int32 [N_VOCAB], or NULL with N_VOCAB = 0 */
+  PTV_CDG_COUNT
+};
+enum PtvCdgDim { PTV_CDG_D_B = 0, PTV_CDG_D_H, PTV_CDG_D_Z, PTV_CDG_D_ZI, PTV_CDG_D_PREC, PTV_CDG_D_KEEP_ROWS, PTV_CDG_D_RULE_ROWS,
+                 PTV_CDG_D_N_VOCAB, PTV_CDG_D_COUNT };
+int ptv_chord_decode_grammar(const void* const* tensors, const long* dims, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Note-matrix song bank on device (csrc/dataset.hip): what ArrangementDataset.__getitem__ does BEFORE the data contract above, from
  * the per-bar note matrices (dataset.py:67-93 over converter.py:35-76), and detrend_pianotree (dataset.py:123-213) after it.
  * Bank: the bars of all songs in order.  acc_rec / mel_rec hold one 32-bit record per note, bar after bar, acc_off / mel_off [n_bar+1]

@@ -94,6 +94,10 @@ int ptv_debug_dur_range(const int* words, const int* d, const int* prefix, long 
  * [0, rows) -- samples sample_offset + row of the 32-byte block -- at chord step t, through the device function that kernel calls:
  * out [rows, 12, 4], lane j's four values in word order (root class j, bass class j, class 0 and class 1 of chroma bit j) */
 int ptv_debug_chord_noise(const void* block, long rows, int t, float* out, void* stream);
+/* ... and of the chord grammar's vocabulary draw (ptvae_hip.h "Chord grammar"), through the device function ptv_chord_decide_grammar
+ * calls: out f32 [rows, n_vocab], the Gumbel value of template v, and words uint32 [rows, n_vocab], the Philox word it was made from
+ * (word v >> 4 of the call sub = 16 + (v & 15)); n_vocab in 1..64 */
+int ptv_debug_chord_vocab_noise(const void* block, long rows, int t, int n_vocab, float* out, unsigned* words, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,8 @@ extern "C" const char* ptv_arch(void) { return "gfx950"; }
 // point changed its arguments, and the same host tests pin the number
 // still 7: ptv_note_count_force_build (csrc/keep.hip, "Note-count limits") added as the builders before it were -- a new entry point, no
 // existing one changed, the same host tests pin the number; the header hash moves with the declaration
+// still 7: the chord grammar (csrc/chord_decode.hip: ptv_chord_decide_grammar, ptv_chord_decode_grammar and its PTV_CDG_* tables) added;
+// no existing entry point changed, the same host tests pin the number
 extern "C" int ptv_abi_version(void) { return 7; }
 #ifndef PTV_HEADER_HASH
 #define PTV_HEADER_HASH "unknown"

@@ -1919,11 +1919,135 @@ def check_chord_sampling(temperature=None, chroma_temperature=None, seed=None, d
     return True
 
 
-def chord_decode(z, P, prec, sampling=None, keep=None):
+# ---- the chord grammar (include/ptvae_hip.h "Chord grammar"; INTEGRATION.md "Chord grammar"): a rule word per row and chord step, a
+# vocabulary of chord qualities
+_CDG = SlotTable('CDG')
+CHORD_RULE_VOCAB, CHORD_RULE_ROOT_IN_CHORD, CHORD_RULE_BASS_IN_CHORD = 1 << 24, 1 << 25, 1 << 26
+CHORD_RULE_IDENTITY = 0x00ffffff
+CHORD_ERR_KEEP, CHORD_ERR_ROOT_MASK, CHORD_ERR_NO_TEMPLATE, CHORD_ERR_NO_BASS = 1, 2, 4, 8
+CHORD_MAX_VOCAB = 64
+CHORD_SCALES = {'major': 0xab5, 'minor': 0x5ad, 'harmonic_minor': 0x9ad}       # degrees 0 2 4 5 7 9 11 / 0 2 3 5 7 8 10 / 0 2 3 5 7 8 11
+_TRIADS = ((0, 4, 7), (0, 3, 7), (0, 3, 6), (0, 4, 8))                             # maj, min, dim, aug
+_SEVENTHS = _TRIADS + ((0, 4, 7, 11), (0, 4, 7, 10), (0, 3, 7, 10), (0, 3, 6, 10), (0, 3, 6, 9), (0, 3, 7, 11))   # maj7 7 m7 m7b5 dim7 mMaj7
+CHORD_QUALITIES = {'triads': _TRIADS, 'sevenths': _SEVENTHS}
+
+
+class ChordGrammar(collections.namedtuple('ChordGrammar', 'rule vocab batch')):
+    """the grammar of a chord decode: rule int32 [R, 8] (R = batch or 1: one row serves every sample) and vocab int32 [V], V <= 64, on one
+    device; batch = R"""
+    __slots__ = ()
+
+
+def pitch_class_set(value, what):
+    """a 12-bit set, or an iterable of integers 0..11 -> the set as an int; ValueError for anything else"""
+    if isinstance(value, bool):
+        raise ValueError('%s must be a 12-bit set or an iterable of integers 0..11, got %r' % (what, value))
+    if isinstance(value, int):
+        if not 0 <= value <= 0xfff:
+            raise ValueError('%s must be a 12-bit set, got %r' % (what, value))
+        return value
+    try:
+        items = list(value)
+    except TypeError:
+        raise ValueError('%s must be a 12-bit set or an iterable of integers 0..11, got %r' % (what, value)) from None
+    k = 0
+    for q in items:
+        if isinstance(q, bool) or not isinstance(q, int) or not 0 <= q < 12:
+            raise ValueError('%s: an entry must be an integer in 0..11, got %r' % (what, q))
+        k |= 1 << q
+    return k
+
+
+def chord_vocabulary(qualities):
+    """None / 'triads' / 'sevenths' / an iterable of 12-bit ints or interval tuples -> the list of root-relative templates (ints); every
+    template holds interval 0, fits 12 bits and is distinct from the others; at most 64.  ValueError otherwise."""
+    if qualities is None:
+        return []
+    if isinstance(qualities, str):
+        if qualities not in CHORD_QUALITIES:
+            raise ValueError("qualities must be 'triads', 'sevenths' or an iterable of templates, got %r" % (qualities,))
+        qualities = CHORD_QUALITIES[qualities]
+    try:
+        items = list(qualities)
+    except TypeError:
+        raise ValueError("qualities must be 'triads', 'sevenths' or an iterable of templates, got %r" % (qualities,)) from None
+    out = [pitch_class_set(q, 'a chord quality') for q in items]
+    if not out:
+        raise ValueError('qualities names no chord: a vocabulary needs at least one template (None = no vocabulary)')
+    if len(out) > CHORD_MAX_VOCAB:
+        raise ValueError('a vocabulary holds at most %d templates, got %d' % (CHORD_MAX_VOCAB, len(out)))
+    for q in out:
+        if not q & 1:
+            raise ValueError('a chord quality must hold interval 0 (its root), got 0x%03x' % q)
+    if len(set(out)) != len(out):
+        raise ValueError('the chord qualities must be distinct')
+    return out
+
+
+def _rot12(x, r):
+    """the 12-bit sets x (int tensor or int) moved up by r (int tensor): interval i -> pitch class (r + i) % 12"""
+    return ((x << r) | (x >> (12 - r))) & 0xfff
+
+
+def build_chord_grammar(device, key=None, scale=0xab5, roots=None, pitch_classes=None, vocab=(), root_in_chord=False, bass_in_chord=False,
+                        steps=None, batch=None):
+    """checked host values (DisentangleVAE.chord_grammar judges them) -> ChordGrammar on `device`, built with torch operations there: nothing
+    is copied back and no element is visited on the host.  key: None, an int 0..11 or an int tensor [B] / [B, 8] on the device (its values
+    are taken modulo 12: they are never read on the host, so there is nothing to refuse); scale /
+    roots / pitch_classes: 12-bit sets (roots None: the scale; both relative to the key); vocab: a list of templates; steps: None, 8 host
+    bytes (chord_keep_steps_row) or a device bool / uint8 tensor [B, 8] / [1, 8]: the other steps get the identity word."""
+    R = 1 if batch is None else batch
+    for t in (key, steps):
+        if torch.is_tensor(t) and t.shape[0] != 1:
+            R = t.shape[0]
+    flags = (CHORD_RULE_VOCAB if vocab else 0) | (CHORD_RULE_ROOT_IN_CHORD if root_in_chord else 0) | \
+        (CHORD_RULE_BASS_IN_CHORD if bass_in_chord else 0)
+    i64 = dict(dtype=torch.int64, device=device)
+    if key is None:
+        k = torch.zeros(1, 1, **i64)
+    elif torch.is_tensor(key):
+        k = key.to(torch.int64).remainder(12)
+        k = k.view(-1, 1) if k.dim() == 1 else k
+    else:
+        k = torch.full((1, 1), key, **i64)
+    rset = scale if roots is None else roots
+    word = _rot12(torch.full((1, 1), rset, **i64), k) | (_rot12(torch.full((1, 1), scale, **i64), k) << 12)
+    if pitch_classes is not None:
+        word = word & ((pitch_classes << 12) | 0xfff)
+    word = (word | flags).expand(R if word.shape[0] == 1 else word.shape[0], CHORD_STEPS)
+    if steps is not None:
+        if not torch.is_tensor(steps):
+            steps = torch.frombuffer(bytearray(steps), dtype=torch.uint8).view(1, CHORD_STEPS).to(device)
+        word = torch.where(steps != 0, word, torch.full((1, 1), CHORD_RULE_IDENTITY, **i64))
+    rule = word.to(torch.int32).contiguous()
+    return ChordGrammar(rule, torch.tensor(list(vocab), dtype=torch.int32, device=device), rule.shape[0])
+
+
+def check_chord_grammar(grammar, batch=None):
+    """ValueError unless grammar is None or a ChordGrammar whose arrays fit its batch (and `batch`, the rows of the decode, where known)"""
+    if grammar is None:
+        return
+    if not isinstance(grammar, ChordGrammar):
+        raise ValueError('a chord grammar must be what DisentangleVAE.chord_grammar(...) returns, got %r' % (type(grammar).__name__,))
+    rule, vocab, R = grammar
+    if (not torch.is_tensor(rule) or rule.dtype != torch.int32 or rule.dim() != 2 or rule.shape[1] != CHORD_STEPS or rule.shape[0] != R
+            or R < 1 or not rule.is_contiguous()):
+        raise ValueError('chord_grammar.rule must be a contiguous int32 tensor [%r, 8]' % (R,))
+    if (not torch.is_tensor(vocab) or vocab.dtype != torch.int32 or vocab.dim() != 1 or vocab.shape[0] > CHORD_MAX_VOCAB
+            or vocab.device != rule.device or not vocab.is_contiguous()):
+        raise ValueError('chord_grammar.vocab must be a contiguous int32 tensor [V], V <= %d, on the device of the rule' % CHORD_MAX_VOCAB)
+    if batch is not None and R not in (1, batch):
+        raise ValueError('the chord grammar was built for a batch of %d, the decoded batch has %d rows' % (R, batch))
+
+
+def chord_decode(z, P, prec, sampling=None, keep=None, grammar=None):
     """z f32 [B, Z] on the device, P {CHD_PARAM_NAMES: parameter} -> ChordDecode, through ptv_chord_decode (ONE C call: 53 launches).
     sampling: None (argmax) or the 32-byte sampling_block(device, T_chord, T_chroma, seed, draw, sample_offset); keep: None or a checked
-    ChordKeep of B rows.  No autograd, no synchronisation."""
+    ChordKeep of B rows; grammar: None or a checked ChordGrammar of B rows or one -- the call is then ptv_chord_decode_grammar (the same
+    launches with the decide launch replaced).  No autograd, no synchronisation."""
     dev = z.device
+    if grammar is not None and grammar.rule.device != dev:
+        raise ValueError('the chord grammar must be on the device of z (%s), it is on %s' % (dev, grammar.rule.device))
     z = z.detach().float().contiguous()
     B, Z = z.shape
     w_ih = P['gru.weight_ih_l0'].detach()
@@ -1948,7 +2072,14 @@ def chord_decode(z, P, prec, sampling=None, keep=None):
             raise ValueError('ptv_chord_decode takes contiguous float32 tensors (%s is %s)' % (k, v.dtype))
     dims = {'B': B, 'H': H, 'Z': Z, 'ZI': Zi, 'PREC': prec, 'KEEP_ROWS': 0 if keep is None else keep.steps.shape[0]}
     F_._chain_prio()
-    F_.check(lib().ptv_chord_decode(_CDS.pointers(tens, out), _CDS.dims(dims), stream_ptr()), 'ptv_chord_decode')
-    _CDS.count()
+    if grammar is None:
+        F_.check(lib().ptv_chord_decode(_CDS.pointers(tens, out), _CDS.dims(dims), stream_ptr()), 'ptv_chord_decode')
+        _CDS.count()
+    else:
+        n_vocab = grammar.vocab.shape[0]
+        tens.update(RULE=grammar.rule, VOCAB=grammar.vocab if n_vocab else None)
+        dims.update(RULE_ROWS=grammar.rule.shape[0], N_VOCAB=n_vocab)
+        F_.check(lib().ptv_chord_decode_grammar(_CDG.pointers(tens, out), _CDG.dims(dims), stream_ptr()), 'ptv_chord_decode_grammar')
+        _CDG.count()
     lp = ChordLogprob(out['LOGP'], out['LOGQ'], out['FORCED'], out['ERR'], out['STEP_LOGP'], out['STEP_LOGQ'], out['STEP_FORCED'])
     return ChordDecode(out['C'], out['CHORD14'], out['ROOT'], out['CHROMA'], out['BASS'], lp)

@@ -13,9 +13,10 @@ import torch
 from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
-from .functional_free import (RowSampling, build_chord_keep, build_count_limits, build_dur_limits, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice,
-                              check_chord_keep, check_chord_sampling, check_constraints, check_keep, check_rows, check_sampling, make_block,
-                              row_sampling_words, sampling_words, split_top, split_voice)
+from .functional_free import (CHORD_SCALES, CHORD_STEPS, RowSampling, build_chord_grammar, build_chord_keep, build_count_limits, build_dur_limits,
+                              build_keep, build_keep_rhythm, build_keep_top, build_keep_voice, check_chord_grammar, check_chord_keep,
+                              check_chord_sampling, check_constraints, check_keep, check_rows, check_sampling, chord_keep_steps_row,
+                              chord_vocabulary, make_block, pitch_class_set, row_sampling_words, sampling_words, split_top, split_voice)
 from .optim import refresh_weight_shadows
 from .ptvae import HipNormal, PtvaeDecoder, PtvaeEncoder, RnnDecoder, RnnEncoder, TextureEncoder, _require_cuda
 
@@ -61,7 +62,8 @@ class DecodeRequest(collections.namedtuple('DecodeRequest', 'sampled kw mask kee
         return self._replace(mask=mask, keep=keep, batch=n * B)
 
 
-class ChordRequest(collections.namedtuple('ChordRequest', 'sampled temperature chroma_temperature seed draw sample_offset keep')):
+class ChordRequest(collections.namedtuple('ChordRequest', 'sampled temperature chroma_temperature seed draw sample_offset keep grammar',
+                                          defaults=(None,))):
     """the validated keywords of one row-independent chord decode (DisentangleVAE._chord_request); seed / draw / sample_offset None = the
     model's (use_philox, the draw counter)"""
 
@@ -650,17 +652,24 @@ class DisentangleVAE(PytorchModel):
     # decode in which every row feeds back its own token: sharding-invariant like the note decode, sampled from the same Philox domain
     # (note step 15: a slot no note decision uses), with kept chords and log-probabilities.
     def _chord_request(self, batch, chord_temperature=None, chroma_temperature=None, keep_chords=None, seed=None, draw=None,
-                       sample_offset=None, note_sampled=False, required=False):
+                       sample_offset=None, note_sampled=False, required=False, grammar=None):
         """None when no chord keyword is given (the caller keeps decode_tokens), else the ChordRequest; every bad value is a ValueError
         here: no launch, no side effect.  note_sampled: the note decode of the same call is sampled (seed / draw / sample_offset then
         belong to it as well and are no error without a chord temperature); required: the caller runs the chord decode whatever is given"""
-        if chord_temperature is None and chroma_temperature is None and keep_chords is None and not required:
+        if chord_temperature is None and chroma_temperature is None and keep_chords is None and grammar is None and not required:
             return None
         given = (seed, draw, sample_offset)
         sampled = check_chord_sampling(chord_temperature, chroma_temperature, *((None, None, None) if note_sampled and chord_temperature is None
                                                                                  else given))
         check_chord_keep(keep_chords, batch)
-        return ChordRequest(sampled, chord_temperature, chroma_temperature, seed, draw, sample_offset, keep_chords)
+        check_chord_grammar(grammar, batch)
+        return ChordRequest(sampled, chord_temperature, chroma_temperature, seed, draw, sample_offset, keep_chords, grammar)
+
+    @staticmethod
+    def _check_grammar_device(creq, z_chd):
+        """ValueError, before anything is launched, for a grammar that lives on another device than the latents"""
+        if creq is not None and creq.grammar is not None and creq.grammar.rule.device != z_chd.device:
+            raise ValueError('the chord grammar must be on the device of z_chd (%s), it is on %s' % (z_chd.device, creq.grammar.rule.device))
 
     def _decode_chords(self, z_chd, creq, draw, return_logprob=False):
         """the chord decode of a ChordRequest; draw: the draw number a request that names none uses"""
@@ -668,7 +677,7 @@ class DisentangleVAE(PytorchModel):
         return self.chd_decoder.decode_chords(
             z_chd, temperature=creq.temperature, chroma_temperature=creq.chroma_temperature, seed=ph[0] if creq.seed is None else creq.seed,
             draw=draw if creq.draw is None else creq.draw, sample_offset=ph[1] if creq.sample_offset is None else creq.sample_offset,
-            keep=creq.keep, return_logprob=return_logprob)
+            keep=creq.keep, return_logprob=return_logprob, grammar=creq.grammar)
 
     def keep_chords(self, c, steps):
         """The kept chord steps of a chord decode -> functional_free.ChordKeep(c, steps, batch) for keep_chords= (INTEGRATION.md "Chord
@@ -679,16 +688,80 @@ class DisentangleVAE(PytorchModel):
         host."""
         return build_chord_keep(c, steps)
 
+    def chord_grammar(self, key=None, scale='major', roots=None, pitch_classes=None, qualities=None, root_in_chord=None, bass_in_chord=False,
+                      steps=None, batch=None):
+        """The grammar of a chord decode -> functional_free.ChordGrammar(rule int32 [R, 8], vocab int32 [V], batch) for grammar= /
+        chord_grammar= (INTEGRATION.md "Chord grammar"), built on the device; nothing is copied to the host.
+        key: None, an int 0..11, or an int device tensor [B] / [B, 8] (a key per row, or per row and chord step).  The values of a tensor
+        are not read on the host, so they cannot be refused: they are taken modulo 12 (-1 is B, 12 is C), where an int outside 0..11 is a
+        ValueError.
+        scale: 'major', 'minor' (natural), 'harmonic_minor', a 12-bit set or an iterable of degrees 0..11 above the key.  With a key the
+        scale on it is the chroma mask -- the pitch classes a chord may hold -- and the root mask, unless roots= (a 12-bit set or an
+        iterable, relative to the key; absolute without one) names another set.  Without a key the scale is not applied: every root and
+        pitch class is allowed but for roots / pitch_classes.  pitch_classes: an absolute chroma mask, ANDed with the key's.
+        qualities: None (the twelve chroma bits stay independent draws), 'triads' (maj, min, dim, aug), 'sevenths' (the triads, maj7, 7,
+        m7, m7b5, dim7, mMaj7), or an iterable of 12-bit sets / interval tuples that hold 0: the chroma becomes ONE draw from these chords
+        on the decided root, from the model's own distribution conditioned on them (at most 64).
+        root_in_chord (default: True with qualities, else False): the decided root's chroma bit is 1.  bass_in_chord: the bass is a tone
+        of the decided chord.  steps: the chord steps the rule applies to -- an iterable of 0..7, a slice, or a device bool / uint8 tensor
+        [B, 8] / [1, 8]; the others decode as without a grammar.  batch: the rows R of the rule when no tensor gives them (default 1: one
+        row serves every batch).  Every bad value is a ValueError before any device work."""
+        vocab = chord_vocabulary(qualities)
+        if isinstance(scale, str):
+            if scale not in CHORD_SCALES:
+                raise ValueError("scale must be one of %s, a 12-bit set or an iterable of degrees, got %r" % (sorted(CHORD_SCALES), scale))
+            scale_set = CHORD_SCALES[scale]
+        else:
+            scale_set = pitch_class_set(scale, 'scale')
+        roots_set = None if roots is None else pitch_class_set(roots, 'roots')
+        pcs = None if pitch_classes is None else pitch_class_set(pitch_classes, 'pitch_classes')
+        for name, v in (('root_in_chord', root_in_chord), ('bass_in_chord', bass_in_chord)):
+            if not isinstance(v, bool) and not (name == 'root_in_chord' and v is None):
+                raise ValueError('%s must be a bool, got %r' % (name, v))
+        if vocab and root_in_chord is False:
+            raise ValueError('root_in_chord=False contradicts qualities: every chord of a vocabulary holds its root')
+        if batch is not None and (isinstance(batch, bool) or not isinstance(batch, int) or batch < 1):
+            raise ValueError('batch must be an integer >= 1, got %r' % (batch,))
+        rows = batch
+        if torch.is_tensor(key):
+            if key.dtype not in (torch.int32, torch.int64) or key.dim() not in (1, 2) or key.shape[0] < 1 or \
+                    (key.dim() == 2 and key.shape[1] != CHORD_STEPS):
+                raise ValueError('key must be an int 0..11 or an int32 / int64 tensor [B] or [B, 8], got %s %s' % (key.dtype, tuple(key.shape)))
+            if rows is not None and key.shape[0] != rows:
+                raise ValueError('batch is %r, key has %d rows' % (batch, key.shape[0]))
+            rows = key.shape[0]
+        elif key is not None and (isinstance(key, bool) or not isinstance(key, int) or not 0 <= key < 12):
+            raise ValueError('key must be an int 0..11 or an int tensor [B] / [B, 8], got %r' % (key,))
+        dev = key.device if torch.is_tensor(key) else None
+        if torch.is_tensor(steps):
+            if steps.dtype not in (torch.bool, torch.uint8) or steps.dim() != 2 or steps.shape[1] != CHORD_STEPS or steps.shape[0] < 1:
+                raise ValueError('steps must be a bool / uint8 tensor [B, 8] or [1, 8], an iterable of step indices or a slice')
+            if rows is not None and steps.shape[0] not in (1, rows):
+                raise ValueError('steps has %d rows, the grammar %d' % (steps.shape[0], rows))
+            if dev is not None and steps.device != dev:
+                raise ValueError('steps must be on the device of key')
+            dev = steps.device
+        elif steps is not None:
+            steps = chord_keep_steps_row(steps)
+        if key is None:
+            scale_set = 0xfff                                # a scale stands on a key: without one only roots / pitch_classes restrict
+        return build_chord_grammar(self.device if dev is None else dev, key, scale_set, roots_set, pcs, vocab,
+                                   bool(vocab) if root_in_chord is None else root_in_chord, bass_in_chord, steps, batch)
+
     def decode_chords(self, z_chd, *, chord_temperature=None, chroma_temperature=None, seed=None, draw=None, sample_offset=None,
-                      keep_chords=None, return_logprob=False):
+                      keep_chords=None, return_logprob=False, grammar=None):
         """Row-independent free-running chord decode of z_chd -> (c f32 [B,8,36], chord14 f32 [B,8,14]), with return_logprob=True also a
         ChordLogprob (RnnDecoder.decode_chords).  seed / sample_offset default to use_philox()'s, else 7 / 0; draw defaults to the
         model's draw counter, which a sampled decode that names none advances.  Without a temperature: the argmax (of each row's own
-        trajectory).  Bad values are a ValueError before anything is launched and before the counter moves."""
+        trajectory).  grammar: what chord_grammar() returns -- allowed roots and pitch classes, a chord-quality vocabulary, a chord-tone
+        bass; a grammar alone is no sampled decode (the argmax snapped to the grammar; the counter stays).  Bad values are a ValueError
+        before anything is launched and before the counter moves."""
         if not torch.is_tensor(z_chd) or z_chd.dim() != 2:
             raise ValueError('z_chd must be a tensor [B, z_dim]')
-        creq = self._chord_request(z_chd.shape[0], chord_temperature, chroma_temperature, keep_chords, seed, draw, sample_offset, required=True)
+        creq = self._chord_request(z_chd.shape[0], chord_temperature, chroma_temperature, keep_chords, seed, draw, sample_offset, required=True,
+                                   grammar=grammar)
         _require_cuda(z_chd, 'DisentangleVAE.decode_chords')
+        self._check_grammar_device(creq, z_chd)
         self.eval()
         out = self._decode_chords(z_chd, creq, self._sample_draws, return_logprob)
         if creq.sampled and draw is None:
@@ -699,26 +772,29 @@ class DisentangleVAE(PytorchModel):
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
                          sample_offset=None, top_k=None, min_p=None, top_p=None, rows=None, pitch_mask=None, ascending=None, keep=None,
-                         return_logprob=False, chord_temperature=None, chroma_temperature=None, keep_chords=None):
+                         return_logprob=False, chord_temperature=None, chroma_temperature=None, keep_chords=None, chord_grammar=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as
         inference_decode's (they leave the chord decoder at its argmax).  return_logprob=True appends the decode's log-probabilities
         (PtvaeDecoder.decode_logprob: a DecodeLogprob of device tensors) as a seventh element.
-        chord_temperature / chroma_temperature / keep_chords (any of them given): c comes from the row-independent chord decode
+        chord_temperature / chroma_temperature / keep_chords / chord_grammar (any of them given): c comes from the row-independent chord decode
         (decode_chords above) instead of decode_tokens, and return_logprob appends its ChordLogprob as an eighth element.  One call is one
         draw: both decoders take seed / draw / sample_offset, and when no draw is named both use the counter's value and it advances
-        once.  With none of the three the call is what it was: the same launches, the same bits."""
+        once.  chord_grammar: what chord_grammar() returns (INTEGRATION.md "Chord grammar"); alone it is no sampled decode.  With none of
+        the four the call is what it was: the same launches, the same bits."""
         kw = locals()
         B = z_chd.shape[0]
         note_sampled = temperature is not None or dur_temperature is not None or rows is not None
-        creq = self._chord_request(B, chord_temperature, chroma_temperature, keep_chords, seed, draw, sample_offset, note_sampled)
+        creq = self._chord_request(B, chord_temperature, chroma_temperature, keep_chords, seed, draw, sample_offset, note_sampled,
+                                   grammar=chord_grammar)
         note_kw = {k: kw[k] for k in DECODE_KEYS}
         if creq is not None and creq.sampled and not note_sampled:
             note_kw.update(seed=None, draw=None, sample_offset=None)                # (they belong to the chord decode alone)
         req = self._request(B, **note_kw)                                           # (bad values are a ValueError whatever device the inputs are on)
         _require_cuda(z_chd, 'DisentangleVAE.decode_to_inputs')
         _require_cuda(z_rhy, 'DisentangleVAE.decode_to_inputs')
+        self._check_grammar_device(creq, z_chd)
         self.eval()
         refresh_weight_shadows()
         draw0 = self._sample_draws
@@ -742,7 +818,7 @@ class DisentangleVAE(PytorchModel):
         DecodeLogprob(logp [B,2], logq [B,2], counts [B,4], err [B], step_logp [B,32,4], step_counts [B,32,4]) of device tensors --
         log p under the model's own softmax and log q under the distribution the decode drew from, (pitch, duration) sums over the
         decisions taken.  **sampling: the keywords of a sampled decode (inference_decode); with chord_temperature / chroma_temperature /
-        keep_chords the ChordLogprob of the row-independent chord decode follows the DecodeLogprob."""
+        keep_chords / chord_grammar the ChordLogprob of the row-independent chord decode follows the DecodeLogprob."""
         return self.decode_to_inputs(z_chd, z_rhy, max_notes, return_logprob=True, **sampling)
 
     @staticmethod
@@ -795,7 +871,8 @@ class DisentangleVAE(PytorchModel):
 
     def reencode(self, z_chd, z_rhy, **sampling):
         """(dist_chd, dist_rhy) of the music decoded from (z_chd, z_rhy): decode_to_inputs, then inference_encode; **sampling: the
-        keywords of a sampled decode (inference_decode) and of the chord decode (chord_temperature, chroma_temperature, keep_chords)"""
+        keywords of a sampled decode (inference_decode) and of the chord decode (chord_temperature, chroma_temperature, keep_chords,
+        chord_grammar)"""
         pr_mat, _, c, _, _, _ = self.decode_to_inputs(z_chd, z_rhy, **sampling)
         return self.inference_encode(pr_mat, c)
 

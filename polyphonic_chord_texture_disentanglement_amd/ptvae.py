@@ -221,13 +221,16 @@ class RnnDecoder(nn.Module, _PrecMixin):
             return chord_tokens(root.transpose(0, 1), chroma.transpose(0, 1).reshape(T, z_chd.size(0), 24), bass.transpose(0, 1))
 
     def decode_chords(self, z_chd, *, temperature=None, chroma_temperature=None, seed=7, draw=0, sample_offset=0, keep=None,
-                      return_logprob=False):
+                      return_logprob=False, grammar=None):
         """Row-independent free-running chord decode of z_chd [B, z_dim] -> (c [B,8,36], chord14 [B,8,14]) on the device (ptv_chord_decode,
         one C call; INTEGRATION.md "Chord decode").  Every row feeds back its OWN token: unlike decode_tokens -- which keeps the
         reference's union over the batch (ptvae.py:74-77) -- a row's chords do not depend on the rest of the batch; at B = 1 the two agree.
         temperature (root and bass) / chroma_temperature (the 12 chroma bits; default: temperature), floats >= 0: the decisions are
         draws from softmax(logits / T), Philox noise keyed by (seed, draw, sample_offset + row, chord step); None: the argmax.
         keep: a functional_free.ChordKeep (DisentangleVAE.keep_chords) whose steps are forced and fed back like decisions.
+        grammar: a functional_free.ChordGrammar (DisentangleVAE.chord_grammar; INTEGRATION.md "Chord grammar"): allowed roots and pitch
+        classes, a chord-quality vocabulary, a chord-tone bass -- ptv_chord_decode_grammar; ChordLogprob.logq is then taken over the
+        allowed sets, and err carries the grammar's yield bits.
         return_logprob=True appends a ChordLogprob(logp [B,3], logq [B,3], forced [B,3], err [B], step_logp [B,8,3], step_logq [B,8,3],
         step_forced [B,8,3]) of device tensors, heads in the order (root, chroma, bass).  The step-major logits of the decode stay in
         last_chord_logits = (root [8,B,12], chroma [8,B,24], bass [8,B,12]).  No autograd graph, no synchronisation."""
@@ -236,12 +239,15 @@ class RnnDecoder(nn.Module, _PrecMixin):
         if not torch.is_tensor(z_chd) or z_chd.dim() != 2 or z_chd.shape[0] < 1 or z_chd.shape[1] != self.z_dim:
             raise ValueError('z_chd must be a tensor [B, %d]' % self.z_dim)
         FF_.check_chord_keep(keep, z_chd.shape[0])
+        FF_.check_chord_grammar(grammar, z_chd.shape[0])
         _require_cuda(z_chd, 'RnnDecoder.decode_chords')
+        if grammar is not None and grammar.rule.device != z_chd.device:
+            raise ValueError('the chord grammar must be on the device of z_chd (%s), it is on %s' % (z_chd.device, grammar.rule.device))
         if int(self.num_step / 4) != FF_.CHORD_STEPS:
             raise NotImplementedError('the chord decode is built for 8 chord steps')
         with torch.no_grad():
             block = FF_.sampling_block(z_chd.device, temperature, chroma_temperature, seed, draw, sample_offset) if sampled else None
-            out = FF_.chord_decode(z_chd, dict(zip(F_.CHD_PARAM_NAMES, self._params())), self._prec, block, keep)
+            out = FF_.chord_decode(z_chd, dict(zip(F_.CHD_PARAM_NAMES, self._params())), self._prec, block, keep, grammar)
         self.last_chord_logits = (out.root, out.chroma, out.bass)
         return (out.c, out.chord14, out.logprob) if return_logprob else (out.c, out.chord14)
 
