@@ -1358,6 +1358,40 @@ int ptv_dur_range_force_build(const unsigned char* lo, int lo_rows, const unsign
 int ptv_note_count_force_build(const unsigned char* lo, int lo_rows, const unsigned char* hi, int hi_rows, const unsigned char* steps,
                                int steps_rows, const int* src_pitch, const int* src_dur, int flags, long B, int* force_pitch, int* force_dur,
                                int* yielded, void* stream);
+/* Sounding state: restrictions that depend on what the decode itself decided at earlier time steps -- "do not strike a key that is still
+ * down", "at most four voices", "never silent" (csrc/sounding.hip; INTEGRATION.md "Sounding state").  A launch of the note
+ * loop decides ONE time step and reads that step's mask row and force words from memory, so the rule is one small launch between two note
+ * loops that writes the next step's row and words; no decode kernel knows of it.
+ * Accepted notes of a step s of row b: the slots 1..15 of xhat[b][s] in order, up to the first pitch 129.  A slot whose pitch lies outside
+ *   0..127 is skipped.  The duration is d = 1 + the five bit columns read most significant first (v & 1 of each), cut to min(d, 32 - s)
+ *   (ptv_grid_to_pr's parse).
+ * State: rem uint8 [B][128], zero before step 0.  After step s is decided: rem[p] = max(rem[p] - 1, 0) for every p; then for each accepted
+ *   note (p, d) in slot order rem[p] = d - 1 -- a later onset of a pitch replaces the earlier one, as in the piano-roll.  The held set
+ *   going into step s + 1 is H = {p : rem[p] > 0}, h = |H|; held[b][s + 1] = h and held[b][0] = 0 (int32 [B][32]).
+ * The effective step s + 1 of a SELECTED (row, step) (steps uint8 [rows][32], non-zero = selected), from the caller's base mask row and
+ *   base pitch force words w[0..14]:
+ *   no_restrike (bit 0 of the control word, a uint32 in DEVICE memory): mask_eff = mask_base & ~bits(H).  It is a pitch mask like any
+ *     other: a forced pitch is never checked against it, and where PTV_FORCE_BELOW lets a mask yield this one yields too.
+ *   max_sounding K (uint8 [rows][32]: 1..127, 0 = none) and min_sounding F (uint8 [rows][32]: 0..15) count SOUNDING pitches: with
+ *     H' = clamp(K - h, 0, 15) (15 where K is 0) and F' = clamp(F - h, 0, 15) the step's words are what ptv_note_count_force_build's rule
+ *     makes of lo = F', hi = H' without the room flag -- an owned step is copied, J is the forced prefix, E = max(H', J), only words equal
+ *     to -1 are replaced, the ceiling wins.  Duration words are never touched.  At a selected step that the keep does not own,
+ *     onsets + h <= K whenever J <= H'; kept notes win over the cap as they win over the note-count limits.  A floor is "not <eos> while
+ *     anything else is allowed": nothing guarantees it.
+ *   An unselected step gets the base row and the base words.  The state is tracked at every step regardless.
+ * ptv_sounding_step: one launch takes t_done in -1..30 and writes everything of step t_done + 1: rem, mask_eff[b][t_done + 1][0..3], the
+ *   15 words of row (t_done + 1) * B + b of force_eff [15][32B], held[b][t_done + 1] -- every element by one writer, nothing of any other
+ *   step.  t_done = -1 reads no grid (xhat may be NULL) and writes zeros to rem: the first call initialises the state.
+ *   xhat: int64 [B][32][16][6], the grid the decode writes.  mask_base: int32 [mask_rows][32][4], or NULL = every pitch allowed;
+ *   force_base: int32 [15][32B], or NULL = every word -1; max_sounding / min_sounding / steps: each with its own row count in {1, B}.
+ *   mask_eff int32 [B][32][4] or NULL (then mask_base must be NULL: no mask rule is written); force_eff int32 [15][32B] or NULL (then
+ *   force_base must be NULL: no count rule is on).  The note loop of step t_done + 1 is handed the EFFECTIVE arrays.
+ *   A NULL required pointer (max_sounding, min_sounding, steps, control, rem, held; xhat unless t_done = -1), a base table without its
+ *   output, an output that is its source, a row count outside {1, B}, B < 1 or t_done outside -1..30: PTV_ERR_ARG before any launch. */
+int ptv_sounding_step(const long* xhat, int t_done, long B, const int* mask_base, int mask_rows, const int* force_base,
+                      const unsigned char* max_sounding, int max_rows, const unsigned char* min_sounding, int min_rows,
+                      const unsigned char* steps, int steps_rows, const unsigned* control, unsigned char* rem, int* mask_eff,
+                      int* force_eff, int* held, void* stream);
 /* the duration entries of the constrained step loop with force arrays: as the two below, and a word PTV_FORCE_DUR_RANGE of force / force_idx
  * limits the note.  ptv_dur_out_token_sample_cons: idx is plane d of the decisions, the planes of the bits before it lie idx_stride words
  * apart below it (idx - k * idx_stride, k = 1..d, written by the calls before).  idx and the force array must be given. */
@@ -1459,6 +1493,12 @@ enum PtvDffTensor {
   PTV_DFF_WAIT_EVENT, PTV_DFF_RECORD_EVENT,   /* hipEvent_t or NULL: the persistent-launch turn around the cluster-mode note loops */
   PTV_DFF_SAMPLE,           /* NULL, or the sampling block of a sampled decode (32 bytes on the device, 48 with D_SAMPLE_TRUNC, 64 with D_SAMPLE_CONS, 80 with D_SAMPLE_ROWS; "Sampled decode" above): D_INFERENCE only,
                              * anything else is PTV_ERR_ARG before the first launch */
+  /* the sounding state ("Sounding state" above): with D_SND != 0 the call runs ptv_sounding_step(-1) before the loop and
+   * ptv_sounding_step(ts) behind every note loop for ts < 31, on the call's own stream.  The caller hands the note loop the EFFECTIVE arrays
+   * itself: io[13] is SND_FORCE_EFF (where given) and the block's mask address is SND_MASK_EFF (where given); the grid is io[11] */
+  PTV_DFF_SND_MASK_BASE, PTV_DFF_SND_FORCE_BASE,      /* the base tables, or NULL */
+  PTV_DFF_SND_MAX, PTV_DFF_SND_MIN, PTV_DFF_SND_STEPS, PTV_DFF_SND_CONTROL, PTV_DFF_SND_REM,
+  PTV_DFF_SND_MASK_EFF, PTV_DFF_SND_FORCE_EFF, PTV_DFF_SND_HELD,
   PTV_DFF_COUNT
 };
 enum PtvDffDim {
@@ -1473,6 +1513,8 @@ enum PtvDffDim {
   PTV_DFF_D_SAMPLE_TRUNC,   /* != 0: PTV_DFF_SAMPLE is the 48-byte block of a truncated sampled decode (top_k / min_p / top_p); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
   PTV_DFF_D_SAMPLE_CONS,    /* != 0: PTV_DFF_SAMPLE is the 64-byte block of a constrained decode (pitch mask / ascending notes); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
   PTV_DFF_D_SAMPLE_ROWS,    /* != 0: PTV_DFF_SAMPLE is the 80-byte block of a row-wise decode ("Per-row sampling"); without PTV_DFF_SAMPLE: PTV_ERR_ARG */
+  PTV_DFF_D_SND,            /* != 0: the sounding state is tracked (the PTV_DFF_SND_* slots); D_INFERENCE only -- with D_TRAIN, D_REPLAY or a coin: PTV_ERR_ARG.  0: nothing new is launched */
+  PTV_DFF_D_SND_MASK_ROWS, PTV_DFF_D_SND_MAX_ROWS, PTV_DFF_D_SND_MIN_ROWS, PTV_DFF_D_SND_STEPS_ROWS,   /* the row counts of ptv_sounding_step's tables */
   PTV_DFF_D_COUNT
 };
 int ptv_decoder_free_fwd(const void* const* t, const long* d, const void* const* wl, const void* const* io, const void* const* wr,

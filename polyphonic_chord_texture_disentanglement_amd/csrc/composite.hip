@@ -646,6 +646,21 @@ extern "C" int ptv_decoder_free_fwd(const void* const* t, const long* d, const v
   if (cons && !t[PTV_DFF_SAMPLE]) return PTV_ERR_ARG;
   const bool rowwise = d[PTV_DFF_D_SAMPLE_ROWS] != 0;                           // ... and per-row parameters (the 80-byte block)
   if (rowwise && !t[PTV_DFF_SAMPLE]) return PTV_ERR_ARG;
+  // the sounding state ("Sounding state"): inference only, one ptv_sounding_step before the loop and one behind every note loop but the last
+  const bool snd = d[PTV_DFF_D_SND] != 0;
+  if (snd) {
+    if (!inference || train || replay) return PTV_ERR_ARG;
+    for (int i = 0; i < 31; i++) if (time_coin[i]) return PTV_ERR_ARG;
+    for (int i = 0; i < 32; i++) if (note_mask[i]) return PTV_ERR_ARG;
+  }
+  auto sounding = [&](int t_done) -> int {
+    return ptv_sounding_step((const long*)io[11], t_done, B, (const int*)T_(t, PTV_DFF_SND_MASK_BASE), (int)d[PTV_DFF_D_SND_MASK_ROWS],
+                             (const int*)T_(t, PTV_DFF_SND_FORCE_BASE), (const unsigned char*)T_(t, PTV_DFF_SND_MAX),
+                             (int)d[PTV_DFF_D_SND_MAX_ROWS], (const unsigned char*)T_(t, PTV_DFF_SND_MIN), (int)d[PTV_DFF_D_SND_MIN_ROWS],
+                             (const unsigned char*)T_(t, PTV_DFF_SND_STEPS), (int)d[PTV_DFF_D_SND_STEPS_ROWS],
+                             (const unsigned*)T_(t, PTV_DFF_SND_CONTROL), M_<unsigned char>(t, PTV_DFF_SND_REM),
+                             M_<int>(t, PTV_DFF_SND_MASK_EFF), M_<int>(t, PTV_DFF_SND_FORCE_EFF), M_<int>(t, PTV_DFF_SND_HELD), stream);
+  };
   bool need_resum = inference;
   for (int i = 0; i < 31 && !need_resum; i++) need_resum = !time_coin[i];
   {
@@ -678,6 +693,10 @@ extern "C" int ptv_decoder_free_fwd(const void* const* t, const long* d, const v
   float* zg = M_<float>(t, PTV_DFF_ZG);
   const long ld_t = 2L * He + Zi;
   const float* w_ih_t = (const float*)T_(t, PTV_DFF_W_IH_T);
+  if (snd) {                                       // step 0's row and words, and the zeroed state: no memset, nothing depends on the prologue
+    if (!io[11] || (t[PTV_DFF_SND_FORCE_EFF] && io[13] != t[PTV_DFF_SND_FORCE_EFF])) return PTV_ERR_ARG;
+    PTV_TRY(sounding(-1));
+  }
   // ---- prologue (ptvae.py:435-437,457-462)
   PTV_TRY(ptv_gemm(P, 0, 0, B, Ht, Zs, T_(t, PTV_DFF_Z), Zs, T_(t, PTV_DFF_W_ZHID), Zs, NS, Ht, (const float*)T_(t, PTV_DFF_B_ZHID), 1.f, 0, 0, 0, 0, stream));
   PTV_TRY(ptv_gemm(P, 0, 0, B, Zi, Zs, T_(t, PTV_DFF_Z), Zs, T_(t, PTV_DFF_W_ZIN), Zs, M_<void>(t, PTV_DFF_Z_IN), Zi, (const float*)T_(t, PTV_DFF_B_ZIN), 1.f, 0,
@@ -730,6 +749,7 @@ extern "C" int ptv_decoder_free_fwd(const void* const* t, const long* d, const v
                      0, 0, 0, A16 | B16, stream));
     PTV_TRY(ptv_free_note_loop(wl, io, ldp, B, ts, inference ? 0u : note_mask[ts], loop_flags, stream));
     if (ts == 31) break;
+    if (snd) PTV_TRY(sounding(ts));
     float* tok_next = TOKS + (long)(ts + 1) * B * 2 * He;
     if (!inference && time_coin[ts]) {
       if (!t[PTV_DFF_XS]) return PTV_ERR_ARG;

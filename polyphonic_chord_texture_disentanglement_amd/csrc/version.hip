@@ -26,6 +26,8 @@ extern "C" const char* ptv_arch(void) { return "gfx950"; }
 // existing one changed, the same host tests pin the number; the header hash moves with the declaration
 // still 7: the chord grammar (csrc/chord_decode.hip: ptv_chord_decide_grammar, ptv_chord_decode_grammar and its PTV_CDG_* tables) added;
 // no existing entry point changed, the same host tests pin the number
+// still 7: the sounding state (csrc/sounding.hip: ptv_sounding_step; PTV_DFF_SND_* / PTV_DFF_D_SND* appended to ptv_decoder_free_fwd's
+// enums, all zero = the call as it was) added; no existing entry point changed, the header hash moves with the declarations
 extern "C" int ptv_abi_version(void) { return 7; }
 #ifndef PTV_HEADER_HASH
 #define PTV_HEADER_HASH "unknown"

@@ -688,6 +688,171 @@ def build_count_limits(device, min_count=None, max_count=None, onsets=None, rest
     return (out, yielded) if return_counts else out
 
 
+# ---------------------------------------------------------------------------------------------
+# sounding state (INTEGRATION.md "Sounding state"; include/ptvae_hip.h states the rule): restrictions that see what the
+# decode itself decided at earlier time steps.  A Sounding holds the caller's tables; a SoundingRun what one decode reads and writes.
+# ---------------------------------------------------------------------------------------------
+SOUNDING_NO_RESTRIKE = 1        # bit 0 of the control word
+
+
+class Sounding:
+    """the sounding rules of a decode, for sounding= (DisentangleVAE.sounding; ptv_sounding_step): control (int32 device tensor [1], bit 0
+    = no_restrike), max_sounding / min_sounding / steps (uint8 device tensors [rows, 32], rows 1 or batch; 0 in max_sounding = no
+    ceiling), batch, and what the host knows of them: no_restrike, ceiling, floor (a rule of that kind was given).  What it demands of
+    the decode, like a Keep: needs_constrained -- a mask rule or PTV_FORCE_NOT_EOS words, which only the constrained kernels honour;
+    needs_force -- count words, so the decode runs with force arrays (an all-free keep where the caller gave none)"""
+
+    def __init__(self, control, max_sounding, min_sounding, steps, batch, no_restrike=False, ceiling=False, floor=False):
+        self.control, self.max_sounding, self.min_sounding, self.steps, self.batch = control, max_sounding, min_sounding, steps, batch
+        self.no_restrike, self.ceiling, self.floor = bool(no_restrike), bool(ceiling), bool(floor)
+
+    @property
+    def needs_constrained(self):
+        return self.no_restrike or self.floor
+
+    @property
+    def needs_force(self):
+        return self.ceiling or self.floor
+
+    def tables(self):
+        return self.max_sounding, self.min_sounding, self.steps
+
+    def _with(self, fn, batch):
+        return Sounding(self.control, *(fn(t) if t.shape[0] > 1 else t for t in self.tables()), batch, self.no_restrike, self.ceiling,
+                        self.floor)
+
+    def tiled(self, n):
+        """the rules of the batch repeated n times (decode_best_of): a table with one row per sample is tiled like a mask's rows"""
+        return self._with(lambda t: t.repeat(n, 1), n * self.batch)
+
+    def sliced(self, lo, hi):
+        """the rules of the rows lo..hi-1 of the batch (a shard of a decode: the state of a row depends on that row alone)"""
+        if not 0 <= lo < hi <= self.batch:
+            raise ValueError('rows %r..%r are not rows of a batch of %d' % (lo, hi, self.batch))
+        return self._with(lambda t: t[lo:hi].contiguous(), hi - lo)
+
+
+def build_sounding(device, no_restrike=False, max_sounding=None, min_sounding=None, steps=None, batch=None):
+    """the sounding rules of a free-running decode -> Sounding (INTEGRATION.md "Sounding state").  no_restrike: a bool -- a pitch that
+    still sounds is not struck again; max_sounding: at most that many pitches sound at a step, a host int 1..127 or an integer device
+    tensor [32] / [B, 32] (0 = no ceiling there); min_sounding: at least that many, a host int 0..15 or such a tensor (a floor is "not
+    <eos> while anything else is allowed": nothing guarantees it).  steps: as build_keep's, None = all 32 -- the rules act at the selected
+    steps, the state is tracked at all of them.  At least one of the three rules must be given.  batch: the rows of the decode.
+    ValueError before anything touches the GPU; nothing is copied to the host."""
+    if not isinstance(no_restrike, bool):
+        raise ValueError('no_restrike must be a bool, got %r' % (no_restrike,))
+    if batch is not None and (isinstance(batch, bool) or not isinstance(batch, int) or batch < 1):
+        raise ValueError('batch must be an integer >= 1, got %r' % (batch,))
+    sizes = set() if batch is None else {batch}
+    for name, v, lo, hi in (('max_sounding', max_sounding, 1, 127), ('min_sounding', min_sounding, 0, 15)):
+        if v is None:
+            continue
+        if torch.is_tensor(v):
+            if v.device.type != 'cuda':
+                raise ValueError('%s must be a device tensor, got one on %s' % (name, v.device))
+            if v.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError('%s must be an integer tensor, got %s' % (name, v.dtype))
+            if not ((v.dim() == 1 and v.shape[0] == 32) or (v.dim() == 2 and v.shape[1] == 32 and v.shape[0] >= 1)):
+                raise ValueError('%s must have shape [32] or [B, 32], got %s' % (name, tuple(v.shape)))
+            if v.dim() == 2 and v.shape[0] > 1:
+                sizes.add(v.shape[0])
+        elif isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError('%s must be an integer in %d..%d or an integer device tensor [32] / [B, 32], got %r' % (name, lo, hi, v))
+    sel = steps if steps is None or torch.is_tensor(steps) else keep_steps_row(steps)
+    if torch.is_tensor(sel):
+        if sel.device.type != 'cuda':
+            raise ValueError('steps must be on the device (or a host iterable of step indices / a slice)')
+        if sel.dtype not in (torch.bool, torch.uint8):
+            raise ValueError('steps must be bool or uint8, got %s' % (sel.dtype,))
+        if sel.dim() != 2 or sel.shape[1] != 32 or sel.shape[0] < 1:
+            raise ValueError('steps must have shape [B, 32] or [1, 32], got %s' % (tuple(sel.shape),))
+        if sel.shape[0] > 1:
+            sizes.add(sel.shape[0])
+    if not no_restrike and max_sounding is None and min_sounding is None:
+        raise ValueError('sounding needs no_restrike=True, max_sounding or min_sounding')
+    if len(sizes) > 1:
+        raise ValueError('the batch sizes of batch, max_sounding, min_sounding and steps disagree: %s' % (sorted(sizes),))
+    if not sizes:
+        raise ValueError('batch is needed: no [B, 32] tensor tells the number of samples')
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise ValueError('the sounding state lives on the device, got %s' % (dev,))
+    # ---- nothing below raises
+    def rows(v, hi):
+        if torch.is_tensor(v):
+            return v.to(dev).reshape(-1, 32).clamp(0, hi).to(torch.uint8).contiguous()
+        return torch.full((1, 32), 0 if v is None else v, dtype=torch.uint8, device=dev)
+    if sel is None:
+        sel = torch.ones(1, 32, dtype=torch.uint8, device=dev)
+    elif torch.is_tensor(sel):
+        sel = (sel.to(dev) != 0).to(torch.uint8).contiguous()
+    else:
+        sel = torch.frombuffer(bytearray(sel), dtype=torch.uint8).view(1, 32).to(dev)
+    control = torch.tensor([SOUNDING_NO_RESTRIKE if no_restrike else 0], dtype=torch.int32, device=dev)
+    return Sounding(control, rows(max_sounding, 127), rows(min_sounding, 15), sel, sizes.pop(), no_restrike, max_sounding is not None,
+                    min_sounding is not None)
+
+
+def check_sounding(sounding, batch=None, device=None):
+    """ValueError unless sounding is None or a Sounding whose tables fit its batch (and `batch` / `device`, where the caller knows them)"""
+    if sounding is None:
+        return
+    if not isinstance(sounding, Sounding):
+        raise ValueError('sounding must be what DisentangleVAE.sounding(...) returns, got %r' % (type(sounding).__name__,))
+    B = sounding.batch
+    c = sounding.control
+    if not torch.is_tensor(c) or c.device.type != 'cuda' or c.dtype != torch.int32 or tuple(c.shape) != (1,):
+        raise ValueError('sounding.control must be an int32 device tensor [1]')
+    for name, t_ in zip(('max_sounding', 'min_sounding', 'steps'), sounding.tables()):
+        if (not torch.is_tensor(t_) or t_.device != c.device or t_.dtype != torch.uint8 or t_.dim() != 2 or t_.shape[1] != 32
+                or t_.shape[0] not in (1, B) or not t_.is_contiguous()):
+            raise ValueError('sounding.%s must be a contiguous uint8 tensor [1, 32] or [%d, 32] on the device of its control word' % (name, B))
+    if batch is not None and B != batch:
+        raise ValueError('sounding was built for a batch of %d, the decoded batch has %d rows' % (B, batch))
+    if device is not None and c.device != device:
+        raise ValueError('sounding is on %s, the decode on %s' % (c.device, device))
+
+
+class SoundingRun:
+    """what ONE decode with a Sounding reads and writes: the rules `snd`, the base tables (mask_base int32 [rows, 32, 4] / force_base int32
+    [15, 32 B], or None), the state rem uint8 [B, 128], and the outputs mask_eff int32 [B, 32, 4] / force_eff int32 [15, 32 B] (each None
+    where that rule is off) and held int32 [B, 32].  The note loop is handed the effective arrays; step() is the launch between two of
+    them.  Nothing is zeroed here: ptv_sounding_step(-1) initialises the state"""
+
+    def __init__(self, snd, B, dev, mask=False, mask_base=None, force=False, force_base=None):
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.snd, self.B = snd, B
+        self.mask_base, self.force_base = (mask_base if mask else None), (force_base if force else None)
+        self.rem = torch.empty(B, 128, dtype=torch.uint8, device=dev)
+        self.held = torch.empty(B, 32, **i32)
+        self.mask_eff = torch.empty(B, 32, 4, **i32) if mask else None
+        self.force_eff = torch.empty(15, 32 * B, **i32) if force else None
+
+    def step(self, xhat, t_done):
+        """ptv_sounding_step on the current stream: everything of time step t_done + 1 (t_done = -1: step 0 and the zeroed state)"""
+        s, mb = self.snd, self.mask_base
+        call('ptv_sounding_step', ptr(xhat), t_done, self.B, ptr(mb), 1 if mb is None else mb.shape[0], ptr(self.force_base),
+             ptr(s.max_sounding), s.max_sounding.shape[0], ptr(s.min_sounding), s.min_sounding.shape[0], ptr(s.steps), s.steps.shape[0],
+             ptr(s.control), ptr(self.rem), ptr(self.mask_eff), ptr(self.force_eff), ptr(self.held), stream_ptr())
+
+    def slots(self):
+        """(the PTV_DFF_SND_* tensors, the PTV_DFF_D_SND* dims) of ptv_decoder_free_fwd"""
+        s, mb = self.snd, self.mask_base
+        return (dict(SND_MASK_BASE=mb, SND_FORCE_BASE=self.force_base, SND_MAX=s.max_sounding, SND_MIN=s.min_sounding, SND_STEPS=s.steps,
+                     SND_CONTROL=s.control, SND_REM=self.rem, SND_MASK_EFF=self.mask_eff, SND_FORCE_EFF=self.force_eff, SND_HELD=self.held),
+                dict(SND=1, SND_MASK_ROWS=1 if mb is None else mb.shape[0], SND_MAX_ROWS=s.max_sounding.shape[0],
+                     SND_MIN_ROWS=s.min_sounding.shape[0], SND_STEPS_ROWS=s.steps.shape[0]))
+
+
+def sounding_block(blk, mask_eff):
+    """the block of a decode under a SoundingRun with a mask rule: a copy of `blk` whose mask address is mask_eff's and whose "one mask
+    row" flag is clear (mask_eff has a row per sample); it carries mask_eff as its pitch_mask.  Device operations only"""
+    out = clone_block(blk, mask_eff)
+    out[6:7].bitwise_and_(~CONS_MASK_ROW1)
+    out[7:8].copy_(torch.tensor([mask_eff.data_ptr()], dtype=torch.int64))
+    return out
+
+
 def split_voice(x, voice_steps, below=None, lowest=None, whole_steps=None):
     """the selection of build_keep_voice as two model grids (ptv_grid_split_voice) -> (x_voice, x_rest int64 [B, 32, 16, 6], kept_n int32
     [B, 32], err int32 [B]): per step the kept notes and what the decoder would re-draw, each a valid step"""
@@ -1158,7 +1323,9 @@ class FreeBuffers:
 
 # what a step-loop forward was called with, beside the parameters: emb3 = the ground-truth embedding as [16, R, E] or None, coins as given,
 # masks / time_coins = coin_masks(coins), force_pitch [15, R] / force_dur [5, 15 R] int32 or None, sampling = the block or None
-FreeInputs = collections.namedtuple('FreeInputs', 'z emb3 xs coins masks time_coins force_pitch force_dur sampling inference prec')
+# sounding = the SoundingRun of a decode with sounding rules (force_pitch / the block's mask are then its EFFECTIVE arrays) or None
+FreeInputs = collections.namedtuple('FreeInputs', 'z emb3 xs coins masks time_coins force_pitch force_dur sampling inference prec sounding',
+                                    defaults=(None,))
 # the packs and tables of a step-loop forward: tok0 / tok0_lds = the first note token of every time step and its row stride (0: one <sos>
 # row), dur_tabs, the MFMA operands of the time GRU and of the per-step products (bf16 shadows on the persistent path), wE =
 # dec_notes_emb_gru's eight, and on the persistent path pk = _free_packs, wl / wr = note_loop_weights / resum_weights
@@ -1245,13 +1412,18 @@ def _free_fwd_composite(plan, P, buf, tbl, inp):
         F_.zero_skip_sync()
     t = _composite_tensors(plan, P, buf, tbl, inp)
     cluster = int(bool(plan.cluster) and not plan.capturing)
-    dvals = _DFF.dims({'B': B, 'ZS': inp.z.shape[1], 'ZI': buf.z_in.shape[1], 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'E': E, 'NP': NP,
+    dvals = {'B': B, 'ZS': inp.z.shape[1], 'ZI': buf.z_in.shape[1], 'HE': He, 'HT': Ht, 'HN': Hn, 'HD': Hd, 'E': E, 'NP': NP,
                        'LDP': buf.pitch.stride(0), 'TRAIN': int(plan.train), 'REPLAY': int(plan.replay),
                        'INFERENCE': int(bool(inp.inference)),
                        'LOOP_FLAGS': note_loop_word(plan.train, plan.replay, NOTE_LOOP_SPLIT, plan.cluster), 'CLUSTER': cluster,
                        'RESUM_TRAIN': int(plan.train and not plan.replay), 'TOK0_LDS': tbl.tok0_lds,
                        'W_IH_T_BF16': tbl.w_ih_t16.dtype == torch.bfloat16, 'W_HH_T_BF16': tbl.w_hh_t.dtype == torch.bfloat16,
-                       'SAMPLE_TRUNC': plan.kind.trunc, 'SAMPLE_CONS': plan.kind.cons, 'SAMPLE_ROWS': plan.kind.rows})
+                       'SAMPLE_TRUNC': plan.kind.trunc, 'SAMPLE_CONS': plan.kind.cons, 'SAMPLE_ROWS': plan.kind.rows}
+    if inp.sounding is not None:                            # (without it the call launches nothing new)
+        snd_t, snd_d = inp.sounding.slots()
+        t.update(snd_t)
+        dvals.update(snd_d)
+    dvals = _DFF.dims(dvals)
     masks, tc = inp.masks, inp.time_coins
     # the cluster-mode note loops take the persistent-launch turn (functional._PersistTurn): the library records again after the last one
     turn = F_._CompositeTurn(F_.cur_stream()) if cluster else None
@@ -1315,6 +1487,8 @@ def _free_fwd_persistent(plan, P, buf, tbl, inp):
     B, pk, st = buf.dims[0], tbl.pk, stream_ptr()
     word = note_loop_word(plan.train, plan.replay, NOTE_LOOP_SPLIT, plan.cluster, plan.kind)
     _first_tokens(buf, tbl)
+    if inp.sounding is not None:
+        inp.sounding.step(buf.xhat, -1)
     for t in range(32):
         ns = _time_step(plan, P, buf, tbl, inp, t)
         H0GC = gemm(ns, pk['w_cat'], bias=pk['b_cat'], prec=inp.prec)
@@ -1324,6 +1498,8 @@ def _free_fwd_persistent(plan, P, buf, tbl, inp):
         with (F_._PersistTurn() if plan.cluster and not plan.capturing else contextlib.nullcontext()):
             call('ptv_free_note_loop', tbl.wl, io, buf.pitch.stride(0), B, t, inp.masks[t], word, st)
         if t < 31:
+            if inp.sounding is not None:
+                inp.sounding.step(buf.xhat, t)
             _next_time_token(plan, P, buf, tbl, inp, t)
 
 
@@ -1331,6 +1507,8 @@ def _free_fwd_steps(plan, P, buf, tbl, inp):
     """the generic loop, one launch per cell and head: 32 time steps of 15 note steps of 5 duration steps"""
     B, Ht = buf.dims[0], buf.dims[4]
     _first_tokens(buf, tbl)
+    if inp.sounding is not None:
+        inp.sounding.step(buf.xhat, -1)
     for t in range(32):
         rows = slice(t * B, (t + 1) * B)
         ns = _time_step(plan, P, buf, tbl, inp, t)
@@ -1339,6 +1517,8 @@ def _free_fwd_steps(plan, P, buf, tbl, inp):
         for n in range(15):
             _note_step(plan, P, buf, tbl, inp, t, n, GCt)
         if t < 31:
+            if inp.sounding is not None:
+                inp.sounding.step(buf.xhat, t)
             _next_time_token(plan, P, buf, tbl, inp, t)
 
 
@@ -1491,11 +1671,14 @@ class DecoderStepFn(torch.autograd.Function):
         He, Ht, Hn, Hd = (P['dec_%s_gru.weight_hh_l0' % n].shape[1] for n in ('notes_emb', 'time', 'notes', 'dur'))
         dims = (B, R, E, He, Ht, Hn, Hd, NP)
         force_pitch, force_dur = (force.get('pitch'), force.get('dur')) if force else (None, None)       # [15, R], [5, 15 R] int32
+        run = force.get('sounding') if force else None      # a SoundingRun: 'pitch' and the block's mask are its effective arrays
+        if run is not None and (not inference or any(any(r) for r in coins[0]) or any(coins[1])):
+            raise ValueError('sounding is inference only: it cannot be combined with training or teacher forcing')
         plan = _free_plan(prec, dims, z.dtype, coins, inference, any(ctx.needs_input_grad),
                           force_pitch is not None or force_dur is not None, block_kind(sampling), _num_cu(),
                           torch.cuda.is_current_stream_capturing())
         inp = FreeInputs(z, emb.view(16, R, E) if emb is not None else None, xs, coins, *coin_masks(coins, inference), force_pitch, force_dur,
-                         sampling, inference, prec)
+                         sampling, inference, prec, run)
 
         # ---- allocate by the plan, then launch (the composite runs the prologue itself)
         buf = FreeBuffers(plan, dims + (Zi,), prec, inference, dev)

@@ -14,7 +14,7 @@ from . import functional as F_
 from ._lib import call, ptr, stream_ptr
 from .amc_dl.torch_plus import PytorchModel
 from .functional_free import (CHORD_SCALES, CHORD_STEPS, RowSampling, build_chord_grammar, build_chord_keep, build_count_limits, build_dur_limits,
-                              build_keep, build_keep_rhythm, build_keep_top, build_keep_voice, check_chord_grammar, check_chord_keep,
+                              build_sounding, check_sounding, build_keep, build_keep_rhythm, build_keep_top, build_keep_voice, check_chord_grammar, check_chord_keep,
                               check_chord_sampling, check_constraints, check_keep, check_rows, check_sampling, chord_keep_steps_row,
                               chord_vocabulary, make_block, pitch_class_set, row_sampling_words, sampling_words, split_top, split_voice)
 from .optim import refresh_weight_shadows
@@ -38,10 +38,10 @@ CHD_DEC_SLOT = 4        # the chord decoder beside the PianoTree decoder
 ENC_CHAIN = True
 DT_PAD_COL = 3          # column of dt_x that is set for a <pad> row (is_note class 3, dataset.py:194-195): its zeros count the live rows
 DT_SHAPE = (32, 16, 39)
-# the keywords of a free-running decode (inference_decode); rows (a functional_free.RowSampling) and the last two are device objects, the
-# rest host values
-DECODE_KEYS = ('temperature', 'dur_temperature', 'seed', 'draw', 'sample_offset', 'top_k', 'min_p', 'top_p', 'rows', 'ascending', 'pitch_mask',
-               'keep')
+# the keywords of a free-running decode (inference_decode); rows (a functional_free.RowSampling), sounding (a functional_free.Sounding)
+# and the last two are device objects, the rest host values
+DECODE_KEYS = ('temperature', 'dur_temperature', 'seed', 'draw', 'sample_offset', 'top_k', 'min_p', 'top_p', 'rows', 'sounding', 'ascending',
+               'pitch_mask', 'keep')
 
 
 class DecodeRequest(collections.namedtuple('DecodeRequest', 'sampled kw mask keep batch')):
@@ -50,10 +50,12 @@ class DecodeRequest(collections.namedtuple('DecodeRequest', 'sampled kw mask kee
 
     def tiled(self, n):
         """the request of the batch repeated n times (decode_best_of): a mask or keep with one row per sample is tiled alike, and so is
-        the table of rows= -- candidate k of row b draws as sample sample_id[b] + k * B"""
+        the table of rows= -- candidate k of row b draws as sample sample_id[b] + k * B -- and so are the tables of sounding="""
         mask, keep, B = self.mask, self.keep, self.batch
         if self.kw.get('rows') is not None:
             self = self._replace(kw=dict(self.kw, rows=self.kw['rows'].tiled(n)))
+        if self.kw.get('sounding') is not None:
+            self = self._replace(kw=dict(self.kw, sounding=self.kw['sounding'].tiled(n)))
         if mask is not None and mask.shape[0] == B and B > 1:
             mask = mask.repeat(n, 1, 1)
         if keep is not None:
@@ -405,12 +407,13 @@ class DisentangleVAE(PytorchModel):
     # and combines with seed, draw, pitch_mask, ascending and keep like a constrained decode.
     @staticmethod
     def _check_sampling(temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None, top_k=None, min_p=None,
-                        top_p=None, rows=None, pitch_mask=None, ascending=None, keep=None, batch=None):
+                        top_p=None, rows=None, sounding=None, pitch_mask=None, ascending=None, keep=None, batch=None):
         """ValueError for a bad sampling keyword; True for a sampled decode, False for the argmax decode (constrained or not).  No side
         effect, no launch.  batch: the rows of the decoded batch where the caller knows them (pitch_mask's row count and keep's batch are
         held to it)"""
         check_constraints(pitch_mask, ascending, batch)
         check_keep(keep, batch)
+        check_sounding(sounding, batch)
         if rows is not None:                                   # per-row sampling: a sampled decode whose rule is the table's
             if any(v is not None for v in (temperature, dur_temperature, top_k, min_p, top_p, sample_offset)):
                 raise ValueError('rows carries temperature, dur_temperature, top_k, min_p, top_p and the sample ids of every row: it cannot '
@@ -439,6 +442,8 @@ class DisentangleVAE(PytorchModel):
         keep, mask = sampling.get('keep'), sampling.get('pitch_mask')
         if keep is not None and self.decoder.force_trace is not None:
             raise ValueError('keep cannot be combined with decoder.force_trace: both fill the force arrays')
+        if sampling.get('sounding') is not None and self.decoder.force_trace is not None:
+            raise ValueError('sounding cannot be combined with decoder.force_trace: both fill the force arrays')
         return DecodeRequest(sampled, {k: sampling.get(k) for k in DECODE_KEYS[:-2]}, None if mask is None else mask.contiguous(), keep, batch)
 
     def _sampling_words(self, req):
@@ -447,11 +452,15 @@ class DisentangleVAE(PytorchModel):
         kind, whose kernels alone honour its words: an `ascending` nobody gave becomes False, the vacuous constraint (flags 0, no mask).  A
         top keep does the same with True: its ceilings count on notes that ascend (_request has refused ascending=False).  A keep with
         duration limits (DurKeep) is promoted like a rhythm keep; built into a top keep it stays a top keep.  Note-count limits with a
-        floor (CountKeep) are promoted like a rhythm keep, with room=True like a top keep; without a floor they promote nothing"""
+        floor (CountKeep) are promoted like a rhythm keep, with room=True like a top keep; without a floor they promote nothing.
+        Sounding rules follow the keep family: no_restrike or a floor (Sounding.needs_constrained) promotes like a rhythm keep, a ceiling
+        alone promotes nothing and runs in every kind"""
         kw = req.kw
         ascending = kw['ascending']
         if ascending is None and req.keep is not None and req.keep.needs_constrained:
             ascending = req.keep.needs_ascending
+        if ascending is None and kw['sounding'] is not None and kw['sounding'].needs_constrained:
+            ascending = False
         if not req.sampled:
             if req.mask is None and ascending is None:
                 return None
@@ -479,6 +488,9 @@ class DisentangleVAE(PytorchModel):
         block = None if words is None else make_block(words, req.mask, dec_z.device, req.kw['rows'])
         if req.keep is not None:
             _require_cuda(dec_z, 'DisentangleVAE decode with kept steps')
+        if req.kw['sounding'] is not None:
+            _require_cuda(dec_z, 'DisentangleVAE decode with sounding rules')
+            return self.decoder(dec_z, True, None, None, 0., 0., sampling=block, keep=req.keep, sounding=req.kw['sounding'])
         return self.decoder(dec_z, True, None, None, 0., 0., sampling=block, keep=req.keep)
 
     def row_sampling(self, batch, temperature, dur_temperature=None, top_k=None, min_p=None, top_p=None, sample_id=None, sample_offset=None):
@@ -580,6 +592,17 @@ class DisentangleVAE(PytorchModel):
         output path writes, not a limit on the decode: this is.  ValueError before any launch; nothing is copied to the host."""
         return build_count_limits(self.device, min_count, max_count, onsets, rests, steps, room, batch, keep, return_counts)
 
+    def sounding(self, no_restrike=False, max_sounding=None, min_sounding=None, steps=None, batch=None):
+        """The sounding rules of a decode -> functional_free.Sounding for sounding= (ptv_sounding_step; INTEGRATION.md "Sounding state"):
+        restrictions that see what the decode itself decided at earlier time steps.  no_restrike=True: a pitch that still sounds is not
+        struck again; max_sounding: at most that many pitches sound at a step (held ones included), a host int 1..127 or an integer
+        device tensor [32] / [B, 32]; min_sounding: at least that many, a host int 0..15 or such a tensor -- "not <eos> while anything
+        else is allowed", as a note-count floor without room.  steps: as keep()'s, default all.  At least one rule must be given;
+        batch: the rows of the decode.  no_restrike or a floor makes the decode the constrained kind (an `ascending` nobody gave becomes
+        False, no temperature is the constrained argmax); a ceiling alone runs in every kind.  Kept notes win over the cap.  Every bad
+        value is a ValueError before anything touches the GPU."""
+        return build_sounding(self.device, no_restrike, max_sounding, min_sounding, steps, batch)
+
     def split_top(self, x, top_steps, above=None, highest=None, whole_steps=None):
         """The selection of keep_top as two grids -> (x_top, x_rest, kept_n, err) (ptv_grid_split_top), the mirror of split_voice: x_top
         holds per step the notes keep_top forces (a top step: the kept notes and an <eos>; a whole step: the step; a free step: the empty
@@ -634,7 +657,7 @@ class DisentangleVAE(PytorchModel):
         return out
 
     def inference_decode(self, z_chd, z_rhy, *, temperature=None, dur_temperature=None, seed=None, draw=None, sample_offset=None,
-                         top_k=None, min_p=None, top_p=None, rows=None, pitch_mask=None, ascending=None, keep=None):
+                         top_k=None, min_p=None, top_p=None, rows=None, pitch_mask=None, ascending=None, keep=None, sounding=None):
         kw = locals()
         return self._inference_decode(z_chd, z_rhy, self._request(z_chd.shape[0], **{k: kw[k] for k in DECODE_KEYS}))
 
@@ -772,7 +795,7 @@ class DisentangleVAE(PytorchModel):
     # (ptv_grid_to_pr, ptv_chord_tokens); inference_decode above stays the reference's host form
     def decode_to_inputs(self, z_chd, z_rhy, max_notes=10, *, temperature=None, dur_temperature=None, seed=None, draw=None,
                          sample_offset=None, top_k=None, min_p=None, top_p=None, rows=None, pitch_mask=None, ascending=None, keep=None,
-                         return_logprob=False, chord_temperature=None, chroma_temperature=None, keep_chords=None, chord_grammar=None):
+                         sounding=None, return_logprob=False, chord_temperature=None, chroma_temperature=None, keep_chords=None, chord_grammar=None):
         """Free-running decode of (z_chd, z_rhy) -> (pr_mat f32 [B,32,128], x int64 [B,32,16,6], c f32 [B,8,36], notes int32
         [B,32*max_notes,3], count int32 [B], err int32 [B]); nothing leaves the device.  (pr_mat, c) feed inference_encode, (x, c,
         pr_mat) feed loss(); notes / count / err as PtvaeDecoder.grid_to_pr_and_notes_batch.  The keywords of a sampled decode as

@@ -269,15 +269,20 @@ DecodeLogprob = collections.namedtuple('DecodeLogprob', 'logp logq counts err st
 LastDecode = collections.namedtuple('LastDecode', 'pitch dur xhat sampling force')      # what an inference decode leaves for decode_logprob()
 
 
-class _DecodeGraph(collections.namedtuple('_DecodeGraph', 'graph z outs block mask mask_addr force rows rows_addr', defaults=(None, None))):
+class _DecodeGraph(collections.namedtuple('_DecodeGraph', 'graph z outs block mask mask_addr force rows rows_addr run',
+                                          defaults=(None, None, None))):
     """one captured inference decode: graph, z (static input), outs (static outputs), block / mask / mask_addr (static sampling block, the
     static pitch mask of a constrained one and the one-word tensor holding that mask's address; None where the kind has none), force (the
     static force arrays of a decode with kept steps, or None), rows / rows_addr (the static row table of a row-wise decode and the
-    one-word tensor holding its address, or None)"""
+    one-word tensor holding its address, or None), run (the static functional_free.SoundingRun of a decode with sounding rules, or None:
+    its Sounding holds static tables and a static control word, its base tables are static too -- force['pitch'] is then its force_eff,
+    mask its mask_base and mask_addr the address of its mask_eff)"""
 
-    def refresh(self, z, sampling, keep):
+    def refresh(self, z, sampling, keep, sounding=None):
         """the caller's inputs into the static tensors, before every replay"""
         self.z.copy_(z)
+        if self.run is not None:
+            return self._refresh_sounding(sampling, keep, sounding)
         if self.force is not None:
             self.force['pitch'].copy_(keep.pitch)
             self.force['dur'].copy_(keep.dur)
@@ -285,6 +290,32 @@ class _DecodeGraph(collections.namedtuple('_DecodeGraph', 'graph z outs block ma
             self.block.copy_(sampling)
             if self.mask is not None and sampling.pitch_mask is not None:
                 self.mask[:sampling.pitch_mask.shape[0]].copy_(sampling.pitch_mask)   # (a one-row mask: row 0, the block's flag says so)
+                self.block[7:8].copy_(self.mask_addr)
+            if self.rows is not None:
+                self.rows.copy_(sampling.rows.table)
+                self.block[8:9].copy_(self.rows_addr)
+
+    def _refresh_sounding(self, sampling, keep, sounding):
+        """a decode with sounding rules: the caller's rules, mask and keep into the static BASE tables (every table has a row per sample
+        here, so one capture serves every Sounding); the block keeps pointing at the effective mask"""
+        run, B = self.run, self.z.shape[0]
+        run.snd.control.copy_(sounding.control)
+        for dst, src in zip(run.snd.tables(), sounding.tables()):
+            dst.copy_(src.expand(B, 32))
+        if keep is None:
+            run.force_base.fill_(-1)
+            self.force['dur'].fill_(-1)
+        else:
+            run.force_base.copy_(keep.pitch)
+            self.force['dur'].copy_(keep.dur)
+        if self.block is not None:
+            self.block.copy_(sampling)
+            if self.mask is not None:
+                if sampling.pitch_mask is None:
+                    self.mask.fill_(-1)
+                else:
+                    self.mask.copy_(sampling.pitch_mask.expand(B, 32, 4))
+                self.block[6:7].bitwise_and_(~FF_.CONS_MASK_ROW1)
                 self.block[7:8].copy_(self.mask_addr)
             if self.rows is not None:
                 self.rows.copy_(sampling.rows.table)
@@ -338,23 +369,30 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         self.summaries_needed = True       # emb_x() starts the ground-truth note summaries early unless told they are dead values
         self.last_dur_idx = None
         self._last_decode = None           # LastDecode of the last inference decode: decode_logprob()
+        self.last_sounding = None          # (mask_eff or None, force_pitch_eff or None, held) of the last inference decode with sounding=
+        self._graph_effective = None
 
     def _params(self):
         sd = dict(self.named_parameters())
         return [sd[n] for n in F_.DEC_PARAM_NAMES]
 
-    def _graph_decode(self, z, coins, sampling=None, keep=None):
+    def _graph_decode(self, z, coins, sampling=None, keep=None, sounding=None):
         """Free-running decode replayed from a captured hipGraph: the step loop is ~9,000 tiny launches whose order and arguments depend
         only on (B, precision) -- capture once, then one graph launch per call.  The graph holds raw parameter pointers, so it is
         re-captured if the parameter storage moves.  Each kind of decode (functional_free.BlockKind: argmax, sampled, truncated,
         constrained, row-wise) is a graph of its own (other kernels), and kept steps (keep: functional_free.Keep) double the kinds: the key holds
         the kind number and, only with a keep, one more element.  What a caller may vary -- z, seed / draw / temperatures / top_k / min_p
         / top_p / flags in the block, the pitch mask, the row table, the force arrays of a keep -- lives in static tensors that _DecodeGraph.refresh
-        fills before every replay, so one capture per key serves them all."""
+        fills before every replay, so one capture per key serves them all.  A decode with sounding rules (sounding: functional_free.Sounding)
+        has one more key element instead of the keep's: its graph always holds force arrays, the base and effective tables, the state and
+        the control word as static tensors, so one capture serves every Sounding, with a keep or without."""
         ps = self._params_free()
         kind = FF_.block_kind(sampling)
-        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind.kind) + ((True,) if keep is not None else ())
+        key = (z.shape[0], self._prec, z.device.index, tuple(p.data_ptr() for p in ps), kind.kind) + ((True,) if keep is not None and sounding is None else ()) \
+            + (('sounding',) if sounding is not None else ())
         ent = self._graphs.get(key)
+        if ent is None and sounding is not None:
+            ent = self._graphs[key] = self._capture_sounding(z, coins, sampling, keep, sounding, kind, ps, key)
         if ent is None:
             block = mask = mask_addr = rows = rows_addr = None
             if kind.cons:                                      # (captured with every pitch allowed; the flags are the first caller's)
@@ -389,9 +427,51 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
                 del self._graphs[k]                                         # with and without kept steps) is kept
             self.graph_captures += 1
             ent = self._graphs[key] = _DecodeGraph(g, static_z, outs, block, mask, mask_addr, force, rows, rows_addr)
-        ent.refresh(z, sampling, keep)
+        ent.refresh(z, sampling, keep, sounding)
         ent.graph.replay()
+        if ent.run is not None:                                # what decode_logprob() and last_sounding read: the effective arrays
+            self._graph_effective = (ent.block, ent.force, ent.run)
         return ent.outs
+
+    def _capture_sounding(self, z, coins, sampling, keep, sounding, kind, ps, key):
+        """the _DecodeGraph of a decode with sounding rules (see _graph_decode): static tables with a row per sample, every rule wired --
+        the mask rule wherever the kind has a mask, the count rule always; what a Sounding switches off it switches off in its tables"""
+        B, dev = z.shape[0], z.device
+        u8 = dict(dtype=torch.uint8, device=dev)
+        snd = FF_.Sounding(sounding.control.clone(), torch.zeros(B, 32, **u8), torch.zeros(B, 32, **u8), torch.ones(B, 32, **u8), B,
+                           True, True, True)
+        block = mask = mask_addr = rows = rows_addr = None
+        if kind.cons:
+            mask = torch.full((B, 32, 4), -1, dtype=torch.int32, device=dev)
+        force_base = torch.full((15, 32 * B), -1, dtype=torch.int32, device=dev)
+        run = FF_.SoundingRun(snd, B, dev, mask=bool(kind.cons), mask_base=mask, force=True, force_base=force_base)
+        if sampling is not None:
+            block = FF_.sounding_block(sampling, run.mask_eff) if kind.cons else FF_.clone_block(sampling)
+            ps = ps + [block]
+        if kind.cons:
+            mask_addr = torch.tensor([run.mask_eff.data_ptr()], dtype=torch.int64, device=dev)
+        if kind.rows:
+            rows = sampling.rows.table.clone()
+            rows_addr = torch.tensor([rows.data_ptr()], dtype=torch.int64, device=dev)
+            block.rows = FF_.RowSampling(rows, B)
+            block[8:9].copy_(rows_addr)
+        static_z = z.detach().clone()
+        force = {'pitch': run.force_eff, 'dur': torch.full((5, 480 * B), -1, dtype=torch.int32, device=dev), 'sounding': run}
+        ent = _DecodeGraph(None, static_z, None, block, mask, mask_addr, force, rows, rows_addr, run)
+        ent.refresh(z, sampling, keep, sounding)               # (warm-up and capture run on the first caller's tables)
+        cur = torch.cuda.current_stream()
+        s = self._graph_stream = self._graph_stream or torch.cuda.Stream(device=dev)      # (one stream for both: see _graph_decode)
+        s.wait_stream(cur)
+        with torch.cuda.stream(s):
+            FF_.DecoderStepFn.apply(static_z, None, None, coins, True, force, self._prec, *ps)
+        cur.wait_stream(s)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            outs = FF_.DecoderStepFn.apply(static_z, None, None, coins, True, force, self._prec, *ps)
+        for k in [k for k in self._graphs if k[4:] == key[4:]]:
+            del self._graphs[k]
+        self.graph_captures += 1
+        return ent._replace(graph=g, outs=outs)
 
     def _params_free(self):
         sd = dict(self.named_parameters())
@@ -435,14 +515,27 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         return notes, time
 
     def decoder(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None,
-                keep=None):
+                keep=None, sounding=None):
         """sampling: None (argmax decisions) or a block of functional_free.sampling_block() -- the decisions of the free-running decode
         are then seeded draws from softmax(logits / T), with top_k / min_p / top_p in the block over the truncated support of the pitch row,
         and with pitch_mask / ascending over the allowed classes only (temperature 0: the constrained argmax);
         inference only (ValueError otherwise, before any launch).
         keep: None or a functional_free.Keep (DisentangleVAE.keep) -- the decisions of its kept time steps are forced where they are taken,
         so they reach the following steps as if decided; everything else is decided as without it.  Its rows are the rows of z.  Inference
-        only, and not together with force_trace (ValueError before any launch)"""
+        only, and not together with force_trace (ValueError before any launch).
+        sounding: None or a functional_free.Sounding (DisentangleVAE.sounding) -- between two time steps the next step's mask row and
+        pitch force words are rewritten from what is sounding (INTEGRATION.md "Sounding state"); the decode runs on the EFFECTIVE arrays,
+        which last_sounding = (mask_eff or None, force_pitch_eff or None, held) and decode_logprob() then read.  Inference only, not
+        together with force_trace; no_restrike or a floor needs a constrained block (ValueError before any launch)"""
+        if sounding is not None:
+            if not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None:
+                raise ValueError('sounding is inference only: it cannot be combined with training or teacher forcing')
+            FF_.check_sounding(sounding, z.size(0), z.device)
+            if self.force_trace is not None:
+                raise ValueError('sounding cannot be combined with force_trace: both fill the force arrays')
+            if sounding.needs_constrained and not (torch.is_tensor(sampling) and FF_.block_kind(sampling).cons):
+                raise ValueError('sounding with no_restrike or min_sounding needs a constrained block (functional_free.sampling_block(..., '
+                                 'ascending=False) at least): only the constrained kernels honour its mask and its words')
         if sampling is not None and (not inference or teacher_forcing_ratio1 != 0 or teacher_forcing_ratio2 != 0 or coins is not None):
             raise ValueError('sampling is inference only: it cannot be combined with training or teacher forcing')
         if keep is not None:
@@ -467,11 +560,21 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
             coins = ([[False] * (self.max_simu_note - 2)] * self.num_step, [False] * (self.num_step - 1))
             smp = () if sampling is None else (FF_._check_block(sampling, z.device, B),)
             force = self.force_trace if keep is None else {'pitch': keep.pitch, 'dur': keep.dur}
-            if self.use_graph and not torch.is_grad_enabled() and self.force_trace is None:
-                pitch, dur, xhat, idx = self._graph_decode(z, coins, sampling, keep)
+            graphed = self.use_graph and not torch.is_grad_enabled() and self.force_trace is None
+            self.last_sounding = run = None
+            if sounding is not None and not graphed:
+                sampling, force, run = self._sounding_run(z, sampling, keep, sounding)
+                smp = () if sampling is None else (sampling,)
+            if graphed:
+                pitch, dur, xhat, idx = self._graph_decode(z, coins, sampling, keep, sounding)
+                if sounding is not None:
+                    sampling, force, run = self._graph_effective
             else:
                 pitch, dur, xhat, idx = FF_.DecoderStepFn.apply(z, None, None, coins, True, force, self._prec,
                                                                 *self._params_free(), *smp)
+            if run is not None:
+                force = {'pitch': force.get('pitch'), 'dur': force.get('dur')} if force else None
+                self.last_sounding = (run.mask_eff, run.force_eff, run.held)
             self.last_dur_idx, self.last_xhat = idx, xhat
             self._last_decode = LastDecode(pitch, dur, xhat, sampling, force)      # what decode_logprob() reads: references, nothing copied (an eager decode's logits live until the next decode)
             return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
@@ -511,6 +614,24 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         # reference shapes [B,32,15,130] / [B,32,15,5,2] as permuted views of the step-major buffers
         return pitch.permute(2, 1, 0, 3), dur.view(15, 32, B, 5, 2).permute(2, 1, 0, 3, 4)
 
+    def _sounding_run(self, z, sampling, keep, sounding):
+        """an eager decode with sounding rules -> (the effective block, the force dict of DecoderStepFn, the SoundingRun): the effective
+        arrays are allocated here -- a mask only where no_restrike is on, force arrays only where a count rule is on or a keep is given
+        (an all-free keep where the caller gave none) -- and the block is cloned with mask_eff's address"""
+        B, dev = z.size(0), z.device
+        want_mask = sounding.no_restrike
+        want_force = sounding.needs_force or keep is not None
+        mask_base = getattr(sampling, 'pitch_mask', None) if want_mask else None
+        run = FF_.SoundingRun(sounding, B, dev, mask=want_mask, mask_base=mask_base, force=want_force,
+                              force_base=keep.pitch if keep is not None else None)
+        if want_mask:
+            sampling = FF_.sounding_block(sampling, run.mask_eff)
+        force = {'sounding': run}
+        if want_force:
+            force.update(pitch=run.force_eff,
+                         dur=keep.dur if keep is not None else torch.full((5, 480 * B), -1, dtype=torch.int32, device=dev))
+        return sampling, force, run
+
     def decode_logprob(self):
         """Log-probabilities of the LAST inference decode (ptv_decode_logprob + ptv_decode_logprob_fold; INTEGRATION.md "Decode
         log-probabilities") -> DecodeLogprob(logp [B,2], logq [B,2], counts int32 [B,4], err int32 [B], step_logp [B,32,4],
@@ -541,9 +662,9 @@ class PtvaeDecoder(nn.Module, _PrecMixin):
         return DecodeLogprob(sums[:, 0:2], sums[:, 2:4], counts, err, step_logp, step_counts)
 
     def forward(self, z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=None, *, live=None, sampling=None,
-                keep=None):
+                keep=None, sounding=None):
         return self.decoder(z, inference, x, lengths, teacher_forcing_ratio1, teacher_forcing_ratio2, coins=coins, live=live, sampling=sampling,
-                            keep=keep)
+                            keep=keep, sounding=sounding)
 
     # ---- the reference's helper METHODS (ptvae.py:292-428), callable by reference-side code.  Forward-only entry points onto the
     # kernels the fused path runs (`decoder()` never calls them: it runs DecoderTFFn / DecoderStepFn); results carry no autograd graph.

@@ -30,9 +30,13 @@ decode and beside the constrained scalar kind with the same values ('constrained
 (b) the six-group table of the tests -- no rule, T = 0, top_k = 4, top_p = 0.85, min_p = 0.2, top_k = 8 + top_p = 0.9 + min_p = 0.05 by
 row % 6, so that every wave holds four rules and both selects diverge between its rows -- beside 'constrained top_k+top_p', the scalar
 decode of its most expensive member.
+The sounding rows (--sounding 1; sounding state, DisentangleVAE.sounding: one ptv_sounding_step launch between two note loops, 32 more
+launches on the decode's chain, and the note loops on the effective mask and force arrays) run no_restrike under plain sampling -- sent
+as the constrained kind with the vacuous constraint, as the model sends it -- beside the plain sampled decode, and no_restrike +
+max_sounding = 4 + min_sounding = 1 under mask + ascending + top_k + top_p, beside the same setting without sounding.
 
     python scripts/bench_sampling.py [--batch 2048] [--rounds 3] [--reps 5] [--temperature 1.0] [--top-k 8] [--min-p 0.9] [--top-p 0.9]
-                                     [--constrained 1] [--keep 1] [--logprob 1] [--rows 1] [--eager]
+                                     [--constrained 1] [--keep 1] [--logprob 1] [--rows 1] [--sounding 1] [--eager]
 
 --top-k 0, --min-p 0 and --top-p 0 switch the rule off; with top_k and min_p both off the 'truncated' decode is not timed, with top_p
 off the two nucleus rows are not; --constrained 0 leaves the constrained rows out.
@@ -62,6 +66,7 @@ def main():
     ap.add_argument('--keep', type=int, default=1, help='0 = no keep rows')
     ap.add_argument('--logprob', type=int, default=1, help='0 = no logprob / best-of rows')
     ap.add_argument('--rows', type=int, default=1, help='0 = no per-row sampling rows')
+    ap.add_argument('--sounding', type=int, default=1, help='0 = no sounding rows')
     ap.add_argument('--eager', action='store_true', help='no graph replay')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs the MI355X'
@@ -118,6 +123,13 @@ def main():
         rowwise['rows mixed'] = (('constrained top_k+top_p',), m.row_sampling(a.batch, col('t', a.temperature), top_k=col('top_k'),
                                                                            min_p=col('min_p'), top_p=col('top_p')))
         kinds += ['constrained plain', 'constrained top_k+top_p'] + list(rowwise)
+    sounds = {}                                              # kind -> (the kind it is compared with, its Sounding)
+    if a.sounding:
+        sounds['sounding no_restrike'] = ('sampled', m.sounding(no_restrike=True, batch=a.batch))
+        if a.constrained:
+            sounds['sounding all+mask+ascending+top_k+top_p'] = ('mask+ascending+top_k+top_p',
+                                                                 m.sounding(no_restrike=True, max_sounding=4, min_sounding=1, batch=a.batch))
+        kinds += list(sounds)
     blocks = {'argmax': [None] * (a.rounds + 1),
               'sampled': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d) for d in range(a.rounds + 1)],
               'truncated': [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, **trunc) for d in range(a.rounds + 1)]}
@@ -143,28 +155,33 @@ def main():
     if 'keep top' in keeps:                                  # a top keep needs the constrained kind with the ascending flag
         blocks['keep top'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=True) for d in range(a.rounds + 1)]
 
-    def run(block, keep=None):
-        with torch.no_grad():
-            m.decoder(z, True, None, None, 0., 0., sampling=block, keep=keep)
+    for k, (base, _) in sounds.items():
+        blocks[k] = blocks[base]
+    if 'sounding no_restrike' in sounds:                     # no_restrike needs the constrained kind: the vacuous constraint
+        blocks['sounding no_restrike'] = [FF_.sampling_block(dev, a.temperature, seed=7, draw=d, ascending=False) for d in range(a.rounds + 1)]
 
-    def timed(block, keep=None):
+    def run(block, keep=None, snd=None):
+        with torch.no_grad():
+            m.decoder(z, True, None, None, 0., 0., sampling=block, keep=keep, sounding=snd)
+
+    def timed(block, keep=None, snd=None):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.reps):
-            run(block, keep)
+            run(block, keep, snd)
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.reps
 
     for _ in range(2):                                       # warm-up: every graph captured, allocator settled
         for k in kinds:
-            run(blocks[k][-1], keeps[k][1] if k in keeps else None)
+            run(blocks[k][-1], keeps[k][1] if k in keeps else None, sounds[k][1] if k in sounds else None)
     torch.cuda.synchronize()
     captures = m.decoder.graph_captures
     ms = {k: [] for k in kinds}
     for r in range(a.rounds):                                # interleaved: drift of the box hits all alike
         for k in kinds:
-            ms[k].append(timed(blocks[k][r], keeps[k][1] if k in keeps else None))
+            ms[k].append(timed(blocks[k][r], keeps[k][1] if k in keeps else None, sounds[k][1] if k in sounds else None))
     assert m.decoder.graph_captures == captures              # a new draw is not a new capture
     rate = {k: [round(a.batch / (v * 1e-3), 1) for v in vs] for k, vs in ms.items()}
     best = {k: max(v) for k, v in rate.items()}
@@ -182,6 +199,10 @@ def main():
     for k, other in (('count limits', 'keep rhythm'), ('count limits+mask+ascending+top_k+top_p', 'keep rhythm+mask+ascending+top_k+top_p')):
         if k in keeps and other in keeps:                    # the count limits beside the keep they are made like, round by round
             out[k + '_over_' + other + '_by_round'] = [round(x / y, 4) for x, y in zip(rate[k], rate[other])]
+    for k, (base, _) in sounds.items():
+        out[k + '_over_' + base + '_best'] = round(best[k] / best[base], 4)
+        out[k + '_over_' + base + '_by_round'] = [round(x / y, 4) for x, y in zip(rate[k], rate[base])]
+        out[k + '_minus_' + base + '_ms_by_round'] = [round(x - y, 3) for x, y in zip(ms[k], ms[base])]
     for k, (bases, _) in rowwise.items():
         for base in bases:
             out[k + '_over_' + base + '_best'] = round(best[k] / best[base], 4)
